@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- BASELINE.json metric: sentences/sec (+ input MiB/s) of Tokenizer::tokenize on MI355X, synthetic IPADIC-shaped dictionary.
 
-  python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run)
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]        (N>1: launched by torch.distributed.run)
 
 A STEP is one pass of the hot path over one whole 100 000-sentence corpus in batches of 4096 (24 full batches and the 1 696-sentence tail),
 inputs resident in HBM, dense token streams left in HBM.
@@ -12,9 +12,12 @@ inputs resident in HBM, dense token streams left in HBM.
           job's rate and `scaling` is "strong" (the work of a step does not grow with N).
 
 Rank 0 prints ONE compact JSON line (<= 6 KB: compact_line) as the LAST line of stdout and writes everything it measured to bench_full.json (next to this
-script, and under gpurun_out/ when that directory exists).  At N = 1 the line carries the per-launch roofline of the dominant kernel (HIP events on the
-kernel's stream), the per-stage fractions (runtime ablation mode), the CPU baseline (the oracle restatement pinned to one core, best of five passes) and a
-few scalars of every extra leg (bench_extras.py: cfg 3, cfg 5, the dense-lattice dictionary, one context, host-buffer calls).
+script).  A plain run measures the headline only: set-up, the prewarm and W warmup steps, exactly K timed steps (no HIP events on the kernels' streams),
+the line.  --full adds everything else: the work counters and HIP events of the per-launch roofline of the dominant kernel, the kernel alone, the
+per-stage fractions (runtime ablation mode), the CPU baseline (the oracle restatement pinned to one core, best of five passes) and a few scalars of every
+extra leg (bench_extras.py: cfg 3, cfg 5, the dense-lattice dictionary, one context, host-buffer calls); at N > 1 the one-GPU leg (speedup_vs_1gpu) and
+the check of one gathered + reassembled step against one GPU.  --dump-outputs DIR (N = 1) writes what the last timed step computed
+(bench_engine.dump_outputs).
 
 The job itself (Workload / GpuEngine / run_job) lives in bench_engine.py and is re-exported here: tests/test_dist_cpu.py drives it over gloo.
 """
@@ -27,7 +30,7 @@ import time
 import numpy as np
 
 from bench_engine import (BATCH, HBM_PEAK_GBS, N_SENT, ROOT, GpuEngine, PackedWorkload, Workload, algorithmic_bytes, c_getenv,  # noqa: F401 (re-exported)
-                          chunk_steps_for, cpu_model, cpu_quota, expand_gathered, result_rate_guess, run_job)
+                          chunk_steps_for, cpu_model, cpu_quota, dump_outputs, expand_gathered, result_rate_guess, run_job, step_outputs)
 
 LINE_LIMIT = 6144  # bytes: the driver's record of round 5 lost a 24 KB line (BENCH_r05.json parsed: null)
 KERNEL = "k_tokenize_pool (fused lattice build + Viterbi + backtrace, LDS page pool)"
@@ -114,15 +117,12 @@ def fit_line(line, limit=LINE_LIMIT):
 
 
 def emit(full, real_stdout=None):
-    """bench_full.json (beside the script, and under gpurun_out/ where that exists), then the compact line as the LAST line of stdout."""
-    text = json.dumps(full)
-    for d in (ROOT, os.path.join(ROOT, "gpurun_out")):
-        if os.path.isdir(d):
-            try:
-                with open(os.path.join(d, "bench_full.json"), "w") as f:
-                    f.write(text + "\n")
-            except OSError as e:
-                print(f"bench_full.json not written to {d}: {e}", file=sys.stderr)
+    """bench_full.json beside the script, then the compact line as the LAST line of stdout."""
+    try:
+        with open(os.path.join(ROOT, "bench_full.json"), "w") as f:
+            f.write(json.dumps(full) + "\n")
+    except OSError as e:
+        print(f"bench_full.json not written to {ROOT}: {e}", file=sys.stderr)
     line = fit_line(compact_line(full))
     sys.stdout.flush()
     if real_stdout is not None:
@@ -130,7 +130,7 @@ def emit(full, real_stdout=None):
     print(line, flush=True)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -149,7 +149,19 @@ def main():
     ap.add_argument("--force-dist", action="store_true", help="take the multi-rank code path even with one rank (self-test)")
     ap.add_argument("--single-process", action="store_true", help="--gpus N in ONE process through kgpu_multi_* (no torch.distributed)")
     ap.add_argument("--devices", default="", help="--single-process: the device of every entry, e.g. 0,0 (default: entry g -> device g)")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="measure and check everything besides the headline too (roofline, stages, CPU baseline, other "
+                    "configs, host-buffer legs; N > 1: the one-GPU leg, the gathered-step check); the --no-* options trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="N = 1: write what the last timed step computed to DIR/<name>.npy (float64, <= 64 MB)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.gpus > 1 or args.force_dist or args.single_process):
+        ap.error("--dump-outputs is for the single-GPU run (--gpus 1)")
+    return args
+
+
+def main():
+    args = parse_args()
 
     # stdout carries the result line only: everything else that libraries print there (RCCL's banner ...) goes to stderr until the result is ready
     sys.stdout.flush()
@@ -177,7 +189,7 @@ def main():
     _lib.lib()  # before any HIP call of this process: the library asks for the hardware queues it needs (kgpu_api.cpp: kgpu_preinit)
     sd = synth.build_dict()
     extras_dir = extras_proc = None
-    if world == 1 and not args.no_extras:  # before the HIP runtime is initialised in this process: fork is safe
+    if world == 1 and args.full and not args.no_extras:  # before the HIP runtime is initialised in this process: fork is safe
         import multiprocessing as mp
         import tempfile
 
@@ -215,24 +227,25 @@ def main():
     eng = GpuEngine(tok, dev, wl, queue=args.queue, streams=args.streams if multi else 0, ring=3 * cs if multi else 1, compact=compact)
     Q = eng.Q
 
-    # ---- untimed: device-side work counters of every distinct batch of corpus 0 (algorithmic bytes)
+    # ---- untimed (--full): device-side work counters of every distinct batch of corpus 0 (algorithmic bytes)
     work = {k: 0 for k in ("sentences", "B", "C", "T", "N", "E", "K")}
-    for c in eng.ctxs:
-        c.set_profiling(PROFILE_WORK)
-    run_job(eng, 1)
-    for c in eng.ctxs:
-        for k, v in c.work().items():
-            work[k] += v
-        c.set_profiling(PROFILE_OFF)
+    if args.full:
+        for c in eng.ctxs:
+            c.set_profiling(PROFILE_WORK)
+        run_job(eng, 1)
+        for c in eng.ctxs:
+            for k, v in c.work().items():
+                work[k] += v
+            c.set_profiling(PROFILE_OFF)
     sample_tokens = None
-    if rank == 0 and world == 1:  # keep batch 0's GPU result for the bit-exact check in the cpu_baseline leg
+    if args.full and rank == 0 and world == 1:  # keep batch 0's GPU result for the bit-exact check in the cpu_baseline leg
         eng.enqueue(0, 0)
         k = eng._retire((0, 0))
         t, o, _ = eng.out[0][0]
         sample_tokens = (t[:k].cpu().numpy().copy(), o.cpu().numpy().copy())
         eng.drain()
 
-    # ---- multi-rank: the gather, and (untimed) the check of one gathered + reassembled step against one GPU
+    # ---- multi-rank: the gather, and (untimed, --full) the check of one gathered + reassembled step against one GPU
     size_pg = dist.new_group(backend="gloo") if multi else None  # CPU-side size exchange of the gather
     gathered = {"tokens": 0, "sentences": 0, "chunks": 0}
 
@@ -251,8 +264,9 @@ def main():
     gather_check = None
     if multi:
         got = {}
-        job(1, lambda c0, r: got.update(r=r))
-        if rank == 0:
+        if args.full:
+            job(1, lambda c0, r: got.update(r=r))
+        if "r" in got and rank == 0:
             tok_all, cnt_all, sizes_all = got["r"][:3]
             tok_np, cnt_np = tok_all.cpu().numpy(), cnt_all.cpu().numpy()
             if compact:  # the check wants the 24-byte records: expand the gathered chunk on the host (one step per rank here)
@@ -275,7 +289,7 @@ def main():
 
     # ---- N > 1: the same steps on ONE GPU (rank 0 alone, the others wait): the denominator of speedup_vs_1gpu
     one_gpu = None
-    if world > 1 and not args.no_one_gpu_leg:
+    if world > 1 and args.full and not args.no_one_gpu_leg:
         if rank == 0:
             eng1 = GpuEngine(tok, dev, Workload(corpora, 0, 1), queue=args.queue, streams=0, ring=1)
             run_job(eng1, max(2, min(W, 5)))
@@ -304,10 +318,10 @@ def main():
                 break
     if W > 0:
         job(W)
-    # HIP events around every 4th launch chain of every context, on the stream the kernels run on (what profiles/r06_kernel_stats.csv is compared with).  They are
+    # --full: HIP events around every 4th launch chain of every context, on the stream the kernels run on (what profiles/r06_kernel_stats.csv is compared with).  They are
     # not free -- a record is a barrier packet on its stream: five interleaved runs 124.5-136.6 M sentences/s against 136.9-138.5 with none and 136.7-137.8 with the
     # events on two of the eight contexts (BENCH_EVENT_CTXS=0,5: the per-launch fraction FALLS there while the rate rises; profiles/experiments/r06_tile_sweep.txt).
-    ev = os.environ.get("BENCH_EVENT_CTXS", "all")   # (measurement: "all", a list like "0,5", or "" for none)
+    ev = os.environ.get("BENCH_EVENT_CTXS", "all") if args.full else ""   # (measurement: "all", a list like "0,5", or "" for none)
     timed_ctxs = set(range(len(eng.ctxs))) if ev == "all" else {int(x) % len(eng.ctxs) for x in ev.split(",") if x.strip()}
     for i, c in enumerate(eng.ctxs):
         if i in timed_ctxs and not os.environ.get("BENCH_NO_EVENTS"):
@@ -346,6 +360,9 @@ def main():
             prof[k] = [x + y for x, y in zip(prof[k], p[k])] if isinstance(prof[k], list) else prof[k] + p[k]
         c.set_profiling(PROFILE_OFF)
 
+    if args.dump_outputs:  # what the last timed step computed, before any other leg reuses the engine's buffers
+        dump_outputs(args.dump_outputs, *step_outputs(eng, K - 1))
+
     if rank != 0:
         dist.destroy_process_group()
         return
@@ -353,22 +370,6 @@ def main():
     sentences = sum(len(corpora[s % len(corpora)]) for s in range(K))  # whole job: all ranks' shards
     per_corpus_bytes = [sum(len(x.encode("utf-8")) for x in c) for c in corpora]
     bytes_in = sum(per_corpus_bytes[s % len(corpora)] for s in range(K))
-    a, b, c_ = algorithmic_bytes(work)  # of this rank's shard of corpus 0 (world 1: the whole corpus)
-    n_work = max(work["sentences"], 1)
-    per_sentence_bytes = (a + b + c_) / n_work
-    per_launch_bytes = per_sentence_bytes * BATCH
-    avg_kernel_s = prof["first_ms"] / max(prof["launches"], 1) / 1e3    # the dominant kernel's own launches (what rocprofv3 reports for it)
-    # every 4th launch chain is timed, tail batches included: scale the bytes to the average timed launch
-    avg_launch_sentences = wl.sentences(0) / wl.nb(0)
-    achieved = per_sentence_bytes * avg_launch_sentences / avg_kernel_s / 1e9 if avg_kernel_s > 0 else 0.0
-    job_rate_bytes = per_sentence_bytes * sentences / elapsed / 1e9
-    traffic = None
-    tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")  # written from a separate rocprofv3 --pmc pass (tools/make_traffic_json.py)
-    if os.path.exists(tpath):
-        try:
-            traffic = json.load(open(tpath))
-        except Exception:
-            traffic = None
     plan = eng.ctxs[0].plan()
     full = {
         "metric": "sentences/sec", "value": sentences / elapsed, "unit": "sentences/s", "n_gpus": world, "steps": K, "warmup": W,
@@ -378,23 +379,42 @@ def main():
                    "residency": "inputs resident in HBM, dense tokens left in HBM",
                    "sharding": f"sentence i -> GPU i mod N, dictionary replicated, one gatherv to rank 0 per {cs} step(s)" if multi else "single GPU"},
         "input_MiB_per_s": bytes_in / elapsed / 2**20,
-        "work_per_sentence": {k: work[k] / n_work for k in ("B", "C", "T", "N", "E", "K")},
-        "routing": {k: prof[k] for k in ("batches", "sentences", "deferred", "redone", "long_launches", "arena_regrows")},
-        "launch_plan": plan,
-        "roofline": {
-            "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-            "traffic": traffic.get("hbm_bytes_per_launch") if traffic else None,
-            "traffic_stale": (traffic.get("kernel_src_sha16") != kernel_source_hash()) if traffic else None,  # counters measured on other kernel sources than these
-            "traffic_source": traffic.get("source") if traffic else None,
-            "kernel": KERNEL, "algorithmic_bytes_per_sentence": per_sentence_bytes, "algorithmic_bytes_per_launch": per_launch_bytes,
-            "stage_bytes_per_launch": {"A_lattice": a / n_work * BATCH, "B_viterbi": b / n_work * BATCH, "C_emit": c_ / n_work * BATCH},
-            "avg_kernel_ms": avg_kernel_s * 1e3, "launches_timed": prof["launches"],
-            "avg_launch_chain_ms": prof["tokenize_ms"] / max(prof["launches"], 1), "aux_kernels_avg_ms": prof["aux_ms"] / max(prof["launches"], 1),
-            "launches_in_flight": Q, "achieved_at_job_rate": job_rate_bytes, "frac_at_job_rate": job_rate_bytes / HBM_PEAK_GBS,
-        },
         "sentences_total": sentences,
     }
-    roof = full["roofline"]
+    if args.full:
+        a, b, c_ = algorithmic_bytes(work)  # of this rank's shard of corpus 0 (world 1: the whole corpus)
+        n_work = max(work["sentences"], 1)
+        per_sentence_bytes = (a + b + c_) / n_work
+        per_launch_bytes = per_sentence_bytes * BATCH
+        avg_kernel_s = prof["first_ms"] / max(prof["launches"], 1) / 1e3    # the dominant kernel's own launches (what rocprofv3 reports for it)
+        # every 4th launch chain is timed, tail batches included: scale the bytes to the average timed launch
+        avg_launch_sentences = wl.sentences(0) / wl.nb(0)
+        achieved = per_sentence_bytes * avg_launch_sentences / avg_kernel_s / 1e9 if avg_kernel_s > 0 else 0.0
+        job_rate_bytes = per_sentence_bytes * sentences / elapsed / 1e9
+        traffic = None
+        tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")  # written from a separate rocprofv3 --pmc pass (tools/make_traffic_json.py)
+        if os.path.exists(tpath):
+            try:
+                traffic = json.load(open(tpath))
+            except Exception:
+                traffic = None
+        full.update({
+            "work_per_sentence": {k: work[k] / n_work for k in ("B", "C", "T", "N", "E", "K")},
+            "routing": {k: prof[k] for k in ("batches", "sentences", "deferred", "redone", "long_launches", "arena_regrows")},
+            "launch_plan": plan,
+            "roofline": {
+                "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                "traffic": traffic.get("hbm_bytes_per_launch") if traffic else None,
+                "traffic_stale": (traffic.get("kernel_src_sha16") != kernel_source_hash()) if traffic else None,  # counters measured on other kernel sources than these
+                "traffic_source": traffic.get("source") if traffic else None,
+                "kernel": KERNEL, "algorithmic_bytes_per_sentence": per_sentence_bytes, "algorithmic_bytes_per_launch": per_launch_bytes,
+                "stage_bytes_per_launch": {"A_lattice": a / n_work * BATCH, "B_viterbi": b / n_work * BATCH, "C_emit": c_ / n_work * BATCH},
+                "avg_kernel_ms": avg_kernel_s * 1e3, "launches_timed": prof["launches"],
+                "avg_launch_chain_ms": prof["tokenize_ms"] / max(prof["launches"], 1), "aux_kernels_avg_ms": prof["aux_ms"] / max(prof["launches"], 1),
+                "launches_in_flight": Q, "achieved_at_job_rate": job_rate_bytes, "frac_at_job_rate": job_rate_bytes / HBM_PEAK_GBS,
+            },
+        })
+        roof = full["roofline"]
     if multi:
         full["gather"] = {"chunks": gathered["chunks"], "tokens": gathered["tokens"], "sentences": gathered["sentences"],
                           "complete": gathered["sentences"] == sentences, "reassembled_step_equals_one_gpu": gather_check,
@@ -406,41 +426,15 @@ def main():
             full["one_gpu_leg"] = one_gpu
             full["speedup_vs_1gpu"] = full["value"] / one_gpu["value"]
         assert gathered["sentences"] == sentences, (gathered, sentences)
-        assert gather_check, "gathered + reassembled token stream differs from the single-GPU stream"
+        assert gather_check or not args.full, "gathered + reassembled token stream differs from the single-GPU stream"
 
-    if world == 1:
-        # ---- the dominant kernel alone on the chip: one full batch at a time, HIP events around every launch
-        full_batches = [i for i in range(wl.nb(0)) if len(wl.packed[0][i][1]) - 1 == BATCH]
-        c0 = eng.ctxs[0]
-        c0.set_profiling(PROFILE_EVENTS)
-        for _ in range(2):
-            c0.profile(reset=True)
-            for bi in full_batches:
-                d_utf8, d_off, n, total = eng.inputs[0][bi]
-                t, o, st = eng.out[0][bi]
-                c0.tokenize(d_utf8.data_ptr(), d_off.data_ptr(), n, total, t.data_ptr(), eng.cap, o.data_ptr(), st.data_ptr())
-                c0.sync()
-        p = c0.profile(reset=True)
-        c0.set_profiling(PROFILE_OFF)
-        alone_ms = p["first_ms"] / max(p["launches"], 1)
-        roof["kernel_alone_ms"] = alone_ms
-        roof["frac_alone"] = per_launch_bytes / (alone_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if alone_ms > 0 else None
-        # ---- the box's own streaming-read bandwidth (a 4 GiB int64 reduction, best of 6): second denominator of the roofline
-        try:
-            x = torch.empty(1 << 29, dtype=torch.int64, device=dev).fill_(1)
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            best = 0.0
-            for _ in range(6):
-                ev0.record(); x.sum(); ev1.record(); ev1.synchronize()
-                best = max(best, x.numel() * 8 / (ev0.elapsed_time(ev1) * 1e-3) / 1e9)
-            del x
-            roof["peak_measured_read"], roof["frac_of_measured_read"] = best, achieved / best
-        except Exception as e:  # never let the auxiliary measurement break the bench line
-            print(f"streaming-read measurement skipped: {e}", file=sys.stderr)
-
-    if world == 1 and not args.no_stages:
+    legs = world == 1 and args.full  # everything below measures something besides the headline
+    if legs:
         import bench_extras
 
+        bench_extras.kernel_alone_leg(eng, wl, roof, per_launch_bytes, achieved, dev, torch)
+
+    if legs and not args.no_stages:
         roof["stages"] = bench_extras.stage_split(eng, tok, dev, corpora, args.queue, torch, (a, b, c_))
         for k, name in (("A", "A_lattice"), ("B", "B_viterbi"), ("C", "C_emit")):
             roof[f"stage_{k}_ms"], roof[f"stage_{k}_frac"] = roof["stages"][name]["ms_per_step"], roof["stages"][name]["frac"]
@@ -453,9 +447,7 @@ def main():
         except Exception as e:
             print(f"instruction roofline skipped: {e}", file=sys.stderr)
 
-    if world == 1 and not args.no_extras:
-        import bench_extras
-
+    if legs and not args.no_extras:
         for name, leg in (("pcie_inclusive", lambda: bench_extras.host_paths(tok, wl, eng.cap, corpora)), ("multi_merge", bench_extras.multi_merge_leg)):
             try:
                 full[name] = leg()
@@ -472,14 +464,12 @@ def main():
         open(os.path.join(extras_dir, "go"), "w").close()
 
     # ---- CPU baseline (rank 0, N == 1 only)
-    if world == 1 and not args.no_cpu:
-        import bench_extras
-
+    if legs and not args.no_cpu:
         full["cpu_baseline"] = bench_extras.cpu_baseline_leg(sd, corpora, sample_tokens, args.cpu_passes)
         full["speedup_vs_cpu_1thread"] = full["value"] / full["cpu_baseline"]["value"]
 
     # ---- the other single-GPU configs (SURVEY 8d cfg 3, cfg 5), the dense dictionary, one context
-    if world == 1 and not args.no_extras:
+    if legs and not args.no_extras:
         import shutil
 
         eng.close()

@@ -301,6 +301,42 @@ def expand_gathered(tok8_all, cnt2_all, sizes, steps_sentences):
     return (np.concatenate(toks) if toks else np.zeros((0, 6), np.int32)), (np.concatenate(cnts) if cnts else np.zeros(0, np.int64))
 
 
+DUMP_LIMIT = 64 << 20    # bytes: --dump-outputs writes at most this much
+DUMP_SAMPLE = 16384      # sentences whose token records --dump-outputs writes (a fixed, seeded sample of the step)
+
+
+def step_outputs(engine, step):
+    """What a caller of the device path holds after `step` (single-rank engine, 24-byte records), copied to the host in sentence order:
+    (token records [T, 6] int32: id, class, position, start, end, byte length; per-sentence token counts int64; per-sentence status uint8)."""
+    toks, counts, status = [], [], []
+    for b in range(engine.nb(step)):
+        t, o, st = engine.out[step % engine.ring][b]
+        n = engine.inputs[step % len(engine.inputs)][b][2]
+        off = o[: n + 1].cpu().numpy()
+        toks.append(t[int(off[0]) : int(off[-1])].cpu().numpy())
+        counts.append(np.diff(off))
+        status.append(st[:n].cpu().numpy())
+    return np.concatenate(toks).reshape(-1, 6), np.concatenate(counts).astype(np.int64), np.concatenate(status)
+
+
+def dump_outputs(outdir, tokens, counts, status, limit=DUMP_LIMIT, sample=DUMP_SAMPLE, seed=0):
+    """--dump-outputs: step_outputs() as float64 .npy files (every value is an integer below 2^53, so they are exact): token_counts and status of
+    every sentence, and the token records of a fixed sample of sentences (seeded, independent of the outputs; sample_sentences holds their
+    indices, sample_tokens their records in that order).  The sample is cut short if the files would exceed `limit` bytes.  -> {name: shape}"""
+    n = len(counts)
+    starts = np.concatenate([[0], np.cumsum(counts)])
+    sel = np.sort(np.random.default_rng(seed).choice(n, size=min(n, sample), replace=False))
+    room = (limit - 16 * n - 8 * len(sel) - 4096) // (6 * 8)  # what is left for sample_tokens rows (4096: the four .npy headers)
+    keep = int(np.searchsorted(np.cumsum(counts[sel]), room, side="right"))
+    sel = sel[:keep]
+    rows = np.concatenate([np.arange(starts[i], starts[i + 1]) for i in sel]) if len(sel) else np.zeros(0, np.int64)
+    arrays = {"token_counts": counts, "status": status, "sample_sentences": sel, "sample_tokens": tokens[rows].reshape(-1, 6)}
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), np.asarray(a, dtype=np.float64))
+    return {name: a.shape for name, a in arrays.items()}
+
+
 def chunk_steps_for(nb_per_step):
     """Steps per gather chunk: about a dozen batches, so that the host side of a gather (size exchange, one
     grouped send/recv call) stays a small part of the chunk whatever the rank count."""

@@ -276,6 +276,39 @@ def run_single_process(args):
 
 # ------------------------------------------------------------------ legs of the N = 1 run (each returns a dict for bench_full.json)
 
+def kernel_alone_leg(eng, wl, roof, per_launch_bytes, achieved, dev, torch):
+    """Fills roof (the report's roofline) with the dominant kernel alone on the chip (one full batch at a time, HIP events around every launch) and
+    the box's own streaming-read bandwidth (a 4 GiB int64 reduction, best of 6): the second denominator of the roofline."""
+    from kanpyo_amd.device import PROFILE_EVENTS, PROFILE_OFF
+
+    full_batches = [i for i in range(wl.nb(0)) if len(wl.packed[0][i][1]) - 1 == BATCH]
+    c0 = eng.ctxs[0]
+    c0.set_profiling(PROFILE_EVENTS)
+    for _ in range(2):
+        c0.profile(reset=True)
+        for bi in full_batches:
+            d_utf8, d_off, n, total = eng.inputs[0][bi]
+            t, o, st = eng.out[0][bi]
+            c0.tokenize(d_utf8.data_ptr(), d_off.data_ptr(), n, total, t.data_ptr(), eng.cap, o.data_ptr(), st.data_ptr())
+            c0.sync()
+    p = c0.profile(reset=True)
+    c0.set_profiling(PROFILE_OFF)
+    alone_ms = p["first_ms"] / max(p["launches"], 1)
+    roof["kernel_alone_ms"] = alone_ms
+    roof["frac_alone"] = per_launch_bytes / (alone_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if alone_ms > 0 else None
+    try:
+        x = torch.empty(1 << 29, dtype=torch.int64, device=dev).fill_(1)
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        best = 0.0
+        for _ in range(6):
+            ev0.record(); x.sum(); ev1.record(); ev1.synchronize()
+            best = max(best, x.numel() * 8 / (ev0.elapsed_time(ev1) * 1e-3) / 1e9)
+        del x
+        roof["peak_measured_read"], roof["frac_of_measured_read"] = best, achieved / best
+    except Exception as e:  # never let the auxiliary measurement break the bench line
+        print(f"streaming-read measurement skipped: {e}", file=sys.stderr)
+
+
 def measure_stages(eng, torch, stage_bytes, steps=3):
     """Per-stage roofline: the same pipeline with every sentence stopped after a stage (kgpu_ctx_set_ablation, measurement-only mode of the runtime);
     a stage's time is the difference of consecutive stop levels at full occupancy.  Five interleaved repetitions of `steps` steps per level, the FASTEST

@@ -67,6 +67,18 @@ def _zipf_weights(n: int, s: float, shift: float = 2.0) -> np.ndarray:
     return w / w.sum()
 
 
+def _cdf(p: np.ndarray) -> np.ndarray:
+    c = p.cumsum()
+    c /= c[-1]
+    return c
+
+
+def _draw(rng, pool: np.ndarray, cdf: np.ndarray, size) -> np.ndarray:
+    """rng.choice(pool, size=size, p=p) with cdf = _cdf(p) computed once: the same draws from the same random stream (Generator.choice
+    with p is cdf.searchsorted(random(size), side="right")), without re-validating and re-summing p on every call."""
+    return pool[cdf.searchsorted(rng.random(size), side="right")]
+
+
 @dataclass
 class SynthDict:
     dict: Dict
@@ -96,7 +108,7 @@ def _make_words(rng, pool, weights, count, len_lo, len_hi, len_p, seen, out):
 
 def build_dict(n_records: int = 392_000, seed: int = SEED_DICT, n_context: int = N_CONTEXT, dense: bool = False) -> SynthDict:
     """The synthetic IPADIC-shaped dictionary (deterministic in its arguments).  KANPYO_SYNTH_CACHE=<dir>: the built object is kept there as a pickle
-    and loaded by later processes (the measurement tools set it: 20 s of building per process otherwise); unset = always built."""
+    and loaded by later processes (the measurement tools set it: ~5 s of building per process otherwise); unset = always built."""
     cache = os.environ.get("KANPYO_SYNTH_CACHE")
     if not cache:
         return _build_dict(n_records, seed, n_context, dense)
@@ -151,12 +163,13 @@ def _build_dict(n_records: int, seed: int, n_context: int, dense: bool) -> Synth
     for pool, w, frac, lo, hi, p in plan:
         _make_words(rng, pool, w, int(tgt_unique * frac), lo, hi, p, seen, words)
     # kanji stem + hiragana ending (verbs / adjectives)
+    c_hira, c_kata, c_kanji = _cdf(w_hira), _cdf(w_kata), _cdf(w_kanji)
     n_mixed = int(tgt_unique * 0.10)
     made = 0
     while made < n_mixed:
         k = rng.integers(1, 3)
         h = rng.integers(1, 4)
-        w = "".join(map(chr, rng.choice(kanji, size=k, p=w_kanji))) + "".join(map(chr, rng.choice(hira, size=h, p=w_hira)))
+        w = "".join(map(chr, _draw(rng, kanji, c_kanji, k))) + "".join(map(chr, _draw(rng, hira, c_hira, h)))
         if w not in seen:
             seen.add(w); words.append(w); made += 1
     # forced nested prefixes: the rest extend an earlier surface by 1-3 chars
@@ -165,8 +178,8 @@ def _build_dict(n_records: int, seed: int, n_context: int, dense: bool) -> Synth
         if len(base) > 10:
             continue
         last = ord(base[-1])
-        pool, w = (hira, w_hira) if 0x3041 <= last <= 0x3093 else (kata, w_kata) if 0x30A1 <= last <= 0x30F6 else (kanji, w_kanji)
-        ext = base + "".join(map(chr, rng.choice(pool, size=int(rng.integers(1, 4)), p=w)))
+        pool, c = (hira, c_hira) if 0x3041 <= last <= 0x3093 else (kata, c_kata) if 0x30A1 <= last <= 0x30F6 else (kanji, c_kanji)
+        ext = base + "".join(map(chr, _draw(rng, pool, c, int(rng.integers(1, 4)))))
         if ext not in seen:
             seen.add(ext); words.append(ext)
 

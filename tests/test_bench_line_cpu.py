@@ -4,6 +4,9 @@ import json
 import os
 import sys
 
+import numpy as np
+import pytest
+
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import bench  # noqa: E402
@@ -92,3 +95,80 @@ def test_bench_py_is_short():
     """The review's bound: bench.py = the headline and the line (<= 500 lines); the job in bench_engine.py, the other legs in bench_extras.py."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     assert sum(1 for _ in open(os.path.join(root, "bench.py"))) <= 500
+
+
+def test_plain_run_and_its_options():
+    """A plain run is the headline alone; --full brings the other legs back, --dump-outputs is for the single-GPU run, --steps is the timed steps."""
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.gpus, a.steps, a.warmup, a.full, a.dump_outputs) == (1, 7, 2, False, None)
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+    for bad in (["--steps", "0"], ["--gpus", "2", "--dump-outputs", "out"], ["--force-dist", "--dump-outputs", "out"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+
+
+class _HostEngine:
+    """bench_engine.GpuEngine's output buffers as the device leaves them, in host tensors: token capacity beyond the count, offsets and status of
+    the full batch size behind a ragged last batch (stale values there)."""
+
+    def __init__(self, counts, batch):
+        import torch
+
+        self.ring, self.inputs, self.out = 1, [[]], [[]]
+        for lo in range(0, len(counts), batch):
+            c = counts[lo : lo + batch]
+            off = np.full(batch + 1, 99, np.int64)
+            off[0], off[1 : len(c) + 1] = 0, np.cumsum(c)
+            t = np.full((off[len(c)] + 5, 6), -1, np.int32)
+            t[: off[len(c)], 0] = np.repeat(np.arange(lo, lo + len(c)), c)  # the sentence a record belongs to
+            t[: off[len(c)], 1] = np.arange(off[len(c)])
+            st = np.zeros(batch, np.uint8)
+            st[len(c) :] = 7
+            self.inputs[0].append((None, None, len(c), 0))
+            self.out[0].append((torch.from_numpy(t), torch.from_numpy(off), torch.from_numpy(st)))
+
+    def nb(self, step):
+        return len(self.inputs[0])
+
+
+def test_step_outputs_concatenates_the_batches_of_a_step():
+    from bench_engine import step_outputs
+
+    counts = np.random.default_rng(1).integers(1, 9, size=1000)
+    tok, cnt, st = step_outputs(_HostEngine(counts, 96), 5)
+    assert np.array_equal(cnt, counts) and len(st) == 1000 and not st.any()
+    assert np.array_equal(tok[:, 0], np.repeat(np.arange(1000), counts)) and tok.shape == (counts.sum(), 6)
+
+
+def test_dump_outputs_writes_a_fixed_sample_within_the_limit(tmp_path):
+    """cfg 2's size: 100 000 sentences of ~32 records are 73 MB as int32 -- more than the dump may hold: all counts and status, the records of a
+    seeded sample of sentences (the same whatever the outputs), float64 files of at most 64 MB in all; a tighter limit cuts the sample short."""
+    from bench_engine import dump_outputs
+
+    rng = np.random.default_rng(2)
+    n = 100_000
+    counts = rng.integers(1, 64, size=n)
+    tokens = np.zeros((int(counts.sum()), 6), np.int32)
+    tokens[:, 0] = np.repeat(np.arange(n), counts)
+    tokens[:, 1] = rng.integers(0, 392_000, size=len(tokens))
+    status = np.zeros(n, np.uint8)
+    shapes = dump_outputs(str(tmp_path / "a"), tokens, counts, status)
+    files = {p.stem: np.load(p) for p in (tmp_path / "a").iterdir()}
+    assert set(files) == {"token_counts", "status", "sample_sentences", "sample_tokens"} and {k: v.shape for k, v in files.items()} == shapes
+    assert all(v.dtype == np.float64 for v in files.values())
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= 64 << 20
+    sel = files["sample_sentences"].astype(np.int64)
+    assert len(sel) == 16384 and np.all(np.diff(sel) > 0)
+    assert np.array_equal(files["token_counts"], counts) and np.array_equal(files["sample_tokens"][:, 0], np.repeat(sel, counts[sel]))
+    starts = np.concatenate([[0], np.cumsum(counts)])
+    assert np.array_equal(files["sample_tokens"], tokens[np.concatenate([np.arange(starts[i], starts[i + 1]) for i in sel])])
+    counts2 = counts.copy()
+    counts2[0] += 1  # other outputs, the same sample
+    tokens2 = np.concatenate([tokens[:1], tokens])
+    dump_outputs(str(tmp_path / "b"), tokens2, counts2, status)
+    assert np.array_equal(np.load(tmp_path / "b" / "sample_sentences.npy"), files["sample_sentences"])
+    dump_outputs(str(tmp_path / "c"), tokens, counts, status, limit=4 << 20)
+    assert sum(p.stat().st_size for p in (tmp_path / "c").iterdir()) <= 4 << 20
+    cut = np.load(tmp_path / "c" / "sample_sentences.npy")
+    assert 0 < len(cut) < len(sel) and np.array_equal(cut, files["sample_sentences"][: len(cut)])

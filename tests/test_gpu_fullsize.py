@@ -143,3 +143,40 @@ def test_cfg4_workload_one_rank_over_rccl(full, compact):
             assert at_t == len(tok_all) and at_c == len(cnt_all)
     finally:
         dist.destroy_process_group()
+
+
+def test_bench_plain_run_dumps_its_last_step(full, tmp_path):
+    """bench.py --gpus 1 --steps 2 --warmup 1 --dump-outputs DIR: the plain run's line carries the headline alone (no roofline, CPU baseline or other
+    configs) over exactly the steps asked for, and the files are the last timed step's result -- token counts and status of all 100 000 cfg 2
+    sentences and the records of the seeded sample -- equal to the oracle's on the same corpus."""
+    import json
+    import subprocess
+    import sys
+
+    from conftest import ROOT
+    from kanpyo_amd import synth
+    from kanpyo_amd.tokenizer import pack_sentences
+
+    sd, _, orc = full
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--prewarm-seconds", "0.1",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().split("\n")[-1])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["steps"] == 2 and line["sentences_total"] == 200_000 and line["ms_per_step"] > 0 and line["value"] > 1e6
+    assert not line.get("roofline") and "cpu_baseline" not in line and "extra_summary" not in line
+    assert sorted(p.name for p in out.iterdir()) == ["sample_sentences.npy", "sample_tokens.npy", "status.npy", "token_counts.npy"]
+    assert sum(p.stat().st_size for p in out.iterdir()) <= 64 << 20
+    got = {p.stem: np.load(p) for p in out.iterdir()}
+    assert all(a.dtype == np.float64 for a in got.values())
+
+    utf8, offs = pack_sentences(synth.make_corpus(sd, 100_000, seed=1, kind="cfg2"))
+    exp = orc.tokenize_batch(utf8, offs, 8)
+    eoff = exp.offsets.astype(np.int64)
+    assert np.array_equal(got["token_counts"], np.diff(eoff)) and not got["status"].any()
+    sel = got["sample_sentences"].astype(np.int64)
+    assert len(sel) == 16384 and len(np.unique(sel)) == len(sel)
+    rows = np.concatenate([np.arange(eoff[i], eoff[i + 1]) for i in sel])
+    assert np.array_equal(got["sample_tokens"], exp.tokens.view(np.int32).reshape(-1, 6)[rows].astype(np.float64))

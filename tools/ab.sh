@@ -6,7 +6,7 @@
 # A VARIANT is "label" or "label:ENV=val,ENV2=val,..." (a ';' inside a value stands for a comma: KGPU_POOL=10:1:64;40:4:32) -- environment settings for one arm (KGPU_LIB=<other build of the library>, KGPU_POOL=40:4:48,
 # KGPU_WINDOW=12, KGPU_STREAMS=..., GPU_MAX_HW_QUEUES=..., BENCH_Q=...).  The arms run interleaved, REPS times each (default 2), on the same box.
 # COMMAND (default: the bench.py headline) is one of
-#   bench                 python bench.py --no-cpu --no-extras --no-stages  -> M sentences/s (value), the pool kernel's launch duration in flight / alone
+#   bench                 python bench.py --full --no-cpu --no-extras --no-stages  -> M sentences/s (value), the pool kernel's launch duration in flight / alone
 #   dense[:n[:batch]]     python tools/bench_cfg.py dense n batch           -> cfg 2-shaped text over the dense-lattice dictionary
 #   cfg3[:n[:batch]]      python tools/bench_cfg.py cfg3 n batch            -> the tool's result line       (defaults 400000, 65536)
 #   cfg5[:n[:batch]]      python tools/bench_cfg.py cfg5 n batch                                            (defaults 1000, 4096)
@@ -22,7 +22,7 @@ shift $((OPTIND - 1))
 cd "$(dirname "$0")/.."
 IFS=: read -r kind a1 a2 <<< "$CMD"
 case $kind in
-  bench)   run() { timeout 300 python bench.py --steps 40 --warmup 10 --no-cpu --no-extras --no-stages 2>/dev/null | tail -n 1 | python -c "import json,sys; d=json.load(sys.stdin); r=d['roofline']; print(round(d['value']/1e6,2), 'M sentences/s, kernel ms in flight / alone', r.get('avg_kernel_ms'), r.get('kernel_alone_ms'))"; } ;;
+  bench)   run() { timeout 300 python bench.py --steps 40 --warmup 10 --full --no-cpu --no-extras --no-stages 2>/dev/null | tail -n 1 | python -c "import json,sys; d=json.load(sys.stdin); r=d['roofline']; print(round(d['value']/1e6,2), 'M sentences/s, kernel ms in flight / alone', r.get('avg_kernel_ms'), r.get('kernel_alone_ms'))"; } ;;
   dense)   run() { timeout 300 python tools/bench_cfg.py dense 100000 4096 2>&1 | grep -v amdgpu.ids | tail -1; } ;;
   cfg3)    run() { timeout 600 python tools/bench_cfg.py cfg3 ${a1:-400000} ${a2:-65536} 2>&1 | grep -v amdgpu.ids | tail -1; } ;;
   cfg5)    run() { timeout 600 python tools/bench_cfg.py cfg5 ${a1:-1000} ${a2:-4096} 2>&1 | grep -v amdgpu.ids | tail -1; } ;;

@@ -10,15 +10,15 @@ mkdir -p "$OUT"
 export KANPYO_SYNTH_CACHE=/tmp/kanpyo_synth   # (the synthetic dictionary is built once per box, not once per process)
 # the plain bench line: no GPU_MAX_HW_QUEUES in the environment -- the library sets it itself (config.streams says whether that took effect)
 # (bench.py prints the compact line and writes the full report to bench_full.json beside itself: both are kept)
-(unset GPU_MAX_HW_QUEUES; python "$REPO/bench.py" > "$OUT/${TAG}_bench_line.json" 2> "$OUT/bench.err"; cp "$REPO/bench_full.json" "$OUT/${TAG}_bench.json")
+(unset GPU_MAX_HW_QUEUES; python "$REPO/bench.py" --full > "$OUT/${TAG}_bench_line.json" 2> "$OUT/bench.err"; cp "$REPO/bench_full.json" "$OUT/${TAG}_bench.json")
 # under rocprofv3 the profiler initialises the runtime before the library is loaded: there the variable comes from the environment
 export GPU_MAX_HW_QUEUES=16
 cd /tmp && export TMPDIR=/tmp
-timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python "$REPO/bench.py" --steps 20 --warmup 5 --no-cpu --no-extras --no-stages > "$OUT/trace_line.json" 2> "$OUT/trace.err"
+timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python "$REPO/bench.py" --steps 20 --warmup 5 --full --no-cpu --no-extras --no-stages > "$OUT/trace_line.json" 2> "$OUT/trace.err"
 cp "$REPO/bench_full.json" "$OUT/trace.json"
 cp "$(find "$OUT/trace" -name "*kernel_stats.csv" | head -1)" "$OUT/${TAG}_kernel_stats.csv"
 # the same trace per dispatch: k_tokenize_pool by grid size (full 4096-sentence batches, the ragged last batch of a pass, small calls)
-{ echo "# rocprofv3 --kernel-trace of: python bench.py --steps 20 --warmup 5 --no-cpu --no-extras; bench line of the same run: trace.json"; python "$REPO/tools/trace_pool.py" "$(find "$OUT/trace" -name "*kernel_trace.csv" | head -1)" 480; python - "$OUT/trace.json" <<'PY'
+{ echo "# rocprofv3 --kernel-trace of: python bench.py --steps 20 --warmup 5 --full --no-cpu --no-extras --no-stages; bench line of the same run: trace.json"; python "$REPO/tools/trace_pool.py" "$(find "$OUT/trace" -name "*kernel_trace.csv" | head -1)" 480; python - "$OUT/trace.json" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); r = d["roofline"]
 print(f"bench.py (same run, HIP events): value {d['value']:.0f} sentences/s, avg_kernel_ms {r['avg_kernel_ms']:.4f}, avg_launch_chain_ms {r['avg_launch_chain_ms']:.4f}, launches_timed {r['launches_timed']}")
@@ -35,7 +35,7 @@ done
 BENCH_Q=8 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_cfg3" -- python "$REPO/tools/bench_cfg.py" cfg3 100000 > "$OUT/trace_cfg3.log" 2>&1
 cp "$(find "$OUT/trace_cfg3" -name "*kernel_stats.csv" | head -1)" "$OUT/${TAG}_cfg3_kernel_stats.csv"
 fi
-bash "$REPO/tools/pmc_passes.sh" "$OUT/pmc" python "$REPO/bench.py" --steps 2 --warmup 1 --queue 1 --no-cpu --no-extras --no-stages > "$OUT/pmc.log" 2>&1
+bash "$REPO/tools/pmc_passes.sh" "$OUT/pmc" python "$REPO/bench.py" --steps 2 --warmup 1 --queue 1 --full --no-cpu --no-extras --no-stages > "$OUT/pmc.log" 2>&1
 python "$REPO/tools/pmc_summary.py" "$OUT/pmc" --json "$OUT/${TAG}_pmc_summary.json" > "$OUT/${TAG}_pmc_summary.txt"
 python "$REPO/tools/make_traffic_json.py" "$OUT/${TAG}_pmc_summary.json" "$OUT/pmc_traffic.json" "$TAG" > /dev/null
 if [ "$PART" = all ]; then
@@ -49,7 +49,7 @@ bash "$REPO/tools/pmc_phases.sh" "$OUT/phases" 1 2 3 4 5 6 7 0 > "$OUT/${TAG}_ph
 # the bench line once more, now that the counter files belong to this tree (traffic_stale false)
 cp "$OUT/pmc_traffic.json" "$OUT/pmc_instructions.json" "$REPO/profiles/"
 cp "$OUT/${TAG}_bench.json" "$OUT/${TAG}_bench_first.json"
-(cd "$REPO" && unset GPU_MAX_HW_QUEUES && python bench.py > "$OUT/${TAG}_bench_line.json" 2> "$OUT/bench2.err"; cp "$REPO/bench_full.json" "$OUT/${TAG}_bench.json")
+(cd "$REPO" && unset GPU_MAX_HW_QUEUES && python bench.py --full > "$OUT/${TAG}_bench_line.json" 2> "$OUT/bench2.err"; cp "$REPO/bench_full.json" "$OUT/${TAG}_bench.json")
 (cd "$REPO/kanpyo_amd/csrc" && make -s resource-usage 2>&1 | grep -E "Function Name|VGPRs:|SGPRs Spill|VGPRs Spill|ScratchSize|Occupancy|LDS Size" > "$OUT/${TAG}_resource_usage.txt")
 rm -rf "$OUT"/trace "$OUT"/trace_cfg5_q8 "$OUT"/trace_cfg5_q1 "$OUT"/trace_cfg3 "$OUT"/pmc/pass*/ "$OUT"/pmc_cfg5/pass*/ "$OUT"/pmc_cfg5_team/pass*/ "$OUT"/phases
 echo done

@@ -24,7 +24,7 @@ write_kb = d[main]["WRITE_SIZE"]["per_dispatch"]  # behind it finds an empty lis
 out = {
     "kernel_src_sha16": kernel_source_hash(),
     "source": f"profiles/{tag}_pmc_summary.json (rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over "
-              "`python bench.py --steps 2 --warmup 1 --queue 1 --no-cpu --no-extras`, tools/pmc_passes.sh)",
+              "`python bench.py --steps 2 --warmup 1 --queue 1 --full --no-cpu --no-extras`, tools/pmc_passes.sh)",
     "per": "one k_tokenize_pool launch over a full batch of 4096 sentences (grid 1024 x 256): " + main,
     "batches": batches,
     "fetch_size_kb": fetch_kb,

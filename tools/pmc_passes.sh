@@ -1,7 +1,7 @@
 #!/bin/bash
 # Separate rocprofv3 --pmc passes (never combined with tracing; only the counter groups that have run clean on this pool --
 # other groups have hung the profiler) over a short run of a command.
-# usage (GPU box): bash tools/pmc_passes.sh <outdir> <command...>      e.g.  ... python bench.py --steps 2 --warmup 1 --queue 1 --no-cpu --no-extras
+# usage (GPU box): bash tools/pmc_passes.sh <outdir> <command...>      e.g.  ... python bench.py --steps 2 --warmup 1 --queue 1 --full --no-cpu --no-extras
 set -u
 OUT=$(realpath -m "$1"); shift
 mkdir -p "$OUT"
