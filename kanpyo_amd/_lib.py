@@ -30,15 +30,16 @@ SYMBOLS = [
 
 
 def kernel_source_hash() -> str:
-    """sha256[:16] over every source and header the library is built from (the Makefile's SRCS and HDRS: kernels, device helpers,
-    shared structs, the runtime's launch planning).  Profile-derived files under profiles/ record it, bench.py compares: a counter
-    file measured on other code says so (`stale`)."""
+    """sha256[:16] over every source and header the library is built from (csrc/*.hip, *.cpp, *.h, sorted, and the public header).
+    Profile-derived files under profiles/ record it, bench.py compares: a counter file measured on other code says so (`stale`)."""
+    import glob
     import hashlib
 
+    csrc = os.path.join(_HERE, "csrc")
+    names = sorted(os.path.basename(p) for ext in ("hip", "cpp", "h") for p in glob.glob(os.path.join(csrc, "*." + ext)))
     h = hashlib.sha256()
-    for name in ("kgpu_pool.hip", "kgpu_kernels.hip", "kgpu_window.hip", "kgpu_device.h", "kgpu_internal.h", "kgpu_chartrie.cpp",
-                 "kgpu_api.cpp", "kgpu_multi.cpp", "kgpu_runtime.h", "kgpu_index_build.cpp", "../../include/kanpyo_gpu.h"):
-        with open(os.path.join(_HERE, "csrc", name), "rb") as f:
+    for name in names + ["../../include/kanpyo_gpu.h"]:
+        with open(os.path.join(csrc, name), "rb") as f:
             h.update(name.encode() + b"\0" + f.read())
     return h.hexdigest()[:16]
 

@@ -1,0 +1,345 @@
+// kanpyo_amd/csrc/kgpu_host.cpp -- kgpu_tokenize_batch beyond the small calls: the large-call pipeline over host buffers.
+//
+// Owns: the worker pool (with no threads its tasks run on the calling thread), parallel_copy, is_pinned_host, the chunk's input
+// staging and mapped result block (ChunkBlock, shared with kgpu_multi.cpp), the 24-byte per-chunk fallback for tokens beyond the
+// 8-byte record (HostJob), the pipeline itself, and kgpu_host_alloc / kgpu_host_free.
+#include <algorithm>
+#include <atomic>
+#include <cstdlib>
+#include <cstring>
+#include <ctime>
+#include <functional>
+#include <mutex>
+#include <thread>
+#include <pthread.h>
+#include <vector>
+
+#include "kgpu_runtime.h"
+
+// ---- the 24-byte form of one chunk ----------------------------------------------------------------------
+// What a chunk of a large call falls back to when a token does not fit the 8-byte record (pipe_finish): 24-byte records on the
+// device, device-to-host copies on the context's stream.
+struct HostJob {
+    kgpu_ctx *c = nullptr;
+    uint64_t lo = 0, m = 0;        // sentences [lo, lo + m) of the call
+    std::vector<uint64_t> rel;     // chunk-relative byte offsets (must outlive the asynchronous H2D copy)
+};
+
+static int host_job_submit(HostJob &j, const uint8_t *utf8, const uint64_t *offsets) {
+    kgpu_ctx *c = j.c;
+    const uint64_t *off = offsets + j.lo;
+    const uint64_t n = j.m, base = off[0], total = off[n] - base;
+    j.rel.resize((size_t)n + 1);
+    for (uint64_t i = 0; i <= n; ++i) j.rel[(size_t)i] = off[i] - base;
+    const uint64_t cap = total + n + 1;  // tokens <= chars + 1 <= bytes + 1 per sentence: never too small
+    int rc;
+    if ((rc = c->in_utf8.ensure((size_t)total + 16)) || (rc = c->in_off.ensure((size_t)(n + 1) * 8)) ||
+        (rc = c->out_tok.ensure((size_t)cap * sizeof(kgpu_token) + 64)) ||
+        (rc = c->out_off.ensure((size_t)(n + 1) * 8)) || (rc = c->out_status.ensure((size_t)n + 16)))
+        return rc;
+    if ((total && (rc = ctx_h2d(c, c->in_utf8.p, utf8 + base, (size_t)total, "H2D utf8"))) ||
+        (rc = ctx_h2d(c, c->in_off.p, j.rel.data(), (size_t)(n + 1) * 8, "H2D offsets")))
+        return rc;
+    return kgpu_tokenize_device(c, (const uint8_t *)c->in_utf8.p, (const uint64_t *)c->in_off.p, n, total,
+                                (kgpu_token *)c->out_tok.p, cap, (uint64_t *)c->out_off.p, (uint8_t *)c->out_status.p);
+}
+
+// Wait for the job, copy its results behind the `tok_done` tokens already delivered (or only count, once the
+// caller's buffer has overflowed) and make the chunk-local token offsets global.
+static int host_job_finish(HostJob &j, kgpu_token *tokens, uint64_t token_capacity, uint64_t *tok_offsets, uint8_t *status,
+                           uint64_t &tok_done, bool &overflow) {
+    kgpu_ctx *c = j.c;
+    uint64_t got = 0;
+    int rc = kgpu_ctx_sync(c, &got);
+    if (rc) return rc;
+    if (tok_done + got > token_capacity) overflow = true;
+    hipError_t e;
+    if (!overflow) {
+        if (got && (e = hipMemcpyAsync(tokens + tok_done, c->out_tok.p, (size_t)got * sizeof(kgpu_token), hipMemcpyDeviceToHost, c->stream)) != hipSuccess) { set_error("D2H tokens: %s", hipGetErrorString(e)); return KGPU_ERR_HIP; }
+        if ((e = hipMemcpyAsync(tok_offsets + j.lo, c->out_off.p, (size_t)(j.m + 1) * 8, hipMemcpyDeviceToHost, c->stream)) != hipSuccess) { set_error("D2H offsets: %s", hipGetErrorString(e)); return KGPU_ERR_HIP; }
+    }
+    if (status && j.m && (e = hipMemcpyAsync(status + j.lo, c->out_status.p, (size_t)j.m, hipMemcpyDeviceToHost, c->stream)) != hipSuccess) { set_error("D2H status: %s", hipGetErrorString(e)); return KGPU_ERR_HIP; }
+    // pageable destinations make these copies synchronous; pinned ones (kgpu_host_alloc) run at DMA speed while the
+    // next chunks' kernels execute.  The offsets fix-up below needs the data, so wait for this stream's copies here.
+    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) { set_error("D2H sync: %s", hipGetErrorString(e)); return KGPU_ERR_HIP; }
+    if (!overflow) for (uint64_t i = 0; i <= j.m; ++i) tok_offsets[j.lo + i] += tok_done;  // chunk-local -> global
+    tok_done += got;
+    return KGPU_OK;
+}
+
+// ---- large host calls: 8-byte records over PCIe, expanded by a few host threads ---------------------------
+// What a large call moves device -> host is 24 bytes per token, seven times its input (32 tokens per 113-byte sentence on the
+// cfg 2 corpus): ~65 M sentences/s at PCIe speed, and through pageable destinations far less.  Here the compaction kernel writes
+// 8-byte kgpu_token8 records straight into pinned, device-mapped host memory (its stores are the transfer: no copy node, no
+// D2H call), and worker threads expand them into the caller's 24-byte records (any memory: the expansion replaces the copy
+// a pageable destination costs anyway) while the next chunks compute.
+namespace kgpu {
+// A few host threads for the large calls: expansion of the 8-byte records, staging copies.  Heap-allocated and never destroyed (its
+// threads end with the process).  fork(): the child has none of the parent's threads, and its copy of the pool may hold a locked mutex
+// or a condition variable with waiters -- the child handler abandons it and the first use there makes a fresh one.  Thread creation
+// can fail (std::system_error): start() reports how many threads run, and with none submit() runs every task on the calling thread
+// (every counter a caller waits on is set before its tasks are submitted, so wait_zero then returns at once).
+unsigned WorkerPool::start() {
+    std::lock_guard<std::mutex> g(mu);
+    if (!th.empty()) return (unsigned)th.size();
+    unsigned n = 0;
+    if (const char *e = getenv("KGPU_HOST_THREADS")) n = (unsigned)atoi(e);
+    if (n == 0) n = std::min(8u, std::max(2u, std::thread::hardware_concurrency() / 8));
+    for (unsigned i = 0; i < n; ++i) {
+        try {
+            th.emplace_back([this] {
+                for (;;) {
+                    std::function<void()> f;
+                    { std::unique_lock<std::mutex> l(mu); cv.wait(l, [this] { return !q.empty(); }); f = std::move(q.front()); q.pop_front(); }
+                    f();
+                }
+            });
+        } catch (...) { break; }  // out of threads: run with what there is
+    }
+    return (unsigned)th.size();
+}
+void WorkerPool::submit(std::function<void()> f) {
+    bool queued;
+    { std::lock_guard<std::mutex> g(mu); queued = !th.empty(); if (queued) q.push_back(std::move(f)); }
+    if (queued) cv.notify_one();
+    else f();   // no worker threads: the caller's own
+}
+// A counter of tasks reaching zero: a short spin (the common case: the workers are almost through), then sleeps on the pool's
+// completion signal instead of burning a core the workers could use.
+void WorkerPool::wait_zero(std::atomic<int> &counter) {
+    // (the tasks waited for here are tens of microseconds long: a sleep costs more than it saves until the wait has lasted a while)
+    timespec t0; clock_gettime(CLOCK_MONOTONIC, &t0);
+    for (;;) {
+        for (int spin = 0; spin < 64; ++spin) { if (counter.load(std::memory_order_acquire) == 0) return; std::this_thread::yield(); }
+        timespec t1; clock_gettime(CLOCK_MONOTONIC, &t1);
+        if ((t1.tv_sec - t0.tv_sec) * 1000000ll + (t1.tv_nsec - t0.tv_nsec) / 1000 > 2000) break;
+    }
+    std::unique_lock<std::mutex> l(done_mu);
+    while (counter.load(std::memory_order_acquire) != 0) done_cv.wait_for(l, std::chrono::microseconds(200));
+}
+void WorkerPool::task_done(std::atomic<int> &counter) {
+    if (counter.fetch_sub(1, std::memory_order_acq_rel) == 1) { std::lock_guard<std::mutex> g(done_mu); done_cv.notify_all(); }
+}
+static std::atomic<WorkerPool *> g_pool{nullptr};
+static std::atomic<int> g_pool_lock{0};
+static void pool_atfork_child() { g_pool.store(nullptr, std::memory_order_relaxed); g_pool_lock.store(0, std::memory_order_relaxed); }
+WorkerPool &workers() {
+    WorkerPool *w = g_pool.load(std::memory_order_acquire);
+    if (w) return *w;
+    while (g_pool_lock.exchange(1, std::memory_order_acquire)) std::this_thread::yield();
+    static bool hooked = false;
+    if (!hooked) { hooked = true; pthread_atfork(nullptr, nullptr, pool_atfork_child); }
+    w = g_pool.load(std::memory_order_relaxed);
+    if (!w) { w = new WorkerPool(); g_pool.store(w, std::memory_order_release); }
+    g_pool_lock.store(0, std::memory_order_release);
+    return *w;
+}
+}  // namespace kgpu
+
+// The layout of a chunk's two blocks (kgpu_runtime.h: ChunkBlock) and the context's buffers big enough for it.
+int ChunkBlock::prepare(kgpu_ctx *c, uint64_t n_, uint64_t total_, bool staged) {
+    n = n_; total = total_;
+    cap = total + n + 1;  // tokens <= chars + 1 <= bytes + 1 per sentence: never too small
+    in_off = ((size_t)(n + 1) * 8 + 63) & ~(size_t)63;
+    const size_t in_bytes = in_off + (size_t)total + 16;
+    off_first = ((size_t)cap * 8 + 63) & ~(size_t)63;
+    off_toff = off_first + (((size_t)n * 8 + 63) & ~(size_t)63);
+    off_status = off_toff + (((size_t)(n + 1) * 8 + 63) & ~(size_t)63);
+    int rc;
+    if ((rc = c->in_block.ensure(in_bytes)) || (rc = c->pin_out.ensure(off_status + (size_t)n + 64, true)) || (rc = c->out_status.ensure((size_t)n + 16)) ||
+        (rc = c->out_off.ensure((size_t)(n + 1) * 8)) || (staged && (rc = c->pin_in.ensure(in_bytes, false))))
+        return rc;
+    return KGPU_OK;
+}
+// The launch chain over the input block (its offsets start at `base`: the text pointer is biased by it), 8-byte records into the mapped block.
+int ChunkBlock::launch(kgpu_ctx *c, uint64_t base, const char *who) const {
+    uint8_t *dblk = (uint8_t *)c->in_block.p, *po = (uint8_t *)c->pin_out.d;
+    return tokenize_device_impl(c, dblk + in_off - base, (const uint64_t *)dblk, n, total, nullptr, (kgpu_token8 *)po, (uint32_t *)(po + off_first), po + off_status,
+                                (uint64_t *)(po + off_toff), cap, (uint64_t *)c->out_off.p, (uint8_t *)c->out_status.p, who);
+}
+MergeSrc ChunkBlock::results(const kgpu_ctx *c) const {
+    const uint8_t *ph = (const uint8_t *)c->pin_out.h;
+    return MergeSrc{(const kgpu_token8 *)ph, (const uint32_t *)(ph + off_first), (const uint64_t *)(ph + off_toff), ph + off_status};
+}
+
+struct PipeJob {
+    kgpu_ctx *c = nullptr;
+    uint64_t lo = 0, m = 0;
+    ChunkBlock blk;                                     // its input block and mapped result block
+    std::atomic<int> tasks{0};                          // expansion tasks still reading pin_out
+    bool stream = false;                                // the call is large: its 24-byte records are written with non-temporal stores (kgpu_runtime.h: expand_tokens)
+};
+
+// memcpy of a large block with the workers' help (the calling thread's staging copy is what limits a large call otherwise)
+void kgpu::parallel_copy(void *dst, const void *src, size_t bytes) {
+    constexpr size_t PIECE = 256 * 1024;
+    if (bytes < 2 * PIECE) { std::memcpy(dst, src, bytes); return; }
+    const size_t np = std::min<size_t>(8, bytes / PIECE), each = ((bytes + np - 1) / np + 63) & ~(size_t)63;  // np * each >= bytes (rounded UP: a floor here lost the last bytes of a chunk)
+    std::atomic<int> left{(int)np - 1};
+    for (size_t k = 1; k < np; ++k) {
+        const size_t lo = k * each, hi = std::min(bytes, lo + each);
+        std::atomic<int> *l = &left;
+        workers().submit([=] { if (hi > lo) std::memcpy((uint8_t *)dst + lo, (const uint8_t *)src + lo, hi - lo); workers().task_done(*l); });
+    }
+    std::memcpy(dst, src, std::min(bytes, each));
+    workers().wait_zero(left);
+}
+
+bool kgpu::is_pinned_host(const void *p) {
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return at.type == hipMemoryTypeHost;
+}
+
+// The chunk's input goes to the device as ONE block [offsets (absolute, as the caller has them) | bytes]; the kernels subtract
+// offsets[0] themselves, the text pointer is biased by it.  Pinned caller memory is copied from directly (DMA), pageable memory through
+// the context's pinned staging block, filled with the workers' help.
+static int pipe_submit(PipeJob &j, const uint8_t *utf8, const uint64_t *offsets, bool pinned_in) {
+    kgpu_ctx *c = j.c;
+    workers().wait_zero(j.tasks);  // the block's previous results are still being expanded
+    const uint64_t *off = offsets + j.lo;
+    const uint64_t n = j.m, base = off[0], total = off[n] - base;
+    int rc;
+    if ((rc = j.blk.prepare(c, n, total, !pinned_in))) return rc;
+    uint8_t *dblk = (uint8_t *)c->in_block.p;
+    const size_t in_off = j.blk.in_off;
+    if (pinned_in) {
+        if ((rc = ctx_h2d(c, dblk, off, (size_t)(n + 1) * 8, "H2D input")) ||
+            (total && (rc = ctx_h2d(c, dblk + in_off, utf8 + base, (size_t)total, "H2D input"))))
+            return rc;
+    } else {
+        std::memcpy(c->pin_in.h, off, (size_t)(n + 1) * 8);
+        if (total) parallel_copy((uint8_t *)c->pin_in.h + in_off, utf8 + base, (size_t)total);
+        if ((rc = ctx_h2d(c, dblk, c->pin_in.h, in_off + (size_t)total, "H2D input block"))) return rc;
+    }
+    return j.blk.launch(c, base, "kgpu_tokenize_batch");
+}
+
+
+// Wait for the chunk's kernels (its records are in host memory then), hand the expansion to the workers in slices of 2048 sentences.
+static int pipe_finish(PipeJob &j, const uint8_t *utf8, const uint64_t *offsets, kgpu_token *tokens, uint64_t token_capacity, uint64_t *tok_offsets,
+                       uint8_t *status, uint64_t &tok_done, bool &overflow, std::atomic<int> &outstanding) {
+    kgpu_ctx *c = j.c;
+    uint64_t got = 0;
+    int rc = kgpu_ctx_sync(c, &got);
+    if (rc == KGPU_ERR_CAPACITY && c->h_ctl->pack_overflow) {  // a token beyond the 8-byte packing: this chunk once more, 24-byte records, the plain way
+        // (the previous chunk's last expansion slice stores tok_offsets[j.lo] too -- the boundary entry -- and host_job_finish copies and then adds
+        // to it: wait for the expansions in flight first)
+        workers().wait_zero(outstanding);
+        HostJob hj;
+        hj.c = c; hj.lo = j.lo; hj.m = j.m;
+        if ((rc = host_job_submit(hj, utf8, offsets))) return rc;
+        return host_job_finish(hj, tokens, token_capacity, tok_offsets, status, tok_done, overflow);
+    }
+    if (rc) return rc;
+    if (tok_done + got > token_capacity) overflow = true;
+    const uint64_t tok_base = tok_done;
+    tok_done += got;
+    const MergeSrc r = j.blk.results(c);
+    const kgpu_token8 *rec = r.rec;
+    const uint32_t *first = r.first;
+    const uint64_t *toff = r.toff;
+    const uint8_t *st = r.st;
+    const uint64_t SLICE = std::min<uint64_t>(2048, std::max<uint64_t>(256, j.m / 8));  // (a lone 4096-sentence call: eight slices, not two)
+    const int nt = (int)((j.m + SLICE - 1) / SLICE);
+    if (nt == 0) { if (!overflow) tok_offsets[j.lo] = tok_base; return KGPU_OK; }
+    j.tasks.store(nt, std::memory_order_release);
+    outstanding.fetch_add(nt, std::memory_order_acq_rel);
+    const bool ovf = overflow, jstream = j.stream;
+    const uint64_t lo = j.lo, m = j.m;
+    for (int t = 0; t < nt; ++t) {
+        const uint64_t a = (uint64_t)t * SLICE, b = std::min(m, a + SLICE);
+        std::atomic<int> *jt = &j.tasks, *out = &outstanding;
+        workers().submit([=] {
+            if (!ovf) {
+                const bool stream = jstream;
+                expand_tokens(rec + toff[a], toff + a, first + 2 * a, b - a, tokens + tok_base + toff[a], stream);
+                for (uint64_t i = a; i < b; ++i) tok_offsets[lo + i] = tok_base + toff[i];
+                if (b == m) tok_offsets[lo + m] = tok_base + toff[m];
+                if (stream) expand_fence();
+            }
+            if (status) std::memcpy(status + lo + a, st + a, (size_t)(b - a));
+            workers().task_done(*jt);
+            workers().task_done(*out);
+        });
+    }
+    return KGPU_OK;
+}
+
+extern "C" int kgpu_tokenize_batch(kgpu_dict *d, const uint8_t *utf8, const uint64_t *offsets, uint64_t n,
+                                   kgpu_token *tokens, uint64_t token_capacity, uint64_t *tok_offsets,
+                                   uint8_t *status, uint64_t *n_tokens) {
+    if (!d || !offsets || !tok_offsets || (token_capacity && !tokens)) {
+        set_error("kgpu_tokenize_batch: null argument");
+        return KGPU_ERR_INVALID_ARG;
+    }
+    for (uint64_t i = 0; i < n; ++i)
+        if (offsets[i + 1] < offsets[i]) { set_error("kgpu_tokenize_batch: offsets not monotone at %llu", (unsigned long long)i); return KGPU_ERR_INVALID_ARG; }
+    if (offsets[n] - offsets[0] && !utf8) { set_error("kgpu_tokenize_batch: null utf8"); return KGPU_ERR_INVALID_ARG; }
+    const uint64_t kd0 = small_trace_on() ? cpu_ns() : 0;
+    HIPCHECK(hipSetDevice(d->device));
+    if (kd0) g_sc[11] += cpu_ns() - kd0;   // (KGPU_SMALL_TRACE: the CPU time of hipSetDevice)
+
+    {
+        const int rc = tokenize_small(d, utf8, offsets, n, tokens, token_capacity, tok_offsets, status, n_tokens);
+        if (rc != -1) return rc;  // -1: not a small call, or a sentence needs a kernel that path does not launch: take the general path below
+    }
+
+    // A large call goes through in chunks on pooled contexts, several in flight: while chunk k's records are expanded on the host,
+    // chunk k+1 .. k+4 compute and chunk k+5's input is on its way.  Results are delivered in order, so the tokens stay dense.
+    const TestHooks hooks = test_hooks();
+    workers().start();   // (none to be had: the workers' tasks run on this thread)
+    // chunks of 8192 sentences, ten in the device pipeline (measured on 400k sentences: 16384 x 6: 55.6, 8192 x 10: 61.2, 4096 x 14: 58.8 M sentences/s)
+    const uint64_t CHUNK_BYTES = std::min<uint64_t>(hooks.chunk_bytes, 2ull << 20);
+    const uint64_t CHUNK_SENTS = std::min<uint64_t>(hooks.chunk_sents, std::min<uint64_t>(8192, std::max<uint64_t>(1024, n / 12)));   // (round 6: the floor was 2048 -- with the pool kernel at 59 us per 4096 sentences a 4096-sentence call runs 182 -> 174 us as four chunks)
+    const bool pinned_in = (offsets[n] - offsets[0]) != 0 && is_pinned_host(utf8) && is_pinned_host(offsets);
+    constexpr int MAX_DEPTH = 16;
+    const int DEPTH = (int)std::min<uint64_t>(MAX_DEPTH, std::max<uint64_t>(3, hooks.depth));
+    PipeJob jobs[MAX_DEPTH];
+    std::atomic<int> outstanding{0};
+    int rc = KGPU_OK;
+    uint64_t done = 0, tok_done = 0;
+    bool overflow = false;
+    tok_offsets[0] = 0;
+    int head = 0, inflight = 0;  // jobs[head .. head + inflight) (mod DEPTH) are active, oldest first
+    while (!rc && (done < n || (n == 0 && done == 0 && inflight == 0))) {
+        if (inflight == DEPTH - 2) {  // two slots stay out of the GPU pipeline: their blocks are being expanded
+            rc = pipe_finish(jobs[head], utf8, offsets, tokens, token_capacity, tok_offsets, status, tok_done, overflow, outstanding);
+            head = (head + 1) % DEPTH; --inflight;
+            if (rc) break;
+        }
+        PipeJob &j = jobs[(head + inflight) % DEPTH];
+        if (!j.c && (rc = pool_get(d, &j.c))) break;
+        uint64_t m = 0;
+        while (done + m < n && m < CHUNK_SENTS && (m == 0 || offsets[done + m + 1] - offsets[done] <= CHUNK_BYTES)) ++m;
+        j.lo = done; j.m = m;
+        j.stream = expand_stream_wanted((uint64_t)n * 2);   // by the CALL's size (32 768 tokens ~ 16 384 sentences and more): a 4096-sentence call's records are read back at once
+        if ((rc = pipe_submit(j, utf8, offsets, pinned_in))) break;
+        ++inflight;
+        done += m;
+        if (n == 0) break;
+    }
+    while (inflight) {  // drain in order (also after an error: the contexts go back to the pool idle)
+        int r2 = pipe_finish(jobs[head], utf8, offsets, tokens, token_capacity, tok_offsets, status, tok_done, overflow, outstanding);
+        if (!rc) rc = r2;
+        head = (head + 1) % DEPTH; --inflight;
+    }
+    workers().wait_zero(outstanding);
+    for (int k = 0; k < DEPTH; ++k)
+        if (jobs[k].c) pool_put(d, jobs[k].c);
+    if (n_tokens) *n_tokens = tok_done;
+    if (!rc && overflow) {
+        set_error("token buffer too small: need %llu, capacity %llu", (unsigned long long)tok_done, (unsigned long long)token_capacity);
+        return KGPU_ERR_CAPACITY;
+    }
+    return rc;
+}
+
+// Pinned, device-visible host memory for the buffers of kgpu_tokenize_batch: the copies then run as DMA
+// at PCIe speed and overlap the kernels (pageable memory is staged by the runtime, synchronously).
+extern "C" void *kgpu_host_alloc(uint64_t bytes) {
+    void *p = nullptr;
+    if (hipHostMalloc(&p, (size_t)(bytes ? bytes : 1), hipHostMallocDefault) != hipSuccess) { set_error("kgpu_host_alloc: %llu bytes failed", (unsigned long long)bytes); return nullptr; }
+    return p;
+}
+extern "C" void kgpu_host_free(void *p) { if (p) (void)hipHostFree(p); }

@@ -1,5 +1,5 @@
 // kanpyo_amd/csrc/kgpu_internal.h -- shared between the host runtime
-// (kgpu_api.cpp, kgpu_index_build.cpp) and the HIP kernels (kgpu_kernels.hip)
+// (kgpu_dict.cpp, kgpu_ctx.cpp, kgpu_index_build.cpp) and the HIP kernels (kgpu_kernels.hip)
 // of libkanpyo_gpu.so.  Not part of the public ABI.  Plain structs only, so it
 // compiles as host C++ and as HIP.
 #pragma once
@@ -56,7 +56,7 @@ struct DictView {
                              // the root, or {0, byte steps attempted before the walk failed}
     const Morph8 *morph;     uint32_t n_morph;
     const Morph8 *unk_morph; uint32_t n_unk_morph;   // == morph + n_morph: one table (record of node sid: morph[sid > 0 ? sid - 1 : n_morph - 1 - sid])
-    const int16_t *conn;     uint32_t conn_rows;  // element (right,left) at left*rows+right (ids frequency-ranked, see kgpu_api.cpp)
+    const int16_t *conn;     uint32_t conn_rows;  // element (right,left) at left*rows+right (ids frequency-ranked, see kgpu_dict.cpp)
     uint32_t bos_right, eos_left;                  // the ranked ids of context id 0 (BOS/EOS Morph(0,0,0))
     const uint8_t *cat;      uint32_t cat_len;    // char_category_def.rs:17,33-38
     const CatInfo *cinfo;                          // 256 entries
@@ -125,7 +125,7 @@ struct LaunchPlan {
     uint32_t pool_bytes[2];
     uint32_t pool_waves[2];
     uint32_t pool_max_pages[2];  // of 64: larger reservations are routed to the next launch
-    bool pool_limit_auto;        // the shipped plan (no KGPU_POOL): the runtime may pick the pool shape per batch (kgpu_api.cpp: enqueue)
+    bool pool_limit_auto;        // the shipped plan (no KGPU_POOL): the runtime may pick the pool shape per batch (kgpu_ctx.cpp: enqueue)
     uint32_t alt_pool_bytes, alt_pool_waves;   // ... the shape for chains that hold a windowed launch: smaller workgroups (20 KB, two wavefronts) find their LDS
     int alt_pool_workgroups;                   // sooner on a chip full of 10 KB single-wavefront workgroups (0: not available)
     int pool_workgroups[2];   // persistent grid per pool launch
@@ -153,7 +153,7 @@ int window_workgroups_per_cu(uint32_t lds_bytes);
 int window_team_workgroups_per_cu(uint32_t lds_bytes, int team);
 int launch_general_only(const DictView &d, const BatchArgs &a, void *stream);
 int launch_small_call(const DictView &d, const BatchArgs &a, const LaunchPlan &plan, void *stream);  // pool kernel alone, one sentence per wavefront  // kgpu_lattice_dump: HBM-scratch kernel alone
-int launch_scan_compact(const BatchArgs &a, Control *host_ctl, void *stream, bool small_workgroups = false, bool small_scan_only = false /* measurement */);  // host_ctl: device pointer of the pinned result block
+int launch_scan_compact(const BatchArgs &a, Control *host_ctl, void *stream, bool small_workgroups = false);  // host_ctl: device pointer of the pinned result block
 LaunchPlan default_launch_plan(int device);
 int pool_workgroups_per_cu(uint32_t pool_bytes, uint32_t waves);
 

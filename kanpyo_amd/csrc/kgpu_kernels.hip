@@ -596,7 +596,7 @@ int launch_tokenize(const DictView &d, const BatchArgs &a, const LaunchPlan &pla
     return launch_general_over(d, a, plan, in_list, in_count, stop_after, stream);
 }
 
-// What a chain that ended on work list `li` left out (kgpu_api.cpp: enqueue_tail): the windowed kernel over that list unless it was in the chain,
+// What a chain that ended on work list `li` left out (kgpu_ctx.cpp: enqueue_tail): the windowed kernel over that list unless it was in the chain,
 // then the general kernel over what is left.
 int launch_tail_only(const DictView &d, const BatchArgs &a, const LaunchPlan &plan, int li, bool window_was_in_chain, void *stream) {
     Control *ctl = a.ctl;
@@ -630,7 +630,7 @@ int launch_general_only(const DictView &d, const BatchArgs &a, void *stream) {
     return (int)hipGetLastError();
 }
 
-int launch_scan_compact(const BatchArgs &a, Control *host_ctl, void *stream, bool small_workgroups, bool small_scan_only) {
+int launch_scan_compact(const BatchArgs &a, Control *host_ctl, void *stream, bool small_workgroups) {
     // Measured (tools/ab_scan.sh): records bound for mapped host memory (the large host call: a.toff8) 83.8 against 66.6 M sentences/s end to end in one
     // launch; the device-resident 24-byte path 92.8 against 96.9 -- there the separate kernels stay.  KGPU_SCAN_COMPACT=1 / 2 force one form (experiments),
     // KGPU_SCAN_WG the sentences per workgroup.
@@ -646,7 +646,7 @@ int launch_scan_compact(const BatchArgs &a, Control *host_ctl, void *stream, boo
     }
     // small_workgroups: behind a chain that holds a windowed launch the chip is full of single-wavefront workgroups at four 128-VGPR wavefronts per SIMD -- a
     // workgroup of one wavefront finds a place as soon as ANY of them ends, one of sixteen (or four) needs a CU (or a SIMD row) to drain
-    const unsigned scan_threads = !(small_workgroups || small_scan_only) ? 1024u : a.n > 1024 ? 256u : 64u, wpb = small_workgroups ? 1u : 4u;
+    const unsigned scan_threads = !small_workgroups ? 1024u : a.n > 1024 ? 256u : 64u, wpb = small_workgroups ? 1u : 4u;
     hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(scan_threads), 0, (hipStream_t)stream, a, host_ctl);
     uint64_t blocks = (a.n + wpb - 1) / wpb;
     if (blocks > 2048 * (4 / wpb)) blocks = 2048 * (4 / wpb);

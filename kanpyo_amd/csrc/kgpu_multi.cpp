@@ -25,8 +25,6 @@ namespace kgpu {
 // Global sentence j of a super-chunk lives in shard j mod G at local index j / G.  Per slice of the super-chunk: its token total is a difference of two
 // entries of every shard's offset table (O(G), on the merging thread), an exclusive scan over the slices gives every slice its base, and one task per
 // slice then walks the G shard cursors once -- offsets, expansion of the 8-byte records and status bytes in the same pass, no division per sentence.
-struct MergeSrc { const kgpu_token8 *rec; const uint32_t *first; const uint64_t *toff; const uint8_t *st; };
-
 // sentences j < x of a super-chunk with j mod G == g
 static inline uint64_t shard_prefix(uint64_t x, uint64_t g, uint64_t G) { return (x + G - 1 - g) / G; }
 
@@ -90,8 +88,7 @@ constexpr int GPU_DEPTH = 6;   // ... of which in the device pipeline
 
 struct ShardJob {
     kgpu_ctx *c = nullptr;
-    uint64_t m = 0, cap = 0;
-    size_t off_first = 0, off_toff = 0, off_status = 0;  // inside pin_out: records | first | token offsets | status
+    ChunkBlock blk;   // its input block and mapped result block
 };
 
 struct MultiCall {
@@ -127,20 +124,12 @@ int shard_submit(MultiCall &mc, int g, uint64_t c) {
     ShardJob &j = mc.jobs[(size_t)g * NSLOT + (size_t)(c % NSLOT)];
     kgpu_ctx *ctx = j.c;
     const uint64_t lo = mc.chunk_lo(c), m = mc.shard_count(c, g);
-    j.m = m;
     uint64_t total = 0;
     for (uint64_t k = 0; k < m; ++k) { const uint64_t i = lo + (uint64_t)g + k * (uint64_t)mc.G; total += mc.offsets[i + 1] - mc.offsets[i]; }
-    j.cap = total + m + 1;  // tokens <= chars + 1 <= bytes + 1 per sentence: never too small
-    const size_t in_off_bytes = ((size_t)(m + 1) * 8 + 63) & ~(size_t)63, in_bytes = in_off_bytes + (size_t)total + 16;
-    j.off_first = ((size_t)j.cap * 8 + 63) & ~(size_t)63;
-    j.off_toff = j.off_first + (((size_t)m * 8 + 63) & ~(size_t)63);
-    j.off_status = j.off_toff + (((size_t)(m + 1) * 8 + 63) & ~(size_t)63);
     int rc;
-    if ((rc = ctx->in_block.ensure(in_bytes)) || (rc = ctx->pin_out.ensure(j.off_status + (size_t)m + 64, true)) || (rc = ctx->out_status.ensure((size_t)m + 16)) ||
-        (rc = ctx->out_off.ensure((size_t)(m + 1) * 8)) || (rc = ctx->pin_in.ensure(in_bytes, false)))
-        return rc;
+    if ((rc = j.blk.prepare(ctx, m, total, true))) return rc;
     uint64_t *h_off = (uint64_t *)ctx->pin_in.h;
-    uint8_t *h_txt = (uint8_t *)ctx->pin_in.h + in_off_bytes;
+    uint8_t *h_txt = (uint8_t *)ctx->pin_in.h + j.blk.in_off;
     {
         uint64_t at = 0;
         for (uint64_t k = 0; k < m; ++k) { const uint64_t i = lo + (uint64_t)g + k * (uint64_t)mc.G; h_off[k] = at; at += mc.offsets[i + 1] - mc.offsets[i]; }
@@ -165,13 +154,8 @@ int shard_submit(MultiCall &mc, int g, uint64_t c) {
         piece(0, std::min(m, each));
         if (np > 1) workers().wait_zero(left);
     }
-    hipError_t e;
-    uint8_t *dblk = (uint8_t *)ctx->in_block.p;
-    ctx->h2d_queued = true;
-    if ((e = hipMemcpyAsync(dblk, ctx->pin_in.h, in_off_bytes + (size_t)total, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) { set_error("H2D input block: %s", hipGetErrorString(e)); return KGPU_ERR_HIP; }
-    uint8_t *po = (uint8_t *)ctx->pin_out.d;
-    return tokenize_device_impl(ctx, dblk + in_off_bytes, (const uint64_t *)dblk, m, total, nullptr, (kgpu_token8 *)po, (uint32_t *)(po + j.off_first), po + j.off_status,
-                                (uint64_t *)(po + j.off_toff), j.cap, (uint64_t *)ctx->out_off.p, (uint8_t *)ctx->out_status.p, "kgpu_tokenize_batch_multi");
+    if ((rc = ctx_h2d(ctx, ctx->in_block.p, ctx->pin_in.h, j.blk.in_off + (size_t)total, "H2D input block"))) return rc;
+    return j.blk.launch(ctx, 0, "kgpu_tokenize_batch_multi");   // (the shard's offsets start at 0)
 }
 
 void device_thread(MultiCall *pmc, int g) {
@@ -269,8 +253,7 @@ static int multi_impl(kgpu_dict *const *dicts, int n_dicts, const uint8_t *utf8,
         std::vector<MergeSrc> src((size_t)G);
         for (int g = 0; g < G; ++g) {
             const ShardJob &j = mc.jobs[(size_t)g * NSLOT + slot];
-            const uint8_t *ph = (const uint8_t *)j.c->pin_out.h;
-            src[(size_t)g] = MergeSrc{(const kgpu_token8 *)ph, (const uint32_t *)(ph + j.off_first), (const uint64_t *)(ph + j.off_toff), ph + j.off_status};
+            src[(size_t)g] = j.blk.results(j.c);
         }
         // slice totals from the shards' offset tables (O(slices x G) on this thread), then one task per slice does everything else
         const uint64_t SLICE = 2048;

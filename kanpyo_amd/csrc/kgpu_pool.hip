@@ -194,7 +194,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(KGPU_POOL_
     const uint32_t lane = threadIdx.x & 63u, wave = bcast32(threadIdx.x >> 6) /* SGPR: everything per-sentence is wave-uniform */, W = blockDim.x >> 6;
     const int32_t base_root = d.da[1].base;
     // a sentence this kernel does not serve: onto the next launch's list; its token count reads 0 until a later kernel has served it (when the
-    // host left the tail of the chain out -- no recent batch needed it -- the batch is run again with it: kgpu_api.cpp)
+    // host left the tail of the chain out -- no recent batch needed it -- the batch is run again with it: kgpu_ctx.cpp)
     auto defer_s = [&](uint64_t s_) { work_defer(io, lane, s_); if (lane == 0) a.tok_count[s_] = 0; };
     uint64_t *bm = (uint64_t *)pool;
     // W == 1: the workgroup is one wavefront with a pool of its own -- a fixed LDS slice.  Nothing to share, nothing to wait for:

@@ -1,5 +1,6 @@
-// kanpyo_amd/csrc/kgpu_runtime.h -- the host runtime's own types, shared by kgpu_api.cpp (dictionary, contexts, the host-buffer
-// entry points) and kgpu_multi.cpp (the multi-device entry points).  Not part of the public ABI.
+// kanpyo_amd/csrc/kgpu_runtime.h -- the host runtime's own types and the functions its files share: kgpu_dict.cpp (dictionary),
+// kgpu_ctx.cpp (contexts, launch chain), kgpu_host.cpp (large host calls), kgpu_small.cpp (small calls), kgpu_multi.cpp (the
+// multi-device entry points).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -56,9 +57,9 @@ struct PinBuf {
 
 }  // namespace kgpu
 
-using namespace kgpu;  // (a private header of two translation units that both speak this namespace's vocabulary)
+using namespace kgpu;  // (a private header of the runtime's translation units, which all speak this namespace's vocabulary)
 
-struct Combiner;  // kgpu_api.cpp: concurrent small calls sharing a launch
+struct Combiner;  // kgpu_small.cpp: concurrent small calls sharing a launch
 
 struct kgpu_dict {
     int device = 0;
@@ -87,7 +88,7 @@ struct kgpu_dict {
     // number of contexts shares three streams; each context waits on its own completion event.
     std::vector<hipStream_t> streams;
     unsigned next_stream = 0;
-    // A second set for chains that START with the windowed kernel (batches of long sentences: kgpu_api.cpp, ctx_pick_chain): such a launch holds a thousand
+    // A second set for chains that START with the windowed kernel (batches of long sentences: kgpu_ctx.cpp, ctx_pick_chain): such a launch holds a thousand
     // single-wavefront workgroups for milliseconds and its slots empty out one by one, so the chip fills only when more of them overlap than the four launches
     // the pool kernel wants -- one stream per context, up to eight, created when the first such batch arrives (round 5: cfg 5 2.97 -> 3.96 Gchar/s).
     std::vector<hipStream_t> long_streams;
@@ -217,15 +218,49 @@ struct WorkerPool {
     void task_done(std::atomic<int> &counter); // a task's last statement
 };
 WorkerPool &workers();
-struct TestHooks { bool no_small_calls = false, legacy_host_path = false, plain_leaves = false, byte_trie = false; uint64_t chunk_bytes = 4ull << 20, chunk_sents = 16384, depth = 12, multi_chunk_sents = 0; };
+struct TestHooks { bool no_small_calls = false, plain_leaves = false, byte_trie = false; uint64_t chunk_bytes = 4ull << 20, chunk_sents = 16384, depth = 12, multi_chunk_sents = 0; };
 TestHooks test_hooks();  // test-only environment hooks, read once per process (or per call under KGPU_TEST_HOOKS_REREAD)
-void parallel_copy(void *dst, const void *src, size_t bytes);
-bool is_pinned_host(const void *p);
+bool env_flag_now(const char *name);
+
+// kgpu_dict.cpp
+unsigned planned_streams();        // shared streams per dictionary (by the hardware queues the process has)
+unsigned planned_long_streams();   // ... and streams for chains that start with the windowed kernel
+void dict_release(kgpu_dict *d);   // one reference less: the last one frees the dictionary
+
+// kgpu_ctx.cpp
 // the pooled contexts of a dictionary (one per call in flight)
 int pool_get(kgpu_dict *d, kgpu_ctx **c);
 void pool_put(kgpu_dict *d, kgpu_ctx *c);
+int ctx_h2d(kgpu_ctx *c, void *dst, const void *src, size_t bytes, const char *what);   // a batch's H2D copy on c->stream (sets h2d_queued)
 int tokenize_device_impl(kgpu_ctx *c, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n, uint64_t total_bytes,
                          kgpu_token *d_tokens, kgpu_token8 *d_tokens8, uint32_t *d_first, uint8_t *status8, uint64_t *toff8, uint64_t token_capacity,
                          uint64_t *d_tok_offsets, uint8_t *d_status, const char *who);
+
+// kgpu_host.cpp
+void parallel_copy(void *dst, const void *src, size_t bytes);
+bool is_pinned_host(const void *p);
+// A finished chunk's results in host memory: 8-byte records, (position, start) of every sentence's first token, token offsets, status bytes.
+struct MergeSrc { const kgpu_token8 *rec; const uint32_t *first; const uint64_t *toff; const uint8_t *st; };
+// One chunk of a large host call on a pooled context (kgpu_host.cpp: pipe_submit; kgpu_multi.cpp: shard_submit).  Its input goes to the device as
+// ONE block [offsets | bytes] (c->in_block, staged in c->pin_in unless it is copied from pinned memory directly); the compaction kernel writes the
+// results into the mapped block c->pin_out: records | first | token offsets | status.
+struct ChunkBlock {
+    uint64_t n = 0, total = 0, cap = 0;                    // sentences, bytes, token capacity
+    size_t in_off = 0;                                     // the offsets' share of the input block: the bytes follow
+    size_t off_first = 0, off_toff = 0, off_status = 0;    // inside pin_out
+    int prepare(kgpu_ctx *c, uint64_t n, uint64_t total, bool staged);   // the layout, and c's buffers big enough for it
+    int launch(kgpu_ctx *c, uint64_t base, const char *who) const;        // the chain over in_block (offsets start at `base`), records into pin_out
+    MergeSrc results(const kgpu_ctx *c) const;                           // where the host reads them once the chunk is synced
+};
+
+// kgpu_small.cpp
+Combiner *combiner_new();
+void combiner_delete(Combiner *c);
+// a call of at most 128 sentences / 16 KB as one launch, shared with concurrent callers: KGPU_OK / KGPU_ERR_CAPACITY served, -1 take the general path
+int tokenize_small(kgpu_dict *d, const uint8_t *utf8, const uint64_t *offsets, uint64_t n, kgpu_token *tokens, uint64_t token_capacity,
+                   uint64_t *tok_offsets, uint8_t *status, uint64_t *n_tokens);
+bool small_trace_on();                 // KGPU_SMALL_TRACE
+uint64_t cpu_ns();                     // this thread's CPU time
+extern std::atomic<uint64_t> g_sc[16];  // ... summed per phase (kgpu_debug_small_cpu; [11]: kgpu_tokenize_batch's hipSetDevice)
 
 }  // namespace kgpu

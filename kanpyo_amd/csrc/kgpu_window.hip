@@ -14,7 +14,7 @@
 //     is relaxed by streaming them from the FIFO, 64 per step.
 // LDS-resident lattices (kgpu_pool.hip) do not scale to long sentences (LDS x time grows with the square of the length: DESIGN.md
 // section 8); this kernel's LDS is independent of the length and its HBM traffic is one write per node.  It serves everything the pool
-// kernel routes away -- from ~125 characters up to any length -- and whole batches of long sentences, which start with it (kgpu_api.cpp: ctx_pick_chain);
+// kernel routes away -- from ~125 characters up to any length -- and whole batches of long sentences, which start with it (kgpu_ctx.cpp: ctx_pick_chain);
 // for short work lists it runs as a TEAM of wavefronts per sentence (below).  (Rounds 2-3 had a second long-sentence kernel that kept the whole lattice in
 // HBM and staged blocks of it in LDS for the sweep: 44 bytes per node, ~70 per byte, read back several times.  On 190-512-character
 // sentences the two were level, on 2048-character documents this one is 1.6x faster: round 4 removed the other.)
@@ -388,7 +388,7 @@ __global__ __launch_bounds__(64 * TEAM) __attribute__((amdgpu_waves_per_eu(TEAM 
         uint32_t fhead_end = 0xFFFFFFFFu;   // end position of the FIFO's head entry (0xFFFFFFFF: the FIFO is empty)
         uint32_t wT = 0, wE = 0;
         bool failed = false;
-        uint32_t why = 0;  // which limit a failed sentence ran into (Control::phase[why] counts them: KGPU_WINDOW_TRACE)
+        uint32_t why = 0;  // which limit a failed sentence ran into (Control::phase[why] counts them)
         if constexpr (TEAM == 1) if (lane == 0) { carry8(1)[0] = make_uint2(0u, d.bos_right << 1); crel(1)[0] = 0; }  // BOS: node 0, ends at 0, dp None -> 0 (lattice.rs:127,156-164)
         uint32_t wbyte0 = 0;  // first byte of the next window's characters
         uint2 pf_rec = make_uint2(0u, 0u);

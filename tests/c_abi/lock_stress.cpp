@@ -1,5 +1,5 @@
-// Stress of the small-call combiner's lock on the CPU.  tests/test_host_lock_cpu.py cuts `struct SpinLock { ... };` out of kanpyo_amd/csrc/kgpu_api.cpp as it
-// stands and passes it in with -include: T threads x N increments of a PLAIN counter (and of a two-word invariant) under the lock, also with a holder that
+// Stress of the small-call combiner's lock on the CPU (tests/test_host_lock_cpu.py builds it), the shipped kanpyo_amd/csrc/kgpu_lock.h as it
+// stands: T threads x N increments of a PLAIN counter (and of a two-word invariant) under the lock, also with a holder that
 // sleeps inside the critical section now and then.  Prints "ok ..." or "FAIL ...".  Built with -fsanitize=thread where the toolchain has it: the counter is
 // not atomic, so a lock that let two threads in is a reported race as well as a wrong sum.
 #include <atomic>
@@ -10,6 +10,8 @@
 #include <mutex>
 #include <thread>
 #include <vector>
+
+#include "../../kanpyo_amd/csrc/kgpu_lock.h"
 
 static bool run(const char *name, int threads, int iters, int nap_every) {
     alignas(64) static SpinLock lock;

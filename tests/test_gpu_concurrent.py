@@ -1,6 +1,6 @@
 """Concurrent callers of kgpu_tokenize_batch: the reference's tokenize() takes &self and is Send + Sync (src/tokenizer.rs:16), and its call
 shape is ONE sentence per call (src/bin/kanpyo.rs:106-126) -- a server calls it from many threads.  Small calls that arrive together share a
-launch (the combiner, kgpu_api.cpp); every caller must still get exactly its own sentences' records, bit-exact against the oracle."""
+launch (the combiner, kgpu_small.cpp); every caller must still get exactly its own sentences' records, bit-exact against the oracle."""
 import threading
 
 import numpy as np

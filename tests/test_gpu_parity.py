@@ -574,10 +574,10 @@ def test_compact_records_device_api(full):
     assert np.array_equal(got, exp.tokens)
 
 
-def test_large_host_call_compact_pipeline_quirks_and_fallback(libs, small, monkeypatch):
+def test_large_host_call_compact_pipeline_quirks_and_fallback(libs, small):
     """The large-call pipeline of kgpu_tokenize_batch (8-byte records into mapped host memory, expanded by worker threads):
     chains whose first token does not start at 0 (an unreachable node heads the best chain and is dropped),
-    empty results, a token beyond the 8-byte packing (the chunk falls back to 24-byte records), the legacy form of the whole call."""
+    empty results, a token beyond the 8-byte packing (the chunk falls back to 24-byte records), a call of many chunks."""
     from kanpyo_amd import Dict, Tokenizer, synth
     from kanpyo_amd.tokenizer import pack_sentences
 
@@ -602,13 +602,10 @@ def test_large_host_call_compact_pipeline_quirks_and_fallback(libs, small, monke
     tok2, orc2 = Tokenizer(d2), oracle.OracleTokenizer.from_dict(d2)
     exp2 = assert_same(tok2, orc2, ["テスト"] * 150 + [long_word + "テスト"] + ["辞書"] * 150, nthreads=2)
     assert (exp2.tokens["end"] - exp2.tokens["start"] == 5000).any()
-    # the legacy form of a large call gives the same records
+    # a large call of many chunks
     sd, tok3, orc3 = small
     sents = synth.make_corpus(sd, 9000, 61, "cfg2") + [""] + synth.make_corpus(sd, 300, 62, "cfg3")
-    a = assert_same(tok3, orc3, sents)
-    monkeypatch.setenv("KGPU_HOST_LEGACY", "1")
-    b = assert_same(tok3, orc3, sents)
-    assert np.array_equal(a.tokens, b.tokens)
+    assert_same(tok3, orc3, sents)
 
 
 def test_large_host_call_chunk_byte_counts(small):

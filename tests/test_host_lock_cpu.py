@@ -1,5 +1,5 @@
-"""The small-call combiner's lock (kgpu_api.cpp: struct SpinLock -- test-and-test-and-set with backoff, a few yields, then a futex sleep on the word) stressed on the CPU, no
-device: the struct is cut out of the source AS IT STANDS and compiled into tests/c_abi/lock_stress.cpp.  The combiner serves the reference's call shape --
+"""The small-call combiner's lock (kgpu_lock.h: struct SpinLock -- test-and-test-and-set with backoff, a few yields, then a futex sleep on the word) stressed on the CPU, no
+device: tests/c_abi/lock_stress.cpp includes the shipped header as it stands.  The combiner serves the reference's call shape --
 tokenize(&self) from many threads, one sentence per call (src/tokenizer.rs:16, src/bin/kanpyo.rs:106-126); its parity under load is
 tests/test_gpu_concurrent.py's business, this test is about the lock letting exactly one thread in."""
 import os
@@ -11,23 +11,13 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "c_abi", "lock_stress.cpp")
-API = os.path.join(ROOT, "kanpyo_amd", "csrc", "kgpu_api.cpp")
-
-
-def shipped_lock(d):
-    s = open(API).read()
-    i = s.index("struct SpinLock {")
-    j = s.index("\n};", i) + 3
-    assert "alignas(64) SpinLock mu;" in s, "the combiner no longer uses SpinLock: point this test at its lock"
-    h = os.path.join(d, "shipped_lock.h")
-    with open(h, "w") as f:
-        f.write("#include <atomic>\n#include <cstdint>\n#include <sched.h>\n#include <linux/futex.h>\n#include <sys/syscall.h>\n#include <unistd.h>\n" + s[i:j] + "\n")
-    return h
+SMALL = os.path.join(ROOT, "kanpyo_amd", "csrc", "kgpu_small.cpp")
 
 
 def build(d, flags, name):
+    assert '#include "kgpu_lock.h"' in open(SMALL).read(), "the combiner no longer uses SpinLock: point this test at its lock"
     exe = os.path.join(d, name)
-    r = subprocess.run(["g++", "-std=c++17", "-O2", "-g", "-pthread", *flags, "-include", shipped_lock(d), SRC, "-o", exe], capture_output=True, text=True)
+    r = subprocess.run(["g++", "-std=c++17", "-O2", "-g", "-pthread", *flags, SRC, "-o", exe], capture_output=True, text=True)
     return r, exe
 
 
