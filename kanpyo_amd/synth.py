@@ -369,6 +369,99 @@ def width_case(rng):
     return d, sents
 
 
+MATRIX_SHAPES = ("square", "nonsquare", "flat", "corner", "big_rows", "huge")
+MATRIX_COSTS = ("plain", "extreme", "ties")
+
+
+def _id_set(nr, hi: int, k: int) -> np.ndarray:
+    """Up to k distinct context ids in [0, hi], hi always among them (every id when the range is that small)."""
+    if hi + 1 <= k:
+        return np.arange(hi + 1)
+    return np.unique(np.concatenate([[0, hi], nr.choice(hi + 1, size=k - 2, replace=False)]))
+
+
+def matrix_case(rng, shape: str | None = None, cost: str | None = None):
+    """Like dense_case, over connection matrices that are not square and context ids that are not plain (row, col) pairs
+    (rng: random.Random).  ConnectionTable::get(right, left) = data[rows * left + right] checks the flat index only
+    (connection.rs:12-14), so a dictionary may have rows != cols, right ids >= rows, and either axis at 65 536 or more --
+    what the runtime's id ranking (kgpu_dict.cpp) and every kernel's rows-only indexing have to get right.  Shapes:
+      square     rows == cols (1, 3, 40)
+      nonsquare  5x9, 9x5, 1x40, 40x1, plain ids (ranked)
+      flat       some right_id >= rows, the flat index in range (not ranked)
+      corner     as flat, with one record whose (left, right) is the matrix's last element, paired with itself
+      big_rows   rows in 32768..65535, right ids up to 32767 (ranked)
+      huge       rows or cols >= 65536 (not ranked: the size)
+    Costs: plain (today's ranges), extreme (i16 -32768 / 32767 mixed in, words, unknown words and matrix), ties (two or
+    three distinct values everywhere).  Every draw passes the create-time bound max_left * rows + max_right < rows * cols.
+    -> (Dict, sentences, meta) with meta = {shape, cost, rows, cols, in_range, ranked} (ranked: the runtime renumbers
+    the ids, kgpu_dict.cpp: in_range and both axes below 65 536)."""
+    nr = np.random.default_rng(rng.randrange(1 << 30))
+    shape = shape or rng.choice(MATRIX_SHAPES)
+    cost = cost or rng.choice(MATRIX_COSTS)
+    if shape == "square":
+        rows = cols = rng.choice([1, 3, 40])
+        lmax, rmax = cols - 1, rows - 1
+    elif shape == "nonsquare":
+        rows, cols = rng.choice([(5, 9), (9, 5), (1, 40), (40, 1)])
+        lmax, rmax = cols - 1, rows - 1
+    elif shape in ("flat", "corner"):
+        rows, cols = rng.choice([(5, 9), (9, 5), (1, 40), (3, 7)])
+        k = rng.randint(2, cols)                         # left ids below cols - k + 1, right ids up to k rows
+        lmax = cols - k
+        rmax = k * rows - 1 - (0 if shape == "corner" or rows == 1 else rng.randint(1, rows - 1))
+    elif shape == "big_rows":
+        rows, cols = rng.choice([32768, 40000, 65535]), rng.choice([1, 2, 3])
+        lmax, rmax = cols - 1, 32767
+    elif shape == "huge":
+        rows, cols = rng.choice([(70000, 1), (65536, 2), (2, 66000)])
+        lmax, rmax = (32767, 1) if rows == 2 else (cols - 1, 32767)
+    else:
+        raise ValueError(shape)
+    assert lmax * rows + rmax < rows * cols and lmax <= 32767 and rmax <= 32767
+    in_range = rmax < rows and lmax < cols
+    meta = dict(shape=shape, cost=cost, rows=rows, cols=cols, in_range=in_range, ranked=in_range and rows < 65536 and cols < 65536)
+    lids, rids = _id_set(nr, lmax, 40), _id_set(nr, rmax, 40)
+    ties = nr.choice([-7, 0, 3, 100, 2500], size=rng.choice([2, 3]), replace=False)
+
+    def costs(n, lo, hi):
+        if cost == "ties":
+            return nr.choice(ties, size=n)
+        v = nr.integers(lo, hi, size=n)
+        if cost == "extreme":
+            v = np.where(nr.random(n) < 0.4, nr.choice([-32768, 32767], size=n), v)
+        return v
+
+    alpha = "あいうえおか"[: rng.choice([2, 3, 6])]
+    words = set()
+    for _ in range(rng.choice([20, 80, 300])):
+        words.add("".join(nr.choice(list(alpha), size=int(nr.integers(1, rng.choice([3, 5, 12]))))))
+    if shape == "corner":
+        words.add(alpha[0])
+    recs = []
+    for w in sorted(words, key=lambda x: x.encode()):
+        recs += [w] * int(nr.choice([1, 1, 2, 3, 9, rng.choice([17, 33, 70])]))
+    left, right = nr.choice(lids, len(recs)), nr.choice(rids, len(recs))
+    wcost = costs(len(recs), -2000, 9000)
+    left[nr.integers(0, len(recs))], right[nr.integers(0, len(recs))] = lmax, rmax  # both maxima are met
+    if shape == "corner":   # a one-character surface with the last element's (left, right): "cc" reads data[rows * cols - 1]
+        i = recs.index(alpha[0])
+        left[i], right[i] = lmax, rmax
+    morphs = np.stack([left, right, wcost], axis=1)
+    cat = np.zeros(65536, dtype=np.uint8)
+    for ch in alpha:
+        cat[ord(ch)] = 1
+    unk = {0: (1, 1), 1: (2, rng.choice([1, 3]))}
+    um = [(int(nr.choice(lids)), int(nr.choice(rids)), int(c)) for c in costs(1 + unk[1][1], 1000, 9000)]
+    conn = costs(rows * cols, -3000, 3000)
+    d = Dict.from_parts(recs, morphs, rows, cols, conn, ["DEFAULT", "H"], cat,
+                        np.array([0, rng.choice([0, 1])], dtype=np.uint8), np.array([1, rng.choice([0, 1])], dtype=np.uint8), unk, um)
+    sents = ["".join(nr.choice(list(alpha + "xy"), size=int(nr.integers(1, rng.choice([8, 40, 120])))))
+             for _ in range(rng.choice([1, 7, 128, 129, 700, 3000]))]
+    if rng.random() < 0.3:   # a few long ones: the windowed kernel, wide (streamed) buckets
+        sents += ["".join(nr.choice(list(alpha + "x"), size=int(nr.integers(1500, 4000)))) for _ in range(rng.choice([1, 3]))]
+    return d, sents, meta
+
+
 EDGE_SENTENCES = ["", "あ", "ア" * 700, "a" * 300, "𠮷野家で𩸽", "すもももももももものうち", "　　", "1234567890" * 40, "。" * 65]
 
 

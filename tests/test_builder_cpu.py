@@ -138,3 +138,36 @@ def test_build_from_euc_jp_directory(tmp_path):
 def test_ragged_csv_is_rejected():
     with pytest.raises(builder.BuilderError):  # csv::Reader with flexible = false (record.rs:27-31)
         builder.parse_csv("あ,1,1,10,x,y\nい,1,1,10,x\n")
+
+
+def test_matrix_def_non_square_layout():
+    """matrix.def lines are "right left cost" under a "rows cols" header; the value lands at data[left * rows + right]
+    (matrix_def.rs:52-61), the element ConnectionTable::get(right, left) reads (connection.rs:12-14)."""
+    text = "2 3\n" + "".join(f"{r} {c} {10 * r + c}\n" for c in (2, 0, 1) for r in (1, 0))
+    assert builder.parse_matrix_def(text) == (2, 3, [0, 10, 1, 11, 2, 12])
+    assert builder.parse_matrix_def("3 2\n2 1 -7\n") == (3, 2, [0, 0, 0, 0, 0, -7])
+    with pytest.raises(builder.BuilderError):
+        builder.parse_matrix_def("2 3\n2 0 1\n")   # right index 2 >= rows 2
+    with pytest.raises(builder.BuilderError):
+        builder.parse_matrix_def("3 2\n0 2 1\n")   # left index 2 >= cols 2
+
+
+def test_build_with_a_non_square_matrix(tmp_path):
+    """A MeCab directory with a 3x2 matrix.def (rows > cols) whose layout decides the token: あ has records (left 1,
+    right 0) = id 1 and (1, 2) = id 2, い = (1, 0) = id 3.  get(r, l) = data[3 l + r]: id 1 -> い reads (0, 1) = 0,
+    id 2 -> い reads (2, 1) = -100, so id 2 wins; with the values laid out transposed (data[2 r + l]) id 1 -> い would
+    read the -1000 of (1, 1) and win instead."""
+    from oracle import oracle, pyref
+
+    lex = "あ,1,0,0,x\nあ,1,2,0,y\nい,1,0,0,z\n"
+    unk = "DEFAULT,0,0,5000,u\nHIRAGANA,1,1,5000,u\n"
+    matrix = "3 2\n2 0 -500\n1 1 -1000\n2 1 -100\n"
+    for name, text in (("a.csv", lex), ("matrix.def", matrix), ("char.def", CHAR_DEF), ("unk.def", unk)):
+        (tmp_path / name).write_bytes(text.encode("utf-8"))
+    df = builder.build_from_dir(str(tmp_path), encoding="utf-8")
+    assert df.dict.conn_shape == (3, 2)
+    toks, _ = oracle.OracleTokenizer.from_dict(df.dict).tokenize("あい")
+    got = [tuple(int(x) for x in t) for t in toks.tolist()]
+    assert got == [(2, 1, 0, 0, 1, 3), (3, 1, 3, 1, 2, 3), (0, 0, 6, 2, 5, 0)]
+    assert got == pyref.tokenize(pyref.PyDict(*[getattr(df.dict, f) for f in (
+        "index_dict", "connection_dict", "morph_dict", "unk_dict", "char_category", "invoke_list", "group_list")]), "あい")

@@ -85,6 +85,27 @@ def test_keys_of_every_utf8_width_random_chains(libs, seed, monkeypatch):
     assert total > 0
 
 
+@pytest.mark.parametrize("seed", [515, 2718])
+def test_matrix_shapes_random_chains(libs, seed, monkeypatch):
+    """Twelve synth.matrix_case dictionaries per seed (non-square matrices both ways, right ids >= rows, an axis of 65 536 or
+    more, i16 extreme and tied costs) under launch chains drawn from the same seed: the ranked and the unranked id spaces
+    through every kernel's rows-only indexing (connection.rs:12-14)."""
+    from kanpyo_amd import Tokenizer, synth
+
+    _, oracle = libs
+    rng = random.Random(seed)
+    seen = set()
+    for k in range(12):
+        pool, window_kib = rng.choice(POOLS), rng.choice(WINDOWS)
+        monkeypatch.setenv("KGPU_POOL", pool)
+        monkeypatch.setenv("KGPU_WINDOW", window_kib)
+        d, sents, meta = synth.matrix_case(rng)
+        seen.add((meta["ranked"], (meta["rows"] > meta["cols"]) - (meta["rows"] < meta["cols"])))
+        tok, orc = Tokenizer(d), oracle.OracleTokenizer.from_dict(d)
+        _same(tok, orc, sents, f"seed {seed} round {k} pool={pool} window={window_kib} {meta}")
+    assert {r for r, _ in seen} == {True, False} and {1, -1} <= {o for _, o in seen}, seen
+
+
 @pytest.mark.parametrize("seed,nkeys", [(9001, 20000), (4242, 6000), (777, 60000)])
 def test_mixed_corpora_random_chains(libs, seed, nkeys, monkeypatch):
     """IPADIC-shaped dictionaries of random size, shuffled mixes of cfg 2 / cfg 3 / cfg 5 text and edge sentences, three

@@ -146,3 +146,40 @@ def test_npz_cache_round_trip_and_stale_format(tmp_path, fixture_dict):
     (tmp_path / "junk.npz").write_bytes(b"not a zip archive")
     with pytest.raises(ValueError, match="stale dictionary cache"):
         Dict.load_npz(tmp_path / "junk.npz")
+
+
+@pytest.mark.parametrize("rows,cols", [(2, 5), (5, 2), (1, 7), (7, 1)])
+def test_create_time_bound_on_non_square_matrices(rows, cols):
+    """The create-time check is the flat one, max_left * rows + max_right < rows * cols (connection.rs:12-14 checks
+    nothing per axis): the last element is accepted, one past it is not, whether the id that reaches it is a known or an
+    unknown word's; a right id >= rows is fine while the flat index stays inside."""
+    ok = (_lib.KGPU_OK, _lib.KGPU_ERR_NO_DEVICE)
+    p = fixture_dict_parts()
+    p["conn_rows"], p["conn_cols"], p["conn_data"] = rows, cols, list(range(rows * cols))
+    p["morphs"], p["unk_morphs"] = [[0, 0, 1000], [0, 0, 1200], [0, 0, 1100]], [[0, 0, 5000], [0, 0, 5000]]
+
+    def rc(morph, unk=False):
+        q = dict(p)
+        if unk:
+            q["unk_morphs"] = [[0, 0, 5000], morph]
+        else:
+            q["morphs"] = [[0, 0, 1000], morph, [0, 0, 1100]]
+        return _create(Dict.from_parts(**q))
+
+    for unk in (False, True):
+        code, msg = rc([cols - 1, rows - 1, 0], unk)         # flat index rows * cols - 1
+        assert code in ok, (unk, msg)
+        code, msg = rc([cols - 1, rows, 0], unk)             # flat index rows * cols
+        assert code == _lib.KGPU_ERR_BAD_DICT and "does not cover" in msg, (unk, msg)
+        code, msg = rc([0, rows * cols, 0], unk)             # right id alone past the end
+        assert code == _lib.KGPU_ERR_BAD_DICT, (unk, msg)
+        if cols > 1:
+            code, msg = rc([0, rows, 0], unk)                # right >= rows, flat index rows < rows * cols
+            assert code in ok, (unk, msg)
+            code, msg = rc([cols - 2, 2 * rows - 1, 0], unk)  # right >= rows reaching exactly the last element
+            assert code in ok, (unk, msg)
+            code, msg = rc([cols - 2, 2 * rows, 0], unk)
+            assert code == _lib.KGPU_ERR_BAD_DICT, (unk, msg)
+        if rows > 1:
+            code, msg = rc([cols, 0, 0], unk)                # left == cols: flat index rows * cols
+            assert code == _lib.KGPU_ERR_BAD_DICT, (unk, msg)

@@ -1,0 +1,106 @@
+"""Known answers for connection matrices that are not square and costs at the i16 extremes, in both CPU restatements
+(oracle/kanpyo_oracle.c and oracle/pyref.py).  ConnectionTable::get(right, left) = data[rows * left + right]
+(connection.rs:12-14); the Viterbi total is (dp + cost + matrix).min(INF) with a strict '<' against INF, and the
+backtrace stops at the first node without a predecessor (lattice.rs:116-150).  The same dictionaries run on the GPU in
+tests/test_gpu_matrix.py.  CPU only."""
+import numpy as np
+import pytest
+
+from conftest import fixture_dict_parts
+from kanpyo_amd.dict import Dict
+from oracle import oracle, pyref
+
+INF = 1 << 30
+A, I = "あ", "い"
+
+
+def saturation_parts():
+    """The fixture with no unknown hiragana nodes, a 2x3 matrix and two words at the i16 extremes:
+    あ = (left 1, right 1, 32767), い = (left 2, right 1, -32768).  get(r, l) = data[2 l + r]:
+    BOS -> あ data[2] = 0; あ -> あ data[3] = 32767; あ / い -> い data[5] = -32768; あ / い -> EOS data[1] = 0."""
+    p = fixture_dict_parts()
+    p["invoke_list"] = np.array([0, 1, 0], dtype=np.uint8)
+    p["group_list"] = np.array([0, 1, 0], dtype=np.uint8)
+    p["sorted_keywords"] = [A, I]
+    p["morphs"] = [[1, 1, 32767], [2, 1, -32768]]
+    p["conn_rows"], p["conn_cols"], p["conn_data"] = 2, 3, [0, 0, 0, 32767, 0, -32768]
+    return p
+
+
+def transposed_parts():
+    """A 3x2 matrix (rows > cols) where the layout decides the token: あ has two records, (1, 0) = id 1 and (1, 2) = id 2,
+    い = (1, 0) = id 3.  get(r, l) = data[3 l + r]: id 1 -> い reads data[3] = 0, id 2 -> い reads data[5] = -100, so id 2
+    wins.  Indexed by cols instead (data[2 l + r]) the two read data[2] = -500 and data[4] = 0 and id 1 would win."""
+    p = fixture_dict_parts()
+    p["invoke_list"] = np.array([0, 1, 0], dtype=np.uint8)
+    p["sorted_keywords"] = [A, A, I]
+    p["morphs"] = [[1, 0, 0], [1, 2, 0], [1, 0, 0]]
+    p["conn_rows"], p["conn_cols"], p["conn_data"] = 3, 2, [0, 0, -500, 0, 0, -100]
+    return p
+
+
+def saturation_expected(n, m):
+    """n あ then m い, derived by hand.  dp(あ_k) = 32767 + (k - 1) * 65534 = 65534 k - 32767, below INF up to k = 16385
+    (INF - 1) and saturated from k = 16386 on: INF, no predecessor (the total is not < INF).  い_1 after a saturated あ:
+    INF - 65536 < INF, so it takes あ_n as predecessor and the path is alive again -- but the backtrace from EOS stops at
+    あ_n, which has none: only the い and EOS are returned.  Without い, EOS itself stays at INF: no path at all.
+    -> (record count, first record)"""
+    sat = n >= 16386
+    if sat and m == 0:
+        return 0, None
+    if sat:
+        return m + 1, (2, 1, 3 * n, n, n + 1, 3)
+    return n + m + 1, ((1, 1, 0, 0, 1, 3) if n else (2, 1, 0, 0, 1, 3))
+
+
+def _both(d, text):
+    o = oracle.OracleTokenizer.from_dict(d)
+    p = pyref.PyDict(d.index_dict, d.connection_dict, d.morph_dict, d.unk_dict, d.char_category, d.invoke_list, d.group_list)
+    got, _ = o.tokenize(text)
+    got = [tuple(int(x) for x in t) for t in got]
+    assert got == pyref.tokenize(p, text), text[:8]
+    return got
+
+
+def test_saturation_boundary_is_where_the_hand_derivation_puts_it():
+    assert 65534 * 16385 - 32767 == INF - 1 and 65534 * 16386 - 32767 >= INF
+
+
+@pytest.mark.parametrize("n", [16383, 16384, 16385, 16386, 17000])
+@pytest.mark.parametrize("m", [0, 3, 5])
+def test_saturated_dp_and_truncated_backtrace(n, m):
+    d = Dict.from_parts(**saturation_parts())
+    got = _both(d, A * n + I * m)
+    count, first = saturation_expected(n, m)
+    assert len(got) == count
+    if count:
+        assert got[0] == first
+        assert got[-1] == (0, 0, 3 * (n + m), n + m, n + m + 3, 0)   # EOS
+        if m:
+            assert all(t[0] == 2 for t in got[-m - 1 : -1])
+        assert [t[3] for t in got[:-1]] == list(range(n + m - count + 1, n + m))   # one node per character, in order
+
+
+def test_saturation_short_sentences():
+    """The same dictionary far from saturation: every step is exact i16 arithmetic."""
+    d = Dict.from_parts(**saturation_parts())
+    assert _both(d, A + I) == [(1, 1, 0, 0, 1, 3), (2, 1, 3, 1, 2, 3), (0, 0, 6, 2, 5, 0)]
+    assert _both(d, I * 4) == [(2, 1, 3 * k, k, k + 1, 3) for k in range(4)] + [(0, 0, 12, 4, 7, 0)]
+    assert _both(d, "") == [(0, 0, 0, 0, 3, 0)]
+
+
+def test_rows_not_cols_decides_the_token():
+    d = Dict.from_parts(**transposed_parts())
+    assert _both(d, A + I) == [(2, 1, 0, 0, 1, 3), (3, 1, 3, 1, 2, 3), (0, 0, 6, 2, 5, 0)]
+    assert _both(d, A + I + A + I) == [(2, 1, 0, 0, 1, 3), (3, 1, 3, 1, 2, 3), (2, 1, 6, 2, 3, 3), (3, 1, 9, 3, 4, 3), (0, 0, 12, 4, 7, 0)]
+    # あ at the end: its next node is EOS, get(right, 0) = data[0] for id 1 and data[2] = -500 for id 2
+    assert _both(d, A)[0] == (2, 1, 0, 0, 1, 3)
+
+
+def test_flat_index_beyond_rows_is_the_reference_behaviour():
+    """right_id >= rows with rows * left + right inside the matrix: no panic, the flat element is read (connection.rs:13)."""
+    p = transposed_parts()
+    p["morphs"] = [[0, 4, 0], [0, 2, 0], [0, 0, 0]]   # id 1: right 4 >= rows 3; every left is 0, so the flat index stays below 6
+    p["conn_data"] = [0, 0, 0, 0, -300, -200]
+    # id 1 -> い reads data[4] = -300, id 2 -> い reads data[2] = 0: id 1 wins; EOS after い: data[0]
+    assert _both(Dict.from_parts(**p), A + I) == [(1, 1, 0, 0, 1, 3), (3, 1, 3, 1, 2, 3), (0, 0, 6, 2, 5, 0)]

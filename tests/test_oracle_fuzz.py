@@ -96,3 +96,31 @@ def test_pyref_and_c_oracle_agree_on_keys_of_every_utf8_width(seed):
             assert [tuple(int(x) for x in t) for t in got] == exp, (seed, s)
             total += 1
     assert total >= 200
+
+
+@pytest.mark.parametrize("seed", [21, 22, 23])
+def test_pyref_and_c_oracle_agree_on_non_square_matrices(seed):
+    """synth.matrix_case (rows != cols both ways, right ids >= rows with the flat index in range, an axis of 65 536 or more, i16
+    extreme and tied costs): ConnectionTable::get(right, left) = data[rows * left + right] (connection.rs:12-14) in both CPU
+    restatements.  The sentences stay short (|dp| far below 2^31: the C oracle's i32 sum must not overflow)."""
+    import random
+
+    from kanpyo_amd import synth
+
+    rng = random.Random(seed)
+    total, seen = 0, set()
+    for _ in range(40):
+        d, sents, meta = synth.matrix_case(rng)
+        seen.add((meta["ranked"], (meta["rows"] > meta["cols"]) - (meta["rows"] < meta["cols"])))
+        parts = (d.index_dict, d.connection_dict, d.morph_dict, d.unk_dict, d.char_category, d.invoke_list, d.group_list)
+        o = oracle.OracleTokenizer(*parts)
+        p = pyref.PyDict(*parts)
+        assert (p.row, p.col) == (meta["rows"], meta["cols"])
+        for s in sents[:30]:
+            s = s[:24]
+            exp = pyref.tokenize(p, s)
+            got, _ctr = o.tokenize(s)
+            assert [tuple(int(x) for x in t) for t in got] == exp, (seed, meta, s)
+            total += 1
+    assert total >= 680  # x 3 seeds > 2000 sentences
+    assert {r for r, _ in seen} == {True, False} and {1, -1} <= {o for _, o in seen}, seen

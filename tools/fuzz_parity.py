@@ -18,7 +18,7 @@ os.environ["KGPU_TEST_HOOKS_REREAD"] = "1"
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
 rng = random.Random(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
 t_end = time.time() + budget
-rounds = sentences = 0
+rounds = sentences = matrix_rounds = 0
 while time.time() < t_end:
     nkeys = rng.choice([6000, 12000, 20000, 60000])
     pool = rng.choice(["0", "8:2:64", "16:4:32", "40:4:32", "40:4:32", "40:8:20", "80:8:20", "80:10:64", "160:16:64", "80:8:20,160:4:64", "24:3:48", "auto", "auto", "auto"])
@@ -31,10 +31,18 @@ while time.time() < t_end:
     os.environ["KGPU_WINDOW_TEAM"] = rng.choice(["-1", "-1", "0", "2", "2"])     # the two-wavefronts-per-sentence form of window-first chains: by the load / never / always
     os.environ["KGPU_WINDOW_FIRST"] = rng.choice(["1024", "1024", "0", "64", "300"])  # average bytes per sentence from which a chain starts with the windowed kernel
     os.environ["KGPU_BYTE_TRIE"] = "1" if rng.random() < 0.15 else "0"  # (read at dictionary creation: KGPU_TEST_HOOKS_REREAD below)
-    if rng.random() < 0.4:  # a dense little dictionary: wide buckets, many targets -- or keys of every UTF-8 width
-        dd, mix = synth.dense_case(rng) if rng.random() < 0.6 else synth.width_case(rng)
+    if rng.random() < 0.4:  # a dense little dictionary: wide buckets, many targets -- or keys of every UTF-8 width, or a matrix that is not square
+        kind = rng.random()
+        if kind < 0.45:
+            dd, mix = synth.dense_case(rng)
+        elif kind < 0.7:
+            dd, mix = synth.width_case(rng)
+        else:
+            dd, mix, meta = synth.matrix_case(rng)
+            matrix_rounds += 1
+            print(f"    matrix_case {meta['shape']} {meta['rows']}x{meta['cols']} costs={meta['cost']} ranked={meta['ranked']}", flush=True)
         tok, orc = Tokenizer(dd), oracle.OracleTokenizer.from_dict(dd)
-        print(f"[{time.time() - (t_end - budget):6.1f}s] dense / width dictionary byte_trie={os.environ['KGPU_BYTE_TRIE']} pool={pool} window={window_kib} team={os.environ['KGPU_WINDOW_TEAM']} first={os.environ['KGPU_WINDOW_FIRST']} n={len(mix)}", flush=True)
+        print(f"[{time.time() - (t_end - budget):6.1f}s] dense / width / matrix dictionary byte_trie={os.environ['KGPU_BYTE_TRIE']} pool={pool} window={window_kib} team={os.environ['KGPU_WINDOW_TEAM']} first={os.environ['KGPU_WINDOW_FIRST']} n={len(mix)}", flush=True)
         utf8, offs = pack_sentences(mix)
         exp = orc.tokenize_batch(utf8, offs, 16)
         got_t, got_off, status = tok.tokenize_packed(utf8, offs)
@@ -60,4 +68,4 @@ while time.time() < t_end:
             sys.exit(1)
         rounds += 1
         sentences += len(mix)
-print(f"fuzz ok: {rounds} batches, {sentences} sentences, bit-exact")
+print(f"fuzz ok: {rounds} batches ({matrix_rounds} matrix_case), {sentences} sentences, bit-exact")
