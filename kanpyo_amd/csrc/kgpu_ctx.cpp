@@ -1,8 +1,8 @@
 // kanpyo_amd/csrc/kgpu_ctx.cpp -- the contexts of include/kanpyo_gpu.h and the launch chain behind them.
 //
-// Owns: context create / destroy, the lease of a dictionary's pooled contexts, the choice of chain and stream per batch
-// (ctx_pick_chain), the one way a batch's host-to-device copy is queued (ctx_h2d), the launch sequence (tokenize -> scan ->
-// compact) and its reruns in kgpu_ctx_sync, the profiling / ablation / plan getters, and the lattice dump.
+// Owns: context create / destroy, the lease of a dictionary's pooled contexts, the stream of a batch (ctx_pick_stream), the one
+// way a batch's host-to-device copy is queued (ctx_h2d), running a batch's chain (kgpu_chain.cpp decides it) with the scan and
+// compaction behind it, the reruns in kgpu_ctx_sync, the profiling / ablation / plan getters, and the lattice dump.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -54,16 +54,24 @@ extern "C" int kgpu_ctx_create(kgpu_dict *d, void *hip_stream, kgpu_ctx **out) {
         kgpu_ctx_destroy(c);
         return KGPU_ERR_HIP;
     }
-    c->plan = default_launch_plan(d->device);
+    hipDeviceProp_t p;
+    const int cus = hipGetDeviceProperties(&p, d->device) == hipSuccess ? p.multiProcessorCount : 256;
+    c->plan = make_launch_plan(cus, Occupancy{pool_workgroups_per_cu, window_workgroups_per_cu, window_team_workgroups_per_cu});
     *out = c;
     return KGPU_OK;
+}
+
+// The pending batch is over (completed or given up): the context is free, its share of the dictionary's long sentences in flight is returned.
+static void ctx_retire(kgpu_ctx *c) {
+    c->pending = false;
+    if (c->steer.counted_long) { c->dict->steer.long_sentences_in_flight.fetch_sub(c->steer.counted_long, std::memory_order_relaxed); c->steer.counted_long = 0; }
 }
 
 extern "C" void kgpu_ctx_destroy(kgpu_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->dict->device);
     if (c->pending && c->done_ev) (void)hipEventSynchronize(c->done_ev);
-    if (c->counted_long) { c->dict->long_sentences_in_flight.fetch_sub(c->counted_long, std::memory_order_relaxed); c->counted_long = 0; }
+    ctx_retire(c);
     if (c->done_ev) (void)hipEventDestroy(c->done_ev);
     if (c->switch_ev) (void)hipEventDestroy(c->switch_ev);
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
@@ -88,27 +96,16 @@ static int next_event(kgpu_ctx *c, hipEvent_t *ev) {
     return KGPU_OK;
 }
 
-// Which chain the next batch gets, and on which stream.  A batch of long sentences (by its average length: the host knows n and the bytes, not the
-// lengths) starts with the windowed kernel -- the pool launch in front of it would only route: a thousand 40 KB workgroups that each look at four sentences
-// and pass them on, waiting for LDS on a chip full of single-wavefront workgroups (cfg 5, 8 in flight: 2.97 -> 3.40 Gchar/s without it) -- and runs on a stream
-// of the long set, one per context, so that eight such launches overlap instead of four (-> 3.96; both: profiles/experiments/r05_long_chains.txt).
+// The stream of the next batch.  A chain that starts with the windowed kernel (kgpu_chain.cpp: starts_with_window) runs on a stream of the long set,
+// one per context, so that eight such launches overlap instead of four (cfg 5, 8 in flight: 3.40 -> 3.96 Gchar/s; profiles/experiments/r05_long_chains.txt).
 // The context's previous batch is complete here (kgpu_ctx_sync), so switching streams needs no ordering for the context's own buffers; whatever the
 // host-buffer paths queued on the old stream for THIS batch (their H2D copy) is ordered in front by an event.
-static int ctx_pick_chain(kgpu_ctx *c, uint64_t n, uint64_t total_bytes, bool dump) {
-    const unsigned lim = c->plan.window_first_bytes;   // (KGPU_WINDOW_FIRST, read with the launch plan when the context is created)
-    c->window_first = lim && n && c->plan.n_pools && c->plan.window_lds_bytes && !dump && c->stop_after == 0 && !c->no_window && total_bytes >= (uint64_t)lim * n;
-    // Dense lattices: when four reservations of the learnt size (LDS bytes per input byte, steered by the redo rate: kgpu_ctx_sync) do not fit the pool, the
-    // batch's pool workgroups get THREE wavefronts -- a fourth sentence would only wait for pages (the dense-lattice dictionary, natural density N/C = 8.6:
-    // 57.8 -> 62.2 M sentences/s; cfg 2's reservations fit and it stays at four: three would cost it 21 %; profiles/experiments/r06_tile_sweep.txt)
-    {
-        const uint64_t est1 = n ? ((total_bytes / n) * c->dict->est_q8.load(std::memory_order_relaxed) >> 8) + 768u : 0u;
-        c->roomy = n && c->plan.n_pools && c->plan.pool_limit_auto && c->plan.pool_waves[0] == 4 && 4u * est1 * 100u > (uint64_t)c->plan.pool_bytes[0] * 92u;
-    }
+static int ctx_pick_stream(kgpu_ctx *c, const Batch &b) {
     if (c->own_stream) { c->h2d_queued = false; return KGPU_OK; }
     hipStream_t want = c->short_stream;
     // ... and so does a pool-first chain whose last batch sent an eighth or more of its sentences on to the windowed kernel: its launches behind the pool
     // kernel are the long ones (cfg 3 in batches of 4096: 15.4 -> 17.5 M sentences/s on eight streams; a pool-ONLY chain loses there: cfg 2 101 -> 86)
-    if ((c->window_first || c->long_share) && planned_long_streams()) {
+    if ((starts_with_window(c->plan, b) || c->steer.long_share) && planned_long_streams()) {
         if (!c->long_stream) {
             kgpu_dict *d = c->dict;
             std::lock_guard<std::mutex> g(d->pool_mu);
@@ -134,78 +131,42 @@ static int ctx_pick_chain(kgpu_ctx *c, uint64_t n, uint64_t total_bytes, bool du
     return KGPU_OK;
 }
 
-static int enqueue(kgpu_ctx *c, const BatchArgs &a) {
+// The pending chain (c->chain) on c->stream, then scan + compaction.  ev: timing events {behind the first launch, behind the chain, behind the scan} or null.
+static int run_chain(kgpu_ctx *c, const BatchArgs &a, const hipEvent_t *ev, const char *what) {
+    const Chain &ch = c->chain;
+    if (ev && !ch.event_behind_first) HIPCHECK(hipEventRecord(ev[0], c->stream));
+    for (int k = 0; k < ch.n; ++k) {
+        hipError_t e = (hipError_t)launch_step(c->dict->view, a, ch.steps[k], c->stop_after, c->stream);
+        if (e == hipSuccess && ev && k == 0 && ch.event_behind_first) e = hipEventRecord(ev[0], c->stream);
+        if (e != hipSuccess) { set_error("%s launch: %s", what, hipGetErrorString(e)); return KGPU_ERR_HIP; }
+    }
+    // (the two small kernels behind a pool-only chain on a partner stream of each shared stream, so that the shared stream goes on with the next pool launch at once:
+    // measured with 16 hardware queues, cfg 2 100.5 -> 72.9 M sentences/s -- whatever lets a fifth pool launch start early loses, profiles/experiments/r05_long_chains.txt)
+    if (ev) HIPCHECK(hipEventRecord(ev[1], c->stream));
+    c->h_ctl->pack_overflow = 0;  // set by the compaction's workgroups in the host copy directly; this context's previous batch has been synced
+    hipError_t e = (hipError_t)launch_scan_compact(a, c->h_ctl_dev, c->stream, ch.small_scan);
+    if (e != hipSuccess) { set_error("scan/compact launch: %s", hipGetErrorString(e)); return KGPU_ERR_HIP; }
+    if (ev) HIPCHECK(hipEventRecord(ev[2], c->stream));
+    HIPCHECK(hipEventRecord(c->done_ev, c->stream));
+    c->ctl_dirty = false;
+    c->pending = true;
+    return KGPU_OK;
+}
+
+static int enqueue(kgpu_ctx *c, const BatchArgs &a, const Batch &b) {
     // The Control block is zero here: the previous launch's scan kernel left it so.
     if (c->ctl_dirty) HIPCHECK(hipMemsetAsync(c->d_ctl, 0, sizeof(Control), c->stream));
     c->ctl_dirty = true;  // until this enqueue is through
-    hipEvent_t e0 = nullptr, ef = nullptr, e1 = nullptr, e2 = nullptr;
+    hipEvent_t ev[4] = {};
     int rc;
     const bool timed = c->profiling && (c->launch_seq++ % c->event_every) == 0;
     if (timed) {
-        if ((rc = next_event(c, &e0)) || (rc = next_event(c, &ef)) || (rc = next_event(c, &e1)) || (rc = next_event(c, &e2))) return rc;
-        HIPCHECK(hipEventRecord(e0, c->stream));
+        for (hipEvent_t &e : ev) if ((rc = next_event(c, &e))) return rc;
+        HIPCHECK(hipEventRecord(ev[0], c->stream));
     }
-    if (a.n) {
-        const int pools_now = (c->window_first && !c->no_window) ? 0 : c->dict->big_pool_batches.load(std::memory_order_relaxed) > 0 ? c->plan.n_pools : std::min(c->plan.n_pools, 1);
-        c->last_pools = pools_now;
-        // The windowed kernel is in the chain while recent batches left the pools sentences (starts armed) -- an empty launch of a few thousand
-        // workgroups behind a chip full of long-running wavefronts is not free -- or always, without a pool kernel in front of it.
-        const bool window_now = c->plan.window_lds_bytes && !c->no_window && !a.dump_lattice && c->stop_after == 0 &&
-                                (pools_now == 0 || c->dict->window_batches.load(std::memory_order_relaxed) > 0);
-        c->last_window = window_now;
-        // The general kernel closes the chain when nothing else is in it, in ablation / dump runs, and while recent batches left it sentences;
-        // otherwise nothing does -- a sentence that needed more shows in the last work list's count, and kgpu_ctx_sync launches what is missing
-        // over that list.
-        c->last_tail = (pools_now == 0 && !window_now) || c->stop_after != 0 || a.dump_lattice || c->no_window ||
-                       c->dict->tail_batches.load(std::memory_order_relaxed) > 0;
-        // Two wavefronts per sentence (the windowed kernel's team form) when the list is short against the chip: the sentences of this batch AND of the
-        // window-first batches in flight lately are at most twice the form's resident workgroups -- a lone batch of 1000 documents fills a quarter of the
-        // single-wavefront slots and each document is one wavefront's chain; with four or more such batches in flight the ordinary form is the better use of the LDS.
-        const int team_mode = c->plan.window_team_mode;   // KGPU_WINDOW_TEAM: 0 never, 2 whenever possible, default by the load
-        bool team_now = false;
-        if (pools_now == 0 && window_now && c->plan.window_team_workgroups > 0 && team_mode != 0) {
-            if (!c->counted_long) { c->counted_long = (int)std::min<uint64_t>(a.n, 1u << 30); c->dict->long_sentences_in_flight.fetch_add(c->counted_long, std::memory_order_relaxed); }
-            const int cur = c->dict->long_sentences_in_flight.load(std::memory_order_relaxed), old = c->dict->long_peak.load(std::memory_order_relaxed);
-            const int peak = std::max(cur, old - old / 8);
-            c->dict->long_peak.store(peak, std::memory_order_relaxed);
-            // measured on cfg 5 (1000 documents per batch, Mchar/s, ordinary / team form): 1 in flight 1084 / 1495, 2: 1957 / 2153, 4: 3376 / 2372, 8: 4145 / 2405
-            team_now = team_mode == 2 || peak <= 2 * c->plan.window_team_workgroups;
-        }
-        c->last_team = team_now;
-        // The pool's SHAPE for this batch.  A pool-only chain keeps four wavefronts on 40 KB (cfg 2 100.9 M sentences/s; two on 20 KB: 98.4-99.3, the dense dictionary
-        // 53.7 -> 50.8).  A chain that holds a windowed launch shares the chip with thousands of 10 KB single-wavefront workgroups that run for a millisecond: a
-        // workgroup of two wavefronts on 20 KB finds its LDS and its wavefront slots far sooner than one of four on 40 KB -- cfg 3 at 4096 per batch 18.5 -> 21.9 M
-        // sentences/s, at 65 536 23.9 -> 25.3 -- and in small batches (one sentence per wavefront slot: the pool launch lasts as long as its longest sentence) it
-        // routes a little earlier (56 of its 64 pages of 312 B instead of all).  profiles/experiments/r05_long_chains.txt, sections 5 and 8.
-        LaunchPlan pl = c->plan;
-        if (pools_now > 0 && c->long_share && pl.pool_limit_auto && pl.alt_pool_workgroups > 0) {
-            pl.pool_bytes[0] = pl.alt_pool_bytes; pl.pool_waves[0] = pl.alt_pool_waves; pl.pool_workgroups[0] = pl.alt_pool_workgroups;
-            pl.pool_max_pages[0] = a.n <= 4u * 4096u ? 56u : 64u;
-        }
-        else if (pools_now > 0 && c->roomy) pl.pool_waves[0] = 3;   // (the same pools, the same grid: a workgroup's tickets hand its share out to three wavefronts)
-        // The windowed launch behind the pools: as many workgroups as the last batch's share of routed sentences suggests (+ a quarter), not the chip's 4096 -- the
-        // list is strided, so an estimate that is too small only makes a workgroup take a second sentence (the context's first batch gets the full grid).
-        int window_grid = 0;
-        if (pools_now > 0 && window_now && c->rt.batches > 0)
-            window_grid = (int)std::min<uint64_t>(1u << 20, std::max<uint64_t>(256, ((a.n * c->win_share_q8) >> 8) * 5 / 4 + 64));
-        hipError_t e = (hipError_t)launch_tokenize(c->dict->view, a, pl, pools_now, c->stop_after, c->stream, ef, window_now, c->last_tail, team_now, window_grid);
-        if (e != hipSuccess) { set_error("k_tokenize launch: %s", hipGetErrorString(e)); return KGPU_ERR_HIP; }
-    } else if (timed) HIPCHECK(hipEventRecord(ef, c->stream));
-    // (the two small kernels behind a pool-only chain on a partner stream of each shared stream, so that the shared stream goes on with the next pool launch at once:
-    // measured with 16 hardware queues, cfg 2 100.5 -> 72.9 M sentences/s -- whatever lets a fifth pool launch start early loses, profiles/experiments/r05_long_chains.txt)
-    if (timed) HIPCHECK(hipEventRecord(e1, c->stream));
-    {
-        c->h_ctl->pack_overflow = 0;  // set by the compaction's workgroups in the host copy directly; this context's previous batch has been synced
-        const bool small_wgs = a.n && c->last_window && (c->last_pools == 0 || c->long_share);   // (behind chains with a windowed launch)
-        hipError_t e = (hipError_t)launch_scan_compact(a, c->h_ctl_dev, c->stream, small_wgs);
-        if (e != hipSuccess) { set_error("scan/compact launch: %s", hipGetErrorString(e)); return KGPU_ERR_HIP; }
-    }
-    if (timed) HIPCHECK(hipEventRecord(e2, c->stream));
-    HIPCHECK(hipEventRecord(c->done_ev, c->stream));
-    c->ctl_dirty = false;
+    c->chain = build_chain(c->plan, b, c->dict->steer, c->steer);
     c->last = a;
-    c->pending = true;
-    return KGPU_OK;
+    return run_chain(c, a, timed ? ev + 1 : nullptr, "k_tokenize");
 }
 
 int kgpu::tokenize_device_impl(kgpu_ctx *c, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n, uint64_t total_bytes,
@@ -221,7 +182,8 @@ int kgpu::tokenize_device_impl(kgpu_ctx *c, const uint8_t *d_utf8, const uint64_
     HIPCHECK(hipSetDevice(c->dict->device));
     int rc;
     if (c->pending && (rc = kgpu_ctx_sync(c, nullptr)) != KGPU_OK && rc != KGPU_ERR_CAPACITY) return rc;
-    if ((rc = ctx_pick_chain(c, n, total_bytes, false))) return rc;
+    const Batch b{n, total_bytes, c->dict->steer.est_q8.load(std::memory_order_relaxed), c->stop_after, false, false, c->rt.batches > 0};
+    if ((rc = ctx_pick_stream(c, b))) return rc;
     if ((rc = c->arena.ensure(ARENA_INITIAL)) || (rc = c->stage.ensure((size_t)(total_bytes + n + 1) * sizeof(kgpu_token) + 64)) ||
         (rc = c->tok_count.ensure((size_t)(n + 1) * 4)) ||
         (rc = c->ovf.ensure((size_t)(n + 1) * 4 * 4)))
@@ -246,29 +208,18 @@ int kgpu::tokenize_device_impl(kgpu_ctx *c, const uint8_t *d_utf8, const uint64_
         }
         a.stat_slots = (unsigned long long *)c->stat_slots.p;
     }
-    a.est_q8 = c->dict->est_q8.load(std::memory_order_relaxed);
+    a.est_q8 = b.est_q8;
     for (int k = 0; k < 4; ++k) a.ovf[k] = (uint32_t *)c->ovf.p + (size_t)k * (n + 1);
-    return enqueue(c, a);
+    c->batch = b;
+    return enqueue(c, a, b);
 }
 
-// The long-sentence kernel alone over work list `li` of the pending batch (which the chain left unserved), then scan + compaction again.
+// The tail chain (c->chain) over work list `li` of the pending batch, which the first chain left unserved, then scan + compaction again.
 static int enqueue_tail(kgpu_ctx *c, int li) {
-    const BatchArgs &a = c->last;
     // (the scan kernel zeroed the control block after publishing it; the completed batch is behind us on the stream)
-    HIPCHECK(hipMemcpyAsync(&c->d_ctl->ovf_count[li], &c->tail_count, sizeof(unsigned), hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(hipMemcpyAsync(&c->d_ctl->ovf_count[li], &c->tail_saved.ovf_count[li], sizeof(unsigned), hipMemcpyHostToDevice, c->stream));
     c->ctl_dirty = true;
-    const bool window_was_in = c->last_window;
-    hipError_t e = (hipError_t)launch_tail_only(c->dict->view, a, c->plan, li, window_was_in || c->no_window, c->stream);
-    if (e != hipSuccess) { set_error("tail launch: %s", hipGetErrorString(e)); return KGPU_ERR_HIP; }
-    if (!window_was_in && !c->no_window && c->plan.window_lds_bytes) c->last_window = true;
-    c->last_tail = true;
-    c->h_ctl->pack_overflow = 0;
-    e = (hipError_t)launch_scan_compact(a, c->h_ctl_dev, c->stream);
-    if (e != hipSuccess) { set_error("scan/compact launch: %s", hipGetErrorString(e)); return KGPU_ERR_HIP; }
-    HIPCHECK(hipEventRecord(c->done_ev, c->stream));
-    c->ctl_dirty = false;
-    c->pending = true;
-    return KGPU_OK;
+    return run_chain(c, c->last, nullptr, "tail");
 }
 
 extern "C" int kgpu_tokenize_device(kgpu_ctx *c, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n,
@@ -293,32 +244,26 @@ extern "C" void kgpu_expand_tokens(const kgpu_token8 *in, const uint64_t *tok_of
     if (stream) expand_fence();
 }
 
-// The pending batch is over (completed or given up): the context is free, its share of the dictionary's long sentences in flight is returned.
-static void ctx_retire(kgpu_ctx *c) {
-    c->pending = false;
-    if (c->counted_long) { c->dict->long_sentences_in_flight.fetch_sub(c->counted_long, std::memory_order_relaxed); c->counted_long = 0; }
-}
-
 extern "C" int kgpu_ctx_sync(kgpu_ctx *c, uint64_t *n_tokens) {
     if (!c) { set_error("kgpu_ctx_sync: null ctx"); return KGPU_ERR_INVALID_ARG; }
     HIPCHECK(hipSetDevice(c->dict->device));
     for (;;) {
         if (!c->pending) { if (n_tokens) *n_tokens = 0; return KGPU_OK; }
         HIPCHECK(hipEventSynchronize(c->done_ev));  // this context's batch only: later work on a shared stream is not waited for
-        if (c->h_ctl->window_fail && !c->h_ctl->arena_overflow && !c->no_window) {
+        if (c->h_ctl->window_fail && !c->h_ctl->arena_overflow) {
             // the windowed kernel met a sentence it cannot hold and had no list to hand it on to: the batch once more without it
-            c->no_window = true;
             c->rt.window_reruns++;
             // the rerun counts everything again: drop what this run left in the per-wavefront slots
             if (c->last.stat_slots) HIPCHECK(hipMemsetAsync(c->last.stat_slots, 0, (size_t)STAT_SLOTS * STAT_WORDS * 8, c->stream));
             c->tail_pass = false;
-            int rc = enqueue(c, c->last);
-            c->no_window = false;
+            Batch b = c->batch;
+            b.no_window = true;
+            int rc = enqueue(c, c->last, b);
             if (rc) { ctx_retire(c); return rc; }
             continue;
         }
-        const int li_last = c->last_pools - 1 + (c->last_window ? 1 : 0) + (c->last_team ? 1 : 0);   // the list the chain ended on
-        if (!c->last_tail && c->last.n && li_last >= 0 && !c->h_ctl->arena_overflow && c->h_ctl->ovf_count[li_last] > 0) {
+        const int li = c->chain.last_list();
+        if (li >= 0 && !c->h_ctl->arena_overflow && c->h_ctl->ovf_count[li] > 0) {
             // The chain ended without its tail and a sentence needed it: ONLY what is missing (the windowed kernel if it was not in the chain,
             // then the general kernel), over the last work list (still in device memory; its length goes back into the control block the scan
             // kernel zeroed), then scan + compaction once more.  The pool kernel's work is not repeated: a corpus with a sparse but steady
@@ -327,10 +272,9 @@ extern "C" int kgpu_ctx_sync(kgpu_ctx *c, uint64_t *n_tokens) {
             c->rt.tail_reruns++;
             c->tail_saved = *c->h_ctl;
             c->tail_pass = true;
-            c->tail_li = li_last;
-            c->tail_had_window = c->last_window;
-            c->tail_count = c->h_ctl->ovf_count[li_last];
-            int rc = enqueue_tail(c, li_last);
+            c->first_pass = c->chain;
+            c->chain = tail_chain(c->plan, c->first_pass);
+            int rc = enqueue_tail(c, li);
             if (rc) { ctx_retire(c); c->tail_pass = false; return rc; }
             continue;
         }
@@ -346,66 +290,27 @@ extern "C" int kgpu_ctx_sync(kgpu_ctx *c, uint64_t *n_tokens) {
             c->tail_pass = false;  // (the whole batch runs again: nothing of an earlier pass is merged)
             // the rerun counts everything again: drop what the aborted run left in the per-wavefront slots (ctl->work went with the control block)
             if (a.stat_slots) HIPCHECK(hipMemsetAsync(a.stat_slots, 0, (size_t)STAT_SLOTS * STAT_WORDS * 8, c->stream));
-            if ((rc = enqueue(c, a))) { ctx_retire(c); return rc; }
+            if ((rc = enqueue(c, a, c->batch))) { ctx_retire(c); return rc; }
             continue;
         }
         break;
     }
     ctx_retire(c);
-    bool first_window = c->last_window, first_tail = c->last_tail;   // what the FIRST pass of this batch had in its chain (the arming below decays on that)
+    const Chain &first = c->tail_pass ? c->first_pass : c->chain;   // what the FIRST pass of this batch had in its chain (the arming decays on that)
+    const Chain *tail = c->tail_pass ? &c->chain : nullptr;
     if (c->tail_pass) {   // the published block is the tail pass's: put back what the first pass had counted
         c->tail_pass = false;
-        first_window = c->tail_had_window; first_tail = false;
         Control &h = *c->h_ctl;
         const Control &sv = c->tail_saved;
-        for (int k = 0; k < 4; ++k) { if (k <= c->tail_li) h.ovf_count[k] = sv.ovf_count[k]; h.late_count[k] += sv.late_count[k]; }   // lists up to the one the tail served are the first pass's
+        for (int k = 0; k < 4; ++k) { if (k <= first.last_list()) h.ovf_count[k] = sv.ovf_count[k]; h.late_count[k] += sv.late_count[k]; }   // lists up to the one the tail served are the first pass's
         for (int k = 0; k < 7; ++k) h.work[k] += sv.work[k];
         for (int k = 0; k < 10; ++k) h.phase[k] += sv.phase[k];
         h.pack_overflow |= sv.pack_overflow;
     }
     c->rt.batches++; c->rt.sentences += c->last.n;
     for (int k = 0; k < 4; ++k) { c->rt.deferred[k] += c->h_ctl->ovf_count[k]; c->rt.redone[k] += c->h_ctl->late_count[k]; }
-    if (c->last_window && c->last.n) c->rt.long_launches++;
-    if (c->last.n && c->last_pools > 0) {
-        // arming of the launches behind the pools: what the pools left arms the windowed kernel, what the windowed kernel left arms the general
-        // kernel; eight clean batches disarm (a wrong guess costs one small extra launch over the batch's last list, not the batch)
-        const unsigned pool_left = c->h_ctl->ovf_count[c->last_pools - 1];
-        if (c->plan.window_lds_bytes) {
-            if (pool_left > 0) c->dict->window_batches.store(64, std::memory_order_relaxed);
-            else if (first_window) c->dict->window_batches.fetch_sub(8, std::memory_order_relaxed);
-        }
-        if (c->last_window || !c->plan.window_lds_bytes) {   // (a batch whose pools left sentences while the windowed kernel was disarmed re-arms that one, not this)
-            const unsigned behind = c->last_window ? c->h_ctl->ovf_count[c->last_pools] : pool_left;   // what the last launch in front of the general kernel left
-            if (behind > 0) c->dict->tail_batches.store(64, std::memory_order_relaxed);
-            else if (first_tail) c->dict->tail_batches.fetch_sub(8, std::memory_order_relaxed);
-        }
-    }
-    if (c->last.n && c->last_pools > 0) {
-        c->win_share_q8 = c->plan.window_lds_bytes ? (uint32_t)std::min<uint64_t>(256, (uint64_t)c->h_ctl->ovf_count[c->last_pools - 1] * 256 / c->last.n) : 0u;
-        c->long_share = c->long_share ? c->win_share_q8 >= 16 : c->win_share_q8 >= 32;   // (entered at an eighth, left below a sixteenth: a share that hovers around the limit does not flap between streams)
-    }
-    if (c->last.n && c->last_pools == 0 && c->last_window && c->plan.n_pools) {
-        // a chain that started with the windowed kernel: what it left arms the general kernel behind it, as above
-        if (c->h_ctl->ovf_count[c->last_team ? 1 : 0] > 0) c->dict->tail_batches.store(64, std::memory_order_relaxed);
-        else if (first_tail) c->dict->tail_batches.fetch_sub(8, std::memory_order_relaxed);
-    }
-    if (c->last.n && c->plan.n_pools && c->last_pools > 0) {
-        // The pool kernel reserves est LDS bytes per input byte up front: a reservation that proves
-        // too small costs a redo (late_count), one that is too large only idles pages until the
-        // lattice is known -- steer for a redo rate of 1-3 %.  Applied to the value the batch ran with; races between
-        // contexts only lose an adjustment.
-        if (c->plan.n_pools > 1) {
-            if (c->h_ctl->ovf_count[0] > 0) c->dict->big_pool_batches.store(64, std::memory_order_relaxed);
-            else if (c->last_pools > 1) c->dict->big_pool_batches.fetch_sub(1, std::memory_order_relaxed);
-        }
-        const unsigned late = c->h_ctl->late_count[0];
-        uint32_t est = c->last.est_q8;
-        if ((uint64_t)late * 4 > c->last.n) est += est / 4;
-        else if ((uint64_t)late * 32 > c->last.n) est += est / 16;
-        else if ((uint64_t)late * 100 < c->last.n) est -= est / 128;
-        est = std::min<uint32_t>(std::max<uint32_t>(est, 16 * 256), 1024 * 256);
-        if (est != c->last.est_q8) c->dict->est_q8.store(est, std::memory_order_relaxed);
-    }
+    if (first.find(Kernel::Window) || (tail && tail->find(Kernel::Window))) c->rt.long_launches++;
+    chain_feedback(c->plan, first, tail, *c->h_ctl, c->last.n, c->last.est_q8, c->dict->steer, c->steer);
     if (c->profiling) {
         for (size_t i = 0; i + 4 <= c->ev_used; i += 4) {
             float t0f = 0, t01 = 0, t12 = 0;
@@ -528,7 +433,7 @@ void kgpu::pool_put(kgpu_dict *d, kgpu_ctx *c) {
     d->pool.push_back(c);
 }
 
-// A host-buffer path's copy of a batch's input, queued on the context's stream in front of the batch: the flag makes ctx_pick_chain order the
+// A host-buffer path's copy of a batch's input, queued on the context's stream in front of the batch: the flag makes ctx_pick_stream order the
 // batch behind it if the batch goes to another stream.
 int kgpu::ctx_h2d(kgpu_ctx *c, void *dst, const void *src, size_t bytes, const char *what) {
     const hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream);
@@ -546,7 +451,7 @@ extern "C" int kgpu_lattice_dump(kgpu_dict *d, const uint8_t *utf8, uint64_t len
     kgpu_ctx *c = nullptr;
     int rc = pool_get(d, &c);
     if (rc) return rc;
-    // (the copies below go on c->stream, where the dump's own launch follows: no ctx_pick_chain, so no h2d_queued -- and none left behind)
+    // (the copies below go on c->stream, where the dump's own launch follows: no ctx_pick_stream, so no h2d_queued -- and none left behind)
     auto give_back = [&]() { c->h2d_queued = false; pool_put(d, c); };
     const uint64_t offs[2] = {0, len};
     Control hc{};

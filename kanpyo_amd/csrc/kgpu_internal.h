@@ -1,5 +1,5 @@
 // kanpyo_amd/csrc/kgpu_internal.h -- shared between the host runtime
-// (kgpu_dict.cpp, kgpu_ctx.cpp, kgpu_index_build.cpp) and the HIP kernels (kgpu_kernels.hip)
+// (kgpu_dict.cpp, kgpu_ctx.cpp, kgpu_chain.cpp, kgpu_index_build.cpp) and the HIP kernels (kgpu_kernels.hip)
 // of libkanpyo_gpu.so.  Not part of the public ABI.  Plain structs only, so it
 // compiles as host C++ and as HIP.
 #pragma once
@@ -116,45 +116,14 @@ struct BatchArgs {
 };                                   // (added to by its owner, summed on the host: hot atomics on a few words would distort the run)
 constexpr uint32_t STAT_SLOTS = 16384, STAT_WORDS = 32;  // words 0..6: Control::work, 16..25: Control::phase
 
-// Launch plan of one batch: the LDS page-pool kernel (kgpu_pool.hip) once or twice -- W independent
-// wavefronts per workgroup share pool_bytes of LDS, each sentence takes what it needs -- then the windowed kernel
-// (kgpu_window.hip: bounded LDS whatever the length) for whatever fits no pool, then the general kernel, whose lattices
-// live in HBM scratch, as the last resort.  A sentence that a launch cannot serve is pushed onto the next launch's work list.
-struct LaunchPlan {
-    int n_pools;
-    uint32_t pool_bytes[2];
-    uint32_t pool_waves[2];
-    uint32_t pool_max_pages[2];  // of 64: larger reservations are routed to the next launch
-    bool pool_limit_auto;        // the shipped plan (no KGPU_POOL): the runtime may pick the pool shape per batch (kgpu_ctx.cpp: enqueue)
-    uint32_t alt_pool_bytes, alt_pool_waves;   // ... the shape for chains that hold a windowed launch: smaller workgroups (20 KB, two wavefronts) find their LDS
-    int alt_pool_workgroups;                   // sooner on a chip full of 10 KB single-wavefront workgroups (0: not available)
-    int pool_workgroups[2];   // persistent grid per pool launch
-    int general_workgroups;
-    uint32_t window_lds_bytes;  // > 0: the windowed kernel (kgpu_window.hip) behind the pools; 0: the general kernel serves what they route away
-    int window_workgroups;
-    int window_team;             // wavefronts per sentence of the windowed kernel's team form (KGPU_WINDOW_TEAM_SIZE, default 2)
-    int window_team_workgroups;  // resident workgroups of that form on the whole chip (0: not available)
-    int window_team_mode;        // KGPU_WINDOW_TEAM: 0 never, 2 whenever the chain starts with the windowed kernel, -1 (default) by the load
-    uint32_t window_first_bytes; // KGPU_WINDOW_FIRST: a batch averaging this many bytes per sentence or more gets no pool launch in front (default 1024; 0 = never)
-};
-
-// Launchers (kgpu_kernels.hip).  `stream` is a hipStream_t.
-// n_pools_now <= plan.n_pools: how many of the pool launches to issue for this batch (the chain
-// stays complete without the later ones: their work falls through to the next launch).
-int launch_tokenize(const DictView &d, const BatchArgs &a, const LaunchPlan &plan, int n_pools_now,
-                    uint32_t stop_after /* kgpu_ctx_set_ablation; 0 = run everything */, void *stream,
-                    void *event_after_first /* hipEvent_t recorded behind the first (dominant) launch, or null */,
-                    bool window_now /* the windowed kernel behind the pools (plan.window_lds_bytes) */,
-                    bool tail_now /* false: nothing behind a chain that has a work list (the host launches what is missing if a sentence needed it) */,
-                    bool team_now = false /* a chain without pool launches: the windowed kernel's two-wavefronts-per-sentence form first, its ordinary form behind it */,
-                    int window_grid = 0 /* > 0: workgroups of the windowed launch behind the pools (the host's estimate of its work list; any grid is correct, the list is strided) */);
-int launch_tail_only(const DictView &d, const BatchArgs &a, const LaunchPlan &plan, int list_index, bool window_was_in_chain, void *stream);
-int window_workgroups_per_cu(uint32_t lds_bytes);
-int window_team_workgroups_per_cu(uint32_t lds_bytes, int team);
-int launch_general_only(const DictView &d, const BatchArgs &a, void *stream);
-int launch_small_call(const DictView &d, const BatchArgs &a, const LaunchPlan &plan, void *stream);  // pool kernel alone, one sentence per wavefront  // kgpu_lattice_dump: HBM-scratch kernel alone
-int launch_scan_compact(const BatchArgs &a, Control *host_ctl, void *stream, bool small_workgroups = false);  // host_ctl: device pointer of the pinned result block
-LaunchPlan default_launch_plan(int device);
+// Launchers (kgpu_kernels.hip, kgpu_pool.hip, kgpu_window.hip).  `stream` is a hipStream_t.
+struct Step;  // kgpu_chain.h
+int launch_step(const DictView &d, const BatchArgs &a, const Step &s, uint32_t stop_after /* kgpu_ctx_set_ablation; 0 = run everything */, void *stream);
+int launch_general_only(const DictView &d, const BatchArgs &a, void *stream);  // kgpu_lattice_dump: HBM-scratch kernel alone
+int launch_small_call(const DictView &d, const BatchArgs &a, void *stream);  // pool kernel alone, one sentence per wavefront
+int launch_scan_compact(const BatchArgs &a, Control *host_ctl, void *stream, bool small_workgroups);  // host_ctl: device pointer of the pinned result block
 int pool_workgroups_per_cu(uint32_t pool_bytes, uint32_t waves);
+int window_workgroups_per_cu(uint32_t lds_bytes);
+int window_team_workgroups_per_cu(uint32_t lds_bytes);
 
 }  // namespace kgpu

@@ -23,14 +23,12 @@
 // fully taken, and any sentence length / lattice shape works.  It is the LAST RESORT of the launch chain (what the LDS-resident
 // pool kernel, kgpu_pool.hip, and the windowed kernel, kgpu_window.hip, cannot hold) and the kernel behind kgpu_lattice_dump: its
 // slabs ARE the lattice.  (Round 2-3 also instantiated it with an LDS-blocked sweep as "the long-sentence kernel"; the windowed kernel
-// took that place in round 4.)  Also here: scan / compaction kernels and the launch chain.
+// took that place in round 4.)  Also here: the scan / compaction kernels, and the thin launchers of a chain's steps (the chain itself: kgpu_chain.cpp).
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cstdlib>
-#include <cstring>
 #include <type_traits>
 
+#include "kgpu_chain.h"
 #include "kgpu_device.h"
 
 namespace kgpu {
@@ -524,106 +522,30 @@ __global__ __launch_bounds__(256) void k_scan_compact(BatchArgs a, Control *host
 
 int launch_tokenize_pool(const DictView &d, const BatchArgs &a, const WorkIO &io, uint32_t pool_bytes, uint32_t waves,
                          uint32_t max_pages, int n_workgroups, uint32_t stop_after, void *stream);  // kgpu_pool.hip
-int pool_workgroups_per_cu(uint32_t pool_bytes, uint32_t waves);
+int launch_tokenize_window(const DictView &d, const BatchArgs &a, const WorkIO &io, uint32_t lds_bytes, int n_workgroups, bool team, bool claim, void *stream);  // kgpu_window.hip
 
-// Launch chain: the LDS page-pool kernel(s) -> the windowed kernel (whatever the pools route away: long sentences, lattices too dense for a
-// pool) -> the general kernel (what the windowed kernel hands back: the last resort).  Every launch is a persistent grid over its work list
-// (the first one: the identity over [0, n)) and pushes what it does not serve onto the next launch's list.
-int launch_tokenize_window(const DictView &d, const BatchArgs &a, const WorkIO &io, uint32_t lds_bytes, int n_workgroups, int team, void *stream, bool claim = false);  // kgpu_window.hip
-
-static int launch_window_over(const DictView &d, const BatchArgs &a, const LaunchPlan &plan, const uint32_t *in_list, const unsigned int *in_count, int li, void *stream, int grid = 0) {
-    WorkIO io{in_list, in_count, a.ovf[li], &a.ctl->ovf_count[li], nullptr};
-    uint64_t wg = plan.window_workgroups;
-    if (!in_list && a.n < wg) wg = a.n;
-    // behind the pools the list's length is on the device; a grid of the chip's full size is mostly workgroups that find nothing -- and each of them has to find a free
-    // slot on a chip full of long-running wavefronts before it can say so, which is what the launch (and the scan behind it) then waits for: the host's estimate instead
-    if (in_list && grid > 0 && (uint64_t)grid < wg) wg = (uint64_t)grid;
-    // more sentences expected than workgroups: they are claimed one by one instead of every G-th being a workgroup's (kgpu_window.hip; KGPU_WINDOW_CLAIM=0 / 1 forces it)
-    static const int claim_mode = [] { const char *e = getenv("KGPU_WINDOW_CLAIM"); return e ? atoi(e) : -1; }();
-    const uint64_t expected = in_list ? (grid > 64 ? ((uint64_t)grid - 64) * 4 / 5 : 0) : a.n;
-    const bool claim = claim_mode >= 0 ? claim_mode != 0 : expected > wg;
-    return launch_tokenize_window(d, a, io, plan.window_lds_bytes, (int)(wg ? wg : 1), 1, stream, claim);
-}
-static int launch_general_over(const DictView &d, const BatchArgs &a, const LaunchPlan &plan, const uint32_t *in_list, const unsigned int *in_count, uint32_t stop_after, void *stream) {
-    WorkIO io{in_list, in_count, nullptr, nullptr, nullptr};
-    uint64_t wg = plan.general_workgroups;
-    if (!in_list && a.n < wg) wg = a.n;
-    hipLaunchKernelGGL(k_tokenize_general, dim3((unsigned)(wg ? wg : 1)), dim3(64), 0, (hipStream_t)stream, d, a, io, stop_after);
+// One launch of a chain (kgpu_chain.h): a persistent grid over its work list that pushes what it does not serve onto the next one.
+int launch_step(const DictView &d, const BatchArgs &a, const Step &s, uint32_t stop_after, void *stream) {
+    Control *ctl = a.ctl;
+    const WorkIO io{s.in >= 0 ? a.ovf[s.in] : nullptr, s.in >= 0 ? &ctl->ovf_count[s.in] : nullptr, s.out >= 0 ? a.ovf[s.out] : nullptr,
+                    s.out >= 0 ? &ctl->ovf_count[s.out] : nullptr, s.kernel == Kernel::Pool ? &ctl->late_count[s.out] : nullptr};
+    switch (s.kernel) {
+    case Kernel::Pool: return launch_tokenize_pool(d, a, io, s.lds_bytes, s.waves, s.max_pages, s.grid, stop_after, stream);
+    case Kernel::WindowTeam: return launch_tokenize_window(d, a, io, s.lds_bytes, s.grid, true, false, stream);
+    case Kernel::Window: return launch_tokenize_window(d, a, io, s.lds_bytes, s.grid, false, s.claim, stream);
+    case Kernel::General: hipLaunchKernelGGL(k_tokenize_general, dim3((unsigned)s.grid), dim3(64), 0, (hipStream_t)stream, d, a, io, stop_after); break;
+    }
     return (int)hipGetLastError();
 }
 
-int launch_tokenize(const DictView &d, const BatchArgs &a, const LaunchPlan &plan, int n_pools_now, uint32_t stop_after, void *stream,
-                    void *event_after_first, bool window_now, bool tail_now, bool team_now, int window_grid) {
-    Control *ctl = a.ctl;
-    const uint32_t *in_list = nullptr;
-    const unsigned int *in_count = nullptr;
-    int li = 0;  // next free work list
-    for (int k = 0; k < plan.n_pools && k < n_pools_now; ++k, ++li) {
-        WorkIO io{in_list, in_count, a.ovf[li], &ctl->ovf_count[li], &ctl->late_count[li]};
-        uint64_t wg = plan.pool_workgroups[k];
-        const uint64_t want = (a.n + plan.pool_waves[k] - 1) / plan.pool_waves[k];
-        if (!in_list && want < wg) wg = want;
-        int e = launch_tokenize_pool(d, a, io, plan.pool_bytes[k], plan.pool_waves[k], plan.pool_max_pages[k], (int)(wg ? wg : 1), stop_after, stream);
-        if (e) return e;
-        if (k == 0 && event_after_first && hipEventRecord((hipEvent_t)event_after_first, (hipStream_t)stream) != hipSuccess) return (int)hipGetLastError();
-        in_list = a.ovf[li];
-        in_count = &ctl->ovf_count[li];
-    }
-    if (event_after_first && (plan.n_pools == 0 || n_pools_now == 0) && hipEventRecord((hipEvent_t)event_after_first, (hipStream_t)stream) != hipSuccess) return (int)hipGetLastError();
-    if (window_now && plan.window_lds_bytes && stop_after == 0) {
-        bool behind_team = false;
-        if (team_now && !in_list && plan.window_team_workgroups > 0 && a.n) {
-            // a short list of long sentences: two wavefronts per sentence (kgpu_window.hip, TEAM), one workgroup each; what that form cannot hold goes on to
-            // the ordinary form behind it
-            WorkIO io{nullptr, nullptr, a.ovf[li], &ctl->ovf_count[li], nullptr};
-            int e = launch_tokenize_window(d, a, io, plan.window_lds_bytes, (int)std::min<uint64_t>(a.n, 1u << 30), plan.window_team, stream);
-            if (e) return e;
-            in_list = a.ovf[li];
-            in_count = &ctl->ovf_count[li];
-            ++li;
-            behind_team = true;
-        }
-        int e = launch_window_over(d, a, plan, in_list, in_count, li, stream, behind_team ? 256 : window_grid);   // (what a team hands on is rare: a small strided grid)
-        if (e) return e;
-        in_list = a.ovf[li];
-        in_count = &ctl->ovf_count[li];
-        ++li;
-    }
-    // No recent batch left a sentence for the rest of the chain: it is left out (an empty launch still costs its 5.5 us on the stream, 4 % of a
-    // cfg 2 batch's chain -- and far more behind a chip full of long-running wavefronts); the host finds a sentence that needed it in the last
-    // list's count and launches what is missing over that list (launch_tail_only).
-    if (!tail_now && in_list) return (int)hipGetLastError();
-    return launch_general_over(d, a, plan, in_list, in_count, stop_after, stream);
-}
-
-// What a chain that ended on work list `li` left out (kgpu_ctx.cpp: enqueue_tail): the windowed kernel over that list unless it was in the chain,
-// then the general kernel over what is left.
-int launch_tail_only(const DictView &d, const BatchArgs &a, const LaunchPlan &plan, int li, bool window_was_in_chain, void *stream) {
-    Control *ctl = a.ctl;
-    if (li < 0 || li > 2) return (int)hipErrorInvalidValue;
-    if (!window_was_in_chain && plan.window_lds_bytes) {
-        int e = launch_window_over(d, a, plan, a.ovf[li], &ctl->ovf_count[li], li + 1, stream);
-        if (e) return e;
-        ++li;
-    }
-    return launch_general_over(d, a, plan, a.ovf[li], &ctl->ovf_count[li], 0u, stream);
-}
-
-int launch_small_call(const DictView &d, const BatchArgs &a, const LaunchPlan &plan, void *stream) {
+int launch_small_call(const DictView &d, const BatchArgs &a, void *stream) {
     Control *ctl = a.ctl;
     WorkIO io{nullptr, nullptr, a.ovf[0], &ctl->ovf_count[0], &ctl->late_count[0]};
     // every wavefront gets at most one sentence -- and a workgroup of its own with a 64 KB LDS slice (at most 128 of them: the chip has room): no pages to
     // reserve, no wavefronts that start only to find nothing and meet at the barrier (one sentence: 52 -> 44.5 us per call, 64: 65.7 -> 57.3; round 6),
-    // and anything up to ~350 characters stays in this one launch.  KGPU_SMALL_POOL=<KiB>:<wavefronts> (measurement) overrides.
-    static const struct Shape { uint32_t bytes, waves; } sh = [] {
-        Shape s{64u * 1024u, 1u};
-        if (const char *e = getenv("KGPU_SMALL_POOL")) { int k = atoi(e), w = 1; if (const char *c = strchr(e, ':')) w = atoi(c + 1); if (k >= 8 && k <= 64 && w >= 1 && w <= 16) s = Shape{(uint32_t)k * 1024u, (uint32_t)w}; }
-        return s;
-    }();
-    const uint64_t wg = (a.n + sh.waves - 1) / sh.waves;
-    return launch_tokenize_pool(d, a, io, sh.bytes, sh.waves, 64u, (int)(wg ? wg : 1), 0u, stream);
+    // and anything up to ~350 characters stays in this one launch.
+    return launch_tokenize_pool(d, a, io, 64u * 1024u, 1u, 64u, (int)(a.n ? a.n : 1), 0u, stream);
 }
-
 int launch_general_only(const DictView &d, const BatchArgs &a, void *stream) {
     WorkIO io{nullptr, nullptr, nullptr, nullptr, nullptr};
     hipLaunchKernelGGL(k_tokenize_general, dim3(1), dim3(64), 0, (hipStream_t)stream, d, a, io, 0u);
@@ -632,13 +554,9 @@ int launch_general_only(const DictView &d, const BatchArgs &a, void *stream) {
 
 int launch_scan_compact(const BatchArgs &a, Control *host_ctl, void *stream, bool small_workgroups) {
     // Measured (tools/ab_scan.sh): records bound for mapped host memory (the large host call: a.toff8) 83.8 against 66.6 M sentences/s end to end in one
-    // launch; the device-resident 24-byte path 92.8 against 96.9 -- there the separate kernels stay.  KGPU_SCAN_COMPACT=1 / 2 force one form (experiments),
-    // KGPU_SCAN_WG the sentences per workgroup.
-    static const int mode = [] { const char *e = getenv("KGPU_SCAN_COMPACT"); return e ? atoi(e) : 0; }();
-    static const int wg_env = [] { const char *e = getenv("KGPU_SCAN_WG"); const int v = e ? atoi(e) : 0; return (v >= 4 && v <= 256) ? v : 0; }();
-    if (a.n <= 65536 && (mode == 1 || (mode == 0 && a.toff8))) {
-        uint32_t per_wg = wg_env ? (uint32_t)wg_env : a.n <= 4096 ? 64u : a.n <= 16384 ? 128u : 256u;
-        if ((a.n + per_wg - 1) / per_wg > 65536) per_wg = 256;
+    // launch; the device-resident 24-byte path 92.8 against 96.9 -- there the separate kernels stay.
+    if (a.n <= 65536 && a.toff8) {
+        const uint32_t per_wg = a.n <= 4096 ? 64u : a.n <= 16384 ? 128u : 256u;
         const uint64_t wgs = a.n ? (a.n + per_wg - 1) / per_wg : 1;
         if (a.out8) hipLaunchKernelGGL(k_scan_compact<true>, dim3((unsigned)wgs), dim3(256), 0, (hipStream_t)stream, a, host_ctl, per_wg);
         else hipLaunchKernelGGL(k_scan_compact<false>, dim3((unsigned)wgs), dim3(256), 0, (hipStream_t)stream, a, host_ctl, per_wg);
@@ -656,80 +574,6 @@ int launch_scan_compact(const BatchArgs &a, Control *host_ctl, void *stream, boo
     if (a.out8) hipLaunchKernelGGL(k_compact8, dim3((unsigned)blocks), dim3(64 * wpb), 0, (hipStream_t)stream, a, host_ctl);
     else hipLaunchKernelGGL(k_compact, dim3((unsigned)blocks), dim3(64 * wpb), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
-}
-
-LaunchPlan default_launch_plan(int device) {
-    hipDeviceProp_t p;
-    int cus = 256;
-    if (hipGetDeviceProperties(&p, device) == hipSuccess) cus = p.multiProcessorCount;
-    LaunchPlan t{};
-    t.general_workgroups = cus * 2;  // the last resort is rarely needed: few workgroups, so that an empty launch drains quickly on a busy chip
-    // Default: four 40 KB pools per CU with 4 wavefronts each (16 sentences in flight per CU, any mix of
-    // sizes).  A workgroup holds its LDS until its last wavefront is through, and the next launch's workgroups
-    // start only then: four-wavefront workgroups drain sooner at the tail of a 4096-sentence batch than eight-
-    // or sixteen-wavefront ones (80:8 66.3, 160:16 63.9, 40:4 68.6 M sentences/s; two-wavefront pools lose to
-    // fragmentation, and any shape that is not 16 wavefronts per CU loses to the batch size: 4096 = 256 x 16).
-    // A sentence expected to need more than 40 of a pool's 64 pages (25 KB, ~155 chars) goes to the
-    // long-sentence kernel instead: LDS x time grows with the square of the length, and a few long sentences
-    // would otherwise hold the pools while the short ones wait (cfg 3 in batches of 16384, M sentences/s by this limit:
-    // 16 pages 16.3, 24 16.8, 32 17.6-18.4, 40 17.8-18.8, 48 17.1-18.4; round 2, batches of 4096: 56 11.6, 64 10.7 against 12.3; cfg 2 is
-    // indifferent: 96.8-97.2 at 40, 96.4-97.0 at 48).
-    // KGPU_POOL="<KiB>:<wavefronts>[:<max pages>][,...]", "0" = none.
-    t.n_pools = 0;
-    {
-        const char *e = getenv("KGPU_POOL");
-        const char *q = e ? e : "40:4:32";
-        t.pool_limit_auto = e == nullptr;
-        while (*q && t.n_pools < 2) {
-            int kib = atoi(q), w = 8, mp = 64;
-            const char *c = q;
-            while (*c && *c != ',' && *c != ':') ++c;
-            if (*c == ':' && atoi(c + 1) > 0) {
-                w = atoi(c + 1);
-                ++c;
-                while (*c && *c != ',' && *c != ':') ++c;
-                if (*c == ':' && atoi(c + 1) > 0) mp = atoi(c + 1);
-            }
-            if (w > 16) w = 16;
-            if (mp > 64) mp = 64;
-            if (kib >= 8 && kib <= 160) {
-                const int per_cu = pool_workgroups_per_cu((uint32_t)kib * 1024, (uint32_t)w);
-                if (per_cu > 0) {
-                    t.pool_bytes[t.n_pools] = (uint32_t)kib * 1024; t.pool_waves[t.n_pools] = (uint32_t)w;
-                    t.pool_max_pages[t.n_pools] = (uint32_t)mp;
-                    t.pool_workgroups[t.n_pools] = cus * per_cu;
-                    ++t.n_pools;
-                }
-            }
-            while (*q && *q != ',') ++q;
-            if (*q == ',') ++q;
-        }
-    }
-    t.alt_pool_bytes = 20 * 1024; t.alt_pool_waves = 2;
-    {
-        const int per_cu = (t.pool_limit_auto && t.n_pools) ? pool_workgroups_per_cu(t.alt_pool_bytes, t.alt_pool_waves) : 0;
-        t.alt_pool_workgroups = per_cu > 0 ? cus * per_cu : 0;
-    }
-    // windowed kernel (everything the pools route away): KGPU_WINDOW="<KiB>" of LDS per single-wavefront workgroup, "0" = off (the general kernel then serves it all)
-    {
-        const char *e = getenv("KGPU_WINDOW");
-        int kib = e ? atoi(e) : 10;   // 10 KB: 16 workgroups per CU = the four wavefronts per SIMD its 128 VGPRs allow (round 4, after big buckets lost their pair tables: cfg 3 22.5 M sentences/s against 19.2 at 12 KB and 20.8 at 11, cfg 5 2.67 against 2.71 Gchar/s)
-        if (kib < 8 || kib > 160) kib = 0;
-        t.window_lds_bytes = (uint32_t)kib * 1024;
-        const int per_cu = kib ? window_workgroups_per_cu(t.window_lds_bytes) : 0;
-        t.window_workgroups = cus * per_cu;
-        if (per_cu <= 0) t.window_lds_bytes = 0;
-        const char *ts = getenv("KGPU_WINDOW_TEAM_SIZE");
-        t.window_team = ts && atoi(ts) >= 2 && atoi(ts) <= 4 ? atoi(ts) : 2;
-        t.window_team_workgroups = t.window_lds_bytes ? cus * std::max(0, window_team_workgroups_per_cu(t.window_lds_bytes, t.window_team)) : 0;
-        const char *tm = getenv("KGPU_WINDOW_TEAM");
-        t.window_team_mode = tm ? atoi(tm) : -1;
-        const char *wf = getenv("KGPU_WINDOW_FIRST");
-        t.window_first_bytes = (uint32_t)std::max(0, wf ? atoi(wf) : 1024);
-    }
-    if (const char *e = getenv("KGPU_GENERAL_WG")) { int v = atoi(e); if (v > 0) t.general_workgroups = v; }
-    if (const char *e = getenv("KGPU_POOL_WG")) { int v = atoi(e); if (v > 0 && t.n_pools) t.pool_workgroups[0] = v; }
-    return t;
 }
 
 }  // namespace kgpu

@@ -13,7 +13,7 @@
 #include <thread>
 #include <vector>
 
-#include "kgpu_internal.h"
+#include "kgpu_chain.h"
 
 #define HIPCHECK(expr)                                                                  \
     do {                                                                                \
@@ -70,32 +70,17 @@ struct kgpu_dict {
     std::vector<void *> allocs;
     std::mutex pool_mu;
     std::vector<kgpu_ctx *> pool;
-    // LDS bytes reserved per input byte (x256) by the pool kernel before the lattice is known; a
-    // property of the dictionary + the text, so it is learnt once and shared by all contexts
-    std::atomic<uint32_t> est_q8{64 * 256};   // (round 6: the lattice takes ~52 bytes of LDS per input byte on IPADIC-shaped text; was 80)
-    // Batches left for which the second (whole-CU) pool is launched.  Its workgroups need a CU's
-    // entire LDS just to start and find their list empty, which stalls them -- and the launches
-    // queued behind -- until both 80 KB pools of that CU have drained; so it is only issued while
-    // recent batches actually overflowed the first pool (otherwise those rare sentences take the
-    // HBM-scratch kernel).  Performance heuristic only: the chain is complete either way.
-    std::atomic<int> big_pool_batches{0};
-    // Same for the long-sentence kernel (its workgroups hold 32 KB of LDS each): issued while recent
-    // batches still had sentences left after the pools.
-    std::atomic<int> window_batches{64};  // the windowed kernel: in the chain while recent batches left the pools sentences (starts armed)
-    std::atomic<int> tail_batches{0};     // the general kernel behind it: while recent batches left the windowed kernel (or, without one, the pools) sentences
+    Steering steer;   // the launch chain's dictionary-wide state (kgpu_chain.h)
     // Streams handed round-robin to contexts created without one.  HIP multiplexes streams onto three
     // hardware queues: a 4th stream queues behind the 1st and unbalances them (measured -25 %), so any
     // number of contexts shares three streams; each context waits on its own completion event.
     std::vector<hipStream_t> streams;
     unsigned next_stream = 0;
-    // A second set for chains that START with the windowed kernel (batches of long sentences: kgpu_ctx.cpp, ctx_pick_chain): such a launch holds a thousand
+    // A second set for chains that START with the windowed kernel (batches of long sentences: kgpu_ctx.cpp, ctx_pick_stream): such a launch holds a thousand
     // single-wavefront workgroups for milliseconds and its slots empty out one by one, so the chip fills only when more of them overlap than the four launches
     // the pool kernel wants -- one stream per context, up to eight, created when the first such batch arrives (round 5: cfg 5 2.97 -> 3.96 Gchar/s).
     std::vector<hipStream_t> long_streams;
     unsigned next_long = 0;
-    std::atomic<int> long_sentences_in_flight{0};   // sentences of window-first batches between enqueue and completion (decides the two-wavefront form)
-    std::atomic<int> long_peak{0};                  // ... its recent maximum (decays by an eighth per enqueue): a caller that keeps eight batches in flight is not
-                                                    // mistaken for a lone one by the batch that happens to be enqueued while the others are being collected
     std::vector<uint32_t> left_of_rank, right_of_rank;  // device (ranked) context id -> the dictionary's own; empty = identity
     // One reference for the handle the caller holds plus one per live context: the tables and the shared
     // streams go when the last one does (a context outliving kgpu_dict_destroy keeps working).
@@ -107,14 +92,8 @@ struct kgpu_ctx {
     hipStream_t stream = nullptr;       // the stream of the pending / next batch (one of the dictionary's shared streams unless the caller gave one)
     hipStream_t short_stream = nullptr, long_stream = nullptr;   // what `stream` alternates between (library-owned streams only)
     bool own_stream = false;            // the caller's stream: never switched
-    bool window_first = false;          // the next batch's chain starts with the windowed kernel (no pool launch in front)
-    bool roomy = false;                 // ... its pool workgroups run three wavefronts instead of four (four reservations of the learnt size do not fit a pool)
-    bool last_team = false;             // the pending batch's chain started with the two-wavefronts-per-sentence form (one more work list in the chain)
-    int counted_long = 0;               // what the pending batch added to kgpu_dict::long_sentences_in_flight
-    uint32_t win_share_q8 = 0;          // share of the last pool-first batch's sentences that the pools routed to the windowed kernel (x256): an eighth or more
-                                        // and the next batch runs on the context's long stream too (cfg 3: a third of the sentences, three quarters of the characters)
-    bool long_share = false;            // ... with hysteresis: entered at win_share_q8 >= 32, left below 16
-    bool h2d_queued = false;            // a host-buffer path has queued this batch's H2D copy on `stream` (ctx_pick_chain orders the batch behind it if it switches streams)
+    ContextSteering steer;              // the launch chain's state of this context (kgpu_chain.h)
+    bool h2d_queued = false;            // a host-buffer path has queued this batch's H2D copy on `stream` (ctx_pick_stream orders the batch behind it if it switches streams)
     hipEvent_t switch_ev = nullptr;     // orders a batch behind what was queued on the stream the context used before
     hipEvent_t done_ev = nullptr;  // recorded behind the batch's last kernel: contexts may share a stream
     Control *d_ctl = nullptr;
@@ -122,15 +101,11 @@ struct kgpu_ctx {
     Control *h_ctl_dev = nullptr;  // device-side address of h_ctl
     bool ctl_dirty = true;     // d_ctl must be zeroed by the host (first launch, or after a failed enqueue)
     uint32_t launch_seq = 0;
-    int last_pools = 0;        // pool launches issued for the pending batch
-    bool last_window = false;  // ... and whether the windowed kernel was
-    bool no_window = false;    // the pending batch is a rerun without the windowed kernel (it had flagged Control::window_fail)
-    bool last_tail = true;     // ... whether the last-resort launch closed the chain (left out while no recent batch needed the tail)
-    bool tail_pass = false;    // the pending launches are the tail of the batch's chain alone (it had been left out and a sentence needed it)
-    Control tail_saved{};      // ... what the first pass had published
-    unsigned tail_count = 0;   // ... the length of the work list the tail serves (source of an asynchronous copy: lives here)
-    int tail_li = 0;           // ... that list's index
-    bool tail_had_window = false;  // ... whether the first pass had the windowed kernel in its chain
+    Batch batch{};             // what the pending batch's chain was built from (a rerun builds it again)
+    Chain chain;               // the pending launches
+    bool tail_pass = false;    // ... are the tail of the batch's chain alone (it had been left out and a sentence needed it)
+    Chain first_pass;          // ... then the chain that ran first
+    Control tail_saved{};      // ... what it had published (the length of the list the tail serves is copied back from here: lives in the context)
     uint32_t event_every = 1;  // KGPU_PROFILE_SAMPLED: HIP events on every 4th launch only
     DevBuf arena, stage, tok_count;
     // host-buffer path staging

@@ -94,14 +94,14 @@ static int small_call(kgpu_dict *d, kgpu_ctx *c, SmallReq *const *reqs, size_t n
     a.stage = (kgpu_token *)c->stage.p; a.tok_count = (uint32_t *)c->tok_count.p;
     a.status = c->sm_dev + SM_OFF_STATUS; a.out = (kgpu_token *)(c->sm_dev + SM_OFF_TOK); a.out_cap = total + n;
     a.tok_offsets = (uint64_t *)(c->sm_dev + SM_OFF_TOFF);
-    a.est_q8 = d->est_q8.load(std::memory_order_relaxed);
+    a.est_q8 = d->steer.est_q8.load(std::memory_order_relaxed);
     for (int k = 0; k < 4; ++k) a.ovf[k] = (uint32_t *)c->ovf.p + (size_t)k * (n + 1);
     a.fused_host = c->h_ctl_dev; a.fused_seq = seq;
     if (c->ctl_dirty) HIPCHECK(hipMemsetAsync(c->d_ctl, 0, sizeof(Control), c->stream));
     c->ctl_dirty = true;
     const uint64_t tt1 = trace ? now_ns() : 0, cc1 = trace ? cpu_ns() : 0;
     {
-        hipError_t e = (hipError_t)launch_small_call(d->view, a, c->plan, c->stream);
+        hipError_t e = (hipError_t)launch_small_call(d->view, a, c->stream);
         if (e != hipSuccess) { set_error("small-call launch: %s", hipGetErrorString(e)); return KGPU_ERR_HIP; }
     }
     const uint64_t tt2 = trace ? now_ns() : 0, cc2 = trace ? cpu_ns() : 0;

@@ -14,7 +14,7 @@
 //     is relaxed by streaming them from the FIFO, 64 per step.
 // LDS-resident lattices (kgpu_pool.hip) do not scale to long sentences (LDS x time grows with the square of the length: DESIGN.md
 // section 8); this kernel's LDS is independent of the length and its HBM traffic is one write per node.  It serves everything the pool
-// kernel routes away -- from ~125 characters up to any length -- and whole batches of long sentences, which start with it (kgpu_ctx.cpp: ctx_pick_chain);
+// kernel routes away -- from ~125 characters up to any length -- and whole batches of long sentences, which start with it (kgpu_chain.cpp: starts_with_window);
 // for short work lists it runs as a TEAM of wavefronts per sentence (below).  (Rounds 2-3 had a second long-sentence kernel that kept the whole lattice in
 // HBM and staged blocks of it in LDS for the sweep: 44 bytes per node, ~70 per byte, read back several times.  On 190-512-character
 // sentences the two were level, on 2048-character documents this one is 1.6x faster: round 4 removed the other.)
@@ -106,7 +106,7 @@ __device__ __forceinline__ uint32_t win_walk(const DictView &d, BY &&byte, uint3
 //   * the VALUE token: the dp of the carried and far entries.  Held from the first relaxation to the last.
 // Per window and wavefront: [structure: stage, seeds, walk, scan, emit] -> gather -> [value: seed dp, sweep, carry / far dp out] -> node records out; with TEAM = 2
 // both chains (structure ~920, value ~640 of a window's ~2000 clocks per character) fit inside the other wavefront's window, so a sentence runs about twice as
-// fast on twice the LDS -- which is why the host picks this only when the slots would otherwise stay empty (launch_tokenize_window).  Seeds enter a window's
+// fast on twice the LDS -- which is why the host picks this only when the slots would otherwise stay empty (kgpu_chain.cpp: build_chain).  Seeds enter a window's
 // buckets before their dp exists: the slot holds a marker (SEED_MARK | index) that the value phase replaces.  The carry lists live in two banks of the
 // workgroup's shared LDS (window k writes bank k & 1, window k + 1 reads it); what this form cannot hold (a carry list beyond CCAP entries) fails the
 // sentence on to the next launch: the single-wavefront form of this kernel.
@@ -1068,16 +1068,14 @@ int window_workgroups_per_cu(uint32_t lds_bytes) {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)k_tokenize_window<false, 1>, 64, (size_t)lds_bytes) != hipSuccess) return 0;
     return n;
 }
-// ... of the form with `team` wavefronts per sentence (0: it does not fit)
-template <int TEAM>
-static int team_per_cu(uint32_t lds_bytes) {
-    const uint32_t tb = team_lds_bytes(lds_bytes, TEAM);
-    if (tb > 64 * 1024 && hipFuncSetAttribute((const void *)k_tokenize_window<false, TEAM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tb) != hipSuccess) return 0;
+// ... of the form with two wavefronts per sentence (0: it does not fit)
+int window_team_workgroups_per_cu(uint32_t lds_bytes) {
+    const uint32_t tb = team_lds_bytes(lds_bytes, 2);
+    if (tb > 64 * 1024 && hipFuncSetAttribute((const void *)k_tokenize_window<false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tb) != hipSuccess) return 0;
     int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)k_tokenize_window<false, TEAM>, 64 * TEAM, (size_t)tb) != hipSuccess) return 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)k_tokenize_window<false, 2>, 64 * 2, (size_t)tb) != hipSuccess) return 0;
     return n;
 }
-int window_team_workgroups_per_cu(uint32_t lds_bytes, int team) { return team == 2 ? team_per_cu<2>(lds_bytes) : team == 3 ? team_per_cu<3>(lds_bytes) : team == 4 ? team_per_cu<4>(lds_bytes) : 0; }
 
 template <bool PROF, int TEAM>
 static int launch_window_inst(const WinArgs &wa, int n_workgroups, void *stream) {
@@ -1090,12 +1088,10 @@ static int launch_window_inst(const WinArgs &wa, int n_workgroups, void *stream)
     return (int)hipGetLastError();
 }
 
-// team: wavefronts per sentence (1; 2-4: the host picks that when the work list is short against the chip's slots)
-int launch_tokenize_window(const DictView &d, const BatchArgs &a, const WorkIO &io, uint32_t lds_bytes, int n_workgroups, int team, void *stream, bool claim) {
-    const WinArgs wa{d, a, io, lds_bytes, (team <= 1 && claim) ? 1u : 0u};
-    if (team == 2) return a.count_work ? launch_window_inst<true, 2>(wa, n_workgroups, stream) : launch_window_inst<false, 2>(wa, n_workgroups, stream);
-    if (team == 3) return a.count_work ? launch_window_inst<true, 3>(wa, n_workgroups, stream) : launch_window_inst<false, 3>(wa, n_workgroups, stream);
-    if (team == 4) return a.count_work ? launch_window_inst<true, 4>(wa, n_workgroups, stream) : launch_window_inst<false, 4>(wa, n_workgroups, stream);
+// team: two wavefronts per sentence (the host picks that when the work list is short against the chip's slots); claim: the ordinary form only
+int launch_tokenize_window(const DictView &d, const BatchArgs &a, const WorkIO &io, uint32_t lds_bytes, int n_workgroups, bool team, bool claim, void *stream) {
+    const WinArgs wa{d, a, io, lds_bytes, (!team && claim) ? 1u : 0u};
+    if (team) return a.count_work ? launch_window_inst<true, 2>(wa, n_workgroups, stream) : launch_window_inst<false, 2>(wa, n_workgroups, stream);
     return a.count_work ? launch_window_inst<true, 1>(wa, n_workgroups, stream) : launch_window_inst<false, 1>(wa, n_workgroups, stream);
 }
 
