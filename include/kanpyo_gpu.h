@@ -83,7 +83,7 @@ typedef struct kgpu_token8 {
  *   index_dict      index.rs:75-84 + trie/da.rs:237-245
  *   connection_dict connection.rs:44-51
  *   morph_dict      morph.rs:61-72
- *   unk_dict        unk_dict.rs:60-73 (the trailing feature table is ignored)
+ *   unk_dict        unk_dict.rs:60-73 (the trailing feature table is ignored here: kgpu_dict_set_features takes it)
  *   char_category / invoke_list / group_list: the pub Vec<u8>/Vec<bool> fields
  *                   of CharCategoryDef (char_category_def.rs:14-20), one byte each */
 typedef struct kgpu_dict_blobs {
@@ -347,6 +347,41 @@ void kgpu_lattice_free(kgpu_lattice *l);
 int kgpu_index_build(const uint8_t *keys, const uint64_t *key_offsets, uint64_t n,
                      uint8_t **blob, size_t *blob_len);
 void kgpu_free(void *p);
+
+/* ---- the `kanpyo tokenize` output (reference src/bin/kanpyo.rs:106-126 tokenize, :174-197 print_tokens) ----
+ * Per token one line: surface, '\t', the morph's features joined with ',', '\n'.  The surface is input[position .. position + byte_len],
+ * or "EOS" for KGPU_CLASS_DUMMY; the features are empty for the dummy class and for id 0 (BOS_EOS_ID, src/lattice/node.rs:3), else
+ * morph_feature_table.morph_features[id - 1] (known) or unk_dict.morph_feature_table.morph_features[id - 1] (unknown) through name_list
+ * (:178-188).  A sentence without tokens (EOS unreachable, or KGPU_SENT_INVALID_UTF8) renders to 0 bytes. */
+
+/* The display tables, in the reference's own serialised form (bincode 2, standard config: kanpyo-dict/src/morph_feature.rs:6-37):
+ *   morph_feature_dict  morph_feature.dict (kanpyo-dict/src/dict.rs:58-59): dict.morph_feature_table.write_dict
+ *   unk_feature_dict    the tail of unk.dict behind the morph block (unk_dict.rs:71): dict.unk_dict.morph_feature_table.write_dict
+ * Trailing bytes are ignored.  KGPU_ERR_BAD_DICT wherever the reference would panic while printing: fewer rows than (unknown) morphs
+ * (kanpyo.rs:178-186, morph_features[id - 1]), a feature id at or past name_list.len() in a row a token can name (:181,188; rows past the
+ * morph count are never printed and not checked).  Like Dict::load, the call also fails on a truncated blob, an integer tag that does not
+ * fit its type and a name that is not UTF-8.  Once per handle (a second call: KGPU_ERR_INVALID_ARG); kgpu_dict_info.device_bytes
+ * grows by what is uploaded.  The lines calls below return KGPU_ERR_INVALID_ARG on a handle without them. */
+int kgpu_dict_set_features(kgpu_dict *d, const uint8_t *morph_feature_dict, size_t morph_feature_len,
+                           const uint8_t *unk_feature_dict, size_t unk_feature_len);
+/* Tokenizer::tokenize + print_tokens for n sentences in host memory: text_offsets[i] .. text_offsets[i + 1] are sentence i's lines
+ * (n + 1 entries).  status may be NULL.  KGPU_ERR_CAPACITY: *n_bytes is the exact size needed (the kgpu_tokenize_batch protocol). */
+int kgpu_tokenize_batch_lines(kgpu_dict *d, const uint8_t *utf8, const uint64_t *offsets, uint64_t n,
+                              uint8_t *text, uint64_t text_capacity, uint64_t *text_offsets, uint8_t *status, uint64_t *n_bytes);
+/* Device-resident: render records that a synced kgpu_tokenize_device batch (or anyone) left in HBM -- sentence i's records are
+ * d_tokens[d_tok_offsets[i] .. d_tok_offsets[i + 1]) -- into d_text / d_text_offsets (n + 1); enqueued on c's stream.  kgpu_ctx_sync_lines
+ * waits and reports the byte count: KGPU_ERR_CAPACITY (nothing written) when it exceeds text_capacity, KGPU_ERR_INVALID_ARG when a record
+ * names a class, id or surface the dictionary or its sentence does not have. */
+int kgpu_format_lines_device(kgpu_ctx *c, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n,
+                             const kgpu_token *d_tokens, const uint64_t *d_tok_offsets,
+                             uint8_t *d_text, uint64_t text_capacity, uint64_t *d_text_offsets);
+int kgpu_ctx_sync_lines(kgpu_ctx *c, uint64_t *n_bytes);
+/* Host helper: the CLI's read_line + trim_end (src/bin/kanpyo.rs:114-122) over a block of input.  Lines end at '\n' only (a final line
+ * without one counts; empty input has none); each line loses its trailing Unicode White_Space (U+0009-000D, U+0020, U+0085, U+00A0,
+ * U+1680, U+2000-200A, U+2028, U+2029, U+202F, U+205F, U+3000: complete encodings only, invalid bytes are kept).  The trimmed lines are
+ * packed into `out` (len bytes always suffice), delimited by offsets[0 .. *n_lines] (*n_lines + 1 entries).  KGPU_ERR_CAPACITY:
+ * offsets_capacity < lines + 1, *n_lines = lines. */
+int kgpu_split_lines(const uint8_t *in, uint64_t len, uint8_t *out, uint64_t *offsets, uint64_t offsets_capacity, uint64_t *n_lines);
 
 #ifdef __cplusplus
 }

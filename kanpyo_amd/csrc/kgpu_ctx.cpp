@@ -71,8 +71,11 @@ extern "C" void kgpu_ctx_destroy(kgpu_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->dict->device);
     if (c->pending && c->done_ev) (void)hipEventSynchronize(c->done_ev);
+    if (c->lines_pending && c->lines_ev) (void)hipEventSynchronize(c->lines_ev);
     ctx_retire(c);
     if (c->done_ev) (void)hipEventDestroy(c->done_ev);
+    if (c->lines_ev) (void)hipEventDestroy(c->lines_ev);
+    c->lines_len.release(); c->lines_ctl.release(); c->lines_text.release(); c->lines_off.release(); c->lines_status.release();
     if (c->switch_ev) (void)hipEventDestroy(c->switch_ev);
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
     c->arena.release(); c->ovf.release(); c->stat_slots.release(); c->stage.release(); c->tok_count.release();
@@ -413,6 +416,71 @@ extern "C" int kgpu_ctx_get_routing(kgpu_ctx *c, kgpu_routing *out, size_t out_s
     if (!c || !out || out_size < 8) { set_error("kgpu_ctx_get_routing: bad argument"); return KGPU_ERR_INVALID_ARG; }
     std::memcpy(out, &c->rt, std::min(out_size, sizeof(kgpu_routing)));
     if (reset) c->rt = kgpu_routing{};
+    return KGPU_OK;
+}
+
+// ------------------------------------------------------- the CLI's output lines (kgpu_format.hip; reference src/bin/kanpyo.rs:174-197)
+int kgpu::enqueue_lines(kgpu_ctx *c, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n, const kgpu_token *d_tokens, const uint64_t *d_tok_offsets,
+                        uint8_t *d_text, uint64_t text_capacity, uint64_t *d_text_offsets, const uint8_t *status_in, uint8_t *status_out, const char *who) {
+    kgpu_dict *d = c->dict;
+    {
+        std::lock_guard<std::mutex> g(d->feat_mu);
+        if (!d->feat) { set_error("%s: the dictionary has no feature tables: call kgpu_dict_set_features first", who); return KGPU_ERR_INVALID_ARG; }
+    }
+    if (c->lines_pending) { c->lines_pending = false; HIPCHECK(hipEventSynchronize(c->lines_ev)); }   // (its words are about to be reset)
+    int rc;
+    if ((rc = c->lines_len.ensure((size_t)n * 8 + 8)) || (rc = c->lines_ctl.ensure(16, true))) return rc;
+    if (!c->lines_ev) HIPCHECK(hipEventCreateWithFlags(&c->lines_ev, hipEventDisableTiming));
+    unsigned long long *h = (unsigned long long *)c->lines_ctl.h;
+    h[0] = 0; h[1] = 0;   // (this context's previous render has been synced)
+    LinesArgs a{};
+    a.utf8 = d_utf8; a.offsets = d_offsets; a.n = n; a.tokens = d_tokens; a.tok_offsets = d_tok_offsets;
+    a.feat = d->feat; a.feat_off = d->feat_off;
+    a.n_morph = (uint32_t)d->info.n_morphs; a.n_rows = (uint32_t)(d->info.n_morphs + d->info.n_unk_morphs);
+    a.sent_len = (uint64_t *)c->lines_len.p;
+    a.text = d_text; a.text_cap = text_capacity; a.text_offsets = d_text_offsets;
+    a.status_in = status_in; a.status_out = status_out;
+    a.host_ctl = (unsigned long long *)c->lines_ctl.d;
+    const hipError_t e = (hipError_t)launch_format_lines(a, c->stream);
+    if (e != hipSuccess) { set_error("%s: render launch: %s", who, hipGetErrorString(e)); return KGPU_ERR_HIP; }
+    HIPCHECK(hipEventRecord(c->lines_ev, c->stream));
+    c->lines_pending = true;
+    c->lines_cap = text_capacity;
+    return KGPU_OK;
+}
+
+extern "C" int kgpu_format_lines_device(kgpu_ctx *c, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n,
+                                        const kgpu_token *d_tokens, const uint64_t *d_tok_offsets,
+                                        uint8_t *d_text, uint64_t text_capacity, uint64_t *d_text_offsets) {
+    const char *who = "kgpu_format_lines_device";
+    if (!c || !d_offsets || !d_tok_offsets || !d_text_offsets || (n && (!d_utf8 || !d_tokens)) || (text_capacity && !d_text)) {
+        set_error("%s: null argument", who);
+        return KGPU_ERR_INVALID_ARG;
+    }
+    if (c->pending) { set_error("%s: the context's tokenize batch is not synced (kgpu_ctx_sync) yet", who); return KGPU_ERR_INVALID_ARG; }
+    HIPCHECK(hipSetDevice(c->dict->device));
+    int rc;
+    if (c->lines_pending && (rc = kgpu_ctx_sync_lines(c, nullptr)) != KGPU_OK && rc != KGPU_ERR_CAPACITY) return rc;
+    return enqueue_lines(c, d_utf8, d_offsets, n, d_tokens, d_tok_offsets, d_text, text_capacity, d_text_offsets, nullptr, nullptr, who);
+}
+
+extern "C" int kgpu_ctx_sync_lines(kgpu_ctx *c, uint64_t *n_bytes) {
+    if (!c) { set_error("kgpu_ctx_sync_lines: null ctx"); return KGPU_ERR_INVALID_ARG; }
+    if (!c->lines_pending) { if (n_bytes) *n_bytes = 0; return KGPU_OK; }
+    HIPCHECK(hipSetDevice(c->dict->device));
+    c->lines_pending = false;
+    HIPCHECK(hipEventSynchronize(c->lines_ev));
+    const unsigned long long *h = (const unsigned long long *)c->lines_ctl.h;
+    const uint64_t need = h[0];
+    if (n_bytes) *n_bytes = need;
+    if (h[1]) {
+        set_error("kgpu_ctx_sync_lines: a token record names a class, morph id or surface outside the dictionary or its sentence");
+        return KGPU_ERR_INVALID_ARG;
+    }
+    if (need > c->lines_cap) {
+        set_error("text buffer too small: need %llu, capacity %llu", (unsigned long long)need, (unsigned long long)c->lines_cap);
+        return KGPU_ERR_CAPACITY;
+    }
     return KGPU_OK;
 }
 

@@ -122,6 +122,25 @@ int launch_step(const DictView &d, const BatchArgs &a, const Step &s, uint32_t s
 int launch_general_only(const DictView &d, const BatchArgs &a, void *stream);  // kgpu_lattice_dump: HBM-scratch kernel alone
 int launch_small_call(const DictView &d, const BatchArgs &a, void *stream);  // pool kernel alone, one sentence per wavefront
 int launch_scan_compact(const BatchArgs &a, Control *host_ctl, void *stream, bool small_workgroups);  // host_ctl: device pointer of the pinned result block
+// The CLI's output lines of a batch (kgpu_format.hip; reference src/bin/kanpyo.rs:174-197): `surface \t f1,f2,... \n` per token.
+struct LinesArgs {
+    const uint8_t *utf8;           // the batch's text, biased like BatchArgs::utf8: sentence s is utf8[offsets[s] .. offsets[s + 1])
+    const uint64_t *offsets;       // n + 1
+    uint64_t n;
+    const kgpu_token *tokens;      // sentence s's records: tokens[tok_offsets[s] .. tok_offsets[s + 1])
+    const uint64_t *tok_offsets;   // n + 1
+    const uint8_t *feat;           // the dictionary's joined feature strings (kgpu_features.cpp) ...
+    const uint32_t *feat_off;      // ... row r is feat[feat_off[r] .. feat_off[r + 1]); known id k at row k - 1, unknown id u at n_morph + u - 1
+    uint32_t n_morph, n_rows;      // rows = known + unknown morphs
+    uint64_t *sent_len;            // device scratch, n + 1: each sentence's rendered bytes, then (k_lines_scan, in place) their offsets
+    uint8_t *text; uint64_t text_cap;
+    uint64_t *text_offsets;        // n + 1: the scan's mirror for the caller (may be mapped host memory: the write pass reads sent_len)
+    const uint8_t *status_in;      // optional: mirrored into status_out (mapped host memory) by the length pass
+    uint8_t *status_out;
+    unsigned long long *host_ctl;  // device pointer of pinned, mapped words: [0] total bytes, [1] a record out of range
+};
+int launch_format_lines(const LinesArgs &a, void *stream);
+
 int pool_workgroups_per_cu(uint32_t pool_bytes, uint32_t waves);
 int window_workgroups_per_cu(uint32_t lds_bytes);
 int window_team_workgroups_per_cu(uint32_t lds_bytes);

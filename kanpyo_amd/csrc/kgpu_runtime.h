@@ -82,6 +82,11 @@ struct kgpu_dict {
     std::vector<hipStream_t> long_streams;
     unsigned next_long = 0;
     std::vector<uint32_t> left_of_rank, right_of_rank;  // device (ranked) context id -> the dictionary's own; empty = identity
+    // kgpu_dict_set_features (kgpu_features.cpp): every known and unknown morph's features joined with ',', in the one index space of the
+    // morph records (unknown id u at row n_morphs + u - 1): row r is feat[feat_off[r] .. feat_off[r + 1]).  Set once, before any lines call.
+    std::mutex feat_mu;
+    const uint8_t *feat = nullptr;
+    const uint32_t *feat_off = nullptr;
     // One reference for the handle the caller holds plus one per live context: the tables and the shared
     // streams go when the last one does (a context outliving kgpu_dict_destroy keeps working).
     std::atomic<int> refs{1};
@@ -115,6 +120,13 @@ struct kgpu_ctx {
     // single-launch small calls: one pinned, device-mapped block (input | offsets | tokens | token offsets | status)
     uint8_t *sm_host = nullptr, *sm_dev = nullptr;
     uint32_t sm_seq = 0;
+    // the CLI's output lines (kgpu_format.hip): per-sentence scratch, the mapped words the scan publishes ([0] bytes, [1] a bad record), and for
+    // kgpu_tokenize_batch_lines the mapped text, text offsets and status of a chunk (the render's stores are the transfer)
+    DevBuf lines_len;
+    PinBuf lines_ctl, lines_text, lines_off, lines_status;
+    hipEvent_t lines_ev = nullptr;
+    bool lines_pending = false;
+    uint64_t lines_cap = 0;
     // last enqueued batch (for the arena-overflow retry and for sync)
     BatchArgs last{};
     bool pending = false;
@@ -210,6 +222,9 @@ int ctx_h2d(kgpu_ctx *c, void *dst, const void *src, size_t bytes, const char *w
 int tokenize_device_impl(kgpu_ctx *c, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n, uint64_t total_bytes,
                          kgpu_token *d_tokens, kgpu_token8 *d_tokens8, uint32_t *d_first, uint8_t *status8, uint64_t *toff8, uint64_t token_capacity,
                          uint64_t *d_tok_offsets, uint8_t *d_status, const char *who);
+// the render of a batch's lines on c->stream behind whatever is queued there; status_in / status_out: optional mirror of the status bytes
+int enqueue_lines(kgpu_ctx *c, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n, const kgpu_token *d_tokens, const uint64_t *d_tok_offsets,
+                  uint8_t *d_text, uint64_t text_capacity, uint64_t *d_text_offsets, const uint8_t *status_in, uint8_t *status_out, const char *who);
 
 // kgpu_host.cpp
 void parallel_copy(void *dst, const void *src, size_t bytes);
@@ -218,13 +233,16 @@ bool is_pinned_host(const void *p);
 struct MergeSrc { const kgpu_token8 *rec; const uint32_t *first; const uint64_t *toff; const uint8_t *st; };
 // One chunk of a large host call on a pooled context (kgpu_host.cpp: pipe_submit; kgpu_multi.cpp: shard_submit).  Its input goes to the device as
 // ONE block [offsets | bytes] (c->in_block, staged in c->pin_in unless it is copied from pinned memory directly); the compaction kernel writes the
-// results into the mapped block c->pin_out: records | first | token offsets | status.
+// results into the mapped block c->pin_out: records | first | token offsets | status.  With `lines` (kgpu_tokenize_batch_lines) the 24-byte records
+// stay in HBM (c->out_tok) and the render behind the chain writes the chunk's text, text offsets and status into c's mapped lines_* blocks.
 struct ChunkBlock {
     uint64_t n = 0, total = 0, cap = 0;                    // sentences, bytes, token capacity
+    bool lines = false;
     size_t in_off = 0;                                     // the offsets' share of the input block: the bytes follow
     size_t off_first = 0, off_toff = 0, off_status = 0;    // inside pin_out
     int prepare(kgpu_ctx *c, uint64_t n, uint64_t total, bool staged);   // the layout, and c's buffers big enough for it
     int launch(kgpu_ctx *c, uint64_t base, const char *who) const;        // the chain over in_block (offsets start at `base`), records into pin_out
+    int render(kgpu_ctx *c, uint64_t base, const char *who) const;        // `lines`: the render of the chunk's records (the launch queues one behind its chain)
     MergeSrc results(const kgpu_ctx *c) const;                           // where the host reads them once the chunk is synced
 };
 

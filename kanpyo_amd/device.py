@@ -55,6 +55,18 @@ class DeviceContext:
         _lib.check(_lib.lib().kgpu_ctx_sync(self._h, C.byref(n)))
         return int(n.value)
 
+    def format_lines(self, d_utf8: int, d_offsets: int, n: int, d_tokens: int, d_tok_offsets: int, d_text: int, text_capacity: int, d_text_offsets: int):
+        """kgpu_format_lines_device: enqueue the `kanpyo tokenize` lines of records a synced batch left in HBM (the handle needs set_features)."""
+        _lib.check(_lib.lib().kgpu_format_lines_device(
+            self._h, C.c_void_p(d_utf8), C.c_void_p(d_offsets), n, C.c_void_p(d_tokens), C.c_void_p(d_tok_offsets), C.c_void_p(d_text),
+            text_capacity, C.c_void_p(d_text_offsets)))
+
+    def sync_lines(self) -> int:
+        """Wait for the enqueued render; returns its byte count."""
+        n = C.c_uint64(0)
+        _lib.check(_lib.lib().kgpu_ctx_sync_lines(self._h, C.byref(n)))
+        return int(n.value)
+
     def set_profiling(self, mode: int):
         _lib.check(_lib.lib().kgpu_ctx_set_profiling(self._h, int(mode)))
 

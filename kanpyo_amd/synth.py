@@ -475,3 +475,67 @@ def mixed_case(sd: SynthDict, rng, sizes=(1, 5, 50, 120, 700, 4096, 9000)):
     mix += rng.sample(EDGE_SENTENCES, rng.randrange(len(EDGE_SENTENCES)))
     rng.shuffle(mix)
     return mix
+
+
+# ------------------------------------------------------------------- display tables (the CLI's feature columns)
+
+# IPADIC-shaped feature rows: POS x4, conjugation type, conjugation form -- then base form, reading, pronunciation (9 fields, ipadic's *.csv)
+_KNOWN_POS = [
+    ("名詞", "一般", "*", "*", "*", "*"), ("名詞", "固有名詞", "地域", "一般", "*", "*"), ("名詞", "サ変接続", "*", "*", "*", "*"),
+    ("名詞", "副詞可能", "*", "*", "*", "*"), ("動詞", "自立", "*", "*", "五段・ラ行", "基本形"), ("動詞", "自立", "*", "*", "一段", "連用形"),
+    ("動詞", "非自立", "*", "*", "五段・カ行促音便", "連用タ接続"), ("形容詞", "自立", "*", "*", "形容詞・アウオ段", "基本形"),
+    ("助詞", "格助詞", "一般", "*", "*", "*"), ("助詞", "係助詞", "*", "*", "*", "*"), ("助詞", "連体化", "*", "*", "*", "*"),
+    ("助動詞", "*", "*", "*", "特殊・タ", "基本形"), ("副詞", "一般", "*", "*", "*", "*"), ("連体詞", "*", "*", "*", "*", "*"),
+    ("接続詞", "*", "*", "*", "*", "*"), ("記号", "一般", "*", "*", "*", "*"),
+]
+_UNK_ROWS = [
+    ("名詞", "一般", "*", "*", "*", "*", "*"), ("名詞", "固有名詞", "地域", "一般", "*", "*", "*"), ("名詞", "固有名詞", "人名", "一般", "*", "*", "*"),
+    ("名詞", "固有名詞", "組織", "*", "*", "*", "*"), ("名詞", "数", "*", "*", "*", "*", "*"), ("名詞", "サ変接続", "*", "*", "*", "*", "*"),
+    ("記号", "一般", "*", "*", "*", "*", "*"), ("記号", "空白", "*", "*", "*", "*", "*"), ("形容詞", "自立", "*", "*", "*", "*", "*"),
+    ("感動詞", "*", "*", "*", "*", "*", "*"),
+]
+
+
+def record_surfaces(sd: SynthDict) -> list:
+    """Surface (str) of every known record, in id order: records are numbered in surface-byte order, a surface with duplicates takes
+    1 + IndexTable.dup[first id] consecutive ids (index.rs:46-51) -- read back from index.dict's duplicate map."""
+    import struct
+
+    blob = sd.dict.index_dict
+    (n_da,) = struct.unpack_from("<Q", blob, 0)
+    at = 8 + 8 * n_da
+    (m,) = struct.unpack_from("<Q", blob, at)
+    dup = dict(struct.iter_unpack("<qQ", blob[at + 8 : at + 8 + 16 * m]))
+    out, rid = [], 1
+    for k in sorted(sd.surfaces, key=lambda w: w.encode("utf-8")):
+        cnt = 1 + int(dup.get(rid, 0))
+        out.extend([k] * cnt)
+        rid += cnt
+    if len(out) != sd.dict.n_morphs:
+        raise ValueError(f"record_surfaces: {len(out)} records from the index, {sd.dict.n_morphs} morphs")
+    return out
+
+
+_HIRA_TO_KATA = {c: c + 0x60 for c in range(0x3041, 0x3097)}
+
+
+def feature_tables(sd: SynthDict, seed: int = 7):
+    """IPADIC-shaped display tables for a synthetic dictionary -> (known, unknown) MorphFeatureTable: nine fields per known record
+    (POS x4, conjugation type and form, base form = the surface, reading, pronunciation), seven per unknown row (unk.def).  Its own RNG:
+    the dictionary's and the corpora's draws are untouched."""
+    from .dictfile import MorphFeatureTable
+
+    rng = np.random.default_rng(seed)
+    surf = record_surfaces(sd)
+    pos = rng.integers(0, len(_KNOWN_POS), size=len(surf))
+    rows = []
+    for s, p in zip(surf, pos):
+        reading = s.translate(_HIRA_TO_KATA)
+        rows.append([*_KNOWN_POS[p], s, reading, reading])
+    import struct
+
+    unk = sd.dict.unk_dict
+    (k,) = struct.unpack_from("<Q", unk, 0)
+    (n_unk,) = struct.unpack_from("<q", unk, 8 + 17 * k)
+    urows = [list(_UNK_ROWS[i]) for i in rng.integers(0, len(_UNK_ROWS), size=n_unk)]
+    return MorphFeatureTable.from_features(rows), MorphFeatureTable.from_features(urows)

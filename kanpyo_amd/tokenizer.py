@@ -129,6 +129,50 @@ class Tokenizer:
             _lib.check(rc)
             return tokens[: int(got.value)], toff[: n + 1], status[:n]
 
+    # ---- the CLI's output lines (`kanpyo tokenize`, src/bin/kanpyo.rs:174-197) ------
+    def set_features(self, known, unk) -> None:
+        """kgpu_dict_set_features: the display tables -- morph_feature.dict's and unk.dict's MorphFeatureTable (or their bincode
+        bytes) -- uploaded once per handle.  The lines calls need them."""
+        blobs = [np.frombuffer(t if isinstance(t, (bytes, bytearray)) else t.encode(), dtype=np.uint8) for t in (known, unk)]
+        _lib.check(_lib.lib().kgpu_dict_set_features(self._h, *[x for b in blobs for x in (b.ctypes.data if b.size else None, b.size)]))
+
+    def tokenize_lines_packed(self, utf8: np.ndarray, offsets: np.ndarray, out=None):
+        """-> (text[uint8], text_offsets[uint64 n+1], status[uint8 n]): sentence i's `surface\\tfeatures\\n` lines are
+        text[text_offsets[i]:text_offsets[i+1]].  out=(text, text_offsets, status): caller-owned arrays to reuse."""
+        utf8 = np.ascontiguousarray(utf8, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = offsets.size - 1
+        if n < 0:
+            raise ValueError("offsets needs n+1 entries")
+        total = int(offsets[-1] - offsets[0]) if n else 0
+        cap = total * 16 + 8 * n + 64
+        L = _lib.lib()
+        while True:
+            if out is not None:
+                text, toff, status = out
+                if text.dtype != np.uint8 or toff.dtype != np.uint64 or status.dtype != np.uint8 or toff.size < n + 1 or status.size < n:
+                    raise ValueError("out=(text[uint8], text_offsets[uint64 >= n+1], status[uint8 >= n])")
+                cap = text.size
+            else:
+                text = np.empty(max(cap, 1), dtype=np.uint8)
+                toff = np.empty(n + 1, dtype=np.uint64)
+                status = np.empty(max(n, 1), dtype=np.uint8)
+            status[: max(n, 1)] = 0
+            got = C.c_uint64(0)
+            rc = L.kgpu_tokenize_batch_lines(self._h, utf8.ctypes.data if utf8.size else None, offsets.ctypes.data, n, text.ctypes.data, cap,
+                                             toff.ctypes.data, status.ctypes.data, C.byref(got))
+            if rc == _lib.KGPU_ERR_CAPACITY and out is None:
+                cap = int(got.value)  # exact size reported by the device
+                continue
+            _lib.check(rc)
+            return text[: int(got.value)], toff[: n + 1], status[:n]
+
+    def tokenize_lines(self, sentences: Sequence) -> bytes:
+        """What `kanpyo tokenize` prints for these sentences (str or bytes), one after the other."""
+        utf8, offs = pack_sentences(sentences)
+        text, _, _ = self.tokenize_lines_packed(utf8, offs)
+        return text.tobytes()
+
     def routing(self, reset: bool = False) -> dict:
         """kgpu_dict_get_routing: the routing counters of the handle's pooled contexts (small_calls, combined_calls, ...)."""
         r = _lib.Routing()
@@ -156,6 +200,19 @@ class Tokenizer:
     def tokenize(self, input: str) -> List[Token]:
         """Tokenizer::tokenize (src/tokenizer.rs:16-45): one sentence == a batch of one."""
         return self.tokenize_batch([input])[0]
+
+
+def split_lines(block) -> tuple:
+    """kgpu_split_lines: the CLI's read_line + trim_end (src/bin/kanpyo.rs:114-122) over a block of input bytes
+    -> (uint8 trimmed lines packed, uint64 offsets[n+1]).  Host only: needs no device."""
+    src = np.frombuffer(bytes(block), dtype=np.uint8) if not isinstance(block, np.ndarray) else np.ascontiguousarray(block, dtype=np.uint8)
+    n_max = int(np.count_nonzero(src == 10)) + 1
+    out = np.empty(max(src.size, 1), dtype=np.uint8)
+    offs = np.empty(n_max + 1, dtype=np.uint64)
+    n = C.c_uint64(0)
+    _lib.check(_lib.lib().kgpu_split_lines(src.ctypes.data if src.size else None, src.size, out.ctypes.data, offs.ctypes.data, offs.size, C.byref(n)))
+    k = int(n.value)
+    return out[: int(offs[k])], offs[: k + 1]
 
 
 def tokenize_packed_multi(tokenizers: Sequence[Tokenizer], utf8: np.ndarray, offsets: np.ndarray, token_capacity: int | None = None, out=None, compact: bool = False):
