@@ -382,6 +382,22 @@ int kgpu_ctx_sync_lines(kgpu_ctx *c, uint64_t *n_bytes);
  * packed into `out` (len bytes always suffice), delimited by offsets[0 .. *n_lines] (*n_lines + 1 entries).  KGPU_ERR_CAPACITY:
  * offsets_capacity < lines + 1, *n_lines = lines. */
 int kgpu_split_lines(const uint8_t *in, uint64_t len, uint8_t *out, uint64_t *offsets, uint64_t offsets_capacity, uint64_t *n_lines);
+/* read_line + trim_end (src/bin/kanpyo.rs:114-122) over a block resident in HBM; semantics of kgpu_split_lines.
+ * d_out: len bytes always suffice; must not overlap d_in (KGPU_ERR_INVALID_ARG).  d_offsets: offsets_capacity entries.  len of 2^32 or
+ * more is KGPU_ERR_INVALID_ARG (positions are 32-bit on the device): split the block at a '\n'.  len == 0 is valid: no lines, offsets[0] = 0.
+ * Enqueued on c's stream.  kgpu_ctx_sync_split waits and reports the line count and the packed byte count;
+ * KGPU_ERR_CAPACITY when n_lines + 1 > offsets_capacity (*n_lines is set; d_out / d_offsets contents unspecified). */
+int kgpu_split_lines_device(kgpu_ctx *c, const uint8_t *d_in, uint64_t len, uint8_t *d_out,
+                            uint64_t *d_offsets, uint64_t offsets_capacity);
+int kgpu_ctx_sync_split(kgpu_ctx *c, uint64_t *n_lines, uint64_t *n_bytes);
+
+/* tokenize (:106-126) over a raw block of input in HOST memory: split + trim on the device, Tokenizer::tokenize and
+ * print_tokens per line; the outputs and the errors of kgpu_tokenize_batch_lines, with the line count found, not given.
+ * text_offsets / status: offsets_capacity / offsets_capacity - 1 entries (status may be NULL).  n_lines and n_bytes are required.
+ * KGPU_ERR_CAPACITY: *n_lines and *n_bytes are the exact sizes needed (either may be the one that did not fit). */
+int kgpu_tokenize_text_lines(kgpu_dict *d, const uint8_t *text, uint64_t len,
+                             uint8_t *out_text, uint64_t text_capacity, uint64_t *text_offsets, uint64_t offsets_capacity,
+                             uint8_t *status, uint64_t *n_lines, uint64_t *n_bytes);
 
 #ifdef __cplusplus
 }

@@ -27,6 +27,7 @@ SYMBOLS = [
     "kgpu_host_alloc", "kgpu_host_free", "kgpu_lattice_dump", "kgpu_lattice_free",
     "kgpu_dict_get_routing", "kgpu_tokenize_batch_multi", "kgpu_tokenize_batch_multi_compact", "kgpu_multi_create", "kgpu_multi_destroy", "kgpu_multi_tokenize_device", "kgpu_multi_sync",
     "kgpu_dict_set_features", "kgpu_tokenize_batch_lines", "kgpu_format_lines_device", "kgpu_ctx_sync_lines", "kgpu_split_lines",
+    "kgpu_split_lines_device", "kgpu_ctx_sync_split", "kgpu_tokenize_text_lines",
 ]
 
 
@@ -166,6 +167,9 @@ def lib():
         L.kgpu_format_lines_device.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, vp, C.c_uint64, vp]
         L.kgpu_ctx_sync_lines.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.kgpu_split_lines.argtypes = [vp, C.c_uint64, vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.kgpu_split_lines_device.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint64]
+        L.kgpu_ctx_sync_split.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.kgpu_tokenize_text_lines.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.kgpu_debug_feature_pool.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_uint64, C.c_uint64, vp, C.c_uint64, vp, C.POINTER(C.c_uint64)]
         _lib = L
     return _lib

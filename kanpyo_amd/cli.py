@@ -3,8 +3,9 @@
 Its stdout is the reference binary's, byte for byte: one `surface\\tf1,f2,...` line per token, sentences one after the other.  With INPUT
 that one string is tokenized untrimmed; without it stdin is read line by line (split at '\\n', trailing Unicode White_Space trimmed, as
 read_line + trim_end do) -- here in blocks of whole lines, each tokenized and rendered on the device in one kgpu_tokenize_batch_lines
-call and written out as soon as it is done.  A line that is not UTF-8 ends the run as the reference's `expect` panic does: the lines
-before it are printed, exit status 101.  No subcommand means `tokenize` from stdin.  The `graphviz` subcommand is not served.
+call and written out as soon as it is done.  `--split device` hands each block to kgpu_tokenize_text_lines as it was read: the split and the
+trim run on the device too (`--split host`, the default, splits with kgpu_split_lines on the host).  A line that is not UTF-8 ends the
+run as the reference's `expect` panic does: the lines before it are printed, exit status 101.  No subcommand means `tokenize` from stdin.  The `graphviz` subcommand is not served.
 """
 from __future__ import annotations
 
@@ -67,11 +68,12 @@ def tokenize(args, stdin, stdout) -> int:
     tok.set_features(df.morph_feature_table, df.unk_feature_table)
     if args.input is not None:   # that one string, untrimmed
         one = np.frombuffer(os.fsencode(args.input), dtype=np.uint8)
-        blocks = iter([(one, np.array([0, one.size], dtype=np.uint64))])
+        results = iter([tok.tokenize_lines_packed(one, np.array([0, one.size], dtype=np.uint64))])
+    elif args.split == "device":   # the block as it was read: split, trimmed, tokenized and rendered on the device
+        results = (tok.tokenize_text_lines(b) for b in _blocks(stdin, args.block_bytes))
     else:
-        blocks = (split_lines(b) for b in _blocks(stdin, args.block_bytes))
-    for utf8, offs in blocks:
-        text, toff, status = tok.tokenize_lines_packed(utf8, offs)
+        results = (tok.tokenize_lines_packed(*split_lines(b)) for b in _blocks(stdin, args.block_bytes))
+    for text, toff, status in results:
         bad = np.flatnonzero(status == 1)
         if bad.size:
             stdout.write(text[: int(toff[bad[0]])].tobytes())
@@ -90,6 +92,8 @@ def main(argv=None) -> int:
     t.add_argument("input", nargs="?", default=None, help="Input text to analyze [default: stdin]")
     t.add_argument("-d", "--dict", choices=["ipa"], default="ipa", help="Dictionary")
     t.add_argument("-c", "--custom-dict", default=None, help="Custom dictionary (.dict)")
+    t.add_argument("--split", choices=["host", "device"], default="host",
+                   help="Where stdin's blocks are split into lines and trimmed [default: host]")
     t.add_argument("--block-bytes", type=int, default=BLOCK_BYTES, help=argparse.SUPPRESS)
     args = p.parse_args(argv)
     if args.command is None:   # src/bin/kanpyo.rs:173: no subcommand == tokenize from stdin, default dictionary

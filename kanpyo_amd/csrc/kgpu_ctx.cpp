@@ -72,10 +72,13 @@ extern "C" void kgpu_ctx_destroy(kgpu_ctx *c) {
     (void)hipSetDevice(c->dict->device);
     if (c->pending && c->done_ev) (void)hipEventSynchronize(c->done_ev);
     if (c->lines_pending && c->lines_ev) (void)hipEventSynchronize(c->lines_ev);
+    if (c->split_pending && c->split_ev) (void)hipEventSynchronize(c->split_ev);
     ctx_retire(c);
     if (c->done_ev) (void)hipEventDestroy(c->done_ev);
     if (c->lines_ev) (void)hipEventDestroy(c->lines_ev);
     c->lines_len.release(); c->lines_ctl.release(); c->lines_text.release(); c->lines_off.release(); c->lines_status.release();
+    if (c->split_ev) (void)hipEventDestroy(c->split_ev);
+    c->split_agg.release(); c->split_raw.release(); c->split_text.release(); c->split_off.release(); c->split_ctl.release();
     if (c->switch_ev) (void)hipEventDestroy(c->switch_ev);
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
     c->arena.release(); c->ovf.release(); c->stat_slots.release(); c->stage.release(); c->tok_count.release();

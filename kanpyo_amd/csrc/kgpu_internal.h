@@ -140,6 +140,17 @@ struct LinesArgs {
     unsigned long long *host_ctl;  // device pointer of pinned, mapped words: [0] total bytes, [1] a record out of range
 };
 int launch_format_lines(const LinesArgs &a, void *stream);
+// read_line + trim_end over a block in HBM (kgpu_split.hip; reference src/bin/kanpyo.rs:114-122).
+struct SplitTile { uint32_t x, y, z, w; };   // one tile's aggregate, then its carry (kgpu_split.hip says which word is what)
+struct SplitArgs {
+    const uint8_t *in; uint64_t len;   // the block (any alignment), len < 2^32
+    uint8_t *out;                      // the trimmed lines packed back to back: len bytes always suffice
+    uint64_t *offsets; uint64_t off_cap;   // lines + 1 entries; nothing is stored when they do not fit
+    SplitTile *agg; uint32_t ntiles;   // device scratch, ntiles + 1 entries (split_tiles)
+    unsigned long long *host_ctl;      // device pointer of pinned, mapped words: [0] lines, [1] packed bytes
+};
+uint32_t split_tiles(const uint8_t *d_in, uint64_t len);
+int launch_split_lines(const SplitArgs &a, void *stream);
 
 int pool_workgroups_per_cu(uint32_t pool_bytes, uint32_t waves);
 int window_workgroups_per_cu(uint32_t lds_bytes);

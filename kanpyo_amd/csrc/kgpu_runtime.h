@@ -1,6 +1,6 @@
 // kanpyo_amd/csrc/kgpu_runtime.h -- the host runtime's own types and the functions its files share: kgpu_dict.cpp (dictionary),
 // kgpu_ctx.cpp (contexts, launch chain), kgpu_host.cpp (large host calls), kgpu_small.cpp (small calls), kgpu_multi.cpp (the
-// multi-device entry points).  Not part of the public ABI.
+// multi-device entry points), kgpu_split_host.cpp (lines of a raw block).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -127,6 +127,13 @@ struct kgpu_ctx {
     hipEvent_t lines_ev = nullptr;
     bool lines_pending = false;
     uint64_t lines_cap = 0;
+    // read_line + trim_end on the device (kgpu_split.hip): the tile aggregates, the mapped words the carry kernel publishes ([0] lines, [1] packed
+    // bytes), and for kgpu_tokenize_text_lines the device copy of the raw block, its packed lines and their offsets
+    DevBuf split_agg, split_raw, split_text, split_off;
+    PinBuf split_ctl;
+    hipEvent_t split_ev = nullptr;
+    bool split_pending = false;
+    uint64_t split_cap = 0;
     // last enqueued batch (for the arena-overflow retry and for sync)
     BatchArgs last{};
     bool pending = false;

@@ -67,6 +67,18 @@ class DeviceContext:
         _lib.check(_lib.lib().kgpu_ctx_sync_lines(self._h, C.byref(n)))
         return int(n.value)
 
+    def split_lines(self, d_in: int, len: int, d_out: int, d_offsets: int, offsets_capacity: int):
+        """kgpu_split_lines_device: enqueue read_line + trim_end over a block in HBM -> the trimmed lines packed in d_out (len bytes suffice,
+        no overlap with d_in) and their uint64 offsets in d_offsets."""
+        _lib.check(_lib.lib().kgpu_split_lines_device(
+            self._h, C.c_void_p(d_in), len, C.c_void_p(d_out), C.c_void_p(d_offsets), offsets_capacity))
+
+    def sync_split(self) -> tuple:
+        """Wait for the enqueued split; returns (n_lines, n_bytes): d_offsets holds n_lines + 1 entries, d_out n_bytes bytes."""
+        n, b = C.c_uint64(0), C.c_uint64(0)
+        _lib.check(_lib.lib().kgpu_ctx_sync_split(self._h, C.byref(n), C.byref(b)))
+        return int(n.value), int(b.value)
+
     def set_profiling(self, mode: int):
         _lib.check(_lib.lib().kgpu_ctx_set_profiling(self._h, int(mode)))
 

@@ -167,6 +167,26 @@ class Tokenizer:
             _lib.check(rc)
             return text[: int(got.value)], toff[: n + 1], status[:n]
 
+    def tokenize_text_lines(self, block):
+        """kgpu_tokenize_text_lines: a raw block of input (bytes or uint8 array) -> (text, text_offsets, status) as
+        tokenize_lines_packed(*split_lines(block)) gives them; the split and the trim run on the device."""
+        src = np.frombuffer(bytes(block), dtype=np.uint8) if not isinstance(block, np.ndarray) else np.ascontiguousarray(block, dtype=np.uint8)
+        cap, ocap = src.size * 16 + 64, src.size // 16 + 1024
+        L = _lib.lib()
+        while True:
+            text = np.empty(max(cap, 1), dtype=np.uint8)
+            toff = np.empty(ocap, dtype=np.uint64)
+            status = np.zeros(ocap, dtype=np.uint8)
+            n, got = C.c_uint64(0), C.c_uint64(0)
+            rc = L.kgpu_tokenize_text_lines(self._h, src.ctypes.data if src.size else None, src.size, text.ctypes.data, cap, toff.ctypes.data, ocap,
+                                            status.ctypes.data, C.byref(n), C.byref(got))
+            if rc == _lib.KGPU_ERR_CAPACITY and (int(got.value) > cap or int(n.value) + 1 > ocap):   # exact sizes reported by the device
+                cap, ocap = max(cap, int(got.value)), max(ocap, int(n.value) + 1)
+                continue
+            _lib.check(rc)
+            k = int(n.value)
+            return text[: int(got.value)], toff[: k + 1], status[:k]
+
     def tokenize_lines(self, sentences: Sequence) -> bytes:
         """What `kanpyo tokenize` prints for these sentences (str or bytes), one after the other."""
         utf8, offs = pack_sentences(sentences)
