@@ -2,7 +2,8 @@
 //
 // Owns: context create / destroy, the lease of a dictionary's pooled contexts, the stream of a batch (ctx_pick_stream), the one
 // way a batch's host-to-device copy is queued (ctx_h2d), running a batch's chain (kgpu_chain.cpp decides it) with the scan and
-// compaction behind it, the reruns in kgpu_ctx_sync, the profiling / ablation / plan getters, and the lattice dump.
+// compaction behind it, the reruns in kgpu_ctx_sync, the profiling / ablation / plan getters, the two words a launch publishes to the
+// host (HostReport), the render of a batch's lines, and the lattice dump.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -71,14 +72,11 @@ extern "C" void kgpu_ctx_destroy(kgpu_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->dict->device);
     if (c->pending && c->done_ev) (void)hipEventSynchronize(c->done_ev);
-    if (c->lines_pending && c->lines_ev) (void)hipEventSynchronize(c->lines_ev);
-    if (c->split_pending && c->split_ev) (void)hipEventSynchronize(c->split_ev);
     ctx_retire(c);
     if (c->done_ev) (void)hipEventDestroy(c->done_ev);
-    if (c->lines_ev) (void)hipEventDestroy(c->lines_ev);
-    c->lines_len.release(); c->lines_ctl.release(); c->lines_text.release(); c->lines_off.release(); c->lines_status.release();
-    if (c->split_ev) (void)hipEventDestroy(c->split_ev);
-    c->split_agg.release(); c->split_raw.release(); c->split_text.release(); c->split_off.release(); c->split_ctl.release();
+    c->lines_report.release(); c->split_report.release();
+    c->lines_len.release(); c->lines_text.release(); c->lines_off.release(); c->lines_status.release();
+    c->split_agg.release(); c->split_raw.release(); c->split_text.release(); c->split_off.release();
     if (c->switch_ev) (void)hipEventDestroy(c->switch_ev);
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
     c->arena.release(); c->ovf.release(); c->stat_slots.release(); c->stage.release(); c->tok_count.release();
@@ -190,7 +188,7 @@ int kgpu::tokenize_device_impl(kgpu_ctx *c, const uint8_t *d_utf8, const uint64_
     if (c->pending && (rc = kgpu_ctx_sync(c, nullptr)) != KGPU_OK && rc != KGPU_ERR_CAPACITY) return rc;
     const Batch b{n, total_bytes, c->dict->steer.est_q8.load(std::memory_order_relaxed), c->stop_after, false, false, c->rt.batches > 0};
     if ((rc = ctx_pick_stream(c, b))) return rc;
-    if ((rc = c->arena.ensure(ARENA_INITIAL)) || (rc = c->stage.ensure((size_t)(total_bytes + n + 1) * sizeof(kgpu_token) + 64)) ||
+    if ((rc = c->arena.ensure(ARENA_INITIAL)) || (rc = c->stage.ensure((size_t)token_bound(total_bytes, n) * sizeof(kgpu_token) + 64)) ||
         (rc = c->tok_count.ensure((size_t)(n + 1) * 4)) ||
         (rc = c->ovf.ensure((size_t)(n + 1) * 4 * 4)))
         return rc;
@@ -422,20 +420,46 @@ extern "C" int kgpu_ctx_get_routing(kgpu_ctx *c, kgpu_routing *out, size_t out_s
     return KGPU_OK;
 }
 
+// ------------------------------------------------------- a launch's two words for the host (kgpu_runtime.h: HostReport)
+int HostReport::arm() {
+    if (pending) { pending = false; HIPCHECK(hipEventSynchronize(ev)); }
+    if (int rc = ctl.ensure(16, true)) return rc;
+    if (!ev) HIPCHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    unsigned long long *h = (unsigned long long *)ctl.h;
+    h[0] = 0; h[1] = 0;
+    return KGPU_OK;
+}
+int HostReport::record(hipStream_t stream, uint64_t cap_) {
+    HIPCHECK(hipEventRecord(ev, stream));
+    pending = true;
+    cap = cap_;
+    return KGPU_OK;
+}
+int HostReport::wait(uint64_t words[2]) {
+    pending = false;
+    HIPCHECK(hipEventSynchronize(ev));
+    const unsigned long long *h = (const unsigned long long *)ctl.h;
+    words[0] = h[0]; words[1] = h[1];
+    return KGPU_OK;
+}
+void HostReport::release() {
+    if (pending && ev) (void)hipEventSynchronize(ev);
+    if (ev) (void)hipEventDestroy(ev);
+    ev = nullptr; pending = false;
+    ctl.release();
+}
+
 // ------------------------------------------------------- the CLI's output lines (kgpu_format.hip; reference src/bin/kanpyo.rs:174-197)
+int kgpu::require_features(kgpu_dict *d, const char *who) {
+    std::lock_guard<std::mutex> g(d->feat_mu);
+    if (!d->feat) { set_error("%s: the dictionary has no feature tables: call kgpu_dict_set_features first", who); return KGPU_ERR_INVALID_ARG; }
+    return KGPU_OK;
+}
 int kgpu::enqueue_lines(kgpu_ctx *c, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n, const kgpu_token *d_tokens, const uint64_t *d_tok_offsets,
                         uint8_t *d_text, uint64_t text_capacity, uint64_t *d_text_offsets, const uint8_t *status_in, uint8_t *status_out, const char *who) {
     kgpu_dict *d = c->dict;
-    {
-        std::lock_guard<std::mutex> g(d->feat_mu);
-        if (!d->feat) { set_error("%s: the dictionary has no feature tables: call kgpu_dict_set_features first", who); return KGPU_ERR_INVALID_ARG; }
-    }
-    if (c->lines_pending) { c->lines_pending = false; HIPCHECK(hipEventSynchronize(c->lines_ev)); }   // (its words are about to be reset)
     int rc;
-    if ((rc = c->lines_len.ensure((size_t)n * 8 + 8)) || (rc = c->lines_ctl.ensure(16, true))) return rc;
-    if (!c->lines_ev) HIPCHECK(hipEventCreateWithFlags(&c->lines_ev, hipEventDisableTiming));
-    unsigned long long *h = (unsigned long long *)c->lines_ctl.h;
-    h[0] = 0; h[1] = 0;   // (this context's previous render has been synced)
+    if ((rc = require_features(d, who)) || (rc = c->lines_report.arm()) || (rc = c->lines_len.ensure((size_t)n * 8 + 8))) return rc;
     LinesArgs a{};
     a.utf8 = d_utf8; a.offsets = d_offsets; a.n = n; a.tokens = d_tokens; a.tok_offsets = d_tok_offsets;
     a.feat = d->feat; a.feat_off = d->feat_off;
@@ -443,13 +467,10 @@ int kgpu::enqueue_lines(kgpu_ctx *c, const uint8_t *d_utf8, const uint64_t *d_of
     a.sent_len = (uint64_t *)c->lines_len.p;
     a.text = d_text; a.text_cap = text_capacity; a.text_offsets = d_text_offsets;
     a.status_in = status_in; a.status_out = status_out;
-    a.host_ctl = (unsigned long long *)c->lines_ctl.d;
+    a.host_ctl = c->lines_report.dev();
     const hipError_t e = (hipError_t)launch_format_lines(a, c->stream);
     if (e != hipSuccess) { set_error("%s: render launch: %s", who, hipGetErrorString(e)); return KGPU_ERR_HIP; }
-    HIPCHECK(hipEventRecord(c->lines_ev, c->stream));
-    c->lines_pending = true;
-    c->lines_cap = text_capacity;
-    return KGPU_OK;
+    return c->lines_report.record(c->stream, text_capacity);
 }
 
 extern "C" int kgpu_format_lines_device(kgpu_ctx *c, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n,
@@ -463,25 +484,24 @@ extern "C" int kgpu_format_lines_device(kgpu_ctx *c, const uint8_t *d_utf8, cons
     if (c->pending) { set_error("%s: the context's tokenize batch is not synced (kgpu_ctx_sync) yet", who); return KGPU_ERR_INVALID_ARG; }
     HIPCHECK(hipSetDevice(c->dict->device));
     int rc;
-    if (c->lines_pending && (rc = kgpu_ctx_sync_lines(c, nullptr)) != KGPU_OK && rc != KGPU_ERR_CAPACITY) return rc;
+    if (c->lines_report.pending && (rc = kgpu_ctx_sync_lines(c, nullptr)) != KGPU_OK && rc != KGPU_ERR_CAPACITY) return rc;
     return enqueue_lines(c, d_utf8, d_offsets, n, d_tokens, d_tok_offsets, d_text, text_capacity, d_text_offsets, nullptr, nullptr, who);
 }
 
 extern "C" int kgpu_ctx_sync_lines(kgpu_ctx *c, uint64_t *n_bytes) {
     if (!c) { set_error("kgpu_ctx_sync_lines: null ctx"); return KGPU_ERR_INVALID_ARG; }
-    if (!c->lines_pending) { if (n_bytes) *n_bytes = 0; return KGPU_OK; }
+    if (!c->lines_report.pending) { if (n_bytes) *n_bytes = 0; return KGPU_OK; }
     HIPCHECK(hipSetDevice(c->dict->device));
-    c->lines_pending = false;
-    HIPCHECK(hipEventSynchronize(c->lines_ev));
-    const unsigned long long *h = (const unsigned long long *)c->lines_ctl.h;
+    uint64_t h[2];   // [0] bytes, [1] a bad record
+    if (int rc = c->lines_report.wait(h)) return rc;
     const uint64_t need = h[0];
     if (n_bytes) *n_bytes = need;
     if (h[1]) {
         set_error("kgpu_ctx_sync_lines: a token record names a class, morph id or surface outside the dictionary or its sentence");
         return KGPU_ERR_INVALID_ARG;
     }
-    if (need > c->lines_cap) {
-        set_error("text buffer too small: need %llu, capacity %llu", (unsigned long long)need, (unsigned long long)c->lines_cap);
+    if (need > c->lines_report.cap) {
+        set_error("text buffer too small: need %llu, capacity %llu", (unsigned long long)need, (unsigned long long)c->lines_report.cap);
         return KGPU_ERR_CAPACITY;
     }
     return KGPU_OK;

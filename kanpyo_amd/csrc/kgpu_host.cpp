@@ -1,8 +1,10 @@
 // kanpyo_amd/csrc/kgpu_host.cpp -- kgpu_tokenize_batch beyond the small calls: the large-call pipeline over host buffers.
 //
-// Owns: the worker pool (with no threads its tasks run on the calling thread), parallel_copy, is_pinned_host, the chunk's input
-// staging and mapped result block (ChunkBlock, shared with kgpu_multi.cpp), the 24-byte per-chunk fallback for tokens beyond the
-// 8-byte record (HostJob), the pipeline itself, and kgpu_host_alloc / kgpu_host_free.
+// Owns: the worker pool (with no threads its tasks run on the calling thread), parallel_copy, is_pinned_host, the argument check of a
+// host batch, a chunk's input block (ChunkInput) and mapped result block (ChunkBlock, shared with kgpu_multi.cpp), the output side of a
+// lines chunk (LinesChunk, shared with kgpu_split_host.cpp), the chunk sizes of the pipeline (the ring itself is run_pipeline,
+// kgpu_runtime.h), the 24-byte per-chunk fallback for tokens beyond the 8-byte record (HostJob), kgpu_tokenize_batch,
+// kgpu_tokenize_batch_lines, and kgpu_host_alloc / kgpu_host_free.
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
@@ -31,7 +33,7 @@ static int host_job_submit(HostJob &j, const uint8_t *utf8, const uint64_t *offs
     const uint64_t n = j.m, base = off[0], total = off[n] - base;
     j.rel.resize((size_t)n + 1);
     for (uint64_t i = 0; i <= n; ++i) j.rel[(size_t)i] = off[i] - base;
-    const uint64_t cap = total + n + 1;  // tokens <= chars + 1 <= bytes + 1 per sentence: never too small
+    const uint64_t cap = token_bound(total, n);
     int rc;
     if ((rc = c->in_utf8.ensure((size_t)total + 16)) || (rc = c->in_off.ensure((size_t)(n + 1) * 8)) ||
         (rc = c->out_tok.ensure((size_t)cap * sizeof(kgpu_token) + 64)) ||
@@ -136,51 +138,85 @@ WorkerPool &workers() {
 }
 }  // namespace kgpu
 
-// The layout of a chunk's two blocks (kgpu_runtime.h: ChunkBlock) and the context's buffers big enough for it.
-int ChunkBlock::prepare(kgpu_ctx *c, uint64_t n_, uint64_t total_, bool staged) {
+// The layout of a chunk's input block (kgpu_runtime.h: ChunkInput) and the context's buffers big enough for it.
+int ChunkInput::prepare(kgpu_ctx *c, uint64_t n_, uint64_t total_, bool staged) {
     n = n_; total = total_;
-    cap = total + n + 1;  // tokens <= chars + 1 <= bytes + 1 per sentence: never too small
     in_off = ((size_t)(n + 1) * 8 + 63) & ~(size_t)63;
     const size_t in_bytes = in_off + (size_t)total + 16;
+    int rc;
+    if ((rc = c->in_block.ensure(in_bytes)) || (staged && (rc = c->pin_in.ensure(in_bytes, false)))) return rc;
+    return KGPU_OK;
+}
+// ... and of its mapped result block (ChunkBlock)
+int ChunkBlock::prepare(kgpu_ctx *c, uint64_t n, uint64_t total, bool staged) {
+    cap = token_bound(total, n);
     off_first = ((size_t)cap * 8 + 63) & ~(size_t)63;
     off_toff = off_first + (((size_t)n * 8 + 63) & ~(size_t)63);
     off_status = off_toff + (((size_t)(n + 1) * 8 + 63) & ~(size_t)63);
     int rc;
-    if (lines) {   // (the text block starts at 16 bytes per input byte -- cfg 2 renders about 14 -- and grows when a chunk's text outgrows it: pipe_finish_lines)
-        if ((rc = c->in_block.ensure(in_bytes)) || (rc = c->out_tok.ensure((size_t)cap * sizeof(kgpu_token) + 64)) || (rc = c->out_status.ensure((size_t)n + 16)) ||
-            (rc = c->out_off.ensure((size_t)(n + 1) * 8)) || (staged && (rc = c->pin_in.ensure(in_bytes, false))) ||
-            (rc = c->lines_off.ensure((size_t)(n + 1) * 8, true)) || (rc = c->lines_status.ensure((size_t)n + 16, true)) ||
-            (rc = c->lines_text.ensure((size_t)total * 16 + 4096, true)))
-            return rc;
-        return KGPU_OK;
-    }
-    if ((rc = c->in_block.ensure(in_bytes)) || (rc = c->pin_out.ensure(off_status + (size_t)n + 64, true)) || (rc = c->out_status.ensure((size_t)n + 16)) ||
-        (rc = c->out_off.ensure((size_t)(n + 1) * 8)) || (staged && (rc = c->pin_in.ensure(in_bytes, false))))
+    if ((rc = in.prepare(c, n, total, staged)) || (rc = c->pin_out.ensure(off_status + (size_t)n + 64, true)) || (rc = c->out_status.ensure((size_t)n + 16)) ||
+        (rc = c->out_off.ensure((size_t)(n + 1) * 8)))
         return rc;
     return KGPU_OK;
 }
-// The launch chain over the input block (its offsets start at `base`: the text pointer is biased by it), 8-byte records into the mapped block --
-// or, for a lines call, 24-byte records into HBM and the render behind them.
+// The launch chain over the input block (its offsets start at `base`), 8-byte records into the mapped block.
 int ChunkBlock::launch(kgpu_ctx *c, uint64_t base, const char *who) const {
-    uint8_t *dblk = (uint8_t *)c->in_block.p, *po = (uint8_t *)c->pin_out.d;
-    if (lines) {
-        const int rc = tokenize_device_impl(c, dblk + in_off - base, (const uint64_t *)dblk, n, total, (kgpu_token *)c->out_tok.p, nullptr, nullptr, nullptr, nullptr,
-                                            cap, (uint64_t *)c->out_off.p, (uint8_t *)c->out_status.p, who);
-        return rc ? rc : render(c, base, who);
-    }
-    return tokenize_device_impl(c, dblk + in_off - base, (const uint64_t *)dblk, n, total, nullptr, (kgpu_token8 *)po, (uint32_t *)(po + off_first), po + off_status,
+    uint8_t *po = (uint8_t *)c->pin_out.d;
+    return tokenize_device_impl(c, in.d_text(c, base), in.d_offsets(c), in.n, in.total, nullptr, (kgpu_token8 *)po, (uint32_t *)(po + off_first), po + off_status,
                                 (uint64_t *)(po + off_toff), cap, (uint64_t *)c->out_off.p, (uint8_t *)c->out_status.p, who);
-}
-// The chunk's lines into the context's mapped blocks: text, chunk-relative text offsets, status.
-int ChunkBlock::render(kgpu_ctx *c, uint64_t base, const char *who) const {
-    uint8_t *dblk = (uint8_t *)c->in_block.p;
-    return enqueue_lines(c, dblk + in_off - base, (const uint64_t *)dblk, n, (const kgpu_token *)c->out_tok.p, (const uint64_t *)c->out_off.p,
-                         (uint8_t *)c->lines_text.d, c->lines_text.bytes, (uint64_t *)c->lines_off.d, (const uint8_t *)c->out_status.p,
-                         (uint8_t *)c->lines_status.d, who);
 }
 MergeSrc ChunkBlock::results(const kgpu_ctx *c) const {
     const uint8_t *ph = (const uint8_t *)c->pin_out.h;
     return MergeSrc{(const kgpu_token8 *)ph, (const uint32_t *)(ph + off_first), (const uint64_t *)(ph + off_toff), ph + off_status};
+}
+
+// ---- the output side of a lines chunk (kgpu_runtime.h: LinesChunk) ------------------------------------------
+int LinesChunk::prepare(kgpu_ctx *c, uint64_t n_, uint64_t total_) {
+    n = n_; total = total_;
+    int rc;   // (the text block starts at 16 bytes per input byte -- cfg 2 renders about 14 -- and grows when a chunk's text outgrows it: finish)
+    if ((rc = c->out_tok.ensure((size_t)token_bound(total, n) * sizeof(kgpu_token) + 64)) || (rc = c->out_status.ensure((size_t)n + 16)) ||
+        (rc = c->out_off.ensure((size_t)(n + 1) * 8)) || (rc = c->lines_off.ensure((size_t)(n + 1) * 8, true)) ||
+        (rc = c->lines_status.ensure((size_t)n + 16, true)) || (rc = c->lines_text.ensure((size_t)total * 16 + 4096, true)))
+        return rc;
+    return KGPU_OK;
+}
+// The launch chain over the chunk's input where it lies in device memory, 24-byte records into HBM, and the render behind them.
+int LinesChunk::launch(kgpu_ctx *c, const uint8_t *d_utf8_, const uint64_t *d_offsets_, const char *who) {
+    d_utf8 = d_utf8_; d_offsets = d_offsets_;
+    const int rc = tokenize_device_impl(c, d_utf8, d_offsets, n, total, (kgpu_token *)c->out_tok.p, nullptr, nullptr, nullptr, nullptr, token_bound(total, n),
+                                        (uint64_t *)c->out_off.p, (uint8_t *)c->out_status.p, who);
+    return rc ? rc : render(c, who);
+}
+// The chunk's lines into the context's mapped blocks: text, chunk-relative text offsets, status.
+int LinesChunk::render(kgpu_ctx *c, const char *who) const {
+    return enqueue_lines(c, d_utf8, d_offsets, n, (const kgpu_token *)c->out_tok.p, (const uint64_t *)c->out_off.p, (uint8_t *)c->lines_text.d, c->lines_text.bytes,
+                         (uint64_t *)c->lines_off.d, (const uint8_t *)c->out_status.p, (uint8_t *)c->lines_status.d, who);
+}
+// Wait for the chunk's render (its text is in the context's mapped block then) and copy the text behind the bytes already delivered (or only count,
+// once a buffer of the caller's has overflowed).  A rerun of the chunk's chain inside kgpu_ctx_sync came after the render queued behind the first
+// pass: the render once more; a text block too small for the chunk: a bigger one and the render once more.
+int LinesChunk::finish(kgpu_ctx *c, uint64_t lo, LinesSink &s, const char *who) const {
+    const auto reruns = [c] { return c->rt.window_reruns + c->rt.tail_reruns + c->rt.arena_regrows; };
+    const uint64_t r0 = reruns();
+    int rc = kgpu_ctx_sync(c, nullptr);   // (24-byte records with capacity token_bound: never too small)
+    if (rc) return rc;
+    if (reruns() != r0 && (rc = render(c, who))) return rc;
+    uint64_t bytes = 0;
+    rc = kgpu_ctx_sync_lines(c, &bytes);
+    if (rc == KGPU_ERR_CAPACITY) {
+        if ((rc = c->lines_text.ensure((size_t)bytes + 64, true)) || (rc = render(c, who))) return rc;
+        rc = kgpu_ctx_sync_lines(c, &bytes);
+    }
+    if (rc) return rc;
+    if (s.text_done + bytes > s.text_capacity) s.overflow = true;
+    if (!s.overflow) {
+        const uint64_t *toff = (const uint64_t *)c->lines_off.h;
+        if (bytes) parallel_copy(s.text + s.text_done, c->lines_text.h, (size_t)bytes);
+        for (uint64_t i = 0; i <= n; ++i) s.text_offsets[lo + i] = s.text_done + toff[i];
+    }
+    if (s.status && n && (!s.overflow || s.status_after_overflow)) std::memcpy(s.status + lo, c->lines_status.h, (size_t)n);
+    s.text_done += bytes;
+    return KGPU_OK;
 }
 
 struct PipeJob {
@@ -214,28 +250,31 @@ bool kgpu::is_pinned_host(const void *p) {
 
 // The chunk's input goes to the device as ONE block [offsets (absolute, as the caller has them) | bytes]; the kernels subtract
 // offsets[0] themselves, the text pointer is biased by it.  Pinned caller memory is copied from directly (DMA), pageable memory through
-// the context's pinned staging block, filled with the workers' help.
+// the context's pinned staging block, filled with the workers' help.  off: the chunk's first offset.
+static int upload_input(kgpu_ctx *c, const ChunkInput &in, const uint8_t *utf8, const uint64_t *off, bool pinned_in) {
+    uint8_t *dblk = (uint8_t *)c->in_block.p;
+    const uint64_t n = in.n, base = off[0], total = in.total;
+    int rc;
+    if (pinned_in) {
+        if ((rc = ctx_h2d(c, dblk, off, (size_t)(n + 1) * 8, "H2D input")) ||
+            (total && (rc = ctx_h2d(c, dblk + in.in_off, utf8 + base, (size_t)total, "H2D input"))))
+            return rc;
+    } else {
+        std::memcpy(c->pin_in.h, off, (size_t)(n + 1) * 8);
+        if (total) parallel_copy((uint8_t *)c->pin_in.h + in.in_off, utf8 + base, (size_t)total);
+        if ((rc = ctx_h2d(c, dblk, c->pin_in.h, in.in_off + (size_t)total, "H2D input block"))) return rc;
+    }
+    return KGPU_OK;
+}
+
 static int pipe_submit(PipeJob &j, const uint8_t *utf8, const uint64_t *offsets, bool pinned_in) {
     kgpu_ctx *c = j.c;
     workers().wait_zero(j.tasks);  // the block's previous results are still being expanded
     const uint64_t *off = offsets + j.lo;
-    const uint64_t n = j.m, base = off[0], total = off[n] - base;
     int rc;
-    if ((rc = j.blk.prepare(c, n, total, !pinned_in))) return rc;
-    uint8_t *dblk = (uint8_t *)c->in_block.p;
-    const size_t in_off = j.blk.in_off;
-    if (pinned_in) {
-        if ((rc = ctx_h2d(c, dblk, off, (size_t)(n + 1) * 8, "H2D input")) ||
-            (total && (rc = ctx_h2d(c, dblk + in_off, utf8 + base, (size_t)total, "H2D input"))))
-            return rc;
-    } else {
-        std::memcpy(c->pin_in.h, off, (size_t)(n + 1) * 8);
-        if (total) parallel_copy((uint8_t *)c->pin_in.h + in_off, utf8 + base, (size_t)total);
-        if ((rc = ctx_h2d(c, dblk, c->pin_in.h, in_off + (size_t)total, "H2D input block"))) return rc;
-    }
-    return j.blk.launch(c, base, j.blk.lines ? "kgpu_tokenize_batch_lines" : "kgpu_tokenize_batch");
+    if ((rc = j.blk.prepare(c, j.m, off[j.m] - off[0], !pinned_in)) || (rc = upload_input(c, j.blk.in, utf8, off, pinned_in))) return rc;
+    return j.blk.launch(c, off[0], "kgpu_tokenize_batch");
 }
-
 
 // Wait for the chunk's kernels (its records are in host memory then), hand the expansion to the workers in slices of 2048 sentences.
 static int pipe_finish(PipeJob &j, const uint8_t *utf8, const uint64_t *offsets, kgpu_token *tokens, uint64_t token_capacity, uint64_t *tok_offsets,
@@ -287,50 +326,22 @@ static int pipe_finish(PipeJob &j, const uint8_t *utf8, const uint64_t *offsets,
     return KGPU_OK;
 }
 
-// A large call goes through in chunks on pooled contexts, several in flight: while chunk k's results are delivered on the host (its records
-// expanded, or its text copied), chunk k+1 .. k+4 compute and chunk k+5's input is on its way.  `finish` delivers the oldest chunk: results
-// arrive in order, so the caller's output stays dense.  `lines`: the chunks render the CLI's lines behind their chains (ChunkBlock).
-template <class Finish>
-static int run_pipeline(kgpu_dict *d, const uint8_t *utf8, const uint64_t *offsets, uint64_t n, bool lines, std::atomic<int> &outstanding, Finish finish) {
+// The chunk sizes of a call of n sentences (run_pipeline, kgpu_runtime.h).
+ChunkLimits kgpu::chunk_limits(uint64_t n) {
     const TestHooks hooks = test_hooks();
-    workers().start();   // (none to be had: the workers' tasks run on this thread)
     // chunks of 8192 sentences, ten in the device pipeline (measured on 400k sentences: 16384 x 6: 55.6, 8192 x 10: 61.2, 4096 x 14: 58.8 M sentences/s)
-    const uint64_t CHUNK_BYTES = std::min<uint64_t>(hooks.chunk_bytes, 2ull << 20);
-    const uint64_t CHUNK_SENTS = std::min<uint64_t>(hooks.chunk_sents, std::min<uint64_t>(8192, std::max<uint64_t>(1024, n / 12)));   // (round 6: the floor was 2048 -- with the pool kernel at 59 us per 4096 sentences a 4096-sentence call runs 182 -> 174 us as four chunks)
-    const bool pinned_in = (offsets[n] - offsets[0]) != 0 && is_pinned_host(utf8) && is_pinned_host(offsets);
-    constexpr int MAX_DEPTH = 16;
-    const int DEPTH = (int)std::min<uint64_t>(MAX_DEPTH, std::max<uint64_t>(3, hooks.depth));
-    PipeJob jobs[MAX_DEPTH];
-    int rc = KGPU_OK;
-    uint64_t done = 0;
-    int head = 0, inflight = 0;  // jobs[head .. head + inflight) (mod DEPTH) are active, oldest first
-    while (!rc && (done < n || (n == 0 && done == 0 && inflight == 0))) {
-        if (inflight == DEPTH - 2) {  // two slots stay out of the GPU pipeline: their blocks are being expanded
-            rc = finish(jobs[head]);
-            head = (head + 1) % DEPTH; --inflight;
-            if (rc) break;
-        }
-        PipeJob &j = jobs[(head + inflight) % DEPTH];
-        if (!j.c && (rc = pool_get(d, &j.c))) break;
-        uint64_t m = 0;
-        while (done + m < n && m < CHUNK_SENTS && (m == 0 || offsets[done + m + 1] - offsets[done] <= CHUNK_BYTES)) ++m;
-        j.lo = done; j.m = m;
-        j.blk.lines = lines;
-        j.stream = expand_stream_wanted((uint64_t)n * 2);   // by the CALL's size (32 768 tokens ~ 16 384 sentences and more): a 4096-sentence call's records are read back at once
-        if ((rc = pipe_submit(j, utf8, offsets, pinned_in))) break;
-        ++inflight;
-        done += m;
-        if (n == 0) break;
-    }
-    while (inflight) {  // drain in order (also after an error: the contexts go back to the pool idle)
-        int r2 = finish(jobs[head]);
-        if (!rc) rc = r2;
-        head = (head + 1) % DEPTH; --inflight;
-    }
-    workers().wait_zero(outstanding);
-    for (int k = 0; k < DEPTH; ++k)
-        if (jobs[k].c) pool_put(d, jobs[k].c);
-    return rc;
+    return ChunkLimits{std::min<uint64_t>(hooks.chunk_bytes, 2ull << 20),
+                       std::min<uint64_t>(hooks.chunk_sents, std::min<uint64_t>(8192, std::max<uint64_t>(1024, n / 12)))};   // (round 6: the floor was 2048 -- with the pool kernel at 59 us per 4096 sentences a 4096-sentence call runs 182 -> 174 us as four chunks)
+}
+// The ring of kgpu_tokenize_batch / kgpu_tokenize_batch_lines; two of its jobs stay out of the device pipeline: their blocks are being expanded.
+static int batch_depth() { return (int)std::min<uint64_t>(MAX_PIPE_DEPTH, std::max<uint64_t>(3, test_hooks().depth)); }
+static bool batch_is_pinned(const uint8_t *utf8, const uint64_t *offsets, uint64_t n) { return (offsets[n] - offsets[0]) != 0 && is_pinned_host(utf8) && is_pinned_host(offsets); }
+
+int kgpu::check_host_batch(const char *who, const uint64_t *offsets, uint64_t n, const uint8_t *utf8) {
+    for (uint64_t i = 0; i < n; ++i)
+        if (offsets[i + 1] < offsets[i]) { set_error("%s: offsets not monotone at %llu", who, (unsigned long long)i); return KGPU_ERR_INVALID_ARG; }
+    if (offsets[n] - offsets[0] && !utf8) { set_error("%s: null utf8", who); return KGPU_ERR_INVALID_ARG; }
+    return KGPU_OK;
 }
 
 extern "C" int kgpu_tokenize_batch(kgpu_dict *d, const uint8_t *utf8, const uint64_t *offsets, uint64_t n,
@@ -340,9 +351,7 @@ extern "C" int kgpu_tokenize_batch(kgpu_dict *d, const uint8_t *utf8, const uint
         set_error("kgpu_tokenize_batch: null argument");
         return KGPU_ERR_INVALID_ARG;
     }
-    for (uint64_t i = 0; i < n; ++i)
-        if (offsets[i + 1] < offsets[i]) { set_error("kgpu_tokenize_batch: offsets not monotone at %llu", (unsigned long long)i); return KGPU_ERR_INVALID_ARG; }
-    if (offsets[n] - offsets[0] && !utf8) { set_error("kgpu_tokenize_batch: null utf8"); return KGPU_ERR_INVALID_ARG; }
+    if (int rc = check_host_batch("kgpu_tokenize_batch", offsets, n, utf8)) return rc;
     const uint64_t kd0 = small_trace_on() ? cpu_ns() : 0;
     HIPCHECK(hipSetDevice(d->device));
     if (kd0) g_sc[11] += cpu_ns() - kd0;   // (KGPU_SMALL_TRACE: the CPU time of hipSetDevice)
@@ -356,9 +365,11 @@ extern "C" int kgpu_tokenize_batch(kgpu_dict *d, const uint8_t *utf8, const uint
     uint64_t tok_done = 0;
     bool overflow = false;
     tok_offsets[0] = 0;
-    const int rc = run_pipeline(d, utf8, offsets, n, false, outstanding, [&](PipeJob &j) {
-        return pipe_finish(j, utf8, offsets, tokens, token_capacity, tok_offsets, status, tok_done, overflow, outstanding);
-    });
+    const bool pinned_in = batch_is_pinned(utf8, offsets, n);
+    const bool stream = expand_stream_wanted((uint64_t)n * 2);   // by the CALL's size (32 768 tokens ~ 16 384 sentences and more): a 4096-sentence call's records are read back at once
+    const int rc = run_pipeline<PipeJob>(d, offsets, n, batch_depth(), 2, true, &outstanding,
+        [&](PipeJob &j) { j.stream = stream; return pipe_submit(j, utf8, offsets, pinned_in); },
+        [&](PipeJob &j) { return pipe_finish(j, utf8, offsets, tokens, token_capacity, tok_offsets, status, tok_done, overflow, outstanding); });
     if (n_tokens) *n_tokens = tok_done;
     if (!rc && overflow) {
         set_error("token buffer too small: need %llu, capacity %llu", (unsigned long long)tok_done, (unsigned long long)token_capacity);
@@ -367,59 +378,37 @@ extern "C" int kgpu_tokenize_batch(kgpu_dict *d, const uint8_t *utf8, const uint
     return rc;
 }
 
-// Wait for a lines chunk's render (its text is in the context's mapped block then) and copy the text behind the `text_done` bytes already
-// delivered (or only count, once the caller's buffer has overflowed).  A rerun of the chunk's chain inside kgpu_ctx_sync came after the render
-// queued behind the first pass: the render once more; a text block too small for the chunk: a bigger one and the render once more.
-static int pipe_finish_lines(PipeJob &j, const uint64_t *offsets, uint8_t *text, uint64_t text_capacity, uint64_t *text_offsets, uint8_t *status,
-                             uint64_t &text_done, bool &overflow) {
-    kgpu_ctx *c = j.c;
-    const char *who = "kgpu_tokenize_batch_lines";
-    const uint64_t base = offsets[j.lo];
-    const auto reruns = [c] { return c->rt.window_reruns + c->rt.tail_reruns + c->rt.arena_regrows; };
-    const uint64_t r0 = reruns();
-    int rc = kgpu_ctx_sync(c, nullptr);   // (24-byte records with capacity bytes + n + 1: never too small)
-    if (rc) return rc;
-    if (reruns() != r0 && (rc = j.blk.render(c, base, who))) return rc;
-    uint64_t bytes = 0;
-    rc = kgpu_ctx_sync_lines(c, &bytes);
-    if (rc == KGPU_ERR_CAPACITY) {
-        if ((rc = c->lines_text.ensure((size_t)bytes + 64, true)) || (rc = j.blk.render(c, base, who))) return rc;
-        rc = kgpu_ctx_sync_lines(c, &bytes);
-    }
-    if (rc) return rc;
-    if (text_done + bytes > text_capacity) overflow = true;
-    if (!overflow) {
-        const uint64_t *toff = (const uint64_t *)c->lines_off.h;
-        if (bytes) parallel_copy(text + text_done, c->lines_text.h, (size_t)bytes);
-        for (uint64_t i = 0; i <= j.m; ++i) text_offsets[j.lo + i] = text_done + toff[i];
-    }
-    if (status && j.m) std::memcpy(status + j.lo, c->lines_status.h, (size_t)j.m);
-    text_done += bytes;
-    return KGPU_OK;
-}
+// One chunk of kgpu_tokenize_batch_lines: the input block of a host batch, the output side of a lines chunk.
+struct LinesJob {
+    kgpu_ctx *c = nullptr;
+    uint64_t lo = 0, m = 0;
+    ChunkInput in;
+    LinesChunk out;
+};
 
 extern "C" int kgpu_tokenize_batch_lines(kgpu_dict *d, const uint8_t *utf8, const uint64_t *offsets, uint64_t n,
                                          uint8_t *text, uint64_t text_capacity, uint64_t *text_offsets, uint8_t *status, uint64_t *n_bytes) {
-    if (!d || !offsets || !text_offsets || (text_capacity && !text)) { set_error("kgpu_tokenize_batch_lines: null argument"); return KGPU_ERR_INVALID_ARG; }
-    for (uint64_t i = 0; i < n; ++i)
-        if (offsets[i + 1] < offsets[i]) { set_error("kgpu_tokenize_batch_lines: offsets not monotone at %llu", (unsigned long long)i); return KGPU_ERR_INVALID_ARG; }
-    if (offsets[n] - offsets[0] && !utf8) { set_error("kgpu_tokenize_batch_lines: null utf8"); return KGPU_ERR_INVALID_ARG; }
-    {
-        std::lock_guard<std::mutex> g(d->feat_mu);
-        if (!d->feat) { set_error("kgpu_tokenize_batch_lines: the dictionary has no feature tables: call kgpu_dict_set_features first"); return KGPU_ERR_INVALID_ARG; }
-    }
+    const char *who = "kgpu_tokenize_batch_lines";
+    if (!d || !offsets || !text_offsets || (text_capacity && !text)) { set_error("%s: null argument", who); return KGPU_ERR_INVALID_ARG; }
+    int rc;
+    if ((rc = check_host_batch(who, offsets, n, utf8)) || (rc = require_features(d, who))) return rc;
     HIPCHECK(hipSetDevice(d->device));
     // (every call takes the chunk pipeline: the single-launch small-call path renders nothing)
-    std::atomic<int> outstanding{0};
-    uint64_t text_done = 0;
-    bool overflow = false;
+    LinesSink sink{text, text_capacity, text_offsets, status, true};   // (status has n entries whatever the text buffer holds)
     text_offsets[0] = 0;
-    const int rc = run_pipeline(d, utf8, offsets, n, true, outstanding, [&](PipeJob &j) {
-        return pipe_finish_lines(j, offsets, text, text_capacity, text_offsets, status, text_done, overflow);
-    });
-    if (n_bytes) *n_bytes = text_done;
-    if (!rc && overflow) {
-        set_error("text buffer too small: need %llu, capacity %llu", (unsigned long long)text_done, (unsigned long long)text_capacity);
+    const bool pinned_in = batch_is_pinned(utf8, offsets, n);
+    rc = run_pipeline<LinesJob>(d, offsets, n, batch_depth(), 2, true, nullptr,
+        [&](LinesJob &j) {
+            const uint64_t *off = offsets + j.lo;
+            const uint64_t total = off[j.m] - off[0];
+            int r;
+            if ((r = j.in.prepare(j.c, j.m, total, !pinned_in)) || (r = j.out.prepare(j.c, j.m, total)) || (r = upload_input(j.c, j.in, utf8, off, pinned_in))) return r;
+            return j.out.launch(j.c, j.in.d_text(j.c, off[0]), j.in.d_offsets(j.c), who);
+        },
+        [&](LinesJob &j) { return j.out.finish(j.c, j.lo, sink, who); });
+    if (n_bytes) *n_bytes = sink.text_done;
+    if (!rc && sink.overflow) {
+        set_error("text buffer too small: need %llu, capacity %llu", (unsigned long long)sink.text_done, (unsigned long long)text_capacity);
         return KGPU_ERR_CAPACITY;
     }
     return rc;

@@ -129,7 +129,7 @@ int shard_submit(MultiCall &mc, int g, uint64_t c) {
     int rc;
     if ((rc = j.blk.prepare(ctx, m, total, true))) return rc;
     uint64_t *h_off = (uint64_t *)ctx->pin_in.h;
-    uint8_t *h_txt = (uint8_t *)ctx->pin_in.h + j.blk.in_off;
+    uint8_t *h_txt = (uint8_t *)ctx->pin_in.h + j.blk.in.in_off;
     {
         uint64_t at = 0;
         for (uint64_t k = 0; k < m; ++k) { const uint64_t i = lo + (uint64_t)g + k * (uint64_t)mc.G; h_off[k] = at; at += mc.offsets[i + 1] - mc.offsets[i]; }
@@ -154,7 +154,7 @@ int shard_submit(MultiCall &mc, int g, uint64_t c) {
         piece(0, std::min(m, each));
         if (np > 1) workers().wait_zero(left);
     }
-    if ((rc = ctx_h2d(ctx, ctx->in_block.p, ctx->pin_in.h, j.blk.in_off + (size_t)total, "H2D input block"))) return rc;
+    if ((rc = ctx_h2d(ctx, ctx->in_block.p, ctx->pin_in.h, j.blk.in.in_off + (size_t)total, "H2D input block"))) return rc;
     return j.blk.launch(ctx, 0, "kgpu_tokenize_batch_multi");   // (the shard's offsets start at 0)
 }
 
@@ -206,9 +206,7 @@ static int multi_impl(kgpu_dict *const *dicts, int n_dicts, const uint8_t *utf8,
     for (int g = 0; g < n_dicts; ++g) if (!dicts[g]) { set_error("kgpu_tokenize_batch_multi: null dictionary handle %d", g); return KGPU_ERR_INVALID_ARG; }
     DeviceGuard keep_callers_device;   // (above every path that touches a device: the one-dictionary shortcut included)
     if (n_dicts == 1 && !compact) return kgpu_tokenize_batch(dicts[0], utf8, offsets, n, tokens, token_capacity, tok_offsets, status, n_tokens);
-    for (uint64_t i = 0; i < n; ++i)
-        if (offsets[i + 1] < offsets[i]) { set_error("kgpu_tokenize_batch_multi: offsets not monotone at %llu", (unsigned long long)i); return KGPU_ERR_INVALID_ARG; }
-    if (offsets[n] - offsets[0] && !utf8) { set_error("kgpu_tokenize_batch_multi: null utf8"); return KGPU_ERR_INVALID_ARG; }
+    if (int rc = check_host_batch("kgpu_tokenize_batch_multi", offsets, n, utf8)) return rc;
     tok_offsets[0] = 0;
     if (n_tokens) *n_tokens = 0;
     if (n == 0) return KGPU_OK;

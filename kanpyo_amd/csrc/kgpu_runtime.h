@@ -55,6 +55,20 @@ struct PinBuf {
     void release() { if (h) (void)hipHostFree(h); h = d = nullptr; bytes = 0; }
 };
 
+// A launch that publishes two 64-bit words to the host (the render: [0] bytes, [1] a bad record; the split's carry kernel: [0] lines, [1] packed bytes):
+// 16 mapped bytes the kernel stores into, an event behind the launch, and the capacity the launch was given, which the sync compares the words with.
+struct HostReport {
+    PinBuf ctl;
+    hipEvent_t ev = nullptr;
+    bool pending = false;
+    uint64_t cap = 0;
+    int arm();                                   // before the launch: a previous use waited out (its words are about to be reset), block and event there, words zero
+    unsigned long long *dev() const { return (unsigned long long *)ctl.d; }   // what the launch is given
+    int record(hipStream_t stream, uint64_t cap);   // behind the launch
+    int wait(uint64_t words[2]);                 // the launch is through: its two words
+    void release();                              // (waits for a launch still pending)
+};
+
 }  // namespace kgpu
 
 using namespace kgpu;  // (a private header of the runtime's translation units, which all speak this namespace's vocabulary)
@@ -120,20 +134,15 @@ struct kgpu_ctx {
     // single-launch small calls: one pinned, device-mapped block (input | offsets | tokens | token offsets | status)
     uint8_t *sm_host = nullptr, *sm_dev = nullptr;
     uint32_t sm_seq = 0;
-    // the CLI's output lines (kgpu_format.hip): per-sentence scratch, the mapped words the scan publishes ([0] bytes, [1] a bad record), and for
-    // kgpu_tokenize_batch_lines the mapped text, text offsets and status of a chunk (the render's stores are the transfer)
+    // the CLI's output lines (kgpu_format.hip): per-sentence scratch, what the render's scan publishes ([0] bytes, [1] a bad record), and for a chunk
+    // of the host lines calls (LinesChunk) the mapped text, text offsets and status (the render's stores are the transfer)
     DevBuf lines_len;
-    PinBuf lines_ctl, lines_text, lines_off, lines_status;
-    hipEvent_t lines_ev = nullptr;
-    bool lines_pending = false;
-    uint64_t lines_cap = 0;
-    // read_line + trim_end on the device (kgpu_split.hip): the tile aggregates, the mapped words the carry kernel publishes ([0] lines, [1] packed
-    // bytes), and for kgpu_tokenize_text_lines the device copy of the raw block, its packed lines and their offsets
+    HostReport lines_report;
+    PinBuf lines_text, lines_off, lines_status;
+    // read_line + trim_end on the device (kgpu_split.hip): the tile aggregates, what the carry kernel publishes ([0] lines, [1] packed bytes), and
+    // for kgpu_tokenize_text_lines the device copy of the raw block, its packed lines and their offsets
     DevBuf split_agg, split_raw, split_text, split_off;
-    PinBuf split_ctl;
-    hipEvent_t split_ev = nullptr;
-    bool split_pending = false;
-    uint64_t split_cap = 0;
+    HostReport split_report;
     // last enqueued batch (for the arena-overflow retry and for sync)
     BatchArgs last{};
     bool pending = false;
@@ -233,25 +242,104 @@ int tokenize_device_impl(kgpu_ctx *c, const uint8_t *d_utf8, const uint64_t *d_o
 int enqueue_lines(kgpu_ctx *c, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n, const kgpu_token *d_tokens, const uint64_t *d_tok_offsets,
                   uint8_t *d_text, uint64_t text_capacity, uint64_t *d_text_offsets, const uint8_t *status_in, uint8_t *status_out, const char *who);
 
+int require_features(kgpu_dict *d, const char *who);   // KGPU_ERR_INVALID_ARG unless kgpu_dict_set_features has been called
+
 // kgpu_host.cpp
 void parallel_copy(void *dst, const void *src, size_t bytes);
 bool is_pinned_host(const void *p);
+int check_host_batch(const char *who, const uint64_t *offsets, uint64_t n, const uint8_t *utf8);   // a host batch's offsets are monotone, its bytes are there
+// The records a batch of n sentences / `total` bytes can produce: tokens <= chars + 1 <= bytes + 1 per sentence, so a buffer of this many is never too small.
+inline uint64_t token_bound(uint64_t total, uint64_t n) { return total + n + 1; }
 // A finished chunk's results in host memory: 8-byte records, (position, start) of every sentence's first token, token offsets, status bytes.
 struct MergeSrc { const kgpu_token8 *rec; const uint32_t *first; const uint64_t *toff; const uint8_t *st; };
-// One chunk of a large host call on a pooled context (kgpu_host.cpp: pipe_submit; kgpu_multi.cpp: shard_submit).  Its input goes to the device as
-// ONE block [offsets | bytes] (c->in_block, staged in c->pin_in unless it is copied from pinned memory directly); the compaction kernel writes the
-// results into the mapped block c->pin_out: records | first | token offsets | status.  With `lines` (kgpu_tokenize_batch_lines) the 24-byte records
-// stay in HBM (c->out_tok) and the render behind the chain writes the chunk's text, text offsets and status into c's mapped lines_* blocks.
-struct ChunkBlock {
-    uint64_t n = 0, total = 0, cap = 0;                    // sentences, bytes, token capacity
-    bool lines = false;
-    size_t in_off = 0;                                     // the offsets' share of the input block: the bytes follow
-    size_t off_first = 0, off_toff = 0, off_status = 0;    // inside pin_out
+// The input of one chunk of a host call on a pooled context: it goes to the device as ONE block [offsets | bytes] (c->in_block, staged in c->pin_in
+// unless it is copied from pinned memory directly).  The offsets are as the caller has them: the kernels subtract offsets[0], the text pointer is biased by it.
+struct ChunkInput {
+    uint64_t n = 0, total = 0;                             // sentences, bytes
+    size_t in_off = 0;                                     // the offsets' share of the block: the bytes follow
     int prepare(kgpu_ctx *c, uint64_t n, uint64_t total, bool staged);   // the layout, and c's buffers big enough for it
-    int launch(kgpu_ctx *c, uint64_t base, const char *who) const;        // the chain over in_block (offsets start at `base`), records into pin_out
-    int render(kgpu_ctx *c, uint64_t base, const char *who) const;        // `lines`: the render of the chunk's records (the launch queues one behind its chain)
+    const uint64_t *d_offsets(const kgpu_ctx *c) const { return (const uint64_t *)c->in_block.p; }
+    const uint8_t *d_text(const kgpu_ctx *c, uint64_t base) const { return (const uint8_t *)c->in_block.p + in_off - base; }   // (offsets start at `base`)
+};
+// One chunk of kgpu_tokenize_batch / kgpu_tokenize_batch_multi (kgpu_host.cpp: pipe_submit; kgpu_multi.cpp: shard_submit): its input block, and the
+// mapped block c->pin_out the compaction kernel writes the results into: 8-byte records | first | token offsets | status.
+struct ChunkBlock {
+    ChunkInput in;
+    uint64_t cap = 0;                                      // token capacity
+    size_t off_first = 0, off_toff = 0, off_status = 0;    // inside pin_out
+    int prepare(kgpu_ctx *c, uint64_t n, uint64_t total, bool staged);
+    int launch(kgpu_ctx *c, uint64_t base, const char *who) const;        // the chain over the input block, records into pin_out
     MergeSrc results(const kgpu_ctx *c) const;                           // where the host reads them once the chunk is synced
 };
+// Where the chunks of a lines call deliver: the caller's buffers, what has been delivered so far, and whether a buffer has overflowed (from then on the
+// chunks are only counted).  status_after_overflow: the status bytes go out all the same (a status array of n entries whatever happens); not so where
+// the status array is bounded by the capacity that overflowed.
+struct LinesSink {
+    uint8_t *text; uint64_t text_capacity; uint64_t *text_offsets; uint8_t *status;
+    bool status_after_overflow;
+    uint64_t text_done = 0;
+    bool overflow = false;
+};
+// The output side of one chunk of a lines call (kgpu_tokenize_batch_lines, kgpu_tokenize_text_lines) on a pooled context, whatever put its input on the
+// device: the 24-byte records stay in HBM (c->out_tok) and the render behind the chain writes the chunk's text, chunk-relative text offsets and status
+// into c's mapped lines_* blocks.
+struct LinesChunk {
+    uint64_t n = 0, total = 0;                             // sentences, bytes
+    const uint8_t *d_utf8 = nullptr;                       // the chunk's input in device memory (launch)
+    const uint64_t *d_offsets = nullptr;
+    int prepare(kgpu_ctx *c, uint64_t n, uint64_t total);                 // c's buffers big enough
+    int launch(kgpu_ctx *c, const uint8_t *d_utf8, const uint64_t *d_offsets, const char *who);   // the chain, then the render
+    int render(kgpu_ctx *c, const char *who) const;                       // the render of the chunk's records alone
+    int finish(kgpu_ctx *c, uint64_t lo, LinesSink &sink, const char *who) const;   // wait, and deliver behind what the sink holds: sentences [lo, lo + n) of the call
+};
+
+// The chunks of a large host call: at most `bytes` / `sents` each (test_hooks() may lower them).
+struct ChunkLimits { uint64_t bytes, sents; };
+ChunkLimits chunk_limits(uint64_t n);
+constexpr int MAX_PIPE_DEPTH = 16;
+// A large call goes through in chunks on pooled contexts, several in flight: while chunk k's results are delivered on the host (its records
+// expanded, or its text copied), the next chunks compute and the one after them has its input on its way.  `offsets` (n + 1 entries, host memory) cuts the
+// chunks; Job has `c`, `lo`, `m` (context, sentences [lo, lo + m)) and whatever submit / finish keep per chunk.  `depth` jobs form the ring, of which
+// `held_back` stay out of the device pipeline (their results are still being delivered by the workers).  `finish` delivers the oldest chunk: results
+// arrive in order, so the caller's output stays dense.  empty_chunk: a call without sentences still submits one chunk.  host_tasks: what the finishes
+// handed to the workers (null: nothing), waited for before the contexts go back to the pool.
+template <class Job, class Submit, class Finish>
+int run_pipeline(kgpu_dict *d, const uint64_t *offsets, uint64_t n, int depth, int held_back, bool empty_chunk, std::atomic<int> *host_tasks, Submit submit, Finish finish) {
+    workers().start();   // (none to be had: the workers' tasks run on this thread)
+    const ChunkLimits lim = chunk_limits(n);
+    Job jobs[MAX_PIPE_DEPTH];
+    int rc = KGPU_OK;
+    uint64_t done = 0;
+    int head = 0, inflight = 0;  // jobs[head .. head + inflight) (mod depth) are active, oldest first
+    while (!rc && (done < n || empty_chunk)) {
+        empty_chunk = false;
+        if (inflight == depth - held_back) {
+            rc = finish(jobs[head]);
+            head = (head + 1) % depth; --inflight;
+            if (rc) break;
+        }
+        Job &j = jobs[(head + inflight) % depth];
+        if (!j.c && (rc = pool_get(d, &j.c))) break;
+        uint64_t m = 0;
+        while (done + m < n && m < lim.sents && (m == 0 || offsets[done + m + 1] - offsets[done] <= lim.bytes)) ++m;
+        j.lo = done; j.m = m;
+        if ((rc = submit(j))) {   // (a batch may be queued without what follows it: the context goes back to the pool idle)
+            if (j.c->pending) (void)kgpu_ctx_sync(j.c, nullptr);
+            break;
+        }
+        ++inflight;
+        done += m;
+    }
+    while (inflight) {  // drain in order (also after an error: the contexts go back to the pool idle)
+        const int r2 = finish(jobs[head]);
+        if (!rc) rc = r2;
+        head = (head + 1) % depth; --inflight;
+    }
+    if (host_tasks) workers().wait_zero(*host_tasks);
+    for (int k = 0; k < depth; ++k)
+        if (jobs[k].c) pool_put(d, jobs[k].c);
+    return rc;
+}
 
 // kgpu_small.cpp
 Combiner *combiner_new();

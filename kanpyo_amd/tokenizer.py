@@ -170,7 +170,7 @@ class Tokenizer:
     def tokenize_text_lines(self, block):
         """kgpu_tokenize_text_lines: a raw block of input (bytes or uint8 array) -> (text, text_offsets, status) as
         tokenize_lines_packed(*split_lines(block)) gives them; the split and the trim run on the device."""
-        src = np.frombuffer(bytes(block), dtype=np.uint8) if not isinstance(block, np.ndarray) else np.ascontiguousarray(block, dtype=np.uint8)
+        src = _block_bytes(block)
         cap, ocap = src.size * 16 + 64, src.size // 16 + 1024
         L = _lib.lib()
         while True:
@@ -222,10 +222,15 @@ class Tokenizer:
         return self.tokenize_batch([input])[0]
 
 
+def _block_bytes(block) -> np.ndarray:
+    """A block of input (bytes-like or uint8 array) as a contiguous uint8 array."""
+    return np.frombuffer(bytes(block), dtype=np.uint8) if not isinstance(block, np.ndarray) else np.ascontiguousarray(block, dtype=np.uint8)
+
+
 def split_lines(block) -> tuple:
     """kgpu_split_lines: the CLI's read_line + trim_end (src/bin/kanpyo.rs:114-122) over a block of input bytes
     -> (uint8 trimmed lines packed, uint64 offsets[n+1]).  Host only: needs no device."""
-    src = np.frombuffer(bytes(block), dtype=np.uint8) if not isinstance(block, np.ndarray) else np.ascontiguousarray(block, dtype=np.uint8)
+    src = _block_bytes(block)
     n_max = int(np.count_nonzero(src == 10)) + 1
     out = np.empty(max(src.size, 1), dtype=np.uint8)
     offs = np.empty(n_max + 1, dtype=np.uint64)

@@ -317,3 +317,115 @@ def _offset_of_line(text: bytes, k: int) -> int:
     for _ in range(k):
         at = text.index(b"EOS\t\n", at) + 5
     return at
+
+
+# ---- the two branches of a lines chunk's finish, through both host entry points -------------------------------------------------------------
+def _lines_call(tok, entry, block, text_capacity=None):
+    """The block's lines through one host entry point -> (text, text_offsets, status).  text_capacity: the C call itself with a text buffer
+    of that size (so that a first call on fresh contexts is the one that delivers), else the Python wrapper."""
+    import ctypes as C
+
+    from kanpyo_amd import _lib
+    from kanpyo_amd.tokenizer import split_lines
+
+    if entry == "packed":
+        utf8, offs = split_lines(block)
+        if text_capacity is None:
+            return tok.tokenize_lines_packed(utf8, offs)
+        n = len(offs) - 1
+        return tok.tokenize_lines_packed(utf8, offs, out=(np.empty(text_capacity, dtype=np.uint8), np.empty(n + 1, dtype=np.uint64), np.empty(max(n, 1), dtype=np.uint8)))
+    if text_capacity is None:
+        return tok.tokenize_text_lines(block)
+    src = np.frombuffer(block, dtype=np.uint8)
+    ocap = block.count(b"\n") + 2
+    text, toff, status = np.empty(text_capacity, dtype=np.uint8), np.empty(ocap, dtype=np.uint64), np.zeros(ocap, dtype=np.uint8)
+    n, got = C.c_uint64(0), C.c_uint64(0)
+    _lib.check(_lib.lib().kgpu_tokenize_text_lines(tok.handle, src.ctypes.data, src.size, text.ctypes.data, text_capacity, toff.ctypes.data, ocap,
+                                                   status.ctypes.data, C.byref(n), C.byref(got)))
+    return text[: got.value], toff[: n.value + 1], status[: n.value]
+
+
+def _oracle_lines(orc, known, unk, block):
+    from kanpyo_amd.tokenizer import split_lines
+
+    utf8, offs = split_lines(block)
+    exp = orc.tokenize_batch(utf8, offs, 8)
+    return expected_lines(utf8, offs, exp.tokens, exp.offsets, known, unk)
+
+
+@pytest.mark.parametrize("entry", ["packed", "text"])
+def test_chain_runs_again_behind_the_render(entry):
+    """A chunk whose chain ended without its tail and needed it runs the tail inside kgpu_ctx_sync, behind the render that was queued with the first
+    pass: the chunk's finish renders once more, and the bytes are the oracle's.  The recipe of test_gpu_parity.py::
+    test_chain_tail_is_left_out_and_comes_back: clean short batches disarm the tail (the arming is the dictionary's), then a mixed batch."""
+    from kanpyo_amd import Tokenizer, synth
+    from oracle import oracle
+
+    oracle.build()
+    sd = synth.build_dict(20000, seed=5)
+    known, unk = synth.feature_tables(sd)
+    tok, orc = Tokenizer(sd.dict), oracle.OracleTokenizer.from_dict(sd.dict)
+    tok.set_features(known, unk)
+    short = [s[:30].replace("\n", "") for s in synth.make_corpus(sd, 600, 9, "cfg2")]
+    clean = "".join(s + "\n" for s in short).encode()
+    for _ in range(14):
+        _lines_call(tok, entry, clean)
+    assert tok.routing()["tail_reruns"] == 0
+    mixed = short[:100] + ["ア" * 900, "漢字かな" * 150] + [s.replace("\n", "") for s in synth.make_corpus(sd, 5, 10, "cfg3")] + short[100:200]
+    block = "".join(s + "\n" for s in mixed).encode()
+    want, want_off = _oracle_lines(orc, known, unk, block)
+    text, toff, status = _lines_call(tok, entry, block)
+    reruns = tok.routing()["tail_reruns"]
+    print(f"{entry}: tail_reruns {reruns}")
+    assert reruns >= 1, "the mixed batch did not take the tail pass: the render-again branch was not reached"
+    assert not status.any()
+    assert np.array_equal(toff, want_off)
+    assert text.tobytes() == want
+
+
+@pytest.mark.parametrize("entry", ["packed", "text"])
+def test_chunk_text_outgrows_the_first_block(entry):
+    """A chunk's mapped text block is sized by a guess and grown to the size the render reports; the render then runs again.  On the small dictionary
+    of test_edge_cases, whose third morph carries a feature string of 10 200 bytes, a chunk of at most 48 input bytes gets a first block of
+    48 * 16 + 4096 = 4864 bytes (LinesChunk::prepare), which PinBuf::ensure rounds up by a quarter plus 4096: 4864 + 1216 + 4096 = 10 176 bytes --
+    one line of that morph alone (surface + tab + 10 200 + newline) is longer, so the grow-and-render-again branch is taken by arithmetic."""
+    from kanpyo_amd import Dict, Tokenizer
+    from kanpyo_amd.dictfile import MorphFeatureTable
+    from kanpyo_amd.tokenizer import pack_sentences
+    from oracle import oracle
+
+    oracle.build()
+    p = fixture_dict_parts()
+    p["conn_data"] = [0, 100, 200, 100, -30000, 100, 200, 100, -30000]
+    p["morphs"] = [[0, 0, 1000], [1, 1, -20000], [2, 2, 1100]]
+    d = Dict.from_parts(**p)
+    k = MorphFeatureTable([[], [1, 0, 1], [2]], ["", "名" * 10, "長" * 3400])
+    u = MorphFeatureTable([[1]] * len(p["unk_morphs"]), ["", "未知"])
+    assert len(",".join(k.features(3)).encode()) == 10200
+    orc = oracle.OracleTokenizer.from_dict(d)
+    candidates = ["テスト", "辞書", "形態素", "辞書形態素", "形態素テスト", "あ形態素", "テ辞書形態素", "形態素形態素", "テスト辞書"]
+    utf8, offs = pack_sentences(candidates)
+    exp = orc.tokenize_batch(utf8, offs, 1)
+    with_third = [s for i, s in enumerate(candidates)
+                  if any(int(t["cls"]) == 1 and int(t["id"]) == 3 for t in exp.tokens[int(exp.offsets[i]) : int(exp.offsets[i + 1])])]
+    lines, total = [], 0
+    for s in sorted(with_third, key=lambda s: len(s.encode())):   # a few of them, 48 input bytes at most
+        if len(lines) < 3 and total + len(s.encode()) <= 48:
+            lines.append(s)
+            total += len(s.encode())
+    assert lines, "no candidate's oracle tokens include the third morph"
+    need = total * 16 + 4096
+    first_block = need + need // 4 + 4096
+    assert first_block < 10200
+    block = "".join(s + "\n" for s in lines).encode()
+    want, want_off = _oracle_lines(orc, k, u, block)
+    print(f"{entry}: {len(lines)} lines, {total} input bytes, first block {first_block}, rendered {len(want)}")
+    assert len(want) > first_block
+    tok = Tokenizer(d)   # (fresh contexts: their text blocks start at the first guess)
+    tok.set_features(k, u)
+    text, toff, status = _lines_call(tok, entry, block, text_capacity=len(want) + 64)   # delivered by the call that grew the block
+    assert not status.any()
+    assert np.array_equal(toff, want_off)
+    assert text.tobytes() == want
+    text, toff, status = _lines_call(tok, entry, block)   # ... and through the wrapper, whose own first buffer is too small as well
+    assert np.array_equal(toff, want_off) and text.tobytes() == want
