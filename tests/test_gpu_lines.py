@@ -1,6 +1,8 @@
 """The `kanpyo tokenize` output on the device (src/bin/kanpyo.rs:106-126, 174-197): kgpu_tokenize_batch_lines, kgpu_format_lines_device,
 the C consumer and `python -m kanpyo_amd tokenize`.  Expected bytes always come from the oracle's tokens (or the hand-derived fixture
-tokens) and MorphFeatureTable.features in Python -- never from the library's parser, pool or kernels."""
+tokens) and MorphFeatureTable.features in Python -- never from the library's parser, pool or kernels.  These tests reach the renderer
+(kgpu_format.hip) with records the tokenizer wrote; its direct tests on crafted records -- every destination misalignment, window edges, more
+than 32 768 sentences, output past 4 GiB, bad records late in the work -- are tests/test_gpu_format.py, against tests/lines_ref.py."""
 import os
 import subprocess
 import sys
