@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kgpu_internal.h"
+#include "kgpu_tilepack.h"
 
 namespace kgpu {
 namespace dev {
@@ -345,7 +346,8 @@ __device__ __forceinline__ uint64_t wave_min_u64(uint64_t k) {  // over the 64 l
 // first chunk << 30 | last chunk << 31 (the two byte offsets ready-made: one s_bfe each where they are used), D1 = LDS address of bk[p0 + 8 b].  node[t] = {word cost (i16) | BYTE OFFSET of the node's bucket slot << 16 (8 x slot: SLOT_SHIFT; the kernels' LDS budgets keep slots below 8192), byte offset of the node's
 // matrix row (left * rows * 2)}; bk[] = bucket entries {dp, 2 * right | node index << 16} (the node index relative to whatever base the kernel uses).
 //   GATHER: the lane loads its own connection cost M[right(j)][left(ti)] from the matrix into a REGISTER (byte offset = row offset + 2 * right: one add) -- no
-//     pair table in LDS -- and a group of eight tiles is requested while the previous group is swept: the matrix's latency is off the dependency chain.
+//     pair table in LDS -- and a group of TILE_GS tiles is requested while the previous group is swept: the matrix's latency is off the dependency chain.
+//     The tile's two LDS addresses of this lane (node entry, bucket entry) are computed here ONCE and handed to the sweep packed in one register.
 //   SWEEP: dp of the predecessor + that cost; across a target group's chunks the running lexicographic minimum (total, then the bucket word whose upper half
 //     is the node index: strict '<' over ascending insertion order, lattice.rs:125,136); on the last chunk two DPP group minima, the word cost, .min(INF)
 //     (tot < INF after the add = .min(INF) then strict '<', lattice.rs:135-136), the stores: dp into the node's bucket slot, the best predecessor into the
@@ -354,43 +356,65 @@ __device__ __forceinline__ uint64_t wave_min_u64(uint64_t k) {  // over the 64 l
 // stores to the same addresses, and a repeated candidate changes no minimum.  (A masked load would have to merge into the register's old value and so wait for
 // every load in flight.)  What a step costs is its instruction count and its dependent chain (tools/ubench: LDS write -> read 86 cycles, three dependent DPP
 // minima 43, a taken branch 32): no fence per tile -- one wavefront's DS instructions execute in issue order.
-struct TileGroup { uint32_t c[8]; };   // per tile of a group: the lane's connection cost (a dword loaded at the cost's 2-byte-aligned address; the low half counts)
+constexpr uint32_t TILE_GS = 4;   // tiles per group: what is gathered ahead of the sweep.  Four, not eight: every per-group register set halves (with the packed
+                                  // addresses kept, groups of eight are 111 VGPRs in the pool kernel -- above 96 a SIMD with four pool wavefronts has no registers
+                                  // left for the other chains' kernels), and a tile is ~190 cycles of its wavefront against ~133 of a dependent L2 load
+static_assert(64 % TILE_GS == 0, "a window of 64 descriptors is whole groups");
+// per tile of a group: the lane's connection cost (a dword loaded at the cost's 2-byte-aligned address; the low half counts) and the tile's two LDS addresses
+// for this lane -- node entry and bucket entry -- as the gather computed them, packed into one word (kgpu_tilepack.h): the sweep decodes no descriptor again
+struct TileGroup { uint32_t c[TILE_GS]; uint32_t ad[TILE_GS]; };
 constexpr uint32_t TILE_FIRST = 1u << 30, TILE_LAST = 1u << 31;
 constexpr uint32_t SLOT_SHIFT = 19, SLOT_MAX = 8191;   // node[t].x = word cost | slot << SLOT_SHIFT: the upper half IS the slot's byte offset in bk[] (one sdwa add in the sweep)
 __device__ __forceinline__ uint32_t tile_desc0(uint32_t a_node_t, uint32_t Tt, uint32_t Pt, bool first, bool last) {
     return a_node_t | ((Tt - 1u) << 21) | ((Pt - 1u) << 27) | (first ? TILE_FIRST : 0u) | (last ? TILE_LAST : 0u);
 }
-// d0 / d1: a window of descriptors, one per lane; the group's tiles are lanes i0 .. i0 + 7.  Issued in the order the sweep consumes them (loads return in
-// order: tile u then waits for its own cost only, vmcnt(15 - u) with the next group's eight behind it) and on EVERY path -- a conditional gather makes the
-// compiler's count of the loads in flight conservative and a sweep would wait for the next group's loads too.  The kernel's matrix copy is padded by four
-// bytes (kgpu_dict_create): a 16-bit load would get its sign extension as a separate instruction behind vmcnt(0) where the value is carried round the loop.
-__device__ __forceinline__ void tile_gather8(TileGroup &G, uint32_t d0, uint32_t d1, uint32_t i0, uint32_t tg8, uint32_t j8, const uint8_t *connb) {
-    uint32_t lb[8], yy[8];
+// d0 / d1: a window of descriptors, one per lane; the group's tiles are lanes i0 .. i0 + TILE_GS - 1.  Issued in the order the sweep consumes them (loads
+// return in order: tile u then waits for its own cost only, vmcnt(2 TILE_GS - 1 - u) with the next group's behind it) and on EVERY path -- a conditional
+// gather makes the compiler's count of the loads in flight conservative and a sweep would wait for the next group's loads too.  The kernel's matrix copy is
+// padded by four bytes (kgpu_dict_create): a 16-bit load would get its sign extension as a separate instruction behind vmcnt(0) where the value is carried
+// round the loop.
+__device__ __forceinline__ void tile_gather(TileGroup &G, uint32_t d0, uint32_t d1, uint32_t i0, uint32_t tg8, uint32_t j8, const uint8_t *connb) {
+    uint32_t lb[TILE_GS], yy[TILE_GS];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) {
+    for (uint32_t u = 0; u < TILE_GS; ++u) {
         const uint32_t D0 = (uint32_t)__builtin_amdgcn_readlane((int)d0, (int)(i0 + u));
         const uint32_t D1 = (uint32_t)__builtin_amdgcn_readlane((int)d1, (int)(i0 + u));
-        lb[u] = lds_ld<uint32_t>((D0 & 0x3FFFFu) + min(tg8, (D0 >> 18) & 0x3Fu) + 4u);
-        yy[u] = lds_ld<uint32_t>(D1 + min(j8, (D0 >> 24) & 0x3Fu) + 4u);
+        const uint32_t na = (D0 & 0x3FFFFu) + min(tg8, (D0 >> 18) & 0x3Fu);
+        const uint32_t ba = D1 + min(j8, (D0 >> 24) & 0x3Fu);
+        lb[u] = lds_ld<uint32_t>(na + 4u);
+        yy[u] = lds_ld<uint32_t>(ba + 4u);
+        G.ad[u] = TilePackLds::pack(na, ba);
+        asm("" : "+v"(G.ad[u]));   // opaque: left alone, the compiler sees through the pack and carries both addresses to the sweep, two registers a tile
     }
-    __builtin_amdgcn_sched_barrier(0);  // the sixteen reads are one round trip
+    __builtin_amdgcn_sched_barrier(0);  // the group's reads are one round trip
 #pragma unroll
-    for (int u = 0; u < 8; ++u) {
+    for (uint32_t u = 0; u < TILE_GS; ++u) {
         typedef uint32_t __attribute__((aligned(2))) u32_a2;
         G.c[u] = *(const u32_a2 *)(connb + (lb[u] + (yy[u] & 0xFFFFu)));
         __builtin_amdgcn_sched_barrier(0);
     }
 }
-// cnt: tiles of the group to sweep (8, or fewer at the end of a list that is not padded: GUARD); rv / ry: the running minimum of the target group in progress.
+// cnt: tiles of the group to sweep (TILE_GS, or fewer at the end of a list that is not padded: GUARD); rv / ry: the running minimum of the target group in
+// progress.  Of the descriptor only the first / last chunk bits are read here (one v_readlane; the scalar tests are free beside it).
+// TilePackLds::node_addr in ONE instruction: the compiler turns (w & 0xFFFF) << 3 into a shift and a mask (the upper half-word's `>> 16 << 3` it does
+// fold into one sdwa shift by itself).  The shift count sits in a VGPR: gfx9's SDWA takes no inline constant as src0.  tests/test_tile_pack_cpu.py
+// covers TilePackLds::node_addr, NOT this spelling of it: that the two agree rests on the GPU parity tests (tests/test_gpu_tile_groups.py and the rest
+// of the gpu suite run every sweep through it).
+__device__ __forceinline__ uint32_t tile_node_addr(uint32_t w) {
+    static_assert(TilePackLds::unit == 8, "the shift below");
+    uint32_t r;
+    asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_0" : "=v"(r) : "v"(3u), "v"(w));
+    return r;
+}
 template <bool GUARD>
-__device__ __forceinline__ void tile_sweep8(const TileGroup &G, uint32_t d0, uint32_t d1, uint32_t i0, uint32_t cnt, uint32_t tg8, uint32_t j8, uint32_t a_bk, int32_t &rv, uint32_t &ry) {
+__device__ __forceinline__ void tile_sweep(const TileGroup &G, uint32_t d0, uint32_t i0, uint32_t cnt, uint32_t a_bk, int32_t &rv, uint32_t &ry) {
 #pragma unroll
-    for (int u = 0; u < 8; ++u) {
-        if (GUARD && (uint32_t)u >= cnt) break;
+    for (uint32_t u = 0; u < TILE_GS; ++u) {
+        if (GUARD && u >= cnt) break;
         const uint32_t D0 = (uint32_t)__builtin_amdgcn_readlane((int)d0, (int)(i0 + u));
-        const uint32_t na = (D0 & 0x3FFFFu) + min(tg8, (D0 >> 18) & 0x3Fu);
+        const uint32_t na = tile_node_addr(G.ad[u]);
         const uint32_t cs = lds_ld<uint32_t>(na);
-        const uint2 e0 = lds_ld2((uint32_t)__builtin_amdgcn_readlane((int)d1, (int)(i0 + u)) + min(j8, (D0 >> 24) & 0x3Fu));
+        const uint2 e0 = lds_ld2(TilePackLds::bucket_addr(G.ad[u]));
         __builtin_amdgcn_sched_barrier(0);
         const int32_t v0 = (int32_t)e0.x + (int32_t)(int16_t)G.c[u];
         auto reduce_and_store = [&](int32_t bv, uint32_t by) {
@@ -416,28 +440,35 @@ __device__ __forceinline__ void tile_sweep8(const TileGroup &G, uint32_t d0, uin
 // Tiles [ta, tb) of the list at `tiles` (LDS), in order.  null_tile: what the lanes past the end of a window hold -- a descriptor whose gather address is
 // always valid and that is never swept (the last group's gather reads it for the tiles it does not have: NOT a group already swept, whose nodes' row offsets
 // have their best predecessors in the low half by now).  sweep_on = false: measurement (every group's gather, no sweep).
-// A window's groups are gathered one ahead of the sweep: while group g is swept out of one register set the costs of group g + 1 arrive in the other, and
-// are moved over when the sweep is through (eight register moves a group: by then they have long arrived).  Nothing is gathered behind a window's LAST group
-// -- the earlier form alternated the two sets and, to keep the compiler's wait counts exact on every path, gathered "for nothing" behind the end: a third of
-// all gathers on a cfg 2 sentence (~64 tiles in windows of 56, as they were: 13 group gathers for 8 groups) -- and only the last group's sweep (code of its own) tests a
-// tile against the count, so lists need no padding to whole groups.
+// A window's groups are gathered one ahead of the sweep: while group g is swept out of one register set the costs and addresses of group g + 1 arrive in the
+// other.  The group loop is unrolled by two so that the sets swap roles instead of being copied; it has ONE exit, and the window's last one or two groups
+// follow it (with an exit in the middle of the pair the compiler duplicated both sets: 128 VGPRs and scratch).  Nothing is gathered behind a window's LAST
+// group -- an earlier form gathered "for nothing" behind the end to keep the wait counts exact: a third of all gathers on a cfg 2 sentence -- and only the last
+// group's sweep (code of its own) tests a tile against the count, so lists need no padding to whole groups.
 __device__ __forceinline__ void tiles_run(const uint2 *tiles, uint32_t ta, uint32_t tb, uint2 null_tile, uint32_t lane, uint32_t a_bk, const uint8_t *connb, bool sweep_on) {
     const uint32_t j8 = 8u * (lane & 7u), tg8 = lane & 0x38u;   // lane = 8 ti + j
     int32_t rv = 0; uint32_t ry = 0;
-    for (uint32_t w0 = ta; w0 < tb; w0 += 64) {       // a window of 64 descriptors (eight groups) in registers, read out with v_readlane; lanes past the end: the null tile
+    for (uint32_t w0 = ta; w0 < tb; w0 += 64) {       // a window of 64 descriptors (64 / TILE_GS groups) in registers, read out with v_readlane; lanes past the end: the null tile
         const uint2 dd = w0 + lane < tb ? tiles[w0 + lane] : null_tile;
         const uint32_t d0 = dd.x, d1 = dd.y;
-        const uint32_t nt = min(64u, tb - w0), ng = (nt + 7u) >> 3;
+        const uint32_t nt = min(64u, tb - w0), ng = (nt + TILE_GS - 1u) / TILE_GS;
         TileGroup GA, GB;
-        tile_gather8(GA, d0, d1, 0u, tg8, j8, connb);
+        tile_gather(GA, d0, d1, 0u, tg8, j8, connb);
         uint32_t g = 0;
-        for (; g + 1 < ng; ++g) {
-            tile_gather8(GB, d0, d1, 8 * (g + 1), tg8, j8, connb);
-            if (sweep_on) tile_sweep8<false>(GA, d0, d1, 8 * g, 8u, tg8, j8, a_bk, rv, ry);
-            GA = GB;
+        for (; g + 2 < ng; g += 2) {   // GA holds group g
+            tile_gather(GB, d0, d1, TILE_GS * (g + 1), tg8, j8, connb);
+            if (sweep_on) tile_sweep<false>(GA, d0, TILE_GS * g, TILE_GS, a_bk, rv, ry);
+            tile_gather(GA, d0, d1, TILE_GS * (g + 2), tg8, j8, connb);
+            if (sweep_on) tile_sweep<false>(GB, d0, TILE_GS * (g + 1), TILE_GS, a_bk, rv, ry);
         }
-        if (sweep_on) tile_sweep8<true>(GA, d0, d1, 8 * g, nt - 8 * g, tg8, j8, a_bk, rv, ry);
-        else asm volatile("" :: "v"(GA.c[0]), "v"(GA.c[7]));
+        if (g + 2 == ng) {   // two groups left: g in GA, the window's last in GB
+            tile_gather(GB, d0, d1, TILE_GS * (g + 1), tg8, j8, connb);
+            if (sweep_on) {
+                tile_sweep<false>(GA, d0, TILE_GS * g, TILE_GS, a_bk, rv, ry);
+                tile_sweep<true>(GB, d0, TILE_GS * (g + 1), nt - TILE_GS * (g + 1), a_bk, rv, ry);
+            } else asm volatile("" :: "v"(GB.c[0]), "v"(GB.c[TILE_GS - 1]));
+        } else if (sweep_on) tile_sweep<true>(GA, d0, TILE_GS * g, nt - TILE_GS * g, a_bk, rv, ry);
+        else asm volatile("" :: "v"(GA.c[0]), "v"(GA.c[TILE_GS - 1]));
     }
 }
 

@@ -7,15 +7,13 @@
 //   * one double-array walk per start position; its matches (trie id, char length) are parked
 //     in an LDS match buffer so the emit phase re-walks nothing (trie/da.rs:155-182 once per
 //     position);
-//   * every connection cost the sweep will need -- M[right(j)][left(t)] for each (target t,
-//     predecessor j) pair, connection.rs:12-14 -- depends only on the morph ids, not on the DP
-//     values, so all of them are gathered from HBM/L2 into an LDS pair table in ONE parallel pass
-//     before the sweep ("the connection matrix tiled through LDS"); the sweep itself then runs
-//     at LDS latency;
-//   * per position the (target, predecessor) pairs are spread across the 64 lanes, each target
-//     owning an aligned power-of-two lane group, and the strict-'<' first-minimum of
-//     lattice.rs:125-139 is a DPP butterfly min-reduction on the 64-bit key
-//     (total ^ signbit, predecessor node index).
+//   * stage B runs over a list of TILES -- up to 8 targets x 8 predecessors of one start position, pair (ti, j) on lane 8 ti + j (kgpu_device.h:
+//     tiles_run).  A connection cost M[right(j)][left(t)] (connection.rs:12-14) depends only on the morph ids, not on the DP values: every lane
+//     loads its own from the matrix (L2) into a REGISTER, a group of four tiles ahead of the sweep, so the matrix's latency is off the Viterbi
+//     dependency chain and there is no pair table in LDS;
+//   * the sweep adds the predecessor's dp and that cost, keeps the running lexicographic minimum (total, bucket word) across the chunks of a target
+//     group and, on the group's last chunk, takes two 32-bit DPP minima over the eight lanes of a target: the strict-'<' first minimum of
+//     lattice.rs:125-139 (the bucket word's upper half is the node index, ascending in insertion order).
 //
 // LDS page pool.  A workgroup is W independent wavefronts sharing one pool of 64 pages (a u64
 // bitmap, first-fit runs of contiguous pages, LDS atomics).  Every wavefront reserves what its
@@ -50,32 +48,6 @@ constexpr uint32_t NONE16 = 0xFFFFu;
 #ifndef KGPU_EST_SLACK
 #define KGPU_EST_SLACK 768
 #endif
-
-// ---- DPP butterfly: min over aligned groups of 2^lg lanes, every lane gets it.
-// The key is one u64 (total ^ signbit) << 32 | predecessor node index, so one
-// v_cmp_lt_u64 + two v_cndmask per step, no branches.
-template <int CTRL>
-__device__ __forceinline__ uint64_t dpp_min_step(uint64_t k) {
-    const uint32_t oh = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(k >> 32), CTRL, 0xF, 0xF, true);
-    const uint32_t ol = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)k, CTRL, 0xF, 0xF, true);
-    const uint64_t o = ((uint64_t)oh << 32) | ol;
-    return o < k ? o : k;
-}
-__device__ __forceinline__ uint64_t shfl_min_step(uint64_t k, int d) {
-    const uint32_t oh = (uint32_t)__shfl_xor((int)(uint32_t)(k >> 32), d, 64);
-    const uint32_t ol = (uint32_t)__shfl_xor((int)(uint32_t)k, d, 64);
-    const uint64_t o = ((uint64_t)oh << 32) | ol;
-    return o < k ? o : k;
-}
-__device__ __forceinline__ uint64_t group_min(uint64_t k, uint32_t lg) {  // lg wave-uniform
-    if (lg >= 1) k = dpp_min_step<0xB1>(k);   // quad_perm [1,0,3,2]
-    if (lg >= 2) k = dpp_min_step<0x4E>(k);   // quad_perm [2,3,0,1]
-    if (lg >= 3) k = dpp_min_step<0x141>(k);  // row_half_mirror
-    if (lg >= 4) k = dpp_min_step<0x140>(k);  // row_mirror
-    if (lg >= 5) k = shfl_min_step(k, 16);
-    if (lg >= 6) k = shfl_min_step(k, 32);
-    return k;
-}
 
 __device__ __forceinline__ uint32_t align_up(uint32_t v, uint32_t a) { return (v + a - 1) & ~(a - 1); }
 
@@ -282,7 +254,8 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(KGPU_POOL_
         constexpr uint32_t MS = WIDE ? 8u : 4u;   // (launch_tokenize_pool: one word when d.leaf_dup and fewer than 2^21 records)
         const uint32_t need1 = align_up(B + 4, 4) + 22 * (C + 2) + 2 * align_up(C + 2, 4) + align_up(C * MAXM * MS, 16) + 32;
         const uint32_t est = max(need1, (uint32_t)(((uint64_t)B * a.est_q8) >> 8) + KGPU_EST_SLACK);
-        uint32_t npg = own_slice ? POOL_PAGES : pages_for(est);
+        // (clamped: pages_for is exact below 2^32 / page bytes and B * est_q8 can be tens of MB; anything beyond the pool is routed on either way)
+        uint32_t npg = own_slice ? POOL_PAGES : pages_for(min(est, pool_cap + page));
         // routing: a sentence expected to need more than max_pages would hold a large part of the pool for a long
         // time (LDS x time grows with the square of the length); it is better served by the long-sentence kernel
         if (own_slice ? need1 > pool_cap : npg > max_pages) { defer_s(s); continue; }
@@ -803,7 +776,7 @@ static int launch_pool_wide(bool wide, const PoolArgs &pa, uint32_t pool_bytes, 
 int launch_tokenize_pool(const DictView &d, const BatchArgs &a, const WorkIO &io, uint32_t pool_bytes, uint32_t waves,
                          uint32_t max_pages, int n_workgroups, uint32_t stop_after, void *stream) {
     const uint32_t page = ((pool_bytes - POOL_HDR) / POOL_PAGES) & (waves == 1 ? ~7u : ~15u);   // (a workgroup of one wavefront owns its slice: finer pages)
-    if (page == 0) return (int)hipErrorInvalidValue;
+    if (page == 0 || !TilePackLds::fits(pool_bytes)) return (int)hipErrorInvalidValue;   // (stage B packs LDS addresses: kgpu_tilepack.h)
     const PoolArgs pa{d, a, io, pool_bytes, max_pages, stop_after, page, (uint32_t)((1ull << 32) / page) + 1u};
     const bool byte_walk = d.da2 == nullptr, wide = !(d.leaf_dup && d.n_unk_morph < (1u << 21));
     if (a.count_work) return byte_walk ? launch_pool_wide<true, true>(wide, pa, pool_bytes, waves, n_workgroups, stream) : launch_pool_wide<true, false>(wide, pa, pool_bytes, waves, n_workgroups, stream);

@@ -1,0 +1,42 @@
+// kanpyo_amd/csrc/kgpu_tilepack.h -- the two LDS addresses of a stage-B tile in ONE 32-bit word (kgpu_device.h: the gather computes a tile's node and
+// bucket address once and hands both to the sweep in a single register).  No HIP in here: the same code is compiled for the host by
+// tests/test_tile_pack_cpu.py.
+//
+// Both addresses are 8-byte aligned (node[] and bk[] hold uint2 entries at 8-byte aligned bases, the lane offsets are multiples of 8), so a half-word
+// holds an address in units of 2^SHIFT bytes, SHIFT <= 3:
+//   SHIFT = 0: byte addresses -- pack is one shift-or, unpack an `and` and a shift; holds LDS addresses below 64 KB only;
+//   SHIFT = 3: 8-byte units -- one shift more in the pack; holds addresses below 512 KB, i.e. every LDS size of the chip (160 KB per workgroup).
+// Both LDS kernels use SHIFT = 3 (TilePackLds): the pool kernel runs with pools of up to 160 KB (KGPU_POOL=160:4) and one instantiation serves every
+// shape -- a byte-form twin of the kernel for launches of at most 64 KB would save one VALU instruction per tile and cost a second copy of every
+// instantiation.  `fits` is what a launch has to check for a form: the static_assert below holds SHIFT = 3 against the chip's LDS, and the
+// launches check the LDS size they request (launch_tokenize_pool, launch_tokenize_window).
+#pragma once
+#include <cstdint>
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define KGPU_HD __host__ __device__ __forceinline__
+#else
+#define KGPU_HD inline
+#endif
+
+namespace kgpu {
+
+template <uint32_t SHIFT>
+struct TilePack {
+    static_assert(SHIFT <= 3, "node and bucket entries are 8-byte aligned, not more");
+    static constexpr uint32_t unit = 1u << SHIFT;
+    static constexpr uint32_t limit = 65536u << SHIFT;   // the first LDS address a half-word cannot name
+    // every address inside an LDS allocation of `lds_bytes` (addresses 0 .. lds_bytes - 1) can be packed
+    static constexpr bool fits(uint32_t lds_bytes) { return lds_bytes <= limit; }
+    // na, ba: multiples of 8 below `limit`
+    static KGPU_HD constexpr uint32_t pack(uint32_t na, uint32_t ba) { return (na >> SHIFT) | (ba << (16u - SHIFT)); }
+    static KGPU_HD constexpr uint32_t node_addr(uint32_t w) { return (w & 0xFFFFu) << SHIFT; }
+    static KGPU_HD constexpr uint32_t bucket_addr(uint32_t w) { return (w >> 16) << SHIFT; }
+};
+
+constexpr uint32_t LDS_MAX_BYTES = 160u * 1024u;   // per workgroup on gfx950
+typedef TilePack<3> TilePackLds;
+static_assert(TilePackLds::fits(LDS_MAX_BYTES), "the unit form must hold every LDS address of the chip");
+static_assert(!TilePack<0>::fits(LDS_MAX_BYTES) && TilePack<0>::fits(64u * 1024u), "the byte form ends at 64 KB");
+
+}  // namespace kgpu

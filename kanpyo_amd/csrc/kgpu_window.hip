@@ -1080,6 +1080,7 @@ int window_team_workgroups_per_cu(uint32_t lds_bytes) {
 template <bool PROF, int TEAM>
 static int launch_window_inst(const WinArgs &wa, int n_workgroups, void *stream) {
     const uint32_t tb = team_lds_bytes(wa.lds_bytes, TEAM);
+    if (!TilePackLds::fits(tb)) return (int)hipErrorInvalidValue;   // (stage B packs LDS addresses: kgpu_tilepack.h)
     if (tb > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void *)k_tokenize_window<PROF, TEAM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tb);
         if (e != hipSuccess) return (int)e;

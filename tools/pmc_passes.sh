@@ -15,6 +15,7 @@ for grp in \
   "WRITE_SIZE" \
   "TCP_TOTAL_ACCESSES_sum TCP_TCC_READ_REQ_sum TCP_TCC_READ_REQ_LATENCY_sum GRBM_GUI_ACTIVE"; do
   i=$((i+1))
-  timeout 240 rocprofv3 --pmc $grp --output-format csv -d "$OUT/pass$i" -- "$@" > "$OUT/pass$i.log" 2>&1
-  echo "pass $i rc=$? : $grp"
+  timeout -k 10 240 rocprofv3 --pmc $grp --output-format csv -d "$OUT/pass$i" -- "$@" > "$OUT/pass$i.log" 2>&1; rc=$?
+  echo "pass $i rc=$rc : $grp"
+  if [ $rc -ne 0 ]; then echo "pass $i failed: no further pass is started (see $OUT/pass$i.log)" >&2; exit $rc; fi   # a pass that failed or timed out ends the script
 done

@@ -5,9 +5,10 @@ OUT=$(realpath -m "$1"); shift; REPO=$(cd "$(dirname "$0")/.." && pwd)
 STOPS=${@:-1 2 3 4 5 6 7 0}
 mkdir -p "$OUT"; cd /tmp && export TMPDIR=/tmp
 for k in $STOPS; do
-  ABLATE_STOP=$k timeout 200 rocprofv3 --pmc ${KGPU_PMC_COUNTERS:-SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU} \
-     --output-format csv -d "$OUT/stop$k" -- python "$REPO/tools/ablate.py" child cfg2 4096 > "$OUT/stop$k.log" 2>&1
-  echo "stop $k rc=$?"
+  ABLATE_STOP=$k timeout -k 10 200 rocprofv3 --pmc ${KGPU_PMC_COUNTERS:-SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU} \
+     --output-format csv -d "$OUT/stop$k" -- python "$REPO/tools/ablate.py" child cfg2 4096 > "$OUT/stop$k.log" 2>&1; rc=$?
+  echo "stop $k rc=$rc"
+  if [ $rc -ne 0 ]; then echo "stop $k failed: no further pass is started (see $OUT/stop$k.log)" >&2; exit $rc; fi   # a pass that failed or timed out ends the script
 done
 python - "$OUT" $STOPS <<'PY'
 import csv, glob, sys
