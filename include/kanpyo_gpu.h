@@ -399,6 +399,22 @@ int kgpu_tokenize_text_lines(kgpu_dict *d, const uint8_t *text, uint64_t len,
                              uint8_t *out_text, uint64_t text_capacity, uint64_t *text_offsets, uint64_t offsets_capacity,
                              uint8_t *status, uint64_t *n_lines, uint64_t *n_bytes);
 
+/* ---- the `kanpyo graphviz` output (reference src/bin/kanpyo.rs:31-48,127-148 graphviz over src/graphviz.rs:30-163) ----
+ * Lattice::build + the forward pass of Lattice::viterbi + Graphviz::graphviz(dpi, full_state) for n sentences in host memory, all on the
+ * device: text_offsets[i] .. text_offsets[i + 1] (n + 1 entries) is sentence i's DOT document, byte for byte what the reference prints --
+ * the five header lines with dpi in decimal (:36-40), one line per visible node (:55-119: every node in insertion order when full_state
+ * is non-zero, else what the BFS from the last node reaches, :10-28, in the BTreeSet's order), the edge lines (:120-161) and "}".
+ * Labels hold the surface, the morph's feature names without "*" joined by '/', and the cost, separated by newline bytes; nothing is
+ * escaped, as in the reference.  A sentence that is not UTF-8 gets KGPU_SENT_INVALID_UTF8 and 0 bytes (status may be NULL); one whose
+ * lattice does not fit the largest scratch arena gets KGPU_SENT_NO_SCRATCH and 0 bytes.  Needs kgpu_dict_set_features
+ * (KGPU_ERR_INVALID_ARG without).  KGPU_ERR_CAPACITY: *n_bytes is the exact size needed (the kgpu_tokenize_batch_lines protocol; a
+ * call whose input is one chunk -- up to 256 KiB and 1024 sentences -- has written nothing then).  A fixed number of launches per chunk
+ * of the input, whatever it holds; the chunks run one after the other: a debugging aid for batches, not a throughput path. */
+int kgpu_graphviz_batch(kgpu_dict *d, const uint8_t *utf8, const uint64_t *offsets, uint64_t n,
+                        uint64_t dpi, int full_state,
+                        uint8_t *text, uint64_t text_capacity, uint64_t *text_offsets /* n + 1 */,
+                        uint8_t *status /* may be NULL */, uint64_t *n_bytes);
+
 #ifdef __cplusplus
 }
 #endif

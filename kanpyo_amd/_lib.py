@@ -17,6 +17,7 @@ KGPU_ERR_NO_DEVICE = 5
 KGPU_ERR_INTERNAL = 6
 KGPU_SENT_OK = 0
 KGPU_SENT_INVALID_UTF8 = 1
+KGPU_SENT_NO_SCRATCH = 2
 KGPU_SENT_TRUNCATED = 3
 
 # every symbol include/kanpyo_gpu.h declares
@@ -27,7 +28,7 @@ SYMBOLS = [
     "kgpu_host_alloc", "kgpu_host_free", "kgpu_lattice_dump", "kgpu_lattice_free",
     "kgpu_dict_get_routing", "kgpu_tokenize_batch_multi", "kgpu_tokenize_batch_multi_compact", "kgpu_multi_create", "kgpu_multi_destroy", "kgpu_multi_tokenize_device", "kgpu_multi_sync",
     "kgpu_dict_set_features", "kgpu_tokenize_batch_lines", "kgpu_format_lines_device", "kgpu_ctx_sync_lines", "kgpu_split_lines",
-    "kgpu_split_lines_device", "kgpu_ctx_sync_split", "kgpu_tokenize_text_lines",
+    "kgpu_split_lines_device", "kgpu_ctx_sync_split", "kgpu_tokenize_text_lines", "kgpu_graphviz_batch",
 ]
 
 
@@ -170,7 +171,9 @@ def lib():
         L.kgpu_split_lines_device.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint64]
         L.kgpu_ctx_sync_split.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.kgpu_tokenize_text_lines.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.kgpu_graphviz_batch.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_int, vp, C.c_uint64, vp, vp, C.POINTER(C.c_uint64)]
         L.kgpu_debug_feature_pool.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_uint64, C.c_uint64, vp, C.c_uint64, vp, C.POINTER(C.c_uint64)]
+        L.kgpu_debug_label_pool.argtypes = L.kgpu_debug_feature_pool.argtypes
         _lib = L
     return _lib
 

@@ -5,7 +5,12 @@ that one string is tokenized untrimmed; without it stdin is read line by line (s
 read_line + trim_end do) -- here in blocks of whole lines, each tokenized and rendered on the device in one kgpu_tokenize_batch_lines
 call and written out as soon as it is done.  `--split device` hands each block to kgpu_tokenize_text_lines as it was read: the split and the
 trim run on the device too (`--split host`, the default, splits with kgpu_split_lines on the host).  A line that is not UTF-8 ends the
-run as the reference's `expect` panic does: the lines before it are printed, exit status 101.  No subcommand means `tokenize` from stdin.  The `graphviz` subcommand is not served.
+run as the reference's `expect` panic does: the lines before it are printed, exit status 101.  No subcommand means `tokenize` from stdin.
+
+`python -m kanpyo_amd graphviz [INPUT] [-c DICT] [-f/--full-state] [--dpi N]`: the reference's `kanpyo graphviz` (src/bin/kanpyo.rs:31-48,
+127-148 over src/graphviz.rs:30-163): the lattice of ONE sentence as a DOT document, built and rendered on the device in one
+kgpu_graphviz_batch call.  With INPUT that string is drawn untrimmed; without it ONE line of stdin is read and trimmed (read_line +
+trim_end, not a loop: further lines are ignored, empty stdin is the empty sentence).  A first line that is not UTF-8 ends with status 101.
 """
 from __future__ import annotations
 
@@ -85,7 +90,54 @@ def tokenize(args, stdin, stdout) -> int:
     return 0
 
 
-def main(argv=None) -> int:
+# what Rust's str::trim_end strips: the Unicode White_Space code points (char::is_whitespace)
+WHITE_SPACE = "\t\n\x0b\x0c\r \x85\xa0\u1680\u2000\u2001\u2002\u2003\u2004\u2005\u2006\u2007\u2008\u2009\u200a\u2028\u2029\u202f\u205f\u3000"
+
+
+def first_line(data: bytes) -> bytes:
+    """What `kanpyo graphviz` draws when stdin holds `data` (src/bin/kanpyo.rs:134-143): read_line takes the bytes up to and including the
+    first '\n' (all of them if there is none) and fails unless they are UTF-8 (UnicodeDecodeError here); trim_end strips the trailing
+    White_Space.  The lines behind the first are never read."""
+    cut = data.find(b"\n") + 1
+    line = data[:cut] if cut else data
+    return line.decode("utf-8").rstrip(WHITE_SPACE).encode("utf-8")
+
+
+def graphviz(args, stdin, stdout) -> int:
+    from . import dictfile
+    from .tokenizer import Tokenizer
+
+    if args.input is not None:   # that one string, untrimmed
+        raw = os.fsencode(args.input)
+    else:
+        try:
+            raw = first_line(stdin.readline())
+        except UnicodeDecodeError:
+            print("thread 'main' panicked: failed to read from stdin: stream did not contain valid UTF-8", file=sys.stderr)
+            return PANIC_STATUS
+    df = dictfile.load_dict(args.custom_dict or default_dict_path())
+    tok = Tokenizer(df.dict)
+    tok.set_features(df.morph_feature_table, df.unk_feature_table)
+    one = np.frombuffer(raw, dtype=np.uint8)
+    text, _, status = tok.graphviz_packed(one, np.array([0, one.size], dtype=np.uint64), dpi=args.dpi, full_state=args.full_state)
+    if status[0]:   # (an INPUT argument that is not UTF-8: the reference's argument parser rejects it)
+        print(f"kanpyo_amd: the input cannot be drawn (sentence status {int(status[0])})", file=sys.stderr)
+        return 2
+    stdout.write(text.tobytes())
+    stdout.flush()
+    return 0
+
+
+def _dpi(text: str) -> int:
+    """--dpi is a usize in the reference (src/bin/kanpyo.rs:45-47): a decimal in 0 .. 2^64 - 1, nothing else."""
+    digits = text[1:] if text.startswith("+") else text   # (usize::from_str takes a leading '+')
+    if not digits.isascii() or not digits.isdigit() or int(digits) >= 1 << 64:
+        raise argparse.ArgumentTypeError(f"invalid value {text!r}: an unsigned integer below 2^64")
+    return int(digits)
+
+
+def parse_args(argv=None):
+    """The reference's command line (src/bin/kanpyo.rs:14-49).  -> the namespace; .command is "tokenize" or "graphviz"."""
     p = argparse.ArgumentParser(prog="kanpyo_amd", description="Japanese Morphological Analyzer (kanpyo) on AMD Instinct GPUs")
     sub = p.add_subparsers(dest="command")
     t = sub.add_parser("tokenize", help="Tokenize input text")
@@ -95,12 +147,26 @@ def main(argv=None) -> int:
     t.add_argument("--split", choices=["host", "device"], default="host",
                    help="Where stdin's blocks are split into lines and trimmed [default: host]")
     t.add_argument("--block-bytes", type=int, default=BLOCK_BYTES, help=argparse.SUPPRESS)
+    g = sub.add_parser("graphviz", help="Output lattice in Graphviz format")
+    g.add_argument("input", nargs="?", default=None, help="Input text to analyze [default: one line of stdin]")
+    g.add_argument("-d", "--dict", choices=["ipa"], default="ipa", help="Dictionary")
+    g.add_argument("-c", "--custom-dict", default=None, help="Custom dictionary (.dict)")
+    g.add_argument("-f", "--full-state", action="store_true", help="Output full state of lattice")
+    g.add_argument("--dpi", type=_dpi, default=48, help="DPI of output image [default: 48]")
     args = p.parse_args(argv)
     if args.command is None:   # src/bin/kanpyo.rs:173: no subcommand == tokenize from stdin, default dictionary
         args = t.parse_args([])
+        args.command = "tokenize"
+    return args
+
+
+def main(argv=None) -> int:
+    args = parse_args(argv)
     from . import _lib
 
     try:
+        if args.command == "graphviz":
+            return graphviz(args, sys.stdin.buffer, sys.stdout.buffer)
         return tokenize(args, sys.stdin.buffer, sys.stdout.buffer)
     except _lib.KgpuError as e:
         print(f"kanpyo_amd: {e}", file=sys.stderr)

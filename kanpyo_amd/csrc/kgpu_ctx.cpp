@@ -14,9 +14,6 @@
 
 // ----------------------------------------------------------------------- ctx
 
-static constexpr size_t ARENA_INITIAL = 1ull << 28;  // 256 MiB; only the general (HBM-scratch) kernel uses it, grows x2 on demand
-static constexpr size_t ARENA_MAX = 1ull << 37;      // 128 GiB
-
 extern "C" int kgpu_ctx_create(kgpu_dict *d, void *hip_stream, kgpu_ctx **out) {
     if (!d || !out) { set_error("kgpu_ctx_create: null argument"); return KGPU_ERR_INVALID_ARG; }
     *out = nullptr;
@@ -77,6 +74,7 @@ extern "C" void kgpu_ctx_destroy(kgpu_ctx *c) {
     c->lines_report.release(); c->split_report.release();
     c->lines_len.release(); c->lines_text.release(); c->lines_off.release(); c->lines_status.release();
     c->split_agg.release(); c->split_raw.release(); c->split_text.release(); c->split_off.release();
+    c->gv_desc.release(); c->gv_len.release(); c->gv_text.release();
     if (c->switch_ev) (void)hipEventDestroy(c->switch_ev);
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
     c->arena.release(); c->ovf.release(); c->stat_slots.release(); c->stage.release(); c->tok_count.release();

@@ -73,6 +73,21 @@ __device__ __forceinline__ bool slab_ensure(Slab &s, uint64_t need, const BatchA
     return true;
 }
 
+// A slab of exactly `need` bytes (rounded to 256) that nothing reuses: BatchArgs::keep_lattice, where a sentence's slabs outlive the launch.
+__device__ __forceinline__ bool slab_fresh(Slab &s, uint64_t need, const BatchArgs &a, uint32_t lane) {
+    const uint64_t want = round_up(need, 256);
+    uint64_t off = 0;
+    if (lane == 0) off = atomicAdd(&a.ctl->arena_cursor, (unsigned long long)want);
+    off = bcast64(off);
+    if (off + want > a.arena_bytes) {
+        if (lane == 0) atomicExch(&a.ctl->arena_overflow, 1u);
+        return false;
+    }
+    s.ptr = a.arena + off;
+    s.size = want;
+    return true;
+}
+
 // A leaf's payload: (trie id, duplicate count or NONE = "read Morph8::dup of the first record").
 __device__ __forceinline__ void leaf_decode(const DictView &d, int32_t base, uint32_t &id, uint32_t &dup) {
     const uint32_t enc = (uint32_t)(-base);

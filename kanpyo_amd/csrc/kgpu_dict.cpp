@@ -66,6 +66,10 @@ TestHooks kgpu::test_hooks() {
         if (const char *e = getenv("KGPU_HOST_DEPTH")) cur.depth = strtoull(e, nullptr, 10);
         if (const char *e = getenv("KGPU_HOST_CHUNK_BYTES")) cur.chunk_bytes = strtoull(e, nullptr, 10);
         if (const char *e = getenv("KGPU_HOST_CHUNK_SENTS")) cur.chunk_sents = strtoull(e, nullptr, 10);
+        if (const char *e = getenv("KGPU_HOST_GRAPHVIZ_CHUNK_SENTS")) cur.graphviz_chunk_sents = strtoull(e, nullptr, 10);  // kgpu_graphviz_batch: sentences per chunk (0: the default)
+        // ... and the bytes of the scratch arena a chunk's kept lattices may use at first / at most (0: the whole arena / ARENA_MAX): tests of the overflow protocol
+        if (const char *e = getenv("KGPU_HOST_GRAPHVIZ_ARENA_INITIAL")) cur.graphviz_arena_initial = strtoull(e, nullptr, 10);
+        if (const char *e = getenv("KGPU_HOST_GRAPHVIZ_ARENA_MAX")) cur.graphviz_arena_max = strtoull(e, nullptr, 10);
         if (const char *e = getenv("KGPU_MULTI_CHUNK_SENTS")) cur.multi_chunk_sents = strtoull(e, nullptr, 10);  // kgpu_tokenize_batch_multi: sentences per device and chunk (tests: many small super-chunks)
     }
     return cur;

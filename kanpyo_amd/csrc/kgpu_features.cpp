@@ -2,7 +2,9 @@
 //
 // Owns: the bincode 2 (standard config) parser of MorphFeatureTable (kanpyo-dict/src/morph_feature.rs:6-37) with the validation that turns
 // the reference's print-time panics into KGPU_ERR_BAD_DICT, the pre-joined feature pool and its upload (kgpu_dict_set_features), the
-// host-only test hook over both (kgpu_debug_feature_pool), and the CLI's line splitting (kgpu_split_lines: read_line + trim_end).
+// label pool of the graphviz node lines (src/graphviz.rs:56-89) and its upload on the first graphviz call (ensure_label_pool), the
+// host-only test hooks over them (kgpu_debug_feature_pool, kgpu_debug_label_pool), and the CLI's line splitting (kgpu_split_lines:
+// read_line + trim_end).
 #include <algorithm>
 #include <cstring>
 #include <mutex>
@@ -125,9 +127,26 @@ int join_rows(const Table &t, uint64_t need, const char *what, const char *ref_l
     return KGPU_OK;
 }
 
-// Both tables -> the pool in the records' index space (kgpu_runtime.h: kgpu_dict::feat): known rows, then unknown rows.
+// The same rows as a graphviz node's label has them (src/graphviz.rs:56-89): the names equal to "*" dropped, the rest -- an empty name too --
+// joined with '/'.  Behind join_rows, which has checked the rows: a label row is never longer than its ',' row.
+void join_labels(const Table &t, uint64_t need, std::vector<uint8_t> &pool, std::vector<uint32_t> &off) {
+    for (uint64_t r = 0; r < need; ++r) {
+        bool first = true;
+        for (uint64_t j = t.row[r]; j < t.row[r + 1]; ++j) {
+            const uint64_t n0 = t.name[t.ids[j]], n1 = t.name[t.ids[j] + 1];
+            if (n1 - n0 == 1 && t.bytes[(size_t)n0] == '*') continue;
+            if (!first) pool.push_back('/');
+            first = false;
+            pool.insert(pool.end(), t.bytes.begin() + (ptrdiff_t)n0, t.bytes.begin() + (ptrdiff_t)n1);
+        }
+        off.push_back((uint32_t)pool.size());
+    }
+}
+
+// Both tables -> the pool in the records' index space (kgpu_runtime.h: kgpu_dict::feat): known rows, then unknown rows.  lpool / loff: the label
+// pool over the same rows (null: not wanted).
 int build_pool(const uint8_t *known, size_t known_len, const uint8_t *unk, size_t unk_len, uint64_t n_morphs, uint64_t n_unk,
-               std::vector<uint8_t> &pool, std::vector<uint32_t> &off) {
+               std::vector<uint8_t> &pool, std::vector<uint32_t> &off, std::vector<uint8_t> *lpool = nullptr, std::vector<uint32_t> *loff = nullptr) {
     Table tk, tu;
     int rc;
     if ((rc = parse_table(known, known_len, tk, "morph_feature.dict")) || (rc = parse_table(unk, unk_len, tu, "unk.dict feature table"))) return rc;
@@ -135,6 +154,12 @@ int build_pool(const uint8_t *known, size_t known_len, const uint8_t *unk, size_
     off.reserve((size_t)(n_morphs + n_unk + 1));
     if ((rc = join_rows(tk, n_morphs, "morph_feature.dict", "181", pool, off)) || (rc = join_rows(tu, n_unk, "unk.dict feature table", "188", pool, off)))
         return rc;
+    if (lpool) {
+        loff->assign(1, 0);
+        loff->reserve((size_t)(n_morphs + n_unk + 1));
+        join_labels(tk, n_morphs, *lpool, *loff);
+        join_labels(tu, n_unk, *lpool, *loff);
+    }
     return KGPU_OK;
 }
 
@@ -150,7 +175,9 @@ extern "C" int kgpu_dict_set_features(kgpu_dict *d, const uint8_t *morph_feature
     if (d->feat) { set_error("kgpu_dict_set_features: the handle has its feature tables already (once per handle)"); return KGPU_ERR_INVALID_ARG; }
     std::vector<uint8_t> pool;
     std::vector<uint32_t> off;
-    int rc = build_pool(morph_feature_dict, morph_feature_len, unk_feature_dict, unk_feature_len, d->info.n_morphs, d->info.n_unk_morphs, pool, off);
+    std::vector<uint8_t> lpool;
+    std::vector<uint32_t> loff;
+    int rc = build_pool(morph_feature_dict, morph_feature_len, unk_feature_dict, unk_feature_len, d->info.n_morphs, d->info.n_unk_morphs, pool, off, &lpool, &loff);
     if (rc) return rc;
     HIPCHECK(hipSetDevice(d->device));
     void *dp = nullptr, *doff = nullptr;
@@ -164,6 +191,27 @@ extern "C" int kgpu_dict_set_features(kgpu_dict *d, const uint8_t *morph_feature
     d->info.device_bytes += pool_bytes + off_bytes;
     d->feat = (const uint8_t *)dp;
     d->feat_off = (const uint32_t *)doff;
+    d->label_host.swap(lpool);   // stays on the host until a lattice is drawn (ensure_label_pool)
+    d->label_off_host.swap(loff);
+    return KGPU_OK;
+}
+
+// The label pool on the device, uploaded by the first graphviz call of the handle (behind require_features).
+int kgpu::ensure_label_pool(kgpu_dict *d) {
+    std::lock_guard<std::mutex> g(d->feat_mu);
+    if (d->label) return KGPU_OK;
+    HIPCHECK(hipSetDevice(d->device));
+    void *dp = nullptr, *doff = nullptr;
+    const size_t pool_bytes = std::max<size_t>(d->label_host.size(), 16), off_bytes = d->label_off_host.size() * sizeof(uint32_t);
+    HIPCHECK(hipMalloc(&dp, pool_bytes));
+    d->allocs.push_back(dp);
+    HIPCHECK(hipMalloc(&doff, off_bytes));
+    d->allocs.push_back(doff);
+    if (!d->label_host.empty()) HIPCHECK(hipMemcpy(dp, d->label_host.data(), d->label_host.size(), hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(doff, d->label_off_host.data(), off_bytes, hipMemcpyHostToDevice));
+    d->info.device_bytes += pool_bytes + off_bytes;
+    d->label_off = (const uint32_t *)doff;
+    d->label = (const uint8_t *)dp;
     return KGPU_OK;
 }
 
@@ -179,6 +227,20 @@ extern "C" int kgpu_debug_feature_pool(const uint8_t *known, size_t known_len, c
     if (offsets) std::memcpy(offsets, off.data(), off.size() * sizeof(uint32_t));
     if (p.size() > pool_cap) { set_error("pool buffer too small: need %zu", p.size()); return KGPU_ERR_CAPACITY; }
     if (!p.empty()) std::memcpy(pool, p.data(), p.size());
+    return KGPU_OK;
+}
+
+// ... and the label pool of the same tables (offsets: n_morphs + n_unk + 1 entries; the validation is kgpu_debug_feature_pool's).
+extern "C" int kgpu_debug_label_pool(const uint8_t *known, size_t known_len, const uint8_t *unk, size_t unk_len, uint64_t n_morphs, uint64_t n_unk,
+                                     uint8_t *pool, uint64_t pool_cap, uint32_t *offsets, uint64_t *pool_len) {
+    std::vector<uint8_t> p, lp;
+    std::vector<uint32_t> off, loff;
+    const int rc = build_pool(known, known_len, unk, unk_len, n_morphs, n_unk, p, off, &lp, &loff);
+    if (rc) return rc;
+    if (pool_len) *pool_len = lp.size();
+    if (offsets) std::memcpy(offsets, loff.data(), loff.size() * sizeof(uint32_t));
+    if (lp.size() > pool_cap) { set_error("pool buffer too small: need %zu", lp.size()); return KGPU_ERR_CAPACITY; }
+    if (!lp.empty()) std::memcpy(pool, lp.data(), lp.size());
     return KGPU_OK;
 }
 

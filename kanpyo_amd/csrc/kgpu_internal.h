@@ -113,13 +113,28 @@ struct BatchArgs {
     uint32_t *first8;                // [2 n]: position, start of sentence s's first token (0xFFFFFFFF twice: no tokens)
     uint8_t *status8;                // optional (host path): the compaction kernel mirrors status[] there (mapped host memory)
     uint64_t *toff8;                 // optional (host path): ... and tok_offsets[] (n + 1), so that it reads its offsets from HBM, not back over PCIe
+    // general kernel, whole batches (kgpu_graphviz_batch): every sentence's lattice stays in the arena behind the launch -- a fresh slab pair per sentence,
+    // slab N followed by the render passes' per-node scratch (lat_scratch_*) -- and sentence s's descriptor goes to lat_desc[LAT_DESC_WORDS * s ..]:
+    // arena offsets of slab A and slab N, B, C, N, 1 = valid, dp of EOS, (the render's) visible nodes.  The table is zeroed by the host.  0 everywhere else.
+    uint32_t keep_lattice;
+    unsigned long long *lat_desc;
 };                                   // (added to by its owner, summed on the host: hot atomics on a few words would distort the run)
+constexpr uint32_t LAT_DESC_WORDS = 8;
+// The slabs of k_tokenize_general (kgpu_kernels.hip), as kgpu_lattice_dump and the graphviz passes read them.  Slab A: u32[B + 4] arrays, in this order
+// (the kernel has more behind them); slab N: nodeA uint4[N] | bucket uint4[N] | nodeB uint2[N] | pre u32[N].
+enum : uint32_t { SLAB_A_CBYTE = 0, SLAB_A_USPAN = 1, SLAB_A_NB = 2, SLAB_A_BOFF = 3, SLAB_A_BFILL = 4, SLAB_A_PATH = 5 };
+constexpr uint64_t SLAB_N_BYTES_PER_NODE = 44;
+// keep_lattice: the graphviz passes' scratch behind slab N's arrays -- u64[N + 1] x 4 (sorted end|node, sort keys, node-line offsets, edge-group
+// offsets), then u32[N] x 3 (visible id, node of a visible id, flags)
+constexpr uint64_t lat_scratch_off(uint64_t N) { return (N * SLAB_N_BYTES_PER_NODE + 15) & ~15ull; }
+constexpr uint64_t lat_scratch_bytes(uint64_t N) { return (N + 1) * 8 * 4 + N * 4 * 3; }
 constexpr uint32_t STAT_SLOTS = 16384, STAT_WORDS = 32;  // words 0..6: Control::work, 16..25: Control::phase
 
 // Launchers (kgpu_kernels.hip, kgpu_pool.hip, kgpu_window.hip).  `stream` is a hipStream_t.
 struct Step;  // kgpu_chain.h
 int launch_step(const DictView &d, const BatchArgs &a, const Step &s, uint32_t stop_after /* kgpu_ctx_set_ablation; 0 = run everything */, void *stream);
 int launch_general_only(const DictView &d, const BatchArgs &a, void *stream);  // kgpu_lattice_dump: HBM-scratch kernel alone
+int launch_general_keep(const DictView &d, const BatchArgs &a, void *stream);  // kgpu_graphviz_batch: ... over a whole batch, a.keep_lattice set
 int launch_small_call(const DictView &d, const BatchArgs &a, void *stream);  // pool kernel alone, one sentence per wavefront
 int launch_scan_compact(const BatchArgs &a, Control *host_ctl, void *stream, bool small_workgroups);  // host_ctl: device pointer of the pinned result block
 // The CLI's output lines of a batch (kgpu_format.hip; reference src/bin/kanpyo.rs:174-197): `surface \t f1,f2,... \n` per token.
@@ -140,6 +155,24 @@ struct LinesArgs {
     unsigned long long *host_ctl;  // device pointer of pinned, mapped words: [0] total bytes, [1] a record out of range
 };
 int launch_format_lines(const LinesArgs &a, void *stream);
+// The DOT documents of a batch's kept lattices (kgpu_graphviz.hip; reference src/graphviz.rs:30-163).
+struct GraphvizArgs {
+    const uint8_t *utf8;           // as BatchArgs::utf8 / offsets of the launch that kept the lattices
+    const uint64_t *offsets;       // n + 1
+    uint64_t n;
+    uint8_t *arena;                // the arena the descriptors' offsets are relative to
+    unsigned long long *desc;      // BatchArgs::lat_desc; the prepare pass stores a sentence's visible node count in word 7
+    const int16_t *conn; uint32_t conn_rows;   // DictView::conn: the ids in the slabs index it as they are
+    const uint8_t *label;          // the label pool (kgpu_features.cpp): row r is label[label_off[r] .. label_off[r + 1]), rows as LinesArgs::feat
+    const uint32_t *label_off;
+    uint32_t n_morph;
+    uint32_t full_state;
+    uint64_t dpi;
+    uint64_t *sent_len;            // device scratch, n + 1: each document's bytes, then (k_gv_scan, in place) their offsets; [n] = the total
+    uint8_t *text; uint64_t text_cap;   // the write pass: nothing is stored when sent_len[n] > text_cap
+};
+int launch_graphviz_measure(const GraphvizArgs &a, void *stream);   // prepare, lengths, scan: sent_len is final behind it
+int launch_graphviz_write(const GraphvizArgs &a, void *stream);
 // read_line + trim_end over a block in HBM (kgpu_split.hip; reference src/bin/kanpyo.rs:114-122).
 struct SplitTile { uint32_t x, y, z, w; };   // one tile's aggregate, then its carry (kgpu_split.hip says which word is what)
 struct SplitArgs {

@@ -57,7 +57,9 @@ __global__ __launch_bounds__(64) void k_tokenize_general(DictView d, BatchArgs a
 
         // ---- slab A: per-char arrays (C <= B) --------------------------------
         const uint64_t na = (uint64_t)B + 4;
-        if (!slab_ensure(sa, na * (28 + 5 * GMAXM) + 64, a, lane)) {
+        // (keep_lattice: the sentence's own slabs, left behind for the graphviz passes; the descriptor table is zero where a sentence leaves early)
+        unsigned long long *const eos_dp = a.keep_lattice ? a.lat_desc + LAT_DESC_WORDS * s + 6 : a.dump_lattice ? &a.ctl->dump[6] : nullptr;
+        if (!(a.keep_lattice ? slab_fresh(sa, na * (28 + 5 * GMAXM) + 64, a, lane) : slab_ensure(sa, na * (28 + 5 * GMAXM) + 64, a, lane))) {
             if (lane == 0) { a.status[s] = KGPU_SENT_NO_SCRATCH; a.tok_count[s] = 0; }
             continue;
         }
@@ -201,7 +203,7 @@ __global__ __launch_bounds__(64) void k_tokenize_general(DictView d, BatchArgs a
         __syncthreads();
 
         // ---- slab N: per-node arrays -----------------------------------------------
-        if (!slab_ensure(sn, (uint64_t)N * 44 + 64, a, lane)) {
+        if (!(a.keep_lattice ? slab_fresh(sn, lat_scratch_off(N) + lat_scratch_bytes(N) + 64, a, lane) : slab_ensure(sn, (uint64_t)N * 44 + 64, a, lane))) {
             if (lane == 0) { a.status[s] = KGPU_SENT_NO_SCRATCH; a.tok_count[s] = 0; }
             continue;
         }
@@ -254,6 +256,7 @@ __global__ __launch_bounds__(64) void k_tokenize_general(DictView d, BatchArgs a
             nodeB[N - 1] = make_uint2(C, C);
             bucket[0] = make_uint4(0, d.bos_right, 0, 0);  // BOS: dp None -> 0 (lattice.rs:127)
             pre[0] = NONE;
+            if (a.keep_lattice) { nodeA[0] = make_uint4(d.bos_right << 16, 0, 0, 0); nodeB[0] = make_uint2(0, 0); }  // BOS as a node like the others (the dump does not read these)
         }
         __syncthreads();
 
@@ -284,7 +287,7 @@ __global__ __launch_bounds__(64) void k_tokenize_general(DictView d, BatchArgs a
                         const bool ok = tot < INF;
                         pre[t] = ok ? nmin : NONE;
                         if (na_.z != NONE) bucket[na_.z].x = (uint32_t)(ok ? tot : INF);
-                        else if (a.dump_lattice) a.ctl->dump[6] = (unsigned long long)(uint32_t)(ok ? tot : INF);  // EOS has no bucket entry
+                        else if (eos_dp) *eos_dp = (unsigned long long)(uint32_t)(ok ? tot : INF);  // EOS has no bucket entry
                     }
                 }
                 __syncthreads();
@@ -308,7 +311,7 @@ __global__ __launch_bounds__(64) void k_tokenize_general(DictView d, BatchArgs a
                 }
                 pre[t] = prv;
                 if (na_.z != NONE) bucket[na_.z].x = (uint32_t)dpv;
-                else if (a.dump_lattice) a.ctl->dump[6] = (unsigned long long)(uint32_t)dpv;  // EOS has no bucket entry
+                else if (eos_dp) *eos_dp = (unsigned long long)(uint32_t)dpv;  // EOS has no bucket entry
             }
             __syncthreads();
         };
@@ -348,6 +351,11 @@ __global__ __launch_bounds__(64) void k_tokenize_general(DictView d, BatchArgs a
         if (a.dump_lattice && lane == 0) {  // kgpu_lattice_dump: the host reads the lattice straight out of the two slabs
             a.ctl->dump[0] = (unsigned long long)(sa.ptr - a.arena); a.ctl->dump[1] = (unsigned long long)(sn.ptr - a.arena);
             a.ctl->dump[2] = B; a.ctl->dump[3] = C; a.ctl->dump[4] = N; a.ctl->dump[5] = 1;
+        }
+        if (a.keep_lattice && lane == 0) {
+            unsigned long long *ds = a.lat_desc + LAT_DESC_WORDS * s;
+            ds[0] = (unsigned long long)(sa.ptr - a.arena); ds[1] = (unsigned long long)(sn.ptr - a.arena);
+            ds[2] = B; ds[3] = C; ds[4] = N; ds[5] = 1;
         }
         if (a.count_work) {
             wT = wave_sum(wT);
@@ -549,6 +557,13 @@ int launch_small_call(const DictView &d, const BatchArgs &a, void *stream) {
 int launch_general_only(const DictView &d, const BatchArgs &a, void *stream) {
     WorkIO io{nullptr, nullptr, nullptr, nullptr, nullptr};
     hipLaunchKernelGGL(k_tokenize_general, dim3(1), dim3(64), 0, (hipStream_t)stream, d, a, io, 0u);
+    return (int)hipGetLastError();
+}
+
+int launch_general_keep(const DictView &d, const BatchArgs &a, void *stream) {
+    WorkIO io{nullptr, nullptr, nullptr, nullptr, nullptr};
+    const unsigned grid = (unsigned)(a.n < 1 ? 1 : a.n > 4096 ? 4096 : a.n);   // one wavefront a sentence, grid-stride beyond
+    hipLaunchKernelGGL(k_tokenize_general, dim3(grid), dim3(64), 0, (hipStream_t)stream, d, a, io, 0u);
     return (int)hipGetLastError();
 }
 

@@ -1,6 +1,6 @@
 // kanpyo_amd/csrc/kgpu_runtime.h -- the host runtime's own types and the functions its files share: kgpu_dict.cpp (dictionary),
 // kgpu_ctx.cpp (contexts, launch chain), kgpu_host.cpp (large host calls), kgpu_small.cpp (small calls), kgpu_multi.cpp (the
-// multi-device entry points), kgpu_split_host.cpp (lines of a raw block).  Not part of the public ABI.
+// multi-device entry points), kgpu_split_host.cpp (lines of a raw block), kgpu_graphviz_host.cpp (DOT documents of a batch).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -101,6 +101,12 @@ struct kgpu_dict {
     std::mutex feat_mu;
     const uint8_t *feat = nullptr;
     const uint32_t *feat_off = nullptr;
+    // ... and the same rows as a graphviz node's label has them ("*" dropped, '/'-joined): built with the pool above, kept on the host, uploaded by the
+    // handle's first graphviz call (ensure_label_pool, under feat_mu) -- a handle that draws no lattice spends no HBM on it
+    std::vector<uint8_t> label_host;
+    std::vector<uint32_t> label_off_host;
+    const uint8_t *label = nullptr;
+    const uint32_t *label_off = nullptr;
     // One reference for the handle the caller holds plus one per live context: the tables and the shared
     // streams go when the last one does (a context outliving kgpu_dict_destroy keeps working).
     std::atomic<int> refs{1};
@@ -139,6 +145,8 @@ struct kgpu_ctx {
     DevBuf lines_len;
     HostReport lines_report;
     PinBuf lines_text, lines_off, lines_status;
+    // the DOT documents of a chunk (kgpu_graphviz_host.cpp): the lattice descriptors, the documents' lengths / offsets, the chunk's text
+    DevBuf gv_desc, gv_len, gv_text;
     // read_line + trim_end on the device (kgpu_split.hip): the tile aggregates, what the carry kernel publishes ([0] lines, [1] packed bytes), and
     // for kgpu_tokenize_text_lines the device copy of the raw block, its packed lines and their offsets
     DevBuf split_agg, split_raw, split_text, split_off;
@@ -221,7 +229,7 @@ struct WorkerPool {
     void task_done(std::atomic<int> &counter); // a task's last statement
 };
 WorkerPool &workers();
-struct TestHooks { bool no_small_calls = false, plain_leaves = false, byte_trie = false; uint64_t chunk_bytes = 4ull << 20, chunk_sents = 16384, depth = 12, multi_chunk_sents = 0; };
+struct TestHooks { bool no_small_calls = false, plain_leaves = false, byte_trie = false; uint64_t chunk_bytes = 4ull << 20, chunk_sents = 16384, depth = 12, multi_chunk_sents = 0, graphviz_chunk_sents = 0, graphviz_arena_initial = 0, graphviz_arena_max = 0; };
 TestHooks test_hooks();  // test-only environment hooks, read once per process (or per call under KGPU_TEST_HOOKS_REREAD)
 bool env_flag_now(const char *name);
 
@@ -231,6 +239,8 @@ unsigned planned_long_streams();   // ... and streams for chains that start with
 void dict_release(kgpu_dict *d);   // one reference less: the last one frees the dictionary
 
 // kgpu_ctx.cpp
+constexpr size_t ARENA_INITIAL = 1ull << 28;  // 256 MiB; only the general (HBM-scratch) kernel uses it, grows x2 on demand
+constexpr size_t ARENA_MAX = 1ull << 37;      // 128 GiB
 // the pooled contexts of a dictionary (one per call in flight)
 int pool_get(kgpu_dict *d, kgpu_ctx **c);
 void pool_put(kgpu_dict *d, kgpu_ctx *c);
@@ -243,6 +253,7 @@ int enqueue_lines(kgpu_ctx *c, const uint8_t *d_utf8, const uint64_t *d_offsets,
                   uint8_t *d_text, uint64_t text_capacity, uint64_t *d_text_offsets, const uint8_t *status_in, uint8_t *status_out, const char *who);
 
 int require_features(kgpu_dict *d, const char *who);   // KGPU_ERR_INVALID_ARG unless kgpu_dict_set_features has been called
+int ensure_label_pool(kgpu_dict *d);                   // kgpu_features.cpp: the graphviz label pool on the device (first call uploads it)
 
 // kgpu_host.cpp
 void parallel_copy(void *dst, const void *src, size_t bytes);

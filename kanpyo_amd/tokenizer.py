@@ -193,6 +193,38 @@ class Tokenizer:
         text, _, _ = self.tokenize_lines_packed(utf8, offs)
         return text.tobytes()
 
+    # ---- the lattice pictures (`kanpyo graphviz`, src/bin/kanpyo.rs:127-148 over src/graphviz.rs:30-163) ------
+    def graphviz_packed(self, utf8: np.ndarray, offsets: np.ndarray, dpi: int = 48, full_state: bool = False):
+        """kgpu_graphviz_batch -> (text[uint8], text_offsets[uint64 n+1], status[uint8 n]): sentence i's DOT document is
+        text[text_offsets[i]:text_offsets[i+1]], byte for byte what the reference's Graphviz::graphviz(dpi, full_state) prints."""
+        utf8 = np.ascontiguousarray(utf8, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = offsets.size - 1
+        if n < 0:
+            raise ValueError("offsets needs n+1 entries")
+        total = int(offsets[-1] - offsets[0]) if n else 0
+        cap = total * 512 + 1024 * n + 64
+        L = _lib.lib()
+        while True:
+            text = np.empty(max(cap, 1), dtype=np.uint8)
+            toff = np.empty(n + 1, dtype=np.uint64)
+            status = np.zeros(max(n, 1), dtype=np.uint8)
+            got = C.c_uint64(0)
+            rc = L.kgpu_graphviz_batch(self._h, utf8.ctypes.data if utf8.size else None, offsets.ctypes.data, n, int(dpi), 1 if full_state else 0,
+                                       text.ctypes.data, cap, toff.ctypes.data, status.ctypes.data, C.byref(got))
+            if rc == _lib.KGPU_ERR_CAPACITY and int(got.value) > cap:
+                cap = int(got.value)  # exact size reported by the device
+                continue
+            _lib.check(rc)
+            return text[: int(got.value)], toff[: n + 1], status[:n]
+
+    def graphviz(self, sentences: Sequence, dpi: int = 48, full_state: bool = False) -> List[str]:
+        """What `kanpyo graphviz` prints for each of these sentences (str or bytes): one DOT document per sentence."""
+        utf8, offs = pack_sentences(sentences)
+        text, toff, _ = self.graphviz_packed(utf8, offs, dpi, full_state)
+        raw = text.tobytes()
+        return [raw[int(toff[i]) : int(toff[i + 1])].decode("utf-8") for i in range(len(toff) - 1)]
+
     def routing(self, reset: bool = False) -> dict:
         """kgpu_dict_get_routing: the routing counters of the handle's pooled contexts (small_calls, combined_calls, ...)."""
         r = _lib.Routing()

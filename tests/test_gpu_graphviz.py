@@ -1,0 +1,365 @@
+"""`kanpyo graphviz` on the device (src/bin/kanpyo.rs:127-148 over src/graphviz.rs:30-163): kgpu_graphviz_batch, Tokenizer.graphviz*, the C
+consumer and `python -m kanpyo_amd graphviz`.  Every comparison is bytes against bytes.  The expected documents come from the Python
+statement of the renderer (kanpyo_amd/lattice.py::graphviz) -- over the naive restatement's lattice (oracle/pyref.py) on the fixture and the
+hand dictionaries, over kgpu_lattice_dump's (itself checked against pyref in tests/test_gpu_parity.py and test_gpu_matrix.py) on the
+synthetic dictionary -- with the feature names taken from MorphFeatureTable.features in Python and the connection costs from the
+dictionary's own blob: never from the library's label pool, its ranked matrix or its kernels."""
+import ctypes as C
+import os
+import random
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from conftest import ROOT, fixture_dict_parts, load_golden
+
+pytestmark = pytest.mark.gpu
+
+FIXTURE_INPUTS = ["", "テスト", "テ", "テあ", "あいうえお", "辞書あ辞書"]
+
+
+def _pydict(d):
+    from oracle import pyref
+
+    return pyref.PyDict(d.index_dict, d.connection_dict, d.morph_dict, d.unk_dict, d.char_category, d.invoke_list, d.group_list)
+
+
+def _docs(tok, sents, dpi=48, full_state=False):
+    """The device's documents for these sentences, one call -> (list of bytes, status)."""
+    from kanpyo_amd.tokenizer import pack_sentences
+
+    utf8, offs = pack_sentences(sents)
+    text, toff, status = tok.graphviz_packed(utf8, offs, dpi=dpi, full_state=full_state)
+    raw = text.tobytes()
+    assert toff[0] == 0 and int(toff[-1]) == len(raw) and (np.diff(toff.astype(np.int64)) >= 0).all()
+    return [raw[int(toff[i]) : int(toff[i + 1])] for i in range(len(sents))], status
+
+
+def _want_pyref(pd, known, unk, text, dpi, full_state):
+    from kanpyo_amd.lattice import graphviz
+    from test_lattice_cpu import lattice_from_pyref
+
+    conn = lambda r, l: pd.conn[pd.row * l + r]  # noqa: E731  ConnectionTable::get (connection.rs:12-14)
+    return graphviz(lattice_from_pyref(pd, text), conn, known.features, unk.features, dpi, full_state).encode()
+
+
+@pytest.fixture(scope="module")
+def fixture_tok():
+    from kanpyo_amd import Dict, Tokenizer, _lib
+    from kanpyo_amd.dictfile import MorphFeatureTable
+
+    assert _lib.lib().kgpu_device_count() > 0, "no HIP device: the gpu tests need an MI355X"
+    g = load_golden("fixture_graphviz.json")
+    p = fixture_dict_parts()
+    d = Dict.from_parts(**p)
+    known = MorphFeatureTable.from_features([g["features"]["known"].get(str(i), ["名詞", f"k{i}", "*"]) for i in range(1, len(p["morphs"]) + 1)])
+    unk = MorphFeatureTable.from_features([g["features"]["unknown"][str(i)] for i in range(1, len(p["unk_morphs"]) + 1)])
+    tok = Tokenizer(d)
+    tok.set_features(known, unk)
+    return g, d, tok, known, unk
+
+
+@pytest.fixture(scope="module")
+def synth_gv():
+    from kanpyo_amd import Tokenizer, synth
+    from kanpyo_amd.dictfile import DictFile
+
+    sd = synth.build_dict()
+    known, unk = synth.feature_tables(sd)
+    tok = Tokenizer(sd.dict)
+    tok.set_features(known, unk)
+    return sd, tok, DictFile(sd.dict, known, unk)
+
+
+def _want_dump(tok, df, text, dpi, full_state):
+    from kanpyo_amd.lattice import dump_lattice, graphviz_for
+
+    return graphviz_for(dump_lattice(tok, text), df, dpi, full_state).encode()
+
+
+def test_fixture_dictionary_every_mode(fixture_tok):
+    g, d, tok, known, unk = fixture_tok
+    pd = _pydict(d)
+    sents = [g["input"]] + FIXTURE_INPUTS
+    for full_state in (False, True):
+        for dpi in (48, 300):
+            docs, status = _docs(tok, sents, dpi, full_state)   # ONE call
+            assert not status.any()
+            for s, got in zip(sents, docs):
+                assert got == _want_pyref(pd, known, unk, s, dpi, full_state), (s, dpi, full_state)
+    docs, _ = _docs(tok, sents)
+    assert docs[0] == g["dot"].encode()
+    # "": BOS and EOS compare equal (one visible node, labelled by its id; two node lines with full_state; no edge line either way)
+    assert docs[1].count(b"[label=") == 1 and b'0 [label="BOS"' in docs[1] and b" -- " not in docs[1]
+    full, _ = _docs(tok, sents, 48, True)
+    assert full[1].count(b"[label=") == 2 and b'1 [label="EOS"' in full[1] and b" -- " not in full[1]
+    assert sum(1 for ln in full[0].split(b"\n") if b" -- " in ln) == g["full_state_counts"]["edges"]
+    # an unreachable EOS: empty bests, only EOS is visible and it is labelled BOS
+    assert docs[3].count(b"[label=") == 1 and b'0 [label="BOS"' in docs[3] and b"style=bold" not in docs[3]
+    # the Python class: str documents, and a 64-bit dpi in decimal
+    assert tok.graphviz([g["input"]])[0] == g["dot"]
+    assert tok.graphviz(["テスト"], dpi=2**64 - 1)[0].split("\n")[1] == "dpi=18446744073709551615;"
+
+
+def test_synthetic_batch_both_modes(synth_gv):
+    """A few hundred cfg 2 and cfg 3 sentences in one call, non-BMP characters and katakana runs among them; full_state on the ones up to about
+    200 characters (what the Python renderer affords), in one call too."""
+    from kanpyo_amd import synth
+
+    sd, tok, df = synth_gv
+    sents = synth.make_corpus(sd, 260, 21, "cfg2") + synth.make_corpus(sd, 60, 22, "cfg3") + synth.EDGE_SENTENCES + ["ア" * 40 + "𠮷𩸽" + "カタカナ" * 6]
+    docs, status = _docs(tok, sents)
+    assert not status.any()
+    for s, got in zip(sents, docs):
+        assert got == _want_dump(tok, df, s, 48, False), s
+    short = [s for s in sents if len(s) <= 200][:120] + ["", "𠮷野家で𩸽", "ア" * 60]
+    assert len(short) > 100
+    docs, status = _docs(tok, short, 300, True)
+    assert not status.any()
+    for s, got in zip(short, docs):
+        assert got == _want_dump(tok, df, s, 300, True), s
+
+
+def test_long_sentence_with_a_capped_unknown_run(synth_gv):
+    """More than 1024 characters with a groupable run past MAX_UNKNOWN_LEN (lattice.rs:55), full_state false, between ordinary neighbours."""
+    from kanpyo_amd import synth
+
+    sd, tok, df = synth_gv
+    around = synth.make_corpus(sd, 6, 23, "cfg2")
+    long_ = around[0] + "ア" * 1100 + around[1] + "ゞ" * 30 + around[2]
+    assert len(long_) > 1024
+    sents = [around[3], long_, around[4], "x" * 1500, around[5]]
+    docs, status = _docs(tok, sents)
+    assert not status.any()
+    for s, got in zip(sents, docs):
+        assert got == _want_dump(tok, df, s, 48, False), s[:40]
+
+
+def test_unranked_and_non_square_dictionaries(monkeypatch):
+    """tests/test_gpu_matrix.py's recipe: a ranked non-square matrix and unranked ones (right ids >= rows; an axis of 65 536 or more), costs at
+    the i16 extremes among them.  Every edge label is ConnectionTable::get over the dictionary's own ids."""
+    from kanpyo_amd import Dict, Tokenizer, synth
+    from kanpyo_amd.dictfile import MorphFeatureTable
+    from test_matrix_cpu import transposed_parts
+
+    cases = [(Dict.from_parts(**transposed_parts()), True)]
+    for shape, cost in (("nonsquare", "plain"), ("flat", "extreme"), ("huge", "plain"), ("corner", "ties")):
+        d, _, meta = synth.matrix_case(random.Random(77), shape, cost)
+        cases.append((d, meta["ranked"]))
+    assert {r for _, r in cases} == {True, False}
+    texts = ["", "あ", "あい", "いあx", "あいうえおか" * 5, "xあxいx", "ああああいいいいか" * 3]
+    for d, _ranked in cases:
+        info_tok = Tokenizer(d)
+        info = info_tok.info()
+        known = MorphFeatureTable.from_features([["k", str(i), "*"] for i in range(info["n_morphs"])])
+        unk = MorphFeatureTable.from_features([["*", "u", str(i)] for i in range(info["n_unk_morphs"])])
+        info_tok.set_features(known, unk)
+        pd = _pydict(d)
+        for full_state in (False, True):
+            batch = texts + ([] if full_state else ["あい" * 150, "かおえういあx" * 40])   # (the Python renderer bounds what full_state affords)
+            docs, status = _docs(info_tok, batch, 48, full_state)
+            assert not status.any()
+            for s, got in zip(batch, docs):
+                assert got == _want_pyref(pd, known, unk, s, 48, full_state), (s, full_state)
+        info_tok.close()
+
+
+def _raw_call(tok, utf8, offs, cap, dpi=48, full_state=0, fill=0xAB, with_status=True):
+    from kanpyo_amd import _lib
+
+    n = len(offs) - 1
+    buf = np.full(max(cap, 1) + 8, fill, dtype=np.uint8)
+    toff = np.zeros(n + 1, dtype=np.uint64)
+    status = np.full(max(n, 1), 0xEE, dtype=np.uint8)
+    got = C.c_uint64(0)
+    rc = _lib.lib().kgpu_graphviz_batch(tok.handle, utf8.ctypes.data if utf8.size else None, offs.ctypes.data, n, dpi, full_state, buf.ctypes.data, cap,
+                                        toff.ctypes.data, status.ctypes.data if with_status else None, C.byref(got))
+    return rc, buf, toff, status[:n], got.value
+
+
+def test_protocol(fixture_tok):
+    from kanpyo_amd import Tokenizer, _lib
+    from kanpyo_amd.lattice import dump_lattice
+    from kanpyo_amd.tokenizer import pack_sentences
+
+    g, d, tok, known, unk = fixture_tok
+    sents = [g["input"]] + FIXTURE_INPUTS
+    utf8, offs = pack_sentences(sents)
+    lat0 = dump_lattice(tok, g["input"])
+    tokens0 = [a.copy() for a in tok.tokenize_packed(utf8, offs)]
+    docs, _ = _docs(tok, sents)
+    total = sum(len(x) for x in docs)
+    for cap in (0, total - 1):
+        rc, buf, _, _, need = _raw_call(tok, utf8, offs, cap)
+        assert rc == _lib.KGPU_ERR_CAPACITY and need == total
+        assert (buf == 0xAB).all()   # nothing written
+    rc, buf, toff, status, got = _raw_call(tok, utf8, offs, total)
+    assert rc == _lib.KGPU_OK and got == total and buf[:total].tobytes() == b"".join(docs) and (buf[total:] == 0xAB).all()
+    assert toff.tolist() == np.cumsum([0] + [len(x) for x in docs]).tolist() and not status.any()
+    rc, buf2, toff2, _, _ = _raw_call(tok, utf8, offs, total, with_status=False)   # status may be NULL
+    assert rc == _lib.KGPU_OK and np.array_equal(buf2, buf) and np.array_equal(toff2, toff)
+    # a handle without features
+    bare = Tokenizer(d)
+    rc, *_ = _raw_call(bare, utf8, offs, total)
+    assert rc == _lib.KGPU_ERR_INVALID_ARG and b"kgpu_dict_set_features" in _lib.lib().kgpu_last_error()
+    bare.close()
+    # an invalid sentence mid-batch: status 1, 0 bytes, the neighbours as they were
+    bad = sents[:3] + [b"\xe3\x81", b"\xff"] + sents[3:]
+    bdocs, bstatus = _docs(tok, bad)
+    assert bstatus.tolist() == [0, 0, 0, 1, 1] + [0] * (len(sents) - 3)
+    assert bdocs[3] == b"" and bdocs[4] == b"" and bdocs[:3] + bdocs[5:] == docs
+    # no sentences at all
+    e_utf8, e_offs = pack_sentences([])
+    rc, _, toff, _, got = _raw_call(tok, e_utf8, e_offs, 0)
+    assert rc == _lib.KGPU_OK and got == 0 and toff.tolist() == [0]
+    # the handle's other calls are what they were
+    lat1 = dump_lattice(tok, g["input"])
+    assert lat1.nodes == lat0.nodes and lat1.edges == lat0.edges
+    for a, b in zip(tokens0, tok.tokenize_packed(utf8, offs)):
+        assert np.array_equal(a, b)
+    assert _docs(tok, sents)[0] == docs
+
+
+def test_label_pool_is_uploaded_by_the_first_graphviz_call(fixture_tok):
+    from kanpyo_amd import Tokenizer
+
+    g, d, _, known, unk = fixture_tok
+    t = Tokenizer(d)
+    b0 = t.info()["device_bytes"]
+    t.set_features(known, unk)
+    b1 = t.info()["device_bytes"]
+    assert t.tokenize_lines([g["input"]]) and t.info()["device_bytes"] == b1 > b0   # a handle that draws no lattice pays nothing more
+    assert t.graphviz([g["input"]])[0] == g["dot"]
+    b2 = t.info()["device_bytes"]
+    assert b2 > b1
+    t.graphviz([g["input"]], full_state=True)
+    assert t.info()["device_bytes"] == b2
+    t.close()
+
+
+def test_chunking_gives_the_same_bytes(synth_gv, monkeypatch):
+    from kanpyo_amd import _lib, synth
+    from kanpyo_amd.tokenizer import pack_sentences
+
+    sd, tok, df = synth_gv
+    sents = synth.make_corpus(sd, 40, 24, "cfg2") + ["", b"\xff"] + synth.make_corpus(sd, 10, 25, "cfg3")
+    utf8, offs = pack_sentences(sents)
+    for full_state in (False, True):
+        monkeypatch.delenv("KGPU_HOST_GRAPHVIZ_CHUNK_SENTS", raising=False)
+        text, toff, status = tok.graphviz_packed(utf8, offs, full_state=full_state)
+        monkeypatch.setenv("KGPU_HOST_GRAPHVIZ_CHUNK_SENTS", "1")   # one sentence per chunk
+        text1, toff1, status1 = tok.graphviz_packed(utf8, offs, full_state=full_state)
+        monkeypatch.setenv("KGPU_HOST_GRAPHVIZ_CHUNK_SENTS", "7")
+        text7, toff7, status7 = tok.graphviz_packed(utf8, offs, full_state=full_state)
+        monkeypatch.delenv("KGPU_HOST_GRAPHVIZ_CHUNK_SENTS")
+        assert text.tobytes() == text1.tobytes() == text7.tobytes()
+        assert np.array_equal(toff, toff1) and np.array_equal(toff, toff7)
+        assert status.tolist() == status1.tolist() == status7.tolist() and status.sum() == 1
+    # KGPU_ERR_CAPACITY over several chunks: the exact size all the same (the chunks behind the one that did not fit are only measured)
+    docs, _ = _docs(tok, sents)
+    total = sum(len(x) for x in docs)
+    monkeypatch.setenv("KGPU_HOST_GRAPHVIZ_CHUNK_SENTS", "7")
+    for cap in (0, len(docs[0]) + 5, total - 1):
+        rc, _, _, status, need = _raw_call(tok, utf8, offs, cap)
+        assert rc == _lib.KGPU_ERR_CAPACITY and need == total and status.tolist() == [0] * 41 + [1] + [0] * 10
+    rc, buf, toff, _, got = _raw_call(tok, utf8, offs, total)
+    assert rc == _lib.KGPU_OK and got == total and buf[:total].tobytes() == b"".join(docs) and (buf[total:] == 0xAB).all()
+    monkeypatch.delenv("KGPU_HOST_GRAPHVIZ_CHUNK_SENTS")
+    # more sentences than a default chunk holds
+    many = synth.make_corpus(sd, 1100, 26, "cfg2")
+    docs, status = _docs(tok, many)
+    assert not status.any()
+    for k in (0, 1023, 1024, 1099):
+        assert docs[k] == _want_dump(tok, df, many[k], 48, False)
+
+
+def test_arena_overflow_protocol(fixture_tok, monkeypatch):
+    """The kept lattices of a chunk outgrow the arena: the chunk runs again on a doubled one (KGPU_HOST_GRAPHVIZ_ARENA_INITIAL bounds the first);
+    at the largest arena (KGPU_HOST_GRAPHVIZ_ARENA_MAX) the chunk is halved until the sentence that alone does not fit is left with
+    KGPU_SENT_NO_SCRATCH and no bytes, its neighbours' documents being what they always are."""
+    from kanpyo_amd import _lib
+
+    g, d, tok, known, unk = fixture_tok
+    long_ = g["input"] * 20   # 300 bytes: slab A alone is 68 bytes per input byte
+    sents = [g["input"]] + FIXTURE_INPUTS + [long_] + FIXTURE_INPUTS[::-1]
+    for full_state in (False, True):
+        want, status = _docs(tok, sents, 48, full_state)
+        assert not status.any() and want[7] == _want_pyref(_pydict(d), known, unk, long_, 48, full_state)
+        monkeypatch.setenv("KGPU_HOST_GRAPHVIZ_ARENA_INITIAL", "2048")
+        tok.routing(reset=True)
+        docs, status = _docs(tok, sents, 48, full_state)   # regrows until everything fits
+        assert docs == want and not status.any() and tok.routing()["arena_regrows"] >= 3
+        monkeypatch.setenv("KGPU_HOST_GRAPHVIZ_ARENA_MAX", "8192")
+        docs, status = _docs(tok, sents, 48, full_state)
+        assert status.tolist() == [0] * 7 + [_lib.KGPU_SENT_NO_SCRATCH] + [0] * 6
+        assert docs[7] == b"" and docs[:7] == want[:7] and docs[8:] == want[8:]
+        monkeypatch.delenv("KGPU_HOST_GRAPHVIZ_ARENA_INITIAL")
+        monkeypatch.delenv("KGPU_HOST_GRAPHVIZ_ARENA_MAX")
+    assert _docs(tok, sents)[0] == _docs(tok, sents, 48, False)[0]
+
+
+def _write_dict_dir(d, known, unk, tmp_path):
+    from kanpyo_amd.dictfile import _unk_prefix_len
+
+    out = tmp_path / "blobs"
+    out.mkdir()
+    (out / "index.dict").write_bytes(d.index_dict)
+    (out / "connection.dict").write_bytes(d.connection_dict)
+    (out / "morph.dict").write_bytes(d.morph_dict)
+    (out / "unk.dict").write_bytes(d.unk_dict[: _unk_prefix_len(d.unk_dict)] + unk.encode())
+    np.asarray(d.char_category, dtype=np.uint8).tofile(out / "char_category.bin")
+    np.asarray(d.invoke_list, dtype=np.uint8).tofile(out / "invoke.bin")
+    np.asarray(d.group_list, dtype=np.uint8).tofile(out / "group.bin")
+    (out / "morph_feature.dict").write_bytes(known.encode())
+    (out / "unk_feature.dict").write_bytes(unk.encode())
+    return out
+
+
+def test_c_consumer_prints_the_golden_document(fixture_tok, tmp_path):
+    from kanpyo_amd import _lib
+
+    g, d, tok, known, unk = fixture_tok
+    exe = str(tmp_path / "graphviz_consumer")
+    libdir = os.path.dirname(_lib.LIB_PATH)
+    subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"),
+                    os.path.join(ROOT, "tests", "c_abi", "graphviz_consumer.c"), "-o", exe, "-L", libdir, "-lkanpyo_gpu", f"-Wl,-rpath,{libdir}"], check=True)
+    blobs = _write_dict_dir(d, known, unk, tmp_path)
+    r = subprocess.run([exe, str(blobs), g["input"]], capture_output=True, timeout=300)
+    assert r.returncode == 0, r.stderr.decode()
+    assert r.stdout == g["dot"].encode()
+    r = subprocess.run([exe, str(blobs), g["input"], "96", "1"], capture_output=True, timeout=300)
+    assert r.returncode == 0, r.stderr.decode()
+    assert r.stdout == _want_pyref(_pydict(d), known, unk, g["input"], 96, True)
+
+
+def test_cli_stdout_is_the_reference_output(fixture_tok, tmp_path):
+    from kanpyo_amd.dictfile import DictFile, save_dict
+
+    g, d, tok, known, unk = fixture_tok
+    pd = _pydict(d)
+    path = tmp_path / "t.dict"
+    save_dict(DictFile(d, known, unk), str(path))
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    cmd = [sys.executable, "-m", "kanpyo_amd", "graphviz", "-c", str(path)]
+
+    def run(extra, data=None):
+        return subprocess.run(cmd + extra, input=data if data is not None else b"", capture_output=True, env=env, cwd=ROOT, timeout=600)
+
+    r = run([g["input"]])   # INPUT: that string
+    assert r.returncode == 0, r.stderr.decode()
+    assert r.stdout == g["dot"].encode()
+    r = run(["辞書あ "])    # ... untrimmed
+    assert r.returncode == 0 and r.stdout == _want_pyref(pd, known, unk, "辞書あ ", 48, False)
+    r = run([], (g["input"] + " 　\r\nテスト\n").encode())   # stdin: two lines in, only the first drawn, trimmed
+    assert r.returncode == 0, r.stderr.decode()
+    assert r.stdout == g["dot"].encode()
+    r = run([], b"")        # empty stdin: the empty sentence
+    assert r.returncode == 0 and r.stdout == _want_pyref(pd, known, unk, "", 48, False)
+    r = run(["-f", "--dpi", "96"], "辞書あ辞書\n".encode())
+    assert r.returncode == 0 and r.stdout == _want_pyref(pd, known, unk, "辞書あ辞書", 96, True)
+    r = run(["--full-state", "辞書あ辞書"])
+    assert r.returncode == 0 and r.stdout == _want_pyref(pd, known, unk, "辞書あ辞書", 48, True)
+    r = run([], b"\xff\xfe\n" + g["input"].encode() + b"\n")   # a first line that is not UTF-8: the reference's `expect` panics
+    assert r.returncode == 101 and r.stdout == b""
