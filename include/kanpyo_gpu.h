@@ -415,6 +415,65 @@ int kgpu_graphviz_batch(kgpu_dict *d, const uint8_t *utf8, const uint64_t *offse
                         uint8_t *text, uint64_t text_capacity, uint64_t *text_offsets /* n + 1 */,
                         uint8_t *status /* may be NULL */, uint64_t *n_bytes);
 
+/* ---- wakati-gaki: the words of each sentence on one line (NOT an output of the reference: what `mecab -Owakati` prints) ----
+ * A words handle fixes a field, a filter and a separator for one dictionary, which must have its feature tables
+ * (kgpu_dict_set_features).  Rendering a batch gives, for EVERY sentence, exactly one line: the words of its kept tokens joined by the
+ * separator byte, then '\n'.  Line i of the output is sentence i of the input, always.
+ *  1. EOS.  The EOS token (class dummy) is never a word: the line's '\n' stands for it.  A dummy record with any id, position or length
+ *     (crafted records) is skipped the same way.
+ *  2. Field.  KGPU_WORDS_SURFACE (-1): the word is the surface input[position .. position + byte_len).  k >= 0: the word is feature k of
+ *     the token's row -- morph_features[id - 1] of the known or unknown table through name_list, the rows kgpu_tokenize_batch_lines joins
+ *     (reference src/bin/kanpyo.rs:174-197).  The word FALLS BACK TO THE SURFACE when the token has no row (id 0), when the row has k
+ *     features or fewer, and when feature k is the empty string or exactly "*".  IPADIC's layout, for orientation only: 0-3 part of
+ *     speech, 4-5 conjugation, 6 base form, 7 reading, 8 pronunciation; unknown-word rows have 7 columns with "*" at 6.
+ *  3. Filter.  `names` is a list of strings compared bytewise with feature 0 of the token's row.  KGPU_WORDS_ALL: every non-EOS token is
+ *     kept, the list is ignored.  KGPU_WORDS_DROP: tokens whose feature 0 is in the list are dropped.  KGPU_WORDS_KEEP: only tokens whose
+ *     feature 0 is in the list are kept.  A token without a row, or with an empty row, has no feature 0 and matches no name: DROP keeps
+ *     it, KEEP drops it.  A name no row carries is not an error.  An empty list is legal: DROP with it keeps all, KEEP with it makes
+ *     every line empty.
+ *  4. Separator.  One byte, default ' '; '\n' is rejected.  Nothing is escaped.  An empty word is an empty word (crafted zero-length
+ *     surfaces only): two separators then meet.  A token whose surface is itself a space (IPADIC's 記号,空白) is printed as it is: drop
+ *     記号 if that matters.
+ *  5. Sentences with no words -- no kept token, no tokens at all (EOS unreachable), KGPU_SENT_INVALID_UTF8 -- render to the single
+ *     byte '\n'; the status byte is what the tokenize call reports.
+ *  6. Records are range-checked as the lines render checks them (class, id within its table, surface inside the sentence): a bad record
+ *     anywhere makes the sync return KGPU_ERR_INVALID_ARG. */
+#define KGPU_WORDS_SURFACE (-1)
+#define KGPU_WORDS_ALL 0
+#define KGPU_WORDS_DROP 1
+#define KGPU_WORDS_KEEP 2
+typedef struct kgpu_words_spec {
+    uint32_t size;                 /* sizeof(kgpu_words_spec): fields may be appended later */
+    int32_t field;
+    uint32_t filter;               /* KGPU_WORDS_ALL / DROP / KEEP */
+    uint32_t separator;            /* one byte value, 0 = the default ' ' */
+    const uint8_t *names;          /* n_names strings, concatenated ... */
+    const uint64_t *name_offsets;  /* ... n_names + 1 entries */
+    uint64_t n_names;
+} kgpu_words_spec;
+typedef struct kgpu_words kgpu_words;
+/* KGPU_ERR_INVALID_ARG: a null pointer, a `size` smaller than the struct, a field below -1, an unknown filter, a separator above 255 or
+ * equal to '\n', names without offsets (n_names != 0 with name_offsets NULL, or name bytes with names NULL), offsets that run backwards,
+ * a dictionary without feature tables.  The handle is immutable once created: any number of threads may use it at once.  It keeps the
+ * dictionary's tables alive, as a context does (it may outlive kgpu_dict_destroy).  It owns one 8-byte entry per known and unknown morph
+ * and a pool of the distinct names the field selects, uploaded once (about 3 MB of entries for IPADIC) and freed by kgpu_words_destroy.
+ * Host memory: kgpu_dict_set_features keeps a copy of its two blobs in the dictionary handle for this call to parse (their size, ~15 MB
+ * for IPADIC, until the dictionary is released). */
+int kgpu_words_create(kgpu_dict *d, const kgpu_words_spec *spec, kgpu_words **out);
+void kgpu_words_destroy(kgpu_words *w);
+/* kgpu_tokenize_batch_lines with the words render: text_offsets[i] .. text_offsets[i + 1] is sentence i's line (never empty: it ends with
+ * '\n').  The same argument checks, the same KGPU_ERR_CAPACITY with the exact size in *n_bytes, the same status bytes. */
+int kgpu_tokenize_batch_words(kgpu_words *w, const uint8_t *utf8, const uint64_t *offsets, uint64_t n,
+                              uint8_t *text, uint64_t text_capacity, uint64_t *text_offsets, uint8_t *status, uint64_t *n_bytes);
+/* kgpu_tokenize_text_lines with the words render: a raw block of input, split and trimmed on the device, one output line per input line. */
+int kgpu_tokenize_text_words(kgpu_words *w, const uint8_t *text, uint64_t len, uint8_t *out_text, uint64_t text_capacity,
+                             uint64_t *text_offsets, uint64_t offsets_capacity, uint8_t *status, uint64_t *n_lines, uint64_t *n_bytes);
+/* kgpu_format_lines_device with the words render, enqueued on c's stream and waited for with kgpu_ctx_sync_lines (one render pending per
+ * context, whichever kind).  A context whose dictionary is not the handle's: KGPU_ERR_INVALID_ARG. */
+int kgpu_format_words_device(kgpu_ctx *c, const kgpu_words *w, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n,
+                             const kgpu_token *d_tokens, const uint64_t *d_tok_offsets,
+                             uint8_t *d_text, uint64_t text_capacity, uint64_t *d_text_offsets);
+
 #ifdef __cplusplus
 }
 #endif

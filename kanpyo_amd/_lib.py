@@ -29,7 +29,10 @@ SYMBOLS = [
     "kgpu_dict_get_routing", "kgpu_tokenize_batch_multi", "kgpu_tokenize_batch_multi_compact", "kgpu_multi_create", "kgpu_multi_destroy", "kgpu_multi_tokenize_device", "kgpu_multi_sync",
     "kgpu_dict_set_features", "kgpu_tokenize_batch_lines", "kgpu_format_lines_device", "kgpu_ctx_sync_lines", "kgpu_split_lines",
     "kgpu_split_lines_device", "kgpu_ctx_sync_split", "kgpu_tokenize_text_lines", "kgpu_graphviz_batch",
+    "kgpu_words_create", "kgpu_words_destroy", "kgpu_tokenize_batch_words", "kgpu_tokenize_text_words", "kgpu_format_words_device",
 ]
+KGPU_WORDS_SURFACE = -1
+KGPU_WORDS_ALL, KGPU_WORDS_DROP, KGPU_WORDS_KEEP = 0, 1, 2
 
 
 def kernel_source_hash() -> str:
@@ -104,6 +107,11 @@ class Token8(C.Structure):  # kgpu_token8
     _fields_ = [("id", C.c_int32), ("packed", C.c_uint32)]
 
 
+class WordsSpec(C.Structure):  # kgpu_words_spec
+    _fields_ = [("size", C.c_uint32), ("field", C.c_int32), ("filter", C.c_uint32), ("separator", C.c_uint32),
+                ("names", C.c_void_p), ("name_offsets", C.c_void_p), ("n_names", C.c_uint64)]
+
+
 class Work(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("sentences", "B", "C", "T", "N", "E", "K")]
 
@@ -172,6 +180,14 @@ def lib():
         L.kgpu_ctx_sync_split.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.kgpu_tokenize_text_lines.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.kgpu_graphviz_batch.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_int, vp, C.c_uint64, vp, vp, C.POINTER(C.c_uint64)]
+        L.kgpu_words_create.argtypes = [vp, C.POINTER(WordsSpec), C.POINTER(vp)]
+        L.kgpu_words_destroy.argtypes = [vp]
+        L.kgpu_words_destroy.restype = None
+        L.kgpu_tokenize_batch_words.argtypes = L.kgpu_tokenize_batch_lines.argtypes
+        L.kgpu_tokenize_text_words.argtypes = L.kgpu_tokenize_text_lines.argtypes
+        L.kgpu_format_words_device.argtypes = [vp] + L.kgpu_format_lines_device.argtypes
+        L.kgpu_debug_word_table.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_uint64, C.c_uint64, C.POINTER(WordsSpec), vp, vp, C.c_uint64,
+                                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
         L.kgpu_debug_feature_pool.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_uint64, C.c_uint64, vp, C.c_uint64, vp, C.POINTER(C.c_uint64)]
         L.kgpu_debug_label_pool.argtypes = L.kgpu_debug_feature_pool.argtypes
         _lib = L

@@ -11,6 +11,14 @@ run as the reference's `expect` panic does: the lines before it are printed, exi
 127-148 over src/graphviz.rs:30-163): the lattice of ONE sentence as a DOT document, built and rendered on the device in one
 kgpu_graphviz_batch call.  With INPUT that string is drawn untrimmed; without it ONE line of stdin is read and trimmed (read_line +
 trim_end, not a loop: further lines are ignored, empty stdin is the empty sentence).  A first line that is not UTF-8 ends with status 101.
+
+`python -m kanpyo_amd wakati [INPUT] [-c DICT] [--field N | --base-form | --reading | --pronunciation] [--drop POS[,POS...] | --keep POS[,POS...]]
+[--separator S] [--split host|device]`: NOT a subcommand of the reference -- wakati-gaki, what `mecab -Owakati` prints: every input line
+becomes one output line, its words separated by S (one byte, default a space), rendered on the device (kgpu_tokenize_batch_words /
+kgpu_tokenize_text_words).  --field N prints feature N of each token's row instead of the surface (--base-form, --reading, --pronunciation:
+6, 7, 8, IPADIC's columns; the surface where a row has no such feature, or it is empty or "*"); --drop / --keep filter tokens by feature 0,
+the part of speech.  stdin is handled as `tokenize` handles it: blocks of whole lines, and a line that is not UTF-8 ends the run with status
+101 after the lines before it.
 """
 from __future__ import annotations
 
@@ -90,6 +98,51 @@ def tokenize(args, stdin, stdout) -> int:
     return 0
 
 
+def wakati(args, stdin, stdout) -> int:
+    from . import dictfile
+    from .tokenizer import Tokenizer, split_lines
+
+    df = dictfile.load_dict(args.custom_dict or default_dict_path())
+    tok = Tokenizer(df.dict)
+    tok.set_features(df.morph_feature_table, df.unk_feature_table)
+    w = tok.words(field=args.field, drop=args.drop, keep=args.keep, separator=os.fsencode(args.separator))
+    if args.input is not None:   # that one string, untrimmed
+        one = np.frombuffer(os.fsencode(args.input), dtype=np.uint8)
+        results = iter([w.render_packed(one, np.array([0, one.size], dtype=np.uint64))])
+    elif args.split == "device":
+        results = (w.render_text(b) for b in _blocks(stdin, args.block_bytes))
+    else:
+        results = (w.render_packed(*split_lines(b)) for b in _blocks(stdin, args.block_bytes))
+    for text, toff, status in results:
+        bad = np.flatnonzero(status == 1)
+        if bad.size:
+            stdout.write(text[: int(toff[bad[0]])].tobytes())
+            stdout.flush()
+            print("kanpyo_amd: failed to read from stdin: stream did not contain valid UTF-8", file=sys.stderr)
+            return PANIC_STATUS
+        stdout.write(text.tobytes())
+        stdout.flush()
+    return 0
+
+
+def _pos_list(text: str):
+    """--drop / --keep: part-of-speech names separated by commas."""
+    return [p for p in text.split(",") if p]
+
+
+def _separator(text: str) -> str:
+    b = text.encode("utf-8", "surrogateescape")
+    if len(b) != 1 or b == b"\n":
+        raise argparse.ArgumentTypeError(f"invalid separator {text!r}: one byte, not a newline")
+    return text
+
+
+def _field(text: str) -> int:
+    if not text.isascii() or not text.isdigit():
+        raise argparse.ArgumentTypeError(f"invalid field {text!r}: a feature index from 0")
+    return int(text)
+
+
 # what Rust's str::trim_end strips: the Unicode White_Space code points (char::is_whitespace)
 WHITE_SPACE = "\t\n\x0b\x0c\r \x85\xa0\u1680\u2000\u2001\u2002\u2003\u2004\u2005\u2006\u2007\u2008\u2009\u200a\u2028\u2029\u202f\u205f\u3000"
 
@@ -137,7 +190,7 @@ def _dpi(text: str) -> int:
 
 
 def parse_args(argv=None):
-    """The reference's command line (src/bin/kanpyo.rs:14-49).  -> the namespace; .command is "tokenize" or "graphviz"."""
+    """The reference's command line (src/bin/kanpyo.rs:14-49).  -> the namespace; .command is "tokenize" or "graphviz" -- or "wakati", which is this package's own."""
     p = argparse.ArgumentParser(prog="kanpyo_amd", description="Japanese Morphological Analyzer (kanpyo) on AMD Instinct GPUs")
     sub = p.add_subparsers(dest="command")
     t = sub.add_parser("tokenize", help="Tokenize input text")
@@ -153,6 +206,22 @@ def parse_args(argv=None):
     g.add_argument("-c", "--custom-dict", default=None, help="Custom dictionary (.dict)")
     g.add_argument("-f", "--full-state", action="store_true", help="Output full state of lattice")
     g.add_argument("--dpi", type=_dpi, default=48, help="DPI of output image [default: 48]")
+    w = sub.add_parser("wakati", help="One line of separated words per input line (not in the reference)")
+    w.add_argument("input", nargs="?", default=None, help="Input text to analyze [default: stdin]")
+    w.add_argument("-d", "--dict", choices=["ipa"], default="ipa", help="Dictionary")
+    w.add_argument("-c", "--custom-dict", default=None, help="Custom dictionary (.dict)")
+    fld = w.add_mutually_exclusive_group()
+    fld.add_argument("--field", type=_field, default=None, help="Print feature N of the token's row instead of the surface")
+    fld.add_argument("--base-form", dest="field", action="store_const", const=6, help="--field 6 (IPADIC)")
+    fld.add_argument("--reading", dest="field", action="store_const", const=7, help="--field 7 (IPADIC)")
+    fld.add_argument("--pronunciation", dest="field", action="store_const", const=8, help="--field 8 (IPADIC)")
+    flt = w.add_mutually_exclusive_group()
+    flt.add_argument("--drop", type=_pos_list, default=[], help="Drop tokens whose part of speech (feature 0) is one of POS[,POS...]")
+    flt.add_argument("--keep", type=_pos_list, default=[], help="Keep only tokens whose part of speech is one of POS[,POS...]")
+    w.add_argument("--separator", type=_separator, default=" ", help="The byte between words [default: a space]")
+    w.add_argument("--split", choices=["host", "device"], default="host",
+                   help="Where stdin's blocks are split into lines and trimmed [default: host]")
+    w.add_argument("--block-bytes", type=int, default=BLOCK_BYTES, help=argparse.SUPPRESS)
     args = p.parse_args(argv)
     if args.command is None:   # src/bin/kanpyo.rs:173: no subcommand == tokenize from stdin, default dictionary
         args = t.parse_args([])
@@ -167,6 +236,8 @@ def main(argv=None) -> int:
     try:
         if args.command == "graphviz":
             return graphviz(args, sys.stdin.buffer, sys.stdout.buffer)
+        if args.command == "wakati":
+            return wakati(args, sys.stdin.buffer, sys.stdout.buffer)
         return tokenize(args, sys.stdin.buffer, sys.stdout.buffer)
     except _lib.KgpuError as e:
         print(f"kanpyo_amd: {e}", file=sys.stderr)

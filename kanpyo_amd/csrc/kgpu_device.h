@@ -1,6 +1,7 @@
 // kanpyo_amd/csrc/kgpu_device.h -- device-side code shared by the tokenize kernels (LDS-resident: kgpu_pool.hip, windowed: kgpu_window.hip,
 // general: kgpu_kernels.hip): the trie walks, UTF-8 decoding, and -- once, for both LDS kernels -- the Viterbi sweep step, its DPP minima and the
-// connection-cost gather.
+// connection-cost gather; and by the two renderers (kgpu_format.hip, kgpu_words.hip): the wavefront sums and the 64-bit inclusive scan
+// (wave_sum64, wave_incl_scan64, lane63, wave_sync).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -43,6 +44,18 @@ __device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {  // every lane gets
         v += ((uint64_t)hi << 32) | lo;
     }
     return v;
+}
+// (the two renderers, kgpu_format.hip and kgpu_words.hip) inclusive scan of a 64-bit value over the wavefront; the value lane 63 holds, for every lane
+__device__ __forceinline__ uint64_t wave_incl_scan64(uint64_t v, uint32_t lane) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)v, d, 64), hi = (uint32_t)__shfl_up((int)(uint32_t)(v >> 32), d, 64);
+        if (lane >= (uint32_t)d) v += ((uint64_t)hi << 32) | lo;
+    }
+    return v;
+}
+__device__ __forceinline__ uint64_t lane63(uint64_t v) {
+    return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), 63) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 63);
 }
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {  // every lane gets the total
     return (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(v, 0), 63);

@@ -443,6 +443,7 @@ extern "C" void kgpu_dict_destroy(kgpu_dict *d) {
         pooled.swap(d->pool);
     }
     for (auto *c : pooled) kgpu_ctx_destroy(c);
+    d->closed.store(true, std::memory_order_release);
     dict_release(d);
 }
 

@@ -3,11 +3,15 @@
 // Owns: the bincode 2 (standard config) parser of MorphFeatureTable (kanpyo-dict/src/morph_feature.rs:6-37) with the validation that turns
 // the reference's print-time panics into KGPU_ERR_BAD_DICT, the pre-joined feature pool and its upload (kgpu_dict_set_features), the
 // label pool of the graphviz node lines (src/graphviz.rs:56-89) and its upload on the first graphviz call (ensure_label_pool), the
-// host-only test hooks over them (kgpu_debug_feature_pool, kgpu_debug_label_pool), and the CLI's line splitting (kgpu_split_lines:
-// read_line + trim_end).
+// host-only test hooks over them (kgpu_debug_feature_pool, kgpu_debug_label_pool), the per-row word table of a words handle
+// (build_word_table: field, fallback to the surface and filter decided per row; kgpu_words_host.cpp uploads it), and the CLI's line
+// splitting (kgpu_split_lines: read_line + trim_end).
 #include <algorithm>
 #include <cstring>
 #include <mutex>
+#include <string>
+#include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include "kgpu_runtime.h"
@@ -163,7 +167,60 @@ int build_pool(const uint8_t *known, size_t known_len, const uint8_t *unk, size_
     return KGPU_OK;
 }
 
+// One table's first `need` rows -> their word entries, appended to `rows`; the names they select go into `pool` once each (`seen`).
+int word_rows(const Table &t, uint64_t need, const char *what, const kgpu_words_spec &spec, const std::unordered_set<std::string> &listed,
+              std::unordered_map<std::string, uint32_t> &seen, std::vector<WordRow> &rows, std::vector<uint8_t> &pool) {
+    const uint64_t n_rows = t.row.size() - 1, names = t.name.size() - 1;
+    if (n_rows < need) {
+        kgpu::set_error("%s: %llu feature rows for %llu morphs", what, (unsigned long long)n_rows, (unsigned long long)need);
+        return KGPU_ERR_BAD_DICT;
+    }
+    const auto name_of = [&](uint32_t id) { return std::string(t.bytes.begin() + (ptrdiff_t)t.name[id], t.bytes.begin() + (ptrdiff_t)t.name[id + 1]); };
+    for (uint64_t r = 0; r < need; ++r) {
+        const uint64_t j0 = t.row[r], k = t.row[r + 1] - j0;
+        for (uint64_t j = j0; j < j0 + k; ++j)
+            if (t.ids[j] >= names) { kgpu::set_error("%s: feature id %u, name_list has %llu names", what, t.ids[j], (unsigned long long)names); return KGPU_ERR_BAD_DICT; }
+        WordRow e{0, WORD_SURFACE};
+        // the filter: feature 0 against the list; a row without features matches no name
+        const bool match = spec.filter != KGPU_WORDS_ALL && k > 0 && listed.count(name_of(t.ids[j0])) != 0;
+        if ((spec.filter == KGPU_WORDS_DROP && match) || (spec.filter == KGPU_WORDS_KEEP && !match)) e.len_flags |= WORD_DROPPED;
+        // the word: feature `field`, unless the row is too short for it or it is "" or "*" (then the surface)
+        if (spec.field >= 0 && (uint64_t)spec.field < k) {
+            const std::string nm = name_of(t.ids[j0 + (uint64_t)spec.field]);
+            if (!nm.empty() && nm != "*") {
+                if (nm.size() > WORD_LEN_MASK) { kgpu::set_error("%s: a name of %zu bytes", what, nm.size()); return KGPU_ERR_BAD_DICT; }
+                auto it = seen.find(nm);
+                if (it == seen.end()) {
+                    if (pool.size() + nm.size() >= (1ull << 32)) { kgpu::set_error("%s: the distinct names of field %d reach 4 GiB", what, spec.field); return KGPU_ERR_BAD_DICT; }
+                    it = seen.emplace(nm, (uint32_t)pool.size()).first;
+                    pool.insert(pool.end(), nm.begin(), nm.end());
+                }
+                e.off = it->second;
+                e.len_flags = (e.len_flags & WORD_DROPPED) | (uint32_t)nm.size();
+            }
+        }
+        rows.push_back(e);
+    }
+    return KGPU_OK;
+}
+
 }  // namespace
+
+int kgpu::build_word_table(const uint8_t *known, size_t known_len, const uint8_t *unk, size_t unk_len, uint64_t n_morphs, uint64_t n_unk,
+                           const kgpu_words_spec &spec, std::vector<WordRow> &rows, std::vector<uint8_t> &names) {
+    Table tk, tu;
+    int rc;
+    if ((rc = parse_table(known, known_len, tk, "morph_feature.dict")) || (rc = parse_table(unk, unk_len, tu, "unk.dict feature table"))) return rc;
+    std::unordered_set<std::string> listed;
+    for (uint64_t i = 0; i < spec.n_names; ++i) listed.emplace((const char *)spec.names + spec.name_offsets[i], (size_t)(spec.name_offsets[i + 1] - spec.name_offsets[i]));
+    std::unordered_map<std::string, uint32_t> seen;
+    rows.clear(); names.clear();
+    rows.reserve((size_t)(n_morphs + n_unk));
+    if ((rc = word_rows(tk, n_morphs, "morph_feature.dict", spec, listed, seen, rows, names)) ||
+        (rc = word_rows(tu, n_unk, "unk.dict feature table", spec, listed, seen, rows, names)))
+        return rc;
+    return KGPU_OK;
+}
 
 extern "C" int kgpu_dict_set_features(kgpu_dict *d, const uint8_t *morph_feature_dict, size_t morph_feature_len,
                                       const uint8_t *unk_feature_dict, size_t unk_feature_len) {
@@ -193,6 +250,8 @@ extern "C" int kgpu_dict_set_features(kgpu_dict *d, const uint8_t *morph_feature
     d->feat_off = (const uint32_t *)doff;
     d->label_host.swap(lpool);   // stays on the host until a lattice is drawn (ensure_label_pool)
     d->label_off_host.swap(loff);
+    d->feat_blob_known.assign(morph_feature_dict, morph_feature_dict + morph_feature_len);   // what a later kgpu_words_create parses
+    d->feat_blob_unk.assign(unk_feature_dict, unk_feature_dict + unk_feature_len);
     return KGPU_OK;
 }
 

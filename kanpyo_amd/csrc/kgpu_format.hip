@@ -26,18 +26,6 @@ namespace {
 constexpr uint32_t EOS_POS = 0xFFFFFFFFu;   // LDS marker: the surface is the literal "EOS"
 constexpr uint32_t WPB = 4;                 // wavefronts per workgroup (one sentence each at a time)
 
-__device__ __forceinline__ uint64_t wave_incl_scan64(uint64_t v, uint32_t lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)v, d, 64), hi = (uint32_t)__shfl_up((int)(uint32_t)(v >> 32), d, 64);
-        if (lane >= (uint32_t)d) v += ((uint64_t)hi << 32) | lo;
-    }
-    return v;
-}
-__device__ __forceinline__ uint64_t lane63(uint64_t v) {
-    return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), 63) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 63);
-}
-
 // One token's line: surface (sl bytes at byte `pos` of the sentence, or "EOS"), then '\t', the joined features (fl bytes at feat[fo]), '\n'.
 // ok = false: the record is not one the tokenizer could have written for this sentence and dictionary (class, id or surface out of range).
 struct Line { uint32_t sl, pos, fo, fl; bool ok; };
@@ -177,11 +165,15 @@ __global__ __launch_bounds__(256) void k_lines_write(LinesArgs a) {
     }
 }
 
+void launch_lines_scan(const LinesArgs &a, void *stream) {
+    hipLaunchKernelGGL(k_lines_scan, dim3(1), dim3(a.n > 256 ? 1024 : 256), 0, (hipStream_t)stream, a);
+}
+
 int launch_format_lines(const LinesArgs &a, void *stream) {
     const hipStream_t st = (hipStream_t)stream;
     const uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>((a.n + WPB - 1) / WPB, 8192));
     hipLaunchKernelGGL(k_lines_len, dim3((unsigned)blocks), dim3(64 * WPB), 0, st, a);
-    hipLaunchKernelGGL(k_lines_scan, dim3(1), dim3(a.n > 256 ? 1024 : 256), 0, st, a);
+    launch_lines_scan(a, stream);
     hipLaunchKernelGGL(k_lines_write, dim3((unsigned)blocks), dim3(64 * WPB), 0, st, a);
     return (int)hipGetLastError();
 }

@@ -4,7 +4,7 @@
 // host batch, a chunk's input block (ChunkInput) and mapped result block (ChunkBlock, shared with kgpu_multi.cpp), the output side of a
 // lines chunk (LinesChunk, shared with kgpu_split_host.cpp), the chunk sizes of the pipeline (the ring itself is run_pipeline,
 // kgpu_runtime.h), the 24-byte per-chunk fallback for tokens beyond the 8-byte record (HostJob), kgpu_tokenize_batch,
-// kgpu_tokenize_batch_lines, and kgpu_host_alloc / kgpu_host_free.
+// kgpu_tokenize_batch_lines and kgpu_tokenize_batch_words (one body: batch_lines), and kgpu_host_alloc / kgpu_host_free.
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
@@ -174,9 +174,11 @@ MergeSrc ChunkBlock::results(const kgpu_ctx *c) const {
 int LinesChunk::prepare(kgpu_ctx *c, uint64_t n_, uint64_t total_) {
     n = n_; total = total_;
     int rc;   // (the text block starts at 16 bytes per input byte -- cfg 2 renders about 14 -- and grows when a chunk's text outgrows it: finish)
+    // (words: a surface line is at most the input's bytes and a byte per token, and a byte for the sentence; a field's names may be longer: finish grows)
+    const size_t text_guess = words ? (size_t)total * 2 + (size_t)n + 4096 : (size_t)total * 16 + 4096;
     if ((rc = c->out_tok.ensure((size_t)token_bound(total, n) * sizeof(kgpu_token) + 64)) || (rc = c->out_status.ensure((size_t)n + 16)) ||
         (rc = c->out_off.ensure((size_t)(n + 1) * 8)) || (rc = c->lines_off.ensure((size_t)(n + 1) * 8, true)) ||
-        (rc = c->lines_status.ensure((size_t)n + 16, true)) || (rc = c->lines_text.ensure((size_t)total * 16 + 4096, true)))
+        (rc = c->lines_status.ensure((size_t)n + 16, true)) || (rc = c->lines_text.ensure(text_guess, true)))
         return rc;
     return KGPU_OK;
 }
@@ -187,8 +189,11 @@ int LinesChunk::launch(kgpu_ctx *c, const uint8_t *d_utf8_, const uint64_t *d_of
                                         (uint64_t *)c->out_off.p, (uint8_t *)c->out_status.p, who);
     return rc ? rc : render(c, who);
 }
-// The chunk's lines into the context's mapped blocks: text, chunk-relative text offsets, status.
+// The chunk's lines into the context's mapped blocks: text, chunk-relative text offsets, status.  The one place that chooses the renderer.
 int LinesChunk::render(kgpu_ctx *c, const char *who) const {
+    if (words)
+        return enqueue_words(c, words, d_utf8, d_offsets, n, (const kgpu_token *)c->out_tok.p, (const uint64_t *)c->out_off.p, (uint8_t *)c->lines_text.d, c->lines_text.bytes,
+                             (uint64_t *)c->lines_off.d, (const uint8_t *)c->out_status.p, (uint8_t *)c->lines_status.d, who);
     return enqueue_lines(c, d_utf8, d_offsets, n, (const kgpu_token *)c->out_tok.p, (const uint64_t *)c->out_off.p, (uint8_t *)c->lines_text.d, c->lines_text.bytes,
                          (uint64_t *)c->lines_off.d, (const uint8_t *)c->out_status.p, (uint8_t *)c->lines_status.d, who);
 }
@@ -386,9 +391,9 @@ struct LinesJob {
     LinesChunk out;
 };
 
-extern "C" int kgpu_tokenize_batch_lines(kgpu_dict *d, const uint8_t *utf8, const uint64_t *offsets, uint64_t n,
-                                         uint8_t *text, uint64_t text_capacity, uint64_t *text_offsets, uint8_t *status, uint64_t *n_bytes) {
-    const char *who = "kgpu_tokenize_batch_lines";
+// kgpu_tokenize_batch_lines (words null) and kgpu_tokenize_batch_words: the chunks differ in their renderer alone.
+static int batch_lines(kgpu_dict *d, const kgpu_words *words, const char *who, const uint8_t *utf8, const uint64_t *offsets, uint64_t n,
+                       uint8_t *text, uint64_t text_capacity, uint64_t *text_offsets, uint8_t *status, uint64_t *n_bytes) {
     if (!d || !offsets || !text_offsets || (text_capacity && !text)) { set_error("%s: null argument", who); return KGPU_ERR_INVALID_ARG; }
     int rc;
     if ((rc = check_host_batch(who, offsets, n, utf8)) || (rc = require_features(d, who))) return rc;
@@ -402,6 +407,7 @@ extern "C" int kgpu_tokenize_batch_lines(kgpu_dict *d, const uint8_t *utf8, cons
             const uint64_t *off = offsets + j.lo;
             const uint64_t total = off[j.m] - off[0];
             int r;
+            j.out.words = words;
             if ((r = j.in.prepare(j.c, j.m, total, !pinned_in)) || (r = j.out.prepare(j.c, j.m, total)) || (r = upload_input(j.c, j.in, utf8, off, pinned_in))) return r;
             return j.out.launch(j.c, j.in.d_text(j.c, off[0]), j.in.d_offsets(j.c), who);
         },
@@ -412,6 +418,17 @@ extern "C" int kgpu_tokenize_batch_lines(kgpu_dict *d, const uint8_t *utf8, cons
         return KGPU_ERR_CAPACITY;
     }
     return rc;
+}
+
+extern "C" int kgpu_tokenize_batch_lines(kgpu_dict *d, const uint8_t *utf8, const uint64_t *offsets, uint64_t n,
+                                         uint8_t *text, uint64_t text_capacity, uint64_t *text_offsets, uint8_t *status, uint64_t *n_bytes) {
+    return batch_lines(d, nullptr, "kgpu_tokenize_batch_lines", utf8, offsets, n, text, text_capacity, text_offsets, status, n_bytes);
+}
+
+extern "C" int kgpu_tokenize_batch_words(kgpu_words *w, const uint8_t *utf8, const uint64_t *offsets, uint64_t n,
+                                         uint8_t *text, uint64_t text_capacity, uint64_t *text_offsets, uint8_t *status, uint64_t *n_bytes) {
+    if (!w) { set_error("kgpu_tokenize_batch_words: null argument"); return KGPU_ERR_INVALID_ARG; }
+    return batch_lines(w->dict, w, "kgpu_tokenize_batch_words", utf8, offsets, n, text, text_capacity, text_offsets, status, n_bytes);
 }
 
 // Pinned, device-visible host memory for the buffers of kgpu_tokenize_batch: the copies then run as DMA

@@ -155,6 +155,26 @@ struct LinesArgs {
     unsigned long long *host_ctl;  // device pointer of pinned, mapped words: [0] total bytes, [1] a record out of range
 };
 int launch_format_lines(const LinesArgs &a, void *stream);
+void launch_lines_scan(const LinesArgs &a, void *stream);   // k_lines_scan alone (n, sent_len, text_offsets, host_ctl): the words render's second launch
+// The wakati lines of a batch (kgpu_words.hip): per sentence the words of its kept tokens joined by `sep`, then '\n'.
+// One entry per feature row, in the records' index space (LinesArgs::feat_off): where the row's word lies and whether its tokens are kept.
+struct WordRow { uint32_t off, len_flags; };                 // names[off .. off + len); len_flags = len | WORD_SURFACE | WORD_DROPPED
+constexpr uint32_t WORD_SURFACE = 1u << 30, WORD_DROPPED = 1u << 31, WORD_LEN_MASK = WORD_SURFACE - 1;
+struct WordsArgs {
+    const uint8_t *utf8; const uint64_t *offsets; uint64_t n;           // as LinesArgs
+    const kgpu_token *tokens; const uint64_t *tok_offsets;
+    const WordRow *rows;           // n_rows entries: known id k at row k - 1, unknown id u at n_morph + u - 1
+    const uint8_t *names;          // the pool of distinct names the entries point into
+    uint32_t n_morph, n_rows;
+    uint32_t sep;                  // the separator byte
+    uint32_t drop_rowless;         // KGPU_WORDS_KEEP: a token without a row (id 0) is dropped
+    uint64_t *sent_len;            // as LinesArgs: n + 1, lengths then offsets
+    uint8_t *text; uint64_t text_cap;
+    uint64_t *text_offsets;
+    const uint8_t *status_in; uint8_t *status_out;
+    unsigned long long *host_ctl;  // [0] total bytes, [1] a record out of range
+};
+int launch_format_words(const WordsArgs &a, void *stream);
 // The DOT documents of a batch's kept lattices (kgpu_graphviz.hip; reference src/graphviz.rs:30-163).
 struct GraphvizArgs {
     const uint8_t *utf8;           // as BatchArgs::utf8 / offsets of the launch that kept the lattices

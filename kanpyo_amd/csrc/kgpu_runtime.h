@@ -107,9 +107,20 @@ struct kgpu_dict {
     std::vector<uint32_t> label_off_host;
     const uint8_t *label = nullptr;
     const uint32_t *label_off = nullptr;
+    // ... and a copy of the two blobs themselves, which kgpu_words_create parses again for its per-row word table (host memory: their size)
+    std::vector<uint8_t> feat_blob_known, feat_blob_unk;
     // One reference for the handle the caller holds plus one per live context: the tables and the shared
     // streams go when the last one does (a context outliving kgpu_dict_destroy keeps working).
     std::atomic<int> refs{1};
+    std::atomic<bool> closed{false};   // kgpu_dict_destroy has run: a words handle that outlives it empties the context pool when it goes
+};
+
+// A words handle (kgpu_words_host.cpp): a field, a filter and a separator for one dictionary, and the device tables made from them.  Immutable.
+struct kgpu_words {
+    kgpu_dict *dict = nullptr;          // holds a reference, as a context does
+    int32_t field = -1;
+    uint32_t filter = 0, sep = ' ';
+    void *d_rows = nullptr, *d_names = nullptr;   // WordRow per feature row; the pool of distinct names
 };
 
 struct kgpu_ctx {
@@ -252,6 +263,13 @@ int tokenize_device_impl(kgpu_ctx *c, const uint8_t *d_utf8, const uint64_t *d_o
 int enqueue_lines(kgpu_ctx *c, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n, const kgpu_token *d_tokens, const uint64_t *d_tok_offsets,
                   uint8_t *d_text, uint64_t text_capacity, uint64_t *d_text_offsets, const uint8_t *status_in, uint8_t *status_out, const char *who);
 
+// ... and of its wakati lines (kgpu_words_host.cpp over kgpu_words.hip); waited for by kgpu_ctx_sync_lines as well
+int enqueue_words(kgpu_ctx *c, const kgpu_words *w, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n, const kgpu_token *d_tokens, const uint64_t *d_tok_offsets,
+                  uint8_t *d_text, uint64_t text_capacity, uint64_t *d_text_offsets, const uint8_t *status_in, uint8_t *status_out, const char *who);
+// kgpu_features.cpp: the per-row entries (known rows, then unknown rows) and the pool of distinct names of a checked spec, from the two blobs
+int build_word_table(const uint8_t *known, size_t known_len, const uint8_t *unk, size_t unk_len, uint64_t n_morphs, uint64_t n_unk,
+                     const kgpu_words_spec &spec, std::vector<WordRow> &rows, std::vector<uint8_t> &names);
+
 int require_features(kgpu_dict *d, const char *who);   // KGPU_ERR_INVALID_ARG unless kgpu_dict_set_features has been called
 int ensure_label_pool(kgpu_dict *d);                   // kgpu_features.cpp: the graphviz label pool on the device (first call uploads it)
 
@@ -291,10 +309,11 @@ struct LinesSink {
     uint64_t text_done = 0;
     bool overflow = false;
 };
-// The output side of one chunk of a lines call (kgpu_tokenize_batch_lines, kgpu_tokenize_text_lines) on a pooled context, whatever put its input on the
+// The output side of one chunk of a lines or words call (kgpu_tokenize_batch_lines / _words, kgpu_tokenize_text_lines / _words) on a pooled context, whatever put its input on the
 // device: the 24-byte records stay in HBM (c->out_tok) and the render behind the chain writes the chunk's text, chunk-relative text offsets and status
 // into c's mapped lines_* blocks.
 struct LinesChunk {
+    const kgpu_words *words = nullptr;                     // the words calls: render chooses the wakati renderer; null: the `kanpyo tokenize` lines
     uint64_t n = 0, total = 0;                             // sentences, bytes
     const uint8_t *d_utf8 = nullptr;                       // the chunk's input in device memory (launch)
     const uint64_t *d_offsets = nullptr;

@@ -1,7 +1,7 @@
 // kanpyo_amd/csrc/kgpu_split_host.cpp -- read_line + trim_end on the device (kgpu_split.hip) behind the C ABI.
 //
-// Owns: kgpu_split_lines_device / kgpu_ctx_sync_split (a block resident in HBM, on a context's stream) and kgpu_tokenize_text_lines
-// (a raw block in host memory: one copy to the device, the split, then the lines go through the launch chain and the render in chunks
+// Owns: kgpu_split_lines_device / kgpu_ctx_sync_split (a block resident in HBM, on a context's stream) and kgpu_tokenize_text_lines /
+// kgpu_tokenize_text_words (one body, text_lines: a raw block in host memory: one copy to the device, the split, then the lines go through the launch chain and the render in chunks
 // on pooled contexts -- their inputs are pointers into the split's output, nothing of the text returns to the host in between; the
 // chunks are LinesChunk in run_pipeline, kgpu_runtime.h, as those of kgpu_tokenize_batch_lines).
 #include <vector>
@@ -58,10 +58,9 @@ struct TextJob {
     LinesChunk out;
 };
 
-static const char *WHO = "kgpu_tokenize_text_lines";
-
-extern "C" int kgpu_tokenize_text_lines(kgpu_dict *d, const uint8_t *text, uint64_t len, uint8_t *out_text, uint64_t text_capacity, uint64_t *text_offsets,
-                                        uint64_t offsets_capacity, uint8_t *status, uint64_t *n_lines, uint64_t *n_bytes) {
+// kgpu_tokenize_text_lines (words null) and kgpu_tokenize_text_words: the chunks differ in their renderer alone.
+static int text_lines(kgpu_dict *d, const kgpu_words *words, const char *WHO, const uint8_t *text, uint64_t len, uint8_t *out_text, uint64_t text_capacity,
+                      uint64_t *text_offsets, uint64_t offsets_capacity, uint8_t *status, uint64_t *n_lines, uint64_t *n_bytes) {
     if (!d || (len && !text) || (text_capacity && !out_text) || (offsets_capacity && !text_offsets) || !n_lines || !n_bytes) { set_error("%s: null argument", WHO); return KGPU_ERR_INVALID_ARG; }
     *n_lines = 0; *n_bytes = 0;
     if (len >= (1ull << 32)) { set_error("%s: block of 4 GiB or more; split it", WHO); return KGPU_ERR_INVALID_ARG; }
@@ -99,6 +98,7 @@ extern "C" int kgpu_tokenize_text_lines(kgpu_dict *d, const uint8_t *text, uint6
     if (!sink.overflow) text_offsets[0] = 0;
     rc = run_pipeline<TextJob>(d, off.data(), lines, DEPTH, 0, false, nullptr,
         [&](TextJob &j) {
+            j.out.words = words;
             const int r = j.out.prepare(j.c, j.m, off[j.lo + j.m] - off[j.lo]);
             return r ? r : j.out.launch(j.c, d_text, d_off + j.lo, WHO);
         },
@@ -111,4 +111,15 @@ extern "C" int kgpu_tokenize_text_lines(kgpu_dict *d, const uint8_t *text, uint6
         return give_back(KGPU_ERR_CAPACITY);
     }
     return give_back(KGPU_OK);
+}
+
+extern "C" int kgpu_tokenize_text_lines(kgpu_dict *d, const uint8_t *text, uint64_t len, uint8_t *out_text, uint64_t text_capacity, uint64_t *text_offsets,
+                                        uint64_t offsets_capacity, uint8_t *status, uint64_t *n_lines, uint64_t *n_bytes) {
+    return text_lines(d, nullptr, "kgpu_tokenize_text_lines", text, len, out_text, text_capacity, text_offsets, offsets_capacity, status, n_lines, n_bytes);
+}
+
+extern "C" int kgpu_tokenize_text_words(kgpu_words *w, const uint8_t *text, uint64_t len, uint8_t *out_text, uint64_t text_capacity, uint64_t *text_offsets,
+                                        uint64_t offsets_capacity, uint8_t *status, uint64_t *n_lines, uint64_t *n_bytes) {
+    if (!w) { set_error("kgpu_tokenize_text_words: null argument"); return KGPU_ERR_INVALID_ARG; }
+    return text_lines(w->dict, w, "kgpu_tokenize_text_words", text, len, out_text, text_capacity, text_offsets, offsets_capacity, status, n_lines, n_bytes);
 }

@@ -61,8 +61,15 @@ class DeviceContext:
             self._h, C.c_void_p(d_utf8), C.c_void_p(d_offsets), n, C.c_void_p(d_tokens), C.c_void_p(d_tok_offsets), C.c_void_p(d_text),
             text_capacity, C.c_void_p(d_text_offsets)))
 
+    def format_words(self, words, d_utf8: int, d_offsets: int, n: int, d_tokens: int, d_tok_offsets: int, d_text: int, text_capacity: int, d_text_offsets: int):
+        """kgpu_format_words_device: enqueue the wakati lines (one line per sentence: its kept words, separated) of records a synced batch left in
+        HBM, by a Words handle of this context's tokenizer (Tokenizer.words); sync_lines waits for it."""
+        _lib.check(_lib.lib().kgpu_format_words_device(
+            self._h, words.handle, C.c_void_p(d_utf8), C.c_void_p(d_offsets), n, C.c_void_p(d_tokens), C.c_void_p(d_tok_offsets), C.c_void_p(d_text),
+            text_capacity, C.c_void_p(d_text_offsets)))
+
     def sync_lines(self) -> int:
-        """Wait for the enqueued render; returns its byte count."""
+        """Wait for the enqueued render (lines or words); returns its byte count."""
         n = C.c_uint64(0)
         _lib.check(_lib.lib().kgpu_ctx_sync_lines(self._h, C.byref(n)))
         return int(n.value)

@@ -193,6 +193,13 @@ class Tokenizer:
         text, _, _ = self.tokenize_lines_packed(utf8, offs)
         return text.tobytes()
 
+    # ---- wakati-gaki: one line of words per sentence (not an output of the reference) ------
+    def words(self, field=None, drop=(), keep=(), separator=" ") -> "Words":
+        """kgpu_words_create: a Words handle of this dictionary (set_features first).  field: None = the surface, k >= 0 = feature k of the
+        token's row (the surface where the row has no such feature, or it is "" or "*"); drop / keep: part-of-speech names compared with
+        feature 0 (at most one of the two); separator: one byte, not a newline."""
+        return Words(self, field, drop, keep, separator)
+
     # ---- the lattice pictures (`kanpyo graphviz`, src/bin/kanpyo.rs:127-148 over src/graphviz.rs:30-163) ------
     def graphviz_packed(self, utf8: np.ndarray, offsets: np.ndarray, dpi: int = 48, full_state: bool = False):
         """kgpu_graphviz_batch -> (text[uint8], text_offsets[uint64 n+1], status[uint8 n]): sentence i's DOT document is
@@ -252,6 +259,108 @@ class Tokenizer:
     def tokenize(self, input: str) -> List[Token]:
         """Tokenizer::tokenize (src/tokenizer.rs:16-45): one sentence == a batch of one."""
         return self.tokenize_batch([input])[0]
+
+
+def words_spec(field=None, drop=(), keep=(), separator=" "):
+    """-> (_lib.WordsSpec, the arrays it points into) for Tokenizer.words' arguments (kgpu_words_spec, include/kanpyo_gpu.h)."""
+    if drop and keep:
+        raise ValueError("drop and keep exclude each other")
+    sep = separator.encode("utf-8") if isinstance(separator, str) else bytes(separator)
+    if len(sep) != 1:
+        raise ValueError("the separator is one byte")
+    listed = list(keep) if keep else list(drop)
+    filt = _lib.KGPU_WORDS_KEEP if keep else _lib.KGPU_WORDS_DROP if drop else _lib.KGPU_WORDS_ALL
+    names, offs = pack_sentences(listed)
+    names = np.ascontiguousarray(names)
+    spec = _lib.WordsSpec(C.sizeof(_lib.WordsSpec), _lib.KGPU_WORDS_SURFACE if field is None else int(field), filt, sep[0],
+                          names.ctypes.data if names.size else None, offs.ctypes.data, len(listed))
+    return spec, (names, offs)
+
+
+class Words:
+    """A words handle (kgpu_words): a field, a filter and a separator fixed for one Tokenizer.  Every sentence renders to exactly one line --
+    the words of its kept tokens joined by the separator, then a newline -- on the device.  Immutable; usable from many threads at once."""
+
+    def __init__(self, tokenizer: Tokenizer, field=None, drop=(), keep=(), separator=" "):
+        spec, keep_alive = words_spec(field, drop, keep, separator)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().kgpu_words_create(tokenizer.handle, C.byref(spec), C.byref(h)))
+        del keep_alive
+        self._h = h
+        self.tokenizer = tokenizer
+
+    @property
+    def handle(self):
+        return self._h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.lib().kgpu_words_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def render_packed(self, utf8: np.ndarray, offsets: np.ndarray, out=None):
+        """kgpu_tokenize_batch_words -> (text[uint8], text_offsets[uint64 n+1], status[uint8 n]): sentence i's line is
+        text[text_offsets[i]:text_offsets[i+1]].  out=(text, text_offsets, status): caller-owned arrays to reuse."""
+        utf8 = np.ascontiguousarray(utf8, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = offsets.size - 1
+        if n < 0:
+            raise ValueError("offsets needs n+1 entries")
+        total = int(offsets[-1] - offsets[0]) if n else 0
+        cap = total * 2 + n + 64
+        L = _lib.lib()
+        while True:
+            if out is not None:
+                text, toff, status = out
+                if text.dtype != np.uint8 or toff.dtype != np.uint64 or status.dtype != np.uint8 or toff.size < n + 1 or status.size < n:
+                    raise ValueError("out=(text[uint8], text_offsets[uint64 >= n+1], status[uint8 >= n])")
+                cap = text.size
+            else:
+                text = np.empty(max(cap, 1), dtype=np.uint8)
+                toff = np.empty(n + 1, dtype=np.uint64)
+                status = np.empty(max(n, 1), dtype=np.uint8)
+            status[: max(n, 1)] = 0
+            got = C.c_uint64(0)
+            rc = L.kgpu_tokenize_batch_words(self._h, utf8.ctypes.data if utf8.size else None, offsets.ctypes.data, n, text.ctypes.data, cap,
+                                             toff.ctypes.data, status.ctypes.data, C.byref(got))
+            if rc == _lib.KGPU_ERR_CAPACITY and out is None:
+                cap = int(got.value)  # exact size reported by the device
+                continue
+            _lib.check(rc)
+            return text[: int(got.value)], toff[: n + 1], status[:n]
+
+    def render_text(self, block):
+        """kgpu_tokenize_text_words: a raw block of input (bytes or uint8 array) -> (text, text_offsets, status) as
+        render_packed(*split_lines(block)) gives them; the split and the trim run on the device."""
+        src = _block_bytes(block)
+        cap, ocap = src.size * 2 + 64, src.size // 16 + 1024
+        L = _lib.lib()
+        while True:
+            text = np.empty(max(cap, 1), dtype=np.uint8)
+            toff = np.empty(ocap, dtype=np.uint64)
+            status = np.zeros(ocap, dtype=np.uint8)
+            n, got = C.c_uint64(0), C.c_uint64(0)
+            rc = L.kgpu_tokenize_text_words(self._h, src.ctypes.data if src.size else None, src.size, text.ctypes.data, cap, toff.ctypes.data, ocap,
+                                            status.ctypes.data, C.byref(n), C.byref(got))
+            if rc == _lib.KGPU_ERR_CAPACITY and (int(got.value) > cap or int(n.value) + 1 > ocap):   # exact sizes reported by the device
+                cap, ocap = max(cap, int(got.value)), max(ocap, int(n.value) + 1)
+                continue
+            _lib.check(rc)
+            k = int(n.value)
+            return text[: int(got.value)], toff[: k + 1], status[:k]
+
+    def render(self, sentences: Sequence) -> List[str]:
+        """One string of separated words per sentence (str or bytes), without the newline."""
+        utf8, offs = pack_sentences(sentences)
+        text, toff, _ = self.render_packed(utf8, offs)
+        raw = text.tobytes()
+        return [raw[int(toff[i]) : int(toff[i + 1]) - 1].decode("utf-8", "replace") for i in range(len(toff) - 1)]
 
 
 def _block_bytes(block) -> np.ndarray:
