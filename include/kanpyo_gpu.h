@@ -474,6 +474,74 @@ int kgpu_format_words_device(kgpu_ctx *c, const kgpu_words *w, const uint8_t *d_
                              const kgpu_token *d_tokens, const uint64_t *d_tok_offsets,
                              uint8_t *d_text, uint64_t text_capacity, uint64_t *d_text_offsets);
 
+/* ---- word counts: the frequencies of a corpus's words, accumulated on the device (NOT an output of the reference: what
+ * `mecab -Owakati | tr ' ' '\n' | sort | uniq -c | sort -rn` prints) ----
+ * A counts handle is made from a words handle and inherits its field and its filter; the separator plays no part.  It accumulates over any
+ * number of calls until it is reset; only status bytes return from an adding call, and the read-out is as large as the vocabulary, not the input.
+ *  1. Which tokens count.  Exactly the tokens wakati keeps (rules 1 and 3 above): EOS and dummy records never count; a sentence with
+ *     KGPU_SENT_INVALID_UTF8, or without tokens, adds nothing.
+ *  2. The word is wakati's rule 2, with one sharpening: when the word of a KNOWN token with an id (id != 0) is its surface, the word is THE
+ *     DICTIONARY'S KEY OF THAT ID.  For the tokenizer's own records these are the same bytes.  For caller-made records the record's position
+ *     and length are range-checked but do not choose the word.
+ *  3. The key is the word's bytes.  Tokens with different ids and the same bytes are one entry (duplicate surfaces, a base form equal to
+ *     another word's surface, a pool name equal to an unknown surface).  The empty word is a key (crafted zero-length surfaces of tokens that
+ *     are not known-with-an-id only).  Bytes are compared as bytes: "a" and "a\0" differ.
+ *  4. Counts are 64-bit.
+ *  5. The read-out gives the distinct words with their counts, ordered by count descending, then by the word's bytes ascending (memcmp; a
+ *     proper prefix comes first).  An optional `top` cuts the list after the sort.  The order does not depend on the order of insertion.
+ *  6. Capacity.  Words that a feature row determines (a known token with an id; a name of the field) have one counter per row and always fit.
+ *     All other words (unknown-class surfaces, surfaces of tokens without a row) live in a byte-keyed table of `table_slots` slots whose key
+ *     bytes are copied into an arena of `key_bytes` bytes; both are fixed at create (0 selects the default: KGPU_COUNTS_DEFAULT_SLOTS = 2^22
+ *     slots, 64 MiB, and KGPU_COUNTS_DEFAULT_KEY_BYTES = 256 MiB; table_slots is rounded up to a power of two; a key takes its length
+ *     rounded up to 8, plus 8, and a word that several wavefronts meet for the first time at once may take that more than once).  A token
+ *     whose word cannot be inserted is added to overflow_tokens and the call returns KGPU_ERR_CAPACITY -- after it has counted everything
+ *     else.  The handle stays usable and consistent: every reported count is <= the true count, the reported counts and overflow_tokens sum
+ *     to the tokens kept, and while overflow_tokens == 0 every count is exact.  The table does not grow.
+ *  7. Bad records (wakati rule 6) make the sync return KGPU_ERR_INVALID_ARG; the handle's contents are then unspecified until it is reset.
+ *  8. Threads.  Any number of threads may add into one handle at once; read-out and reset take the handle exclusively (a count enqueued on a
+ *     context is synced first).  The handle keeps the words handle's tables and the dictionary alive, as a words handle keeps the dictionary:
+ *     it may outlive both handles. */
+#define KGPU_COUNTS_DEFAULT_SLOTS (1ull << 22)
+#define KGPU_COUNTS_DEFAULT_KEY_BYTES (256ull << 20)
+typedef struct kgpu_counts_opts {
+    uint32_t size;         /* sizeof(kgpu_counts_opts): fields may be appended later */
+    uint32_t reserved;
+    uint64_t table_slots;  /* slots of the byte-keyed table (16 bytes each), 0 = the default */
+    uint64_t key_bytes;    /* bytes of its key arena, 0 = the default; at most 2^34 */
+} kgpu_counts_opts;
+typedef struct kgpu_counts_info {
+    uint32_t size;              /* in: sizeof(kgpu_counts_info) as the caller knows it; that many bytes are written at most */
+    uint32_t reserved;
+    uint64_t tokens_counted;    /* tokens added to a counter: the sum of all counts */
+    uint64_t overflow_tokens;   /* kept tokens that found no slot or no key space */
+    uint64_t sentences;         /* sentences the adding calls have seen */
+    uint64_t table_slots, table_slots_used;
+    uint64_t key_bytes, key_bytes_used;
+} kgpu_counts_info;
+typedef struct kgpu_counts kgpu_counts;
+/* opts may be NULL (the defaults).  KGPU_ERR_INVALID_ARG: a null handle, an opts.size smaller than the struct, sizes beyond 2^32 slots / 2^34 bytes. */
+int kgpu_counts_create(kgpu_words *w, const kgpu_counts_opts *opts, kgpu_counts **out);
+void kgpu_counts_destroy(kgpu_counts *k);
+int kgpu_counts_reset(kgpu_counts *k);   /* every count, overflow_tokens and sentences back to zero */
+int kgpu_counts_get_info(kgpu_counts *k, kgpu_counts_info *info);
+/* The sentences of kgpu_tokenize_batch_words, tokenized and counted: nothing but the status bytes (n entries, may be NULL) comes back. */
+int kgpu_count_batch(kgpu_counts *k, const uint8_t *utf8, const uint64_t *offsets, uint64_t n, uint8_t *status);
+/* The raw block of kgpu_tokenize_text_words.  *n_lines: the lines found (required).  status (may be NULL): status_capacity entries;
+ * KGPU_ERR_CAPACITY with *n_lines set and NOTHING counted when the lines outnumber them. */
+int kgpu_count_text(kgpu_counts *k, const uint8_t *text, uint64_t len, uint8_t *status, uint64_t status_capacity, uint64_t *n_lines);
+/* Device-resident: count records that a synced kgpu_tokenize_device batch (or anyone) left in HBM, enqueued on c's stream; kgpu_ctx_sync_count
+ * waits and reports the tokens this batch added (rules 6 and 7 give its errors).  One render or count may be pending per context, whichever
+ * kind.  A context whose dictionary is not the handle's: KGPU_ERR_INVALID_ARG. */
+int kgpu_count_words_device(kgpu_ctx *c, kgpu_counts *k, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n,
+                            const kgpu_token *d_tokens, const uint64_t *d_tok_offsets);
+int kgpu_ctx_sync_count(kgpu_ctx *c, uint64_t *n_counted);
+/* The read-out of rule 5: entry i is words[word_offsets[i] .. word_offsets[i + 1]) with counts[i]; top = 0: all of them.  *n_entries and
+ * *n_bytes (both required) are the exact sizes; KGPU_ERR_CAPACITY (nothing written) when entries_capacity < *n_entries or words_capacity <
+ * *n_bytes.  word_offsets: entries_capacity + 1 entries, counts: entries_capacity.  Not a hot path: the counters come back to the host, every
+ * row is resolved to its bytes (a name of the field, or the dictionary's key of the id), equal byte strings are merged and the list is sorted. */
+int kgpu_counts_read(kgpu_counts *k, uint64_t top, uint8_t *words, uint64_t words_capacity, uint64_t *word_offsets, uint64_t *counts,
+                     uint64_t entries_capacity, uint64_t *n_entries, uint64_t *n_bytes);
+
 #ifdef __cplusplus
 }
 #endif

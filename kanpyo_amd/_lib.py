@@ -30,7 +30,10 @@ SYMBOLS = [
     "kgpu_dict_set_features", "kgpu_tokenize_batch_lines", "kgpu_format_lines_device", "kgpu_ctx_sync_lines", "kgpu_split_lines",
     "kgpu_split_lines_device", "kgpu_ctx_sync_split", "kgpu_tokenize_text_lines", "kgpu_graphviz_batch",
     "kgpu_words_create", "kgpu_words_destroy", "kgpu_tokenize_batch_words", "kgpu_tokenize_text_words", "kgpu_format_words_device",
+    "kgpu_counts_create", "kgpu_counts_destroy", "kgpu_counts_reset", "kgpu_counts_get_info", "kgpu_count_batch", "kgpu_count_text",
+    "kgpu_count_words_device", "kgpu_ctx_sync_count", "kgpu_counts_read",
 ]
+KGPU_COUNTS_DEFAULT_SLOTS, KGPU_COUNTS_DEFAULT_KEY_BYTES = 1 << 22, 256 << 20
 KGPU_WORDS_SURFACE = -1
 KGPU_WORDS_ALL, KGPU_WORDS_DROP, KGPU_WORDS_KEEP = 0, 1, 2
 
@@ -112,6 +115,15 @@ class WordsSpec(C.Structure):  # kgpu_words_spec
                 ("names", C.c_void_p), ("name_offsets", C.c_void_p), ("n_names", C.c_uint64)]
 
 
+class CountsOpts(C.Structure):  # kgpu_counts_opts
+    _fields_ = [("size", C.c_uint32), ("reserved", C.c_uint32), ("table_slots", C.c_uint64), ("key_bytes", C.c_uint64)]
+
+
+class CountsInfo(C.Structure):  # kgpu_counts_info: read with its size, fields are only ever appended
+    _fields_ = [("size", C.c_uint32), ("reserved", C.c_uint32), ("tokens_counted", C.c_uint64), ("overflow_tokens", C.c_uint64), ("sentences", C.c_uint64),
+                ("table_slots", C.c_uint64), ("table_slots_used", C.c_uint64), ("key_bytes", C.c_uint64), ("key_bytes_used", C.c_uint64)]
+
+
 class Work(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("sentences", "B", "C", "T", "N", "E", "K")]
 
@@ -186,6 +198,18 @@ def lib():
         L.kgpu_tokenize_batch_words.argtypes = L.kgpu_tokenize_batch_lines.argtypes
         L.kgpu_tokenize_text_words.argtypes = L.kgpu_tokenize_text_lines.argtypes
         L.kgpu_format_words_device.argtypes = [vp] + L.kgpu_format_lines_device.argtypes
+        L.kgpu_counts_create.argtypes = [vp, C.POINTER(CountsOpts), C.POINTER(vp)]
+        L.kgpu_counts_destroy.argtypes = [vp]
+        L.kgpu_counts_destroy.restype = None
+        L.kgpu_counts_reset.argtypes = [vp]
+        L.kgpu_counts_get_info.argtypes = [vp, C.POINTER(CountsInfo)]
+        L.kgpu_count_batch.argtypes = [vp, vp, vp, C.c_uint64, vp]
+        L.kgpu_count_text.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.kgpu_count_words_device.argtypes = [vp, vp, vp, vp, C.c_uint64, vp, vp]
+        L.kgpu_ctx_sync_count.argtypes = [vp, C.POINTER(C.c_uint64)]
+        L.kgpu_counts_read.argtypes = [vp, C.c_uint64, vp, C.c_uint64, vp, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.kgpu_debug_counts_order.argtypes = [vp, vp, vp, C.c_uint64] + L.kgpu_counts_read.argtypes[1:]
+        L.kgpu_debug_key_table.argtypes = [vp, C.c_size_t, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), vp]
         L.kgpu_debug_word_table.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_uint64, C.c_uint64, C.POINTER(WordsSpec), vp, vp, C.c_uint64,
                                             C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
         L.kgpu_debug_feature_pool.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_uint64, C.c_uint64, vp, C.c_uint64, vp, C.POINTER(C.c_uint64)]

@@ -19,6 +19,13 @@ kgpu_tokenize_text_words).  --field N prints feature N of each token's row inste
 6, 7, 8, IPADIC's columns; the surface where a row has no such feature, or it is empty or "*"); --drop / --keep filter tokens by feature 0,
 the part of speech.  stdin is handled as `tokenize` handles it: blocks of whole lines, and a line that is not UTF-8 ends the run with status
 101 after the lines before it.
+
+`python -m kanpyo_amd count [INPUT] [-c DICT] [--field N | --base-form | --reading | --pronunciation] [--drop POS[,POS...] | --keep POS[,POS...]]
+[--top N] [--split host|device] [--skip-invalid]`: NOT a subcommand of the reference either -- the word frequencies of the whole input, what
+`wakati | tr ' ' '\n' | sort | uniq -c | sort -rn` gives, accumulated on the device (kgpu_count_batch / kgpu_count_text) and printed at the end
+as `count\tword` lines, by count descending and then by the word's bytes ascending; --top N prints the first N.  The words and the filter are
+wakati's.  A line that is not UTF-8 ends the run with status 101, its 1-based line number on stderr and NOTHING on stdout -- a partial
+frequency table is worse than none; with --skip-invalid such lines are skipped, their numbers go to stderr and the status is 0.
 """
 from __future__ import annotations
 
@@ -125,6 +132,42 @@ def wakati(args, stdin, stdout) -> int:
     return 0
 
 
+def count(args, stdin, stdout) -> int:
+    from . import dictfile
+    from .tokenizer import Tokenizer, split_lines
+
+    df = dictfile.load_dict(args.custom_dict or default_dict_path())
+    tok = Tokenizer(df.dict)
+    tok.set_features(df.morph_feature_table, df.unk_feature_table)
+    counts = tok.words(field=args.field, drop=args.drop, keep=args.keep).counter()
+    if args.input is not None:   # that one string, untrimmed
+        one = np.frombuffer(os.fsencode(args.input), dtype=np.uint8)
+        results = iter([counts.add_packed(one, np.array([0, one.size], dtype=np.uint64))])
+    elif args.split == "device":
+        results = (counts.add_text(b) for b in _blocks(stdin, args.block_bytes))
+    else:
+        results = (counts.add_packed(*split_lines(b)) for b in _blocks(stdin, args.block_bytes))
+    line0 = 0   # lines in the blocks before this one
+    for status in results:
+        for i in np.flatnonzero(status == 1).tolist():
+            print(f"kanpyo_amd: line {line0 + i + 1}: not valid UTF-8" + (" (skipped)" if args.skip_invalid else ""), file=sys.stderr)
+            if not args.skip_invalid:
+                return PANIC_STATUS   # nothing has been printed
+        line0 += len(status)
+    out = bytearray()
+    for word, n in counts.most_common(args.top):
+        out += b"%d\t" % n + word + b"\n"
+    stdout.write(bytes(out))
+    stdout.flush()
+    return 0
+
+
+def _top(text: str) -> int:
+    if not text.isascii() or not text.isdigit() or int(text) < 1:
+        raise argparse.ArgumentTypeError(f"invalid value {text!r}: a count from 1")
+    return int(text)
+
+
 def _pos_list(text: str):
     """--drop / --keep: part-of-speech names separated by commas."""
     return [p for p in text.split(",") if p]
@@ -190,7 +233,7 @@ def _dpi(text: str) -> int:
 
 
 def parse_args(argv=None):
-    """The reference's command line (src/bin/kanpyo.rs:14-49).  -> the namespace; .command is "tokenize" or "graphviz" -- or "wakati", which is this package's own."""
+    """The reference's command line (src/bin/kanpyo.rs:14-49).  -> the namespace; .command is "tokenize" or "graphviz" -- or "wakati" or "count", which are this package's own."""
     p = argparse.ArgumentParser(prog="kanpyo_amd", description="Japanese Morphological Analyzer (kanpyo) on AMD Instinct GPUs")
     sub = p.add_subparsers(dest="command")
     t = sub.add_parser("tokenize", help="Tokenize input text")
@@ -222,6 +265,23 @@ def parse_args(argv=None):
     w.add_argument("--split", choices=["host", "device"], default="host",
                    help="Where stdin's blocks are split into lines and trimmed [default: host]")
     w.add_argument("--block-bytes", type=int, default=BLOCK_BYTES, help=argparse.SUPPRESS)
+    c = sub.add_parser("count", help="Word frequencies of the whole input (not in the reference)")
+    c.add_argument("input", nargs="?", default=None, help="Input text to analyze [default: stdin]")
+    c.add_argument("-d", "--dict", choices=["ipa"], default="ipa", help="Dictionary")
+    c.add_argument("-c", "--custom-dict", default=None, help="Custom dictionary (.dict)")
+    fld = c.add_mutually_exclusive_group()
+    fld.add_argument("--field", type=_field, default=None, help="Count feature N of the token's row instead of the surface")
+    fld.add_argument("--base-form", dest="field", action="store_const", const=6, help="--field 6 (IPADIC)")
+    fld.add_argument("--reading", dest="field", action="store_const", const=7, help="--field 7 (IPADIC)")
+    fld.add_argument("--pronunciation", dest="field", action="store_const", const=8, help="--field 8 (IPADIC)")
+    flt = c.add_mutually_exclusive_group()
+    flt.add_argument("--drop", type=_pos_list, default=[], help="Drop tokens whose part of speech (feature 0) is one of POS[,POS...]")
+    flt.add_argument("--keep", type=_pos_list, default=[], help="Keep only tokens whose part of speech is one of POS[,POS...]")
+    c.add_argument("--top", type=_top, default=None, help="Print the N most frequent words only")
+    c.add_argument("--split", choices=["host", "device"], default="host",
+                   help="Where stdin's blocks are split into lines and trimmed [default: host]")
+    c.add_argument("--skip-invalid", action="store_true", help="Skip lines that are not UTF-8 instead of ending with status 101")
+    c.add_argument("--block-bytes", type=int, default=BLOCK_BYTES, help=argparse.SUPPRESS)
     args = p.parse_args(argv)
     if args.command is None:   # src/bin/kanpyo.rs:173: no subcommand == tokenize from stdin, default dictionary
         args = t.parse_args([])
@@ -238,6 +298,8 @@ def main(argv=None) -> int:
             return graphviz(args, sys.stdin.buffer, sys.stdout.buffer)
         if args.command == "wakati":
             return wakati(args, sys.stdin.buffer, sys.stdout.buffer)
+        if args.command == "count":
+            return count(args, sys.stdin.buffer, sys.stdout.buffer)
         return tokenize(args, sys.stdin.buffer, sys.stdout.buffer)
     except _lib.KgpuError as e:
         print(f"kanpyo_amd: {e}", file=sys.stderr)

@@ -14,6 +14,7 @@
 // 65535 or more distinct characters -- are walked byte by byte as before).
 #include <algorithm>
 #include <cstdint>
+#include <cstring>
 #include <vector>
 
 #include "kgpu_internal.h"
@@ -198,6 +199,53 @@ bool build_char_trie(const std::vector<DaNode> &da, const uint8_t *cat, size_t c
     return true;
 }
 
+// Every key of the byte-level array by its id, for the word counts' read-out (kgpu_count_host.cpp): a depth-first walk over the children lists; the
+// terminator child of a node (byte 0, base < 0: da.rs:118-123) names the id of the key that ends there, and `dup` (index.rs:46-51) the ids behind it
+// that share the key.  A node is visited once (every slot has one parent), so the walk ends whatever the array looks like.
+void build_key_table(const std::vector<DaNode> &da, const std::vector<std::pair<int64_t, uint64_t>> &dup, uint64_t n_morphs, std::vector<uint8_t> &bytes,
+                     std::vector<uint64_t> &off) {
+    bytes.clear();
+    off.assign((size_t)n_morphs + 1, 0);
+    if (da.size() < 2 || da[1].base < 0 || n_morphs == 0) return;
+    const ByteTrie bt(da);
+    std::vector<uint64_t> shares((size_t)n_morphs, 0);   // ids behind id k (0-based index k - 1) that share its key
+    for (const auto &kv : dup)
+        if (kv.first >= 1 && (uint64_t)kv.first <= n_morphs) shares[(size_t)kv.first - 1] = kv.second;
+    std::vector<uint32_t> key_at((size_t)n_morphs, 0xFFFFFFFFu), key_len((size_t)n_morphs, 0);   // into `pool`: keys in the walk's order
+    std::vector<uint8_t> pool, path;
+    struct Frame { uint32_t node, next, end; };
+    std::vector<Frame> stack{Frame{1u, bt.start[1], bt.start[2]}};
+    std::vector<uint8_t> seen(da.size(), 0);
+    seen[1] = 1;
+    while (!stack.empty()) {
+        Frame &f = stack.back();
+        if (f.next == f.end) { stack.pop_back(); if (!path.empty()) path.pop_back(); continue; }
+        const uint32_t q = bt.slot[f.next++];
+        const uint32_t c = (uint32_t)((int64_t)q - da[f.node].base);
+        if (c == 0) {   // the terminator: a key ends on f.node
+            if (da[q].base < 0) {
+                const uint64_t id = (uint64_t)(-(int64_t)da[q].base);
+                if (id >= 1 && id <= n_morphs && pool.size() + path.size() < 0xFFFFFFFFu) {
+                    const uint64_t last = std::min<uint64_t>(n_morphs, id + shares[(size_t)id - 1]);
+                    for (uint64_t k = id; k <= last; ++k)
+                        if (key_at[(size_t)k - 1] == 0xFFFFFFFFu) { key_at[(size_t)k - 1] = (uint32_t)pool.size(); key_len[(size_t)k - 1] = (uint32_t)path.size(); }
+                    pool.insert(pool.end(), path.begin(), path.end());
+                }
+            }
+            continue;
+        }
+        if (seen[q] || da[q].base < 0) continue;
+        seen[q] = 1;
+        path.push_back((uint8_t)c);
+        stack.push_back(Frame{q, bt.start[q], bt.start[q + 1]});
+    }
+    for (size_t k = 0; k < (size_t)n_morphs; ++k) {
+        off[k] = bytes.size();
+        if (key_at[k] != 0xFFFFFFFFu) bytes.insert(bytes.end(), pool.begin() + key_at[k], pool.begin() + key_at[k] + key_len[k]);
+    }
+    off[(size_t)n_morphs] = bytes.size();
+}
+
 }  // namespace kgpu
 
 // ---- test hook (tests/test_chartrie_cpu.py; not in include/kanpyo_gpu.h): build the character-level array from an index.dict blob's double
@@ -263,4 +311,31 @@ extern "C" int kgpu_debug_chartrie_search(const uint8_t *index_blob, size_t blob
     }
     out_offsets[nq] = np;
     return np > cap_pairs ? KGPU_ERR_CAPACITY : KGPU_OK;
+}
+
+// ---- test hook (tests/test_count_cpu.py; not in include/kanpyo_gpu.h): the id -> key table of the word counts' read-out (build_key_table) for an
+// index.dict blob, without a device.  key id k is keys[key_offsets[k - 1] .. key_offsets[k]) (n_morphs + 1 offsets).  KGPU_ERR_CAPACITY: keys_cap <
+// *keys_len (the offsets are written all the same).
+extern "C" int kgpu_debug_key_table(const uint8_t *index_blob, size_t blob_len, uint64_t n_morphs, uint8_t *keys, uint64_t keys_cap, uint64_t *keys_len,
+                                    uint64_t *key_offsets) {
+    using namespace kgpu;
+    if (!index_blob || blob_len < 8 || !keys_len || !key_offsets) return KGPU_ERR_INVALID_ARG;
+    uint64_t n = 0, m = 0;
+    std::memcpy(&n, index_blob, 8);
+    if (n > (blob_len - 8) / 8) return KGPU_ERR_BAD_DICT;
+    std::vector<DaNode> da((size_t)n);
+    if (n) std::memcpy(da.data(), index_blob + 8, (size_t)n * 8);
+    size_t at = 8 + (size_t)n * 8;
+    if (blob_len - at >= 8) { std::memcpy(&m, index_blob + at, 8); at += 8; }
+    if (m > (blob_len - at) / 16) return KGPU_ERR_BAD_DICT;
+    std::vector<std::pair<int64_t, uint64_t>> dup((size_t)m);
+    for (auto &kv : dup) { std::memcpy(&kv.first, index_blob + at, 8); std::memcpy(&kv.second, index_blob + at + 8, 8); at += 16; }
+    std::vector<uint8_t> bytes;
+    std::vector<uint64_t> off;
+    build_key_table(da, dup, n_morphs, bytes, off);
+    std::memcpy(key_offsets, off.data(), off.size() * 8);
+    *keys_len = bytes.size();
+    if (bytes.size() > keys_cap) return KGPU_ERR_CAPACITY;
+    if (!bytes.empty()) std::memcpy(keys, bytes.data(), bytes.size());
+    return KGPU_OK;
 }

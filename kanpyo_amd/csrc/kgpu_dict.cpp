@@ -345,6 +345,7 @@ extern "C" int kgpu_dict_create(const kgpu_dict_blobs *b, int device, kgpu_dict 
     // A leaf (reached through the terminator byte, trie/da.rs:118-123) stores base = -id.  The walk has to load that node
     // anyway, and the record count of the surface (index.rs:46-51) is the next thing it needs: with ids below 2^21 the spare
     // bits hold it (1023 = larger, look it up), and one dependent load per match disappears from the walk.
+    const std::vector<DaNode> da_as_given(da);   // (the word counts' key table is built from the caller's own leaves, lazily)
     uint32_t leaf_dup = 0;
     if (morphs.size() < (1u << 21) && !test_hooks().plain_leaves /* tests: the layout of a dictionary with 2^21 morphs or more */) {
         leaf_dup = 1;
@@ -369,6 +370,8 @@ extern "C" int kgpu_dict_create(const kgpu_dict_blobs *b, int device, kgpu_dict 
     kgpu_dict *d = new kgpu_dict();
     d->combiner = combiner_new();
     d->device = device;
+    d->da_host = da_as_given;
+    d->dup_host = dup;
     d->right_of_rank.resize(rank_r.size()); d->left_of_rank.resize(rank_l.size());
     for (uint32_t i = 0; i < rank_r.size(); ++i) d->right_of_rank[rank_r[i]] = i;
     for (uint32_t i = 0; i < rank_l.size(); ++i) d->left_of_rank[rank_l[i]] = i;

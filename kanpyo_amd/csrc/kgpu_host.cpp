@@ -256,7 +256,7 @@ bool kgpu::is_pinned_host(const void *p) {
 // The chunk's input goes to the device as ONE block [offsets (absolute, as the caller has them) | bytes]; the kernels subtract
 // offsets[0] themselves, the text pointer is biased by it.  Pinned caller memory is copied from directly (DMA), pageable memory through
 // the context's pinned staging block, filled with the workers' help.  off: the chunk's first offset.
-static int upload_input(kgpu_ctx *c, const ChunkInput &in, const uint8_t *utf8, const uint64_t *off, bool pinned_in) {
+int kgpu::upload_input(kgpu_ctx *c, const ChunkInput &in, const uint8_t *utf8, const uint64_t *off, bool pinned_in) {
     uint8_t *dblk = (uint8_t *)c->in_block.p;
     const uint64_t n = in.n, base = off[0], total = in.total;
     int rc;
@@ -339,8 +339,8 @@ ChunkLimits kgpu::chunk_limits(uint64_t n) {
                        std::min<uint64_t>(hooks.chunk_sents, std::min<uint64_t>(8192, std::max<uint64_t>(1024, n / 12)))};   // (round 6: the floor was 2048 -- with the pool kernel at 59 us per 4096 sentences a 4096-sentence call runs 182 -> 174 us as four chunks)
 }
 // The ring of kgpu_tokenize_batch / kgpu_tokenize_batch_lines; two of its jobs stay out of the device pipeline: their blocks are being expanded.
-static int batch_depth() { return (int)std::min<uint64_t>(MAX_PIPE_DEPTH, std::max<uint64_t>(3, test_hooks().depth)); }
-static bool batch_is_pinned(const uint8_t *utf8, const uint64_t *offsets, uint64_t n) { return (offsets[n] - offsets[0]) != 0 && is_pinned_host(utf8) && is_pinned_host(offsets); }
+int kgpu::batch_depth() { return (int)std::min<uint64_t>(MAX_PIPE_DEPTH, std::max<uint64_t>(3, test_hooks().depth)); }
+bool kgpu::batch_is_pinned(const uint8_t *utf8, const uint64_t *offsets, uint64_t n) { return (offsets[n] - offsets[0]) != 0 && is_pinned_host(utf8) && is_pinned_host(offsets); }
 
 int kgpu::check_host_batch(const char *who, const uint64_t *offsets, uint64_t n, const uint8_t *utf8) {
     for (uint64_t i = 0; i < n; ++i)

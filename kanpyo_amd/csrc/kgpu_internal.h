@@ -5,6 +5,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <utility>
 #include <vector>
 
 #include "../../include/kanpyo_gpu.h"
@@ -46,6 +47,10 @@ struct CharTrie {         // host side, before the upload
     uint32_t n_codes = 0;
 };
 bool build_char_trie(const std::vector<DaNode> &da, const uint8_t *cat, size_t cat_len, CharTrie &out);  // false: walk the bytes
+// kgpu_chartrie.cpp: every key of the double array by its id (the ids that share a key through `dup`, index.rs:46-51, included): id k is
+// bytes[off[k - 1] .. off[k]); an id without a key is empty
+void build_key_table(const std::vector<DaNode> &da, const std::vector<std::pair<int64_t, uint64_t>> &dup, uint64_t n_morphs, std::vector<uint8_t> &bytes,
+                     std::vector<uint64_t> &off);
 
 struct DictView {
     const DaNode *da;        uint32_t da_len;
@@ -175,6 +180,26 @@ struct WordsArgs {
     unsigned long long *host_ctl;  // [0] total bytes, [1] a record out of range
 };
 int launch_format_words(const WordsArgs &a, void *stream);
+// The word counts of a batch (kgpu_count.hip; include/kanpyo_gpu.h, "word counts"): every kept token adds one to its word's counter in a counts handle.
+// A word is row-determined when the token is a known one with a row, or when its word is a pool name: those go to `dense`, one counter per feature row
+// (the host resolves a row to its bytes at read-out).  Every other word -- an unknown-class surface, the surface of a token without a row -- goes to the
+// byte-keyed table: open addressing over `slots`, the key's bytes copied into `arena`.
+struct alignas(16) CountSlot { unsigned long long tag, count; };   // tag: 0 = free, else hash << 32 | (arena entry's offset / 8 + 1)
+// An arena entry, 8-byte aligned: u32 length, u32 hash, the key's bytes.  Written whole BEFORE the slot that names it is claimed, never changed after.
+constexpr uint32_t COUNT_ENTRY_HEAD = 8;
+constexpr uint32_t COUNT_PARTIAL_WORDS = 4;   // per workgroup of the count launch: tokens counted, tokens that found no room, a bad record, slots claimed
+constexpr uint32_t COUNT_STAT_WORDS = 8;      // the handle's device words: [0] arena cursor (bytes; may run past the capacity), [1] slots used, [2] tokens counted, [3] overflow tokens
+struct CountsArgs {
+    WordsArgs w;                     // the batch and the handle's word table (utf8 .. drop_rowless; status_in / status_out as the renders mirror them; the rest unused)
+    unsigned long long *dense;       // w.n_rows counters
+    CountSlot *slots; uint32_t slot_mask;   // a power of two of slots
+    uint8_t *arena; uint64_t arena_bytes;
+    unsigned long long *stats;       // COUNT_STAT_WORDS
+    unsigned long long *partial;     // device scratch of the launch: COUNT_PARTIAL_WORDS per workgroup (count_blocks), summed by the publishing kernel
+    unsigned long long *host_ctl;    // [0] tokens this launch counted, [1] bit 0: a record out of range, bit 1: a token found no room
+};
+uint32_t count_blocks(uint64_t n);   // workgroups of the count launch
+int launch_count_words(const CountsArgs &a, void *stream);
 // The DOT documents of a batch's kept lattices (kgpu_graphviz.hip; reference src/graphviz.rs:30-163).
 struct GraphvizArgs {
     const uint8_t *utf8;           // as BatchArgs::utf8 / offsets of the launch that kept the lattices

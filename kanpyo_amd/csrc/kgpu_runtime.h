@@ -1,6 +1,6 @@
 // kanpyo_amd/csrc/kgpu_runtime.h -- the host runtime's own types and the functions its files share: kgpu_dict.cpp (dictionary),
 // kgpu_ctx.cpp (contexts, launch chain), kgpu_host.cpp (large host calls), kgpu_small.cpp (small calls), kgpu_multi.cpp (the
-// multi-device entry points), kgpu_split_host.cpp (lines of a raw block), kgpu_graphviz_host.cpp (DOT documents of a batch).  Not part of the public ABI.
+// multi-device entry points), kgpu_split_host.cpp (lines of a raw block), kgpu_graphviz_host.cpp (DOT documents of a batch), kgpu_words_host.cpp (wakati), kgpu_count_host.cpp (word counts).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -10,6 +10,7 @@
 #include <deque>
 #include <functional>
 #include <mutex>
+#include <shared_mutex>
 #include <thread>
 #include <vector>
 
@@ -109,6 +110,14 @@ struct kgpu_dict {
     const uint32_t *label_off = nullptr;
     // ... and a copy of the two blobs themselves, which kgpu_words_create parses again for its per-row word table (host memory: their size)
     std::vector<uint8_t> feat_blob_known, feat_blob_unk;
+    // The word counts' read-out resolves a known id to its KEY (kgpu_count_host.cpp: dict_key_table): key id k is key_bytes[key_off[k - 1] .. key_off[k]).
+    // Built lazily, once, from the double array as the caller gave it (da_host, dup_host: kept for this and released when the table is there).
+    std::mutex keys_mu;
+    bool keys_built = false;
+    std::vector<DaNode> da_host;
+    std::vector<std::pair<int64_t, uint64_t>> dup_host;
+    std::vector<uint8_t> key_bytes;
+    std::vector<uint64_t> key_off;
     // One reference for the handle the caller holds plus one per live context: the tables and the shared
     // streams go when the last one does (a context outliving kgpu_dict_destroy keeps working).
     std::atomic<int> refs{1};
@@ -121,6 +130,22 @@ struct kgpu_words {
     int32_t field = -1;
     uint32_t filter = 0, sep = ' ';
     void *d_rows = nullptr, *d_names = nullptr;   // WordRow per feature row; the pool of distinct names
+    std::vector<WordRow> h_rows;        // ... and their host copies: a counts handle's read-out resolves a row to its bytes
+    std::vector<uint8_t> h_names;
+    std::atomic<int> refs{1};           // the caller's handle, and one per counts handle made from it: the tables go with the last (words_release)
+};
+
+// A counts handle (kgpu_count_host.cpp): the word frequencies of everything added to it, on the device, by a words handle's field and filter.
+struct kgpu_counts {
+    kgpu_words *words = nullptr;        // holds a reference (its tables and, through it, the dictionary)
+    uint64_t table_slots = 0, key_bytes = 0;
+    void *d_dense = nullptr, *d_slots = nullptr, *d_arena = nullptr, *d_stats = nullptr;
+    std::shared_mutex mu;               // adding calls share it, read-out and reset take it alone
+    std::atomic<uint64_t> sentences{0};
+    std::atomic<uint64_t> version{1};   // bumped by every add and reset: the merged read-out below is that of `cached_version`
+    uint64_t cached_version = 0;
+    std::vector<uint8_t> cached_words;
+    std::vector<uint64_t> cached_off, cached_counts;
 };
 
 struct kgpu_ctx {
@@ -270,12 +295,20 @@ int enqueue_words(kgpu_ctx *c, const kgpu_words *w, const uint8_t *d_utf8, const
 int build_word_table(const uint8_t *known, size_t known_len, const uint8_t *unk, size_t unk_len, uint64_t n_morphs, uint64_t n_unk,
                      const kgpu_words_spec &spec, std::vector<WordRow> &rows, std::vector<uint8_t> &names);
 
+// kgpu_words_host.cpp
+void words_release(kgpu_words *w);   // one reference less: the last one frees the tables and lets go of the dictionary
+// kgpu_count_host.cpp: the count of a batch's records on c->stream behind whatever is queued there (waited for by kgpu_ctx_sync_count)
+int enqueue_count(kgpu_ctx *c, kgpu_counts *k, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n, const kgpu_token *d_tokens, const uint64_t *d_tok_offsets,
+                  const uint8_t *status_in, uint8_t *status_out, const char *who);
+
 int require_features(kgpu_dict *d, const char *who);   // KGPU_ERR_INVALID_ARG unless kgpu_dict_set_features has been called
 int ensure_label_pool(kgpu_dict *d);                   // kgpu_features.cpp: the graphviz label pool on the device (first call uploads it)
 
 // kgpu_host.cpp
 void parallel_copy(void *dst, const void *src, size_t bytes);
 bool is_pinned_host(const void *p);
+int batch_depth();                                                               // the ring of the host batch calls
+bool batch_is_pinned(const uint8_t *utf8, const uint64_t *offsets, uint64_t n);  // ... whose input is copied from directly when it is pinned
 int check_host_batch(const char *who, const uint64_t *offsets, uint64_t n, const uint8_t *utf8);   // a host batch's offsets are monotone, its bytes are there
 // The records a batch of n sentences / `total` bytes can produce: tokens <= chars + 1 <= bytes + 1 per sentence, so a buffer of this many is never too small.
 inline uint64_t token_bound(uint64_t total, uint64_t n) { return total + n + 1; }
@@ -290,6 +323,10 @@ struct ChunkInput {
     const uint64_t *d_offsets(const kgpu_ctx *c) const { return (const uint64_t *)c->in_block.p; }
     const uint8_t *d_text(const kgpu_ctx *c, uint64_t base) const { return (const uint8_t *)c->in_block.p + in_off - base; }   // (offsets start at `base`)
 };
+int upload_input(kgpu_ctx *c, const ChunkInput &in, const uint8_t *utf8, const uint64_t *off, bool pinned_in);   // kgpu_host.cpp: the chunk's block to the device (off: its first offset)
+// kgpu_split_host.cpp: a raw block of host memory on the splitting context sc: one copy to the device, the split; -> the lines' offsets on the host (sc->split_text /
+// sc->split_off hold the packed lines and their offsets on the device until sc is given back)
+int split_block(kgpu_ctx *sc, const uint8_t *text, uint64_t len, const char *who, std::vector<uint64_t> &off, uint64_t &lines);
 // One chunk of kgpu_tokenize_batch / kgpu_tokenize_batch_multi (kgpu_host.cpp: pipe_submit; kgpu_multi.cpp: shard_submit): its input block, and the
 // mapped block c->pin_out the compaction kernel writes the results into: 8-byte records | first | token offsets | status.
 struct ChunkBlock {

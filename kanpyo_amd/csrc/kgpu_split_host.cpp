@@ -3,7 +3,8 @@
 // Owns: kgpu_split_lines_device / kgpu_ctx_sync_split (a block resident in HBM, on a context's stream) and kgpu_tokenize_text_lines /
 // kgpu_tokenize_text_words (one body, text_lines: a raw block in host memory: one copy to the device, the split, then the lines go through the launch chain and the render in chunks
 // on pooled contexts -- their inputs are pointers into the split's output, nothing of the text returns to the host in between; the
-// chunks are LinesChunk in run_pipeline, kgpu_runtime.h, as those of kgpu_tokenize_batch_lines).
+// chunks are LinesChunk in run_pipeline, kgpu_runtime.h, as those of kgpu_tokenize_batch_lines); split_block, the copy and the split in front of them, which
+// kgpu_count_text (kgpu_count_host.cpp) shares.
 #include <vector>
 
 #include "kgpu_runtime.h"
@@ -50,6 +51,25 @@ extern "C" int kgpu_ctx_sync_split(kgpu_ctx *c, uint64_t *n_lines, uint64_t *n_b
     return KGPU_OK;
 }
 
+// ONE copy of the raw block to the device, then the split; the offsets table is sized by a guess and grown to the count the device found
+int kgpu::split_block(kgpu_ctx *sc, const uint8_t *text, uint64_t len, const char *WHO, std::vector<uint64_t> &off, uint64_t &lines) {
+    int rc;
+    uint64_t packed = 0;
+    if ((rc = sc->split_raw.ensure((size_t)len + 16)) || (rc = sc->split_text.ensure((size_t)len + 16))) return rc;
+    if (len && (rc = ctx_h2d(sc, sc->split_raw.p, text, (size_t)len, "H2D text block"))) return rc;
+    for (uint64_t cap = len / 16 + 1024;;) {
+        if ((rc = sc->split_off.ensure((size_t)cap * 8))) return rc;
+        if ((rc = enqueue_split(sc, (const uint8_t *)sc->split_raw.p, len, (uint8_t *)sc->split_text.p, (uint64_t *)sc->split_off.p, cap, WHO))) return rc;
+        rc = kgpu_ctx_sync_split(sc, &lines, &packed);
+        if (rc == KGPU_ERR_CAPACITY) { cap = lines + 1; continue; }
+        if (rc) return rc;
+        break;
+    }
+    off.resize((size_t)lines + 1);
+    if (hipMemcpy(off.data(), sc->split_off.p, (size_t)(lines + 1) * 8, hipMemcpyDeviceToHost) != hipSuccess) { set_error("%s: D2H offsets failed", WHO); return KGPU_ERR_HIP; }
+    return KGPU_OK;
+}
+
 // ---- kgpu_tokenize_text_lines: a raw block in host memory -> the CLI's output ---------------------------------------------------------
 // One chunk of the block's lines on a pooled context: lines [lo, lo + m) of the split's table, whose input is where the split left it.
 struct TextJob {
@@ -71,25 +91,13 @@ static int text_lines(kgpu_dict *d, const kgpu_words *words, const char *WHO, co
     if ((rc = pool_get(d, &sc))) return rc;
     constexpr int DEPTH = 4;   // chunks in flight, one pooled context each (the dictionary's shared streams run that many launches side by side)
     std::vector<uint64_t> off;
-    uint64_t lines = 0, packed = 0;
+    uint64_t lines = 0;
     const auto give_back = [&](int r) {
         sc->h2d_queued = false;
         pool_put(d, sc);
         return r;
     };
-    // ONE copy of the raw block to the device, then the split; the offsets table is sized by a guess and grown to the count the device found
-    if ((rc = sc->split_raw.ensure((size_t)len + 16)) || (rc = sc->split_text.ensure((size_t)len + 16))) return give_back(rc);
-    if (len && (rc = ctx_h2d(sc, sc->split_raw.p, text, (size_t)len, "H2D text block"))) return give_back(rc);
-    for (uint64_t cap = len / 16 + 1024;;) {
-        if ((rc = sc->split_off.ensure((size_t)cap * 8))) return give_back(rc);
-        if ((rc = enqueue_split(sc, (const uint8_t *)sc->split_raw.p, len, (uint8_t *)sc->split_text.p, (uint64_t *)sc->split_off.p, cap, WHO))) return give_back(rc);
-        rc = kgpu_ctx_sync_split(sc, &lines, &packed);
-        if (rc == KGPU_ERR_CAPACITY) { cap = lines + 1; continue; }
-        if (rc) return give_back(rc);
-        break;
-    }
-    off.resize((size_t)lines + 1);
-    if (hipMemcpy(off.data(), sc->split_off.p, (size_t)(lines + 1) * 8, hipMemcpyDeviceToHost) != hipSuccess) { set_error("%s: D2H offsets failed", WHO); return give_back(KGPU_ERR_HIP); }
+    if ((rc = split_block(sc, text, len, WHO, off, lines))) return give_back(rc);
     *n_lines = lines;
     const uint8_t *d_text = (const uint8_t *)sc->split_text.p;   // the chunks' input: pointers into the split's output
     const uint64_t *d_off = (const uint64_t *)sc->split_off.p;

@@ -58,12 +58,17 @@ extern "C" int kgpu_words_create(kgpu_dict *d, const kgpu_words_spec *spec, kgpu
     d->refs.fetch_add(1, std::memory_order_relaxed);
     w->field = sp.field; w->filter = sp.filter; w->sep = sp.separator;
     w->d_rows = dr; w->d_names = dn;
+    w->h_rows = std::move(rows); w->h_names = std::move(names);
     *out = w;
     return KGPU_OK;
 }
 
 extern "C" void kgpu_words_destroy(kgpu_words *w) {
-    if (!w) return;
+    if (w) words_release(w);
+}
+
+void kgpu::words_release(kgpu_words *w) {
+    if (w->refs.fetch_sub(1, std::memory_order_acq_rel) != 1) return;   // a counts handle still reads the tables
     kgpu_dict *d = w->dict;
     (void)hipSetDevice(d->device);
     (void)hipFree(w->d_rows);

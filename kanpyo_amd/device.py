@@ -74,6 +74,18 @@ class DeviceContext:
         _lib.check(_lib.lib().kgpu_ctx_sync_lines(self._h, C.byref(n)))
         return int(n.value)
 
+    def count_words(self, counts, d_utf8: int, d_offsets: int, n: int, d_tokens: int, d_tok_offsets: int):
+        """kgpu_count_words_device: enqueue the word counts of records a synced batch left in HBM into a WordCounts handle of this context's
+        tokenizer (Words.counter); sync_count waits for it."""
+        _lib.check(_lib.lib().kgpu_count_words_device(
+            self._h, counts.handle, C.c_void_p(d_utf8), C.c_void_p(d_offsets), n, C.c_void_p(d_tokens), C.c_void_p(d_tok_offsets)))
+
+    def sync_count(self) -> int:
+        """Wait for the enqueued count; returns the tokens it added.  KgpuError with KGPU_ERR_CAPACITY: some found no room (overflow_tokens)."""
+        n = C.c_uint64(0)
+        _lib.check(_lib.lib().kgpu_ctx_sync_count(self._h, C.byref(n)))
+        return int(n.value)
+
     def split_lines(self, d_in: int, len: int, d_out: int, d_offsets: int, offsets_capacity: int):
         """kgpu_split_lines_device: enqueue read_line + trim_end over a block in HBM -> the trimmed lines packed in d_out (len bytes suffice,
         no overlap with d_in) and their uint64 offsets in d_offsets."""

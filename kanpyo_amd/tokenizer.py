@@ -363,6 +363,95 @@ class Words:
         return [raw[int(toff[i]) : int(toff[i + 1]) - 1].decode("utf-8", "replace") for i in range(len(toff) - 1)]
 
 
+    def counter(self, table_slots=None, key_bytes=None) -> "WordCounts":
+        """A WordCounts handle with this handle's field and filter (kgpu_counts_create); None: the header's defaults."""
+        return WordCounts(self, table_slots, key_bytes)
+
+
+class WordCounts:
+    """A counts handle (kgpu_counts): the word frequencies of everything added to it, accumulated on the device by a Words handle's field and
+    filter (include/kanpyo_gpu.h, "word counts").  Any number of threads may add at once; most_common, info and reset take it alone."""
+
+    def __init__(self, words: Words, table_slots=None, key_bytes=None):
+        opts = _lib.CountsOpts(C.sizeof(_lib.CountsOpts), 0, int(table_slots or 0), int(key_bytes or 0))
+        h = C.c_void_p()
+        _lib.check(_lib.lib().kgpu_counts_create(words.handle, C.byref(opts), C.byref(h)))
+        self._h = h
+        self.words = words
+
+    @property
+    def handle(self):
+        return self._h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.lib().kgpu_counts_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add_packed(self, utf8: np.ndarray, offsets: np.ndarray) -> np.ndarray:
+        """kgpu_count_batch -> status[uint8 n].  KgpuError with KGPU_ERR_CAPACITY: some tokens found no room (info()["overflow_tokens"])."""
+        utf8 = np.ascontiguousarray(utf8, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = offsets.size - 1
+        if n < 0:
+            raise ValueError("offsets needs n+1 entries")
+        status = np.zeros(max(n, 1), dtype=np.uint8)
+        _lib.check(_lib.lib().kgpu_count_batch(self._h, utf8.ctypes.data if utf8.size else None, offsets.ctypes.data, n, status.ctypes.data))
+        return status[:n]
+
+    def add(self, sentences: Sequence) -> np.ndarray:
+        """The sentences (str or bytes) tokenized and counted -> their status bytes."""
+        return self.add_packed(*pack_sentences(sentences))
+
+    def add_text(self, block) -> np.ndarray:
+        """kgpu_count_text: a raw block of input (bytes or uint8 array), split and trimmed on the device -> one status byte per line."""
+        src = _block_bytes(block)
+        cap = src.size // 16 + 1024
+        L = _lib.lib()
+        while True:
+            status = np.zeros(cap, dtype=np.uint8)
+            n = C.c_uint64(0)
+            rc = L.kgpu_count_text(self._h, src.ctypes.data if src.size else None, src.size, status.ctypes.data, cap, C.byref(n))
+            if rc == _lib.KGPU_ERR_CAPACITY and int(n.value) > cap:   # nothing was counted: the exact size, once more
+                cap = int(n.value)
+                continue
+            _lib.check(rc)
+            return status[: int(n.value)]
+
+    def most_common(self, n=None) -> List[tuple]:
+        """kgpu_counts_read -> [(word bytes, count)], by count descending then bytes ascending; n: the first n of them."""
+        top = 0 if n is None else int(n)
+        if n is not None and top <= 0:
+            return []
+        L = _lib.lib()
+        ne, nb = C.c_uint64(0), C.c_uint64(0)
+        rc = L.kgpu_counts_read(self._h, top, None, 0, None, None, 0, C.byref(ne), C.byref(nb))
+        if rc != _lib.KGPU_ERR_CAPACITY:
+            _lib.check(rc)
+            return []
+        words = np.empty(max(int(nb.value), 1), dtype=np.uint8)
+        off = np.empty(int(ne.value) + 1, dtype=np.uint64)
+        counts = np.empty(max(int(ne.value), 1), dtype=np.uint64)
+        _lib.check(L.kgpu_counts_read(self._h, top, words.ctypes.data, words.size, off.ctypes.data, counts.ctypes.data, int(ne.value), C.byref(ne), C.byref(nb)))
+        raw, o, c = words.tobytes(), off.tolist(), counts.tolist()
+        return [(raw[o[i] : o[i + 1]], c[i]) for i in range(int(ne.value))]
+
+    def info(self) -> dict:
+        """kgpu_counts_get_info: tokens_counted, overflow_tokens, sentences, table_slots(_used), key_bytes(_used)."""
+        i = _lib.CountsInfo(C.sizeof(_lib.CountsInfo))
+        _lib.check(_lib.lib().kgpu_counts_get_info(self._h, C.byref(i)))
+        return {n: int(getattr(i, n)) for n, _ in i._fields_ if n not in ("size", "reserved")}
+
+    def reset(self):
+        _lib.check(_lib.lib().kgpu_counts_reset(self._h))
+
+
 def _block_bytes(block) -> np.ndarray:
     """A block of input (bytes-like or uint8 array) as a contiguous uint8 array."""
     return np.frombuffer(bytes(block), dtype=np.uint8) if not isinstance(block, np.ndarray) else np.ascontiguousarray(block, dtype=np.uint8)
