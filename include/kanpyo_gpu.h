@@ -542,6 +542,72 @@ int kgpu_ctx_sync_count(kgpu_ctx *c, uint64_t *n_counted);
 int kgpu_counts_read(kgpu_counts *k, uint64_t top, uint8_t *words, uint64_t words_capacity, uint64_t *word_offsets, uint64_t *counts,
                      uint64_t entries_capacity, uint64_t *n_entries, uint64_t *n_bytes);
 
+/* ---- vocabulary ids: sentences to int32 ids of a fixed word list, on the device (NOT an output of the reference: what a model's embedding
+ * layer takes) ----
+ * A vocabulary handle is made from a words handle and inherits its field and its filter; the separator plays no part.  It also takes a list
+ * of n_words words (packed: word i is words[word_offsets[i] .. word_offsets[i + 1])) and a kgpu_vocab_opts.
+ *  1. Which tokens give an id.  Exactly the tokens wakati keeps (its rules 1 and 3): EOS and dummy records never give one.
+ *  2. The word is the word of the counts section's rule 2, its sharpening included: the word of a KNOWN token with an id whose word is its
+ *     surface is THE DICTIONARY'S KEY OF THAT ID.  The key is the word's bytes (counts rule 3): encode and count agree on a word's identity.
+ *  3. The id of a word is its index in the list, as int32 (n_words <= 2^31 - 1).  A kept token whose word is not in the list gets unk_id,
+ *     which may be any int32, inside the list's range or not.  Specials such as "<pad>" are ordinary entries the caller places where they
+ *     want them; an entry no token's word can equal is not an error.  The same bytes twice in the list: KGPU_ERR_INVALID_ARG, the message
+ *     names both indices.  The empty word is a legal entry.
+ *  4. The sequence of a sentence is [bos_id] if KGPU_VOCAB_ADD_BOS, then the ids of its kept tokens in order, then [eos_id] if
+ *     KGPU_VOCAB_ADD_EOS; L(s) is its length.  A sentence with no kept token -- KGPU_SENT_INVALID_UTF8, an unreachable EOS (wakati rule 5) --
+ *     still gets its bos / eos.  The status byte is what the tokenize call reports.
+ *  5. Ragged output.  id_offsets (n + 1 entries, in ids, not bytes) is the exclusive scan of L; ids[id_offsets[s] + j] is element j of
+ *     sentence s's sequence.  The capacity protocol is kgpu_tokenize_batch_words': on KGPU_ERR_CAPACITY *n_ids is the exact count, and
+ *     nothing was written (the device form always; a host call whose input is one chunk -- up to 2 MiB and 1024 sentences -- too; a larger
+ *     host call may have delivered the chunks that fitted).
+ *  6. Padded output (the device form only, width >= 1).  d_ids is n x width: row s is the first `width` elements of the sequence, then
+ *     pad_id.  When L(s) > width and EOS was asked for, slot width - 1 holds eos_id.  id_offsets is still the exclusive scan of the
+ *     UNTRUNCATED L: the caller sees truncation and can build a mask.  A capacity below n x width is KGPU_ERR_INVALID_ARG at enqueue; the
+ *     padded form never returns KGPU_ERR_CAPACITY.
+ *  7. Bad records (wakati rule 6) make the sync return KGPU_ERR_INVALID_ARG.
+ *  8. The handle is immutable: any number of threads may use it at once.  It keeps the words handle's tables and the dictionary alive, as a
+ *     counts handle does: it may outlive both handles. */
+#define KGPU_VOCAB_ADD_BOS 1u
+#define KGPU_VOCAB_ADD_EOS 2u
+typedef struct kgpu_vocab_opts {
+    uint32_t size;     /* sizeof(kgpu_vocab_opts): fields may be appended later */
+    uint32_t flags;    /* KGPU_VOCAB_ADD_BOS | KGPU_VOCAB_ADD_EOS */
+    int32_t unk_id;
+    int32_t bos_id;    /* read only with KGPU_VOCAB_ADD_BOS */
+    int32_t eos_id;    /* read only with KGPU_VOCAB_ADD_EOS */
+} kgpu_vocab_opts;
+typedef struct kgpu_vocab_info {
+    uint32_t size;            /* in: sizeof(kgpu_vocab_info) as the caller knows it; that many bytes are written at most */
+    uint32_t reserved;
+    uint64_t n_words;
+    uint64_t table_slots;     /* slots of the byte-keyed table (16 bytes each): a power of two, at least 2 x n_words and at least 16 */
+    uint64_t key_bytes;       /* bytes of its key arena: per word its length rounded up to 8, plus 8 */
+    uint64_t rows_resolved;   /* feature rows (known and unknown morphs) whose word is in the list */
+} kgpu_vocab_info;
+typedef struct kgpu_vocab kgpu_vocab;
+/* KGPU_ERR_INVALID_ARG: a null handle, opts or out, an opts.size smaller than the struct, unknown flags, offsets that run backwards, word
+ * bytes without `words`, more than 2^31 - 1 words, the same bytes twice.  The tables are built on the host and uploaded once: 4 bytes per
+ * feature row, 16 per slot, and the key arena. */
+int kgpu_vocab_create(kgpu_words *w, const uint8_t *words, const uint64_t *word_offsets, uint64_t n_words, const kgpu_vocab_opts *opts,
+                      kgpu_vocab **out);
+void kgpu_vocab_destroy(kgpu_vocab *v);
+int kgpu_vocab_get_info(const kgpu_vocab *v, kgpu_vocab_info *info);
+/* The sentences of kgpu_tokenize_batch_words, tokenized and encoded (rule 5): ids has id_capacity entries, id_offsets n + 1, status n (may
+ * be NULL); *n_ids (may be NULL) is the ids written, or needed. */
+int kgpu_encode_batch(kgpu_vocab *v, const uint8_t *utf8, const uint64_t *offsets, uint64_t n, int32_t *ids, uint64_t id_capacity,
+                      uint64_t *id_offsets, uint8_t *status, uint64_t *n_ids);
+/* The raw block of kgpu_tokenize_text_words, split and trimmed on the device, one sequence per line; that call's protocol for the two exact
+ * sizes: id_offsets / status have offsets_capacity / offsets_capacity - 1 entries, n_lines and n_ids are required. */
+int kgpu_encode_text(kgpu_vocab *v, const uint8_t *text, uint64_t len, int32_t *ids, uint64_t id_capacity, uint64_t *id_offsets,
+                     uint64_t offsets_capacity, uint8_t *status, uint64_t *n_lines, uint64_t *n_ids);
+/* Device-resident: encode records that a synced kgpu_tokenize_device batch (or anyone) left in HBM, enqueued on c's stream.  width 0: ragged
+ * (rule 5; pad_id is ignored), else padded (rule 6).  d_ids: id_capacity entries, 4-byte aligned; d_id_offsets: n + 1.  kgpu_ctx_sync_lines
+ * waits and reports id_offsets[n].  One render, count or encode may be pending per context, whichever kind.  A context whose dictionary is not
+ * the handle's: KGPU_ERR_INVALID_ARG. */
+int kgpu_encode_device(kgpu_ctx *c, const kgpu_vocab *v, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n,
+                       const kgpu_token *d_tokens, const uint64_t *d_tok_offsets,
+                       int32_t *d_ids, uint64_t id_capacity, uint64_t width, int32_t pad_id, uint64_t *d_id_offsets);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,5 +8,6 @@ fallback, importing the tokenizer without the built library raises.
 from .token import Token, TokenClass  # noqa: F401
 from .dict import Dict  # noqa: F401
 from .tokenizer import Tokenizer, TOKEN_DTYPE  # noqa: F401
+from .vocab import Vocab  # noqa: F401
 
-__all__ = ["Token", "TokenClass", "Dict", "Tokenizer", "TOKEN_DTYPE"]
+__all__ = ["Token", "TokenClass", "Dict", "Tokenizer", "TOKEN_DTYPE", "Vocab"]

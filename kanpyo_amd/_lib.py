@@ -32,7 +32,9 @@ SYMBOLS = [
     "kgpu_words_create", "kgpu_words_destroy", "kgpu_tokenize_batch_words", "kgpu_tokenize_text_words", "kgpu_format_words_device",
     "kgpu_counts_create", "kgpu_counts_destroy", "kgpu_counts_reset", "kgpu_counts_get_info", "kgpu_count_batch", "kgpu_count_text",
     "kgpu_count_words_device", "kgpu_ctx_sync_count", "kgpu_counts_read",
+    "kgpu_vocab_create", "kgpu_vocab_destroy", "kgpu_vocab_get_info", "kgpu_encode_batch", "kgpu_encode_text", "kgpu_encode_device",
 ]
+KGPU_VOCAB_ADD_BOS, KGPU_VOCAB_ADD_EOS = 1, 2
 KGPU_COUNTS_DEFAULT_SLOTS, KGPU_COUNTS_DEFAULT_KEY_BYTES = 1 << 22, 256 << 20
 KGPU_WORDS_SURFACE = -1
 KGPU_WORDS_ALL, KGPU_WORDS_DROP, KGPU_WORDS_KEEP = 0, 1, 2
@@ -124,6 +126,15 @@ class CountsInfo(C.Structure):  # kgpu_counts_info: read with its size, fields a
                 ("table_slots", C.c_uint64), ("table_slots_used", C.c_uint64), ("key_bytes", C.c_uint64), ("key_bytes_used", C.c_uint64)]
 
 
+class VocabOpts(C.Structure):  # kgpu_vocab_opts
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("unk_id", C.c_int32), ("bos_id", C.c_int32), ("eos_id", C.c_int32)]
+
+
+class VocabInfo(C.Structure):  # kgpu_vocab_info: read with its size, fields are only ever appended
+    _fields_ = [("size", C.c_uint32), ("reserved", C.c_uint32), ("n_words", C.c_uint64), ("table_slots", C.c_uint64), ("key_bytes", C.c_uint64),
+                ("rows_resolved", C.c_uint64)]
+
+
 class Work(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("sentences", "B", "C", "T", "N", "E", "K")]
 
@@ -208,6 +219,16 @@ def lib():
         L.kgpu_count_words_device.argtypes = [vp, vp, vp, vp, C.c_uint64, vp, vp]
         L.kgpu_ctx_sync_count.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.kgpu_counts_read.argtypes = [vp, C.c_uint64, vp, C.c_uint64, vp, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.kgpu_vocab_create.argtypes = [vp, vp, vp, C.c_uint64, C.POINTER(VocabOpts), C.POINTER(vp)]
+        L.kgpu_vocab_destroy.argtypes = [vp]
+        L.kgpu_vocab_destroy.restype = None
+        L.kgpu_vocab_get_info.argtypes = [vp, C.POINTER(VocabInfo)]
+        L.kgpu_encode_batch.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, C.POINTER(C.c_uint64)]
+        L.kgpu_encode_text.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.kgpu_encode_device.argtypes = [vp, vp, vp, vp, C.c_uint64, vp, vp, vp, C.c_uint64, C.c_uint64, C.c_int32, vp]
+        L.kgpu_debug_vocab_table.argtypes = [vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.c_uint64, C.c_uint64, C.POINTER(WordsSpec), vp, vp, C.c_uint64,
+                                             C.POINTER(VocabOpts), vp, vp, C.c_uint64, C.POINTER(C.c_uint64), vp, C.c_uint64, C.POINTER(C.c_uint64),
+                                             C.POINTER(C.c_uint64)]
         L.kgpu_debug_counts_order.argtypes = [vp, vp, vp, C.c_uint64] + L.kgpu_counts_read.argtypes[1:]
         L.kgpu_debug_key_table.argtypes = [vp, C.c_size_t, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), vp]
         L.kgpu_debug_word_table.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_uint64, C.c_uint64, C.POINTER(WordsSpec), vp, vp, C.c_uint64,

@@ -26,6 +26,14 @@ the part of speech.  stdin is handled as `tokenize` handles it: blocks of whole 
 as `count\tword` lines, by count descending and then by the word's bytes ascending; --top N prints the first N.  The words and the filter are
 wakati's.  A line that is not UTF-8 ends the run with status 101, its 1-based line number on stderr and NOTHING on stdout -- a partial
 frequency table is worse than none; with --skip-invalid such lines are skipped, their numbers go to stderr and the status is 0.
+
+`python -m kanpyo_amd encode [INPUT] -c DICT --vocab FILE [--field N | --base-form | --reading | --pronunciation] [--drop POS[,POS...] | --keep POS[,POS...]]
+[--unk WORD] [--bos WORD] [--eos WORD] [--split host|device] [--skip-invalid]`: NOT a subcommand of the reference either -- every input line becomes
+one output line, the vocabulary ids of its words in decimal, separated by one space (kgpu_encode_batch / kgpu_encode_text; the decimal text is made
+on the host).  FILE has one word per line, line k (0-based) is id k: `count ... | cut -f2` makes one.  --unk (default "<unk>"), --bos and --eos name
+words that must be in the file (exit status 2 otherwise); a word outside the file gets --unk's id, --bos / --eos put theirs around every line's ids.
+The words and the filter are wakati's.  A line that is not UTF-8 is handled as `count` handles it: status 101, its line number on stderr and NOTHING
+on stdout; with --skip-invalid such a line prints its bos / eos only.
 """
 from __future__ import annotations
 
@@ -162,6 +170,53 @@ def count(args, stdin, stdout) -> int:
     return 0
 
 
+def encode(args, stdin, stdout) -> int:
+    from . import dictfile
+    from .tokenizer import Tokenizer, split_lines
+    from .vocab import Vocab
+
+    try:
+        listed = Vocab.read_words(args.vocab)
+    except OSError as e:
+        print(f"kanpyo_amd: --vocab: {e}", file=sys.stderr)
+        return 2
+    have = set(listed)
+    for opt, word in (("--unk", args.unk), ("--bos", args.bos), ("--eos", args.eos)):
+        if word is not None and os.fsencode(word) not in have:
+            print(f"kanpyo_amd: {opt} {word!r} is not a line of {args.vocab}", file=sys.stderr)
+            return 2
+    df = dictfile.load_dict(args.custom_dict or default_dict_path())
+    tok = Tokenizer(df.dict)
+    tok.set_features(df.morph_feature_table, df.unk_feature_table)
+    enc = lambda w: None if w is None else os.fsencode(w)   # noqa: E731
+    v = Vocab.from_words(tok.words(field=args.field, drop=args.drop, keep=args.keep), listed, enc(args.unk), enc(args.bos), enc(args.eos))
+    if args.input is not None:   # that one string, untrimmed
+        one = np.frombuffer(os.fsencode(args.input), dtype=np.uint8)
+        results = iter([v.encode_packed(one, np.array([0, one.size], dtype=np.uint64))])
+    elif args.split == "device":
+        results = (v.encode_text(b) for b in _blocks(stdin, args.block_bytes))
+    else:
+        results = (v.encode_packed(*split_lines(b)) for b in _blocks(stdin, args.block_bytes))
+    out = bytearray()   # (nothing is printed before the input is known to be valid, or --skip-invalid says not to care)
+    line0 = 0
+    for ids, ioff, status in results:
+        for i in np.flatnonzero(status == 1).tolist():
+            print(f"kanpyo_amd: line {line0 + i + 1}: not valid UTF-8" + (" (skipped)" if args.skip_invalid else ""), file=sys.stderr)
+            if not args.skip_invalid:
+                return PANIC_STATUS   # nothing has been printed
+        line0 += len(status)
+        o = ioff.tolist()
+        dec = ids.tolist()
+        out += "".join(" ".join(map(str, dec[o[i] : o[i + 1]])) + "\n" for i in range(len(o) - 1)).encode()
+        if args.skip_invalid:
+            stdout.write(bytes(out))
+            stdout.flush()
+            out.clear()
+    stdout.write(bytes(out))
+    stdout.flush()
+    return 0
+
+
 def _top(text: str) -> int:
     if not text.isascii() or not text.isdigit() or int(text) < 1:
         raise argparse.ArgumentTypeError(f"invalid value {text!r}: a count from 1")
@@ -233,7 +288,7 @@ def _dpi(text: str) -> int:
 
 
 def parse_args(argv=None):
-    """The reference's command line (src/bin/kanpyo.rs:14-49).  -> the namespace; .command is "tokenize" or "graphviz" -- or "wakati" or "count", which are this package's own."""
+    """The reference's command line (src/bin/kanpyo.rs:14-49).  -> the namespace; .command is "tokenize" or "graphviz" -- or "wakati", "count" or "encode", which are this package's own."""
     p = argparse.ArgumentParser(prog="kanpyo_amd", description="Japanese Morphological Analyzer (kanpyo) on AMD Instinct GPUs")
     sub = p.add_subparsers(dest="command")
     t = sub.add_parser("tokenize", help="Tokenize input text")
@@ -282,6 +337,26 @@ def parse_args(argv=None):
                    help="Where stdin's blocks are split into lines and trimmed [default: host]")
     c.add_argument("--skip-invalid", action="store_true", help="Skip lines that are not UTF-8 instead of ending with status 101")
     c.add_argument("--block-bytes", type=int, default=BLOCK_BYTES, help=argparse.SUPPRESS)
+    e = sub.add_parser("encode", help="Vocabulary ids of each input line's words (not in the reference)")
+    e.add_argument("input", nargs="?", default=None, help="Input text to analyze [default: stdin]")
+    e.add_argument("-d", "--dict", choices=["ipa"], default="ipa", help="Dictionary")
+    e.add_argument("-c", "--custom-dict", default=None, help="Custom dictionary (.dict)")
+    e.add_argument("--vocab", required=True, help="The vocabulary: one word per line, line k (0-based) is id k")
+    fld = e.add_mutually_exclusive_group()
+    fld.add_argument("--field", type=_field, default=None, help="Encode feature N of the token's row instead of the surface")
+    fld.add_argument("--base-form", dest="field", action="store_const", const=6, help="--field 6 (IPADIC)")
+    fld.add_argument("--reading", dest="field", action="store_const", const=7, help="--field 7 (IPADIC)")
+    fld.add_argument("--pronunciation", dest="field", action="store_const", const=8, help="--field 8 (IPADIC)")
+    flt = e.add_mutually_exclusive_group()
+    flt.add_argument("--drop", type=_pos_list, default=[], help="Drop tokens whose part of speech (feature 0) is one of POS[,POS...]")
+    flt.add_argument("--keep", type=_pos_list, default=[], help="Keep only tokens whose part of speech is one of POS[,POS...]")
+    e.add_argument("--unk", default="<unk>", help="The word of the vocabulary whose id a word outside it gets [default: <unk>]")
+    e.add_argument("--bos", default=None, help="A word of the vocabulary whose id goes in front of every line's ids")
+    e.add_argument("--eos", default=None, help="A word of the vocabulary whose id goes behind every line's ids")
+    e.add_argument("--split", choices=["host", "device"], default="host",
+                   help="Where stdin's blocks are split into lines and trimmed [default: host]")
+    e.add_argument("--skip-invalid", action="store_true", help="A line that is not UTF-8 prints its bos / eos only instead of ending the run with status 101")
+    e.add_argument("--block-bytes", type=int, default=BLOCK_BYTES, help=argparse.SUPPRESS)
     args = p.parse_args(argv)
     if args.command is None:   # src/bin/kanpyo.rs:173: no subcommand == tokenize from stdin, default dictionary
         args = t.parse_args([])
@@ -300,6 +375,8 @@ def main(argv=None) -> int:
             return wakati(args, sys.stdin.buffer, sys.stdout.buffer)
         if args.command == "count":
             return count(args, sys.stdin.buffer, sys.stdout.buffer)
+        if args.command == "encode":
+            return encode(args, sys.stdin.buffer, sys.stdout.buffer)
         return tokenize(args, sys.stdin.buffer, sys.stdout.buffer)
     except _lib.KgpuError as e:
         print(f"kanpyo_amd: {e}", file=sys.stderr)

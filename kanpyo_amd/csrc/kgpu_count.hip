@@ -35,26 +35,7 @@ constexpr uint32_t MAX_BLOCKS = 256; // a hot row costs one global add per workg
 constexpr uint32_t LH = 1024;        // entries of the workgroup's LDS table
 constexpr uint32_t LDS_PROBES = 8;
 
-__device__ __forceinline__ uint32_t key_hash(const uint8_t *p, uint32_t len) {   // FNV-1a over the bytes, then murmur3's finaliser
-    uint32_t h = 2166136261u;
-    for (uint32_t i = 0; i < len; ++i) h = (h ^ p[i]) * 16777619u;
-    h ^= len;
-    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
-    return h;
-}
-
-// Does the arena entry at e hold exactly these bytes?  (The entry is padded to 8 bytes: whole words are read from it, single bytes from the text.)
-__device__ __forceinline__ bool entry_equals(const uint8_t *e, uint32_t h, const uint8_t *p, uint32_t len) {
-    const uint2 head = *(const uint2 *)e;
-    if (head.x != len || head.y != h) return false;
-    for (uint32_t i = 0; i < len; i += 8) {
-        const unsigned long long v = *(const unsigned long long *)(e + COUNT_ENTRY_HEAD + i);
-        const uint32_t m = len - i < 8 ? len - i : 8;
-        for (uint32_t b = 0; b < m; ++b)
-            if ((uint32_t)((v >> (8 * b)) & 0xFFu) != p[i + b]) return false;
-    }
-    return true;
-}
+// (key_hash and entry_equals live in kgpu_words_dev.h: the vocabulary ids share them)
 
 __device__ __forceinline__ void entry_write(uint8_t *e, uint32_t h, const uint8_t *p, uint32_t len) {
     *(uint2 *)e = make_uint2(len, h);

@@ -69,16 +69,6 @@ int deliver(const char *who, const std::vector<uint8_t> &words, const std::vecto
     return KGPU_OK;
 }
 
-// The dictionary's id -> key table, built by the first read-out that needs it (the double array as the caller gave it is released then).
-void dict_key_table(kgpu_dict *d) {
-    std::lock_guard<std::mutex> g(d->keys_mu);
-    if (d->keys_built) return;
-    build_key_table(d->da_host, d->dup_host, d->info.n_morphs, d->key_bytes, d->key_off);
-    std::vector<DaNode>().swap(d->da_host);
-    std::vector<std::pair<int64_t, uint64_t>>().swap(d->dup_host);
-    d->keys_built = true;
-}
-
 int reset_device(kgpu_counts *k) {
     kgpu_dict *d = k->words->dict;
     HIPCHECK(hipSetDevice(d->device));
@@ -99,6 +89,16 @@ void free_counts(kgpu_counts *k) {
 }
 
 }  // namespace
+
+// The dictionary's id -> key table, built by the first read-out or vocabulary handle that needs it (the double array as the caller gave it is released then).
+void kgpu::dict_key_table(kgpu_dict *d) {
+    std::lock_guard<std::mutex> g(d->keys_mu);
+    if (d->keys_built) return;
+    build_key_table(d->da_host, d->dup_host, d->info.n_morphs, d->key_bytes, d->key_off);
+    std::vector<DaNode>().swap(d->da_host);
+    std::vector<std::pair<int64_t, uint64_t>>().swap(d->dup_host);
+    d->keys_built = true;
+}
 
 extern "C" int kgpu_counts_create(kgpu_words *w, const kgpu_counts_opts *opts, kgpu_counts **out) {
     const char *who = "kgpu_counts_create";

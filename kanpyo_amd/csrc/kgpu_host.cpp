@@ -4,7 +4,7 @@
 // host batch, a chunk's input block (ChunkInput) and mapped result block (ChunkBlock, shared with kgpu_multi.cpp), the output side of a
 // lines chunk (LinesChunk, shared with kgpu_split_host.cpp), the chunk sizes of the pipeline (the ring itself is run_pipeline,
 // kgpu_runtime.h), the 24-byte per-chunk fallback for tokens beyond the 8-byte record (HostJob), kgpu_tokenize_batch,
-// kgpu_tokenize_batch_lines and kgpu_tokenize_batch_words (one body: batch_lines), and kgpu_host_alloc / kgpu_host_free.
+// kgpu_tokenize_batch_lines and kgpu_tokenize_batch_words (one body, batch_lines, which kgpu_encode_batch shares), and kgpu_host_alloc / kgpu_host_free.
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
@@ -175,7 +175,8 @@ int LinesChunk::prepare(kgpu_ctx *c, uint64_t n_, uint64_t total_) {
     n = n_; total = total_;
     int rc;   // (the text block starts at 16 bytes per input byte -- cfg 2 renders about 14 -- and grows when a chunk's text outgrows it: finish)
     // (words: a surface line is at most the input's bytes and a byte per token, and a byte for the sentence; a field's names may be longer: finish grows)
-    const size_t text_guess = words ? (size_t)total * 2 + (size_t)n + 4096 : (size_t)total * 16 + 4096;
+    // (vocab: 4 bytes per kept token and bos / eos -- cfg 2 has a token per 3.6 bytes; finish grows)
+    const size_t text_guess = vocab ? ((size_t)total / 2 + (size_t)n * 2 + 1024) * 4 : words ? (size_t)total * 2 + (size_t)n + 4096 : (size_t)total * 16 + 4096;
     if ((rc = c->out_tok.ensure((size_t)token_bound(total, n) * sizeof(kgpu_token) + 64)) || (rc = c->out_status.ensure((size_t)n + 16)) ||
         (rc = c->out_off.ensure((size_t)(n + 1) * 8)) || (rc = c->lines_off.ensure((size_t)(n + 1) * 8, true)) ||
         (rc = c->lines_status.ensure((size_t)n + 16, true)) || (rc = c->lines_text.ensure(text_guess, true)))
@@ -191,6 +192,9 @@ int LinesChunk::launch(kgpu_ctx *c, const uint8_t *d_utf8_, const uint64_t *d_of
 }
 // The chunk's lines into the context's mapped blocks: text, chunk-relative text offsets, status.  The one place that chooses the renderer.
 int LinesChunk::render(kgpu_ctx *c, const char *who) const {
+    if (vocab)
+        return enqueue_encode(c, vocab, d_utf8, d_offsets, n, (const kgpu_token *)c->out_tok.p, (const uint64_t *)c->out_off.p, (int32_t *)c->lines_text.d, c->lines_text.bytes / 4,
+                              0, 0, (uint64_t *)c->lines_off.d, (const uint8_t *)c->out_status.p, (uint8_t *)c->lines_status.d, who);
     if (words)
         return enqueue_words(c, words, d_utf8, d_offsets, n, (const kgpu_token *)c->out_tok.p, (const uint64_t *)c->out_off.p, (uint8_t *)c->lines_text.d, c->lines_text.bytes,
                              (uint64_t *)c->lines_off.d, (const uint8_t *)c->out_status.p, (uint8_t *)c->lines_status.d, who);
@@ -206,17 +210,17 @@ int LinesChunk::finish(kgpu_ctx *c, uint64_t lo, LinesSink &s, const char *who) 
     int rc = kgpu_ctx_sync(c, nullptr);   // (24-byte records with capacity token_bound: never too small)
     if (rc) return rc;
     if (reruns() != r0 && (rc = render(c, who))) return rc;
-    uint64_t bytes = 0;
+    uint64_t bytes = 0;   // (elements of s.unit bytes)
     rc = kgpu_ctx_sync_lines(c, &bytes);
     if (rc == KGPU_ERR_CAPACITY) {
-        if ((rc = c->lines_text.ensure((size_t)bytes + 64, true)) || (rc = render(c, who))) return rc;
+        if ((rc = c->lines_text.ensure((size_t)(bytes * s.unit) + 64, true)) || (rc = render(c, who))) return rc;
         rc = kgpu_ctx_sync_lines(c, &bytes);
     }
     if (rc) return rc;
     if (s.text_done + bytes > s.text_capacity) s.overflow = true;
     if (!s.overflow) {
         const uint64_t *toff = (const uint64_t *)c->lines_off.h;
-        if (bytes) parallel_copy(s.text + s.text_done, c->lines_text.h, (size_t)bytes);
+        if (bytes) parallel_copy(s.text + s.text_done * s.unit, c->lines_text.h, (size_t)(bytes * s.unit));
         for (uint64_t i = 0; i <= n; ++i) s.text_offsets[lo + i] = s.text_done + toff[i];
     }
     if (s.status && n && (!s.overflow || s.status_after_overflow)) std::memcpy(s.status + lo, c->lines_status.h, (size_t)n);
@@ -391,8 +395,8 @@ struct LinesJob {
     LinesChunk out;
 };
 
-// kgpu_tokenize_batch_lines (words null) and kgpu_tokenize_batch_words: the chunks differ in their renderer alone.
-static int batch_lines(kgpu_dict *d, const kgpu_words *words, const char *who, const uint8_t *utf8, const uint64_t *offsets, uint64_t n,
+// kgpu_tokenize_batch_lines (words and vocab null), kgpu_tokenize_batch_words and kgpu_encode_batch: the chunks differ in their renderer alone.
+int kgpu::batch_lines(kgpu_dict *d, const kgpu_words *words, const kgpu_vocab *vocab, const char *who, const uint8_t *utf8, const uint64_t *offsets, uint64_t n,
                        uint8_t *text, uint64_t text_capacity, uint64_t *text_offsets, uint8_t *status, uint64_t *n_bytes) {
     if (!d || !offsets || !text_offsets || (text_capacity && !text)) { set_error("%s: null argument", who); return KGPU_ERR_INVALID_ARG; }
     int rc;
@@ -400,6 +404,7 @@ static int batch_lines(kgpu_dict *d, const kgpu_words *words, const char *who, c
     HIPCHECK(hipSetDevice(d->device));
     // (every call takes the chunk pipeline: the single-launch small-call path renders nothing)
     LinesSink sink{text, text_capacity, text_offsets, status, true};   // (status has n entries whatever the text buffer holds)
+    if (vocab) sink.unit = 4;
     text_offsets[0] = 0;
     const bool pinned_in = batch_is_pinned(utf8, offsets, n);
     rc = run_pipeline<LinesJob>(d, offsets, n, batch_depth(), 2, true, nullptr,
@@ -407,14 +412,14 @@ static int batch_lines(kgpu_dict *d, const kgpu_words *words, const char *who, c
             const uint64_t *off = offsets + j.lo;
             const uint64_t total = off[j.m] - off[0];
             int r;
-            j.out.words = words;
+            j.out.words = words; j.out.vocab = vocab;
             if ((r = j.in.prepare(j.c, j.m, total, !pinned_in)) || (r = j.out.prepare(j.c, j.m, total)) || (r = upload_input(j.c, j.in, utf8, off, pinned_in))) return r;
             return j.out.launch(j.c, j.in.d_text(j.c, off[0]), j.in.d_offsets(j.c), who);
         },
         [&](LinesJob &j) { return j.out.finish(j.c, j.lo, sink, who); });
     if (n_bytes) *n_bytes = sink.text_done;
     if (!rc && sink.overflow) {
-        set_error("text buffer too small: need %llu, capacity %llu", (unsigned long long)sink.text_done, (unsigned long long)text_capacity);
+        set_error("%s buffer too small: need %llu, capacity %llu", vocab ? "id" : "text", (unsigned long long)sink.text_done, (unsigned long long)text_capacity);
         return KGPU_ERR_CAPACITY;
     }
     return rc;
@@ -422,13 +427,13 @@ static int batch_lines(kgpu_dict *d, const kgpu_words *words, const char *who, c
 
 extern "C" int kgpu_tokenize_batch_lines(kgpu_dict *d, const uint8_t *utf8, const uint64_t *offsets, uint64_t n,
                                          uint8_t *text, uint64_t text_capacity, uint64_t *text_offsets, uint8_t *status, uint64_t *n_bytes) {
-    return batch_lines(d, nullptr, "kgpu_tokenize_batch_lines", utf8, offsets, n, text, text_capacity, text_offsets, status, n_bytes);
+    return batch_lines(d, nullptr, nullptr, "kgpu_tokenize_batch_lines", utf8, offsets, n, text, text_capacity, text_offsets, status, n_bytes);
 }
 
 extern "C" int kgpu_tokenize_batch_words(kgpu_words *w, const uint8_t *utf8, const uint64_t *offsets, uint64_t n,
                                          uint8_t *text, uint64_t text_capacity, uint64_t *text_offsets, uint8_t *status, uint64_t *n_bytes) {
     if (!w) { set_error("kgpu_tokenize_batch_words: null argument"); return KGPU_ERR_INVALID_ARG; }
-    return batch_lines(w->dict, w, "kgpu_tokenize_batch_words", utf8, offsets, n, text, text_capacity, text_offsets, status, n_bytes);
+    return batch_lines(w->dict, w, nullptr, "kgpu_tokenize_batch_words", utf8, offsets, n, text, text_capacity, text_offsets, status, n_bytes);
 }
 
 // Pinned, device-visible host memory for the buffers of kgpu_tokenize_batch: the copies then run as DMA

@@ -5,6 +5,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -200,6 +201,36 @@ struct CountsArgs {
 };
 uint32_t count_blocks(uint64_t n);   // workgroups of the count launch
 int launch_count_words(const CountsArgs &a, void *stream);
+// The vocabulary ids of a batch (kgpu_encode.hip; include/kanpyo_gpu.h, "vocabulary ids"): every kept token gives one int32, the index of its word in a
+// vocabulary handle's list.  A row-determined word (the count kernel's predicate) is one load from `row_id`; every other word is looked up in a frozen
+// byte-keyed table of the counts table's layout (slots of {tag, id}, arena entries of {length, hash, bytes}).
+struct alignas(16) VocabSlot { unsigned long long tag; int32_t id; uint32_t pad[2]; };   // tag: 0 = free, else hash << 32 | (arena entry's offset / 8 + 1)
+constexpr uint32_t VOCAB_BOS = 1u, VOCAB_EOS = 2u;   // KGPU_VOCAB_ADD_BOS / _EOS
+struct EncodeArgs {
+    WordsArgs w;                     // the batch and the handle's word table; sent_len: n + 1 lengths then offsets, in ids; text_offsets: the caller's id_offsets; text / text_cap unused
+    const int32_t *row_id;           // w.n_rows entries: the id of the row's word (unk_id when it is not listed)
+    const VocabSlot *slots; uint32_t slot_mask;   // a power of two of slots, load <= 0.5
+    const uint8_t *arena;
+    int32_t unk_id, bos_id, eos_id, pad_id;
+    uint32_t flags;                  // VOCAB_BOS | VOCAB_EOS
+    int32_t *ids; uint64_t id_cap;
+    uint64_t width;                  // 0: ragged; else the padded form's row length
+};
+int launch_encode(const EncodeArgs &a, void *stream);
+// kgpu_vocab_table.cpp (HIP-free, compiles alone): a vocabulary handle's two tables from the word table's rows, the dictionary's id -> key table and the list.
+struct VocabTables {
+    std::vector<int32_t> row_id;
+    std::vector<VocabSlot> slots;
+    std::vector<uint8_t> arena;
+    uint64_t rows_resolved = 0;      // feature rows whose word is in the list
+};
+uint32_t vocab_key_hash(const uint8_t *p, uint64_t len);   // key_hash of kgpu_words_dev.h, restated for the host
+// -> the id of these bytes in the table, or `unk`
+int32_t vocab_find(const VocabTables &t, const uint8_t *p, uint64_t len, int32_t unk);
+// KGPU_OK, or KGPU_ERR_INVALID_ARG with `err` saying why (the same bytes twice in the list: both indices).  key_bytes / key_off: build_key_table's (may be
+// null when no known row's word is its surface).
+int build_vocab_table(const WordRow *rows, size_t n_rows, size_t n_known, const uint8_t *names, const uint8_t *key_bytes, const uint64_t *key_off,
+                      const uint8_t *words, const uint64_t *word_offsets, uint64_t n_words, int32_t unk_id, VocabTables &out, std::string &err);
 // The DOT documents of a batch's kept lattices (kgpu_graphviz.hip; reference src/graphviz.rs:30-163).
 struct GraphvizArgs {
     const uint8_t *utf8;           // as BatchArgs::utf8 / offsets of the launch that kept the lattices

@@ -1,6 +1,6 @@
 // kanpyo_amd/csrc/kgpu_runtime.h -- the host runtime's own types and the functions its files share: kgpu_dict.cpp (dictionary),
 // kgpu_ctx.cpp (contexts, launch chain), kgpu_host.cpp (large host calls), kgpu_small.cpp (small calls), kgpu_multi.cpp (the
-// multi-device entry points), kgpu_split_host.cpp (lines of a raw block), kgpu_graphviz_host.cpp (DOT documents of a batch), kgpu_words_host.cpp (wakati), kgpu_count_host.cpp (word counts).  Not part of the public ABI.
+// multi-device entry points), kgpu_split_host.cpp (lines of a raw block), kgpu_graphviz_host.cpp (DOT documents of a batch), kgpu_words_host.cpp (wakati), kgpu_count_host.cpp (word counts), kgpu_encode_host.cpp (vocabulary ids).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -146,6 +146,15 @@ struct kgpu_counts {
     uint64_t cached_version = 0;
     std::vector<uint8_t> cached_words;
     std::vector<uint64_t> cached_off, cached_counts;
+};
+
+// A vocabulary handle (kgpu_encode_host.cpp): a frozen word -> id table on the device, by a words handle's field and filter.  Immutable.
+struct kgpu_vocab {
+    kgpu_words *words = nullptr;        // holds a reference (its tables and, through it, the dictionary)
+    uint32_t flags = 0;
+    int32_t unk_id = 0, bos_id = 0, eos_id = 0;
+    uint64_t n_words = 0, table_slots = 0, key_bytes = 0, rows_resolved = 0;
+    void *d_row_id = nullptr, *d_slots = nullptr, *d_arena = nullptr;
 };
 
 struct kgpu_ctx {
@@ -297,6 +306,10 @@ int build_word_table(const uint8_t *known, size_t known_len, const uint8_t *unk,
 
 // kgpu_words_host.cpp
 void words_release(kgpu_words *w);   // one reference less: the last one frees the tables and lets go of the dictionary
+// kgpu_encode_host.cpp: the vocabulary ids of a batch's records on c->stream (waited for by kgpu_ctx_sync_lines, which reports the ids); width 0: ragged
+int enqueue_encode(kgpu_ctx *c, const kgpu_vocab *v, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n, const kgpu_token *d_tokens, const uint64_t *d_tok_offsets,
+                   int32_t *d_ids, uint64_t id_capacity, uint64_t width, int32_t pad_id, uint64_t *d_id_offsets, const uint8_t *status_in, uint8_t *status_out, const char *who);
+void dict_key_table(kgpu_dict *d);   // kgpu_count_host.cpp: the dictionary's id -> key table (d->key_bytes, d->key_off), built by the first caller that needs it
 // kgpu_count_host.cpp: the count of a batch's records on c->stream behind whatever is queued there (waited for by kgpu_ctx_sync_count)
 int enqueue_count(kgpu_ctx *c, kgpu_counts *k, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n, const kgpu_token *d_tokens, const uint64_t *d_tok_offsets,
                   const uint8_t *status_in, uint8_t *status_out, const char *who);
@@ -345,12 +358,14 @@ struct LinesSink {
     bool status_after_overflow;
     uint64_t text_done = 0;
     bool overflow = false;
+    uint64_t unit = 1;   // bytes per element of `text`: 1, or 4 where the chunks deliver vocabulary ids (capacities, text_done and the offsets count elements)
 };
 // The output side of one chunk of a lines or words call (kgpu_tokenize_batch_lines / _words, kgpu_tokenize_text_lines / _words) on a pooled context, whatever put its input on the
 // device: the 24-byte records stay in HBM (c->out_tok) and the render behind the chain writes the chunk's text, chunk-relative text offsets and status
 // into c's mapped lines_* blocks.
 struct LinesChunk {
     const kgpu_words *words = nullptr;                     // the words calls: render chooses the wakati renderer; null: the `kanpyo tokenize` lines
+    const kgpu_vocab *vocab = nullptr;                     // the encode calls: render chooses the vocabulary ids; the chunk's output block is counted in 4-byte units
     uint64_t n = 0, total = 0;                             // sentences, bytes
     const uint8_t *d_utf8 = nullptr;                       // the chunk's input in device memory (launch)
     const uint64_t *d_offsets = nullptr;
@@ -359,6 +374,13 @@ struct LinesChunk {
     int render(kgpu_ctx *c, const char *who) const;                       // the render of the chunk's records alone
     int finish(kgpu_ctx *c, uint64_t lo, LinesSink &sink, const char *who) const;   // wait, and deliver behind what the sink holds: sentences [lo, lo + n) of the call
 };
+
+// kgpu_host.cpp / kgpu_split_host.cpp: the bodies of the lines, words and encode host calls (words, vocab: at most one is set; vocab: `text` holds int32 ids
+// and text_capacity, *n_bytes and the offsets count ids)
+int batch_lines(kgpu_dict *d, const kgpu_words *words, const kgpu_vocab *vocab, const char *who, const uint8_t *utf8, const uint64_t *offsets, uint64_t n,
+                uint8_t *text, uint64_t text_capacity, uint64_t *text_offsets, uint8_t *status, uint64_t *n_bytes);
+int text_lines(kgpu_dict *d, const kgpu_words *words, const kgpu_vocab *vocab, const char *who, const uint8_t *text, uint64_t len, uint8_t *out_text, uint64_t text_capacity,
+               uint64_t *text_offsets, uint64_t offsets_capacity, uint8_t *status, uint64_t *n_lines, uint64_t *n_bytes);
 
 // The chunks of a large host call: at most `bytes` / `sents` each (test_hooks() may lower them).
 struct ChunkLimits { uint64_t bytes, sents; };

@@ -78,8 +78,8 @@ struct TextJob {
     LinesChunk out;
 };
 
-// kgpu_tokenize_text_lines (words null) and kgpu_tokenize_text_words: the chunks differ in their renderer alone.
-static int text_lines(kgpu_dict *d, const kgpu_words *words, const char *WHO, const uint8_t *text, uint64_t len, uint8_t *out_text, uint64_t text_capacity,
+// kgpu_tokenize_text_lines (words and vocab null), kgpu_tokenize_text_words and kgpu_encode_text: the chunks differ in their renderer alone.
+int kgpu::text_lines(kgpu_dict *d, const kgpu_words *words, const kgpu_vocab *vocab, const char *WHO, const uint8_t *text, uint64_t len, uint8_t *out_text, uint64_t text_capacity,
                       uint64_t *text_offsets, uint64_t offsets_capacity, uint8_t *status, uint64_t *n_lines, uint64_t *n_bytes) {
     if (!d || (len && !text) || (text_capacity && !out_text) || (offsets_capacity && !text_offsets) || !n_lines || !n_bytes) { set_error("%s: null argument", WHO); return KGPU_ERR_INVALID_ARG; }
     *n_lines = 0; *n_bytes = 0;
@@ -102,11 +102,12 @@ static int text_lines(kgpu_dict *d, const kgpu_words *words, const char *WHO, co
     const uint8_t *d_text = (const uint8_t *)sc->split_text.p;   // the chunks' input: pointers into the split's output
     const uint64_t *d_off = (const uint64_t *)sc->split_off.p;
     LinesSink sink{out_text, text_capacity, text_offsets, status, false};   // (status is bounded by offsets_capacity: nothing of it after an overflow)
+    if (vocab) sink.unit = 4;
     sink.overflow = lines + 1 > offsets_capacity;
     if (!sink.overflow) text_offsets[0] = 0;
     rc = run_pipeline<TextJob>(d, off.data(), lines, DEPTH, 0, false, nullptr,
         [&](TextJob &j) {
-            j.out.words = words;
+            j.out.words = words; j.out.vocab = vocab;
             const int r = j.out.prepare(j.c, j.m, off[j.lo + j.m] - off[j.lo]);
             return r ? r : j.out.launch(j.c, d_text, d_off + j.lo, WHO);
         },
@@ -123,11 +124,11 @@ static int text_lines(kgpu_dict *d, const kgpu_words *words, const char *WHO, co
 
 extern "C" int kgpu_tokenize_text_lines(kgpu_dict *d, const uint8_t *text, uint64_t len, uint8_t *out_text, uint64_t text_capacity, uint64_t *text_offsets,
                                         uint64_t offsets_capacity, uint8_t *status, uint64_t *n_lines, uint64_t *n_bytes) {
-    return text_lines(d, nullptr, "kgpu_tokenize_text_lines", text, len, out_text, text_capacity, text_offsets, offsets_capacity, status, n_lines, n_bytes);
+    return text_lines(d, nullptr, nullptr, "kgpu_tokenize_text_lines", text, len, out_text, text_capacity, text_offsets, offsets_capacity, status, n_lines, n_bytes);
 }
 
 extern "C" int kgpu_tokenize_text_words(kgpu_words *w, const uint8_t *text, uint64_t len, uint8_t *out_text, uint64_t text_capacity, uint64_t *text_offsets,
                                         uint64_t offsets_capacity, uint8_t *status, uint64_t *n_lines, uint64_t *n_bytes) {
     if (!w) { set_error("kgpu_tokenize_text_words: null argument"); return KGPU_ERR_INVALID_ARG; }
-    return text_lines(w->dict, w, "kgpu_tokenize_text_words", text, len, out_text, text_capacity, text_offsets, offsets_capacity, status, n_lines, n_bytes);
+    return text_lines(w->dict, w, nullptr, "kgpu_tokenize_text_words", text, len, out_text, text_capacity, text_offsets, offsets_capacity, status, n_lines, n_bytes);
 }

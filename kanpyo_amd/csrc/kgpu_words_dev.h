@@ -1,4 +1,4 @@
-// kanpyo_amd/csrc/kgpu_words_dev.h -- device code shared by the wakati render (kgpu_words.hip) and the word counts (kgpu_count.hip): one token's
+// kanpyo_amd/csrc/kgpu_words_dev.h -- device code shared by the wakati render (kgpu_words.hip), the word counts (kgpu_count.hip) and the vocabulary ids (kgpu_encode.hip): one token's
 // word by the rules of include/kanpyo_gpu.h, "wakati-gaki" (field, fallback to the surface and the filter are decided per row by
 // kgpu_words_host.cpp's entries; the record's range check is line_of's, kgpu_format.hip).
 #pragma once
@@ -28,6 +28,28 @@ __device__ __forceinline__ Word word_of(const WordsArgs &a, const kgpu_token &t,
     }
     if (!w.ok) w = Word{0, 0, true, false, false};
     return w;
+}
+
+// The byte-keyed tables of the word counts and the vocabulary ids (kgpu_count.hip, kgpu_encode.hip): a key's hash and the compare with an arena entry.
+__device__ __forceinline__ uint32_t key_hash(const uint8_t *p, uint32_t len) {   // FNV-1a over the bytes, then murmur3's finaliser
+    uint32_t h = 2166136261u;
+    for (uint32_t i = 0; i < len; ++i) h = (h ^ p[i]) * 16777619u;
+    h ^= len;
+    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
+    return h;
+}
+
+// Does the arena entry at e hold exactly these bytes?  (The entry is padded to 8 bytes: whole words are read from it, single bytes from the text.)
+__device__ __forceinline__ bool entry_equals(const uint8_t *e, uint32_t h, const uint8_t *p, uint32_t len) {
+    const uint2 head = *(const uint2 *)e;
+    if (head.x != len || head.y != h) return false;
+    for (uint32_t i = 0; i < len; i += 8) {
+        const unsigned long long v = *(const unsigned long long *)(e + COUNT_ENTRY_HEAD + i);
+        const uint32_t m = len - i < 8 ? len - i : 8;
+        for (uint32_t b = 0; b < m; ++b)
+            if ((uint32_t)((v >> (8 * b)) & 0xFFu) != p[i + b]) return false;
+    }
+    return true;
 }
 
 }  // namespace dev

@@ -69,7 +69,7 @@ class DeviceContext:
             text_capacity, C.c_void_p(d_text_offsets)))
 
     def sync_lines(self) -> int:
-        """Wait for the enqueued render (lines or words); returns its byte count."""
+        """Wait for the enqueued render (lines or words) or encode; returns its byte count, or the encode's id count."""
         n = C.c_uint64(0)
         _lib.check(_lib.lib().kgpu_ctx_sync_lines(self._h, C.byref(n)))
         return int(n.value)
@@ -85,6 +85,16 @@ class DeviceContext:
         n = C.c_uint64(0)
         _lib.check(_lib.lib().kgpu_ctx_sync_count(self._h, C.byref(n)))
         return int(n.value)
+
+    def encode(self, vocab, d_utf8: int, d_offsets: int, n: int, d_tokens: int, d_tok_offsets: int, d_ids: int, id_capacity: int, d_id_offsets: int,
+               width: int = 0, pad_id: int = 0):
+        """kgpu_encode_device: enqueue the vocabulary ids (int32) of records a synced batch left in HBM, by a Vocab of this context's tokenizer.
+        width 0: ragged, d_ids holds the sequences back to back; width w: padded, d_ids is n x w (id_capacity >= n * w), rows cut after w
+        elements and filled with pad_id.  d_id_offsets: n + 1 uint64, the exclusive scan of the untruncated lengths.  sync_lines waits for it
+        and returns d_id_offsets[n]."""
+        _lib.check(_lib.lib().kgpu_encode_device(
+            self._h, vocab.handle, C.c_void_p(d_utf8), C.c_void_p(d_offsets), n, C.c_void_p(d_tokens), C.c_void_p(d_tok_offsets), C.c_void_p(d_ids),
+            id_capacity, width, pad_id, C.c_void_p(d_id_offsets)))
 
     def split_lines(self, d_in: int, len: int, d_out: int, d_offsets: int, offsets_capacity: int):
         """kgpu_split_lines_device: enqueue read_line + trim_end over a block in HBM -> the trimmed lines packed in d_out (len bytes suffice,

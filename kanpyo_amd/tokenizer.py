@@ -367,6 +367,13 @@ class Words:
         """A WordCounts handle with this handle's field and filter (kgpu_counts_create); None: the header's defaults."""
         return WordCounts(self, table_slots, key_bytes)
 
+    def vocabulary(self, words, unk_id: int, bos_id=None, eos_id=None) -> "Vocab":
+        """kgpu_vocab_create: a Vocab with this handle's field and filter.  words: the list (str or bytes), id k is words[k]; a kept token whose
+        word is not listed gets unk_id (any int32); bos_id / eos_id: None, or the id put in front of / behind every sentence's ids."""
+        from .vocab import Vocab
+
+        return Vocab(self, words, unk_id, bos_id, eos_id)
+
 
 class WordCounts:
     """A counts handle (kgpu_counts): the word frequencies of everything added to it, accumulated on the device by a Words handle's field and
@@ -450,6 +457,19 @@ class WordCounts:
 
     def reset(self):
         _lib.check(_lib.lib().kgpu_counts_reset(self._h))
+
+    def vocabulary(self, max_size=None, min_count=1, specials=("<pad>", "<unk>"), unk="<unk>", bos=None, eos=None) -> "Vocab":
+        """A Vocab chosen from these counts: specials + [w for w, c in most_common() if c >= min_count][:max_size - len(specials)], words equal
+        to a special dropped from the tail.  unk, bos, eos: words of the list (put them among the specials) whose indices become unk_id, bos_id,
+        eos_id; bos / eos None: not added.  Vocab.words keeps the list."""
+        from .vocab import Vocab
+
+        head = [w.encode("utf-8") if isinstance(w, str) else bytes(w) for w in specials]
+        taken = set(head)
+        tail = [w for w, c in self.most_common() if c >= min_count and w not in taken]
+        if max_size is not None:
+            tail = tail[: max(int(max_size) - len(head), 0)]
+        return Vocab.from_words(self.words, head + tail, unk, bos, eos)
 
 
 def _block_bytes(block) -> np.ndarray:
