@@ -3,7 +3,7 @@
 // returns to the host.
 //
 // Two launches on the context's stream:
-//   k_count_words    one wavefront per sentence, 64 records at a time; a record's word is word_of's (kgpu_words_dev.h), range-checked as the renders do.
+//   k_count_words    one wavefront per sentence, 64 records at a time; the walk, the record check and a record's word are the renders' (kgpu_records_dev.h).
 //       ROW-DETERMINED words (a known token with a row; a pool name) are counted per feature row.  Natural text puts a large share of its tokens on a few
 //       particles, and one word of global memory takes about 90 atomic operations per microsecond chip-wide (kgpu_device.h, above WorkIO): the workgroup
 //       sums in LDS first -- a table of LH entries keyed by the row, claimed with a compare-and-swap, summed with LDS adds -- and adds every distinct row
@@ -18,11 +18,7 @@
 //       No lane ever waits for another: every loop is bounded by the table's size.  A word that finds no slot or no arena space is counted in the
 //       handle's overflow tokens.  Bytes are hashed and compared one at a time from wherever they lie: any alignment, any length, nothing read past them.
 //   k_count_publish  one workgroup: the launch's per-workgroup totals summed into the handle's words and published to the host.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-
-#include "kgpu_words_dev.h"
+#include "kgpu_records_dev.h"
 
 namespace kgpu {
 
@@ -34,8 +30,6 @@ constexpr uint32_t WPB = 8;          // wavefronts per workgroup (one sentence e
 constexpr uint32_t MAX_BLOCKS = 256; // a hot row costs one global add per workgroup: few, large workgroups
 constexpr uint32_t LH = 1024;        // entries of the workgroup's LDS table
 constexpr uint32_t LDS_PROBES = 8;
-
-// (key_hash and entry_equals live in kgpu_words_dev.h: the vocabulary ids share them)
 
 __device__ __forceinline__ void entry_write(uint8_t *e, uint32_t h, const uint8_t *p, uint32_t len) {
     *(uint2 *)e = make_uint2(len, h);
@@ -93,29 +87,24 @@ __global__ __launch_bounds__(64 * WPB) void k_count_words(CountsArgs a) {
     for (uint32_t i = threadIdx.x; i < LH; i += blockDim.x) { hk[i] = 0; hc[i] = 0; }
     if (threadIdx.x < COUNT_PARTIAL_WORDS) tot[threadIdx.x] = 0;
     __syncthreads();
-    const WordsArgs &w = a.w;
     const uint32_t lane = threadIdx.x & 63;
-    const uint64_t wave = (uint64_t)blockIdx.x * WPB + (threadIdx.x >> 6), nwaves = (uint64_t)gridDim.x * WPB;
-    uint64_t cnt = 0, ovf = 0;
-    uint32_t claimed = 0;
-    bool bad = false;
-    for (uint64_t s = wave; s < w.n; s += nwaves) {
-        const uint64_t k0 = w.tok_offsets[s], k1 = w.tok_offsets[s + 1];
-        const uint32_t B = (uint32_t)(w.offsets[s + 1] - w.offsets[s]);
-        const uint8_t *text = w.utf8 + w.offsets[s];
-        bad |= k1 < k0;
-        if (lane == 0 && w.status_out) w.status_out[s] = w.status_in[s];
+    uint64_t cnt_all = 0, ovf_all = 0;
+    uint32_t claimed_all = 0;
+    const bool anybad = walk_sentences<WPB, true>(a.b, [&](uint64_t, uint64_t k0, uint64_t k1, uint32_t B, const uint8_t *text) {
+        uint64_t cnt = 0, ovf = 0;   // (the sentence's own: tallies captured by reference would live in scratch memory)
+        uint32_t claimed = 0;
+        bool bad = false;
         for (uint64_t kw = k0; kw < k1; kw += 64) {   // (wave-uniform)
             Word wd{0, 0, true, false, true};
             kgpu_token t{};
-            if (kw + lane < k1) { t = w.tokens[kw + lane]; wd = word_of(w, t, B); }
+            if (kw + lane < k1) { t = a.b.tokens[kw + lane]; wd = word_of(a.b, a.w, t, B); }
             bad |= !wd.ok;
             bool need = false;
             uint32_t h = 0, i = 0, probes = 0;
             const uint8_t *p = text + wd.src;
             if (wd.kept) {
-                if (t.id != 0 && (t.cls == KGPU_CLASS_KNOWN || !wd.from_text)) {   // row-determined (word_of has checked the id)
-                    lds_add(hk, hc, a.dense, (t.cls == KGPU_CLASS_KNOWN ? 0u : w.n_morph) + (uint32_t)t.id - 1);
+                if (row_determined(t, wd)) {
+                    lds_add(hk, hc, a.dense, feature_row(t.cls == KGPU_CLASS_KNOWN, a.b.n_morph, (uint32_t)t.id));
                     ++cnt;
                 } else {
                     h = key_hash(p, wd.len);
@@ -149,11 +138,10 @@ __global__ __launch_bounds__(64 * WPB) void k_count_words(CountsArgs a) {
                 }
             }
         }
-    }
-    cnt = wave_sum64(cnt);
-    ovf = wave_sum64(ovf);
-    const uint64_t cl = wave_sum64((uint64_t)claimed);
-    const bool anybad = __ballot(bad) != 0;
+        cnt_all += cnt; ovf_all += ovf; claimed_all += claimed;
+        return bad;
+    });
+    const uint64_t cnt = wave_sum64(cnt_all), ovf = wave_sum64(ovf_all), cl = wave_sum64((uint64_t)claimed_all);
     if (lane == 0) {
         if (cnt) atomicAdd(&tot[0], (unsigned long long)cnt);
         if (ovf) atomicAdd(&tot[1], (unsigned long long)ovf);
@@ -163,7 +151,7 @@ __global__ __launch_bounds__(64 * WPB) void k_count_words(CountsArgs a) {
     __syncthreads();
     for (uint32_t e = threadIdx.x; e < LH; e += blockDim.x)
         if (hk[e] != 0) atomicAdd(&a.dense[hk[e] - 1], hc[e]);   // every distinct row of the workgroup: once
-    if (threadIdx.x < COUNT_PARTIAL_WORDS) a.partial[(uint64_t)blockIdx.x * COUNT_PARTIAL_WORDS + threadIdx.x] = tot[threadIdx.x];
+    if (threadIdx.x < COUNT_PARTIAL_WORDS) a.b.sent_len[(uint64_t)blockIdx.x * COUNT_PARTIAL_WORDS + threadIdx.x] = tot[threadIdx.x];
 }
 
 __global__ __launch_bounds__(256) void k_count_publish(CountsArgs a, uint32_t blocks) {
@@ -171,7 +159,7 @@ __global__ __launch_bounds__(256) void k_count_publish(CountsArgs a, uint32_t bl
     if (threadIdx.x < COUNT_PARTIAL_WORDS) sum[threadIdx.x] = 0;
     __syncthreads();
     for (uint32_t k = threadIdx.x; k < blocks * COUNT_PARTIAL_WORDS; k += blockDim.x) {
-        const unsigned long long v = a.partial[k];
+        const unsigned long long v = a.b.sent_len[k];
         if (v) atomicAdd(&sum[k % COUNT_PARTIAL_WORDS], v);
     }
     __syncthreads();
@@ -179,8 +167,8 @@ __global__ __launch_bounds__(256) void k_count_publish(CountsArgs a, uint32_t bl
         if (sum[3]) atomicAdd(&a.stats[1], sum[3]);
         if (sum[0]) atomicAdd(&a.stats[2], sum[0]);
         if (sum[1]) atomicAdd(&a.stats[3], sum[1]);
-        __hip_atomic_store(&a.host_ctl[0], sum[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(&a.host_ctl[1], (sum[2] ? 1ull : 0ull) | (sum[1] ? 2ull : 0ull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(&a.b.host_ctl[0], sum[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(&a.b.host_ctl[1], (sum[2] ? 1ull : 0ull) | (sum[1] ? 2ull : 0ull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
 
@@ -188,7 +176,7 @@ uint32_t count_blocks(uint64_t n) { return (uint32_t)std::max<uint64_t>(1, std::
 
 int launch_count_words(const CountsArgs &a, void *stream) {
     const hipStream_t st = (hipStream_t)stream;
-    const uint32_t blocks = count_blocks(a.w.n);
+    const uint32_t blocks = count_blocks(a.b.n);
     hipLaunchKernelGGL(k_count_words, dim3(blocks), dim3(64 * WPB), 0, st, a);
     hipLaunchKernelGGL(k_count_publish, dim3(1), dim3(256), 0, st, a, blocks);
     return (int)hipGetLastError();

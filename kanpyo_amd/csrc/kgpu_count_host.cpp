@@ -163,31 +163,19 @@ extern "C" int kgpu_counts_get_info(kgpu_counts *k, kgpu_counts_info *info) {
 }
 
 // ---- the count of a batch's records on a context ---------------------------------------------------------------------------------------------
-int kgpu::enqueue_count(kgpu_ctx *c, kgpu_counts *k, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n, const kgpu_token *d_tokens,
-                        const uint64_t *d_tok_offsets, const uint8_t *status_in, uint8_t *status_out, const char *who) {
-    kgpu_dict *d = c->dict;
-    const kgpu_words *w = k->words;
-    if (w->dict != d) { set_error("%s: the context's dictionary is not the counts handle's", who); return KGPU_ERR_INVALID_ARG; }
-    int rc;
-    // (the renders' per-sentence scratch holds the launch's per-workgroup totals: one render or count is pending per context)
-    if ((rc = c->lines_report.arm()) || (rc = c->lines_len.ensure((size_t)count_blocks(n) * COUNT_PARTIAL_WORDS * 8))) return rc;
+int kgpu::enqueue_count(kgpu_ctx *c, kgpu_counts *k, const DeviceRecords &r, const char *who) {
+    if (k->words->dict != c->dict) { set_error("%s: the context's dictionary is not the counts handle's", who); return KGPU_ERR_INVALID_ARG; }
     CountsArgs a{};
-    a.w.utf8 = d_utf8; a.w.offsets = d_offsets; a.w.n = n; a.w.tokens = d_tokens; a.w.tok_offsets = d_tok_offsets;
-    a.w.rows = (const WordRow *)w->d_rows; a.w.names = (const uint8_t *)w->d_names;
-    a.w.n_morph = (uint32_t)d->info.n_morphs; a.w.n_rows = (uint32_t)(d->info.n_morphs + d->info.n_unk_morphs);
-    a.w.sep = w->sep; a.w.drop_rowless = w->filter == KGPU_WORDS_KEEP;
-    a.w.status_in = status_in; a.w.status_out = status_out;
+    // (the renders' per-sentence scratch holds the launch's per-workgroup totals: one render or count is pending per context)
+    if (int rc = records_batch(c, r, (size_t)count_blocks(r.n) * COUNT_PARTIAL_WORDS * 8, nullptr, a.b)) return rc;
+    a.w = word_table(k->words);
     a.dense = (unsigned long long *)k->d_dense;
     a.slots = (CountSlot *)k->d_slots; a.slot_mask = (uint32_t)(k->table_slots - 1);
     a.arena = (uint8_t *)k->d_arena; a.arena_bytes = k->key_bytes;
     a.stats = (unsigned long long *)k->d_stats;
-    a.partial = (unsigned long long *)c->lines_len.p;
-    a.host_ctl = c->lines_report.dev();
     k->version.fetch_add(1, std::memory_order_acq_rel);
-    k->sentences.fetch_add(n, std::memory_order_relaxed);
-    const hipError_t e = (hipError_t)launch_count_words(a, c->stream);
-    if (e != hipSuccess) { set_error("%s: count launch: %s", who, hipGetErrorString(e)); return KGPU_ERR_HIP; }
-    return c->lines_report.record(c->stream, ~0ull);
+    k->sentences.fetch_add(r.n, std::memory_order_relaxed);
+    return records_launched(c, launch_count_words(a, c->stream), who, "count", ~0ull);
 }
 
 extern "C" int kgpu_count_words_device(kgpu_ctx *c, kgpu_counts *k, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n,
@@ -195,11 +183,8 @@ extern "C" int kgpu_count_words_device(kgpu_ctx *c, kgpu_counts *k, const uint8_
     const char *who = "kgpu_count_words_device";
     if (!c || !k || !d_offsets || !d_tok_offsets || (n && (!d_utf8 || !d_tokens))) { set_error("%s: null argument", who); return KGPU_ERR_INVALID_ARG; }
     if (k->words->dict != c->dict) { set_error("%s: the context's dictionary is not the counts handle's", who); return KGPU_ERR_INVALID_ARG; }
-    if (c->pending) { set_error("%s: the context's tokenize batch is not synced (kgpu_ctx_sync) yet", who); return KGPU_ERR_INVALID_ARG; }
-    HIPCHECK(hipSetDevice(c->dict->device));
-    int rc;
-    if (c->lines_report.pending && (rc = kgpu_ctx_sync_lines(c, nullptr)) != KGPU_OK && rc != KGPU_ERR_CAPACITY) return rc;
-    return enqueue_count(c, k, d_utf8, d_offsets, n, d_tokens, d_tok_offsets, nullptr, nullptr, who);
+    if (int rc = begin_records_call(c, who)) return rc;
+    return enqueue_count(c, k, DeviceRecords{d_utf8, d_offsets, n, d_tokens, d_tok_offsets, nullptr, nullptr}, who);
 }
 
 extern "C" int kgpu_ctx_sync_count(kgpu_ctx *c, uint64_t *n_counted) {
@@ -247,9 +232,8 @@ struct CountChunk {
     int finish(kgpu_ctx *c, kgpu_counts *k, uint64_t lo, uint8_t *status, bool &overflow, const char *who) const {
         int rc = kgpu_ctx_sync(c, nullptr);   // (24-byte records with capacity token_bound: never too small)
         if (rc) return rc;
-        if ((rc = enqueue_count(c, k, d_utf8, d_offsets, n, (const kgpu_token *)c->out_tok.p, (const uint64_t *)c->out_off.p, (const uint8_t *)c->out_status.p,
-                                (uint8_t *)c->lines_status.d, who)))
-            return rc;
+        const DeviceRecords r{d_utf8, d_offsets, n, (const kgpu_token *)c->out_tok.p, (const uint64_t *)c->out_off.p, (const uint8_t *)c->out_status.p, (uint8_t *)c->lines_status.d};
+        if ((rc = enqueue_count(c, k, r, who))) return rc;
         rc = kgpu_ctx_sync_count(c, nullptr);
         if (rc == KGPU_ERR_CAPACITY) { overflow = true; rc = KGPU_OK; }
         if (rc) return rc;

@@ -453,22 +453,33 @@ int kgpu::require_features(kgpu_dict *d, const char *who) {
     if (!d->feat) { set_error("%s: the dictionary has no feature tables: call kgpu_dict_set_features first", who); return KGPU_ERR_INVALID_ARG; }
     return KGPU_OK;
 }
-int kgpu::enqueue_lines(kgpu_ctx *c, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n, const kgpu_token *d_tokens, const uint64_t *d_tok_offsets,
-                        uint8_t *d_text, uint64_t text_capacity, uint64_t *d_text_offsets, const uint8_t *status_in, uint8_t *status_out, const char *who) {
-    kgpu_dict *d = c->dict;
+int kgpu::begin_records_call(kgpu_ctx *c, const char *who) {
+    if (c->pending) { set_error("%s: the context's tokenize batch is not synced (kgpu_ctx_sync) yet", who); return KGPU_ERR_INVALID_ARG; }
+    HIPCHECK(hipSetDevice(c->dict->device));
     int rc;
-    if ((rc = require_features(d, who)) || (rc = c->lines_report.arm()) || (rc = c->lines_len.ensure((size_t)n * 8 + 8))) return rc;
+    if (c->lines_report.pending && (rc = kgpu_ctx_sync_lines(c, nullptr)) != KGPU_OK && rc != KGPU_ERR_CAPACITY) return rc;
+    return KGPU_OK;
+}
+int kgpu::records_batch(kgpu_ctx *c, const DeviceRecords &r, size_t scratch_bytes, uint64_t *d_unit_offsets, RecordsBatch &b) {
+    int rc;
+    if ((rc = c->lines_report.arm()) || (rc = c->lines_len.ensure(scratch_bytes))) return rc;
+    const kgpu_dict_info &di = c->dict->info;
+    b = RecordsBatch{r.d_utf8, r.d_offsets, r.n, r.d_tokens, r.d_tok_offsets, (uint32_t)di.n_morphs, (uint32_t)(di.n_morphs + di.n_unk_morphs),
+                     (uint64_t *)c->lines_len.p, d_unit_offsets, r.status_in, r.status_out, c->lines_report.dev()};
+    return KGPU_OK;
+}
+int kgpu::records_launched(kgpu_ctx *c, int launch_error, const char *who, const char *what, uint64_t capacity) {
+    if (launch_error != (int)hipSuccess) { set_error("%s: %s launch: %s", who, what, hipGetErrorString((hipError_t)launch_error)); return KGPU_ERR_HIP; }
+    return c->lines_report.record(c->stream, capacity);
+}
+int kgpu::enqueue_lines(kgpu_ctx *c, const DeviceRecords &r, uint8_t *d_text, uint64_t text_capacity, uint64_t *d_text_offsets, const char *who) {
+    kgpu_dict *d = c->dict;
     LinesArgs a{};
-    a.utf8 = d_utf8; a.offsets = d_offsets; a.n = n; a.tokens = d_tokens; a.tok_offsets = d_tok_offsets;
+    int rc;
+    if ((rc = require_features(d, who)) || (rc = records_batch(c, r, (size_t)r.n * 8 + 8, d_text_offsets, a.b))) return rc;
     a.feat = d->feat; a.feat_off = d->feat_off;
-    a.n_morph = (uint32_t)d->info.n_morphs; a.n_rows = (uint32_t)(d->info.n_morphs + d->info.n_unk_morphs);
-    a.sent_len = (uint64_t *)c->lines_len.p;
-    a.text = d_text; a.text_cap = text_capacity; a.text_offsets = d_text_offsets;
-    a.status_in = status_in; a.status_out = status_out;
-    a.host_ctl = c->lines_report.dev();
-    const hipError_t e = (hipError_t)launch_format_lines(a, c->stream);
-    if (e != hipSuccess) { set_error("%s: render launch: %s", who, hipGetErrorString(e)); return KGPU_ERR_HIP; }
-    return c->lines_report.record(c->stream, text_capacity);
+    a.text = d_text; a.text_cap = text_capacity;
+    return records_launched(c, launch_format_lines(a, c->stream), who, "render", text_capacity);
 }
 
 extern "C" int kgpu_format_lines_device(kgpu_ctx *c, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n,
@@ -479,11 +490,8 @@ extern "C" int kgpu_format_lines_device(kgpu_ctx *c, const uint8_t *d_utf8, cons
         set_error("%s: null argument", who);
         return KGPU_ERR_INVALID_ARG;
     }
-    if (c->pending) { set_error("%s: the context's tokenize batch is not synced (kgpu_ctx_sync) yet", who); return KGPU_ERR_INVALID_ARG; }
-    HIPCHECK(hipSetDevice(c->dict->device));
-    int rc;
-    if (c->lines_report.pending && (rc = kgpu_ctx_sync_lines(c, nullptr)) != KGPU_OK && rc != KGPU_ERR_CAPACITY) return rc;
-    return enqueue_lines(c, d_utf8, d_offsets, n, d_tokens, d_tok_offsets, d_text, text_capacity, d_text_offsets, nullptr, nullptr, who);
+    if (int rc = begin_records_call(c, who)) return rc;
+    return enqueue_lines(c, DeviceRecords{d_utf8, d_offsets, n, d_tokens, d_tok_offsets, nullptr, nullptr}, d_text, text_capacity, d_text_offsets, who);
 }
 
 extern "C" int kgpu_ctx_sync_lines(kgpu_ctx *c, uint64_t *n_bytes) {

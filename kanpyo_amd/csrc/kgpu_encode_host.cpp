@@ -101,36 +101,23 @@ extern "C" int kgpu_vocab_get_info(const kgpu_vocab *v, kgpu_vocab_info *info) {
 }
 
 // ---- the encode of a batch's records on a context --------------------------------------------------------------------------------------------
-int kgpu::enqueue_encode(kgpu_ctx *c, const kgpu_vocab *v, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n, const kgpu_token *d_tokens,
-                         const uint64_t *d_tok_offsets, int32_t *d_ids, uint64_t id_capacity, uint64_t width, int32_t pad_id, uint64_t *d_id_offsets,
-                         const uint8_t *status_in, uint8_t *status_out, const char *who) {
-    kgpu_dict *d = c->dict;
-    const kgpu_words *w = v->words;
-    if (w->dict != d) { set_error("%s: the context's dictionary is not the vocabulary handle's", who); return KGPU_ERR_INVALID_ARG; }
-    if (width && (n > ~0ull / width || id_capacity < n * width)) {
-        set_error("%s: id capacity %llu, the padded form needs n x width = %llu x %llu", who, (unsigned long long)id_capacity, (unsigned long long)n, (unsigned long long)width);
+int kgpu::enqueue_encode(kgpu_ctx *c, const kgpu_vocab *v, const DeviceRecords &r, int32_t *d_ids, uint64_t id_capacity, uint64_t width, int32_t pad_id,
+                         uint64_t *d_id_offsets, const char *who) {
+    if (v->words->dict != c->dict) { set_error("%s: the context's dictionary is not the vocabulary handle's", who); return KGPU_ERR_INVALID_ARG; }
+    if (width && (r.n > ~0ull / width || id_capacity < r.n * width)) {
+        set_error("%s: id capacity %llu, the padded form needs n x width = %llu x %llu", who, (unsigned long long)id_capacity, (unsigned long long)r.n, (unsigned long long)width);
         return KGPU_ERR_INVALID_ARG;
     }
-    int rc;
-    if ((rc = c->lines_report.arm()) || (rc = c->lines_len.ensure((size_t)n * 8 + 8))) return rc;
     EncodeArgs a{};
-    a.w.utf8 = d_utf8; a.w.offsets = d_offsets; a.w.n = n; a.w.tokens = d_tokens; a.w.tok_offsets = d_tok_offsets;
-    a.w.rows = (const WordRow *)w->d_rows; a.w.names = (const uint8_t *)w->d_names;
-    a.w.n_morph = (uint32_t)d->info.n_morphs; a.w.n_rows = (uint32_t)(d->info.n_morphs + d->info.n_unk_morphs);
-    a.w.sep = w->sep; a.w.drop_rowless = w->filter == KGPU_WORDS_KEEP;
-    a.w.sent_len = (uint64_t *)c->lines_len.p;
-    a.w.text_offsets = d_id_offsets;
-    a.w.status_in = status_in; a.w.status_out = status_out;
-    a.w.host_ctl = c->lines_report.dev();
+    if (int rc = records_batch(c, r, (size_t)r.n * 8 + 8, d_id_offsets, a.b)) return rc;
+    a.w = word_table(v->words);
     a.row_id = (const int32_t *)v->d_row_id;
     a.slots = (const VocabSlot *)v->d_slots; a.slot_mask = (uint32_t)(v->table_slots - 1);
     a.arena = (const uint8_t *)v->d_arena;
     a.unk_id = v->unk_id; a.bos_id = v->bos_id; a.eos_id = v->eos_id; a.pad_id = pad_id;
     a.flags = v->flags;
     a.ids = d_ids; a.id_cap = id_capacity; a.width = width;
-    const hipError_t e = (hipError_t)launch_encode(a, c->stream);
-    if (e != hipSuccess) { set_error("%s: encode launch: %s", who, hipGetErrorString(e)); return KGPU_ERR_HIP; }
-    return c->lines_report.record(c->stream, width ? ~0ull : id_capacity);   // (the padded form never reports KGPU_ERR_CAPACITY)
+    return records_launched(c, launch_encode(a, c->stream), who, "encode", width ? ~0ull : id_capacity);   // (the padded form never reports KGPU_ERR_CAPACITY)
 }
 
 extern "C" int kgpu_encode_device(kgpu_ctx *c, const kgpu_vocab *v, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n,
@@ -143,11 +130,8 @@ extern "C" int kgpu_encode_device(kgpu_ctx *c, const kgpu_vocab *v, const uint8_
     }
     if ((uintptr_t)d_ids & 3u) { set_error("%s: d_ids is not 4-byte aligned", who); return KGPU_ERR_INVALID_ARG; }
     if (v->words->dict != c->dict) { set_error("%s: the context's dictionary is not the vocabulary handle's", who); return KGPU_ERR_INVALID_ARG; }
-    if (c->pending) { set_error("%s: the context's tokenize batch is not synced (kgpu_ctx_sync) yet", who); return KGPU_ERR_INVALID_ARG; }
-    HIPCHECK(hipSetDevice(c->dict->device));
-    int rc;
-    if (c->lines_report.pending && (rc = kgpu_ctx_sync_lines(c, nullptr)) != KGPU_OK && rc != KGPU_ERR_CAPACITY) return rc;
-    return enqueue_encode(c, v, d_utf8, d_offsets, n, d_tokens, d_tok_offsets, d_ids, id_capacity, width, pad_id, d_id_offsets, nullptr, nullptr, who);
+    if (int rc = begin_records_call(c, who)) return rc;
+    return enqueue_encode(c, v, DeviceRecords{d_utf8, d_offsets, n, d_tokens, d_tok_offsets, nullptr, nullptr}, d_ids, id_capacity, width, pad_id, d_id_offsets, who);
 }
 
 // ---- the host calls: the lines calls' bodies with the chunks' renderer set to the encode --------------------------------------------------------

@@ -166,7 +166,7 @@ __device__ void put_node(S &o, const GraphvizArgs &a, const Lat &l, uint32_t vid
         const uint32_t b0 = l.cbyte[se.x], b1 = l.cbyte[se.y];
         o.mem(l.text + b0, b1 - b0);
         o.ch('\n');
-        const uint32_t row = sid > 0 ? (uint32_t)sid - 1 : a.n_morph + (uint32_t)(-sid) - 1;
+        const uint32_t row = feature_row(sid > 0, a.n_morph, (uint32_t)(sid > 0 ? sid : -sid));
         const uint32_t f0 = a.label_off[row], f1 = a.label_off[row + 1];
         o.mem(a.label + f0, f1 - f0);
         o.ch('\n');

@@ -192,14 +192,12 @@ int LinesChunk::launch(kgpu_ctx *c, const uint8_t *d_utf8_, const uint64_t *d_of
 }
 // The chunk's lines into the context's mapped blocks: text, chunk-relative text offsets, status.  The one place that chooses the renderer.
 int LinesChunk::render(kgpu_ctx *c, const char *who) const {
-    if (vocab)
-        return enqueue_encode(c, vocab, d_utf8, d_offsets, n, (const kgpu_token *)c->out_tok.p, (const uint64_t *)c->out_off.p, (int32_t *)c->lines_text.d, c->lines_text.bytes / 4,
-                              0, 0, (uint64_t *)c->lines_off.d, (const uint8_t *)c->out_status.p, (uint8_t *)c->lines_status.d, who);
-    if (words)
-        return enqueue_words(c, words, d_utf8, d_offsets, n, (const kgpu_token *)c->out_tok.p, (const uint64_t *)c->out_off.p, (uint8_t *)c->lines_text.d, c->lines_text.bytes,
-                             (uint64_t *)c->lines_off.d, (const uint8_t *)c->out_status.p, (uint8_t *)c->lines_status.d, who);
-    return enqueue_lines(c, d_utf8, d_offsets, n, (const kgpu_token *)c->out_tok.p, (const uint64_t *)c->out_off.p, (uint8_t *)c->lines_text.d, c->lines_text.bytes,
-                         (uint64_t *)c->lines_off.d, (const uint8_t *)c->out_status.p, (uint8_t *)c->lines_status.d, who);
+    const DeviceRecords r{d_utf8, d_offsets, n, (const kgpu_token *)c->out_tok.p, (const uint64_t *)c->out_off.p, (const uint8_t *)c->out_status.p, (uint8_t *)c->lines_status.d};
+    uint8_t *out = (uint8_t *)c->lines_text.d;
+    uint64_t *off = (uint64_t *)c->lines_off.d;
+    if (vocab) return enqueue_encode(c, vocab, r, (int32_t *)out, c->lines_text.bytes / 4, 0, 0, off, who);
+    if (words) return enqueue_words(c, words, r, out, c->lines_text.bytes, off, who);
+    return enqueue_lines(c, r, out, c->lines_text.bytes, off, who);
 }
 // Wait for the chunk's render (its text is in the context's mapped block then) and copy the text behind the bytes already delivered (or only count,
 // once a buffer of the caller's has overflowed).  A rerun of the chunk's chain inside kgpu_ctx_sync came after the render queued behind the first

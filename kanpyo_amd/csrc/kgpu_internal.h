@@ -143,42 +143,44 @@ int launch_general_only(const DictView &d, const BatchArgs &a, void *stream);  /
 int launch_general_keep(const DictView &d, const BatchArgs &a, void *stream);  // kgpu_graphviz_batch: ... over a whole batch, a.keep_lattice set
 int launch_small_call(const DictView &d, const BatchArgs &a, void *stream);  // pool kernel alone, one sentence per wavefront
 int launch_scan_compact(const BatchArgs &a, Control *host_ctl, void *stream, bool small_workgroups);  // host_ctl: device pointer of the pinned result block
-// The CLI's output lines of a batch (kgpu_format.hip; reference src/bin/kanpyo.rs:174-197): `surface \t f1,f2,... \n` per token.
-struct LinesArgs {
+// What every consumer of a batch's 24-byte records reads (kgpu_records_dev.h: the lines, the wakati lines, the vocabulary ids, the word counts).
+constexpr uint32_t feature_row(bool known, uint32_t n_morph, uint32_t id) { return (known ? 0u : n_morph) + id - 1; }   // known id k at row k - 1, unknown id u at n_morph + u - 1
+struct RecordsBatch {
     const uint8_t *utf8;           // the batch's text, biased like BatchArgs::utf8: sentence s is utf8[offsets[s] .. offsets[s + 1])
     const uint64_t *offsets;       // n + 1
     uint64_t n;
     const kgpu_token *tokens;      // sentence s's records: tokens[tok_offsets[s] .. tok_offsets[s + 1])
     const uint64_t *tok_offsets;   // n + 1
-    const uint8_t *feat;           // the dictionary's joined feature strings (kgpu_features.cpp) ...
-    const uint32_t *feat_off;      // ... row r is feat[feat_off[r] .. feat_off[r + 1]); known id k at row k - 1, unknown id u at n_morph + u - 1
-    uint32_t n_morph, n_rows;      // rows = known + unknown morphs
-    uint64_t *sent_len;            // device scratch, n + 1: each sentence's rendered bytes, then (k_lines_scan, in place) their offsets
-    uint8_t *text; uint64_t text_cap;
+    uint32_t n_morph, n_rows;      // feature rows = known + unknown morphs (feature_row)
+    uint64_t *sent_len;            // device scratch, n + 1: each sentence's rendered units (bytes, ids), then (k_lines_scan, in place) their offsets
     uint64_t *text_offsets;        // n + 1: the scan's mirror for the caller (may be mapped host memory: the write pass reads sent_len)
-    const uint8_t *status_in;      // optional: mirrored into status_out (mapped host memory) by the length pass
+    const uint8_t *status_in;      // optional: mirrored into status_out (mapped host memory) by the first pass
     uint8_t *status_out;
-    unsigned long long *host_ctl;  // device pointer of pinned, mapped words: [0] total bytes, [1] a record out of range
+    unsigned long long *host_ctl;  // device pointer of pinned, mapped words: [0] total units, [1] a record out of range (the count: HostReport, kgpu_count.hip)
+};
+void launch_lines_scan(const RecordsBatch &b, void *stream);   // k_lines_scan alone (kgpu_format.hip): every render's second launch
+// The CLI's output lines of a batch (kgpu_format.hip; reference src/bin/kanpyo.rs:174-197): `surface \t f1,f2,... \n` per token.
+struct LinesArgs {
+    RecordsBatch b;
+    const uint8_t *feat;           // the dictionary's joined feature strings (kgpu_features.cpp) ...
+    const uint32_t *feat_off;      // ... row r is feat[feat_off[r] .. feat_off[r + 1])
+    uint8_t *text; uint64_t text_cap;
 };
 int launch_format_lines(const LinesArgs &a, void *stream);
-void launch_lines_scan(const LinesArgs &a, void *stream);   // k_lines_scan alone (n, sent_len, text_offsets, host_ctl): the words render's second launch
-// The wakati lines of a batch (kgpu_words.hip): per sentence the words of its kept tokens joined by `sep`, then '\n'.
-// One entry per feature row, in the records' index space (LinesArgs::feat_off): where the row's word lies and whether its tokens are kept.
+// A words handle's table.  One entry per feature row (feature_row): where the row's word lies and whether its tokens are kept.
 struct WordRow { uint32_t off, len_flags; };                 // names[off .. off + len); len_flags = len | WORD_SURFACE | WORD_DROPPED
 constexpr uint32_t WORD_SURFACE = 1u << 30, WORD_DROPPED = 1u << 31, WORD_LEN_MASK = WORD_SURFACE - 1;
-struct WordsArgs {
-    const uint8_t *utf8; const uint64_t *offsets; uint64_t n;           // as LinesArgs
-    const kgpu_token *tokens; const uint64_t *tok_offsets;
-    const WordRow *rows;           // n_rows entries: known id k at row k - 1, unknown id u at n_morph + u - 1
+struct WordTable {
+    const WordRow *rows;           // n_rows entries
     const uint8_t *names;          // the pool of distinct names the entries point into
-    uint32_t n_morph, n_rows;
     uint32_t sep;                  // the separator byte
     uint32_t drop_rowless;         // KGPU_WORDS_KEEP: a token without a row (id 0) is dropped
-    uint64_t *sent_len;            // as LinesArgs: n + 1, lengths then offsets
+};
+// The wakati lines of a batch (kgpu_words.hip): per sentence the words of its kept tokens joined by `sep`, then '\n'.
+struct WordsArgs {
+    RecordsBatch b;
+    WordTable w;
     uint8_t *text; uint64_t text_cap;
-    uint64_t *text_offsets;
-    const uint8_t *status_in; uint8_t *status_out;
-    unsigned long long *host_ctl;  // [0] total bytes, [1] a record out of range
 };
 int launch_format_words(const WordsArgs &a, void *stream);
 // The word counts of a batch (kgpu_count.hip; include/kanpyo_gpu.h, "word counts"): every kept token adds one to its word's counter in a counts handle.
@@ -191,13 +193,13 @@ constexpr uint32_t COUNT_ENTRY_HEAD = 8;
 constexpr uint32_t COUNT_PARTIAL_WORDS = 4;   // per workgroup of the count launch: tokens counted, tokens that found no room, a bad record, slots claimed
 constexpr uint32_t COUNT_STAT_WORDS = 8;      // the handle's device words: [0] arena cursor (bytes; may run past the capacity), [1] slots used, [2] tokens counted, [3] overflow tokens
 struct CountsArgs {
-    WordsArgs w;                     // the batch and the handle's word table (utf8 .. drop_rowless; status_in / status_out as the renders mirror them; the rest unused)
-    unsigned long long *dense;       // w.n_rows counters
+    RecordsBatch b;                  // sent_len: the launch's per-workgroup totals, COUNT_PARTIAL_WORDS per workgroup (count_blocks), summed by the publishing kernel;
+                                     // host_ctl: [0] tokens this launch counted, [1] bit 0: a record out of range, bit 1: a token found no room; text_offsets unused
+    WordTable w;
+    unsigned long long *dense;       // b.n_rows counters
     CountSlot *slots; uint32_t slot_mask;   // a power of two of slots
     uint8_t *arena; uint64_t arena_bytes;
     unsigned long long *stats;       // COUNT_STAT_WORDS
-    unsigned long long *partial;     // device scratch of the launch: COUNT_PARTIAL_WORDS per workgroup (count_blocks), summed by the publishing kernel
-    unsigned long long *host_ctl;    // [0] tokens this launch counted, [1] bit 0: a record out of range, bit 1: a token found no room
 };
 uint32_t count_blocks(uint64_t n);   // workgroups of the count launch
 int launch_count_words(const CountsArgs &a, void *stream);
@@ -207,8 +209,9 @@ int launch_count_words(const CountsArgs &a, void *stream);
 struct alignas(16) VocabSlot { unsigned long long tag; int32_t id; uint32_t pad[2]; };   // tag: 0 = free, else hash << 32 | (arena entry's offset / 8 + 1)
 constexpr uint32_t VOCAB_BOS = 1u, VOCAB_EOS = 2u;   // KGPU_VOCAB_ADD_BOS / _EOS
 struct EncodeArgs {
-    WordsArgs w;                     // the batch and the handle's word table; sent_len: n + 1 lengths then offsets, in ids; text_offsets: the caller's id_offsets; text / text_cap unused
-    const int32_t *row_id;           // w.n_rows entries: the id of the row's word (unk_id when it is not listed)
+    RecordsBatch b;                  // the units are ids; text_offsets: the caller's id_offsets
+    WordTable w;
+    const int32_t *row_id;           // b.n_rows entries: the id of the row's word (unk_id when it is not listed)
     const VocabSlot *slots; uint32_t slot_mask;   // a power of two of slots, load <= 0.5
     const uint8_t *arena;
     int32_t unk_id, bos_id, eos_id, pad_id;
@@ -224,7 +227,7 @@ struct VocabTables {
     std::vector<uint8_t> arena;
     uint64_t rows_resolved = 0;      // feature rows whose word is in the list
 };
-uint32_t vocab_key_hash(const uint8_t *p, uint64_t len);   // key_hash of kgpu_words_dev.h, restated for the host
+uint32_t vocab_key_hash(const uint8_t *p, uint64_t len);   // key_hash of kgpu_records_dev.h, restated for the host
 // -> the id of these bytes in the table, or `unk`
 int32_t vocab_find(const VocabTables &t, const uint8_t *p, uint64_t len, int32_t unk);
 // KGPU_OK, or KGPU_ERR_INVALID_ARG with `err` saying why (the same bytes twice in the list: both indices).  key_bytes / key_off: build_key_table's (may be
@@ -239,7 +242,7 @@ struct GraphvizArgs {
     uint8_t *arena;                // the arena the descriptors' offsets are relative to
     unsigned long long *desc;      // BatchArgs::lat_desc; the prepare pass stores a sentence's visible node count in word 7
     const int16_t *conn; uint32_t conn_rows;   // DictView::conn: the ids in the slabs index it as they are
-    const uint8_t *label;          // the label pool (kgpu_features.cpp): row r is label[label_off[r] .. label_off[r + 1]), rows as LinesArgs::feat
+    const uint8_t *label;          // the label pool (kgpu_features.cpp): row r is label[label_off[r] .. label_off[r + 1]), rows as LinesArgs::feat (feature_row)
     const uint32_t *label_off;
     uint32_t n_morph;
     uint32_t full_state;

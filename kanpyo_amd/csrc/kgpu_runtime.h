@@ -1,5 +1,5 @@
 // kanpyo_amd/csrc/kgpu_runtime.h -- the host runtime's own types and the functions its files share: kgpu_dict.cpp (dictionary),
-// kgpu_ctx.cpp (contexts, launch chain), kgpu_host.cpp (large host calls), kgpu_small.cpp (small calls), kgpu_multi.cpp (the
+// kgpu_ctx.cpp (contexts, launch chain, the shared head and tail of the four record consumers' enqueues), kgpu_host.cpp (large host calls), kgpu_small.cpp (small calls), kgpu_multi.cpp (the
 // multi-device entry points), kgpu_split_host.cpp (lines of a raw block), kgpu_graphviz_host.cpp (DOT documents of a batch), kgpu_words_host.cpp (wakati), kgpu_count_host.cpp (word counts), kgpu_encode_host.cpp (vocabulary ids).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -293,13 +293,22 @@ int ctx_h2d(kgpu_ctx *c, void *dst, const void *src, size_t bytes, const char *w
 int tokenize_device_impl(kgpu_ctx *c, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n, uint64_t total_bytes,
                          kgpu_token *d_tokens, kgpu_token8 *d_tokens8, uint32_t *d_first, uint8_t *status8, uint64_t *toff8, uint64_t token_capacity,
                          uint64_t *d_tok_offsets, uint8_t *d_status, const char *who);
-// the render of a batch's lines on c->stream behind whatever is queued there; status_in / status_out: optional mirror of the status bytes
-int enqueue_lines(kgpu_ctx *c, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n, const kgpu_token *d_tokens, const uint64_t *d_tok_offsets,
-                  uint8_t *d_text, uint64_t text_capacity, uint64_t *d_text_offsets, const uint8_t *status_in, uint8_t *status_out, const char *who);
-
-// ... and of its wakati lines (kgpu_words_host.cpp over kgpu_words.hip); waited for by kgpu_ctx_sync_lines as well
-int enqueue_words(kgpu_ctx *c, const kgpu_words *w, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n, const kgpu_token *d_tokens, const uint64_t *d_tok_offsets,
-                  uint8_t *d_text, uint64_t text_capacity, uint64_t *d_text_offsets, const uint8_t *status_in, uint8_t *status_out, const char *who);
+// A batch's records where they lie in device memory, with the optional mirror of its status bytes (status_out: mapped host memory): what the
+// four consumers below are given.  Each runs on c->stream behind whatever is queued there, with the context's lines_report and lines_len: one is pending per context.
+struct DeviceRecords {
+    const uint8_t *d_utf8; const uint64_t *d_offsets; uint64_t n; const kgpu_token *d_tokens; const uint64_t *d_tok_offsets;
+    const uint8_t *status_in; uint8_t *status_out;
+};
+// The device entry points' shared preamble: the context's tokenize batch is synced, its device is current, a pending report is waited for (KGPU_ERR_CAPACITY passes).
+int begin_records_call(kgpu_ctx *c, const char *who);
+// An enqueue's head: the report armed, lines_len of scratch_bytes at least, `b` filled from r and the context (unit_offsets: RecordsBatch::text_offsets) ...
+int records_batch(kgpu_ctx *c, const DeviceRecords &r, size_t scratch_bytes, uint64_t *d_unit_offsets, RecordsBatch &b);
+// ... and its tail: a launch error (hipError_t) becomes "<who>: <what> launch: ..."; else the report is recorded with the capacity the sync compares with
+int records_launched(kgpu_ctx *c, int launch_error, const char *who, const char *what, uint64_t capacity);
+WordTable word_table(const kgpu_words *w);   // kgpu_words_host.cpp
+int enqueue_lines(kgpu_ctx *c, const DeviceRecords &r, uint8_t *d_text, uint64_t text_capacity, uint64_t *d_text_offsets, const char *who);
+// ... its wakati lines (kgpu_words_host.cpp over kgpu_words.hip); waited for by kgpu_ctx_sync_lines as well
+int enqueue_words(kgpu_ctx *c, const kgpu_words *w, const DeviceRecords &r, uint8_t *d_text, uint64_t text_capacity, uint64_t *d_text_offsets, const char *who);
 // kgpu_features.cpp: the per-row entries (known rows, then unknown rows) and the pool of distinct names of a checked spec, from the two blobs
 int build_word_table(const uint8_t *known, size_t known_len, const uint8_t *unk, size_t unk_len, uint64_t n_morphs, uint64_t n_unk,
                      const kgpu_words_spec &spec, std::vector<WordRow> &rows, std::vector<uint8_t> &names);
@@ -307,12 +316,10 @@ int build_word_table(const uint8_t *known, size_t known_len, const uint8_t *unk,
 // kgpu_words_host.cpp
 void words_release(kgpu_words *w);   // one reference less: the last one frees the tables and lets go of the dictionary
 // kgpu_encode_host.cpp: the vocabulary ids of a batch's records on c->stream (waited for by kgpu_ctx_sync_lines, which reports the ids); width 0: ragged
-int enqueue_encode(kgpu_ctx *c, const kgpu_vocab *v, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n, const kgpu_token *d_tokens, const uint64_t *d_tok_offsets,
-                   int32_t *d_ids, uint64_t id_capacity, uint64_t width, int32_t pad_id, uint64_t *d_id_offsets, const uint8_t *status_in, uint8_t *status_out, const char *who);
+int enqueue_encode(kgpu_ctx *c, const kgpu_vocab *v, const DeviceRecords &r, int32_t *d_ids, uint64_t id_capacity, uint64_t width, int32_t pad_id, uint64_t *d_id_offsets, const char *who);
 void dict_key_table(kgpu_dict *d);   // kgpu_count_host.cpp: the dictionary's id -> key table (d->key_bytes, d->key_off), built by the first caller that needs it
 // kgpu_count_host.cpp: the count of a batch's records on c->stream behind whatever is queued there (waited for by kgpu_ctx_sync_count)
-int enqueue_count(kgpu_ctx *c, kgpu_counts *k, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n, const kgpu_token *d_tokens, const uint64_t *d_tok_offsets,
-                  const uint8_t *status_in, uint8_t *status_out, const char *who);
+int enqueue_count(kgpu_ctx *c, kgpu_counts *k, const DeviceRecords &r, const char *who);
 
 int require_features(kgpu_dict *d, const char *who);   // KGPU_ERR_INVALID_ARG unless kgpu_dict_set_features has been called
 int ensure_label_pool(kgpu_dict *d);                   // kgpu_features.cpp: the graphviz label pool on the device (first call uploads it)

@@ -13,7 +13,7 @@
 
 namespace kgpu {
 
-// FNV-1a over the bytes, then murmur3's finaliser with the length folded in: key_hash of kgpu_words_dev.h, restated.
+// FNV-1a over the bytes, then murmur3's finaliser with the length folded in: key_hash of kgpu_records_dev.h, restated.
 uint32_t vocab_key_hash(const uint8_t *p, uint64_t len) {
     uint32_t h = 2166136261u;
     for (uint64_t i = 0; i < len; ++i) h = (h ^ p[i]) * 16777619u;

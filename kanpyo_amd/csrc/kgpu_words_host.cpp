@@ -85,25 +85,17 @@ void kgpu::words_release(kgpu_words *w) {
     dict_release(d);
 }
 
-int kgpu::enqueue_words(kgpu_ctx *c, const kgpu_words *w, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n, const kgpu_token *d_tokens,
-                        const uint64_t *d_tok_offsets, uint8_t *d_text, uint64_t text_capacity, uint64_t *d_text_offsets, const uint8_t *status_in,
-                        uint8_t *status_out, const char *who) {
-    kgpu_dict *d = c->dict;
-    if (w->dict != d) { set_error("%s: the context's dictionary is not the words handle's", who); return KGPU_ERR_INVALID_ARG; }
-    int rc;
-    if ((rc = c->lines_report.arm()) || (rc = c->lines_len.ensure((size_t)n * 8 + 8))) return rc;
+WordTable kgpu::word_table(const kgpu_words *w) {
+    return WordTable{(const WordRow *)w->d_rows, (const uint8_t *)w->d_names, w->sep, w->filter == KGPU_WORDS_KEEP};
+}
+
+int kgpu::enqueue_words(kgpu_ctx *c, const kgpu_words *w, const DeviceRecords &r, uint8_t *d_text, uint64_t text_capacity, uint64_t *d_text_offsets, const char *who) {
+    if (w->dict != c->dict) { set_error("%s: the context's dictionary is not the words handle's", who); return KGPU_ERR_INVALID_ARG; }
     WordsArgs a{};
-    a.utf8 = d_utf8; a.offsets = d_offsets; a.n = n; a.tokens = d_tokens; a.tok_offsets = d_tok_offsets;
-    a.rows = (const WordRow *)w->d_rows; a.names = (const uint8_t *)w->d_names;
-    a.n_morph = (uint32_t)d->info.n_morphs; a.n_rows = (uint32_t)(d->info.n_morphs + d->info.n_unk_morphs);
-    a.sep = w->sep; a.drop_rowless = w->filter == KGPU_WORDS_KEEP;
-    a.sent_len = (uint64_t *)c->lines_len.p;
-    a.text = d_text; a.text_cap = text_capacity; a.text_offsets = d_text_offsets;
-    a.status_in = status_in; a.status_out = status_out;
-    a.host_ctl = c->lines_report.dev();
-    const hipError_t e = (hipError_t)launch_format_words(a, c->stream);
-    if (e != hipSuccess) { set_error("%s: render launch: %s", who, hipGetErrorString(e)); return KGPU_ERR_HIP; }
-    return c->lines_report.record(c->stream, text_capacity);
+    if (int rc = records_batch(c, r, (size_t)r.n * 8 + 8, d_text_offsets, a.b)) return rc;
+    a.w = word_table(w);
+    a.text = d_text; a.text_cap = text_capacity;
+    return records_launched(c, launch_format_words(a, c->stream), who, "render", text_capacity);
 }
 
 extern "C" int kgpu_format_words_device(kgpu_ctx *c, const kgpu_words *w, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n,
@@ -115,11 +107,8 @@ extern "C" int kgpu_format_words_device(kgpu_ctx *c, const kgpu_words *w, const 
         return KGPU_ERR_INVALID_ARG;
     }
     if (w->dict != c->dict) { set_error("%s: the context's dictionary is not the words handle's", who); return KGPU_ERR_INVALID_ARG; }
-    if (c->pending) { set_error("%s: the context's tokenize batch is not synced (kgpu_ctx_sync) yet", who); return KGPU_ERR_INVALID_ARG; }
-    HIPCHECK(hipSetDevice(c->dict->device));
-    int rc;
-    if (c->lines_report.pending && (rc = kgpu_ctx_sync_lines(c, nullptr)) != KGPU_OK && rc != KGPU_ERR_CAPACITY) return rc;
-    return enqueue_words(c, w, d_utf8, d_offsets, n, d_tokens, d_tok_offsets, d_text, text_capacity, d_text_offsets, nullptr, nullptr, who);
+    if (int rc = begin_records_call(c, who)) return rc;
+    return enqueue_words(c, w, DeviceRecords{d_utf8, d_offsets, n, d_tokens, d_tok_offsets, nullptr, nullptr}, d_text, text_capacity, d_text_offsets, who);
 }
 
 // Test hook (host only, not in the header): the spec check and the word table of kgpu_words_create without a device or a handle.

@@ -1,4 +1,4 @@
-"""The byte-keyed table of the word counts and the vocabulary ids (kgpu_count.hip, kgpu_encode.hip, kgpu_words_dev.h) and the count kernel's
+"""The byte-keyed table of the word counts and the vocabulary ids (kgpu_count.hip, kgpu_encode.hip, kgpu_records_dev.h) and the count kernel's
 LDS row table on keys CHOSEN AGAINST THEM (tests/table_keys.py): different words with one full 32-bit hash, probe chains that wrap the table's
 end and are inserted by many wavefronts in different orders, a workgroup's row table with more rows than entries, and all of it in one launch.
 Every case is legal input under the header's contract.  Expected values come from count_ref / encode_ref on the crafted records alone, entry
