@@ -369,7 +369,10 @@ __device__ __forceinline__ uint64_t wave_min_u64(uint64_t k) {  // over the 64 l
 
 // ---- STAGE B of the LDS kernels (kgpu_pool.hip, kgpu_window.hip) over a list of TILES: lattice.rs:116-142 with the connection costs of connection.rs:12-14.
 // A tile is up to 8 targets x 8 predecessors of one start position, pair (ti, j) on lane 8 ti + j; a position with T targets and P predecessors is
-// ceil(T / 8) x ceil(P / 8) tiles -- (a, b) = (target group, predecessor chunk), b fastest: a group's chunks are consecutive, the last one reduces and stores.
+// ceil(T / 8) x ceil(P / 8) tiles (kgpu_tilepack.h: tile_count) -- (a, b) = (target group, predecessor chunk), b fastest: a group's chunks are consecutive,
+// the last one reduces and stores.  A position nothing ends at (P = 0) has NO tile in either kernel: every bucket entry starts at dp = INF and the kernels'
+// emit phases give such a position's nodes NONE16 for a best predecessor (kgpu_pool.hip: the marked nodes of emit 3b; kgpu_window.hip: its list builder) --
+// there is no "absent candidate" entry to relax from, except in the pool kernel's measurement build (KGPU_ABSENT_TILES).  A list may be empty.
 // Descriptor (two words, built once per position by the kernel): D0 = LDS address of node[t0 + 8 a] (18 bits) | 8 (Tt - 1) << 18 (6 bits) | 8 (Pt - 1) << 24 (6) |
 // first chunk << 30 | last chunk << 31 (the two byte offsets ready-made: one s_bfe each where they are used), D1 = LDS address of bk[p0 + 8 b].  node[t] = {word cost (i16) | BYTE OFFSET of the node's bucket slot << 16 (8 x slot: SLOT_SHIFT; the kernels' LDS budgets keep slots below 8192), byte offset of the node's
 // matrix row (left * rows * 2)}; bk[] = bucket entries {dp, 2 * right | node index << 16} (the node index relative to whatever base the kernel uses).

@@ -42,6 +42,17 @@ namespace {
 
 constexpr uint32_t MAXM = 8;         // trie matches buffered per start position
 constexpr uint32_t NONE16 = 0xFFFFu;
+// A DEAD position is a start position nothing ends at (P = 0); its nodes are dead nodes: no path reaches them, dp = INF and no best predecessor
+// (lattice.rs:116-142 with an empty edges[pos]).  Stage B has no tile for them -- the emit phase writes that result (phase 3).  DEAD_MARK: set by emit 3a
+// above the 16-bit end position it parks in node[].y, read and dropped by emit 3b.
+// KGPU_ABSENT_TILES (measurement build, make NAME=absent EXTRA=-DKGPU_ABSENT_TILES: the A/B runs' other arm): the builder as it was before -- a dead
+// position is ceil(T / 8) tiles of one "absent candidate" bk[Nb + 1] whose total no real one reaches, and the sweep arrives at the same result.
+#ifdef KGPU_ABSENT_TILES
+constexpr bool ABSENT_TILES = true;
+#else
+constexpr bool ABSENT_TILES = false;
+#endif
+constexpr uint32_t DEAD_MARK = 1u << 16;
 #ifndef KGPU_POOL_SLEEP
 #define KGPU_POOL_SLEEP 16
 #endif
@@ -437,14 +448,15 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(KGPU_POOL_
         KGPU_ARGS();
         // ---- phase 2: prefix sums: node numbering, bucket offsets, tile offsets ------
         // A TILE is the unit of stage B: up to 8 targets x 8 predecessors of one start position, pair (ti, j) on lane 8 ti + j; a position with T
-        // targets and P predecessors is ceil(T / 8) x max(1, ceil(P / 8)) tiles (P = 0: one tile of absent candidates -- every target stays at INF).
+        // targets and P predecessors is tile_count(T, P) = ceil(T / 8) x ceil(P / 8) tiles (kgpu_tilepack.h; the list builder, 3c, goes through the same
+        // functions).  A dead position (P = 0) has none: emit writes its nodes' result.
         uint32_t ncarry = 1, bcarry = 0, tcarry = 0;
         uint64_t Esum = 0;
         for (uint32_t i0 = 0; i0 < C + 2; i0 += 64) {
             const uint32_t i = i0 + lane;
             const uint32_t v = i < C + 2 ? nb[i] : 0;    // targets starting at i
             const uint32_t w = i < C + 2 ? boff[i] : 0;  // predecessors ending at i
-            const uint32_t x = v ? ((v + 7u) >> 3) * max(1u, (w + 7u) >> 3) : 0u;  // tiles of position i
+            const uint32_t x = ABSENT_TILES ? (v ? tile_groups(v) * max(1u, tile_groups(w)) : 0u) : tile_count(v, w);  // tiles of position i
             const uint32_t vs = wave_incl_scan(v, lane), ws = wave_incl_scan(w, lane), xs = wave_incl_scan(x, lane);
             if (i < C + 2) { nb[i] = ncarry + vs - v; boff[i] = bcarry + ws - w; ebase[i] = tcarry + xs - x; }
             ncarry += __shfl(vs, 63, 64);
@@ -464,7 +476,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(KGPU_POOL_
         int32_t *nSid = (int32_t *)(smem + off);    off += 4 * N;   // +id known, -id unknown, 0 dummy
         off = align_up(off, 8);
         const uint32_t off_emit_end = off;                          // everything above is written by emit 3a
-        uint2 *bk = (uint2 *)(smem + off);          off += 8 * (Nb + 2);  // bucket (= edges[e]): {dp, 2 * right | node << 16}; [Nb]: sink for EOS; [Nb + 1]: the absent candidate
+        uint2 *bk = (uint2 *)(smem + off);          off += 8 * (Nb + (ABSENT_TILES ? 2 : 1));  // bucket (= edges[e]): {dp, 2 * right | node << 16}; [Nb]: sink for EOS ([Nb + 1]: the measurement build's absent candidate)
         uint2 *tiles = (uint2 *)(smem + off);                       // the tile list
         if (N > 0xFFFF || Nb + 1 > SLOT_MAX) { defer_s(s); break; }   // (neither fits a pool: 8 bytes per bucket entry)
         // exact requirement: what 3a writes stays below the match buffer; afterwards the buckets and the tile list overlay it
@@ -487,9 +499,12 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(KGPU_POOL_
         KGPU_ARGS();
         // ---- phase 3: emit nodes from the parked matches --------------------------------
         // 3a, lane = start position, LDS only: the node list in insertion order (lattice.rs:177-201) -- per node its
-        // morph id, start and (parked in node[].y) end position
+        // morph id, start and (parked in node[].y) end position.  The scan is through, so P(i) = boff[i + 1] - boff[i] is known: the nodes of a dead position
+        // are parked with DEAD_MARK above their end (folded into the position's index once: nothing per node).  Every attempt parks every node anew, so a
+        // redo rebuilds the marks from its own scan.
         for (uint32_t i = lane; i < C; i += 64) {
             uint32_t t = nb[i];
+            const uint32_t im = i + (!ABSENT_TILES && boff[i + 1] == boff[i] ? DEAD_MARK : 0u);   // (position 0 is never dead: BOS ends there)
             const uint32_t nm = mcnt[i], span = uspan[i];
             uint32_t ufirst = 0, ucnt = 0;
             if (span) {
@@ -503,21 +518,27 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(KGPU_POOL_
                 uint32_t id, end, nrec;
                 if (MS == 4) {
                     const uint32_t w = mbuf[i * MAXM + m];
-                    id = w & 0x1FFFFFu; end = i + ((w >> 21) & 255u); nrec = w >> 29;
+                    id = w & 0x1FFFFFu; end = im + ((w >> 21) & 255u); nrec = w >> 29;
                     if (nrec == 0) nrec = 1u + d.morph[id - 1].dup;  // eight or more records on one surface
                 } else {
                     const uint2 w = *(const uint2 *)(mbuf + 2 * (i * MAXM + m));
-                    id = w.x; end = i + (w.y & 255u); nrec = w.y >> 8;
+                    id = w.x; end = im + (w.y & 255u); nrec = w.y >> 8;
                 }
                 for (uint32_t r = 0; r < nrec; ++r, ++t) { nSid[t] = (int32_t)(id + r); node[t].y = end; }
             }
             if (span)   // lattice.rs:87-97,190-201
-                for (uint32_t r = 0; r < ucnt; ++r, ++t) { nSid[t] = -(int32_t)(ufirst + r); node[t].y = i + span; }
+                for (uint32_t r = 0; r < ucnt; ++r, ++t) { nSid[t] = -(int32_t)(ufirst + r); node[t].y = im + span; }
         }
         wave_sync();
         // 3b, lane = node: its morph record (one gather per 64 nodes instead of one dependent load per record of the
         // busiest position), its slot in the bucket of the position it ends at.  The order inside a bucket is free:
-        // the sweep breaks ties on the node index it carries.
+        // the sweep breaks ties on the node index it carries.  Every node's dp starts at INF and a marked (dead) node's best predecessor at NONE16, where
+        // a live node keeps its matrix row offset for the gather: for a dead node that IS the result, no sweep will write it.  What stage B rests on:
+        //   (a) a dead node is never a tile's target (its position has no descriptor), so no gather reads its node[].y for a row offset; as a
+        //       predecessor -- it stays in the bucket of the position it ends at, INF + costs may still win there (negative costs), nothing prunes it --
+        //       the gather reads its bk[].y and the sweep its bk[].x, both written here;
+        //   (b) the wave_sync() behind this phase orders these writes before every tile's reads;
+        //   (c) the clamped reads below (lanes past the last word) see a parked end with or without the mark and use neither.
         const uint32_t rows2 = d.conn_rows * 2u;   // bytes per matrix row (connection.rs:12-14: element (right, left) at left * rows + right)
         for (uint32_t t0 = 1; t0 < N - 1; t0 += 256) {  // four nodes per lane: the four record gathers are in flight together
             uint32_t tt[4], ee[4];
@@ -533,19 +554,28 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(KGPU_POOL_
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 if (tt[k] < N - 1) {
-                    const uint32_t slot = boff[ee[k]] + atomicAdd(&bfill[ee[k]], 1u);
-                    node[tt[k]] = make_uint2((uint32_t)(uint16_t)mm[k].cost | (slot << SLOT_SHIFT), (uint32_t)(uint16_t)mm[k].left * rows2);
-                    bk[slot].y = ((uint32_t)(uint16_t)mm[k].right << 1) | (tt[k] << 16);   // ids are non-negative i16 (checked at create): 2 * right fits the half-word
+                    const uint32_t en = ABSENT_TILES ? ee[k] : ee[k] & 0xFFFFu;
+                    const uint32_t slot = boff[en] + atomicAdd(&bfill[en], 1u);
+                    const uint32_t row = (uint32_t)(uint16_t)mm[k].left * rows2;
+                    // (a marked node: all ones -- NONE16 in the low half; the upper half is a live node's row offset's and nobody reads a dead node's)
+                    const uint32_t dead = ABSENT_TILES ? 0u : (uint32_t)((int32_t)(ee[k] << 15) >> 31);
+                    node[tt[k]] = make_uint2((uint32_t)(uint16_t)mm[k].cost | (slot << SLOT_SHIFT), row | dead);
+                    const uint32_t by = ((uint32_t)(uint16_t)mm[k].right << 1) | (tt[k] << 16);   // ids are non-negative i16 (checked at create): 2 * right fits the half-word
+                    if (ABSENT_TILES) bk[slot].y = by;   // (its dp: the sweep of its start position, before any tile of its end position)
+                    else bk[slot] = make_uint2((uint32_t)INF, by);
                 }
             }
         }
         if (lane == 0) {
-            node[N - 1] = make_uint2(Nb << SLOT_SHIFT, d.eos_left * rows2);  // EOS: Morph(0,0,0), ranked id; its dp goes to the sink slot
+            // EOS: Morph(0,0,0), ranked id; its dp goes to the sink slot.  Nothing ends at C: EOS is dead like any other node -- no predecessor, the backtrace
+            // returns no token (an unreachable EOS is an empty result)
+            node[N - 1] = make_uint2(Nb << SLOT_SHIFT, !ABSENT_TILES && boff[C + 1] == boff[C] ? NONE16 : d.eos_left * rows2);
             nSid[N - 1] = 0;
             bk[0] = make_uint2(0u, d.bos_right << 1);  // BOS: dp None -> 0 (lattice.rs:127), right_id 0 (ranked), node 0
-            bk[Nb + 1] = make_uint2(0x7FFEFFFFu, 0u);  // what a position without predecessors relaxes from: a total no real one reaches (real <= INF + 32767) that
-                                                       // cannot overflow when a connection cost and a word cost are added, and stays >= INF when they are negative
             node[0] = make_uint2(0u, NONE16);          // ... and no predecessor (the backtrace stops here)
+            // (measurement build) what a position without predecessors relaxes from: a total no real one reaches (real <= INF + 32767) that cannot overflow
+            // when a connection cost and a word cost are added, and stays >= INF when they are negative
+            if (ABSENT_TILES) bk[Nb + 1] = make_uint2(0x7FFEFFFFu, 0u);
             node[N] = make_uint2(0u, 0u);              // what a padding tile gathers for: row 0 of the matrix, never swept, so never overwritten
         }
         wave_sync();
@@ -555,18 +585,22 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(KGPU_POOL_
         }
         const uint32_t lds0 = (uint32_t)(uintptr_t)(KGPU_LDS(uint8_t) *)pool;  // absolute LDS addresses, wave-uniform: SGPRs
         const uint32_t a_node = bcast32(lds0 + (uint32_t)((uint8_t *)node - pool)), a_bk = bcast32(lds0 + (uint32_t)((uint8_t *)bk - pool));
-        // 3c, lane = start position: its tiles (the descriptors of kgpu_device.h: tile_desc0); (a, b) = (target group, predecessor chunk), b fastest.  A position
-        // without predecessors (P = 0) is one chunk of one absent candidate (bk[Nb + 1]): its targets stay at INF with no predecessor.
+        // 3c, lane = start position: its tiles (the descriptors of kgpu_device.h: tile_desc0); (a, b) = (target group, predecessor chunk), b fastest: tile_groups(P)
+        // chunks for each of the tile_groups(T) groups -- tile_count(T, P) descriptors from ebase[q] on, as the scan counted them.  A dead position (P = 0)
+        // writes none (3b has written its nodes' result); a sentence may have no tile at all (one character nothing starts at: EOS alone, dead).
         for (uint32_t q0 = 0; q0 <= C; q0 += 64) {
             const uint32_t q = q0 + lane;
             if (q <= C) {
-                const uint32_t t0 = nb[q], T = nb[q + 1] - t0, p0r = boff[q], Pr = boff[q + 1] - p0r;
-                const uint32_t p0 = Pr ? p0r : Nb + 1, P = Pr ? Pr : 1u;
+                const uint32_t t0 = nb[q], Tr = nb[q + 1] - t0, p0r = boff[q], Pr = boff[q + 1] - p0r;
+                const uint32_t p0 = ABSENT_TILES && !Pr ? Nb + 1 : p0r, P = ABSENT_TILES && !Pr ? 1u : Pr;
+                const uint32_t T = P ? Tr : 0u;   // a dead position: no group, so a group has at least one chunk
                 uint32_t k = ebase[q];
-                const uint32_t kb = (P + 7u) >> 3;
+                const uint32_t kb = tile_groups(P);
                 for (uint32_t ta = 0; ta < T; ta += 8)
-                    for (uint32_t b = 0; b < kb; ++b, ++k)
-                        tiles[k] = make_uint2(tile_desc0(a_node + 8 * (t0 + ta), min(8u, T - ta), min(8u, P - 8 * b), b == 0, b == kb - 1), a_bk + 8 * (p0 + 8 * b));
+                    for (uint32_t b = 0;;) {
+                        tiles[k++] = make_uint2(tile_desc0(a_node + 8 * (t0 + ta), min(8u, T - ta), min(8u, P - 8 * b), b == 0, b == kb - 1), a_bk + 8 * (p0 + 8 * b));
+                        if (++b >= kb) break;
+                    }
             }
         }
         const uint32_t null0 = (a_node + 8 * N) | TILE_FIRST;   // what the last group gathers for the tiles it does not have: a target group that is never reduced (M[BOS's right][0]: always in the matrix)

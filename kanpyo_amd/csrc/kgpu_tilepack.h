@@ -34,6 +34,16 @@ struct TilePack {
     static KGPU_HD constexpr uint32_t bucket_addr(uint32_t w) { return (w >> 16) << SHIFT; }
 };
 
+// ---- how many tiles a start position has.  A tile is up to TILE_DIM targets x TILE_DIM predecessors; a position with T targets (nodes that start there)
+// and P predecessors (nodes that end there) is ceil(T / 8) target groups x ceil(P / 8) predecessor chunks.  P = 0 -- nothing ends at the position -- is NO
+// tile: every target's result is known without a sweep (dp = INF, no best predecessor: lattice.rs:116-142 with an empty edges[pos]) and the kernel's emit
+// phase writes it.  The kernel's scan (how many descriptors a sentence has, where a position's start) and its list builder (tile_groups(P) chunks for each
+// of the target groups) both go through these two, so the list is exactly as long as the scan said: tests/test_tile_count_cpu.py.
+constexpr uint32_t TILE_DIM = 8;
+KGPU_HD constexpr uint32_t tile_groups(uint32_t n) { return (n + TILE_DIM - 1u) / TILE_DIM; }   // chunks of n predecessors, groups of n targets; 0 -> 0
+KGPU_HD constexpr uint32_t tile_count(uint32_t T, uint32_t P) { return tile_groups(T) * tile_groups(P); }   // = P ? ceil(T / 8) * ceil(P / 8) : 0
+static_assert(tile_count(1, 0) == 0 && tile_count(0, 5) == 0 && tile_count(1, 1) == 1 && tile_count(9, 8) == 2 && tile_count(17, 9) == 6, "tile_count");
+
 constexpr uint32_t LDS_MAX_BYTES = 160u * 1024u;   // per workgroup on gfx950
 typedef TilePack<3> TilePackLds;
 static_assert(TilePackLds::fits(LDS_MAX_BYTES), "the unit form must hold every LDS address of the chip");
