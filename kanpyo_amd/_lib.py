@@ -235,6 +235,10 @@ def lib():
                                             C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
         L.kgpu_debug_feature_pool.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_uint64, C.c_uint64, vp, C.c_uint64, vp, C.POINTER(C.c_uint64)]
         L.kgpu_debug_label_pool.argtypes = L.kgpu_debug_feature_pool.argtypes
+        L.kgpu_debug_concurrent_callers.argtypes = [vp, vp, vp, C.c_uint64, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp]
+        shards = [C.c_int, C.c_uint64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.c_uint64, C.c_int]
+        L.kgpu_debug_merge_shards.argtypes = shards + [vp, C.c_uint64, vp, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
+        L.kgpu_debug_merge_shards_compact.argtypes = shards + [vp, vp, C.c_uint64, vp, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]
         _lib = L
     return _lib
 

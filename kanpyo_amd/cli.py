@@ -87,81 +87,76 @@ def _ready(f, select) -> bool:
         return False
 
 
-def tokenize(args, stdin, stdout) -> int:
+def _open(args):
+    """The dictionary of -c (the default one without it) -> its Tokenizer, the display tables uploaded."""
     from . import dictfile
-    from .tokenizer import Tokenizer, split_lines
+    from .tokenizer import Tokenizer
 
     df = dictfile.load_dict(args.custom_dict or default_dict_path())
     tok = Tokenizer(df.dict)
     tok.set_features(df.morph_feature_table, df.unk_feature_table)
+    return tok
+
+
+def _results(args, stdin, packed_call, text_call):
+    """One result per call over the input, in whichever of its three forms: packed_call(utf8, offsets) for the INPUT argument and for the
+    blocks of stdin split on the host, text_call(block) for `--split device`."""
     if args.input is not None:   # that one string, untrimmed
         one = np.frombuffer(os.fsencode(args.input), dtype=np.uint8)
-        results = iter([tok.tokenize_lines_packed(one, np.array([0, one.size], dtype=np.uint64))])
-    elif args.split == "device":   # the block as it was read: split, trimmed, tokenized and rendered on the device
-        results = (tok.tokenize_text_lines(b) for b in _blocks(stdin, args.block_bytes))
-    else:
-        results = (tok.tokenize_lines_packed(*split_lines(b)) for b in _blocks(stdin, args.block_bytes))
+        return iter([packed_call(one, np.array([0, one.size], dtype=np.uint64))])
+    if args.split == "device":   # the block as it was read: split, trimmed and all the rest on the device
+        return (text_call(b) for b in _blocks(stdin, args.block_bytes))
+    from .tokenizer import split_lines
+
+    return (packed_call(*split_lines(b)) for b in _blocks(stdin, args.block_bytes))
+
+
+def _print_lines(results, stdout, panic: str) -> int:
+    """Each result's text as soon as it is there; a line that is not UTF-8 ends the run behind the lines before it."""
     for text, toff, status in results:
         bad = np.flatnonzero(status == 1)
         if bad.size:
             stdout.write(text[: int(toff[bad[0]])].tobytes())
             stdout.flush()
-            print("thread 'main' panicked: failed to read from stdin: stream did not contain valid UTF-8", file=sys.stderr)
+            print(panic, file=sys.stderr)
             return PANIC_STATUS
         stdout.write(text.tobytes())
         stdout.flush()
     return 0
+
+
+def _each_checked(results, skip_invalid: bool, consume=None) -> int:
+    """consume(result) for every result (a status array, or a tuple that ends with one) once its lines that are not UTF-8 have been reported
+    on stderr by their 1-based numbers, which run on across the results; without --skip-invalid the first of them ends the run."""
+    line0 = 0   # lines in the results before this one
+    for r in results:
+        status = r[-1] if isinstance(r, tuple) else r
+        for i in np.flatnonzero(status == 1).tolist():
+            print(f"kanpyo_amd: line {line0 + i + 1}: not valid UTF-8" + (" (skipped)" if skip_invalid else ""), file=sys.stderr)
+            if not skip_invalid:
+                return PANIC_STATUS
+        line0 += len(status)
+        if consume is not None:
+            consume(r)
+    return 0
+
+
+def tokenize(args, stdin, stdout) -> int:
+    tok = _open(args)
+    return _print_lines(_results(args, stdin, tok.tokenize_lines_packed, tok.tokenize_text_lines), stdout,
+                        "thread 'main' panicked: failed to read from stdin: stream did not contain valid UTF-8")
 
 
 def wakati(args, stdin, stdout) -> int:
-    from . import dictfile
-    from .tokenizer import Tokenizer, split_lines
-
-    df = dictfile.load_dict(args.custom_dict or default_dict_path())
-    tok = Tokenizer(df.dict)
-    tok.set_features(df.morph_feature_table, df.unk_feature_table)
-    w = tok.words(field=args.field, drop=args.drop, keep=args.keep, separator=os.fsencode(args.separator))
-    if args.input is not None:   # that one string, untrimmed
-        one = np.frombuffer(os.fsencode(args.input), dtype=np.uint8)
-        results = iter([w.render_packed(one, np.array([0, one.size], dtype=np.uint64))])
-    elif args.split == "device":
-        results = (w.render_text(b) for b in _blocks(stdin, args.block_bytes))
-    else:
-        results = (w.render_packed(*split_lines(b)) for b in _blocks(stdin, args.block_bytes))
-    for text, toff, status in results:
-        bad = np.flatnonzero(status == 1)
-        if bad.size:
-            stdout.write(text[: int(toff[bad[0]])].tobytes())
-            stdout.flush()
-            print("kanpyo_amd: failed to read from stdin: stream did not contain valid UTF-8", file=sys.stderr)
-            return PANIC_STATUS
-        stdout.write(text.tobytes())
-        stdout.flush()
-    return 0
+    w = _open(args).words(field=args.field, drop=args.drop, keep=args.keep, separator=os.fsencode(args.separator))
+    return _print_lines(_results(args, stdin, w.render_packed, w.render_text), stdout,
+                        "kanpyo_amd: failed to read from stdin: stream did not contain valid UTF-8")
 
 
 def count(args, stdin, stdout) -> int:
-    from . import dictfile
-    from .tokenizer import Tokenizer, split_lines
-
-    df = dictfile.load_dict(args.custom_dict or default_dict_path())
-    tok = Tokenizer(df.dict)
-    tok.set_features(df.morph_feature_table, df.unk_feature_table)
-    counts = tok.words(field=args.field, drop=args.drop, keep=args.keep).counter()
-    if args.input is not None:   # that one string, untrimmed
-        one = np.frombuffer(os.fsencode(args.input), dtype=np.uint8)
-        results = iter([counts.add_packed(one, np.array([0, one.size], dtype=np.uint64))])
-    elif args.split == "device":
-        results = (counts.add_text(b) for b in _blocks(stdin, args.block_bytes))
-    else:
-        results = (counts.add_packed(*split_lines(b)) for b in _blocks(stdin, args.block_bytes))
-    line0 = 0   # lines in the blocks before this one
-    for status in results:
-        for i in np.flatnonzero(status == 1).tolist():
-            print(f"kanpyo_amd: line {line0 + i + 1}: not valid UTF-8" + (" (skipped)" if args.skip_invalid else ""), file=sys.stderr)
-            if not args.skip_invalid:
-                return PANIC_STATUS   # nothing has been printed
-        line0 += len(status)
+    counts = _open(args).words(field=args.field, drop=args.drop, keep=args.keep).counter()
+    if _each_checked(_results(args, stdin, counts.add_packed, counts.add_text), args.skip_invalid):
+        return PANIC_STATUS   # nothing has been printed
     out = bytearray()
     for word, n in counts.most_common(args.top):
         out += b"%d\t" % n + word + b"\n"
@@ -171,8 +166,6 @@ def count(args, stdin, stdout) -> int:
 
 
 def encode(args, stdin, stdout) -> int:
-    from . import dictfile
-    from .tokenizer import Tokenizer, split_lines
     from .vocab import Vocab
 
     try:
@@ -185,33 +178,21 @@ def encode(args, stdin, stdout) -> int:
         if word is not None and os.fsencode(word) not in have:
             print(f"kanpyo_amd: {opt} {word!r} is not a line of {args.vocab}", file=sys.stderr)
             return 2
-    df = dictfile.load_dict(args.custom_dict or default_dict_path())
-    tok = Tokenizer(df.dict)
-    tok.set_features(df.morph_feature_table, df.unk_feature_table)
     enc = lambda w: None if w is None else os.fsencode(w)   # noqa: E731
-    v = Vocab.from_words(tok.words(field=args.field, drop=args.drop, keep=args.keep), listed, enc(args.unk), enc(args.bos), enc(args.eos))
-    if args.input is not None:   # that one string, untrimmed
-        one = np.frombuffer(os.fsencode(args.input), dtype=np.uint8)
-        results = iter([v.encode_packed(one, np.array([0, one.size], dtype=np.uint64))])
-    elif args.split == "device":
-        results = (v.encode_text(b) for b in _blocks(stdin, args.block_bytes))
-    else:
-        results = (v.encode_packed(*split_lines(b)) for b in _blocks(stdin, args.block_bytes))
+    v = Vocab.from_words(_open(args).words(field=args.field, drop=args.drop, keep=args.keep), listed, enc(args.unk), enc(args.bos), enc(args.eos))
     out = bytearray()   # (nothing is printed before the input is known to be valid, or --skip-invalid says not to care)
-    line0 = 0
-    for ids, ioff, status in results:
-        for i in np.flatnonzero(status == 1).tolist():
-            print(f"kanpyo_amd: line {line0 + i + 1}: not valid UTF-8" + (" (skipped)" if args.skip_invalid else ""), file=sys.stderr)
-            if not args.skip_invalid:
-                return PANIC_STATUS   # nothing has been printed
-        line0 += len(status)
-        o = ioff.tolist()
-        dec = ids.tolist()
-        out += "".join(" ".join(map(str, dec[o[i] : o[i + 1]])) + "\n" for i in range(len(o) - 1)).encode()
+
+    def decimal(result):
+        ids, ioff, _ = result
+        o, dec = ioff.tolist(), ids.tolist()
+        out.extend("".join(" ".join(map(str, dec[o[i] : o[i + 1]])) + "\n" for i in range(len(o) - 1)).encode())
         if args.skip_invalid:
             stdout.write(bytes(out))
             stdout.flush()
             out.clear()
+
+    if _each_checked(_results(args, stdin, v.encode_packed, v.encode_text), args.skip_invalid, decimal):
+        return PANIC_STATUS   # nothing has been printed
     stdout.write(bytes(out))
     stdout.flush()
     return 0
@@ -255,9 +236,6 @@ def first_line(data: bytes) -> bytes:
 
 
 def graphviz(args, stdin, stdout) -> int:
-    from . import dictfile
-    from .tokenizer import Tokenizer
-
     if args.input is not None:   # that one string, untrimmed
         raw = os.fsencode(args.input)
     else:
@@ -266,11 +244,8 @@ def graphviz(args, stdin, stdout) -> int:
         except UnicodeDecodeError:
             print("thread 'main' panicked: failed to read from stdin: stream did not contain valid UTF-8", file=sys.stderr)
             return PANIC_STATUS
-    df = dictfile.load_dict(args.custom_dict or default_dict_path())
-    tok = Tokenizer(df.dict)
-    tok.set_features(df.morph_feature_table, df.unk_feature_table)
     one = np.frombuffer(raw, dtype=np.uint8)
-    text, _, status = tok.graphviz_packed(one, np.array([0, one.size], dtype=np.uint64), dpi=args.dpi, full_state=args.full_state)
+    text, _, status = _open(args).graphviz_packed(one, np.array([0, one.size], dtype=np.uint64), dpi=args.dpi, full_state=args.full_state)
     if status[0]:   # (an INPUT argument that is not UTF-8: the reference's argument parser rejects it)
         print(f"kanpyo_amd: the input cannot be drawn (sentence status {int(status[0])})", file=sys.stderr)
         return 2
@@ -287,76 +262,56 @@ def _dpi(text: str) -> int:
     return int(digits)
 
 
+def _text_command(sub, name: str, help: str, verb: str = None, first=(), own=(), skip_invalid: str = None):
+    """A subcommand over lines of text: INPUT or stdin, the dictionary, where the blocks are split; with `verb` ("Print", ...) wakati's field and
+    filter as well.  first / own: the command's own options as (flag, keywords), listed in front of / behind those; skip_invalid: its help."""
+    p = sub.add_parser(name, help=help)
+    p.add_argument("input", nargs="?", default=None, help="Input text to analyze [default: stdin]")
+    p.add_argument("-d", "--dict", choices=["ipa"], default="ipa", help="Dictionary")
+    p.add_argument("-c", "--custom-dict", default=None, help="Custom dictionary (.dict)")
+    for flag, kw in first:
+        p.add_argument(flag, **kw)
+    if verb:
+        fld = p.add_mutually_exclusive_group()
+        fld.add_argument("--field", type=_field, default=None, help=f"{verb} feature N of the token's row instead of the surface")
+        fld.add_argument("--base-form", dest="field", action="store_const", const=6, help="--field 6 (IPADIC)")
+        fld.add_argument("--reading", dest="field", action="store_const", const=7, help="--field 7 (IPADIC)")
+        fld.add_argument("--pronunciation", dest="field", action="store_const", const=8, help="--field 8 (IPADIC)")
+        flt = p.add_mutually_exclusive_group()
+        flt.add_argument("--drop", type=_pos_list, default=[], help="Drop tokens whose part of speech (feature 0) is one of POS[,POS...]")
+        flt.add_argument("--keep", type=_pos_list, default=[], help="Keep only tokens whose part of speech is one of POS[,POS...]")
+    for flag, kw in own:
+        p.add_argument(flag, **kw)
+    p.add_argument("--split", choices=["host", "device"], default="host",
+                   help="Where stdin's blocks are split into lines and trimmed [default: host]")
+    if skip_invalid:
+        p.add_argument("--skip-invalid", action="store_true", help=skip_invalid)
+    p.add_argument("--block-bytes", type=int, default=BLOCK_BYTES, help=argparse.SUPPRESS)
+    return p
+
+
 def parse_args(argv=None):
     """The reference's command line (src/bin/kanpyo.rs:14-49).  -> the namespace; .command is "tokenize" or "graphviz" -- or "wakati", "count" or "encode", which are this package's own."""
     p = argparse.ArgumentParser(prog="kanpyo_amd", description="Japanese Morphological Analyzer (kanpyo) on AMD Instinct GPUs")
     sub = p.add_subparsers(dest="command")
-    t = sub.add_parser("tokenize", help="Tokenize input text")
-    t.add_argument("input", nargs="?", default=None, help="Input text to analyze [default: stdin]")
-    t.add_argument("-d", "--dict", choices=["ipa"], default="ipa", help="Dictionary")
-    t.add_argument("-c", "--custom-dict", default=None, help="Custom dictionary (.dict)")
-    t.add_argument("--split", choices=["host", "device"], default="host",
-                   help="Where stdin's blocks are split into lines and trimmed [default: host]")
-    t.add_argument("--block-bytes", type=int, default=BLOCK_BYTES, help=argparse.SUPPRESS)
+    t = _text_command(sub, "tokenize", "Tokenize input text")
     g = sub.add_parser("graphviz", help="Output lattice in Graphviz format")
     g.add_argument("input", nargs="?", default=None, help="Input text to analyze [default: one line of stdin]")
     g.add_argument("-d", "--dict", choices=["ipa"], default="ipa", help="Dictionary")
     g.add_argument("-c", "--custom-dict", default=None, help="Custom dictionary (.dict)")
     g.add_argument("-f", "--full-state", action="store_true", help="Output full state of lattice")
     g.add_argument("--dpi", type=_dpi, default=48, help="DPI of output image [default: 48]")
-    w = sub.add_parser("wakati", help="One line of separated words per input line (not in the reference)")
-    w.add_argument("input", nargs="?", default=None, help="Input text to analyze [default: stdin]")
-    w.add_argument("-d", "--dict", choices=["ipa"], default="ipa", help="Dictionary")
-    w.add_argument("-c", "--custom-dict", default=None, help="Custom dictionary (.dict)")
-    fld = w.add_mutually_exclusive_group()
-    fld.add_argument("--field", type=_field, default=None, help="Print feature N of the token's row instead of the surface")
-    fld.add_argument("--base-form", dest="field", action="store_const", const=6, help="--field 6 (IPADIC)")
-    fld.add_argument("--reading", dest="field", action="store_const", const=7, help="--field 7 (IPADIC)")
-    fld.add_argument("--pronunciation", dest="field", action="store_const", const=8, help="--field 8 (IPADIC)")
-    flt = w.add_mutually_exclusive_group()
-    flt.add_argument("--drop", type=_pos_list, default=[], help="Drop tokens whose part of speech (feature 0) is one of POS[,POS...]")
-    flt.add_argument("--keep", type=_pos_list, default=[], help="Keep only tokens whose part of speech is one of POS[,POS...]")
-    w.add_argument("--separator", type=_separator, default=" ", help="The byte between words [default: a space]")
-    w.add_argument("--split", choices=["host", "device"], default="host",
-                   help="Where stdin's blocks are split into lines and trimmed [default: host]")
-    w.add_argument("--block-bytes", type=int, default=BLOCK_BYTES, help=argparse.SUPPRESS)
-    c = sub.add_parser("count", help="Word frequencies of the whole input (not in the reference)")
-    c.add_argument("input", nargs="?", default=None, help="Input text to analyze [default: stdin]")
-    c.add_argument("-d", "--dict", choices=["ipa"], default="ipa", help="Dictionary")
-    c.add_argument("-c", "--custom-dict", default=None, help="Custom dictionary (.dict)")
-    fld = c.add_mutually_exclusive_group()
-    fld.add_argument("--field", type=_field, default=None, help="Count feature N of the token's row instead of the surface")
-    fld.add_argument("--base-form", dest="field", action="store_const", const=6, help="--field 6 (IPADIC)")
-    fld.add_argument("--reading", dest="field", action="store_const", const=7, help="--field 7 (IPADIC)")
-    fld.add_argument("--pronunciation", dest="field", action="store_const", const=8, help="--field 8 (IPADIC)")
-    flt = c.add_mutually_exclusive_group()
-    flt.add_argument("--drop", type=_pos_list, default=[], help="Drop tokens whose part of speech (feature 0) is one of POS[,POS...]")
-    flt.add_argument("--keep", type=_pos_list, default=[], help="Keep only tokens whose part of speech is one of POS[,POS...]")
-    c.add_argument("--top", type=_top, default=None, help="Print the N most frequent words only")
-    c.add_argument("--split", choices=["host", "device"], default="host",
-                   help="Where stdin's blocks are split into lines and trimmed [default: host]")
-    c.add_argument("--skip-invalid", action="store_true", help="Skip lines that are not UTF-8 instead of ending with status 101")
-    c.add_argument("--block-bytes", type=int, default=BLOCK_BYTES, help=argparse.SUPPRESS)
-    e = sub.add_parser("encode", help="Vocabulary ids of each input line's words (not in the reference)")
-    e.add_argument("input", nargs="?", default=None, help="Input text to analyze [default: stdin]")
-    e.add_argument("-d", "--dict", choices=["ipa"], default="ipa", help="Dictionary")
-    e.add_argument("-c", "--custom-dict", default=None, help="Custom dictionary (.dict)")
-    e.add_argument("--vocab", required=True, help="The vocabulary: one word per line, line k (0-based) is id k")
-    fld = e.add_mutually_exclusive_group()
-    fld.add_argument("--field", type=_field, default=None, help="Encode feature N of the token's row instead of the surface")
-    fld.add_argument("--base-form", dest="field", action="store_const", const=6, help="--field 6 (IPADIC)")
-    fld.add_argument("--reading", dest="field", action="store_const", const=7, help="--field 7 (IPADIC)")
-    fld.add_argument("--pronunciation", dest="field", action="store_const", const=8, help="--field 8 (IPADIC)")
-    flt = e.add_mutually_exclusive_group()
-    flt.add_argument("--drop", type=_pos_list, default=[], help="Drop tokens whose part of speech (feature 0) is one of POS[,POS...]")
-    flt.add_argument("--keep", type=_pos_list, default=[], help="Keep only tokens whose part of speech is one of POS[,POS...]")
-    e.add_argument("--unk", default="<unk>", help="The word of the vocabulary whose id a word outside it gets [default: <unk>]")
-    e.add_argument("--bos", default=None, help="A word of the vocabulary whose id goes in front of every line's ids")
-    e.add_argument("--eos", default=None, help="A word of the vocabulary whose id goes behind every line's ids")
-    e.add_argument("--split", choices=["host", "device"], default="host",
-                   help="Where stdin's blocks are split into lines and trimmed [default: host]")
-    e.add_argument("--skip-invalid", action="store_true", help="A line that is not UTF-8 prints its bos / eos only instead of ending the run with status 101")
-    e.add_argument("--block-bytes", type=int, default=BLOCK_BYTES, help=argparse.SUPPRESS)
+    _text_command(sub, "wakati", "One line of separated words per input line (not in the reference)", "Print",
+                  own=[("--separator", dict(type=_separator, default=" ", help="The byte between words [default: a space]"))])
+    _text_command(sub, "count", "Word frequencies of the whole input (not in the reference)", "Count",
+                  own=[("--top", dict(type=_top, default=None, help="Print the N most frequent words only"))],
+                  skip_invalid="Skip lines that are not UTF-8 instead of ending with status 101")
+    _text_command(sub, "encode", "Vocabulary ids of each input line's words (not in the reference)", "Encode",
+                  first=[("--vocab", dict(required=True, help="The vocabulary: one word per line, line k (0-based) is id k"))],
+                  own=[("--unk", dict(default="<unk>", help="The word of the vocabulary whose id a word outside it gets [default: <unk>]")),
+                       ("--bos", dict(default=None, help="A word of the vocabulary whose id goes in front of every line's ids")),
+                       ("--eos", dict(default=None, help="A word of the vocabulary whose id goes behind every line's ids"))],
+                  skip_invalid="A line that is not UTF-8 prints its bos / eos only instead of ending the run with status 101")
     args = p.parse_args(argv)
     if args.command is None:   # src/bin/kanpyo.rs:173: no subcommand == tokenize from stdin, default dictionary
         args = t.parse_args([])

@@ -8,31 +8,25 @@ from __future__ import annotations
 
 import ctypes as C
 
+import numpy as np
+
 from . import _lib
+from ._calls import TOKEN_DTYPE, Handle, struct_dict
 
 PROFILE_OFF, PROFILE_EVENTS, PROFILE_WORK, PROFILE_SAMPLED, PROFILE_NO_T = 0, 1, 2, 4, 8
 STAGE_ALL, STAGE_LATTICE, STAGE_GATHER, STAGE_VITERBI = 0, 5, 6, 7  # kgpu_ctx_set_ablation
 
 
-class DeviceContext:
+class DeviceContext(Handle):
     """One HIP stream + scratch arena; not thread-safe, make one per thread / per queue slot."""
+
+    _destroy = "kgpu_ctx_destroy"
 
     def __init__(self, tokenizer, stream_ptr: int | None = None):
         self._tok = tokenizer  # keeps the dictionary alive
         h = C.c_void_p()
         _lib.check(_lib.lib().kgpu_ctx_create(tokenizer.handle, C.c_void_p(stream_ptr) if stream_ptr else None, C.byref(h)))
         self._h = h
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib.lib().kgpu_ctx_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def tokenize(self, d_utf8: int, d_offsets: int, n: int, total_bytes: int, d_tokens: int, token_capacity: int,
                  d_tok_offsets: int, d_status: int):
@@ -126,7 +120,7 @@ class DeviceContext:
         """The launch plan (kgpu_plan_info): LDS bytes per workgroup and resident workgroups per CU of both kernels."""
         p = _lib.PlanInfo()
         _lib.check(_lib.lib().kgpu_ctx_get_plan(self._h, C.byref(p), C.sizeof(p)))
-        return {n: int(getattr(p, n)) for n, _ in p._fields_ if n != "reserved"}
+        return struct_dict(p)
 
     def set_ablation(self, stop_after_stage: int):
         """Measurement only: following batches stop after the given stage (STAGE_*), zero tokens; 0 = off."""
@@ -135,7 +129,7 @@ class DeviceContext:
     def work(self, reset: bool = True) -> dict:
         w = _lib.Work()
         _lib.check(_lib.lib().kgpu_ctx_get_work(self._h, C.byref(w), int(reset)))
-        return {n: int(getattr(w, n)) for n, _ in w._fields_}
+        return struct_dict(w)
 
     def phase_cycles(self, reset: bool = True) -> dict:
         """Per-phase shader-clock cycles of the LDS kernel, summed over sentences (PROFILE_WORK runs)."""
@@ -148,10 +142,6 @@ class DeviceContext:
 def expand_tokens(tokens8, tok_offsets, first):
     """kgpu_expand_tokens: 8-byte records (uint32 [T, 2] or uint64 [T]) + token offsets [n + 1] + first [n, 2] -> TOKEN_DTYPE [T]
     (host side, numpy arrays)."""
-    import numpy as np
-
-    from .tokenizer import TOKEN_DTYPE
-
     t8 = np.ascontiguousarray(tokens8).view(np.uint32).reshape(-1, 2)
     toff = np.ascontiguousarray(tok_offsets, dtype=np.uint64)
     fs = np.ascontiguousarray(first, dtype=np.uint32).reshape(-1)

@@ -9,24 +9,28 @@ from __future__ import annotations
 
 import ctypes as C
 import threading
+from functools import partial
 from typing import List, Sequence
 
 import numpy as np
 
 from . import _lib
+from ._calls import Handle, batch_call, block_call, pack_sentences, ptr, struct_dict
+from .device import DeviceContext
 
 
 def _word_bytes(w) -> bytes:
     return w.encode("utf-8") if isinstance(w, str) else bytes(w)
 
 
-class Vocab:
+class Vocab(Handle):
     """A vocabulary handle (kgpu_vocab): a frozen word -> id table on the device.  Immutable; usable from many threads at once; it keeps its
     Words handle's tables and the dictionary alive and may outlive both (encode_tensor alone needs the Tokenizer open).  .words is the list (bytes), id k is words[k]."""
 
-    def __init__(self, words_handle, words: Sequence, unk_id: int, bos_id=None, eos_id=None):
-        from .tokenizer import pack_sentences
+    _destroy = "kgpu_vocab_destroy"
+    _ctx = None   # encode_tensor's DeviceContext, made by its first call
 
+    def __init__(self, words_handle, words: Sequence, unk_id: int, bos_id=None, eos_id=None):
         self.words = [_word_bytes(w) for w in words]
         self.unk_id, self.bos_id, self.eos_id = int(unk_id), bos_id, eos_id
         flags = (_lib.KGPU_VOCAB_ADD_BOS if bos_id is not None else 0) | (_lib.KGPU_VOCAB_ADD_EOS if eos_id is not None else 0)
@@ -34,32 +38,19 @@ class Vocab:
         packed = np.ascontiguousarray(packed)
         opts = _lib.VocabOpts(C.sizeof(_lib.VocabOpts), flags, int(unk_id), int(bos_id or 0), int(eos_id or 0))
         h = C.c_void_p()
-        _lib.check(_lib.lib().kgpu_vocab_create(words_handle.handle, packed.ctypes.data if packed.size else None, offs.ctypes.data, len(self.words),
+        _lib.check(_lib.lib().kgpu_vocab_create(words_handle.handle, ptr(packed), offs.ctypes.data, len(self.words),
                                                 C.byref(opts), C.byref(h)))
         self._h = h
         self._tokenizer = words_handle.tokenizer   # (encode_tensor's context is made from it)
         self._device = self._tokenizer.info()["device"]
         self._extra = (1 if bos_id is not None else 0) + (1 if eos_id is not None else 0)
-        self._ctx = None
         self._ctx_lock = threading.Lock()
 
-    @property
-    def handle(self):
-        return self._h
-
     def close(self):
-        if getattr(self, "_ctx", None) is not None:
+        if self._ctx is not None:
             self._ctx.close()
             self._ctx = None
-        if getattr(self, "_h", None):
-            _lib.lib().kgpu_vocab_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()
 
     def __len__(self):
         return len(self.words)
@@ -68,68 +59,27 @@ class Vocab:
         """kgpu_vocab_get_info: n_words, table_slots, key_bytes, rows_resolved."""
         i = _lib.VocabInfo(C.sizeof(_lib.VocabInfo))
         _lib.check(_lib.lib().kgpu_vocab_get_info(self._h, C.byref(i)))
-        return {n: int(getattr(i, n)) for n, _ in i._fields_ if n not in ("size", "reserved")}
+        return struct_dict(i)
 
     # ---- host memory in and out ------------------------------------------------------------------------------------------------------------
     def encode_packed(self, utf8: np.ndarray, offsets: np.ndarray, out=None):
         """kgpu_encode_batch -> (ids[int32], id_offsets[uint64 n+1], status[uint8 n]): sentence i's sequence is
         ids[id_offsets[i]:id_offsets[i+1]].  out=(ids, id_offsets, status): caller-owned arrays to reuse (too small: KgpuError with
         KGPU_ERR_CAPACITY, nothing written)."""
-        utf8 = np.ascontiguousarray(utf8, dtype=np.uint8)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        n = offsets.size - 1
-        if n < 0:
-            raise ValueError("offsets needs n+1 entries")
-        total = int(offsets[-1] - offsets[0]) if n else 0
-        cap = total // 2 + n * (1 + self._extra) + 64
-        L = _lib.lib()
-        while True:
-            if out is not None:
-                ids, ioff, status = out
-                if ids.dtype != np.int32 or ioff.dtype != np.uint64 or status.dtype != np.uint8 or ioff.size < n + 1 or status.size < n:
-                    raise ValueError("out=(ids[int32], id_offsets[uint64 >= n+1], status[uint8 >= n])")
-                cap = ids.size
-            else:
-                ids = np.empty(max(cap, 1), dtype=np.int32)
-                ioff = np.empty(n + 1, dtype=np.uint64)
-                status = np.empty(max(n, 1), dtype=np.uint8)
-            status[: max(n, 1)] = 0
-            got = C.c_uint64(0)
-            rc = L.kgpu_encode_batch(self._h, utf8.ctypes.data if utf8.size else None, offsets.ctypes.data, n, ids.ctypes.data, cap, ioff.ctypes.data,
-                                     status.ctypes.data, C.byref(got))
-            if rc == _lib.KGPU_ERR_CAPACITY and out is None:
-                cap = int(got.value)   # the exact count reported by the device
-                continue
-            _lib.check(rc)
-            return ids[: int(got.value)], ioff[: n + 1], status[:n]
+        return batch_call(partial(_lib.lib().kgpu_encode_batch, self._h), utf8, offsets, np.int32, lambda total, n: total // 2 + n * (1 + self._extra) + 64,
+                          ("ids[int32]", "id_offsets"), out=out)
 
     def encode_text(self, block):
         """kgpu_encode_text: a raw block of input (bytes or uint8 array) -> (ids, id_offsets, status) as encode_packed(*split_lines(block))
         gives them; the split and the trim run on the device."""
-        from .tokenizer import _block_bytes
+        def first(size):   # (as encode_packed sizes it, with every 16 bytes a possible line)
+            lines = size // 16 + 1024
+            return size // 2 + 64 + lines * self._extra, lines
 
-        src = _block_bytes(block)
-        cap, ocap = src.size // 2 + 64, src.size // 16 + 1024
-        cap += ocap * self._extra
-        L = _lib.lib()
-        while True:
-            ids = np.empty(max(cap, 1), dtype=np.int32)
-            ioff = np.empty(ocap, dtype=np.uint64)
-            status = np.zeros(ocap, dtype=np.uint8)
-            n, got = C.c_uint64(0), C.c_uint64(0)
-            rc = L.kgpu_encode_text(self._h, src.ctypes.data if src.size else None, src.size, ids.ctypes.data, cap, ioff.ctypes.data, ocap,
-                                    status.ctypes.data, C.byref(n), C.byref(got))
-            if rc == _lib.KGPU_ERR_CAPACITY and (int(got.value) > cap or int(n.value) + 1 > ocap):   # exact sizes reported by the device
-                cap, ocap = max(cap, int(got.value)), max(ocap, int(n.value) + 1)
-                continue
-            _lib.check(rc)
-            k = int(n.value)
-            return ids[: int(got.value)], ioff[: k + 1], status[:k]
+        return block_call(partial(_lib.lib().kgpu_encode_text, self._h), block, np.int32, first)
 
     def encode(self, sentences: Sequence) -> List[np.ndarray]:
         """One int32 array per sentence (str or bytes)."""
-        from .tokenizer import pack_sentences
-
         ids, ioff, _ = self.encode_packed(*pack_sentences(sentences))
         o = ioff.tolist()
         return [ids[o[i] : o[i + 1]] for i in range(len(o) - 1)]
@@ -144,9 +94,6 @@ class Vocab:
         width=w    -> (ids int32 [n, w], lengths int64 [n] = min(L, w), status uint8 [n]); rows are cut after w elements (a cut row ends with
         eos_id when the vocabulary adds EOS) and filled with pad_id."""
         import torch
-
-        from .device import DeviceContext
-        from .tokenizer import pack_sentences
 
         if width is not None and int(width) < 1:
             raise ValueError("width is 1 or more (None: ragged)")
