@@ -608,6 +608,57 @@ int kgpu_encode_device(kgpu_ctx *c, const kgpu_vocab *v, const uint8_t *d_utf8, 
                        const kgpu_token *d_tokens, const uint64_t *d_tok_offsets,
                        int32_t *d_ids, uint64_t id_capacity, uint64_t width, int32_t pad_id, uint64_t *d_id_offsets);
 
+/* ---- WordPiece ids: out-of-list words split into subword ids on the device (NOT an output of the reference: the second half of the
+ * "morphological tokenizer, then WordPiece" pipeline of the BERT-Japanese family) ----
+ * A WordPiece vocabulary is a kgpu_vocab made by kgpu_vocab_create_wordpiece; kgpu_encode_batch, kgpu_encode_text, kgpu_encode_device,
+ * kgpu_vocab_get_info and kgpu_vocab_destroy take it as they take a plain one.  A kept token gives the PIECES of its word: zero, one or many
+ * ids.  These are the rules of BERT's WordpieceTokenizer, stated on bytes.  NOT claimed: equal input_ids with a real BERT-Japanese tokenizer,
+ * which also normalises its text (NFKC) and segments with the real IPADIC; what is claimed is the split below.
+ *  1. Which tokens, which word.  Rules 1 and 2 of "vocabulary ids", unchanged: the tokens wakati keeps; the dictionary's key for a known token
+ *     whose word is its surface.
+ *  2. Characters.  A character of a word starts at byte 0 and at every byte that is not 10xxxxxx: defined for any bytes, UTF-8 or not.  A
+ *     piece begins and ends only at a character start or at the word's end.
+ *  3. Tables.  The INITIAL table is the whole list, verbatim: the table of a plain vocabulary (a duplicate is still the verbatim-bytes
+ *     duplicate of rule 3 there).  The CONTINUATION table holds every list entry that starts with the prefix and is longer than it, with the
+ *     prefix stripped, under the entry's own list index.  With prefix_len == 0 the continuation table is the initial table.
+ *  4. The split of a word of len bytes.
+ *     a. The empty word gives no id.
+ *     b. A word of more than max_word_chars characters gives [unk_id].
+ *     c. Otherwise start = 0, and while start < len: take the largest end > start (a character start, or len) such that word[start:end] is in
+ *        the initial table if start == 0, in the continuation table otherwise.
+ *     d. No such end: the WHOLE word gives the single id unk_id; the pieces found so far are discarded.
+ *     e. Otherwise the entry's id is the next piece and start = end.
+ *     So a word that is listed whole gives its one id, as from a plain vocabulary; the surface "##abc" matches a list entry "##abc" at start 0.
+ *  5. Sequence, ragged form, padded form, bad records, immutability: rules 4 to 8 of "vocabulary ids" with "the ids of its kept tokens" read
+ *     as "the pieces of its kept tokens, in order".  A padded row may be cut INSIDE a token's pieces: it holds the first `width` elements of
+ *     the sequence, and with EOS asked for the last slot of a cut row holds eos_id.  id_offsets stays the scan of the untruncated lengths.
+ *  6. Capacity.  A token may give up to max_word_chars ids: no bound by the record count holds.  The protocol is rule 5's: on
+ *     KGPU_ERR_CAPACITY the count is exact and nothing was written. */
+typedef struct kgpu_wordpiece_opts {
+    uint32_t size;            /* sizeof(kgpu_wordpiece_opts) */
+    uint32_t max_word_chars;  /* 0: 100.  1..1024 */
+    uint32_t prefix_len;      /* 0..8 */
+    uint8_t  prefix[8];       /* the continuation prefix; a NULL opts means "##", 100 */
+} kgpu_wordpiece_opts;
+typedef struct kgpu_wordpiece_info {
+    uint32_t size;               /* in: sizeof(kgpu_wordpiece_info) as the caller knows it; that many bytes are written at most */
+    uint32_t reserved;
+    uint64_t cont_words;         /* entries of the continuation table */
+    uint64_t cont_table_slots;   /* its slots (16 bytes each); with prefix_len == 0 the initial table's: the table is shared, not built twice */
+    uint64_t cont_key_bytes;     /* bytes of its key arena */
+    uint64_t rows_whole;         /* row-determined feature rows whose word is one listed piece ... */
+    uint64_t rows_split;         /* ... is several pieces ... */
+    uint64_t rows_unk;           /* ... gives unk_id (too long, or no split); the empty word's rows are in none of the three */
+    uint64_t row_piece_ids;      /* ids in the pool behind the rows that split */
+    uint64_t max_initial_bytes;  /* the longest entry of each table in bytes: no longer prefix of a word is probed */
+    uint64_t max_cont_bytes;
+} kgpu_wordpiece_info;
+/* kgpu_vocab_create's arguments and errors, and wp: KGPU_ERR_INVALID_ARG for a size smaller than the struct, prefix_len > 8 or max_word_chars
+ * > 1024.  Beside the plain handle's tables: 8 bytes per feature row instead of 4, the pool, and the continuation table. */
+int kgpu_vocab_create_wordpiece(kgpu_words *w, const uint8_t *words, const uint64_t *word_offsets, uint64_t n_words,
+                                const kgpu_vocab_opts *opts, const kgpu_wordpiece_opts *wp, kgpu_vocab **out);
+int kgpu_vocab_get_wordpiece_info(const kgpu_vocab *v, kgpu_wordpiece_info *info);   /* KGPU_ERR_INVALID_ARG on a plain vocabulary */
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,7 @@ SYMBOLS = [
     "kgpu_counts_create", "kgpu_counts_destroy", "kgpu_counts_reset", "kgpu_counts_get_info", "kgpu_count_batch", "kgpu_count_text",
     "kgpu_count_words_device", "kgpu_ctx_sync_count", "kgpu_counts_read",
     "kgpu_vocab_create", "kgpu_vocab_destroy", "kgpu_vocab_get_info", "kgpu_encode_batch", "kgpu_encode_text", "kgpu_encode_device",
+    "kgpu_vocab_create_wordpiece", "kgpu_vocab_get_wordpiece_info",
 ]
 KGPU_VOCAB_ADD_BOS, KGPU_VOCAB_ADD_EOS = 1, 2
 KGPU_COUNTS_DEFAULT_SLOTS, KGPU_COUNTS_DEFAULT_KEY_BYTES = 1 << 22, 256 << 20
@@ -135,6 +136,15 @@ class VocabInfo(C.Structure):  # kgpu_vocab_info: read with its size, fields are
                 ("rows_resolved", C.c_uint64)]
 
 
+class WordpieceOpts(C.Structure):  # kgpu_wordpiece_opts
+    _fields_ = [("size", C.c_uint32), ("max_word_chars", C.c_uint32), ("prefix_len", C.c_uint32), ("prefix", C.c_uint8 * 8)]
+
+
+class WordpieceInfo(C.Structure):  # kgpu_wordpiece_info: read with its size, fields are only ever appended
+    _fields_ = [("size", C.c_uint32), ("reserved", C.c_uint32)] + [(n, C.c_uint64) for n in (
+        "cont_words", "cont_table_slots", "cont_key_bytes", "rows_whole", "rows_split", "rows_unk", "row_piece_ids", "max_initial_bytes", "max_cont_bytes")]
+
+
 class Work(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("sentences", "B", "C", "T", "N", "E", "K")]
 
@@ -229,6 +239,11 @@ def lib():
         L.kgpu_debug_vocab_table.argtypes = [vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.c_uint64, C.c_uint64, C.POINTER(WordsSpec), vp, vp, C.c_uint64,
                                              C.POINTER(VocabOpts), vp, vp, C.c_uint64, C.POINTER(C.c_uint64), vp, C.c_uint64, C.POINTER(C.c_uint64),
                                              C.POINTER(C.c_uint64)]
+        L.kgpu_vocab_create_wordpiece.argtypes = [vp, vp, vp, C.c_uint64, C.POINTER(VocabOpts), C.POINTER(WordpieceOpts), C.POINTER(vp)]
+        L.kgpu_vocab_get_wordpiece_info.argtypes = [vp, C.POINTER(WordpieceInfo)]
+        L.kgpu_debug_wordpiece_table.argtypes = [vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.c_uint64, C.c_uint64, C.POINTER(WordsSpec), vp, vp, C.c_uint64,
+                                                 C.POINTER(VocabOpts), C.POINTER(WordpieceOpts), vp, vp, vp, vp, vp, vp, vp, C.POINTER(WordpieceInfo)]
+        L.kgpu_debug_wordpiece_split.argtypes = [vp, vp, C.c_uint64, C.POINTER(WordpieceOpts), C.c_int32, vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.POINTER(C.c_uint64)]
         L.kgpu_debug_counts_order.argtypes = [vp, vp, vp, C.c_uint64] + L.kgpu_counts_read.argtypes[1:]
         L.kgpu_debug_key_table.argtypes = [vp, C.c_size_t, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), vp]
         L.kgpu_debug_word_table.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_uint64, C.c_uint64, C.POINTER(WordsSpec), vp, vp, C.c_uint64,

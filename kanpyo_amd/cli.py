@@ -27,7 +27,7 @@ as `count\tword` lines, by count descending and then by the word's bytes ascendi
 wakati's.  A line that is not UTF-8 ends the run with status 101, its 1-based line number on stderr and NOTHING on stdout -- a partial
 frequency table is worse than none; with --skip-invalid such lines are skipped, their numbers go to stderr and the status is 0.
 
-`python -m kanpyo_amd encode [INPUT] -c DICT --vocab FILE [--field N | --base-form | --reading | --pronunciation] [--drop POS[,POS...] | --keep POS[,POS...]]
+`python -m kanpyo_amd encode [INPUT] -c DICT --vocab FILE [--wordpiece [--prefix S] [--max-word-chars N]] [--field N | --base-form | --reading | --pronunciation] [--drop POS[,POS...] | --keep POS[,POS...]]
 [--unk WORD] [--bos WORD] [--eos WORD] [--split host|device] [--skip-invalid]`: NOT a subcommand of the reference either -- every input line becomes
 one output line, the vocabulary ids of its words in decimal, separated by one space (kgpu_encode_batch / kgpu_encode_text; the decimal text is made
 on the host).  FILE has one word per line, line k (0-based) is id k: `count ... | cut -f2` makes one.  --unk (default "<unk>"), --bos and --eos name
@@ -179,7 +179,16 @@ def encode(args, stdin, stdout) -> int:
             print(f"kanpyo_amd: {opt} {word!r} is not a line of {args.vocab}", file=sys.stderr)
             return 2
     enc = lambda w: None if w is None else os.fsencode(w)   # noqa: E731
-    v = Vocab.from_words(_open(args).words(field=args.field, drop=args.drop, keep=args.keep), listed, enc(args.unk), enc(args.bos), enc(args.eos))
+    if not args.wordpiece and (args.prefix is not None or args.max_word_chars is not None):
+        print("kanpyo_amd: --prefix and --max-word-chars go with --wordpiece", file=sys.stderr)
+        return 2
+    wp = {}
+    if args.wordpiece:
+        wp = dict(wordpiece=True, prefix=os.fsencode("##" if args.prefix is None else args.prefix), max_word_chars=100 if args.max_word_chars is None else args.max_word_chars)
+        if len(wp["prefix"]) > 8 or wp["max_word_chars"] > 1024:
+            print("kanpyo_amd: --prefix has at most 8 bytes, --max-word-chars is at most 1024", file=sys.stderr)
+            return 2
+    v = Vocab.from_words(_open(args).words(field=args.field, drop=args.drop, keep=args.keep), listed, enc(args.unk), enc(args.bos), enc(args.eos), **wp)
     out = bytearray()   # (nothing is printed before the input is known to be valid, or --skip-invalid says not to care)
 
     def decimal(result):
@@ -310,7 +319,10 @@ def parse_args(argv=None):
                   first=[("--vocab", dict(required=True, help="The vocabulary: one word per line, line k (0-based) is id k"))],
                   own=[("--unk", dict(default="<unk>", help="The word of the vocabulary whose id a word outside it gets [default: <unk>]")),
                        ("--bos", dict(default=None, help="A word of the vocabulary whose id goes in front of every line's ids")),
-                       ("--eos", dict(default=None, help="A word of the vocabulary whose id goes behind every line's ids"))],
+                       ("--eos", dict(default=None, help="A word of the vocabulary whose id goes behind every line's ids")),
+                       ("--wordpiece", dict(action="store_true", help="The vocabulary is a WordPiece list (a BERT vocab.txt): a word outside it is cut into its longest listed pieces")),
+                       ("--prefix", dict(default=None, help="With --wordpiece: the continuation prefix, at most 8 bytes [default: ##]")),
+                       ("--max-word-chars", dict(type=_top, default=None, help="With --wordpiece: a longer word gets the --unk id [default: 100]"))],
                   skip_invalid="A line that is not UTF-8 prints its bos / eos only instead of ending the run with status 101")
     args = p.parse_args(argv)
     if args.command is None:   # src/bin/kanpyo.rs:173: no subcommand == tokenize from stdin, default dictionary

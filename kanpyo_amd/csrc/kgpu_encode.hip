@@ -24,14 +24,7 @@ constexpr uint32_t WPB = RENDER_WPB;
 
 // The id of the len bytes at p: the slot whose tag carries the hash and whose arena entry holds the same length and bytes; a free slot ends the probe.
 __device__ __forceinline__ int32_t vocab_lookup(const EncodeArgs &a, const uint8_t *p, uint32_t len) {
-    const uint32_t h = key_hash(p, len);
-    uint32_t i = h & a.slot_mask;
-    for (uint64_t probes = 0; probes <= a.slot_mask; ++probes, i = (i + 1) & a.slot_mask) {   // (64-bit: bounded at 2^32 slots too)
-        const uint4 sl = *(const uint4 *)&a.slots[i];   // tag (x, y), id (z)
-        if ((sl.x | sl.y) == 0) break;
-        if (sl.y == h && entry_equals(a.arena + ((uint64_t)sl.x - 1) * 8, h, p, len)) return (int32_t)sl.z;
-    }
-    return a.unk_id;
+    return table_lookup(a, key_hash(p, len), p, len, a.unk_id);   // (kgpu_records_dev.h: the probe loop, shared with kgpu_wordpiece.hip)
 }
 
 }  // namespace

@@ -234,6 +234,49 @@ int32_t vocab_find(const VocabTables &t, const uint8_t *p, uint64_t len, int32_t
 // null when no known row's word is its surface).
 int build_vocab_table(const WordRow *rows, size_t n_rows, size_t n_known, const uint8_t *names, const uint8_t *key_bytes, const uint64_t *key_off,
                       const uint8_t *words, const uint64_t *word_offsets, uint64_t n_words, int32_t unk_id, VocabTables &out, std::string &err);
+// The insert loop of both byte-keyed tables of a handle: n keys (key i is p[i], len[i] bytes, listed under id[i]) into `out.slots` / `out.arena`, which are sized
+// here (slots: a power of two, at least 2 n and at least 16).  *max_len (may be null): the longest key in bytes.  The same bytes twice: KGPU_ERR_INVALID_ARG.
+struct VocabKey { const uint8_t *p; uint64_t len; int32_t id; };
+int fill_vocab_table(const std::vector<VocabKey> &keys, VocabTables &out, uint32_t *max_len, std::string &err);
+// The bytes feature row r is resolved to, as build_vocab_table resolves it (pool name, or the dictionary's key of a known surface row); false: an unknown
+// row whose word is the surface -- not row-determined.
+bool vocab_row_bytes(const WordRow *rows, size_t r, size_t n_known, const uint8_t *names, const uint8_t *key_bytes, const uint64_t *key_off, const uint8_t *&p, uint64_t &len);
+// WordPiece ids (kgpu_wordpiece.hip; include/kanpyo_gpu.h, "WordPiece ids"): a kept token gives the greedy longest-match pieces of its word over two frozen
+// byte-keyed tables -- the initial table (the whole list) for the piece at byte 0, the continuation table (the entries behind the prefix) for the rest.
+struct WordpieceRow { uint32_t first, count; };   // a row-determined word's pieces: count 1: the id itself in `first`; else piece_ids[first .. first + count)
+struct ByteTable { const VocabSlot *slots; uint32_t slot_mask; const uint8_t *arena; uint32_t max_bytes; };   // max_bytes: the longest entry: no longer prefix is probed
+struct WordpieceArgs {
+    RecordsBatch b;                  // the units are ids; text_offsets: the caller's id_offsets
+    WordTable w;
+    const WordpieceRow *rows;        // b.n_rows entries
+    const int32_t *piece_ids;        // the pool behind the rows that split
+    ByteTable initial, cont;         // (prefix_len 0: the same table twice)
+    uint32_t max_chars;              // a word of more characters gives unk_id
+    int32_t unk_id, bos_id, eos_id, pad_id;
+    uint32_t flags;                  // VOCAB_BOS | VOCAB_EOS
+    int32_t *ids; uint64_t id_cap;
+    uint64_t width;                  // 0: ragged; else the padded form's row length
+};
+int launch_wordpiece(const WordpieceArgs &a, void *stream);
+// kgpu_wordpiece_table.cpp (HIP-free; compiles with kgpu_vocab_table.cpp alone): the tables of a WordPiece handle.
+constexpr uint32_t WORDPIECE_MAX_CHARS = 1024, WORDPIECE_DEFAULT_CHARS = 100, WORDPIECE_MAX_PREFIX = 8;
+struct WordpieceTables {
+    VocabTables initial;             // build_vocab_table's, verbatim: slots, arena, row_id (read by nobody on the device), rows_resolved
+    VocabTables cont;                // slots and arena of the continuation entries; EMPTY when `shared`
+    bool shared = false;             // prefix_len == 0: the continuation table IS the initial table
+    uint32_t initial_max = 0, cont_max = 0;   // the longest entry of each table in bytes
+    std::vector<WordpieceRow> rows;
+    std::vector<int32_t> piece_ids;
+    uint64_t cont_words = 0, rows_whole = 0, rows_split = 0, rows_unk = 0;
+    const VocabTables &continuation() const { return shared ? initial : cont; }
+    uint32_t continuation_max() const { return shared ? initial_max : cont_max; }
+};
+enum WordpieceOutcome { WP_EMPTY = 0, WP_WHOLE = 1, WP_SPLIT = 2, WP_UNK = 3 };
+// The split of include/kanpyo_gpu.h, "WordPiece ids", on the host: the pieces of the len bytes at p are APPENDED to out.
+WordpieceOutcome wordpiece_split(const WordpieceTables &t, const uint8_t *p, uint64_t len, uint32_t max_chars, int32_t unk_id, std::vector<int32_t> &out);
+int build_wordpiece_tables(const WordRow *rows, size_t n_rows, size_t n_known, const uint8_t *names, const uint8_t *key_bytes, const uint64_t *key_off,
+                           const uint8_t *words, const uint64_t *word_offsets, uint64_t n_words, int32_t unk_id, const uint8_t *prefix, uint32_t prefix_len,
+                           uint32_t max_chars, WordpieceTables &out, std::string &err);
 // The DOT documents of a batch's kept lattices (kgpu_graphviz.hip; reference src/graphviz.rs:30-163).
 struct GraphvizArgs {
     const uint8_t *utf8;           // as BatchArgs::utf8 / offsets of the launch that kept the lattices

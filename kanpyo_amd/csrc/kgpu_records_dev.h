@@ -8,11 +8,12 @@
 //   write_units      the heart of a text render's third launch: a window of pieces whose starts lie in LDS, assembled into aligned 16-byte units
 //   launch_render    the three launches on a stream: lengths, k_lines_scan (kgpu_format.hip: exclusive scan of sent_len in place, mirrored into the
 //                    caller's offsets, the total published to the host's mapped words), write
-//   key_hash, entry_equals   the byte-keyed tables of the counts and the ids
+//   key_hash, entry_equals, table_lookup   the byte-keyed tables of the counts and the ids
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "kgpu_device.h"
 
@@ -75,16 +76,19 @@ __device__ __forceinline__ void publish_bad(const RecordsBatch &b, bool anybad) 
     if (anybad && (threadIdx.x & 63) == 0) __hip_atomic_store(&b.host_ctl[1], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// A length kernel's body.  units(token, B) -> what the token contributes and whether its record is good; stored(sum) -> the sentence's entry of sent_len.
+// A length kernel's body.  units(token, B) -> what the token contributes and whether its record is good -- or units(token, B, text) where the units depend on
+// the sentence's bytes (kgpu_wordpiece.hip); stored(sum) -> the sentence's entry of sent_len.
 struct Units { uint64_t n; bool ok; };
 template <class U, class S>
 __device__ __forceinline__ void sentence_units(const RecordsBatch &b, U &&units, S &&stored) {
     const uint32_t lane = threadIdx.x & 63;
-    publish_bad(b, walk_sentences<RENDER_WPB, true>(b, [&](uint64_t s, uint64_t k0, uint64_t k1, uint32_t B, const uint8_t *) {
+    publish_bad(b, walk_sentences<RENDER_WPB, true>(b, [&](uint64_t s, uint64_t k0, uint64_t k1, uint32_t B, const uint8_t *text) {
         uint64_t sum = 0;
         bool bad = false;
         for (uint64_t k = k0 + lane; k < k1; k += 64) {
-            const Units u = units(b.tokens[k], B);
+            Units u;
+            if constexpr (std::is_invocable_v<U, const kgpu_token &, uint32_t, const uint8_t *>) u = units(b.tokens[k], B, text);
+            else u = units(b.tokens[k], B);
             sum += u.n;
             bad |= !u.ok;
         }
@@ -146,12 +150,19 @@ int launch_render(void (*len)(Args), void (*write)(Args), const Args &a, void *s
 }
 
 // The byte-keyed tables of the word counts and the vocabulary ids (kgpu_count.hip, kgpu_encode.hip): a key's hash and the compare with an arena entry.
-__device__ __forceinline__ uint32_t key_hash(const uint8_t *p, uint32_t len) {   // FNV-1a over the bytes, then murmur3's finaliser
-    uint32_t h = 2166136261u;
-    for (uint32_t i = 0; i < len; ++i) h = (h ^ p[i]) * 16777619u;
+// key_hash = key_hash_finish(state after the bytes, length): a consumer that walks a word forward once (kgpu_wordpiece.hip) carries the state and finishes
+// it at every prefix it probes.  The value is what the host computes (vocab_key_hash, kgpu_vocab_table.cpp).
+constexpr uint32_t KEY_HASH_INIT = 2166136261u;
+__device__ __forceinline__ uint32_t key_hash_step(uint32_t state, uint32_t byte) { return (state ^ byte) * 16777619u; }   // FNV-1a
+__device__ __forceinline__ uint32_t key_hash_finish(uint32_t h, uint32_t len) {   // the length folded in, then murmur3's finaliser
     h ^= len;
     h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
     return h;
+}
+__device__ __forceinline__ uint32_t key_hash(const uint8_t *p, uint32_t len) {   // FNV-1a over the bytes, then murmur3's finaliser
+    uint32_t h = KEY_HASH_INIT;
+    for (uint32_t i = 0; i < len; ++i) h = key_hash_step(h, p[i]);
+    return key_hash_finish(h, len);
 }
 
 // Does the arena entry at e hold exactly these bytes?  (The entry is padded to 8 bytes: whole words are read from it, single bytes from the text.)
@@ -165,6 +176,20 @@ __device__ __forceinline__ bool entry_equals(const uint8_t *e, uint32_t h, const
             if ((uint32_t)((v >> (8 * b)) & 0xFFu) != p[i + b]) return false;
     }
     return true;
+}
+
+// A READ-ONLY probe of a frozen table of {tag, id} slots (kgpu_vocab_table.cpp; T: anything with `slots`, `slot_mask` and `arena` -- EncodeArgs, ByteTable): the
+// id of the len bytes at p, whose hash is h -- the slot whose tag carries the hash and whose arena entry holds the same length and bytes; a free slot ends
+// the probe -- or `none`.  Plain loads, bounded by the table.
+template <class T>
+__device__ __forceinline__ int32_t table_lookup(const T &a, uint32_t h, const uint8_t *p, uint32_t len, int32_t none) {
+    uint32_t i = h & a.slot_mask;
+    for (uint64_t probes = 0; probes <= a.slot_mask; ++probes, i = (i + 1) & a.slot_mask) {   // (64-bit: bounded at 2^32 slots too)
+        const uint4 sl = *(const uint4 *)&a.slots[i];   // tag (x, y), id (z)
+        if ((sl.x | sl.y) == 0) break;
+        if (sl.y == h && entry_equals(a.arena + ((uint64_t)sl.x - 1) * 8, h, p, len)) return (int32_t)sl.z;
+    }
+    return none;
 }
 
 }  // namespace dev

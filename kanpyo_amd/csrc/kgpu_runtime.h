@@ -155,6 +155,12 @@ struct kgpu_vocab {
     int32_t unk_id = 0, bos_id = 0, eos_id = 0;
     uint64_t n_words = 0, table_slots = 0, key_bytes = 0, rows_resolved = 0;
     void *d_row_id = nullptr, *d_slots = nullptr, *d_arena = nullptr;
+    // a WordPiece handle (kgpu_vocab_create_wordpiece): the continuation table (the initial table's pointers again when the prefix is empty: `cont_shared`),
+    // the 8-byte row entries and the pool behind them, uploaded once; d_row_id stays null -- the plain kernels never see such a handle
+    bool wordpiece = false, cont_shared = false;
+    uint32_t max_word_chars = 0, initial_max = 0, cont_max = 0;
+    void *d_cont_slots = nullptr, *d_cont_arena = nullptr, *d_wp_rows = nullptr, *d_piece_ids = nullptr;
+    kgpu_wordpiece_info wp{};
 };
 
 struct kgpu_ctx {

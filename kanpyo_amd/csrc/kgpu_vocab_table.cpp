@@ -50,33 +50,24 @@ int32_t vocab_find(const VocabTables &t, const uint8_t *p, uint64_t len, int32_t
     return found ? t.slots[i].id : unk;
 }
 
-int build_vocab_table(const WordRow *rows, size_t n_rows, size_t n_known, const uint8_t *names, const uint8_t *key_bytes, const uint64_t *key_off,
-                      const uint8_t *words, const uint64_t *word_offsets, uint64_t n_words, int32_t unk_id, VocabTables &out, std::string &err) {
-    out = VocabTables{};
-    if (n_words > 0x7FFFFFFFull) { err = "more than 2^31 - 1 words"; return KGPU_ERR_INVALID_ARG; }
-    if (n_words && !word_offsets) { err = "words without offsets"; return KGPU_ERR_INVALID_ARG; }
+int fill_vocab_table(const std::vector<VocabKey> &keys, VocabTables &out, uint32_t *max_len, std::string &err) {
     uint64_t arena_bytes = 0;
-    for (uint64_t i = 0; i < n_words; ++i) {
-        if (word_offsets[i + 1] < word_offsets[i]) { err = "word offsets run backwards at " + std::to_string(i); return KGPU_ERR_INVALID_ARG; }
-        const uint64_t len = word_offsets[i + 1] - word_offsets[i];
-        if (len >= (1ull << 30)) { err = "word " + std::to_string(i) + " has 2^30 bytes or more"; return KGPU_ERR_INVALID_ARG; }
-        arena_bytes += COUNT_ENTRY_HEAD + ((len + 7) & ~7ull);
-    }
-    if (n_words && word_offsets[n_words] != word_offsets[0] && !words) { err = "word offsets without words"; return KGPU_ERR_INVALID_ARG; }
+    for (const VocabKey &k : keys) arena_bytes += COUNT_ENTRY_HEAD + ((k.len + 7) & ~7ull);
     if (arena_bytes / 8 + 1 >= (1ull << 32)) { err = "the words take 32 GiB of key arena or more"; return KGPU_ERR_INVALID_ARG; }
     size_t slots = 16;
-    while (slots < 2 * n_words) slots <<= 1;
+    while (slots < 2 * keys.size()) slots <<= 1;
     out.slots.assign(slots, VocabSlot{0, 0, {0, 0}});
     out.arena.assign((size_t)arena_bytes + 16, 0);   // (16 spare bytes: the device reads whole 8-byte words of an entry, never past its padding)
     uint64_t at = 0;
-    for (uint64_t i = 0; i < n_words; ++i) {
-        const uint64_t len = word_offsets[i + 1] - word_offsets[i];
-        const uint8_t *p = len ? words + word_offsets[i] : nullptr;
+    uint32_t longest = 0;
+    for (const VocabKey &k : keys) {
+        const uint64_t len = k.len;
+        const uint8_t *p = len ? k.p : nullptr;
         const uint32_t h = vocab_key_hash(p, len);
         bool found;
         const size_t slot = probe(out, h, p, len, found);
         if (found) {
-            err = "words " + std::to_string(out.slots[slot].id) + " and " + std::to_string(i) + " of the list are the same bytes";
+            err = "words " + std::to_string(out.slots[slot].id) + " and " + std::to_string(k.id) + " of the list are the same bytes";
             return KGPU_ERR_INVALID_ARG;
         }
         uint8_t *e = out.arena.data() + at;
@@ -85,17 +76,43 @@ int build_vocab_table(const WordRow *rows, size_t n_rows, size_t n_known, const 
         std::memcpy(e + 4, &h, 4);
         if (len) std::memcpy(e + COUNT_ENTRY_HEAD, p, (size_t)len);
         out.slots[slot].tag = ((unsigned long long)h << 32) | (at / 8 + 1);
-        out.slots[slot].id = (int32_t)i;
+        out.slots[slot].id = k.id;
         at += COUNT_ENTRY_HEAD + ((len + 7) & ~7ull);
+        if (len32 > longest) longest = len32;
     }
+    if (max_len) *max_len = longest;
+    return KGPU_OK;
+}
+
+bool vocab_row_bytes(const WordRow *rows, size_t r, size_t n_known, const uint8_t *names, const uint8_t *key_bytes, const uint64_t *key_off, const uint8_t *&p, uint64_t &len) {
+    const WordRow &row = rows[r];
+    if (!(row.len_flags & WORD_SURFACE)) { p = names + row.off; len = row.len_flags & WORD_LEN_MASK; return true; }
+    if (r < n_known && key_off) { p = key_bytes + key_off[r]; len = key_off[r + 1] - key_off[r]; return true; }
+    return false;   // an unknown row whose word is the surface: looked up by its bytes, token by token
+}
+
+int build_vocab_table(const WordRow *rows, size_t n_rows, size_t n_known, const uint8_t *names, const uint8_t *key_bytes, const uint64_t *key_off,
+                      const uint8_t *words, const uint64_t *word_offsets, uint64_t n_words, int32_t unk_id, VocabTables &out, std::string &err) {
+    out = VocabTables{};
+    if (n_words > 0x7FFFFFFFull) { err = "more than 2^31 - 1 words"; return KGPU_ERR_INVALID_ARG; }
+    if (n_words && !word_offsets) { err = "words without offsets"; return KGPU_ERR_INVALID_ARG; }
+    for (uint64_t i = 0; i < n_words; ++i) {
+        if (word_offsets[i + 1] < word_offsets[i]) { err = "word offsets run backwards at " + std::to_string(i); return KGPU_ERR_INVALID_ARG; }
+        const uint64_t len = word_offsets[i + 1] - word_offsets[i];
+        if (len >= (1ull << 30)) { err = "word " + std::to_string(i) + " has 2^30 bytes or more"; return KGPU_ERR_INVALID_ARG; }
+    }
+    if (n_words && word_offsets[n_words] != word_offsets[0] && !words) { err = "word offsets without words"; return KGPU_ERR_INVALID_ARG; }
+    std::vector<VocabKey> keys((size_t)n_words);
+    for (uint64_t i = 0; i < n_words; ++i) {
+        const uint64_t len = word_offsets[i + 1] - word_offsets[i];
+        keys[(size_t)i] = VocabKey{len ? words + word_offsets[i] : nullptr, len, (int32_t)i};
+    }
+    if (int rc = fill_vocab_table(keys, out, nullptr, err)) return rc;
     out.row_id.assign(n_rows, unk_id);
     for (size_t r = 0; r < n_rows; ++r) {
-        const WordRow &row = rows[r];
         const uint8_t *p;
         uint64_t len;
-        if (!(row.len_flags & WORD_SURFACE)) { p = names + row.off; len = row.len_flags & WORD_LEN_MASK; }
-        else if (r < n_known && key_off) { p = key_bytes + key_off[r]; len = key_off[r + 1] - key_off[r]; }
-        else continue;   // an unknown row whose word is the surface: looked up by its bytes, token by token
+        if (!vocab_row_bytes(rows, r, n_known, names, key_bytes, key_off, p, len)) continue;
         const int32_t none = -1;   // (list indices are never negative)
         const int32_t id = vocab_find(out, len ? p : nullptr, len, none);
         if (id != none) { out.row_id[r] = id; ++out.rows_resolved; }

@@ -194,10 +194,11 @@ class Words(Handle):
         """A WordCounts handle with this handle's field and filter (kgpu_counts_create); None: the header's defaults."""
         return WordCounts(self, table_slots, key_bytes)
 
-    def vocabulary(self, words, unk_id: int, bos_id=None, eos_id=None) -> "Vocab":
+    def vocabulary(self, words, unk_id: int, bos_id=None, eos_id=None, wordpiece=False, prefix="##", max_word_chars=100) -> "Vocab":
         """kgpu_vocab_create: a Vocab with this handle's field and filter.  words: the list (str or bytes), id k is words[k]; a kept token whose
-        word is not listed gets unk_id (any int32); bos_id / eos_id: None, or the id put in front of / behind every sentence's ids."""
-        return Vocab(self, words, unk_id, bos_id, eos_id)
+        word is not listed gets unk_id (any int32); bos_id / eos_id: None, or the id put in front of / behind every sentence's ids.
+        wordpiece=True (kgpu_vocab_create_wordpiece): a word outside the list is cut into its longest listed pieces, continuation pieces behind `prefix`."""
+        return Vocab(self, words, unk_id, bos_id, eos_id, wordpiece, prefix, max_word_chars)
 
 
 class WordCounts(Handle):

@@ -4,6 +4,10 @@ A Vocab is made from a Words handle (Words.vocabulary, WordCounts.vocabulary, Vo
 token gives the index of its word in the list, or unk_id; a sentence's sequence is [bos] ids... [eos].  The host forms return numpy arrays
 (ragged: ids + id_offsets); encode_tensor leaves everything in device memory as torch tensors, ragged -- the (input, offsets) pair
 torch.nn.EmbeddingBag takes -- or padded to [n, width].
+
+wordpiece=True (include/kanpyo_gpu.h, "WordPiece ids"): the list is a BERT vocab.txt -- a word outside it is cut greedily into its longest listed
+pieces, continuation pieces listed behind the prefix ("##"), and a kept token gives zero, one or many ids.  What is pinned is that split rule, not
+equal input_ids with a real BERT-Japanese tokenizer (which also normalises its text and needs the real IPADIC).
 """
 from __future__ import annotations
 
@@ -23,6 +27,16 @@ def _word_bytes(w) -> bytes:
     return w.encode("utf-8") if isinstance(w, str) else bytes(w)
 
 
+def wordpiece_opts(prefix="##", max_word_chars=100) -> "_lib.WordpieceOpts":
+    """kgpu_wordpiece_opts of a prefix (str or bytes, at most 8 bytes) and a character limit (1..1024); ValueError otherwise."""
+    p = _word_bytes(prefix)
+    if len(p) > 8:
+        raise ValueError(f"the prefix {p!r} has more than 8 bytes")
+    if not 1 <= int(max_word_chars) <= 1024:
+        raise ValueError("max_word_chars is 1..1024")
+    return _lib.WordpieceOpts(C.sizeof(_lib.WordpieceOpts), int(max_word_chars), len(p), (C.c_uint8 * 8)(*p))
+
+
 class Vocab(Handle):
     """A vocabulary handle (kgpu_vocab): a frozen word -> id table on the device.  Immutable; usable from many threads at once; it keeps its
     Words handle's tables and the dictionary alive and may outlive both (encode_tensor alone needs the Tokenizer open).  .words is the list (bytes), id k is words[k]."""
@@ -30,16 +44,22 @@ class Vocab(Handle):
     _destroy = "kgpu_vocab_destroy"
     _ctx = None   # encode_tensor's DeviceContext, made by its first call
 
-    def __init__(self, words_handle, words: Sequence, unk_id: int, bos_id=None, eos_id=None):
+    def __init__(self, words_handle, words: Sequence, unk_id: int, bos_id=None, eos_id=None, wordpiece=False, prefix="##", max_word_chars=100):
         self.words = [_word_bytes(w) for w in words]
+        self.wordpiece = bool(wordpiece)
+        self._wp = wordpiece_opts(prefix, max_word_chars) if wordpiece else None
         self.unk_id, self.bos_id, self.eos_id = int(unk_id), bos_id, eos_id
         flags = (_lib.KGPU_VOCAB_ADD_BOS if bos_id is not None else 0) | (_lib.KGPU_VOCAB_ADD_EOS if eos_id is not None else 0)
         packed, offs = pack_sentences(self.words)
         packed = np.ascontiguousarray(packed)
         opts = _lib.VocabOpts(C.sizeof(_lib.VocabOpts), flags, int(unk_id), int(bos_id or 0), int(eos_id or 0))
         h = C.c_void_p()
-        _lib.check(_lib.lib().kgpu_vocab_create(words_handle.handle, ptr(packed), offs.ctypes.data, len(self.words),
-                                                C.byref(opts), C.byref(h)))
+        if wordpiece:
+            _lib.check(_lib.lib().kgpu_vocab_create_wordpiece(words_handle.handle, ptr(packed), offs.ctypes.data, len(self.words),
+                                                              C.byref(opts), C.byref(self._wp), C.byref(h)))
+        else:
+            _lib.check(_lib.lib().kgpu_vocab_create(words_handle.handle, ptr(packed), offs.ctypes.data, len(self.words),
+                                                    C.byref(opts), C.byref(h)))
         self._h = h
         self._tokenizer = words_handle.tokenizer   # (encode_tensor's context is made from it)
         self._device = self._tokenizer.info()["device"]
@@ -60,6 +80,19 @@ class Vocab(Handle):
         i = _lib.VocabInfo(C.sizeof(_lib.VocabInfo))
         _lib.check(_lib.lib().kgpu_vocab_get_info(self._h, C.byref(i)))
         return struct_dict(i)
+
+    def wordpiece_info(self) -> dict:
+        """kgpu_vocab_get_wordpiece_info: the continuation table, the row outcomes, the pool (KgpuError on a plain Vocab)."""
+        i = _lib.WordpieceInfo(C.sizeof(_lib.WordpieceInfo))
+        _lib.check(_lib.lib().kgpu_vocab_get_wordpiece_info(self._h, C.byref(i)))
+        return struct_dict(i)
+
+    def split_words(self, words: Sequence) -> List[np.ndarray]:
+        """The split of each word (str or bytes) by this WordPiece Vocab's list, prefix and limit: one int32 array of list indices (or unk_id) per word.
+        HOST ONLY, through the library's host implementation of the rule: a way to look at a split, not a hot path."""
+        if not self.wordpiece:
+            raise ValueError("split_words: not a WordPiece vocabulary")
+        return split_words(self.words, words, self.unk_id, self._wp)
 
     # ---- host memory in and out ------------------------------------------------------------------------------------------------------------
     def encode_packed(self, utf8: np.ndarray, offsets: np.ndarray, out=None):
@@ -125,16 +158,20 @@ class Vocab(Handle):
                 break
             n_tok = int(got.value)
             d_ioff = torch.empty(n + 1, dtype=torch.int64, device=dev)
-            if width is None:
-                id_cap = n_tok + n * self._extra   # (every record kept, and bos / eos: never too small)
-                d_ids = torch.empty(max(id_cap, 1), dtype=torch.int32, device=dev)
-            else:
-                id_cap = n * int(width)
-                d_ids = torch.empty((n, int(width)), dtype=torch.int32, device=dev)
-            torch.cuda.synchronize(dev)
-            ctx.encode(self, d_utf8.data_ptr(), d_off.data_ptr(), n, d_tok.data_ptr(), d_toff.data_ptr(), d_ids.data_ptr(), id_cap, d_ioff.data_ptr(),
-                       width=0 if width is None else int(width), pad_id=int(pad_id))
-            count = ctx.sync_lines()
+            id_cap = n_tok + n * self._extra if width is None else n * int(width)   # (ragged, a plain Vocab: every record kept, and bos / eos: never too small)
+            while True:   # (a WordPiece Vocab's tokens may give several ids each: once more with the count the device reports)
+                d_ids = torch.empty(max(id_cap, 1), dtype=torch.int32, device=dev) if width is None else torch.empty((n, int(width)), dtype=torch.int32, device=dev)
+                torch.cuda.synchronize(dev)
+                ctx.encode(self, d_utf8.data_ptr(), d_off.data_ptr(), n, d_tok.data_ptr(), d_toff.data_ptr(), d_ids.data_ptr(), id_cap, d_ioff.data_ptr(),
+                           width=0 if width is None else int(width), pad_id=int(pad_id))
+                got = C.c_uint64(0)
+                rc = L.kgpu_ctx_sync_lines(ctx._h, C.byref(got))
+                if rc == _lib.KGPU_ERR_CAPACITY and width is None and int(got.value) > id_cap:
+                    id_cap = int(got.value)
+                    continue
+                _lib.check(rc)
+                break
+            count = int(got.value)
         if width is None:
             return d_ids[:count], d_ioff, d_st[:n]
         return d_ids, torch.clamp(d_ioff[1:] - d_ioff[:-1], max=int(width)), d_st[:n]
@@ -159,12 +196,13 @@ class Vocab(Handle):
         return lines
 
     @classmethod
-    def load(cls, words_handle, path, unk="<unk>", bos=None, eos=None) -> "Vocab":
-        """A Vocab over the file's list.  unk, bos, eos: WORDS that must be in the file (ValueError otherwise); bos / eos None: not added."""
-        return cls.from_words(words_handle, cls.read_words(path), unk, bos, eos)
+    def load(cls, words_handle, path, unk="<unk>", bos=None, eos=None, wordpiece=False, prefix="##", max_word_chars=100) -> "Vocab":
+        """A Vocab over the file's list.  unk, bos, eos: WORDS that must be in the file (ValueError otherwise); bos / eos None: not added.
+        wordpiece=True reads a BERT vocab.txt as it is: load(words, "vocab.txt", unk="[UNK]", bos="[CLS]", eos="[SEP]", wordpiece=True)."""
+        return cls.from_words(words_handle, cls.read_words(path), unk, bos, eos, wordpiece, prefix, max_word_chars)
 
     @classmethod
-    def from_words(cls, words_handle, words: Sequence, unk="<unk>", bos=None, eos=None) -> "Vocab":
+    def from_words(cls, words_handle, words: Sequence, unk="<unk>", bos=None, eos=None, wordpiece=False, prefix="##", max_word_chars=100) -> "Vocab":
         """A Vocab whose unk / bos / eos ids are the list indices of those words."""
         words = [_word_bytes(w) for w in words]
         index = {}
@@ -179,4 +217,21 @@ class Vocab(Handle):
             if b not in index:
                 raise ValueError(f"the {what} word {b!r} is not in the vocabulary")
             ids.append(index[b])
-        return cls(words_handle, words, ids[0], ids[1], ids[2])
+        return cls(words_handle, words, ids[0], ids[1], ids[2], wordpiece, prefix, max_word_chars)
+
+
+def split_words(vocab: Sequence, words: Sequence, unk_id: int, opts=None) -> List[np.ndarray]:
+    """kgpu_debug_wordpiece_split: the WordPiece split of each of `words` by the list `vocab` (opts: wordpiece_opts(...), None: "##", 100), on the
+    host, with no device and no handle -> one int32 array per word."""
+    vp, voff = pack_sentences([_word_bytes(w) for w in vocab])
+    ip, ioff = pack_sentences([_word_bytes(w) for w in words])
+    vp, ip = np.ascontiguousarray(vp), np.ascontiguousarray(ip)
+    n = len(ioff) - 1
+    ooff = np.zeros(n + 1, dtype=np.uint64)
+    got = C.c_uint64(0)
+    cap = int(ioff[-1]) + 1   # (a piece is a byte at least; an over-long word is one id)
+    ids = np.empty(cap, dtype=np.int32)
+    _lib.check(_lib.lib().kgpu_debug_wordpiece_split(ptr(vp), voff.ctypes.data, len(voff) - 1, C.byref(opts) if opts is not None else None, int(unk_id),
+                                                     ptr(ip), ioff.ctypes.data, n, ids.ctypes.data, cap, ooff.ctypes.data, C.byref(got)))
+    o = ooff.tolist()
+    return [ids[o[i] : o[i + 1]].copy() for i in range(n)]
