@@ -160,6 +160,7 @@ Chain build_chain(const LaunchPlan &plan, const Batch &b, Steering &st, ContextS
     }
     if (general || ch.n == 0) ch.steps[ch.n++] = general_step(plan, b.n, ch.last_list());
     ch.small_scan = window && (pools == 0 || cs.long_share);
+    ch.aux_one_launch = pools > 0 && !ch.small_scan && b.n <= AUX_ONE_LAUNCH_MAX;
     return ch;
 }
 

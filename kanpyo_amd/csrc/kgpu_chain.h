@@ -57,10 +57,15 @@ struct Chain {
     int n = 0;
     bool event_behind_first = false;  // the first-launch event goes behind steps[0] (a pool launch); otherwise in front of the chain
     bool small_scan = false;          // the scan / compaction behind it runs small workgroups (launch_scan_compact)
+    bool aux_one_launch = false;      // ... is ONE launch without LDS (k_aux_one_launch): a pool launch in front, no small_scan, at most AUX_ONE_LAUNCH_MAX sentences
     int pools() const;
     const Step *find(Kernel k) const;
     int last_list() const { return n ? steps[n - 1].out : -1; }   // >= 0: the chain ended without the general kernel, on this list
 };
+
+// The largest batch whose scan and compaction are one launch: every wavefront of that launch sums the counts in front of its sentences itself, reads that
+// grow with the square of the batch (measured at 4096; larger batches keep the two launches).
+constexpr uint64_t AUX_ONE_LAUNCH_MAX = 4096;
 
 // What the chain of a batch is built from.
 struct Batch {

@@ -55,6 +55,7 @@ extern "C" int kgpu_ctx_create(kgpu_dict *d, void *hip_stream, kgpu_ctx **out) {
     hipDeviceProp_t p;
     const int cus = hipGetDeviceProperties(&p, d->device) == hipSuccess ? p.multiProcessorCount : 256;
     c->plan = make_launch_plan(cus, Occupancy{pool_workgroups_per_cu, window_workgroups_per_cu, window_team_workgroups_per_cu});
+    c->aux_mode = test_hooks().aux_launch;
     *out = c;
     return KGPU_OK;
 }
@@ -146,7 +147,7 @@ static int run_chain(kgpu_ctx *c, const BatchArgs &a, const hipEvent_t *ev, cons
     // measured with 16 hardware queues, cfg 2 100.5 -> 72.9 M sentences/s -- whatever lets a fifth pool launch start early loses, profiles/experiments/r05_long_chains.txt)
     if (ev) HIPCHECK(hipEventRecord(ev[1], c->stream));
     c->h_ctl->pack_overflow = 0;  // set by the compaction's workgroups in the host copy directly; this context's previous batch has been synced
-    hipError_t e = (hipError_t)launch_scan_compact(a, c->h_ctl_dev, c->stream, ch.small_scan);
+    hipError_t e = (hipError_t)launch_scan_compact(a, c->h_ctl_dev, c->stream, ch.small_scan, ch.aux_one_launch, c->aux_mode, &c->aux_form);
     if (e != hipSuccess) { set_error("scan/compact launch: %s", hipGetErrorString(e)); return KGPU_ERR_HIP; }
     if (ev) HIPCHECK(hipEventRecord(ev[2], c->stream));
     HIPCHECK(hipEventRecord(c->done_ev, c->stream));
@@ -355,6 +356,9 @@ extern "C" int kgpu_ctx_sync(kgpu_ctx *c, uint64_t *n_tokens) {
     }
     return KGPU_OK;
 }
+
+// Tests only (not in the header): the form of the context's last scan + compaction, as launch_scan_compact numbers it (0: none yet).
+extern "C" int kgpu_debug_aux_form(kgpu_ctx *c) { return c ? c->aux_form : -1; }
 
 extern "C" int kgpu_ctx_set_profiling(kgpu_ctx *c, int mode) {
     if (!c) { set_error("kgpu_ctx_set_profiling: null ctx"); return KGPU_ERR_INVALID_ARG; }

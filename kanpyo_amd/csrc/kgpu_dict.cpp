@@ -70,6 +70,7 @@ TestHooks kgpu::test_hooks() {
         // ... and the bytes of the scratch arena a chunk's kept lattices may use at first / at most (0: the whole arena / ARENA_MAX): tests of the overflow protocol
         if (const char *e = getenv("KGPU_HOST_GRAPHVIZ_ARENA_INITIAL")) cur.graphviz_arena_initial = strtoull(e, nullptr, 10);
         if (const char *e = getenv("KGPU_HOST_GRAPHVIZ_ARENA_MAX")) cur.graphviz_arena_max = strtoull(e, nullptr, 10);
+        if (const char *e = getenv("KGPU_AUX_LAUNCH")) cur.aux_launch = atoi(e);   // scan + compaction behind a chain: 0 two launches, 1 one, 2 two with the single-wavefront scan (read when a context is created)
         if (const char *e = getenv("KGPU_MULTI_CHUNK_SENTS")) cur.multi_chunk_sents = strtoull(e, nullptr, 10);  // kgpu_tokenize_batch_multi: sentences per device and chunk (tests: many small super-chunks)
     }
     return cur;

@@ -142,7 +142,7 @@ int launch_step(const DictView &d, const BatchArgs &a, const Step &s, uint32_t s
 int launch_general_only(const DictView &d, const BatchArgs &a, void *stream);  // kgpu_lattice_dump: HBM-scratch kernel alone
 int launch_general_keep(const DictView &d, const BatchArgs &a, void *stream);  // kgpu_graphviz_batch: ... over a whole batch, a.keep_lattice set
 int launch_small_call(const DictView &d, const BatchArgs &a, void *stream);  // pool kernel alone, one sentence per wavefront
-int launch_scan_compact(const BatchArgs &a, Control *host_ctl, void *stream, bool small_workgroups);  // host_ctl: device pointer of the pinned result block
+int launch_scan_compact(const BatchArgs &a, Control *host_ctl, void *stream, bool small_workgroups, bool one_launch, int mode, int *form);  // host_ctl: device pointer of the pinned result block; one_launch: Chain::aux_one_launch; mode: KGPU_AUX_LAUNCH
 // What every consumer of a batch's 24-byte records reads (kgpu_records_dev.h: the lines, the wakati lines, the vocabulary ids, the word counts).
 constexpr uint32_t feature_row(bool known, uint32_t n_morph, uint32_t id) { return (known ? 0u : n_morph) + id - 1; }   // known id k at row k - 1, unknown id u at n_morph + u - 1
 struct RecordsBatch {

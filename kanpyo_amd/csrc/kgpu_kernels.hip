@@ -528,6 +528,116 @@ __global__ __launch_bounds__(256) void k_scan_compact(BatchArgs a, Control *host
     }
 }
 
+// The control block of a launch, published by the wavefront that knows the batch's total: every dword to the pinned host copy (n_tokens from `total`;
+// not pack_overflow, which the compaction's wavefronts set in the host copy directly and the host clears before the launch), the device copy zeroed.
+__device__ __forceinline__ void publish_control(const BatchArgs &a, Control *host_ctl, uint64_t total, uint32_t lane) {
+    static_assert(sizeof(Control) % 4 == 0, "Control is copied dword by dword");
+    for (uint32_t k = lane; k < sizeof(Control) / 4; k += 64) {
+        uint32_t *dc = (uint32_t *)a.ctl, *hc = (uint32_t *)host_ctl;
+        uint32_t x = dc[k];
+        const uint32_t nt = (uint32_t)(offsetof(Control, n_tokens) / 4);
+        if (k == nt) x = (uint32_t)total;
+        if (k == nt + 1) x = (uint32_t)(total >> 32);
+        if (k != (uint32_t)(offsetof(Control, pack_overflow) / 4)) __hip_atomic_store(&hc[k], x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        dc[k] = 0;
+    }
+}
+
+// Scan + compaction in ONE launch WITHOUT LDS and without a barrier (pool-only chains of up to AUX_ONE_LAUNCH_MAX sentences: kgpu_chain.cpp).  The pool
+// plan fills a CU's LDS (four 40 KB workgroups) and four of the five wavefront slots per SIMD that the pool kernel's registers allow: a workgroup that asks
+// for ANY LDS -- k_scan_counts, k_scan_compact -- waits until a pool workgroup has drained, one that asks for none and has at most four wavefronts takes the
+// spare slot at once.  A wavefront owns G (at most 64) consecutive sentences.  It sums the token counts in front of them itself (the pool kernel has just
+// written them: L2 hits, 16-byte loads, lane-strided), scans its own G counts on the DPP network, stores their offsets and copies their records as
+// k_compact / k_compact8 do.  The wavefront that owns sentence n - 1 knows the total: it writes tok_offsets[n] (and toff8[n]) and publishes the control
+// block.  No wavefront waits for another.  n = 0: one wavefront that publishes {0}.
+// (The toff8 stores are not reached today: launch_scan_compact keeps k_scan_compact for batches with a.toff8 -- the large host call -- until that path is
+// measured with this kernel.  They are what k_scan_compact / k_compact8 write, so that the switch is the launcher's condition alone.)
+template <bool REC8>
+__global__ __launch_bounds__(256) void k_aux_one_launch(BatchArgs a, Control *host_ctl, uint32_t G) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t wave = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const uint64_t s0 = wave * G;
+    if (s0 >= a.n && wave != 0) return;   // (wave-uniform; wave 0 of an empty batch stays)
+    uint64_t part = 0;
+    const uint4 *c4 = (const uint4 *)a.tok_count;   // (the buffer's start: 16-byte aligned)
+    const uint64_t q = s0 >> 2;
+#pragma unroll 4
+    for (uint64_t i = lane; i < q; i += 64) { const uint4 c = c4[i]; part += (uint64_t)c.x + c.y + c.z + c.w; }
+    if (4 * q + lane < s0) part += a.tok_count[4 * q + lane];
+    const uint64_t prefix = wave_sum64(part);
+    const uint64_t si = s0 + lane;
+    const bool mine = lane < G && si < a.n;
+    const uint32_t v = mine ? a.tok_count[si] : 0u;
+    const uint64_t slot = mine ? a.offsets[si] - a.offsets[0] + si : 0u;   // the sentence's first staging slot
+    const uint32_t vs = wave_incl_scan(v, lane);
+    const uint64_t off = prefix + vs - v;
+    if (mine) a.tok_offsets[si] = off;
+    if (s0 + G >= a.n) {   // the batch's last sentence is this wavefront's
+        const uint64_t total = prefix + (uint32_t)__builtin_amdgcn_readlane((int)vs, 63);
+        if (lane == 0) { a.tok_offsets[a.n] = total; if (a.toff8) a.toff8[a.n] = total; }
+        publish_control(a, host_ctl, total, lane);
+    }
+    for (uint32_t t = 0; t < G && s0 + t < a.n; ++t) {
+        const uint64_t sx = s0 + t;
+        const uint32_t cnt = (uint32_t)__builtin_amdgcn_readlane((int)v, (int)t);
+        const uint64_t dst = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(off >> 32), (int)t) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)off, (int)t);
+        const uint64_t sl = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(slot >> 32), (int)t) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)slot, (int)t);
+        const kgpu_token *src = a.stage + sl;
+        if constexpr (REC8) {
+            if (lane == 0) {
+                const uint2 f = cnt ? make_uint2(src[0].position, src[0].start) : make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
+                *(uint2 *)(a.first8 + 2 * sx) = f;
+                if (a.status8) a.status8[sx] = a.status[sx];
+                if (a.toff8) a.toff8[sx] = dst;
+            }
+            if (dst + cnt > a.out_cap) continue;
+            bool bad = false;
+            for (uint32_t k = lane; k < cnt; k += 64) {
+                const kgpu_token tk = src[k];
+                const uint32_t chars = tk.end - tk.start;
+                bad |= chars > 0xFFFu || tk.byte_len > 0x3FFFFu;
+                *(uint2 *)(a.out8 + dst + k) = make_uint2((uint32_t)tk.id, tk.cls | (chars << 2) | (tk.byte_len << 14));
+            }
+            if (__ballot(bad) != 0 && lane == 0) __hip_atomic_store(&host_ctl->pack_overflow, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        } else {
+            if (dst + cnt > a.out_cap) continue;
+            const uint32_t *srcw = (const uint32_t *)src;
+            uint32_t *out = (uint32_t *)(a.out + dst);
+            for (uint32_t w = lane; w < cnt * 6; w += 64) out[w] = srcw[w];
+        }
+    }
+}
+
+// k_scan_counts without LDS: ONE wavefront, behind a chain with small_scan (a chip full of windowed workgroups has no free LDS either: cfg 3, seven
+// interleaved pairs: 33.7-34.3 -> 34.5-34.6 M sentences/s in batches of 65 536; 16.2-16.7 -> 16.6-17.1 in batches of 4096, above in each pair, the ranges overlap; behind a pool-only chain it is level with k_scan_counts or below).  A round covers 4096 counts: each lane sums 64 consecutive ones (sixteen 16-byte
+// loads issued together), the lane totals are scanned on the DPP network, the lane writes its 64 offsets; the carry goes from round to round in a register.
+__global__ __launch_bounds__(64) void k_scan_counts_wave(BatchArgs a, Control *host_ctl) {
+    const uint32_t lane = threadIdx.x;
+    uint64_t carry = 0;
+    for (uint64_t base = 0; base < a.n; base += 4096) {
+        const uint64_t i0 = base + 64u * lane;
+        uint32_t c[64];
+        if (i0 + 64 <= a.n) {
+            const uint4 *c4 = (const uint4 *)(a.tok_count + i0);
+#pragma unroll
+            for (uint32_t k = 0; k < 16; ++k) { const uint4 x = c4[k]; c[4 * k] = x.x; c[4 * k + 1] = x.y; c[4 * k + 2] = x.z; c[4 * k + 3] = x.w; }
+        } else {
+#pragma unroll
+            for (uint32_t k = 0; k < 64; ++k) c[k] = i0 + k < a.n ? a.tok_count[i0 + k] : 0u;
+        }
+        uint64_t sum = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < 64; ++k) sum += c[k];
+        const uint64_t vs = wave_incl_scan64(sum, lane);
+        uint64_t o = carry + vs - sum;
+#pragma unroll
+        for (uint32_t k = 0; k < 64; ++k) { if (i0 + k < a.n) a.tok_offsets[i0 + k] = o; o += c[k]; }
+        carry += lane63(vs);
+    }
+    if (lane == 0) { a.tok_offsets[a.n] = carry; if (a.toff8) a.toff8[a.n] = carry; }
+    publish_control(a, host_ctl, carry, lane);
+}
+
 int launch_tokenize_pool(const DictView &d, const BatchArgs &a, const WorkIO &io, uint32_t pool_bytes, uint32_t waves,
                          uint32_t max_pages, int n_workgroups, uint32_t stop_after, void *stream);  // kgpu_pool.hip
 int launch_tokenize_window(const DictView &d, const BatchArgs &a, const WorkIO &io, uint32_t lds_bytes, int n_workgroups, bool team, bool claim, void *stream);  // kgpu_window.hip
@@ -567,10 +677,32 @@ int launch_general_keep(const DictView &d, const BatchArgs &a, void *stream) {
     return (int)hipGetLastError();
 }
 
-int launch_scan_compact(const BatchArgs &a, Control *host_ctl, void *stream, bool small_workgroups) {
+#ifndef KGPU_AUX_G
+#define KGPU_AUX_G 4   // sentences per wavefront of k_aux_one_launch up to 4096 sentences (make NAME=g8 EXTRA=-DKGPU_AUX_G=8: A/B runs only)
+#endif
+// one_launch: what the batch's chain decided (Chain::aux_one_launch); mode: KGPU_AUX_LAUNCH (measurement / test only) -- 0 two launches, 1 one launch
+// whatever the chain says (batches of up to 65 536 sentences), 2 two launches with the single-wavefront scan, anything else: by the chain (one launch where it
+// asks for it; otherwise two, the single-wavefront scan where the chain asks for small workgroups).  0 is what ran before the one launch existed.
+// *form: what was launched (kgpu_debug_aux_form: the tests' witness) -- 1 k_aux_one_launch, 2 k_scan_compact, 3 k_scan_counts + compaction, 4 k_scan_counts_wave + compaction.
+int launch_scan_compact(const BatchArgs &a, Control *host_ctl, void *stream, bool small_workgroups, bool one_launch, int mode, int *form) {
     // Measured (tools/ab_scan.sh): records bound for mapped host memory (the large host call: a.toff8) 83.8 against 66.6 M sentences/s end to end in one
     // launch; the device-resident 24-byte path 92.8 against 96.9 -- there the separate kernels stay.
+    if (!a.toff8 && a.n <= 65536 && (mode == 1 || (one_launch && mode != 0 && mode != 2))) {
+        // G sentences per wavefront: four up to 4096 sentences (1024 wavefronts, a prefix of 2048 counts on average; eight, this kernel built
+        // with -DKGPU_AUX_G=8: 134.7-136.2 M sentences/s on cfg 2 where four gave 137.6-139.3 and the two launches 131.5-136.0), then as many as keep the grid
+        // there (forced runs only: the chain asks for one launch up to 4096 sentences) -- the prefix reads grow as n * n / G.  Workgroups of four wavefronts
+        // (one per SIMD: the pool plan's spare slot), one where a windowed launch fills the chip.  profiles/experiments/aux_one_launch.txt
+        uint32_t G = KGPU_AUX_G;
+        *form = 1;
+        while (G < 64 && (uint64_t)G * 1024 < a.n) G *= 2;
+        const uint64_t waves = a.n ? (a.n + G - 1) / G : 1, wpb = small_workgroups || waves < 4 ? 1 : 4;
+        const unsigned wgs = (unsigned)((waves + wpb - 1) / wpb);
+        if (a.out8) hipLaunchKernelGGL(k_aux_one_launch<true>, dim3(wgs), dim3((unsigned)(64 * wpb)), 0, (hipStream_t)stream, a, host_ctl, G);
+        else hipLaunchKernelGGL(k_aux_one_launch<false>, dim3(wgs), dim3((unsigned)(64 * wpb)), 0, (hipStream_t)stream, a, host_ctl, G);
+        return (int)hipGetLastError();
+    }
     if (a.n <= 65536 && a.toff8) {
+        *form = 2;
         const uint32_t per_wg = a.n <= 4096 ? 64u : a.n <= 16384 ? 128u : 256u;
         const uint64_t wgs = a.n ? (a.n + per_wg - 1) / per_wg : 1;
         if (a.out8) hipLaunchKernelGGL(k_scan_compact<true>, dim3((unsigned)wgs), dim3(256), 0, (hipStream_t)stream, a, host_ctl, per_wg);
@@ -580,7 +712,10 @@ int launch_scan_compact(const BatchArgs &a, Control *host_ctl, void *stream, boo
     // small_workgroups: behind a chain that holds a windowed launch the chip is full of single-wavefront workgroups at four 128-VGPR wavefronts per SIMD -- a
     // workgroup of one wavefront finds a place as soon as ANY of them ends, one of sixteen (or four) needs a CU (or a SIMD row) to drain
     const unsigned scan_threads = !small_workgroups ? 1024u : a.n > 1024 ? 256u : 64u, wpb = small_workgroups ? 1u : 4u;
-    hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(scan_threads), 0, (hipStream_t)stream, a, host_ctl);
+    const bool wave_scan = mode == 2 || (small_workgroups && mode != 0);
+    *form = wave_scan ? 4 : 3;
+    if (wave_scan) hipLaunchKernelGGL(k_scan_counts_wave, dim3(1), dim3(64), 0, (hipStream_t)stream, a, host_ctl);
+    else hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(scan_threads), 0, (hipStream_t)stream, a, host_ctl);
     uint64_t blocks = (a.n + wpb - 1) / wpb;
     if (blocks > 2048 * (4 / wpb)) blocks = 2048 * (4 / wpb);
     if (blocks == 0) blocks = 1;

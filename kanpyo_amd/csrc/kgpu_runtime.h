@@ -206,6 +206,8 @@ struct kgpu_ctx {
     BatchArgs last{};
     bool pending = false;
     LaunchPlan plan{};
+    int aux_form = 0;    // what the last batch's scan + compaction was (launch_scan_compact; kgpu_debug_aux_form)
+    int aux_mode = -1;   // KGPU_AUX_LAUNCH as the context found it when it was created (launch_scan_compact; -1: the chain decides)
     DevBuf ovf;
     DevBuf stat_slots;                             // profiling runs: per-wavefront counters of the pool kernel (BatchArgs::stat_slots)
     std::vector<unsigned long long> stat_host;
@@ -280,7 +282,7 @@ struct WorkerPool {
     void task_done(std::atomic<int> &counter); // a task's last statement
 };
 WorkerPool &workers();
-struct TestHooks { bool no_small_calls = false, plain_leaves = false, byte_trie = false; uint64_t chunk_bytes = 4ull << 20, chunk_sents = 16384, depth = 12, multi_chunk_sents = 0, graphviz_chunk_sents = 0, graphviz_arena_initial = 0, graphviz_arena_max = 0; };
+struct TestHooks { bool no_small_calls = false, plain_leaves = false, byte_trie = false; uint64_t chunk_bytes = 4ull << 20, chunk_sents = 16384, depth = 12, multi_chunk_sents = 0, graphviz_chunk_sents = 0, graphviz_arena_initial = 0, graphviz_arena_max = 0; int aux_launch = -1; };
 TestHooks test_hooks();  // test-only environment hooks, read once per process (or per call under KGPU_TEST_HOOKS_REREAD)
 bool env_flag_now(const char *name);
 

@@ -31,6 +31,8 @@ while time.time() < t_end:
     os.environ["KGPU_WINDOW_TEAM"] = rng.choice(["-1", "-1", "0", "2", "2"])     # the two-wavefronts-per-sentence form of window-first chains: by the load / never / always
     os.environ["KGPU_WINDOW_FIRST"] = rng.choice(["1024", "1024", "0", "64", "300"])  # average bytes per sentence from which a chain starts with the windowed kernel
     os.environ["KGPU_BYTE_TRIE"] = "1" if rng.random() < 0.15 else "0"  # (read at dictionary creation: KGPU_TEST_HOOKS_REREAD below)
+    aux = rng.choice([None, None, "0", "1", "2"])   # scan + compaction behind a chain: by the chain / two launches / one / two with the single-wavefront scan (read when a context is created)
+    os.environ.pop("KGPU_AUX_LAUNCH", None) if aux is None else os.environ.__setitem__("KGPU_AUX_LAUNCH", aux)
     if rng.random() < 0.4:  # a dense little dictionary: wide buckets, many targets -- or keys of every UTF-8 width, or a matrix that is not square
         kind = rng.random()
         if kind < 0.45:
@@ -42,7 +44,7 @@ while time.time() < t_end:
             matrix_rounds += 1
             print(f"    matrix_case {meta['shape']} {meta['rows']}x{meta['cols']} costs={meta['cost']} ranked={meta['ranked']}", flush=True)
         tok, orc = Tokenizer(dd), oracle.OracleTokenizer.from_dict(dd)
-        print(f"[{time.time() - (t_end - budget):6.1f}s] dense / width / matrix dictionary byte_trie={os.environ['KGPU_BYTE_TRIE']} pool={pool} window={window_kib} team={os.environ['KGPU_WINDOW_TEAM']} first={os.environ['KGPU_WINDOW_FIRST']} n={len(mix)}", flush=True)
+        print(f"[{time.time() - (t_end - budget):6.1f}s] dense / width / matrix dictionary byte_trie={os.environ['KGPU_BYTE_TRIE']} pool={pool} window={window_kib} team={os.environ['KGPU_WINDOW_TEAM']} first={os.environ['KGPU_WINDOW_FIRST']} aux={aux} n={len(mix)}", flush=True)
         utf8, offs = pack_sentences(mix)
         exp = orc.tokenize_batch(utf8, offs, 16)
         got_t, got_off, status = tok.tokenize_packed(utf8, offs)
@@ -54,7 +56,7 @@ while time.time() < t_end:
         continue
     sd = synth.build_dict(nkeys, seed=rng.randrange(1 << 30))
     tok, orc = Tokenizer(sd.dict), oracle.OracleTokenizer.from_dict(sd.dict)
-    print(f"[{time.time() - (t_end - budget):6.1f}s] keys={nkeys} byte_trie={os.environ['KGPU_BYTE_TRIE']} pool={pool} window={window_kib} team={os.environ['KGPU_WINDOW_TEAM']} first={os.environ['KGPU_WINDOW_FIRST']}", flush=True)
+    print(f"[{time.time() - (t_end - budget):6.1f}s] keys={nkeys} byte_trie={os.environ['KGPU_BYTE_TRIE']} pool={pool} window={window_kib} team={os.environ['KGPU_WINDOW_TEAM']} first={os.environ['KGPU_WINDOW_FIRST']} aux={aux}", flush=True)
     for _ in range(3):
         mix = synth.mixed_case(sd, rng)
         utf8, offs = pack_sentences(mix)
