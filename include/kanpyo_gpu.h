@@ -613,7 +613,7 @@ int kgpu_encode_device(kgpu_ctx *c, const kgpu_vocab *v, const uint8_t *d_utf8, 
  * A WordPiece vocabulary is a kgpu_vocab made by kgpu_vocab_create_wordpiece; kgpu_encode_batch, kgpu_encode_text, kgpu_encode_device,
  * kgpu_vocab_get_info and kgpu_vocab_destroy take it as they take a plain one.  A kept token gives the PIECES of its word: zero, one or many
  * ids.  These are the rules of BERT's WordpieceTokenizer, stated on bytes.  NOT claimed: equal input_ids with a real BERT-Japanese tokenizer,
- * which also normalises its text (NFKC) and segments with the real IPADIC; what is claimed is the split below.
+ * which segments with the real IPADIC (its NFKC is available: "text normalisation" below); what is claimed is the split below.
  *  1. Which tokens, which word.  Rules 1 and 2 of "vocabulary ids", unchanged: the tokens wakati keeps; the dictionary's key for a known token
  *     whose word is its surface.
  *  2. Characters.  A character of a word starts at byte 0 and at every byte that is not 10xxxxxx: defined for any bytes, UTF-8 or not.  A
@@ -658,6 +658,53 @@ typedef struct kgpu_wordpiece_info {
 int kgpu_vocab_create_wordpiece(kgpu_words *w, const uint8_t *words, const uint64_t *word_offsets, uint64_t n_words,
                                 const kgpu_vocab_opts *opts, const kgpu_wordpiece_opts *wp, kgpu_vocab **out);
 int kgpu_vocab_get_wordpiece_info(const kgpu_vocab *v, kgpu_wordpiece_info *info);   /* KGPU_ERR_INVALID_ARG on a plain vocabulary */
+
+/* ---- text normalisation: NFC / NFKC of lines on the device (NOT an output of the reference: the first stage of every MeCab-style pipeline; half-width
+ * katakana, full-width ASCII, U+3231, U+2460 and U+3000 match no IPADIC key and no vocabulary line until they have been through NFKC) ----
+ * The tables are derived from Unicode kgpu_normalize_unicode_version() (tools/gen_normalize_tables.py) and are dictionary-independent: the kgpu_dict *
+ * of the calls below only names the device and the context pool.  They are uploaded by a handle's first normalise call (about 200 KB, counted in
+ * kgpu_dict_info.device_bytes).
+ *  1. Line i of the output is line i of the input, always; text_offsets has n + 1 entries.  The empty line is the empty line.
+ *  2. Boundary.  A code point c has a BOUNDARY BEFORE it, for a form with decomposition D (NFD for NFC, NFKD for NFKC), when ccc(c) == 0 and the first
+ *     code point f of D(c) has ccc(f) == 0, is the second member of no primary composition pair and is no Hangul V or T jamo (U+1161-1175,
+ *     U+11A8-11C2).  (Not "ccc 0 and quick-check Yes": under this rule every full-width letter starts a segment of its own, and half-width KA + the
+ *     half-width voiced mark are one.)
+ *  3. Segment.  A segment starts at a line's first code point and at every boundary, and ends before the next boundary or at the line's end.  The
+ *     normalised line is the concatenation of the normalised segments.
+ *  4. Inert.  c is inert when it has a boundary before it and the form maps it to itself.  A segment of one inert code point is copied as it is
+ *     (nearly all of Japanese text).  Any other segment is decomposed (the full canonical or compatibility decomposition; Hangul syllables by
+ *     arithmetic), its non-starters are put into canonical order (a stable sort by combining class), and it is composed (the 941 primary pairs of
+ *     Unicode 13 and Hangul LV / LVT; a non-starter is blocked as UAX #15 says).  Unassigned code points, noncharacters and private use are inert.
+ *  5. Oversize.  A segment holds its first code point and KGPU_NORMALIZE_MAX_SEGMENT more after decomposition: a starter with 64 combining marks is
+ *     normalised, one with 65 is not (UAX #15's stream-safe limit is 30).  A line with a longer segment is copied unchanged and gets
+ *     KGPU_SENT_NOT_NORMALIZED.
+ *  6. A line that is not UTF-8 is copied unchanged with KGPU_SENT_INVALID_UTF8: a later tokenize call reports the same line.
+ *  7. Capacity.  The output has up to 11 times the input's bytes (U+FDFA: 3 -> 33).  KGPU_ERR_CAPACITY: *n_bytes is the exact size needed (the
+ *     kgpu_tokenize_batch_lines protocol) and nothing was written; kgpu_normalize_text reports *n_lines too, and either may be what did not fit.
+ *  8. An unknown form and null arguments are KGPU_ERR_INVALID_ARG, returned before anything touches a device.  The host forms take less than 4 GiB a call.
+ *  9. The device result equals kgpu_normalize_host on every line, for any bytes: both run the same segment code over the same tables.  The one
+ *     difference is a single line of 4 GiB or more: kgpu_normalize_host rejects it (KGPU_ERR_INVALID_ARG), kgpu_normalize_device, which never sees
+ *     the lengths on the host, copies it unchanged with KGPU_SENT_NOT_NORMALIZED (positions inside a line are 32-bit). */
+#define KGPU_NORMALIZE_NFC 1
+#define KGPU_NORMALIZE_NFKC 2
+#define KGPU_NORMALIZE_MAX_SEGMENT 64
+#define KGPU_SENT_NOT_NORMALIZED 4 /* per-line status of the normalise calls: a segment was oversize (rule 5), the line is unchanged */
+const char *kgpu_normalize_unicode_version(void); /* "13.0.0" */
+/* Host, no device needed: one string.  status may be NULL. */
+int kgpu_normalize_host(int form, const uint8_t *in, uint64_t len, uint8_t *out, uint64_t capacity, uint64_t *n_bytes, uint8_t *status);
+/* Host memory in and out, normalised on the device: n lines packed as kgpu_tokenize_batch takes them.  status may be NULL. */
+int kgpu_normalize_batch(kgpu_dict *d, int form, const uint8_t *utf8, const uint64_t *offsets, uint64_t n,
+                         uint8_t *text, uint64_t text_capacity, uint64_t *text_offsets, uint8_t *status, uint64_t *n_bytes);
+/* A raw block in host memory: split + trim on the device (kgpu_split_lines_device), then normalised; the arguments of kgpu_tokenize_text_lines. */
+int kgpu_normalize_text(kgpu_dict *d, int form, const uint8_t *text, uint64_t len, uint8_t *out_text, uint64_t text_capacity,
+                        uint64_t *text_offsets, uint64_t offsets_capacity, uint8_t *status, uint64_t *n_lines, uint64_t *n_bytes);
+/* Device-resident, enqueued on c's stream: three launches whatever the batch holds.  d_text must not overlap d_utf8 (KGPU_ERR_INVALID_ARG where the
+ * call can tell: d_utf8 inside d_text's text_capacity bytes).  d_text_offsets: n + 1, d_status: n.  kgpu_ctx_sync_normalize waits and reports the byte
+ * count: KGPU_ERR_CAPACITY (nothing written to d_text) when it exceeds text_capacity.  One render, count, encode or normalise may be pending per
+ * context, whichever kind.  The normalised buffers are what kgpu_tokenize_device takes next. */
+int kgpu_normalize_device(kgpu_ctx *c, int form, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n,
+                          uint8_t *d_text, uint64_t text_capacity, uint64_t *d_text_offsets, uint8_t *d_status);
+int kgpu_ctx_sync_normalize(kgpu_ctx *c, uint64_t *n_bytes);
 
 #ifdef __cplusplus
 }

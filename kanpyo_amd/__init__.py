@@ -7,7 +7,7 @@ fallback, importing the tokenizer without the built library raises.
 """
 from .token import Token, TokenClass  # noqa: F401
 from .dict import Dict  # noqa: F401
-from .tokenizer import Tokenizer, TOKEN_DTYPE  # noqa: F401
+from .tokenizer import Tokenizer, TOKEN_DTYPE, normalize_host  # noqa: F401
 from .vocab import Vocab  # noqa: F401
 
-__all__ = ["Token", "TokenClass", "Dict", "Tokenizer", "TOKEN_DTYPE", "Vocab"]
+__all__ = ["Token", "TokenClass", "Dict", "Tokenizer", "TOKEN_DTYPE", "Vocab", "normalize_host"]

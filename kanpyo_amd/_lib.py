@@ -19,6 +19,9 @@ KGPU_SENT_OK = 0
 KGPU_SENT_INVALID_UTF8 = 1
 KGPU_SENT_NO_SCRATCH = 2
 KGPU_SENT_TRUNCATED = 3
+KGPU_SENT_NOT_NORMALIZED = 4   # the normalise calls: a segment was oversize, the line is unchanged
+NORMALIZE_NFC, NORMALIZE_NFKC = 1, 2
+KGPU_NORMALIZE_MAX_SEGMENT = 64
 
 # every symbol include/kanpyo_gpu.h declares
 SYMBOLS = [
@@ -34,6 +37,7 @@ SYMBOLS = [
     "kgpu_count_words_device", "kgpu_ctx_sync_count", "kgpu_counts_read",
     "kgpu_vocab_create", "kgpu_vocab_destroy", "kgpu_vocab_get_info", "kgpu_encode_batch", "kgpu_encode_text", "kgpu_encode_device",
     "kgpu_vocab_create_wordpiece", "kgpu_vocab_get_wordpiece_info",
+    "kgpu_normalize_unicode_version", "kgpu_normalize_host", "kgpu_normalize_batch", "kgpu_normalize_text", "kgpu_normalize_device", "kgpu_ctx_sync_normalize",
 ]
 KGPU_VOCAB_ADD_BOS, KGPU_VOCAB_ADD_EOS = 1, 2
 KGPU_COUNTS_DEFAULT_SLOTS, KGPU_COUNTS_DEFAULT_KEY_BYTES = 1 << 22, 256 << 20
@@ -41,14 +45,24 @@ KGPU_WORDS_SURFACE = -1
 KGPU_WORDS_ALL, KGPU_WORDS_DROP, KGPU_WORDS_KEEP = 0, 1, 2
 
 
+def normalize_form(form) -> int:
+    """"NFC" / "NFKC" (any case), or the header's 1 / 2 -> KGPU_NORMALIZE_*; ValueError otherwise."""
+    key = form.upper() if isinstance(form, str) else form
+    if key in ("NFC", NORMALIZE_NFC):
+        return NORMALIZE_NFC
+    if key in ("NFKC", NORMALIZE_NFKC):
+        return NORMALIZE_NFKC
+    raise ValueError(f"unknown normalisation form {form!r}: NFC or NFKC")
+
+
 def kernel_source_hash() -> str:
-    """sha256[:16] over every source and header the library is built from (csrc/*.hip, *.cpp, *.h, sorted, and the public header).
+    """sha256[:16] over every source and header the library is built from (csrc/*.hip, *.cpp, *.h, *.inc, sorted, and the public header).
     Profile-derived files under profiles/ record it, bench.py compares: a counter file measured on other code says so (`stale`)."""
     import glob
     import hashlib
 
     csrc = os.path.join(_HERE, "csrc")
-    names = sorted(os.path.basename(p) for ext in ("hip", "cpp", "h") for p in glob.glob(os.path.join(csrc, "*." + ext)))
+    names = sorted(os.path.basename(p) for ext in ("hip", "cpp", "h", "inc") for p in glob.glob(os.path.join(csrc, "*." + ext)))
     h = hashlib.sha256()
     for name in names + ["../../include/kanpyo_gpu.h"]:
         with open(os.path.join(csrc, name), "rb") as f:
@@ -241,6 +255,13 @@ def lib():
                                              C.POINTER(C.c_uint64)]
         L.kgpu_vocab_create_wordpiece.argtypes = [vp, vp, vp, C.c_uint64, C.POINTER(VocabOpts), C.POINTER(WordpieceOpts), C.POINTER(vp)]
         L.kgpu_vocab_get_wordpiece_info.argtypes = [vp, C.POINTER(WordpieceInfo)]
+        L.kgpu_normalize_unicode_version.argtypes = []
+        L.kgpu_normalize_unicode_version.restype = C.c_char_p
+        L.kgpu_normalize_host.argtypes = [C.c_int, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint8)]
+        L.kgpu_normalize_batch.argtypes = [vp, C.c_int, vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, C.POINTER(C.c_uint64)]
+        L.kgpu_normalize_text.argtypes = [vp, C.c_int, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.kgpu_normalize_device.argtypes = [vp, C.c_int, vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp]
+        L.kgpu_ctx_sync_normalize.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.kgpu_debug_wordpiece_table.argtypes = [vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.c_uint64, C.c_uint64, C.POINTER(WordsSpec), vp, vp, C.c_uint64,
                                                  C.POINTER(VocabOpts), C.POINTER(WordpieceOpts), vp, vp, vp, vp, vp, vp, vp, C.POINTER(WordpieceInfo)]
         L.kgpu_debug_wordpiece_split.argtypes = [vp, vp, C.c_uint64, C.POINTER(WordpieceOpts), C.c_int32, vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.POINTER(C.c_uint64)]

@@ -34,12 +34,22 @@ on the host).  FILE has one word per line, line k (0-based) is id k: `count ... 
 words that must be in the file (exit status 2 otherwise); a word outside the file gets --unk's id, --bos / --eos put theirs around every line's ids.
 The words and the filter are wakati's.  A line that is not UTF-8 is handled as `count` handles it: status 101, its line number on stderr and NOTHING
 on stdout; with --skip-invalid such a line prints its bos / eos only.
+
+`--normalize {none,nfc,nfkc}` (default none) on `tokenize`, `wakati`, `count`, `encode` and `graphviz`: the input -- INPUT, or stdin's lines with either
+--split -- is normalised on the device first (include/kanpyo_gpu.h, "text normalisation"), and what is printed are the surfaces and words of the
+NORMALISED text: half-width katakana, full-width letters and digits, U+3231 and the ideographic space then match the dictionary's keys.
+
+`python -m kanpyo_amd normalize [INPUT] [-c DICT] [--form nfkc|nfc] [--split host|device]`: NOT a subcommand of the reference either -- the
+normalised lines themselves, one output line per input line (kgpu_normalize_batch / kgpu_normalize_text).  Like every subcommand it needs a
+dictionary: the device work runs on a dictionary handle's context pool.  A line that is not UTF-8 ends the run with status 101 as `wakati` does; a
+line with an oversize segment prints unchanged, with a warning on stderr.
 """
 from __future__ import annotations
 
 import argparse
 import os
 import sys
+from functools import partial
 
 import numpy as np
 
@@ -111,10 +121,19 @@ def _results(args, stdin, packed_call, text_call):
     return (packed_call(*split_lines(b)) for b in _blocks(stdin, args.block_bytes))
 
 
+def _warn_unnormalized(status, line0: int) -> None:
+    """One stderr line per line the normaliser left as it was (status 4: a segment too long), by its 1-based number."""
+    for i in np.flatnonzero(status == 4).tolist():
+        print(f"kanpyo_amd: line {line0 + i + 1}: a segment is too long to normalise (left unchanged)", file=sys.stderr)
+
+
 def _print_lines(results, stdout, panic: str) -> int:
     """Each result's text as soon as it is there; a line that is not UTF-8 ends the run behind the lines before it."""
+    line0 = 0
     for text, toff, status in results:
         bad = np.flatnonzero(status == 1)
+        _warn_unnormalized(status[: int(bad[0])] if bad.size else status, line0)
+        line0 += len(status)
         if bad.size:
             stdout.write(text[: int(toff[bad[0]])].tobytes())
             stdout.flush()
@@ -135,26 +154,61 @@ def _each_checked(results, skip_invalid: bool, consume=None) -> int:
             print(f"kanpyo_amd: line {line0 + i + 1}: not valid UTF-8" + (" (skipped)" if skip_invalid else ""), file=sys.stderr)
             if not skip_invalid:
                 return PANIC_STATUS
+        _warn_unnormalized(status, line0)
         line0 += len(status)
         if consume is not None:
             consume(r)
     return 0
 
 
+def _form(args):
+    """--normalize as the binding's keyword: None, "NFC" or "NFKC"."""
+    form = getattr(args, "normalize", "none")
+    return None if form == "none" else form.upper()
+
+
 def tokenize(args, stdin, stdout) -> int:
     tok = _open(args)
-    return _print_lines(_results(args, stdin, tok.tokenize_lines_packed, tok.tokenize_text_lines), stdout,
+    packed, text = tok.tokenize_lines_packed, tok.tokenize_text_lines
+    if _form(args):
+        packed, text = partial(packed, normalize=_form(args)), partial(text, normalize=_form(args))
+    return _print_lines(_results(args, stdin, packed, text), stdout,
                         "thread 'main' panicked: failed to read from stdin: stream did not contain valid UTF-8")
 
 
+def _words(args, **kw):
+    """The Words handle of the command's field and filter; with --normalize it normalises whatever goes through it."""
+    if _form(args):
+        kw["normalize"] = _form(args)
+    return _open(args).words(field=args.field, drop=args.drop, keep=args.keep, **kw)
+
+
+def normalize(args, stdin, stdout) -> int:
+    tok = _open(args)
+    form = args.form.upper()
+    line0 = 0
+    for text, toff, status in _results(args, stdin, partial(tok.normalize_packed, form=form), partial(tok.normalize_text, form=form)):
+        bad = np.flatnonzero(status == 1)
+        shown = int(bad[0]) if bad.size else len(status)
+        _warn_unnormalized(status[:shown], line0)
+        raw, o = text.tobytes(), toff.tolist()
+        stdout.write(b"".join(raw[o[i] : o[i + 1]] + b"\n" for i in range(shown)))
+        stdout.flush()
+        if bad.size:
+            print("kanpyo_amd: failed to read from stdin: stream did not contain valid UTF-8", file=sys.stderr)
+            return PANIC_STATUS
+        line0 += len(status)
+    return 0
+
+
 def wakati(args, stdin, stdout) -> int:
-    w = _open(args).words(field=args.field, drop=args.drop, keep=args.keep, separator=os.fsencode(args.separator))
+    w = _words(args, separator=os.fsencode(args.separator))
     return _print_lines(_results(args, stdin, w.render_packed, w.render_text), stdout,
                         "kanpyo_amd: failed to read from stdin: stream did not contain valid UTF-8")
 
 
 def count(args, stdin, stdout) -> int:
-    counts = _open(args).words(field=args.field, drop=args.drop, keep=args.keep).counter()
+    counts = _words(args).counter()
     if _each_checked(_results(args, stdin, counts.add_packed, counts.add_text), args.skip_invalid):
         return PANIC_STATUS   # nothing has been printed
     out = bytearray()
@@ -188,7 +242,7 @@ def encode(args, stdin, stdout) -> int:
         if len(wp["prefix"]) > 8 or wp["max_word_chars"] > 1024:
             print("kanpyo_amd: --prefix has at most 8 bytes, --max-word-chars is at most 1024", file=sys.stderr)
             return 2
-    v = Vocab.from_words(_open(args).words(field=args.field, drop=args.drop, keep=args.keep), listed, enc(args.unk), enc(args.bos), enc(args.eos), **wp)
+    v = Vocab.from_words(_words(args), listed, enc(args.unk), enc(args.bos), enc(args.eos), **wp)
     out = bytearray()   # (nothing is printed before the input is known to be valid, or --skip-invalid says not to care)
 
     def decimal(result):
@@ -253,8 +307,11 @@ def graphviz(args, stdin, stdout) -> int:
         except UnicodeDecodeError:
             print("thread 'main' panicked: failed to read from stdin: stream did not contain valid UTF-8", file=sys.stderr)
             return PANIC_STATUS
-    one = np.frombuffer(raw, dtype=np.uint8)
-    text, _, status = _open(args).graphviz_packed(one, np.array([0, one.size], dtype=np.uint64), dpi=args.dpi, full_state=args.full_state)
+    one, offs = np.frombuffer(raw, dtype=np.uint8), np.array([0, len(raw)], dtype=np.uint64)
+    tok = _open(args)
+    if _form(args):   # the lattice of the normalised sentence
+        one, offs, _ = tok.normalize_packed(one, offs, _form(args))
+    text, _, status = tok.graphviz_packed(one, offs, dpi=args.dpi, full_state=args.full_state)
     if status[0]:   # (an INPUT argument that is not UTF-8: the reference's argument parser rejects it)
         print(f"kanpyo_amd: the input cannot be drawn (sentence status {int(status[0])})", file=sys.stderr)
         return 2
@@ -269,6 +326,10 @@ def _dpi(text: str) -> int:
     if not digits.isascii() or not digits.isdigit() or int(digits) >= 1 << 64:
         raise argparse.ArgumentTypeError(f"invalid value {text!r}: an unsigned integer below 2^64")
     return int(digits)
+
+
+NORMALIZE_CHOICES = ["none", "nfc", "nfkc"]
+NORMALIZE_HELP = "Normalise the input on the device first: the output refers to the normalised text [default: none]"
 
 
 def _text_command(sub, name: str, help: str, verb: str = None, first=(), own=(), skip_invalid: str = None):
@@ -291,6 +352,8 @@ def _text_command(sub, name: str, help: str, verb: str = None, first=(), own=(),
         flt.add_argument("--keep", type=_pos_list, default=[], help="Keep only tokens whose part of speech is one of POS[,POS...]")
     for flag, kw in own:
         p.add_argument(flag, **kw)
+    if name != "normalize":
+        p.add_argument("--normalize", choices=NORMALIZE_CHOICES, default="none", help=NORMALIZE_HELP)
     p.add_argument("--split", choices=["host", "device"], default="host",
                    help="Where stdin's blocks are split into lines and trimmed [default: host]")
     if skip_invalid:
@@ -300,7 +363,7 @@ def _text_command(sub, name: str, help: str, verb: str = None, first=(), own=(),
 
 
 def parse_args(argv=None):
-    """The reference's command line (src/bin/kanpyo.rs:14-49).  -> the namespace; .command is "tokenize" or "graphviz" -- or "wakati", "count" or "encode", which are this package's own."""
+    """The reference's command line (src/bin/kanpyo.rs:14-49).  -> the namespace; .command is "tokenize" or "graphviz" -- or "wakati", "count", "encode" or "normalize", which are this package's own."""
     p = argparse.ArgumentParser(prog="kanpyo_amd", description="Japanese Morphological Analyzer (kanpyo) on AMD Instinct GPUs")
     sub = p.add_subparsers(dest="command")
     t = _text_command(sub, "tokenize", "Tokenize input text")
@@ -310,6 +373,9 @@ def parse_args(argv=None):
     g.add_argument("-c", "--custom-dict", default=None, help="Custom dictionary (.dict)")
     g.add_argument("-f", "--full-state", action="store_true", help="Output full state of lattice")
     g.add_argument("--dpi", type=_dpi, default=48, help="DPI of output image [default: 48]")
+    g.add_argument("--normalize", choices=NORMALIZE_CHOICES, default="none", help=NORMALIZE_HELP)
+    _text_command(sub, "normalize", "NFC / NFKC of each input line (not in the reference)",
+                  own=[("--form", dict(choices=["nfkc", "nfc"], default="nfkc", help="The normalisation form [default: nfkc]"))])
     _text_command(sub, "wakati", "One line of separated words per input line (not in the reference)", "Print",
                   own=[("--separator", dict(type=_separator, default=" ", help="The byte between words [default: a space]"))])
     _text_command(sub, "count", "Word frequencies of the whole input (not in the reference)", "Count",
@@ -344,6 +410,8 @@ def main(argv=None) -> int:
             return count(args, sys.stdin.buffer, sys.stdout.buffer)
         if args.command == "encode":
             return encode(args, sys.stdin.buffer, sys.stdout.buffer)
+        if args.command == "normalize":
+            return normalize(args, sys.stdin.buffer, sys.stdout.buffer)
         return tokenize(args, sys.stdin.buffer, sys.stdout.buffer)
     except _lib.KgpuError as e:
         print(f"kanpyo_amd: {e}", file=sys.stderr)

@@ -75,7 +75,7 @@ extern "C" void kgpu_ctx_destroy(kgpu_ctx *c) {
     c->lines_report.release(); c->split_report.release();
     c->lines_len.release(); c->lines_text.release(); c->lines_off.release(); c->lines_status.release();
     c->split_agg.release(); c->split_raw.release(); c->split_text.release(); c->split_off.release();
-    c->gv_desc.release(); c->gv_len.release(); c->gv_text.release();
+    c->gv_desc.release(); c->gv_len.release(); c->gv_text.release(); c->norm_text.release();
     if (c->switch_ev) (void)hipEventDestroy(c->switch_ev);
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
     c->arena.release(); c->ovf.release(); c->stat_slots.release(); c->stage.release(); c->tok_count.release();

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/kanpyo_gpu.h"
+#include "kgpu_normalize_core.h"
 
 namespace kgpu {
 
@@ -306,6 +307,28 @@ struct SplitArgs {
 };
 uint32_t split_tiles(const uint8_t *d_in, uint64_t len);
 int launch_split_lines(const SplitArgs &a, void *stream);
+
+// Text normalisation (kgpu_normalize.hip; include/kanpyo_gpu.h, "text normalisation"): line i of the batch, NFC or NFKC, into text[text_offsets[i] ..).
+struct NormArgs {
+    NormTables t;                      // the tables in device memory (kgpu_normalize_core.h)
+    uint32_t form;                     // NORM_FORM_NFC / NORM_FORM_NFKC
+    const uint8_t *utf8;               // line i is utf8[offsets[i] .. offsets[i + 1])
+    const uint64_t *offsets;           // n + 1
+    uint64_t n;
+    uint64_t *sent_len;                // device scratch, n + 1: each line's output bytes, then (k_lines_scan, in place) their offsets
+    uint8_t *mode;                     // device scratch, n: how the write pass treats the line
+    uint64_t *text_offsets;            // n + 1: the scan's mirror for the caller
+    uint8_t *status;                   // n
+    uint8_t *text; uint64_t text_cap;  // nothing is stored when sent_len[n] > text_cap
+    unsigned long long *host_ctl;      // device pointer of pinned, mapped words: [0] the output's bytes
+};
+int launch_normalize(const NormArgs &a, void *stream);
+// kgpu_normalize_table.cpp (HIP-free, compiles alone): the tables in host memory, their sizes in bytes, and one line on the host -> its status; out_len is
+// the normalised length, and the bytes are in `out` when they fit `capacity` (the line itself where the status is not KGPU_SENT_OK)
+struct NormTableSizes { size_t stage1, stage2, dec, pool, comp_key, comp_val; };
+NormTables norm_host_tables();
+NormTableSizes norm_table_sizes();
+uint8_t norm_line_host(uint32_t form, const uint8_t *s, uint32_t len, uint8_t *out, uint64_t capacity, uint64_t &out_len);
 
 int pool_workgroups_per_cu(uint32_t pool_bytes, uint32_t waves);
 int window_workgroups_per_cu(uint32_t lds_bytes);

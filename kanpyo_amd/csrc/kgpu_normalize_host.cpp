@@ -1,0 +1,133 @@
+// kanpyo_amd/csrc/kgpu_normalize_host.cpp -- NFC / NFKC on the device (kgpu_normalize.hip) behind the C ABI (include/kanpyo_gpu.h, "text normalisation").
+//
+// Owns: the upload of the tables (kgpu_normalize_table.cpp holds them; once per dictionary handle), kgpu_normalize_device / kgpu_ctx_sync_normalize (a batch
+// resident in HBM, on a context's stream, reported through the context's lines_report as a render is), and the two host forms: kgpu_normalize_batch (packed
+// lines: one copy to the device, the three launches, the results back) and kgpu_normalize_text (a raw block: split_block first, the normaliser reads the
+// split's output where it lies).  Each host call is one batch on one pooled context: the normaliser moves a byte or two per input byte.
+#include <vector>
+
+#include "kgpu_runtime.h"
+
+static bool known_form(int form) { return form == KGPU_NORMALIZE_NFC || form == KGPU_NORMALIZE_NFKC; }
+
+static int ensure_norm_tables(kgpu_dict *d) {
+    std::lock_guard<std::mutex> g(d->feat_mu);   // (the lock of everything a handle uploads after its creation: allocs and device_bytes change under it)
+    if (d->norm_ready) return KGPU_OK;
+    const NormTables h = norm_host_tables();
+    const NormTableSizes z = norm_table_sizes();
+    const void *src[6] = {h.stage1, h.stage2, h.dec, h.pool, h.comp_key, h.comp_val};
+    const size_t bytes[6] = {z.stage1, z.stage2, z.dec, z.pool, z.comp_key, z.comp_val};
+    size_t at[6], total = 0;
+    for (int k = 0; k < 6; ++k) { at[k] = total; total += (bytes[k] + 15) & ~(size_t)15; }
+    uint8_t *p = nullptr;
+    HIPCHECK(hipMalloc((void **)&p, total));
+    for (int k = 0; k < 6; ++k)
+        if (hipMemcpy(p + at[k], src[k], bytes[k], hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(p); set_error("upload of the normaliser's tables failed"); return KGPU_ERR_HIP; }
+    d->allocs.push_back(p);   // (recorded once it is whole: a failed upload leaves nothing behind)
+    d->info.device_bytes += total;
+    d->norm = NormTables{(const uint16_t *)(p + at[0]), (const uint32_t *)(p + at[1]), (const uint32_t *)(p + at[2]), (const uint32_t *)(p + at[3]),
+                         (const uint64_t *)(p + at[4]), (const uint32_t *)(p + at[5]), h.n_comp};
+    d->norm_ready = true;
+    return KGPU_OK;
+}
+
+int kgpu::enqueue_normalize(kgpu_ctx *c, int form, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n, uint8_t *d_text, uint64_t text_capacity,
+                            uint64_t *d_text_offsets, uint8_t *d_status, const char *who) {
+    int rc;
+    if ((rc = ensure_norm_tables(c->dict)) || (rc = c->lines_report.arm()) || (rc = c->lines_len.ensure(((size_t)n + 1) * 8 + (size_t)n + 16))) return rc;
+    NormArgs a{};
+    a.t = c->dict->norm; a.form = (uint32_t)form;
+    a.utf8 = d_utf8; a.offsets = d_offsets; a.n = n;
+    a.sent_len = (uint64_t *)c->lines_len.p; a.mode = (uint8_t *)c->lines_len.p + ((size_t)n + 1) * 8;
+    a.text_offsets = d_text_offsets; a.status = d_status;
+    a.text = d_text; a.text_cap = text_capacity;
+    a.host_ctl = c->lines_report.dev();
+    return records_launched(c, launch_normalize(a, c->stream), who, "normalise", text_capacity);
+}
+
+extern "C" int kgpu_normalize_device(kgpu_ctx *c, int form, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n,
+                                     uint8_t *d_text, uint64_t text_capacity, uint64_t *d_text_offsets, uint8_t *d_status) {
+    const char *who = "kgpu_normalize_device";
+    if (!c || !d_offsets || !d_text_offsets || (n && (!d_utf8 || !d_status)) || (text_capacity && !d_text)) { set_error("%s: null argument", who); return KGPU_ERR_INVALID_ARG; }
+    if (!known_form(form)) { set_error("%s: unknown form %d", who, form); return KGPU_ERR_INVALID_ARG; }
+    if (d_text && d_utf8 && d_utf8 >= d_text && (d_utf8 == d_text || d_utf8 < d_text + text_capacity)) { set_error("%s: d_text overlaps d_utf8", who); return KGPU_ERR_INVALID_ARG; }
+    if (int rc = begin_records_call(c, who)) return rc;
+    return enqueue_normalize(c, form, d_utf8, d_offsets, n, d_text, text_capacity, d_text_offsets, d_status, who);
+}
+
+extern "C" int kgpu_ctx_sync_normalize(kgpu_ctx *c, uint64_t *n_bytes) {
+    if (!c) { set_error("kgpu_ctx_sync_normalize: null ctx"); return KGPU_ERR_INVALID_ARG; }
+    return kgpu_ctx_sync_lines(c, n_bytes);   // (the normaliser reports as a render does: [0] bytes, [1] stays 0)
+}
+
+// The lines in device memory (d_in, d_off: n + 1 offsets; `total` bytes) normalised on c into c->norm_text, and the results into the caller's host arrays.
+// lines_short: the caller's offsets table cannot hold the lines (the sizes are still found).  *n_bytes: the exact size.
+static int normalize_to_host(kgpu_ctx *c, int form, const uint8_t *d_in, const uint64_t *d_off, uint64_t n, uint64_t total, uint8_t *text, uint64_t text_capacity,
+                             uint64_t *text_offsets, uint8_t *status, bool lines_short, uint64_t *n_bytes, const char *who) {
+    int rc;
+    const uint64_t bound = total * NORM_MAX_EXPANSION, room = text_capacity < bound ? text_capacity : bound;
+    if ((rc = c->norm_text.ensure((size_t)room + 16)) || (rc = c->out_off.ensure(((size_t)n + 1) * 8)) || (rc = c->out_status.ensure((size_t)n + 16))) return rc;
+    if ((rc = enqueue_normalize(c, form, d_in, d_off, n, (uint8_t *)c->norm_text.p, room, (uint64_t *)c->out_off.p, (uint8_t *)c->out_status.p, who))) return rc;
+    uint64_t need = 0;
+    rc = kgpu_ctx_sync_normalize(c, &need);
+    *n_bytes = need;
+    if (rc != KGPU_OK && rc != KGPU_ERR_CAPACITY) return rc;
+    if (rc == KGPU_ERR_CAPACITY || lines_short) {
+        set_error("%s: buffers too small: need %llu text bytes (capacity %llu) and %llu offsets", who, (unsigned long long)need, (unsigned long long)text_capacity,
+                  (unsigned long long)(n + 1));
+        return KGPU_ERR_CAPACITY;
+    }
+    if (need && hipMemcpy(text, c->norm_text.p, (size_t)need, hipMemcpyDeviceToHost) != hipSuccess) { set_error("%s: D2H text failed", who); return KGPU_ERR_HIP; }
+    if (hipMemcpy(text_offsets, c->out_off.p, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost) != hipSuccess) { set_error("%s: D2H offsets failed", who); return KGPU_ERR_HIP; }
+    if (status && n && hipMemcpy(status, c->out_status.p, (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) { set_error("%s: D2H status failed", who); return KGPU_ERR_HIP; }
+    return KGPU_OK;
+}
+
+extern "C" int kgpu_normalize_batch(kgpu_dict *d, int form, const uint8_t *utf8, const uint64_t *offsets, uint64_t n,
+                                    uint8_t *text, uint64_t text_capacity, uint64_t *text_offsets, uint8_t *status, uint64_t *n_bytes) {
+    const char *who = "kgpu_normalize_batch";
+    if (!d || !offsets || !text_offsets || !n_bytes || (text_capacity && !text)) { set_error("%s: null argument", who); return KGPU_ERR_INVALID_ARG; }
+    *n_bytes = 0;
+    if (!known_form(form)) { set_error("%s: unknown form %d", who, form); return KGPU_ERR_INVALID_ARG; }
+    int rc;
+    if ((rc = check_host_batch(who, offsets, n, utf8))) return rc;
+    const uint64_t total = offsets[n] - offsets[0];
+    if (total >= (1ull << 32)) { set_error("%s: 4 GiB of text or more; split the batch", who); return KGPU_ERR_INVALID_ARG; }
+    HIPCHECK(hipSetDevice(d->device));
+    kgpu_ctx *c = nullptr;
+    if ((rc = pool_get(d, &c))) return rc;
+    const auto give_back = [&](int r) {
+        c->h2d_queued = false;
+        pool_put(d, c);
+        return r;
+    };
+    if ((rc = c->in_utf8.ensure((size_t)total + 16)) || (rc = c->in_off.ensure(((size_t)n + 1) * 8))) return give_back(rc);
+    if (total && (rc = ctx_h2d(c, c->in_utf8.p, utf8 + offsets[0], (size_t)total, "H2D text"))) return give_back(rc);
+    if ((rc = ctx_h2d(c, c->in_off.p, offsets, ((size_t)n + 1) * 8, "H2D offsets"))) return give_back(rc);
+    const uint8_t *d_in = (const uint8_t *)c->in_utf8.p - offsets[0];   // (the offsets are as the caller has them)
+    return give_back(normalize_to_host(c, form, d_in, (const uint64_t *)c->in_off.p, n, total, text, text_capacity, text_offsets, status, false, n_bytes, who));
+}
+
+extern "C" int kgpu_normalize_text(kgpu_dict *d, int form, const uint8_t *text, uint64_t len, uint8_t *out_text, uint64_t text_capacity,
+                                   uint64_t *text_offsets, uint64_t offsets_capacity, uint8_t *status, uint64_t *n_lines, uint64_t *n_bytes) {
+    const char *who = "kgpu_normalize_text";
+    if (!d || (len && !text) || (text_capacity && !out_text) || (offsets_capacity && !text_offsets) || !n_lines || !n_bytes) { set_error("%s: null argument", who); return KGPU_ERR_INVALID_ARG; }
+    *n_lines = 0; *n_bytes = 0;
+    if (!known_form(form)) { set_error("%s: unknown form %d", who, form); return KGPU_ERR_INVALID_ARG; }
+    if (len >= (1ull << 32)) { set_error("%s: block of 4 GiB or more; split it", who); return KGPU_ERR_INVALID_ARG; }
+    HIPCHECK(hipSetDevice(d->device));
+    int rc;
+    kgpu_ctx *c = nullptr;
+    if ((rc = pool_get(d, &c))) return rc;
+    const auto give_back = [&](int r) {
+        c->h2d_queued = false;
+        pool_put(d, c);
+        return r;
+    };
+    std::vector<uint64_t> off;
+    uint64_t lines = 0;
+    if ((rc = split_block(c, text, len, who, off, lines))) return give_back(rc);
+    *n_lines = lines;
+    return give_back(normalize_to_host(c, form, (const uint8_t *)c->split_text.p, (const uint64_t *)c->split_off.p, lines, off[lines], out_text, text_capacity,
+                                       text_offsets, status, lines + 1 > offsets_capacity, n_bytes, who));
+}

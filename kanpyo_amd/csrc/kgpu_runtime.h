@@ -1,6 +1,6 @@
 // kanpyo_amd/csrc/kgpu_runtime.h -- the host runtime's own types and the functions its files share: kgpu_dict.cpp (dictionary),
 // kgpu_ctx.cpp (contexts, launch chain, the shared head and tail of the four record consumers' enqueues), kgpu_host.cpp (large host calls), kgpu_small.cpp (small calls), kgpu_multi.cpp (the
-// multi-device entry points), kgpu_split_host.cpp (lines of a raw block), kgpu_graphviz_host.cpp (DOT documents of a batch), kgpu_words_host.cpp (wakati), kgpu_count_host.cpp (word counts), kgpu_encode_host.cpp (vocabulary ids).  Not part of the public ABI.
+// multi-device entry points), kgpu_split_host.cpp (lines of a raw block), kgpu_graphviz_host.cpp (DOT documents of a batch), kgpu_words_host.cpp (wakati), kgpu_count_host.cpp (word counts), kgpu_encode_host.cpp (vocabulary ids), kgpu_normalize_host.cpp (text normalisation).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -120,6 +120,9 @@ struct kgpu_dict {
     std::vector<uint64_t> key_off;
     // One reference for the handle the caller holds plus one per live context: the tables and the shared
     // streams go when the last one does (a context outliving kgpu_dict_destroy keeps working).
+    // The normaliser's tables (kgpu_normalize_host.cpp: ensure_norm_tables): dictionary-independent, uploaded by the handle's first normalise call
+    bool norm_ready = false;   // (under feat_mu)
+    NormTables norm{};
     std::atomic<int> refs{1};
     std::atomic<bool> closed{false};   // kgpu_dict_destroy has run: a words handle that outlives it empties the context pool when it goes
 };
@@ -202,6 +205,8 @@ struct kgpu_ctx {
     // for kgpu_tokenize_text_lines the device copy of the raw block, its packed lines and their offsets
     DevBuf split_agg, split_raw, split_text, split_off;
     HostReport split_report;
+    // text normalisation (kgpu_normalize.hip): the host forms' normalised text on the device (their offsets and status bytes: out_off, out_status)
+    DevBuf norm_text;
     // last enqueued batch (for the arena-overflow retry and for sync)
     BatchArgs last{};
     bool pending = false;
@@ -328,6 +333,10 @@ int enqueue_encode(kgpu_ctx *c, const kgpu_vocab *v, const DeviceRecords &r, int
 void dict_key_table(kgpu_dict *d);   // kgpu_count_host.cpp: the dictionary's id -> key table (d->key_bytes, d->key_off), built by the first caller that needs it
 // kgpu_count_host.cpp: the count of a batch's records on c->stream behind whatever is queued there (waited for by kgpu_ctx_sync_count)
 int enqueue_count(kgpu_ctx *c, kgpu_counts *k, const DeviceRecords &r, const char *who);
+
+// kgpu_normalize_host.cpp: the normalisation of a batch in device memory on c->stream behind whatever is queued there (waited for by kgpu_ctx_sync_normalize)
+int enqueue_normalize(kgpu_ctx *c, int form, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n, uint8_t *d_text, uint64_t text_capacity,
+                      uint64_t *d_text_offsets, uint8_t *d_status, const char *who);
 
 int require_features(kgpu_dict *d, const char *who);   // KGPU_ERR_INVALID_ARG unless kgpu_dict_set_features has been called
 int ensure_label_pool(kgpu_dict *d);                   // kgpu_features.cpp: the graphviz label pool on the device (first call uploads it)

@@ -90,6 +90,29 @@ class DeviceContext(Handle):
             self._h, vocab.handle, C.c_void_p(d_utf8), C.c_void_p(d_offsets), n, C.c_void_p(d_tokens), C.c_void_p(d_tok_offsets), C.c_void_p(d_ids),
             id_capacity, width, pad_id, C.c_void_p(d_id_offsets)))
 
+    def normalize(self, d_utf8: int, d_offsets: int, n: int, d_text: int, text_capacity: int, d_text_offsets: int, d_status: int, form="NFKC"):
+        """kgpu_normalize_device: enqueue NFC / NFKC of n lines in HBM -> the normalised lines packed in d_text (up to 11 times the input's bytes;
+        no overlap with d_utf8), their uint64 offsets in d_text_offsets (n + 1) and a status byte per line in d_status: the buffers tokenize takes
+        next.  sync_normalize waits for it."""
+        _lib.check(_lib.lib().kgpu_normalize_device(
+            self._h, _lib.normalize_form(form), C.c_void_p(d_utf8), C.c_void_p(d_offsets), n, C.c_void_p(d_text), text_capacity,
+            C.c_void_p(d_text_offsets), C.c_void_p(d_status)))
+
+    def sync_normalize(self) -> int:
+        """Wait for the enqueued normalisation; returns its byte count.  KgpuError with KGPU_ERR_CAPACITY: text_capacity was too small (nothing
+        was written); try_sync_normalize returns the size instead."""
+        n = C.c_uint64(0)
+        _lib.check(_lib.lib().kgpu_ctx_sync_normalize(self._h, C.byref(n)))
+        return int(n.value)
+
+    def try_sync_normalize(self) -> tuple:
+        """-> (fits, bytes): sync_normalize without the exception for a capacity that was too small."""
+        n = C.c_uint64(0)
+        rc = _lib.lib().kgpu_ctx_sync_normalize(self._h, C.byref(n))
+        if rc != _lib.KGPU_ERR_CAPACITY:
+            _lib.check(rc)
+        return rc == _lib.KGPU_OK, int(n.value)
+
     def split_lines(self, d_in: int, len: int, d_out: int, d_offsets: int, offsets_capacity: int):
         """kgpu_split_lines_device: enqueue read_line + trim_end over a block in HBM -> the trimmed lines packed in d_out (len bytes suffice,
         no overlap with d_in) and their uint64 offsets in d_offsets."""

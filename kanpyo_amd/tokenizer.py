@@ -24,6 +24,33 @@ from .vocab import Vocab
 TEXT_UNITS = ("text[uint8]", "text_offsets")   # what the rendering calls name their out= arrays
 
 
+def merge_status(status: np.ndarray, normalize_status: np.ndarray) -> np.ndarray:
+    """The status bytes of a call over normalised text: the tokenizer's, and KGPU_SENT_NOT_NORMALIZED where the normaliser said so and the
+    tokenizer said 0 (in place)."""
+    status[(status == _lib.KGPU_SENT_OK) & (normalize_status[: status.size] == _lib.KGPU_SENT_NOT_NORMALIZED)] = _lib.KGPU_SENT_NOT_NORMALIZED
+    return status
+
+
+def normalized_call(tokenizer, form, call, utf8=None, offsets=None, block=None, **kw):
+    """call(utf8, offsets, **kw) over the input normalised on the device first (Tokenizer.normalize_packed, or normalize_text for a raw block,
+    whose lines are then packed): every result's last element is the status array, merged with the normaliser's (merge_status)."""
+    text, toff, nstatus = tokenizer.normalize_text(block, form) if block is not None else tokenizer.normalize_packed(utf8, offsets, form)
+    result = call(text, toff, **kw)
+    merge_status(result[-1] if isinstance(result, tuple) else result, nstatus)
+    return result
+
+
+def normalize_host(data, form="NFKC") -> bytes:
+    """kgpu_normalize_host: NFC / NFKC of one string (bytes, or str -> its UTF-8) on the host, by the code and the tables the device runs.
+    Needs no device.  Bytes that are not UTF-8, and a line with an oversize segment (include/kanpyo_gpu.h), come back unchanged."""
+    raw = data.encode("utf-8") if isinstance(data, str) else bytes(data)
+    src = np.frombuffer(raw, dtype=np.uint8)
+    out = np.empty(max(src.size * 11, 1), dtype=np.uint8)
+    got = C.c_uint64(0)
+    _lib.check(_lib.lib().kgpu_normalize_host(_lib.normalize_form(form), ptr(src), src.size, out.ctypes.data, out.size, C.byref(got), None))
+    return out[: got.value].tobytes()
+
+
 def _token_room(total: int, n: int) -> int:
     """The token records a first call allocates for n sentences of `total` bytes."""
     return total // 2 + n + 64
@@ -74,15 +101,42 @@ class Tokenizer(Handle):
         blobs = [np.frombuffer(t if isinstance(t, (bytes, bytearray)) else t.encode(), dtype=np.uint8) for t in (known, unk)]
         _lib.check(_lib.lib().kgpu_dict_set_features(self._h, *[x for b in blobs for x in (b.ctypes.data if b.size else None, b.size)]))
 
-    def tokenize_lines_packed(self, utf8: np.ndarray, offsets: np.ndarray, out=None):
+    # ---- text normalisation (include/kanpyo_gpu.h, "text normalisation"; not an output of the reference) ------
+    def normalize_packed(self, utf8: np.ndarray, offsets: np.ndarray, form="NFKC", out=None):
+        """kgpu_normalize_batch -> (text[uint8], text_offsets[uint64 n+1], status[uint8 n]): line i, NFC or NFKC, is
+        text[text_offsets[i]:text_offsets[i+1]] -- the (utf8, offsets) pair every packed call takes.  A line that is not UTF-8 (status 1) or
+        has an oversize segment (status 4) comes back unchanged.  out=(text, text_offsets, status): caller-owned arrays to reuse."""
+        return batch_call(partial(_lib.lib().kgpu_normalize_batch, self._h, _lib.normalize_form(form)), utf8, offsets, np.uint8, lambda total, n: total * 2 + 64,
+                          TEXT_UNITS, out=out)
+
+    def normalize_text(self, block, form="NFKC"):
+        """kgpu_normalize_text: a raw block of input (bytes or uint8 array) -> (text, text_offsets, status) as
+        normalize_packed(*split_lines(block)) gives them; the split and the trim run on the device too."""
+        return block_call(partial(_lib.lib().kgpu_normalize_text, self._h, _lib.normalize_form(form)), block, np.uint8, lambda size: (size * 2 + 64, size // 16 + 1024))
+
+    def normalize(self, sentences: Sequence, form="NFKC") -> list:
+        """The sentences normalised on the device: str in gives str out, bytes in gives bytes out (a line that is not UTF-8 comes back as it is)."""
+        text, toff, _ = self.normalize_packed(*pack_sentences(sentences), form)
+        raw, o = text.tobytes(), toff.tolist()
+        return [raw[o[i] : o[i + 1]].decode("utf-8") if isinstance(s, str) else raw[o[i] : o[i + 1]] for i, s in enumerate(sentences)]
+
+    def tokenize_lines_packed(self, utf8: np.ndarray, offsets: np.ndarray, out=None, normalize=None):
         """-> (text[uint8], text_offsets[uint64 n+1], status[uint8 n]): sentence i's `surface\\tfeatures\\n` lines are
-        text[text_offsets[i]:text_offsets[i+1]].  out=(text, text_offsets, status): caller-owned arrays to reuse."""
+        text[text_offsets[i]:text_offsets[i+1]].  out=(text, text_offsets, status): caller-owned arrays to reuse.
+        normalize="NFC" / "NFKC": the input goes through normalize_packed first; the surfaces are those of the NORMALISED text, and a status
+        byte is 4 where the normaliser left a line as it was and the tokenizer said 0."""
+        if normalize is not None:
+            return normalized_call(self, normalize, self.tokenize_lines_packed, utf8, offsets, out=out)
         return batch_call(partial(_lib.lib().kgpu_tokenize_batch_lines, self._h), utf8, offsets, np.uint8, lambda total, n: total * 16 + 8 * n + 64,
                           TEXT_UNITS, out=out)
 
-    def tokenize_text_lines(self, block):
+    def tokenize_text_lines(self, block, normalize=None):
         """kgpu_tokenize_text_lines: a raw block of input (bytes or uint8 array) -> (text, text_offsets, status) as
-        tokenize_lines_packed(*split_lines(block)) gives them; the split and the trim run on the device."""
+        tokenize_lines_packed(*split_lines(block)) gives them; the split and the trim run on the device.
+        normalize="NFC" / "NFKC": the block goes through normalize_text first (split, trim and normalisation on the device), its lines then
+        through tokenize_lines_packed; surfaces and status as there."""
+        if normalize is not None:
+            return normalized_call(self, normalize, self.tokenize_lines_packed, block=block)
         return block_call(partial(_lib.lib().kgpu_tokenize_text_lines, self._h), block, np.uint8, lambda size: (size * 16 + 64, size // 16 + 1024))
 
     def tokenize_lines(self, sentences: Sequence) -> bytes:
@@ -92,11 +146,13 @@ class Tokenizer(Handle):
         return text.tobytes()
 
     # ---- wakati-gaki: one line of words per sentence (not an output of the reference) ------
-    def words(self, field=None, drop=(), keep=(), separator=" ") -> "Words":
+    def words(self, field=None, drop=(), keep=(), separator=" ", normalize=None) -> "Words":
         """kgpu_words_create: a Words handle of this dictionary (set_features first).  field: None = the surface, k >= 0 = feature k of the
         token's row (the surface where the row has no such feature, or it is "" or "*"); drop / keep: part-of-speech names compared with
-        feature 0 (at most one of the two); separator: one byte, not a newline."""
-        return Words(self, field, drop, keep, separator)
+        feature 0 (at most one of the two); separator: one byte, not a newline.  normalize="NFC" / "NFKC": everything rendered, counted or
+        encoded through the handle (Words.render*, WordCounts.add*, Vocab.encode_packed / encode_text / encode / encode_tensor) normalises its
+        input on the device first; positions and surfaces then refer to the NORMALISED text."""
+        return Words(self, field, drop, keep, separator, normalize)
 
     # ---- the lattice pictures (`kanpyo graphviz`, src/bin/kanpyo.rs:127-148 over src/graphviz.rs:30-163) ------
     def graphviz_packed(self, utf8: np.ndarray, offsets: np.ndarray, dpi: int = 48, full_state: bool = False):
@@ -120,8 +176,12 @@ class Tokenizer(Handle):
         return {n: (list(getattr(r, n)) if n in ("deferred", "redone") else getattr(r, n)) for n, *_ in r._fields_}
 
     # ---- reference-shaped API --------------------------------------------------
-    def tokenize_batch(self, sentences: Sequence[str]) -> List[List[Token]]:
+    def tokenize_batch(self, sentences: Sequence[str], normalize=None) -> List[List[Token]]:
+        """normalize="NFC" / "NFKC": the sentences are normalised on the device first; Token.position, start, end and surface then refer to
+        the NORMALISED sentence."""
         utf8, offs = pack_sentences(sentences)
+        if normalize is not None:
+            utf8, offs, _ = self.normalize_packed(utf8, offs, normalize)
         tokens, toff, status = self.tokenize_packed(utf8, offs)
         out = []
         for i, s in enumerate(sentences):
@@ -164,7 +224,8 @@ class Words(Handle):
 
     _destroy = "kgpu_words_destroy"
 
-    def __init__(self, tokenizer: Tokenizer, field=None, drop=(), keep=(), separator=" "):
+    def __init__(self, tokenizer: Tokenizer, field=None, drop=(), keep=(), separator=" ", normalize=None):
+        self.normalize = None if normalize is None else _lib.normalize_form(normalize)   # (what the handles made from this one inherit)
         spec, keep_alive = words_spec(field, drop, keep, separator)
         h = C.c_void_p()
         _lib.check(_lib.lib().kgpu_words_create(tokenizer.handle, C.byref(spec), C.byref(h)))
@@ -172,15 +233,24 @@ class Words(Handle):
         self._h = h
         self.tokenizer = tokenizer
 
-    def render_packed(self, utf8: np.ndarray, offsets: np.ndarray, out=None):
+    def render_packed(self, utf8: np.ndarray, offsets: np.ndarray, out=None, normalize=None):
         """kgpu_tokenize_batch_words -> (text[uint8], text_offsets[uint64 n+1], status[uint8 n]): sentence i's line is
-        text[text_offsets[i]:text_offsets[i+1]].  out=(text, text_offsets, status): caller-owned arrays to reuse."""
+        text[text_offsets[i]:text_offsets[i+1]].  out=(text, text_offsets, status): caller-owned arrays to reuse.  normalize: None = the form the
+        handle was made with (Tokenizer.words)."""
+        form = self.normalize if normalize is None else normalize
+        if form is not None:
+            return normalized_call(self.tokenizer, form, self._render_packed, utf8, offsets, out=out)
+        return self._render_packed(utf8, offsets, out=out)
+
+    def _render_packed(self, utf8, offsets, out=None):
         return batch_call(partial(_lib.lib().kgpu_tokenize_batch_words, self._h), utf8, offsets, np.uint8, lambda total, n: total * 2 + n + 64,
                           TEXT_UNITS, out=out)
 
     def render_text(self, block):
         """kgpu_tokenize_text_words: a raw block of input (bytes or uint8 array) -> (text, text_offsets, status) as
         render_packed(*split_lines(block)) gives them; the split and the trim run on the device."""
+        if self.normalize is not None:
+            return normalized_call(self.tokenizer, self.normalize, self._render_packed, block=block)
         return block_call(partial(_lib.lib().kgpu_tokenize_text_words, self._h), block, np.uint8, lambda size: (size * 2 + 64, size // 16 + 1024))
 
     def render(self, sentences: Sequence) -> List[str]:
@@ -214,8 +284,10 @@ class WordCounts(Handle):
         self._h = h
         self.words = words
 
-    def add_packed(self, utf8: np.ndarray, offsets: np.ndarray) -> np.ndarray:
+    def add_packed(self, utf8: np.ndarray, offsets: np.ndarray, _normalized: bool = False) -> np.ndarray:
         """kgpu_count_batch -> status[uint8 n].  KgpuError with KGPU_ERR_CAPACITY: some tokens found no room (info()["overflow_tokens"])."""
+        if self.words.normalize is not None and not _normalized:
+            return normalized_call(self.words.tokenizer, self.words.normalize, self.add_packed, utf8, offsets, _normalized=True)
         utf8, offsets, n, _ = packed_input(utf8, offsets)
         status = np.zeros(max(n, 1), dtype=np.uint8)
         _lib.check(_lib.lib().kgpu_count_batch(self._h, ptr(utf8), offsets.ctypes.data, n, status.ctypes.data))
@@ -227,6 +299,8 @@ class WordCounts(Handle):
 
     def add_text(self, block) -> np.ndarray:
         """kgpu_count_text: a raw block of input (bytes or uint8 array), split and trimmed on the device -> one status byte per line."""
+        if self.words.normalize is not None:
+            return normalized_call(self.words.tokenizer, self.words.normalize, self.add_packed, block=block, _normalized=True)
         src = block_bytes(block)
         caps = (src.size // 16 + 1024,)
         n = C.c_uint64(0)

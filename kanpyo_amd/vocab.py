@@ -7,7 +7,10 @@ torch.nn.EmbeddingBag takes -- or padded to [n, width].
 
 wordpiece=True (include/kanpyo_gpu.h, "WordPiece ids"): the list is a BERT vocab.txt -- a word outside it is cut greedily into its longest listed
 pieces, continuation pieces listed behind the prefix ("##"), and a kept token gives zero, one or many ids.  What is pinned is that split rule, not
-equal input_ids with a real BERT-Japanese tokenizer (which also normalises its text and needs the real IPADIC).
+equal input_ids with a real BERT-Japanese tokenizer (its NFKC is available -- Tokenizer.words(normalize="NFKC") -- but it segments with the real IPADIC).
+
+A Vocab made from a Words handle with normalize="NFC" / "NFKC" normalises the input of every encode call on the device first; the ids are those of
+the NORMALISED text, and a status byte is 4 where the normaliser left a line as it was.  Unlike the plain host forms, that needs the Tokenizer open.
 """
 from __future__ import annotations
 
@@ -62,6 +65,7 @@ class Vocab(Handle):
                                                     C.byref(opts), C.byref(h)))
         self._h = h
         self._tokenizer = words_handle.tokenizer   # (encode_tensor's context is made from it)
+        self._normalize = getattr(words_handle, "normalize", None)   # the form the encode calls normalise their input with first
         self._device = self._tokenizer.info()["device"]
         self._extra = (1 if bos_id is not None else 0) + (1 if eos_id is not None else 0)
         self._ctx_lock = threading.Lock()
@@ -95,16 +99,30 @@ class Vocab(Handle):
         return split_words(self.words, words, self.unk_id, self._wp)
 
     # ---- host memory in and out ------------------------------------------------------------------------------------------------------------
-    def encode_packed(self, utf8: np.ndarray, offsets: np.ndarray, out=None):
+    def _open_tokenizer(self):
+        if not getattr(self._tokenizer, "_h", None):
+            raise RuntimeError("the Vocab normalises and tokenizes on its Tokenizer, which has been closed")
+        return self._tokenizer
+
+    def encode_packed(self, utf8: np.ndarray, offsets: np.ndarray, out=None, _normalized: bool = False):
         """kgpu_encode_batch -> (ids[int32], id_offsets[uint64 n+1], status[uint8 n]): sentence i's sequence is
         ids[id_offsets[i]:id_offsets[i+1]].  out=(ids, id_offsets, status): caller-owned arrays to reuse (too small: KgpuError with
         KGPU_ERR_CAPACITY, nothing written)."""
+        if self._normalize is not None and not _normalized:
+            from .tokenizer import normalized_call
+
+            return normalized_call(self._open_tokenizer(), self._normalize, self.encode_packed, utf8, offsets, out=out, _normalized=True)
         return batch_call(partial(_lib.lib().kgpu_encode_batch, self._h), utf8, offsets, np.int32, lambda total, n: total // 2 + n * (1 + self._extra) + 64,
                           ("ids[int32]", "id_offsets"), out=out)
 
     def encode_text(self, block):
         """kgpu_encode_text: a raw block of input (bytes or uint8 array) -> (ids, id_offsets, status) as encode_packed(*split_lines(block))
         gives them; the split and the trim run on the device."""
+        if self._normalize is not None:
+            from .tokenizer import normalized_call
+
+            return normalized_call(self._open_tokenizer(), self._normalize, self.encode_packed, block=block, _normalized=True)
+
         def first(size):   # (as encode_packed sizes it, with every 16 bytes a possible line)
             lines = size // 16 + 1024
             return size // 2 + 64 + lines * self._extra, lines
@@ -118,14 +136,17 @@ class Vocab(Handle):
         return [ids[o[i] : o[i + 1]] for i in range(len(o) - 1)]
 
     # ---- device memory out -----------------------------------------------------------------------------------------------------------------
-    def encode_tensor(self, sentences: Sequence, width=None, pad_id: int = 0):
+    def encode_tensor(self, sentences: Sequence, width=None, pad_id: int = 0, normalize=None):
         """The sentences (str or bytes) as torch tensors on the device, in ONE DeviceContext batch: upload, tokenize, sync, encode, sync_lines.
         No id passes through host memory.  THE WHOLE BATCH MUST FIT DEVICE MEMORY (its text, 24 bytes per token and 4 bytes per id): cut a
         corpus into batches.  The batch is tokenized on a DeviceContext of this Vocab's Tokenizer, made by the first call: unlike the host
         forms, which work on a Vocab that has outlived its Words and its Tokenizer, encode_tensor NEEDS THE TOKENIZER OPEN (RuntimeError otherwise).
         width=None -> (ids int32 [total], offsets int64 [n + 1], status uint8 [n]); ids and offsets[:-1] are what torch.nn.EmbeddingBag takes.
         width=w    -> (ids int32 [n, w], lengths int64 [n] = min(L, w), status uint8 [n]); rows are cut after w elements (a cut row ends with
-        eos_id when the vocabulary adds EOS) and filled with pad_id."""
+        eos_id when the vocabulary adds EOS) and filled with pad_id.
+        normalize="NFC" / "NFKC" (None: the form the Vocab's Words handle was made with): the uploaded text is normalised on the device first
+        (DeviceContext.normalize, sync_normalize) and the normalised buffers are what is tokenized and encoded: no text returns to the host.  The
+        status is the tokenizer's, 4 where the normaliser left a line as it was and the tokenizer said 0."""
         import torch
 
         if width is not None and int(width) < 1:
@@ -141,6 +162,21 @@ class Vocab(Handle):
             dev = torch.device("cuda", self._device)
             d_utf8 = torch.from_numpy(np.concatenate([utf8, np.zeros(16, dtype=np.uint8)])).to(dev)
             d_off = torch.from_numpy(offs.view(np.int64)).to(dev)
+            form = self._normalize if normalize is None else _lib.normalize_form(normalize)
+            d_nst = None
+            if form is not None:   # the normalised lines and their offsets take the input's place; a capacity too small grows once, to the size reported
+                d_nst = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+                d_noff = torch.empty(n + 1, dtype=torch.int64, device=dev)
+                ncap = total * 2 + 64
+                while True:
+                    d_norm = torch.zeros(ncap + 16, dtype=torch.uint8, device=dev)
+                    torch.cuda.synchronize(dev)
+                    ctx.normalize(d_utf8.data_ptr(), d_off.data_ptr(), n, d_norm.data_ptr(), ncap, d_noff.data_ptr(), d_nst.data_ptr(), form)
+                    fits, total = ctx.try_sync_normalize()
+                    if fits:
+                        break
+                    ncap = total
+                d_utf8, d_off = d_norm, d_noff
             d_toff = torch.empty(n + 1, dtype=torch.int64, device=dev)
             d_st = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
             cap = total // 2 + n + 64
@@ -172,6 +208,8 @@ class Vocab(Handle):
                 _lib.check(rc)
                 break
             count = int(got.value)
+            if d_nst is not None:   # (on the device: the normaliser's 4 shows where the tokenizer said 0)
+                d_st = torch.where((d_st == 0) & (d_nst == _lib.KGPU_SENT_NOT_NORMALIZED), d_nst, d_st)
         if width is None:
             return d_ids[:count], d_ioff, d_st[:n]
         return d_ids, torch.clamp(d_ioff[1:] - d_ioff[:-1], max=int(width)), d_st[:n]
