@@ -1,8 +1,8 @@
 // kanpyo_amd/csrc/kgpu_count_host.cpp -- the counts handle behind the word counts (include/kanpyo_gpu.h, "word counts"; kgpu_count.hip).
 //
 // Owns: kgpu_counts_create / _destroy / _reset / _get_info; the count's enqueue on a context (enqueue_count), kgpu_count_words_device and
-// kgpu_ctx_sync_count; the host calls kgpu_count_batch and kgpu_count_text -- the chunk pipeline of the lines calls (run_pipeline, kgpu_runtime.h) with a
-// chunk that returns no text (CountChunk); the read-out kgpu_counts_read with the dictionary's id -> key table behind it; and the host-only test hook
+// kgpu_ctx_sync_count; the host calls kgpu_count_batch and kgpu_count_text -- the lines calls' sources and records chunk (ChunkSource, RecordsChunk,
+// kgpu_runtime.h) with a finish that counts (CountChunk) under one body (count_call); the read-out kgpu_counts_read with the dictionary's id -> key table behind it; and the host-only test hook
 // kgpu_debug_counts_order (the merge and the order of the read-out without a device).
 //
 // ACCUMULATION IS NOT IDEMPOTENT.  The renders of a lines chunk are queued behind the chunk's first pass and simply run once more when kgpu_ctx_sync
@@ -209,31 +209,12 @@ extern "C" int kgpu_ctx_sync_count(kgpu_ctx *c, uint64_t *n_counted) {
 // ---- the host calls: the lines calls' chunk pipeline with a chunk that returns status bytes only -----------------------------------------------
 namespace {
 
-// The output side of one count chunk on a pooled context: the 24-byte records stay in HBM (c->out_tok); when they are final the count kernel reads
-// them and mirrors the status bytes into c's mapped lines_status.
-struct CountChunk {
-    uint64_t n = 0, total = 0;
-    const uint8_t *d_utf8 = nullptr;
-    const uint64_t *d_offsets = nullptr;
-    int prepare(kgpu_ctx *c, uint64_t n_, uint64_t total_) {
-        n = n_; total = total_;
-        int rc;
-        if ((rc = c->out_tok.ensure((size_t)token_bound(total, n) * sizeof(kgpu_token) + 64)) || (rc = c->out_status.ensure((size_t)n + 16)) ||
-            (rc = c->out_off.ensure((size_t)(n + 1) * 8)) || (rc = c->lines_status.ensure((size_t)n + 16, true)))
-            return rc;
-        return KGPU_OK;
-    }
-    int launch(kgpu_ctx *c, const uint8_t *d_utf8_, const uint64_t *d_offsets_, const char *who) {   // the chain alone
-        d_utf8 = d_utf8_; d_offsets = d_offsets_;
-        return tokenize_device_impl(c, d_utf8, d_offsets, n, total, (kgpu_token *)c->out_tok.p, nullptr, nullptr, nullptr, nullptr, token_bound(total, n),
-                                    (uint64_t *)c->out_off.p, (uint8_t *)c->out_status.p, who);
-    }
+// One count chunk: when its records are final the count kernel reads them and mirrors the status bytes into c's mapped lines_status.
+struct CountChunk : RecordsChunk {
     // Wait for the chain (reruns included: the records are final behind it), count, wait for the count.  overflow: a token found no room (the call goes on).
     int finish(kgpu_ctx *c, kgpu_counts *k, uint64_t lo, uint8_t *status, bool &overflow, const char *who) const {
         int rc = kgpu_ctx_sync(c, nullptr);   // (24-byte records with capacity token_bound: never too small)
-        if (rc) return rc;
-        const DeviceRecords r{d_utf8, d_offsets, n, (const kgpu_token *)c->out_tok.p, (const uint64_t *)c->out_off.p, (const uint8_t *)c->out_status.p, (uint8_t *)c->lines_status.d};
-        if ((rc = enqueue_count(c, k, r, who))) return rc;
+        if (rc || (rc = enqueue_count(c, k, records(c), who))) return rc;
         rc = kgpu_ctx_sync_count(c, nullptr);
         if (rc == KGPU_ERR_CAPACITY) { overflow = true; rc = KGPU_OK; }
         if (rc) return rc;
@@ -242,10 +223,11 @@ struct CountChunk {
     }
 };
 
-struct CountBatchJob { kgpu_ctx *c = nullptr; uint64_t lo = 0, m = 0; ChunkInput in; CountChunk out; };
-struct CountTextJob { kgpu_ctx *c = nullptr; uint64_t lo = 0, m = 0; CountChunk out; };
-
-int overflow_error(const char *who) {
+// The body of both host calls, under the handle's shared lock (the caller's, for the whole call).
+int count_call(const ChunkSource &src, kgpu_counts *k, uint8_t *status, const char *who) {
+    bool overflow = false;
+    const int rc = run_chunks(src, CountChunk{}, who, [&](ChunkJob<CountChunk> &j) { return j.out.finish(j.c, k, j.lo, status, overflow, who); });
+    if (rc || !overflow) return rc;
     set_error("%s: the counts handle's table or key arena is full: tokens were added to overflow_tokens (everything else is counted)", who);
     return KGPU_ERR_CAPACITY;
 }
@@ -255,61 +237,25 @@ int overflow_error(const char *who) {
 extern "C" int kgpu_count_batch(kgpu_counts *k, const uint8_t *utf8, const uint64_t *offsets, uint64_t n, uint8_t *status) {
     const char *who = "kgpu_count_batch";
     if (!k || !offsets) { set_error("%s: null argument", who); return KGPU_ERR_INVALID_ARG; }
-    kgpu_dict *d = k->words->dict;
-    int rc;
-    if ((rc = check_host_batch(who, offsets, n, utf8))) return rc;
-    HIPCHECK(hipSetDevice(d->device));
     std::shared_lock<std::shared_mutex> g(k->mu);
-    bool overflow = false;
-    const bool pinned_in = batch_is_pinned(utf8, offsets, n);
-    rc = run_pipeline<CountBatchJob>(d, offsets, n, batch_depth(), 2, false, nullptr,
-        [&](CountBatchJob &j) {
-            const uint64_t *off = offsets + j.lo;
-            const uint64_t total = off[j.m] - off[0];
-            int r;
-            if ((r = j.in.prepare(j.c, j.m, total, !pinned_in)) || (r = j.out.prepare(j.c, j.m, total)) || (r = upload_input(j.c, j.in, utf8, off, pinned_in))) return r;
-            return j.out.launch(j.c, j.in.d_text(j.c, off[0]), j.in.d_offsets(j.c), who);
-        },
-        [&](CountBatchJob &j) { return j.out.finish(j.c, k, j.lo, status, overflow, who); });
-    if (!rc && overflow) return overflow_error(who);
-    return rc;
+    ChunkSource src;
+    if (int rc = src.packed(k->words->dict, who, utf8, offsets, n, false, false)) return rc;
+    return count_call(src, k, status, who);
 }
 
 extern "C" int kgpu_count_text(kgpu_counts *k, const uint8_t *text, uint64_t len, uint8_t *status, uint64_t status_capacity, uint64_t *n_lines) {
     const char *who = "kgpu_count_text";
     if (!k || (len && !text) || !n_lines) { set_error("%s: null argument", who); return KGPU_ERR_INVALID_ARG; }
     *n_lines = 0;
-    if (len >= (1ull << 32)) { set_error("%s: block of 4 GiB or more; split it", who); return KGPU_ERR_INVALID_ARG; }
-    kgpu_dict *d = k->words->dict;
-    HIPCHECK(hipSetDevice(d->device));
     std::shared_lock<std::shared_mutex> g(k->mu);
-    kgpu_ctx *sc = nullptr;   // the splitting context: it owns the block, the packed lines and their offsets until the call is over
-    int rc;
-    if ((rc = pool_get(d, &sc))) return rc;
-    const auto give_back = [&](int r) {
-        sc->h2d_queued = false;
-        pool_put(d, sc);
-        return r;
-    };
-    std::vector<uint64_t> off;
-    uint64_t lines = 0;
-    if ((rc = split_block(sc, text, len, who, off, lines))) return give_back(rc);
-    *n_lines = lines;
-    if (status && lines > status_capacity) {
-        set_error("%s: status capacity %llu, the block has %llu lines (nothing was counted)", who, (unsigned long long)status_capacity, (unsigned long long)lines);
-        return give_back(KGPU_ERR_CAPACITY);
+    ChunkSource src;
+    if (int rc = src.block(k->words->dict, who, text, len, false)) return rc;
+    *n_lines = src.n;
+    if (status && src.n > status_capacity) {
+        set_error("%s: status capacity %llu, the block has %llu lines (nothing was counted)", who, (unsigned long long)status_capacity, (unsigned long long)src.n);
+        return KGPU_ERR_CAPACITY;
     }
-    const uint8_t *d_text = (const uint8_t *)sc->split_text.p;   // the chunks' input: pointers into the split's output
-    const uint64_t *d_off = (const uint64_t *)sc->split_off.p;
-    bool overflow = false;
-    rc = run_pipeline<CountTextJob>(d, off.data(), lines, 4, 0, false, nullptr,
-        [&](CountTextJob &j) {
-            const int r = j.out.prepare(j.c, j.m, off[j.lo + j.m] - off[j.lo]);
-            return r ? r : j.out.launch(j.c, d_text, d_off + j.lo, who);
-        },
-        [&](CountTextJob &j) { return j.out.finish(j.c, k, j.lo, status, overflow, who); });
-    if (!rc && overflow) rc = overflow_error(who);
-    return give_back(rc);
+    return count_call(src, k, status, who);
 }
 
 // ---- the read-out ----------------------------------------------------------------------------------------------------------------------------

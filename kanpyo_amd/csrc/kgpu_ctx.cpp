@@ -1,6 +1,6 @@
 // kanpyo_amd/csrc/kgpu_ctx.cpp -- the contexts of include/kanpyo_gpu.h and the launch chain behind them.
 //
-// Owns: context create / destroy, the lease of a dictionary's pooled contexts, the stream of a batch (ctx_pick_stream), the one
+// Owns: context create / destroy, the lease of a dictionary's pooled contexts (pool_get / pool_put; the scope guard over them is PooledCtx, kgpu_runtime.h), the stream of a batch (ctx_pick_stream), the one
 // way a batch's host-to-device copy is queued (ctx_h2d), running a batch's chain (kgpu_chain.cpp decides it) with the scan and
 // compaction behind it, the reruns in kgpu_ctx_sync, the profiling / ablation / plan getters, the two words a launch publishes to the
 // host (HostReport), the render of a batch's lines, and the lattice dump.
@@ -549,18 +549,17 @@ extern "C" int kgpu_lattice_dump(kgpu_dict *d, const uint8_t *utf8, uint64_t len
     if (len >= (1ull << 31)) { set_error("kgpu_lattice_dump: sentence too long"); return KGPU_ERR_INVALID_ARG; }
     *out = kgpu_lattice{};
     HIPCHECK(hipSetDevice(d->device));
-    kgpu_ctx *c = nullptr;
-    int rc = pool_get(d, &c);
+    PooledCtx lease(d);   // (the copies below go on c->stream, where the dump's own launch follows: no ctx_pick_stream, so no h2d_queued -- and none left behind)
+    kgpu_ctx *c = lease.c;
+    int rc = lease.rc;
     if (rc) return rc;
-    // (the copies below go on c->stream, where the dump's own launch follows: no ctx_pick_stream, so no h2d_queued -- and none left behind)
-    auto give_back = [&]() { c->h2d_queued = false; pool_put(d, c); };
     const uint64_t offs[2] = {0, len};
     Control hc{};
     if ((c->pending && (rc = kgpu_ctx_sync(c, nullptr)) != KGPU_OK && rc != KGPU_ERR_CAPACITY) ||
         (rc = c->arena.ensure(ARENA_INITIAL)) || (rc = c->stage.ensure((size_t)(len + 2) * sizeof(kgpu_token) + 64)) ||
         (rc = c->tok_count.ensure(8)) || (rc = c->in_utf8.ensure((size_t)len + 16)) || (rc = c->in_off.ensure(16)) ||
-        (rc = c->out_status.ensure(16))) { give_back(); return rc; }
-    auto fail = [&](hipError_t e, const char *what) { set_error("kgpu_lattice_dump: %s: %s", what, hipGetErrorString(e)); c->ctl_dirty = true; give_back(); return KGPU_ERR_HIP; };
+        (rc = c->out_status.ensure(16))) return rc;
+    auto fail = [&](hipError_t e, const char *what) { set_error("kgpu_lattice_dump: %s: %s", what, hipGetErrorString(e)); c->ctl_dirty = true; return KGPU_ERR_HIP; };
     hipError_t e;
     if (len && (e = hipMemcpyAsync(c->in_utf8.p, utf8, (size_t)len, hipMemcpyHostToDevice, c->stream)) != hipSuccess) return fail(e, "H2D");
     if ((e = hipMemcpyAsync(c->in_off.p, offs, 16, hipMemcpyHostToDevice, c->stream)) != hipSuccess) return fail(e, "H2D");
@@ -577,10 +576,10 @@ extern "C" int kgpu_lattice_dump(kgpu_dict *d, const uint8_t *utf8, uint64_t len
         if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return fail(e, "sync");
         if (!hc.arena_overflow) break;
         size_t want = c->arena.bytes * 2;
-        if (want > ARENA_MAX) { set_error("scratch arena exceeded %zu bytes", ARENA_MAX); give_back(); return KGPU_ERR_INTERNAL; }
-        if ((rc = c->arena.ensure(want))) { give_back(); return rc; }
+        if (want > ARENA_MAX) { set_error("scratch arena exceeded %zu bytes", ARENA_MAX); return KGPU_ERR_INTERNAL; }
+        if ((rc = c->arena.ensure(want))) return rc;
     }
-    if (!hc.dump[5]) { set_error("kgpu_lattice_dump: the sentence is not valid UTF-8"); give_back(); return KGPU_ERR_INVALID_ARG; }
+    if (!hc.dump[5]) { set_error("kgpu_lattice_dump: the sentence is not valid UTF-8"); return KGPU_ERR_INVALID_ARG; }
     const uint64_t B = hc.dump[2], C = hc.dump[3], N = hc.dump[4], na = B + 4;
     std::vector<uint32_t> cbyte(C + 1), boff(C + 2), pre(N);
     std::vector<uint32_t> nodeA(4 * N), bucket(4 * N), nodeB(2 * N);
@@ -592,7 +591,7 @@ extern "C" int kgpu_lattice_dump(kgpu_dict *d, const uint8_t *utf8, uint64_t len
         (e = hipMemcpy(bucket.data(), sn + N * 16, N * 16, hipMemcpyDeviceToHost)) != hipSuccess ||
         (e = hipMemcpy(nodeB.data(), sn + N * 32, N * 8, hipMemcpyDeviceToHost)) != hipSuccess ||
         (e = hipMemcpy(pre.data(), sn + N * 40, N * 4, hipMemcpyDeviceToHost)) != hipSuccess) return fail(e, "slab read-back");
-    give_back();
+    lease.put();   // (the rest is host work)
     out->n_nodes = N; out->n_positions = C + 2;
     out->nodes = (kgpu_lattice_node *)calloc((size_t)N, sizeof(kgpu_lattice_node));
     out->edge_offsets = (uint32_t *)calloc((size_t)C + 3, 4);

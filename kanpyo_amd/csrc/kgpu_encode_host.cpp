@@ -4,8 +4,8 @@
 // kgpu_vocab_create_wordpiece / kgpu_vocab_get_wordpiece_info (include/kanpyo_gpu.h, "WordPiece ids": the same handle with build_wordpiece_tables' tables,
 // kgpu_wordpiece_table.cpp; enqueue_encode sends it to kgpu_wordpiece.hip's launcher, a plain handle to kgpu_encode.hip's as before); the
 // encode's enqueue on a context (enqueue_encode: the renders' lines_report and lines_len, waited for by kgpu_ctx_sync_lines, which reports the ids),
-// kgpu_encode_device; the host calls kgpu_encode_batch and kgpu_encode_text -- the lines calls' bodies (batch_lines, kgpu_host.cpp; text_lines,
-// kgpu_split_host.cpp) with LinesChunk::vocab set, the chunk's output counted in 4-byte units; and the host-only test hooks kgpu_debug_vocab_table,
+// kgpu_encode_device; the host calls kgpu_encode_batch and kgpu_encode_text -- the lines calls' wrappers (batch_lines, kgpu_host.cpp; text_lines,
+// kgpu_split_host.cpp) with the handle as the Renderer, the chunk's output counted in 4-byte units; and the host-only test hooks kgpu_debug_vocab_table,
 // kgpu_debug_wordpiece_table and kgpu_debug_wordpiece_split.
 //
 // AN ENCODE IS IDEMPOTENT, as a render is: queued behind a chunk's first pass it simply runs again when kgpu_ctx_sync had to rerun the chain
@@ -211,13 +211,13 @@ extern "C" int kgpu_encode_device(kgpu_ctx *c, const kgpu_vocab *v, const uint8_
 extern "C" int kgpu_encode_batch(kgpu_vocab *v, const uint8_t *utf8, const uint64_t *offsets, uint64_t n, int32_t *ids, uint64_t id_capacity,
                                  uint64_t *id_offsets, uint8_t *status, uint64_t *n_ids) {
     if (!v) { set_error("kgpu_encode_batch: null argument"); return KGPU_ERR_INVALID_ARG; }
-    return batch_lines(v->words->dict, nullptr, v, "kgpu_encode_batch", utf8, offsets, n, (uint8_t *)ids, id_capacity, id_offsets, status, n_ids);
+    return batch_lines(v->words->dict, Renderer(v), "kgpu_encode_batch", utf8, offsets, n, (uint8_t *)ids, id_capacity, id_offsets, status, n_ids);
 }
 
 extern "C" int kgpu_encode_text(kgpu_vocab *v, const uint8_t *text, uint64_t len, int32_t *ids, uint64_t id_capacity, uint64_t *id_offsets,
                                 uint64_t offsets_capacity, uint8_t *status, uint64_t *n_lines, uint64_t *n_ids) {
     if (!v) { set_error("kgpu_encode_text: null argument"); return KGPU_ERR_INVALID_ARG; }
-    return text_lines(v->words->dict, nullptr, v, "kgpu_encode_text", text, len, (uint8_t *)ids, id_capacity, id_offsets, offsets_capacity, status, n_lines, n_ids);
+    return text_lines(v->words->dict, Renderer(v), "kgpu_encode_text", text, len, (uint8_t *)ids, id_capacity, id_offsets, offsets_capacity, status, n_lines, n_ids);
 }
 
 namespace {

@@ -113,10 +113,11 @@ extern "C" int kgpu_graphviz_batch(kgpu_dict *d, const uint8_t *utf8, const uint
         if (offsets[i + 1] - offsets[i] >= (1ull << 31)) { set_error("%s: sentence %llu too long", who, (unsigned long long)i); return KGPU_ERR_INVALID_ARG; }
     if ((rc = ensure_label_pool(d))) return rc;
     HIPCHECK(hipSetDevice(d->device));
-    Call k{d, nullptr, utf8, offsets, dpi, full_state, text, text_capacity, text_offsets, status};
-    if ((rc = pool_get(d, &k.c))) return rc;
-    kgpu_ctx *c = k.c;
-    if (c->pending && (rc = kgpu_ctx_sync(c, nullptr)) != KGPU_OK && rc != KGPU_ERR_CAPACITY) { pool_put(d, c); return rc; }
+    PooledCtx lease(d);
+    if (lease.rc) return lease.rc;
+    kgpu_ctx *c = lease.c;
+    Call k{d, c, utf8, offsets, dpi, full_state, text, text_capacity, text_offsets, status};
+    if (c->pending && (rc = kgpu_ctx_sync(c, nullptr)) != KGPU_OK && rc != KGPU_ERR_CAPACITY) return rc;
     rc = KGPU_OK;
     text_offsets[0] = 0;
     const uint64_t hook = test_hooks().graphviz_chunk_sents, max_sents = hook ? hook : CHUNK_SENTS;
@@ -126,8 +127,6 @@ extern "C" int kgpu_graphviz_batch(kgpu_dict *d, const uint8_t *utf8, const uint
         rc = run_chunk(k, done, m);
         done += m;
     }
-    c->h2d_queued = false;
-    pool_put(d, c);
     if (n_bytes) *n_bytes = k.text_done;
     if (!rc && k.overflow) {
         set_error("text buffer too small: need %llu, capacity %llu", (unsigned long long)k.text_done, (unsigned long long)text_capacity);

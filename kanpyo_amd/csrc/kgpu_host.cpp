@@ -1,10 +1,11 @@
 // kanpyo_amd/csrc/kgpu_host.cpp -- kgpu_tokenize_batch beyond the small calls: the large-call pipeline over host buffers.
 //
 // Owns: the worker pool (with no threads its tasks run on the calling thread), parallel_copy, is_pinned_host, the argument check of a
-// host batch, a chunk's input block (ChunkInput) and mapped result block (ChunkBlock, shared with kgpu_multi.cpp), the output side of a
-// lines chunk (LinesChunk, shared with kgpu_split_host.cpp), the chunk sizes of the pipeline (the ring itself is run_pipeline,
-// kgpu_runtime.h), the 24-byte per-chunk fallback for tokens beyond the 8-byte record (HostJob), kgpu_tokenize_batch,
-// kgpu_tokenize_batch_lines and kgpu_tokenize_batch_words (one body, batch_lines, which kgpu_encode_batch shares), and kgpu_host_alloc / kgpu_host_free.
+// host batch, a chunk's input block (ChunkInput) and mapped result block (ChunkBlock, shared with kgpu_multi.cpp), the chunk sizes of the
+// pipeline (the ring itself is run_pipeline, kgpu_runtime.h), the 24-byte per-chunk fallback for tokens beyond the 8-byte record (HostJob),
+// kgpu_tokenize_batch; the frame of the other chunked host calls -- a chunk's records (RecordsChunk), its render (LinesChunk) by one of three
+// renderers (Renderer), a packed batch as a source of chunks (ChunkSource::packed, ::stage) -- with the body of the lines / words / encode calls over a
+// source and a renderer (lines_call) and its two wrappers (batch_lines, text_lines: the argument checks, the sink and the message of each column), kgpu_tokenize_batch_lines / _words; and kgpu_host_alloc / kgpu_host_free.
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
@@ -170,34 +171,48 @@ MergeSrc ChunkBlock::results(const kgpu_ctx *c) const {
     return MergeSrc{(const kgpu_token8 *)ph, (const uint32_t *)(ph + off_first), (const uint64_t *)(ph + off_toff), ph + off_status};
 }
 
-// ---- the output side of a lines chunk (kgpu_runtime.h: LinesChunk) ------------------------------------------
-int LinesChunk::prepare(kgpu_ctx *c, uint64_t n_, uint64_t total_) {
+// ---- one chunk of a chunked host call (kgpu_runtime.h: RecordsChunk, LinesChunk, Renderer) ------------------
+int RecordsChunk::prepare(kgpu_ctx *c, uint64_t n_, uint64_t total_) {
     n = n_; total = total_;
-    int rc;   // (the text block starts at 16 bytes per input byte -- cfg 2 renders about 14 -- and grows when a chunk's text outgrows it: finish)
-    // (words: a surface line is at most the input's bytes and a byte per token, and a byte for the sentence; a field's names may be longer: finish grows)
-    // (vocab: 4 bytes per kept token and bos / eos -- cfg 2 has a token per 3.6 bytes; finish grows)
-    const size_t text_guess = vocab ? ((size_t)total / 2 + (size_t)n * 2 + 1024) * 4 : words ? (size_t)total * 2 + (size_t)n + 4096 : (size_t)total * 16 + 4096;
+    int rc;
     if ((rc = c->out_tok.ensure((size_t)token_bound(total, n) * sizeof(kgpu_token) + 64)) || (rc = c->out_status.ensure((size_t)n + 16)) ||
-        (rc = c->out_off.ensure((size_t)(n + 1) * 8)) || (rc = c->lines_off.ensure((size_t)(n + 1) * 8, true)) ||
-        (rc = c->lines_status.ensure((size_t)n + 16, true)) || (rc = c->lines_text.ensure(text_guess, true)))
+        (rc = c->out_off.ensure((size_t)(n + 1) * 8)) || (rc = c->lines_status.ensure((size_t)n + 16, true)))
         return rc;
     return KGPU_OK;
 }
-// The launch chain over the chunk's input where it lies in device memory, 24-byte records into HBM, and the render behind them.
-int LinesChunk::launch(kgpu_ctx *c, const uint8_t *d_utf8_, const uint64_t *d_offsets_, const char *who) {
-    d_utf8 = d_utf8_; d_offsets = d_offsets_;
-    const int rc = tokenize_device_impl(c, d_utf8, d_offsets, n, total, (kgpu_token *)c->out_tok.p, nullptr, nullptr, nullptr, nullptr, token_bound(total, n),
-                                        (uint64_t *)c->out_off.p, (uint8_t *)c->out_status.p, who);
+// The launch chain over the chunk's input where it lies in device memory, 24-byte records into HBM.
+int RecordsChunk::launch(kgpu_ctx *c, const char *who) const {
+    return tokenize_device_impl(c, d_utf8, d_offsets, n, total, (kgpu_token *)c->out_tok.p, nullptr, nullptr, nullptr, nullptr, token_bound(total, n),
+                                (uint64_t *)c->out_off.p, (uint8_t *)c->out_status.p, who);
+}
+DeviceRecords RecordsChunk::records(const kgpu_ctx *c) const {
+    return DeviceRecords{d_utf8, d_offsets, n, (const kgpu_token *)c->out_tok.p, (const uint64_t *)c->out_off.p, (const uint8_t *)c->out_status.p, (uint8_t *)c->lines_status.d};
+}
+
+// The three renderers.  LINES: the text block starts at 16 bytes per input byte -- cfg 2 renders about 14.  WORDS: a surface line is at most the input's
+// bytes and a byte per token, and a byte for the sentence; a field's names may be longer.  IDS: 4 bytes per kept token and bos / eos -- cfg 2 has a token
+// per 3.6 bytes.  LinesChunk::finish grows the block when a chunk's output outgrows the guess.
+size_t Renderer::first_bytes(uint64_t total, uint64_t n) const {
+    return kind == IDS ? ((size_t)total / 2 + (size_t)n * 2 + 1024) * 4 : kind == WORDS ? (size_t)total * 2 + (size_t)n + 4096 : (size_t)total * 16 + 4096;
+}
+int Renderer::enqueue(kgpu_ctx *c, const DeviceRecords &r, void *d_out, size_t out_bytes, uint64_t *d_off, const char *who) const {
+    if (kind == IDS) return enqueue_encode(c, vocab, r, (int32_t *)d_out, out_bytes / 4, 0, 0, d_off, who);
+    if (kind == WORDS) return enqueue_words(c, words, r, (uint8_t *)d_out, out_bytes, d_off, who);
+    return enqueue_lines(c, r, (uint8_t *)d_out, out_bytes, d_off, who);
+}
+
+int LinesChunk::prepare(kgpu_ctx *c, uint64_t n_, uint64_t total_) {
+    int rc;   // (the mapped blocks are allocated in the order offsets, status, text)
+    if ((rc = c->lines_off.ensure((size_t)(n_ + 1) * 8, true)) || (rc = RecordsChunk::prepare(c, n_, total_)) || (rc = c->lines_text.ensure(renderer.first_bytes(total, n), true))) return rc;
+    return KGPU_OK;
+}
+int LinesChunk::launch(kgpu_ctx *c, const char *who) const {
+    const int rc = RecordsChunk::launch(c, who);
     return rc ? rc : render(c, who);
 }
-// The chunk's lines into the context's mapped blocks: text, chunk-relative text offsets, status.  The one place that chooses the renderer.
+// The chunk's lines into the context's mapped blocks: text, chunk-relative text offsets, status.
 int LinesChunk::render(kgpu_ctx *c, const char *who) const {
-    const DeviceRecords r{d_utf8, d_offsets, n, (const kgpu_token *)c->out_tok.p, (const uint64_t *)c->out_off.p, (const uint8_t *)c->out_status.p, (uint8_t *)c->lines_status.d};
-    uint8_t *out = (uint8_t *)c->lines_text.d;
-    uint64_t *off = (uint64_t *)c->lines_off.d;
-    if (vocab) return enqueue_encode(c, vocab, r, (int32_t *)out, c->lines_text.bytes / 4, 0, 0, off, who);
-    if (words) return enqueue_words(c, words, r, out, c->lines_text.bytes, off, who);
-    return enqueue_lines(c, r, out, c->lines_text.bytes, off, who);
+    return renderer.enqueue(c, records(c), c->lines_text.d, c->lines_text.bytes, (uint64_t *)c->lines_off.d, who);
 }
 // Wait for the chunk's render (its text is in the context's mapped block then) and copy the text behind the bytes already delivered (or only count,
 // once a buffer of the caller's has overflowed).  A rerun of the chunk's chain inside kgpu_ctx_sync came after the render queued behind the first
@@ -385,53 +400,80 @@ extern "C" int kgpu_tokenize_batch(kgpu_dict *d, const uint8_t *utf8, const uint
     return rc;
 }
 
-// One chunk of kgpu_tokenize_batch_lines: the input block of a host batch, the output side of a lines chunk.
-struct LinesJob {
-    kgpu_ctx *c = nullptr;
-    uint64_t lo = 0, m = 0;
+// A packed batch in host memory as the source of a chunked call: the ring of kgpu_tokenize_batch, two jobs held back.
+int ChunkSource::packed(kgpu_dict *d_, const char *who, const uint8_t *utf8_, const uint64_t *offsets_, uint64_t n_, bool features, bool empty_chunk_) {
+    int rc;
+    if ((rc = check_host_batch(who, offsets_, n_, utf8_)) || (features && (rc = require_features(d_, who)))) return rc;
+    HIPCHECK(hipSetDevice(d_->device));
+    d = d_; offsets = offsets_; n = n_; utf8 = utf8_;
+    depth = batch_depth(); held_back = 2; empty_chunk = empty_chunk_;
+    pinned = batch_is_pinned(utf8, offsets, n);
+    return KGPU_OK;
+}
+int ChunkSource::stage(kgpu_ctx *c, uint64_t lo, uint64_t m, const uint8_t *&d_utf8, const uint64_t *&d_offsets) const {
+    if (split.c) {   // the input is where the split left it
+        d_utf8 = (const uint8_t *)split.c->split_text.p; d_offsets = (const uint64_t *)split.c->split_off.p + lo;
+        return KGPU_OK;
+    }
+    const uint64_t *off = offsets + lo;
     ChunkInput in;
-    LinesChunk out;
-};
+    int rc;
+    if ((rc = in.prepare(c, m, off[m] - off[0], !pinned)) || (rc = upload_input(c, in, utf8, off, pinned))) return rc;
+    d_utf8 = in.d_text(c, off[0]); d_offsets = in.d_offsets(c);
+    return KGPU_OK;
+}
 
-// kgpu_tokenize_batch_lines (words and vocab null), kgpu_tokenize_batch_words and kgpu_encode_batch: the chunks differ in their renderer alone.
-int kgpu::batch_lines(kgpu_dict *d, const kgpu_words *words, const kgpu_vocab *vocab, const char *who, const uint8_t *utf8, const uint64_t *offsets, uint64_t n,
+// kgpu_tokenize_*_lines, kgpu_tokenize_*_words and kgpu_encode_*: the chunks differ in their renderer alone, the calls in their source.
+// (every call takes the chunk pipeline: the single-launch small-call path renders nothing)
+static int lines_call(const ChunkSource &src, const Renderer &r, const char *who, LinesSink &sink, uint64_t *n_units) {
+    sink.unit = r.unit();
+    if (!sink.overflow) sink.text_offsets[0] = 0;
+    LinesChunk proto;
+    proto.renderer = r;
+    const int rc = run_chunks(src, proto, who, [&](ChunkJob<LinesChunk> &j) { return j.out.finish(j.c, j.lo, sink, who); });
+    if (n_units) *n_units = sink.text_done;
+    return rc;
+}
+
+int kgpu::batch_lines(kgpu_dict *d, const Renderer &r, const char *who, const uint8_t *utf8, const uint64_t *offsets, uint64_t n,
                        uint8_t *text, uint64_t text_capacity, uint64_t *text_offsets, uint8_t *status, uint64_t *n_bytes) {
     if (!d || !offsets || !text_offsets || (text_capacity && !text)) { set_error("%s: null argument", who); return KGPU_ERR_INVALID_ARG; }
+    ChunkSource src;
     int rc;
-    if ((rc = check_host_batch(who, offsets, n, utf8)) || (rc = require_features(d, who))) return rc;
-    HIPCHECK(hipSetDevice(d->device));
-    // (every call takes the chunk pipeline: the single-launch small-call path renders nothing)
+    if ((rc = src.packed(d, who, utf8, offsets, n, true, true))) return rc;
     LinesSink sink{text, text_capacity, text_offsets, status, true};   // (status has n entries whatever the text buffer holds)
-    if (vocab) sink.unit = 4;
-    text_offsets[0] = 0;
-    const bool pinned_in = batch_is_pinned(utf8, offsets, n);
-    rc = run_pipeline<LinesJob>(d, offsets, n, batch_depth(), 2, true, nullptr,
-        [&](LinesJob &j) {
-            const uint64_t *off = offsets + j.lo;
-            const uint64_t total = off[j.m] - off[0];
-            int r;
-            j.out.words = words; j.out.vocab = vocab;
-            if ((r = j.in.prepare(j.c, j.m, total, !pinned_in)) || (r = j.out.prepare(j.c, j.m, total)) || (r = upload_input(j.c, j.in, utf8, off, pinned_in))) return r;
-            return j.out.launch(j.c, j.in.d_text(j.c, off[0]), j.in.d_offsets(j.c), who);
-        },
-        [&](LinesJob &j) { return j.out.finish(j.c, j.lo, sink, who); });
-    if (n_bytes) *n_bytes = sink.text_done;
-    if (!rc && sink.overflow) {
-        set_error("%s buffer too small: need %llu, capacity %llu", vocab ? "id" : "text", (unsigned long long)sink.text_done, (unsigned long long)text_capacity);
-        return KGPU_ERR_CAPACITY;
-    }
-    return rc;
+    if ((rc = lines_call(src, r, who, sink, n_bytes)) || !sink.overflow) return rc;
+    set_error("%s buffer too small: need %llu, capacity %llu", r.noun(), (unsigned long long)sink.text_done, (unsigned long long)text_capacity);
+    return KGPU_ERR_CAPACITY;
+}
+
+// The text column (kgpu_tokenize_text_lines / _words, kgpu_encode_text): the chunks' inputs are pointers into the split's output -- nothing of the text
+// returns to the host in between.
+int kgpu::text_lines(kgpu_dict *d, const Renderer &r, const char *WHO, const uint8_t *text, uint64_t len, uint8_t *out_text, uint64_t text_capacity,
+                      uint64_t *text_offsets, uint64_t offsets_capacity, uint8_t *status, uint64_t *n_lines, uint64_t *n_bytes) {
+    if (!d || (len && !text) || (text_capacity && !out_text) || (offsets_capacity && !text_offsets) || !n_lines || !n_bytes) { set_error("%s: null argument", WHO); return KGPU_ERR_INVALID_ARG; }
+    *n_lines = 0; *n_bytes = 0;
+    ChunkSource src;
+    int rc;
+    if ((rc = src.block(d, WHO, text, len, true))) return rc;
+    *n_lines = src.n;
+    LinesSink sink{out_text, text_capacity, text_offsets, status, false};   // (status is bounded by offsets_capacity: nothing of it after an overflow)
+    sink.overflow = src.n + 1 > offsets_capacity;
+    if ((rc = lines_call(src, r, WHO, sink, n_bytes)) || !sink.overflow) return rc;
+    set_error("%s: buffers too small: need %llu text bytes (capacity %llu) and %llu offsets (capacity %llu)", WHO, (unsigned long long)sink.text_done,
+              (unsigned long long)text_capacity, (unsigned long long)(src.n + 1), (unsigned long long)offsets_capacity);
+    return KGPU_ERR_CAPACITY;
 }
 
 extern "C" int kgpu_tokenize_batch_lines(kgpu_dict *d, const uint8_t *utf8, const uint64_t *offsets, uint64_t n,
                                          uint8_t *text, uint64_t text_capacity, uint64_t *text_offsets, uint8_t *status, uint64_t *n_bytes) {
-    return batch_lines(d, nullptr, nullptr, "kgpu_tokenize_batch_lines", utf8, offsets, n, text, text_capacity, text_offsets, status, n_bytes);
+    return batch_lines(d, Renderer(), "kgpu_tokenize_batch_lines", utf8, offsets, n, text, text_capacity, text_offsets, status, n_bytes);
 }
 
 extern "C" int kgpu_tokenize_batch_words(kgpu_words *w, const uint8_t *utf8, const uint64_t *offsets, uint64_t n,
                                          uint8_t *text, uint64_t text_capacity, uint64_t *text_offsets, uint8_t *status, uint64_t *n_bytes) {
     if (!w) { set_error("kgpu_tokenize_batch_words: null argument"); return KGPU_ERR_INVALID_ARG; }
-    return batch_lines(w->dict, w, nullptr, "kgpu_tokenize_batch_words", utf8, offsets, n, text, text_capacity, text_offsets, status, n_bytes);
+    return batch_lines(w->dict, Renderer(w), "kgpu_tokenize_batch_words", utf8, offsets, n, text, text_capacity, text_offsets, status, n_bytes);
 }
 
 // Pinned, device-visible host memory for the buffers of kgpu_tokenize_batch: the copies then run as DMA

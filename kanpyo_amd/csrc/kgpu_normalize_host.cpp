@@ -94,18 +94,13 @@ extern "C" int kgpu_normalize_batch(kgpu_dict *d, int form, const uint8_t *utf8,
     const uint64_t total = offsets[n] - offsets[0];
     if (total >= (1ull << 32)) { set_error("%s: 4 GiB of text or more; split the batch", who); return KGPU_ERR_INVALID_ARG; }
     HIPCHECK(hipSetDevice(d->device));
-    kgpu_ctx *c = nullptr;
-    if ((rc = pool_get(d, &c))) return rc;
-    const auto give_back = [&](int r) {
-        c->h2d_queued = false;
-        pool_put(d, c);
-        return r;
-    };
-    if ((rc = c->in_utf8.ensure((size_t)total + 16)) || (rc = c->in_off.ensure(((size_t)n + 1) * 8))) return give_back(rc);
-    if (total && (rc = ctx_h2d(c, c->in_utf8.p, utf8 + offsets[0], (size_t)total, "H2D text"))) return give_back(rc);
-    if ((rc = ctx_h2d(c, c->in_off.p, offsets, ((size_t)n + 1) * 8, "H2D offsets"))) return give_back(rc);
+    PooledCtx lease(d);
+    kgpu_ctx *c = lease.c;
+    if ((rc = lease.rc) || (rc = c->in_utf8.ensure((size_t)total + 16)) || (rc = c->in_off.ensure(((size_t)n + 1) * 8))) return rc;
+    if (total && (rc = ctx_h2d(c, c->in_utf8.p, utf8 + offsets[0], (size_t)total, "H2D text"))) return rc;
+    if ((rc = ctx_h2d(c, c->in_off.p, offsets, ((size_t)n + 1) * 8, "H2D offsets"))) return rc;
     const uint8_t *d_in = (const uint8_t *)c->in_utf8.p - offsets[0];   // (the offsets are as the caller has them)
-    return give_back(normalize_to_host(c, form, d_in, (const uint64_t *)c->in_off.p, n, total, text, text_capacity, text_offsets, status, false, n_bytes, who));
+    return normalize_to_host(c, form, d_in, (const uint64_t *)c->in_off.p, n, total, text, text_capacity, text_offsets, status, false, n_bytes, who);
 }
 
 extern "C" int kgpu_normalize_text(kgpu_dict *d, int form, const uint8_t *text, uint64_t len, uint8_t *out_text, uint64_t text_capacity,
@@ -117,17 +112,12 @@ extern "C" int kgpu_normalize_text(kgpu_dict *d, int form, const uint8_t *text, 
     if (len >= (1ull << 32)) { set_error("%s: block of 4 GiB or more; split it", who); return KGPU_ERR_INVALID_ARG; }
     HIPCHECK(hipSetDevice(d->device));
     int rc;
-    kgpu_ctx *c = nullptr;
-    if ((rc = pool_get(d, &c))) return rc;
-    const auto give_back = [&](int r) {
-        c->h2d_queued = false;
-        pool_put(d, c);
-        return r;
-    };
+    PooledCtx lease(d);
+    kgpu_ctx *c = lease.c;
     std::vector<uint64_t> off;
     uint64_t lines = 0;
-    if ((rc = split_block(c, text, len, who, off, lines))) return give_back(rc);
+    if ((rc = lease.rc) || (rc = split_block(c, text, len, who, off, lines))) return rc;
     *n_lines = lines;
-    return give_back(normalize_to_host(c, form, (const uint8_t *)c->split_text.p, (const uint64_t *)c->split_off.p, lines, off[lines], out_text, text_capacity,
-                                       text_offsets, status, lines + 1 > offsets_capacity, n_bytes, who));
+    return normalize_to_host(c, form, (const uint8_t *)c->split_text.p, (const uint64_t *)c->split_off.p, lines, off[lines], out_text, text_capacity,
+                             text_offsets, status, lines + 1 > offsets_capacity, n_bytes, who);
 }

@@ -1,5 +1,5 @@
 // kanpyo_amd/csrc/kgpu_runtime.h -- the host runtime's own types and the functions its files share: kgpu_dict.cpp (dictionary),
-// kgpu_ctx.cpp (contexts, launch chain, the shared head and tail of the four record consumers' enqueues), kgpu_host.cpp (large host calls), kgpu_small.cpp (small calls), kgpu_multi.cpp (the
+// kgpu_ctx.cpp (contexts, launch chain, the shared head and tail of the four record consumers' enqueues), kgpu_host.cpp (large host calls: the chunk frame of the lines, words, encode and count calls), kgpu_small.cpp (small calls), kgpu_multi.cpp (the
 // multi-device entry points), kgpu_split_host.cpp (lines of a raw block), kgpu_graphviz_host.cpp (DOT documents of a batch), kgpu_words_host.cpp (wakati), kgpu_count_host.cpp (word counts), kgpu_encode_host.cpp (vocabulary ids), kgpu_normalize_host.cpp (text normalisation).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -302,6 +302,17 @@ constexpr size_t ARENA_MAX = 1ull << 37;      // 128 GiB
 // the pooled contexts of a dictionary (one per call in flight)
 int pool_get(kgpu_dict *d, kgpu_ctx **c);
 void pool_put(kgpu_dict *d, kgpu_ctx *c);
+// A pooled context for the length of a scope: `rc` is pool_get's answer, and however the scope is left the context goes back without a copy flagged as
+// queued (a path that put its own copies on c->stream and waited for them left h2d_queued set).  put(): back before the scope ends.
+struct PooledCtx {
+    kgpu_dict *d = nullptr; kgpu_ctx *c = nullptr; int rc = KGPU_OK;
+    PooledCtx() = default;                                  // (empty: get() leases later)
+    explicit PooledCtx(kgpu_dict *d_) { get(d_); }
+    PooledCtx(const PooledCtx &) = delete; PooledCtx &operator=(const PooledCtx &) = delete;
+    ~PooledCtx() { put(); }
+    int get(kgpu_dict *d_) { d = d_; return rc = pool_get(d, &c); }
+    void put() { if (c) { c->h2d_queued = false; pool_put(d, c); c = nullptr; } }
+};
 int ctx_h2d(kgpu_ctx *c, void *dst, const void *src, size_t bytes, const char *what);   // a batch's H2D copy on c->stream (sets h2d_queued)
 int tokenize_device_impl(kgpu_ctx *c, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n, uint64_t total_bytes,
                          kgpu_token *d_tokens, kgpu_token8 *d_tokens8, uint32_t *d_first, uint8_t *status8, uint64_t *toff8, uint64_t token_capacity,
@@ -384,26 +395,61 @@ struct LinesSink {
     bool overflow = false;
     uint64_t unit = 1;   // bytes per element of `text`: 1, or 4 where the chunks deliver vocabulary ids (capacities, text_done and the offsets count elements)
 };
-// The output side of one chunk of a lines or words call (kgpu_tokenize_batch_lines / _words, kgpu_tokenize_text_lines / _words) on a pooled context, whatever put its input on the
-// device: the 24-byte records stay in HBM (c->out_tok) and the render behind the chain writes the chunk's text, chunk-relative text offsets and status
-// into c's mapped lines_* blocks.
-struct LinesChunk {
-    const kgpu_words *words = nullptr;                     // the words calls: render chooses the wakati renderer; null: the `kanpyo tokenize` lines
-    const kgpu_vocab *vocab = nullptr;                     // the encode calls: render chooses the vocabulary ids; the chunk's output block is counted in 4-byte units
+// What the chunks of a lines call render their records into: the `kanpyo tokenize` lines, a words handle's wakati lines or a vocabulary handle's ids.
+// The one value kgpu_tokenize_*_lines, kgpu_tokenize_*_words and kgpu_encode_* differ in, and the one place that tells the three apart (kgpu_host.cpp).
+struct Renderer {
+    enum Kind { LINES, WORDS, IDS } kind = LINES;
+    const kgpu_words *words = nullptr;                     // WORDS
+    const kgpu_vocab *vocab = nullptr;                     // IDS
+    Renderer() = default;
+    explicit Renderer(const kgpu_words *w) : kind(WORDS), words(w) {}
+    explicit Renderer(const kgpu_vocab *v) : kind(IDS), vocab(v) {}
+    uint64_t unit() const { return kind == IDS ? 4 : 1; }                  // bytes per element of the output (LinesSink::unit)
+    const char *noun() const { return kind == IDS ? "id" : "text"; }       // ... and what the overflow message calls it
+    size_t first_bytes(uint64_t total, uint64_t n) const;                   // a chunk's output block to begin with (LinesChunk::finish grows it)
+    int enqueue(kgpu_ctx *c, const DeviceRecords &r, void *d_out, size_t out_bytes, uint64_t *d_offsets, const char *who) const;
+};
+// One chunk of a chunked host call on a pooled context, whatever put its input on the device (ChunkSource::stage): the launch chain writes 24-byte
+// records that stay in HBM (c->out_tok), and whatever reads them mirrors the status bytes into c's mapped lines_status.
+struct RecordsChunk {
     uint64_t n = 0, total = 0;                             // sentences, bytes
-    const uint8_t *d_utf8 = nullptr;                       // the chunk's input in device memory (launch)
+    const uint8_t *d_utf8 = nullptr;                       // the chunk's input in device memory (ChunkSource::stage)
     const uint64_t *d_offsets = nullptr;
     int prepare(kgpu_ctx *c, uint64_t n, uint64_t total);                 // c's buffers big enough
-    int launch(kgpu_ctx *c, const uint8_t *d_utf8, const uint64_t *d_offsets, const char *who);   // the chain, then the render
+    int launch(kgpu_ctx *c, const char *who) const;                       // the chain
+    DeviceRecords records(const kgpu_ctx *c) const;                       // what a consumer of the chunk's records is given
+};
+// ... of a lines, words or encode call: the render behind the chain writes the chunk's text (or ids), chunk-relative offsets and status into c's mapped lines_* blocks.
+struct LinesChunk : RecordsChunk {
+    Renderer renderer;
+    int prepare(kgpu_ctx *c, uint64_t n, uint64_t total);
+    int launch(kgpu_ctx *c, const char *who) const;                       // the chain, then the render
     int render(kgpu_ctx *c, const char *who) const;                       // the render of the chunk's records alone
     int finish(kgpu_ctx *c, uint64_t lo, LinesSink &sink, const char *who) const;   // wait, and deliver behind what the sink holds: sentences [lo, lo + n) of the call
 };
+// Where the lines of a chunked host call come from.  packed(): a packed batch in host memory, each chunk uploaded as one block (ChunkInput) on the batch
+// calls' ring; block(): a raw block, copied and split once on a context of its own, which owns the packed lines until the source goes -- a chunk's input
+// is a pair of pointers into them.  Both check their input, then the features if asked to, and make the dictionary's device current.
+struct ChunkSource {
+    kgpu_dict *d = nullptr;
+    const uint64_t *offsets = nullptr;                     // host memory, n + 1 entries: what cuts the chunks
+    uint64_t n = 0;
+    int depth = 0, held_back = 0;                          // the ring (run_pipeline)
+    bool empty_chunk = false;
+    int packed(kgpu_dict *d, const char *who, const uint8_t *utf8, const uint64_t *offsets, uint64_t n, bool features, bool empty_chunk);   // kgpu_host.cpp
+    int block(kgpu_dict *d, const char *who, const uint8_t *text, uint64_t len, bool features);                                             // kgpu_split_host.cpp
+    int stage(kgpu_ctx *c, uint64_t lo, uint64_t m, const uint8_t *&d_utf8, const uint64_t *&d_offsets) const;   // sentences [lo, lo + m) on c's stream -> where they lie
+    const uint8_t *utf8 = nullptr;                         // packed
+    bool pinned = false;
+    PooledCtx split;                                       // block: the splitting context ...
+    std::vector<uint64_t> split_off;                       // ... and the lines' offsets on the host
+};
 
-// kgpu_host.cpp / kgpu_split_host.cpp: the bodies of the lines, words and encode host calls (words, vocab: at most one is set; vocab: `text` holds int32 ids
-// and text_capacity, *n_bytes and the offsets count ids)
-int batch_lines(kgpu_dict *d, const kgpu_words *words, const kgpu_vocab *vocab, const char *who, const uint8_t *utf8, const uint64_t *offsets, uint64_t n,
+// kgpu_host.cpp: the packed and the text column of the lines / words / encode host calls, one body over a source and a renderer behind both (`text` holds
+// r.unit()-byte elements; the capacity, *n_bytes and the offsets count them)
+int batch_lines(kgpu_dict *d, const Renderer &r, const char *who, const uint8_t *utf8, const uint64_t *offsets, uint64_t n,
                 uint8_t *text, uint64_t text_capacity, uint64_t *text_offsets, uint8_t *status, uint64_t *n_bytes);
-int text_lines(kgpu_dict *d, const kgpu_words *words, const kgpu_vocab *vocab, const char *who, const uint8_t *text, uint64_t len, uint8_t *out_text, uint64_t text_capacity,
+int text_lines(kgpu_dict *d, const Renderer &r, const char *who, const uint8_t *text, uint64_t len, uint8_t *out_text, uint64_t text_capacity,
                uint64_t *text_offsets, uint64_t offsets_capacity, uint8_t *status, uint64_t *n_lines, uint64_t *n_bytes);
 
 // The chunks of a large host call: at most `bytes` / `sents` each (test_hooks() may lower them).
@@ -452,6 +498,20 @@ int run_pipeline(kgpu_dict *d, const uint64_t *offsets, uint64_t n, int depth, i
     for (int k = 0; k < depth; ++k)
         if (jobs[k].c) pool_put(d, jobs[k].c);
     return rc;
+}
+// The ring over a source's chunks: a copy of `proto` per job; submit is stage, prepare, launch (a context's buffers are then first allocated in the order
+// input block, records, mapped blocks: with the records first kgpu_encode_batch measured 2.6 % slower, profiles/experiments/host_frame.txt); finish(job) delivers.
+template <class Chunk> struct ChunkJob { kgpu_ctx *c = nullptr; uint64_t lo = 0, m = 0; Chunk out; };
+template <class Chunk, class Finish>
+int run_chunks(const ChunkSource &src, const Chunk &proto, const char *who, Finish finish) {
+    return run_pipeline<ChunkJob<Chunk>>(src.d, src.offsets, src.n, src.depth, src.held_back, src.empty_chunk, nullptr,
+        [&](ChunkJob<Chunk> &j) {
+            j.out = proto;
+            int r;
+            if ((r = src.stage(j.c, j.lo, j.m, j.out.d_utf8, j.out.d_offsets)) || (r = j.out.prepare(j.c, j.m, src.offsets[j.lo + j.m] - src.offsets[j.lo]))) return r;
+            return j.out.launch(j.c, who);
+        },
+        finish);
 }
 
 // kgpu_small.cpp

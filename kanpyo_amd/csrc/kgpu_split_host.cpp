@@ -1,10 +1,8 @@
 // kanpyo_amd/csrc/kgpu_split_host.cpp -- read_line + trim_end on the device (kgpu_split.hip) behind the C ABI.
 //
-// Owns: kgpu_split_lines_device / kgpu_ctx_sync_split (a block resident in HBM, on a context's stream) and kgpu_tokenize_text_lines /
-// kgpu_tokenize_text_words (one body, text_lines: a raw block in host memory: one copy to the device, the split, then the lines go through the launch chain and the render in chunks
-// on pooled contexts -- their inputs are pointers into the split's output, nothing of the text returns to the host in between; the
-// chunks are LinesChunk in run_pipeline, kgpu_runtime.h, as those of kgpu_tokenize_batch_lines); split_block, the copy and the split in front of them, which
-// kgpu_count_text (kgpu_count_host.cpp) shares.
+// Owns: kgpu_split_lines_device / kgpu_ctx_sync_split (a block resident in HBM, on a context's stream); split_block (a raw block in host memory: one copy
+// to the device, the split) and the source of chunks made of it (ChunkSource::block), which kgpu_count_text shares (kgpu_normalize_text: split_block alone);
+// and kgpu_tokenize_text_lines / kgpu_tokenize_text_words, the text column's wrappers around text_lines (kgpu_host.cpp).
 #include <vector>
 
 #include "kgpu_runtime.h"
@@ -70,65 +68,27 @@ int kgpu::split_block(kgpu_ctx *sc, const uint8_t *text, uint64_t len, const cha
     return KGPU_OK;
 }
 
-// ---- kgpu_tokenize_text_lines: a raw block in host memory -> the CLI's output ---------------------------------------------------------
-// One chunk of the block's lines on a pooled context: lines [lo, lo + m) of the split's table, whose input is where the split left it.
-struct TextJob {
-    kgpu_ctx *c = nullptr;
-    uint64_t lo = 0, m = 0;
-    LinesChunk out;
-};
-
-// kgpu_tokenize_text_lines (words and vocab null), kgpu_tokenize_text_words and kgpu_encode_text: the chunks differ in their renderer alone.
-int kgpu::text_lines(kgpu_dict *d, const kgpu_words *words, const kgpu_vocab *vocab, const char *WHO, const uint8_t *text, uint64_t len, uint8_t *out_text, uint64_t text_capacity,
-                      uint64_t *text_offsets, uint64_t offsets_capacity, uint8_t *status, uint64_t *n_lines, uint64_t *n_bytes) {
-    if (!d || (len && !text) || (text_capacity && !out_text) || (offsets_capacity && !text_offsets) || !n_lines || !n_bytes) { set_error("%s: null argument", WHO); return KGPU_ERR_INVALID_ARG; }
-    *n_lines = 0; *n_bytes = 0;
-    if (len >= (1ull << 32)) { set_error("%s: block of 4 GiB or more; split it", WHO); return KGPU_ERR_INVALID_ARG; }
+// A raw block in host memory as the source of a chunked call: the copy and the split on a pooled context that owns the block, the packed lines and their
+// offsets until the source goes; four chunks in flight, one pooled context each (the dictionary's shared streams run that many launches side by side).
+int ChunkSource::block(kgpu_dict *d_, const char *who, const uint8_t *text, uint64_t len, bool features) {
+    if (len >= (1ull << 32)) { set_error("%s: block of 4 GiB or more; split it", who); return KGPU_ERR_INVALID_ARG; }
     int rc;
-    if ((rc = require_features(d, WHO))) return rc;
-    HIPCHECK(hipSetDevice(d->device));
-    kgpu_ctx *sc = nullptr;   // the splitting context: it owns the block, the packed lines and their offsets until the call is over
-    if ((rc = pool_get(d, &sc))) return rc;
-    constexpr int DEPTH = 4;   // chunks in flight, one pooled context each (the dictionary's shared streams run that many launches side by side)
-    std::vector<uint64_t> off;
-    uint64_t lines = 0;
-    const auto give_back = [&](int r) {
-        sc->h2d_queued = false;
-        pool_put(d, sc);
-        return r;
-    };
-    if ((rc = split_block(sc, text, len, WHO, off, lines))) return give_back(rc);
-    *n_lines = lines;
-    const uint8_t *d_text = (const uint8_t *)sc->split_text.p;   // the chunks' input: pointers into the split's output
-    const uint64_t *d_off = (const uint64_t *)sc->split_off.p;
-    LinesSink sink{out_text, text_capacity, text_offsets, status, false};   // (status is bounded by offsets_capacity: nothing of it after an overflow)
-    if (vocab) sink.unit = 4;
-    sink.overflow = lines + 1 > offsets_capacity;
-    if (!sink.overflow) text_offsets[0] = 0;
-    rc = run_pipeline<TextJob>(d, off.data(), lines, DEPTH, 0, false, nullptr,
-        [&](TextJob &j) {
-            j.out.words = words; j.out.vocab = vocab;
-            const int r = j.out.prepare(j.c, j.m, off[j.lo + j.m] - off[j.lo]);
-            return r ? r : j.out.launch(j.c, d_text, d_off + j.lo, WHO);
-        },
-        [&](TextJob &j) { return j.out.finish(j.c, j.lo, sink, WHO); });
-    *n_bytes = sink.text_done;
-    if (rc) return give_back(rc);
-    if (sink.overflow) {
-        set_error("%s: buffers too small: need %llu text bytes (capacity %llu) and %llu offsets (capacity %llu)", WHO, (unsigned long long)sink.text_done,
-                  (unsigned long long)text_capacity, (unsigned long long)(lines + 1), (unsigned long long)offsets_capacity);
-        return give_back(KGPU_ERR_CAPACITY);
-    }
-    return give_back(KGPU_OK);
+    if (features && (rc = require_features(d_, who))) return rc;
+    HIPCHECK(hipSetDevice(d_->device));
+    d = d_; depth = 4; held_back = 0; empty_chunk = false;
+    if ((rc = split.get(d)) || (rc = split_block(split.c, text, len, who, split_off, n))) return rc;
+    offsets = split_off.data();
+    return KGPU_OK;
 }
 
+// ---- the text column's wrappers: text_lines (kgpu_host.cpp) over such a source -------------------------------------------------------------
 extern "C" int kgpu_tokenize_text_lines(kgpu_dict *d, const uint8_t *text, uint64_t len, uint8_t *out_text, uint64_t text_capacity, uint64_t *text_offsets,
                                         uint64_t offsets_capacity, uint8_t *status, uint64_t *n_lines, uint64_t *n_bytes) {
-    return text_lines(d, nullptr, nullptr, "kgpu_tokenize_text_lines", text, len, out_text, text_capacity, text_offsets, offsets_capacity, status, n_lines, n_bytes);
+    return text_lines(d, Renderer(), "kgpu_tokenize_text_lines", text, len, out_text, text_capacity, text_offsets, offsets_capacity, status, n_lines, n_bytes);
 }
 
 extern "C" int kgpu_tokenize_text_words(kgpu_words *w, const uint8_t *text, uint64_t len, uint8_t *out_text, uint64_t text_capacity, uint64_t *text_offsets,
                                         uint64_t offsets_capacity, uint8_t *status, uint64_t *n_lines, uint64_t *n_bytes) {
     if (!w) { set_error("kgpu_tokenize_text_words: null argument"); return KGPU_ERR_INVALID_ARG; }
-    return text_lines(w->dict, w, nullptr, "kgpu_tokenize_text_words", text, len, out_text, text_capacity, text_offsets, offsets_capacity, status, n_lines, n_bytes);
+    return text_lines(w->dict, Renderer(w), "kgpu_tokenize_text_words", text, len, out_text, text_capacity, text_offsets, offsets_capacity, status, n_lines, n_bytes);
 }

@@ -3,7 +3,7 @@
 // Owns: the check of a kgpu_words_spec, kgpu_words_create / kgpu_words_destroy (the per-row entries and the name pool are built by
 // build_word_table, kgpu_features.cpp, and uploaded once per handle), the render's enqueue on a context (enqueue_words),
 // kgpu_format_words_device, and the host-only test hook kgpu_debug_word_table.  The host calls kgpu_tokenize_batch_words and
-// kgpu_tokenize_text_words are their _lines counterparts with LinesChunk::words set (kgpu_host.cpp, kgpu_split_host.cpp).
+// kgpu_tokenize_text_words are their _lines counterparts with the handle as the Renderer (kgpu_host.cpp, kgpu_split_host.cpp).
 #include <algorithm>
 #include <cstring>
 #include <vector>
