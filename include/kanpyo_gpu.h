@@ -272,7 +272,8 @@ void kgpu_host_free(void *p);
  * kgpu_ctx_sync waits and reports the dense token count (or KGPU_ERR_CAPACITY). */
 int kgpu_ctx_create(kgpu_dict *d, void *hip_stream /* NULL: one of the dictionary's shared streams (kgpu_plan_info.streams of them) */, kgpu_ctx **out);
 /* One batch in flight per ctx; keep four or more contexts busy to fill the chip (eight for cfg 2's 4096-sentence batches).  Contexts may share a
- * stream (each waits on its own completion event); those created with NULL share kgpu_plan_info.streams per dictionary, and a batch of long
+ * stream (each waits on its own completion event); those created with NULL share kgpu_plan_info.streams per dictionary -- a NULL-stream context
+ * runs each batch on the least-loaded of the dictionary's shared streams -- and a batch of long
  * sentences is moved to one of kgpu_plan_info.long_streams for its duration.  With a caller-owned stream everything stays on that stream. */
 void kgpu_ctx_destroy(kgpu_ctx *c);
 int kgpu_tokenize_device(kgpu_ctx *c, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n,

@@ -7,6 +7,20 @@
 
 namespace kgpu {
 
+unsigned pick_stream(const std::atomic<uint64_t> *load, unsigned n, std::atomic<unsigned> &cursor) {
+    if (n <= 1) return 0;
+    const unsigned from = cursor.load(std::memory_order_relaxed) % n;
+    unsigned best = from;
+    uint64_t least = load[from].load(std::memory_order_relaxed);
+    for (unsigned k = 1; k < n && least; ++k) {   // (an empty stream at the cursor: nothing beats it)
+        const unsigned i = (from + k) % n;
+        const uint64_t l = load[i].load(std::memory_order_relaxed);
+        if (l + l / STREAM_TIE_SHARE < least) { least = l; best = i; }   // (lighter by more than the tie band: see kgpu_chain.h)
+    }
+    cursor.store((best + 1) % n, std::memory_order_relaxed);
+    return best;
+}
+
 LaunchPlan make_launch_plan(int cus, const Occupancy &occ) {
     LaunchPlan t{};
     t.general_workgroups = cus * 2;  // the last resort is rarely needed: few workgroups, so that an empty launch drains quickly on a busy chip

@@ -106,4 +106,19 @@ Chain tail_chain(const LaunchPlan &plan, const Chain &ran);   // what a chain th
 void chain_feedback(const LaunchPlan &plan, const Chain &ran, const Chain *tail, const Control &h, uint64_t n, uint32_t est_q8, Steering &st,
                     ContextSteering &cs);
 
+// Which of a dictionary's shared streams a batch goes to: the one with the least load, where a stream's load is the weight of the batches the host
+// knows to be in flight on it (added at the enqueue, taken off when the batch's context retires it).  A weight is the batch's bytes -- a tail batch of
+// 1696 sentences weighs what it costs, not what a full one does -- and a constant, so that empty batches count.  Eight contexts handed round-robin
+// to three streams load them 3 : 3 : 2 for good, and the job then runs at the pace of the streams that carry three.
+constexpr uint64_t STREAM_BATCH_BASE = 256;
+inline uint64_t stream_batch_weight(uint64_t total_bytes) { return total_bytes + STREAM_BATCH_BASE; }
+// -> the least-loaded of load[0 .. n); ties go to the first candidate at or after the cursor, which moves past the pick (equal loads: strict rotation).
+// Loads within an eighth of each other tie: the chunks of a large host call differ by a few per cent in bytes, and the host retires them in order while
+// the streams drain independently -- told apart byte by byte, streams that hold three such chunks each are picked at random, one ends up with four while
+// another runs dry, and the call loses a sixth of its rate against plain rotation (profiles/experiments/stream_balance.txt).  A stream with a batch fewer
+// among up to seven, or with a tail batch in a full one's place, is outside the band.
+constexpr uint64_t STREAM_TIE_SHARE = 8;
+// Relaxed atomics, as Steering: two callers that pick the same stream at once lose nothing but a little balance.
+unsigned pick_stream(const std::atomic<uint64_t> *load, unsigned n, std::atomic<unsigned> &cursor);
+
 }  // namespace kgpu

@@ -1,7 +1,7 @@
 // kanpyo_amd/csrc/kgpu_ctx.cpp -- the contexts of include/kanpyo_gpu.h and the launch chain behind them.
 //
-// Owns: context create / destroy, the lease of a dictionary's pooled contexts (pool_get / pool_put; the scope guard over them is PooledCtx, kgpu_runtime.h), the stream of a batch (ctx_pick_stream), the one
-// way a batch's host-to-device copy is queued (ctx_h2d), running a batch's chain (kgpu_chain.cpp decides it) with the scan and
+// Owns: context create / destroy, the lease of a dictionary's pooled contexts (pool_get / pool_put; the scope guard over them is PooledCtx, kgpu_runtime.h), the stream of a batch (ctx_begin_batch chooses the shared stream by load before the
+// batch's first command, ctx_pick_stream places the batch), the one way a batch's host-to-device copy is queued (ctx_h2d), running a batch's chain (kgpu_chain.cpp decides it) with the scan and
 // compaction behind it, the reruns in kgpu_ctx_sync, the profiling / ablation / plan getters, the two words a launch publishes to the
 // host (HostReport), the render of a batch's lines, and the lattice dump.
 #include <algorithm>
@@ -28,17 +28,23 @@ extern "C" int kgpu_ctx_create(kgpu_dict *d, void *hip_stream, kgpu_ctx **out) {
         // which its streams get one fewer; a stream beyond that shares a queue and unbalances them (4 streams on the
         // default: 52 M sentences/s instead of 68).  Four concurrent launches are the optimum (71.5; five: 58), so:
         // 4 streams when the process was started with GPU_MAX_HW_QUEUES >= 5, else 3.  KGPU_STREAMS overrides.
+        // The dictionary's first such context creates them all: a context is not tied to one of them -- each of its batches goes to the least-loaded
+        // (ctx_begin_batch), so a single context uses them in turn, and eight contexts load three streams 8 : 8 : 8 over any 24 batches, not 3 : 3 : 2.
         const unsigned n_streams = planned_streams();
-        if (d->streams.size() < n_streams) {
+        if (!d->stream_load) {
+            d->stream_load.reset(new std::atomic<uint64_t>[n_streams]);
+            d->stream_batches.reset(new std::atomic<uint64_t>[n_streams]);
+            for (unsigned k = 0; k < n_streams; ++k) { d->stream_load[k].store(0, std::memory_order_relaxed); d->stream_batches[k].store(0, std::memory_order_relaxed); }
+            d->streams.reserve(n_streams);   // (read without the lock once a context exists: never reallocated)
+        }
+        while (d->streams.size() < n_streams) {
             hipStream_t st = nullptr;
             hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
             if (e != hipSuccess) { set_error("hipStreamCreate: %s", hipGetErrorString(e)); kgpu_ctx_destroy(c); return KGPU_ERR_HIP; }
             d->streams.push_back(st);
-            c->stream = st;
-        } else {
-            c->stream = d->streams[d->next_stream++ % d->streams.size()];
         }
-        c->short_stream = c->stream;
+        c->short_idx = pick_stream(d->stream_load.get(), n_streams, d->stream_cursor);   // (until its first batch: what the small calls and the dumps run on)
+        c->stream = c->short_stream = d->streams[c->short_idx];
     }
     if (hipMalloc((void **)&c->d_ctl, sizeof(Control)) != hipSuccess ||
         hipHostMalloc((void **)&c->h_ctl, sizeof(Control), hipHostMallocMapped) != hipSuccess ||
@@ -60,9 +66,11 @@ extern "C" int kgpu_ctx_create(kgpu_dict *d, void *hip_stream, kgpu_ctx **out) {
     return KGPU_OK;
 }
 
-// The pending batch is over (completed or given up): the context is free, its share of the dictionary's long sentences in flight is returned.
+// The pending batch is over (completed or given up): the context is free, its share of the dictionary's long sentences in flight and its weight on
+// its shared stream are returned.
 static void ctx_retire(kgpu_ctx *c) {
     c->pending = false;
+    if (c->load_weight) { c->dict->stream_load[c->load_idx].fetch_sub(c->load_weight, std::memory_order_relaxed); c->load_weight = 0; }
     if (c->steer.counted_long) { c->dict->steer.long_sentences_in_flight.fetch_sub(c->steer.counted_long, std::memory_order_relaxed); c->steer.counted_long = 0; }
 }
 
@@ -99,11 +107,39 @@ static int next_event(kgpu_ctx *c, hipEvent_t *ev) {
     return KGPU_OK;
 }
 
-// The stream of the next batch.  A chain that starts with the windowed kernel (kgpu_chain.cpp: starts_with_window) runs on a stream of the long set,
+// The head of a batch, before its first command is queued (ctx_h2d: a host-buffer path's copy; else ctx_pick_stream): its shared stream is the least-loaded of
+// the dictionary's (kgpu_chain.h: pick_stream).  Chosen HERE and not behind the copy: a batch that left the stream its copy is on would have to wait for an
+// event there, behind the other contexts' whole backlog.  The context moves only when nothing of its own is pending where it is -- the tokenize batch retired,
+// no lines / count / encode / normalise / split call waiting for its sync -- so its buffers need no ordering between the streams; otherwise it stays.  A
+// context that is on its long stream keeps `stream` (the copy goes there, as before; ctx_pick_stream decides where the batch runs).  The caller's own stream: never.
+static void ctx_begin_batch(kgpu_ctx *c) {
+    if (c->batch_begun) return;
+    c->batch_begun = true;
+    if (c->own_stream || c->pending || c->lines_report.pending || c->split_report.pending) return;
+    kgpu_dict *d = c->dict;
+    const bool on_short = c->stream == c->short_stream;
+    c->short_idx = pick_stream(d->stream_load.get(), (unsigned)d->streams.size(), d->stream_cursor);
+    c->short_stream = d->streams[c->short_idx];
+    if (on_short) c->stream = c->short_stream;
+}
+
+// The batch is queued on a shared stream: its weight there until ctx_retire (a tail pass or a rerun inside kgpu_ctx_sync stays on the stream and under this weight).
+static void ctx_count_load(kgpu_ctx *c, uint64_t total_bytes) {
+    if (c->own_stream || c->stream != c->short_stream || c->load_weight) return;
+    kgpu_dict *d = c->dict;
+    c->load_idx = c->short_idx;
+    c->load_weight = stream_batch_weight(total_bytes);
+    d->stream_load[c->load_idx].fetch_add(c->load_weight, std::memory_order_relaxed);
+    d->stream_batches[c->load_idx].fetch_add(1, std::memory_order_relaxed);
+}
+
+// The stream the batch runs on: the short stream ctx_begin_batch chose, or the context's long stream.  A chain that starts with the windowed kernel (kgpu_chain.cpp: starts_with_window) runs on a stream of the long set,
 // one per context, so that eight such launches overlap instead of four (cfg 5, 8 in flight: 3.40 -> 3.96 Gchar/s; profiles/experiments/r05_long_chains.txt).
 // The context's previous batch is complete here (kgpu_ctx_sync), so switching streams needs no ordering for the context's own buffers; whatever the
 // host-buffer paths queued on the old stream for THIS batch (their H2D copy) is ordered in front by an event.
 static int ctx_pick_stream(kgpu_ctx *c, const Batch &b) {
+    ctx_begin_batch(c);
+    c->batch_begun = false;   // (the next ctx_h2d or tokenize call begins the next batch)
     if (c->own_stream) { c->h2d_queued = false; return KGPU_OK; }
     hipStream_t want = c->short_stream;
     // ... and so does a pool-first chain whose last batch sent an eighth or more of its sentences on to the windowed kernel: its launches behind the pool
@@ -172,9 +208,27 @@ static int enqueue(kgpu_ctx *c, const BatchArgs &a, const Batch &b) {
     return run_chain(c, a, timed ? ev + 1 : nullptr, "k_tokenize");
 }
 
+static int tokenize_batch(kgpu_ctx *c, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n, uint64_t total_bytes,
+                          kgpu_token *d_tokens, kgpu_token8 *d_tokens8, uint32_t *d_first, uint8_t *status8, uint64_t *toff8, uint64_t token_capacity,
+                          uint64_t *d_tok_offsets, uint8_t *d_status, const char *who);
+
+// A batch on the context: tokenize_batch below.  However it fails, the context is left without a batch begun -- the next batch chooses its stream anew -- and,
+// if a host-buffer path had queued this batch's copy, with that copy through: it writes the context's input block, which the next batch's copy on
+// another stream writes again (an error path: the wait behind a shared stream's backlog costs nothing that matters).
 int kgpu::tokenize_device_impl(kgpu_ctx *c, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n, uint64_t total_bytes,
                                 kgpu_token *d_tokens, kgpu_token8 *d_tokens8, uint32_t *d_first, uint8_t *status8, uint64_t *toff8, uint64_t token_capacity,
                                 uint64_t *d_tok_offsets, uint8_t *d_status, const char *who) {
+    const int rc = tokenize_batch(c, d_utf8, d_offsets, n, total_bytes, d_tokens, d_tokens8, d_first, status8, toff8, token_capacity, d_tok_offsets, d_status, who);
+    if (rc && c) {
+        if (c->h2d_queued && !c->pending) (void)hipStreamSynchronize(c->stream);
+        c->batch_begun = c->h2d_queued = false;
+    }
+    return rc;
+}
+
+static int tokenize_batch(kgpu_ctx *c, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n, uint64_t total_bytes,
+                          kgpu_token *d_tokens, kgpu_token8 *d_tokens8, uint32_t *d_first, uint8_t *status8, uint64_t *toff8, uint64_t token_capacity,
+                          uint64_t *d_tok_offsets, uint8_t *d_status, const char *who) {
     if (!c || !d_offsets || !d_tok_offsets || (n && !d_status) || (total_bytes && !d_utf8) ||
         (token_capacity && !d_tokens && !d_tokens8) || (d_tokens8 && n && !d_first)) {
         set_error("%s: null argument", who);
@@ -214,7 +268,9 @@ int kgpu::tokenize_device_impl(kgpu_ctx *c, const uint8_t *d_utf8, const uint64_
     a.est_q8 = b.est_q8;
     for (int k = 0; k < 4; ++k) a.ovf[k] = (uint32_t *)c->ovf.p + (size_t)k * (n + 1);
     c->batch = b;
-    return enqueue(c, a, b);
+    if ((rc = enqueue(c, a, b))) return rc;
+    ctx_count_load(c, total_bytes);
+    return KGPU_OK;
 }
 
 // The tail chain (c->chain) over work list `li` of the pending batch, which the first chain left unserved, then scan + compaction again.
@@ -359,6 +415,19 @@ extern "C" int kgpu_ctx_sync(kgpu_ctx *c, uint64_t *n_tokens) {
 
 // Tests only (not in the header): the form of the context's last scan + compaction, as launch_scan_compact numbers it (0: none yet).
 extern "C" int kgpu_debug_aux_form(kgpu_ctx *c) { return c ? c->aux_form : -1; }
+// ... and how many batches each of the dictionary's shared streams has been given since the last reset: -> the number of shared streams (0: none created yet),
+// the first `cap` of their counts in out[].
+extern "C" int kgpu_debug_stream_batches(kgpu_dict *d, uint64_t *out, int cap, int reset) {
+    if (!d) return -1;
+    std::lock_guard<std::mutex> g(d->pool_mu);
+    const int n = (int)d->streams.size();
+    if (!d->stream_batches || n < (int)planned_streams()) return 0;
+    for (int k = 0; k < n; ++k) {
+        const uint64_t v = reset ? d->stream_batches[k].exchange(0, std::memory_order_relaxed) : d->stream_batches[k].load(std::memory_order_relaxed);
+        if (out && k < cap) out[k] = v;
+    }
+    return n;
+}
 
 extern "C" int kgpu_ctx_set_profiling(kgpu_ctx *c, int mode) {
     if (!c) { set_error("kgpu_ctx_set_profiling: null ctx"); return KGPU_ERR_INVALID_ARG; }
@@ -530,13 +599,15 @@ int kgpu::pool_get(kgpu_dict *d, kgpu_ctx **out) {
     return KGPU_OK;
 }
 void kgpu::pool_put(kgpu_dict *d, kgpu_ctx *c) {
+    c->batch_begun = c->h2d_queued = false;   // (a path that waited for its ctx_h2d copies itself, without a tokenize batch behind them)
     std::lock_guard<std::mutex> g(d->pool_mu);
     d->pool.push_back(c);
 }
 
-// A host-buffer path's copy of a batch's input, queued on the context's stream in front of the batch: the flag makes ctx_pick_stream order the
-// batch behind it if the batch goes to another stream.
+// A host-buffer path's copy of a batch's input, queued in front of the batch on the stream ctx_begin_batch chooses for it: the flag makes ctx_pick_stream
+// order the batch behind the copy if the batch goes to another stream (a long one).  Everything a path queues ahead of tokenize_device_impl goes through here.
 int kgpu::ctx_h2d(kgpu_ctx *c, void *dst, const void *src, size_t bytes, const char *what) {
+    ctx_begin_batch(c);
     const hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream);
     if (e != hipSuccess) { set_error("%s: %s", what, hipGetErrorString(e)); return KGPU_ERR_HIP; }
     c->h2d_queued = true;
@@ -549,7 +620,7 @@ extern "C" int kgpu_lattice_dump(kgpu_dict *d, const uint8_t *utf8, uint64_t len
     if (len >= (1ull << 31)) { set_error("kgpu_lattice_dump: sentence too long"); return KGPU_ERR_INVALID_ARG; }
     *out = kgpu_lattice{};
     HIPCHECK(hipSetDevice(d->device));
-    PooledCtx lease(d);   // (the copies below go on c->stream, where the dump's own launch follows: no ctx_pick_stream, so no h2d_queued -- and none left behind)
+    PooledCtx lease(d);   // (the copies below go on c->stream, where the dump's own launch follows and is waited for: no batch is begun)
     kgpu_ctx *c = lease.c;
     int rc = lease.rc;
     if (rc) return rc;

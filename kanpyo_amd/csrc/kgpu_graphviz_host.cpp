@@ -46,7 +46,7 @@ int run_chunk(Call &k, uint64_t lo, uint64_t m) {
     k.rel.resize((size_t)m + 1);
     for (uint64_t i = 0; i <= m; ++i) k.rel[(size_t)i] = off[i] - base;
     hipError_t e;
-    // (every copy and launch goes on c->stream and is waited for below: no ctx_pick_stream, so no h2d_queued -- as kgpu_lattice_dump)
+    // (every copy and launch goes on c->stream and is waited for below: no batch is begun -- as kgpu_lattice_dump)
     if (total && (e = hipMemcpyAsync(c->in_utf8.p, k.utf8 + base, (size_t)total, hipMemcpyHostToDevice, c->stream)) != hipSuccess) return hip_fail(k, e, "H2D");
     if ((e = hipMemcpyAsync(c->in_off.p, k.rel.data(), (size_t)(m + 1) * 8, hipMemcpyHostToDevice, c->stream)) != hipSuccess) return hip_fail(k, e, "H2D");
     GraphvizArgs g{};

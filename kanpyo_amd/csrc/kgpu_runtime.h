@@ -9,6 +9,7 @@
 #include <condition_variable>
 #include <deque>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <shared_mutex>
 #include <thread>
@@ -86,11 +87,15 @@ struct kgpu_dict {
     std::mutex pool_mu;
     std::vector<kgpu_ctx *> pool;
     Steering steer;   // the launch chain's dictionary-wide state (kgpu_chain.h)
-    // Streams handed round-robin to contexts created without one.  HIP multiplexes streams onto three
+    // Streams shared by the contexts created without one.  HIP multiplexes streams onto three
     // hardware queues: a 4th stream queues behind the 1st and unbalances them (measured -25 %), so any
-    // number of contexts shares three streams; each context waits on its own completion event.
+    // number of contexts shares three streams; each context waits on its own completion event.  All of them are created with the
+    // dictionary's first such context (under pool_mu) and stay until the dictionary goes: a batch reads the vector without the lock.
+    // Every batch goes to the least-loaded of them (kgpu_chain.h: pick_stream; kgpu_ctx.cpp: ctx_begin_batch): stream_load[k] is the weight of
+    // the batches in flight on streams[k] as the host knows it, stream_batches[k] what it has been given (kgpu_debug_stream_batches: the tests' witness).
     std::vector<hipStream_t> streams;
-    unsigned next_stream = 0;
+    std::unique_ptr<std::atomic<uint64_t>[]> stream_load, stream_batches;
+    std::atomic<unsigned> stream_cursor{0};
     // A second set for chains that START with the windowed kernel (batches of long sentences: kgpu_ctx.cpp, ctx_pick_stream): such a launch holds a thousand
     // single-wavefront workgroups for milliseconds and its slots empty out one by one, so the chip fills only when more of them overlap than the four launches
     // the pool kernel wants -- one stream per context, up to eight, created when the first such batch arrives (round 5: cfg 5 2.97 -> 3.96 Gchar/s).
@@ -170,9 +175,13 @@ struct kgpu_ctx {
     kgpu_dict *dict = nullptr;
     hipStream_t stream = nullptr;       // the stream of the pending / next batch (one of the dictionary's shared streams unless the caller gave one)
     hipStream_t short_stream = nullptr, long_stream = nullptr;   // what `stream` alternates between (library-owned streams only)
+    unsigned short_idx = 0;             // short_stream is dict->streams[short_idx]: chosen anew for every batch (ctx_begin_batch)
+    uint64_t load_weight = 0;           // what the pending batch added to dict->stream_load[load_idx] (0: nothing; ctx_retire takes it off)
+    unsigned load_idx = 0;
     bool own_stream = false;            // the caller's stream: never switched
     ContextSteering steer;              // the launch chain's state of this context (kgpu_chain.h)
-    bool h2d_queued = false;            // a host-buffer path has queued this batch's H2D copy on `stream` (ctx_pick_stream orders the batch behind it if it switches streams)
+    bool batch_begun = false;           // the next batch's short stream is chosen (ctx_begin_batch: by its first ctx_h2d, or by ctx_pick_stream), until ctx_pick_stream has placed the batch
+    bool h2d_queued = false;            // ... and a host-buffer path has queued its H2D copy on `stream` (ctx_h2d alone sets it; ctx_pick_stream orders the batch behind it if it goes to a long stream)
     hipEvent_t switch_ev = nullptr;     // orders a batch behind what was queued on the stream the context used before
     hipEvent_t done_ev = nullptr;  // recorded behind the batch's last kernel: contexts may share a stream
     Control *d_ctl = nullptr;
@@ -301,9 +310,8 @@ constexpr size_t ARENA_INITIAL = 1ull << 28;  // 256 MiB; only the general (HBM-
 constexpr size_t ARENA_MAX = 1ull << 37;      // 128 GiB
 // the pooled contexts of a dictionary (one per call in flight)
 int pool_get(kgpu_dict *d, kgpu_ctx **c);
-void pool_put(kgpu_dict *d, kgpu_ctx *c);
-// A pooled context for the length of a scope: `rc` is pool_get's answer, and however the scope is left the context goes back without a copy flagged as
-// queued (a path that put its own copies on c->stream and waited for them left h2d_queued set).  put(): back before the scope ends.
+void pool_put(kgpu_dict *d, kgpu_ctx *c);   // (it goes back without a batch begun: a path that queued copies with ctx_h2d and waited for them itself, no tokenize batch behind them, left the flags set)
+// A pooled context for the length of a scope: `rc` is pool_get's answer, and however the scope is left the context goes back.  put(): back before the scope ends.
 struct PooledCtx {
     kgpu_dict *d = nullptr; kgpu_ctx *c = nullptr; int rc = KGPU_OK;
     PooledCtx() = default;                                  // (empty: get() leases later)
@@ -311,9 +319,9 @@ struct PooledCtx {
     PooledCtx(const PooledCtx &) = delete; PooledCtx &operator=(const PooledCtx &) = delete;
     ~PooledCtx() { put(); }
     int get(kgpu_dict *d_) { d = d_; return rc = pool_get(d, &c); }
-    void put() { if (c) { c->h2d_queued = false; pool_put(d, c); c = nullptr; } }
+    void put() { if (c) { pool_put(d, c); c = nullptr; } }
 };
-int ctx_h2d(kgpu_ctx *c, void *dst, const void *src, size_t bytes, const char *what);   // a batch's H2D copy on c->stream (sets h2d_queued)
+int ctx_h2d(kgpu_ctx *c, void *dst, const void *src, size_t bytes, const char *what);   // a batch's H2D copy: begins the batch (its stream is chosen), then the copy on c->stream
 int tokenize_device_impl(kgpu_ctx *c, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n, uint64_t total_bytes,
                          kgpu_token *d_tokens, kgpu_token8 *d_tokens8, uint32_t *d_first, uint8_t *status8, uint64_t *toff8, uint64_t token_capacity,
                          uint64_t *d_tok_offsets, uint8_t *d_status, const char *who);

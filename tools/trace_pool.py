@@ -3,7 +3,7 @@
 full-batch dispatches of the product kernel on their own -- the timed region of `bench.py --steps K` is its last 24 K full batches (what comes before is the
 prewarm and the warmup, which run without the HIP events the timed region's launches are bracketed by): the figure bench.py's avg_kernel_ms is to be held against.
 With N it also prints, per hardware queue (the trace's Queue_Id) and over that timed region (from the start of the N-th last full-batch dispatch to the
-trace's end): the share of the time a kernel of the queue was running, the gaps between consecutive kernels of a batch (the pool launch, then the scan and
+first 200 us in which no queue runs a kernel -- the host has left the loop that keeps eight batches in flight -- or the trace's end): the share of the time a kernel of the queue was running, the gaps between consecutive kernels of a batch (the pool launch, then the scan and
 the compaction or the one launch that does both) and from a batch's last kernel to the next batch's pool launch, and the averages of the kernels behind
 the pool launch -- the stream-side figures that the chip-side durations above do not show.
 usage: python tools/trace_pool.py <kernel_trace.csv> [N]"""
@@ -41,10 +41,20 @@ def avg(v):
 
 if len(sys.argv) > 2 and full:
     t0 = full[-min(n, len(full))][0]
-    print(f"per hardware queue over the timed region ({len(queues)} queues):")
+    # the region ends where no queue runs a kernel for IDLE_NS: the host has left the loop that keeps eight batches in flight (what bench.py --full runs behind
+    # it -- one context, which now visits every shared stream -- would otherwise stretch every queue's span)
+    IDLE_NS = 200_000
+    t1, busy_until = None, None
+    for b, e, _ in sorted(k for ks in queues.values() for k in ks if k[0] >= t0):
+        if busy_until is not None and b - busy_until >= IDLE_NS:
+            t1 = busy_until
+            break
+        busy_until = e if busy_until is None else max(busy_until, e)
+    t1 = busy_until if t1 is None else t1
+    print(f"per hardware queue over the timed region ({len(queues)} queues; {(t1 - t0) / 1e6:.2f} ms, to the first {IDLE_NS // 1000} us without a kernel on any queue):")
     every = defaultdict(list)
     for q, ks in sorted(queues.items()):
-        ks = sorted(k for k in ks if k[0] >= t0)
+        ks = sorted(k for k in ks if t0 <= k[0] < t1)
         if len(ks) < 2:
             continue
         span = (ks[-1][1] - ks[0][0]) / 1e3
