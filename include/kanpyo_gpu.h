@@ -707,6 +707,71 @@ int kgpu_normalize_device(kgpu_ctx *c, int form, const uint8_t *d_utf8, const ui
                           uint8_t *d_text, uint64_t text_capacity, uint64_t *d_text_offsets, uint8_t *d_status);
 int kgpu_ctx_sync_normalize(kgpu_ctx *c, uint64_t *n_bytes);
 
+/* ---- source alignment: token records of normalised text mapped back to the text the caller supplied (what highlighting, span labels, search
+ * offsets and de-identification need; NOT an output of the reference) ----
+ * The `_aligned` normalise calls give, beside the normalised lines, the EDIT RECORDS of every line: one per segment that changed.
+ *  1. A segment ("text normalisation", rule 3) gives an edit exactly when its normalised bytes differ from its source bytes.  A copied single inert
+ *     code point never gives one; a walked segment that comes out byte-identical (an already composed U+00E9, a precomposed Hangul syllable) gives
+ *     none either.  One edit is one segment: edits are never merged and never split.
+ *  2. A line's edits are ascending and disjoint, in the source and in the normalised line.  out_len >= 1: normalisation never deletes a character.
+ *  3. Between edits the two lines are byte-identical.
+ *  4. A line that is copied unchanged has no edits: KGPU_SENT_INVALID_UTF8, KGPU_SENT_NOT_NORMALIZED, and every line without a walked segment.
+ *  5. edit_offsets has n + 1 entries, counted in records: the exclusive scan of the lines' edit counts.  Line i's edits are
+ *     edits[edit_offsets[i] .. edit_offsets[i + 1]); their positions are relative to the line.
+ *  6. Capacity.  There are two exact sizes, text bytes and edit records (at most one per input byte).  KGPU_ERR_CAPACITY: BOTH are reported and
+ *     nothing was written to either buffer (the kgpu_normalize_text protocol: either may be the one that did not fit).
+ *  7. The device result equals kgpu_normalize_host_aligned on every line (the same segment code: "text normalisation", rule 9).  Positions are 32-bit.
+ * kgpu_source_spans_* map token records through the edits: span k belongs to token k (tok_offsets is shared), and holds kgpu_token's position,
+ * byte_len, start and end in SOURCE coordinates.  Every normalised character of a changed segment maps to the WHOLE source segment.  For a token t
+ * of a line with edits E, with out_end(e) = e.out_pos + e.out_len, and src_end, out_char_end, src_char_end likewise:
+ *  8. Start.  e = the last edit with e.out_pos <= t.position.  None: (t.position, t.start) as they are.  t.position < out_end(e): the token starts
+ *     inside the edit: (e.src_pos, e.src_char).  Otherwise (t.position - out_end(e) + src_end(e), t.start - out_char_end(e) + src_char_end(e)).
+ *  9. End, for byte_len > 0: q = t.position + t.byte_len, e = the last edit with e.out_pos < q.  None: (q, t.end) as they are.  q <= out_end(e): the
+ *     token ends inside the edit or at its end: (src_end(e), src_char_end(e)).  Otherwise shifted as in rule 8.
+ * 10. A record with byte_len == 0 (the EOS dummy): position and start by rule 8 -- for the EOS the source line's byte length and character count --,
+ *     byte_len = 0, end = start + (t.end - t.start): the EOS keeps its + 3.
+ * 11. Consequences.  U+3231 -> "(株)" tokenized as three tokens gives three spans that all cover U+3231.  Span starts and span ends are each
+ *     non-decreasing along a sentence.  Spans overlap only inside one edit.
+ * 12. Arbitrary records.  A record's fields are only compared with edit fields and added to them (32-bit, wrapping), never used as addresses: no
+ *     record, a bad one of kgpu_format_words_device's rule 6 included, causes an access outside the line's edits.  Every loop is bounded by the
+ *     line's edit count. */
+typedef struct kgpu_norm_edit {
+    uint32_t out_pos, src_pos;     /* byte offset of the segment in the normalised / the source line        */
+    uint32_t out_char, src_char;   /* char index of the segment's first code point in each                  */
+    uint16_t out_len, src_len;     /* bytes (a segment is <= 65 code points on either side: <= 260 bytes)   */
+    uint16_t out_chars, src_chars; /* code points                                                           */
+} kgpu_norm_edit;
+typedef struct kgpu_span { uint32_t position, byte_len, start, end; } kgpu_span; /* kgpu_token's four fields, in SOURCE coordinates */
+/* kgpu_normalize_host with the line's edits: host only, the definition of the device results.  edits may be NULL when edit_capacity is 0. */
+int kgpu_normalize_host_aligned(int form, const uint8_t *in, uint64_t len, uint8_t *out, uint64_t capacity, uint64_t *n_bytes, uint8_t *status,
+                                kgpu_norm_edit *edits, uint64_t edit_capacity, uint64_t *n_edits);
+/* kgpu_normalize_batch / kgpu_normalize_text with the edits; edit_offsets: n + 1 (offsets_capacity) entries. */
+int kgpu_normalize_batch_aligned(kgpu_dict *d, int form, const uint8_t *utf8, const uint64_t *offsets, uint64_t n,
+                                 uint8_t *text, uint64_t text_capacity, uint64_t *text_offsets, uint8_t *status, uint64_t *n_bytes,
+                                 kgpu_norm_edit *edits, uint64_t edit_capacity, uint64_t *edit_offsets, uint64_t *n_edits);
+int kgpu_normalize_text_aligned(kgpu_dict *d, int form, const uint8_t *text, uint64_t len, uint8_t *out_text, uint64_t text_capacity,
+                                uint64_t *text_offsets, uint64_t offsets_capacity, uint8_t *status, uint64_t *n_lines, uint64_t *n_bytes,
+                                kgpu_norm_edit *edits, uint64_t edit_capacity, uint64_t *edit_offsets, uint64_t *n_edits);
+/* kgpu_normalize_device with the edits, all in device memory: four launches whatever the batch holds.  d_edit_offsets: n + 1.
+ * kgpu_ctx_sync_normalize_aligned waits and reports both sizes: KGPU_ERR_CAPACITY (nothing written to d_text or d_edits) when either exceeds its
+ * capacity.  One render, count, encode, normalise or span mapping may be pending per context, whichever kind. */
+int kgpu_normalize_device_aligned(kgpu_ctx *c, int form, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n,
+                                  uint8_t *d_text, uint64_t text_capacity, uint64_t *d_text_offsets, uint8_t *d_status,
+                                  kgpu_norm_edit *d_edits, uint64_t edit_capacity, uint64_t *d_edit_offsets);
+int kgpu_ctx_sync_normalize_aligned(kgpu_ctx *c, uint64_t *n_bytes, uint64_t *n_edits);
+/* The spans of n sentences' records on the host: the definition of the device results.  spans: tok_offsets[n] - tok_offsets[0] records, span k of
+ * the call for record tok_offsets[0] + k. */
+void kgpu_source_spans_host(const kgpu_token *tokens, const uint64_t *tok_offsets, uint64_t n, const kgpu_norm_edit *edits,
+                            const uint64_t *edit_offsets, kgpu_span *spans);
+/* Device-resident: the spans of records a synced kgpu_tokenize_device batch (or anyone) left in HBM, one launch on c's stream; d_spans[k] belongs
+ * to d_tokens[k] (d_spans 16-byte aligned: KGPU_ERR_INVALID_ARG otherwise), and nothing is stored at or behind span_capacity.  The token count is
+ * read from d_tok_offsets on the device.  It takes the context's one pending render-kind slot; kgpu_ctx_sync_lines waits for it (0 bytes). */
+int kgpu_source_spans_device(kgpu_ctx *c, const kgpu_token *d_tokens, const uint64_t *d_tok_offsets, uint64_t n,
+                             const kgpu_norm_edit *d_edits, const uint64_t *d_edit_offsets, kgpu_span *d_spans, uint64_t span_capacity);
+/* Host arrays in, computed on the device, host arrays out: kgpu_source_spans_host's arguments. */
+int kgpu_source_spans_batch(kgpu_dict *d, const kgpu_token *tokens, const uint64_t *tok_offsets, uint64_t n, const kgpu_norm_edit *edits,
+                            const uint64_t *edit_offsets, kgpu_span *spans);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,10 @@ TOKEN_DTYPE = np.dtype(
     [("id", "<i4"), ("cls", "<u4"), ("position", "<u4"), ("start", "<u4"), ("end", "<u4"), ("byte_len", "<u4")]
 )
 TOKEN8_DTYPE = np.dtype([("id", "<i4"), ("packed", "<u4")])  # kgpu_token8: cls | chars << 2 | byte_len << 14
+# kgpu_norm_edit and kgpu_span (include/kanpyo_gpu.h, "source alignment")
+EDIT_DTYPE = np.dtype([("out_pos", "<u4"), ("src_pos", "<u4"), ("out_char", "<u4"), ("src_char", "<u4"),
+                       ("out_len", "<u2"), ("src_len", "<u2"), ("out_chars", "<u2"), ("src_chars", "<u2")])
+SPAN_DTYPE = np.dtype([("position", "<u4"), ("byte_len", "<u4"), ("start", "<u4"), ("end", "<u4")])
 
 
 def pinned_empty(shape, dtype=np.uint8) -> np.ndarray:

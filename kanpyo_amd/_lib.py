@@ -38,6 +38,8 @@ SYMBOLS = [
     "kgpu_vocab_create", "kgpu_vocab_destroy", "kgpu_vocab_get_info", "kgpu_encode_batch", "kgpu_encode_text", "kgpu_encode_device",
     "kgpu_vocab_create_wordpiece", "kgpu_vocab_get_wordpiece_info",
     "kgpu_normalize_unicode_version", "kgpu_normalize_host", "kgpu_normalize_batch", "kgpu_normalize_text", "kgpu_normalize_device", "kgpu_ctx_sync_normalize",
+    "kgpu_normalize_host_aligned", "kgpu_normalize_batch_aligned", "kgpu_normalize_text_aligned", "kgpu_normalize_device_aligned", "kgpu_ctx_sync_normalize_aligned",
+    "kgpu_source_spans_host", "kgpu_source_spans_device", "kgpu_source_spans_batch",
 ]
 KGPU_VOCAB_ADD_BOS, KGPU_VOCAB_ADD_EOS = 1, 2
 KGPU_COUNTS_DEFAULT_SLOTS, KGPU_COUNTS_DEFAULT_KEY_BYTES = 1 << 22, 256 << 20
@@ -125,6 +127,15 @@ class Token(C.Structure):  # kgpu_token
 
 class Token8(C.Structure):  # kgpu_token8
     _fields_ = [("id", C.c_int32), ("packed", C.c_uint32)]
+
+
+class NormEdit(C.Structure):  # kgpu_norm_edit: 24 bytes, one per segment of a line that normalisation changed
+    _fields_ = [("out_pos", C.c_uint32), ("src_pos", C.c_uint32), ("out_char", C.c_uint32), ("src_char", C.c_uint32),
+                ("out_len", C.c_uint16), ("src_len", C.c_uint16), ("out_chars", C.c_uint16), ("src_chars", C.c_uint16)]
+
+
+class Span(C.Structure):  # kgpu_span: kgpu_token's position, byte_len, start and end in source coordinates
+    _fields_ = [("position", C.c_uint32), ("byte_len", C.c_uint32), ("start", C.c_uint32), ("end", C.c_uint32)]
 
 
 class WordsSpec(C.Structure):  # kgpu_words_spec
@@ -262,6 +273,16 @@ def lib():
         L.kgpu_normalize_text.argtypes = [vp, C.c_int, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.kgpu_normalize_device.argtypes = [vp, C.c_int, vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp]
         L.kgpu_ctx_sync_normalize.argtypes = [vp, C.POINTER(C.c_uint64)]
+        edits_out = [vp, C.c_uint64, vp, C.POINTER(C.c_uint64)]   # edits, edit_capacity, edit_offsets, n_edits
+        L.kgpu_normalize_host_aligned.argtypes = L.kgpu_normalize_host.argtypes + [vp, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.kgpu_normalize_batch_aligned.argtypes = L.kgpu_normalize_batch.argtypes + edits_out
+        L.kgpu_normalize_text_aligned.argtypes = L.kgpu_normalize_text.argtypes + edits_out
+        L.kgpu_normalize_device_aligned.argtypes = L.kgpu_normalize_device.argtypes + [vp, C.c_uint64, vp]
+        L.kgpu_ctx_sync_normalize_aligned.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.kgpu_source_spans_host.argtypes = [vp, vp, C.c_uint64, vp, vp, vp]
+        L.kgpu_source_spans_host.restype = None
+        L.kgpu_source_spans_device.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, vp, C.c_uint64]
+        L.kgpu_source_spans_batch.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, vp]
         L.kgpu_debug_wordpiece_table.argtypes = [vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.c_uint64, C.c_uint64, C.POINTER(WordsSpec), vp, vp, C.c_uint64,
                                                  C.POINTER(VocabOpts), C.POINTER(WordpieceOpts), vp, vp, vp, vp, vp, vp, vp, C.POINTER(WordpieceInfo)]
         L.kgpu_debug_wordpiece_split.argtypes = [vp, vp, C.c_uint64, C.POINTER(WordpieceOpts), C.c_int32, vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.POINTER(C.c_uint64)]

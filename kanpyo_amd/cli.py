@@ -43,6 +43,12 @@ NORMALISED text: half-width katakana, full-width letters and digits, U+3231 and 
 normalised lines themselves, one output line per input line (kgpu_normalize_batch / kgpu_normalize_text).  Like every subcommand it needs a
 dictionary: the device work runs on a dictionary handle's context pool.  A line that is not UTF-8 ends the run with status 101 as `wakati` does; a
 line with an oversize segment prints unchanged, with a warning on stderr.
+
+`python -m kanpyo_amd align [INPUT] [-c DICT] [--form nfkc|nfc]`: NOT a subcommand of the reference either -- an inspection tool for the source
+alignment (include/kanpyo_gpu.h, "source alignment"): every line is normalised with its edit records, tokenized, and its token records are mapped back
+to the line as it was given (kgpu_normalize_batch_aligned, kgpu_tokenize_batch, kgpu_source_spans_batch: all on the device); one output line per token,
+`source_start\tsource_end\tsource surface\tnormalised surface` (character positions), and `EOS` behind each input line.  The text is formatted on
+the host -- which needs the lines there: stdin's blocks are split on the host whatever --split says.  A line that is not UTF-8 ends the run with status 101.
 """
 from __future__ import annotations
 
@@ -201,6 +207,37 @@ def normalize(args, stdin, stdout) -> int:
     return 0
 
 
+def align(args, stdin, stdout) -> int:
+    from .tokenizer import merge_status, split_lines
+
+    tok = _open(args)
+    form = args.form.upper()
+
+    def packed(utf8, offs):
+        text, ntoff, nstatus, edits, eoff = tok.normalize_packed_aligned(utf8, offs, form)
+        tokens, toff, status = tok.tokenize_packed(text, ntoff)
+        spans = tok.source_spans(tokens, toff, edits, eoff)
+        merge_status(status, nstatus)
+        src, norm, so, no, to = utf8.tobytes(), text.tobytes(), offs.tolist(), ntoff.tolist(), toff.tolist()
+        out = []
+        for i in range(len(status)):
+            rows = []
+            for k in range(to[i], to[i + 1] if status[i] != 1 else to[i]):
+                t, sp = tokens[k], spans[k]
+                if int(t["cls"]) == 0:   # the EOS dummy: the line below stands for it
+                    continue
+                s0, n0 = so[i] + int(sp["position"]), no[i] + int(t["position"])
+                rows.append(b"%d\t%d\t" % (int(sp["start"]), int(sp["end"])) + src[s0 : s0 + int(sp["byte_len"])] + b"\t" + norm[n0 : n0 + int(t["byte_len"])] + b"\n")
+            out.append(b"".join(rows) + b"EOS\n")
+        loff = np.zeros(len(out) + 1, dtype=np.uint64)
+        if out:
+            loff[1:] = np.cumsum([len(x) for x in out])
+        return np.frombuffer(b"".join(out), dtype=np.uint8), loff, status
+
+    return _print_lines(_results(args, stdin, packed, lambda block: packed(*split_lines(block))), stdout,
+                        "kanpyo_amd: failed to read from stdin: stream did not contain valid UTF-8")
+
+
 def wakati(args, stdin, stdout) -> int:
     w = _words(args, separator=os.fsencode(args.separator))
     return _print_lines(_results(args, stdin, w.render_packed, w.render_text), stdout,
@@ -352,7 +389,7 @@ def _text_command(sub, name: str, help: str, verb: str = None, first=(), own=(),
         flt.add_argument("--keep", type=_pos_list, default=[], help="Keep only tokens whose part of speech is one of POS[,POS...]")
     for flag, kw in own:
         p.add_argument(flag, **kw)
-    if name != "normalize":
+    if name not in ("normalize", "align"):
         p.add_argument("--normalize", choices=NORMALIZE_CHOICES, default="none", help=NORMALIZE_HELP)
     p.add_argument("--split", choices=["host", "device"], default="host",
                    help="Where stdin's blocks are split into lines and trimmed [default: host]")
@@ -363,7 +400,7 @@ def _text_command(sub, name: str, help: str, verb: str = None, first=(), own=(),
 
 
 def parse_args(argv=None):
-    """The reference's command line (src/bin/kanpyo.rs:14-49).  -> the namespace; .command is "tokenize" or "graphviz" -- or "wakati", "count", "encode" or "normalize", which are this package's own."""
+    """The reference's command line (src/bin/kanpyo.rs:14-49).  -> the namespace; .command is "tokenize" or "graphviz" -- or "wakati", "count", "encode", "normalize" or "align", which are this package's own."""
     p = argparse.ArgumentParser(prog="kanpyo_amd", description="Japanese Morphological Analyzer (kanpyo) on AMD Instinct GPUs")
     sub = p.add_subparsers(dest="command")
     t = _text_command(sub, "tokenize", "Tokenize input text")
@@ -375,6 +412,8 @@ def parse_args(argv=None):
     g.add_argument("--dpi", type=_dpi, default=48, help="DPI of output image [default: 48]")
     g.add_argument("--normalize", choices=NORMALIZE_CHOICES, default="none", help=NORMALIZE_HELP)
     _text_command(sub, "normalize", "NFC / NFKC of each input line (not in the reference)",
+                  own=[("--form", dict(choices=["nfkc", "nfc"], default="nfkc", help="The normalisation form [default: nfkc]"))])
+    _text_command(sub, "align", "Each token's place in the line as it was given, through NFC / NFKC (not in the reference)",
                   own=[("--form", dict(choices=["nfkc", "nfc"], default="nfkc", help="The normalisation form [default: nfkc]"))])
     _text_command(sub, "wakati", "One line of separated words per input line (not in the reference)", "Print",
                   own=[("--separator", dict(type=_separator, default=" ", help="The byte between words [default: a space]"))])
@@ -412,6 +451,8 @@ def main(argv=None) -> int:
             return encode(args, sys.stdin.buffer, sys.stdout.buffer)
         if args.command == "normalize":
             return normalize(args, sys.stdin.buffer, sys.stdout.buffer)
+        if args.command == "align":
+            return align(args, sys.stdin.buffer, sys.stdout.buffer)
         return tokenize(args, sys.stdin.buffer, sys.stdout.buffer)
     except _lib.KgpuError as e:
         print(f"kanpyo_amd: {e}", file=sys.stderr)

@@ -84,6 +84,7 @@ extern "C" void kgpu_ctx_destroy(kgpu_ctx *c) {
     c->lines_len.release(); c->lines_text.release(); c->lines_off.release(); c->lines_status.release();
     c->split_agg.release(); c->split_raw.release(); c->split_text.release(); c->split_off.release();
     c->gv_desc.release(); c->gv_len.release(); c->gv_text.release(); c->norm_text.release();
+    c->norm_edits.release(); c->norm_eoff.release(); c->span_out.release();
     if (c->switch_ev) (void)hipEventDestroy(c->switch_ev);
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
     c->arena.release(); c->ovf.release(); c->stat_slots.release(); c->stage.release(); c->tok_count.release();
@@ -498,6 +499,7 @@ int HostReport::arm() {
     if (!ev) HIPCHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     unsigned long long *h = (unsigned long long *)ctl.h;
     h[0] = 0; h[1] = 0;
+    two_sizes = false; cap1 = 0; word1 = 0;
     return KGPU_OK;
 }
 int HostReport::record(hipStream_t stream, uint64_t cap_) {
@@ -571,10 +573,19 @@ extern "C" int kgpu_ctx_sync_lines(kgpu_ctx *c, uint64_t *n_bytes) {
     if (!c) { set_error("kgpu_ctx_sync_lines: null ctx"); return KGPU_ERR_INVALID_ARG; }
     if (!c->lines_report.pending) { if (n_bytes) *n_bytes = 0; return KGPU_OK; }
     HIPCHECK(hipSetDevice(c->dict->device));
-    uint64_t h[2];   // [0] bytes, [1] a bad record
+    uint64_t h[2];   // [0] bytes, [1] a bad record -- or, behind an aligned normalise, its edits
     if (int rc = c->lines_report.wait(h)) return rc;
     const uint64_t need = h[0];
     if (n_bytes) *n_bytes = need;
+    if (c->lines_report.two_sizes) {
+        c->lines_report.word1 = h[1];
+        if (need > c->lines_report.cap || h[1] > c->lines_report.cap1) {
+            set_error("buffers too small: need %llu text bytes (capacity %llu) and %llu edit records (capacity %llu)", (unsigned long long)need,
+                      (unsigned long long)c->lines_report.cap, (unsigned long long)h[1], (unsigned long long)c->lines_report.cap1);
+            return KGPU_ERR_CAPACITY;
+        }
+        return KGPU_OK;
+    }
     if (h[1]) {
         set_error("kgpu_ctx_sync_lines: a token record names a class, morph id or surface outside the dictionary or its sentence");
         return KGPU_ERR_INVALID_ARG;

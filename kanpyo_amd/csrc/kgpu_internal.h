@@ -323,12 +323,31 @@ struct NormArgs {
     unsigned long long *host_ctl;      // device pointer of pinned, mapped words: [0] the output's bytes
 };
 int launch_normalize(const NormArgs &a, void *stream);
+// ... with the lines' edit records (include/kanpyo_gpu.h, "source alignment"): the ALIGN instantiations of the same two kernels and a second scan
+struct NormAlignArgs : NormArgs {
+    uint64_t *edit_len;                // device scratch, n + 1: each line's edits, then (k_lines_scan, in place) their offsets
+    uint64_t *edit_offsets;            // n + 1: that scan's mirror for the caller
+    kgpu_norm_edit *edits; uint64_t edit_cap;   // nothing is stored, text included, when sent_len[n] > text_cap or edit_len[n] > edit_cap
+};                                     // host_ctl: [1] the edits
+int launch_normalize_aligned(const NormAlignArgs &a, void *stream);
+// The source spans of a batch's records (kgpu_align.hip): spans[k] = tokens[k] mapped through its line's edits.  b: tokens, tok_offsets and n; offsets is
+// any array of n + 1 readable words (the text is not looked at).
+struct SpansArgs {
+    RecordsBatch b;
+    const kgpu_norm_edit *edits;       // line s's edits: edits[edit_offsets[s] .. edit_offsets[s + 1])
+    const uint64_t *edit_offsets;      // n + 1
+    kgpu_span *spans; uint64_t span_cap;   // no store at or behind span_cap
+};
+int launch_source_spans(const SpansArgs &a, void *stream);
 // kgpu_normalize_table.cpp (HIP-free, compiles alone): the tables in host memory, their sizes in bytes, and one line on the host -> its status; out_len is
 // the normalised length, and the bytes are in `out` when they fit `capacity` (the line itself where the status is not KGPU_SENT_OK)
 struct NormTableSizes { size_t stage1, stage2, dec, pool, comp_key, comp_val; };
 NormTables norm_host_tables();
 NormTableSizes norm_table_sizes();
 uint8_t norm_line_host(uint32_t form, const uint8_t *s, uint32_t len, uint8_t *out, uint64_t capacity, uint64_t &out_len);
+// ... and its edits: n_edits is their number, and text and edits are written when BOTH fit
+uint8_t norm_line_host_aligned(uint32_t form, const uint8_t *s, uint32_t len, uint8_t *out, uint64_t capacity, uint64_t &out_len, kgpu_norm_edit *edits,
+                               uint64_t edit_capacity, uint64_t &n_edits);
 
 int pool_workgroups_per_cu(uint32_t pool_bytes, uint32_t waves);
 int window_workgroups_per_cu(uint32_t lds_bytes);

@@ -16,7 +16,17 @@
 //                 destination are aligned alike.  Nothing is written when the total exceeds the capacity.
 // Walked segments are normalised three times in all (once for the length, twice in the write pass: its size, then its bytes) and their bytes are stored
 // one by one: the price of keeping nothing between the launches but a length per line.  Clean text never pays it.
+//
+// Both kernels are templates on ALIGN.  <false> is the normaliser above, statement for statement.  <true> (include/kanpyo_gpu.h, "source alignment") also
+// keeps what the write pass knows at the moment it stores a segment -- where it starts and ends in the source and in the output -- as one 24-byte edit
+// record per walked segment whose bytes changed (norm_segment_edit, kgpu_normalize_core.h: the host's statements):
+//   k_norm_len<true>    also counts each line's edits; a second k_lines_scan turns the counts into the caller's edit_offsets (four launches in all)
+//   k_norm_write<true>  three more wavefront prefix sums per pass beside the byte scan -- edits emitted, output code points, source code points (the
+//                       popcount of classify's lead mask) -- and their totals carried from pass to pass; a lane stores its edits with plain stores,
+//                       each bounded by the line's scanned edit count as the text stores are bounded by its length
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "kgpu_device.h"
 
@@ -127,21 +137,28 @@ __device__ __forceinline__ Line line_of(const NormArgs &a, uint64_t i) {
     return Line{p, hi - lo, (uint32_t)((uintptr_t)p & 15u)};
 }
 
+template <bool ALIGN> using ArgsOf = std::conditional_t<ALIGN, NormAlignArgs, NormArgs>;
+
 }  // namespace
 
-__global__ __launch_bounds__(64) void k_norm_len(NormArgs a) {
+template <bool ALIGN>
+__global__ __launch_bounds__(64) void k_norm_len(ArgsOf<ALIGN> a) {
     __shared__ uint32_t seg[NORM_BUF * 64];
     const uint32_t lane = threadIdx.x;
     LdsColumn buf{seg + lane};
     for (uint64_t i = blockIdx.x; i < a.n; i += gridDim.x) {
         const Line L = line_of(a, i);
         if (L.len >= (1ull << 32)) {   // (positions inside a line are 32-bit)
-            if (lane == 0) { a.sent_len[i] = L.len; a.mode[i] = MODE_COPY; a.status[i] = KGPU_SENT_NOT_NORMALIZED; }
+            if (lane == 0) {
+                a.sent_len[i] = L.len; a.mode[i] = MODE_COPY; a.status[i] = KGPU_SENT_NOT_NORMALIZED;
+                if constexpr (ALIGN) a.edit_len[i] = 0;
+            }
             continue;
         }
         const int64_t len = (int64_t)L.len;
         const uint32_t end = (uint32_t)L.len;
         uint64_t bytes = 0;
+        uint32_t edits = 0;   // (ALIGN) walked segments of this lane whose bytes change
         bool bad = false, over = false, walked = false;
         for (int64_t u = 0; u < (int64_t)L.mis + len; u += PASS) {
             const int64_t r0 = u + lane * 16 - (int64_t)L.mis;
@@ -153,7 +170,11 @@ __global__ __launch_bounds__(64) void k_norm_len(NormArgs a) {
                              uint32_t n, next;
                              const uint32_t r = norm_segment(a.t, a.form, L.p, (uint32_t)(r0 + k), end, buf, n, next);
                              walked = true;
-                             if (r == NORM_OVERSIZE) over = true; else bytes += r;
+                             if (r == NORM_OVERSIZE) over = true;
+                             else {
+                                 bytes += r;
+                                 if constexpr (ALIGN) edits += norm_segment_edit(L.p, (uint32_t)(r0 + k), next, buf, n, r).differs;
+                             }
                          });
         }
         const bool any_bad = __ballot(bad) != 0, any_over = __ballot(over) != 0, any_walked = __ballot(walked) != 0;
@@ -164,13 +185,23 @@ __global__ __launch_bounds__(64) void k_norm_len(NormArgs a) {
             a.mode[i] = (as_it_is || !any_walked) ? MODE_COPY : MODE_NORMALIZE;
             a.status[i] = any_bad ? KGPU_SENT_INVALID_UTF8 : any_over ? KGPU_SENT_NOT_NORMALIZED : KGPU_SENT_OK;
         }
+        if constexpr (ALIGN) {   // (a line that comes out as it went in has no edits)
+            const uint32_t line_edits = wave_sum(edits);
+            if (lane == 0) a.edit_len[i] = (any_bad || any_over) ? 0u : line_edits;
+        }
     }
 }
 
-__global__ __launch_bounds__(64) void k_norm_write(NormArgs a) {
+template <bool ALIGN>
+__global__ __launch_bounds__(64) void k_norm_write(ArgsOf<ALIGN> a) {
     __shared__ uint32_t seg[NORM_BUF * 64];
     const uint64_t *toff = a.sent_len;   // the scan's offsets in device memory
     if (toff[a.n] > a.text_cap) return;   // the host reports KGPU_ERR_CAPACITY with the size needed
+    const uint64_t *eoff = nullptr;       // (ALIGN) ... and the edits'
+    if constexpr (ALIGN) {
+        eoff = a.edit_len;
+        if (eoff[a.n] > a.edit_cap) return;   // either size may be the one that does not fit: nothing is written then
+    }
     const uint32_t lane = threadIdx.x;
     LdsColumn buf{seg + lane};
     for (uint64_t i = blockIdx.x; i < a.n; i += gridDim.x) {
@@ -200,33 +231,70 @@ __global__ __launch_bounds__(64) void k_norm_write(NormArgs a) {
         const int64_t len = (int64_t)L.len;
         const uint32_t end = (uint32_t)L.len;
         uint64_t base = 0;   // output bytes of the passes before this one
+        uint32_t ebase = 0, ocbase = 0, scbase = 0;   // (ALIGN) ... their edits, output code points and source code points
+        uint64_t line_edits = 0;
+        kgpu_norm_edit *ed = nullptr;
+        if constexpr (ALIGN) { line_edits = eoff[i + 1] - eoff[i]; ed = a.edits + eoff[i]; }
         for (int64_t u = 0; u < (int64_t)L.mis + len; u += PASS) {
             const int64_t r0 = u + lane * 16 - (int64_t)L.mis;
             const bool mine = !(r0 + 16 <= 0 || r0 >= len);
             Masks m{0, 0, 0, false};
-            uint32_t bytes = 0;
+            uint32_t bytes = 0, n_sc = 0;   // (ALIGN) this lane's source code points ...
+            uint64_t n_oc_ed = 0;           // ... and its output code points | edits << 32: ONE counter (two, each added to by one of the two
+                                            // lambdas, and the compiler merges the additions into one through a pointer: both counters in scratch)
             if (mine) {
                 m = classify(a.t, a.form, L.p, len, r0);
-                each_segment(m, len, r0, [&](uint32_t, uint32_t l) { bytes += l; },
+                each_segment(m, len, r0,
+                             [&](uint32_t, uint32_t l) {
+                                 bytes += l;
+                                 if constexpr (ALIGN) ++n_oc_ed;
+                             },
                              [&](uint32_t k) {
                                  uint32_t n, next;
                                  const uint32_t r = norm_segment(a.t, a.form, L.p, (uint32_t)(r0 + k), end, buf, n, next);
-                                 if (r != NORM_OVERSIZE) bytes += r;
+                                 if (r != NORM_OVERSIZE) {
+                                     bytes += r;
+                                     if constexpr (ALIGN) n_oc_ed += n | (uint64_t)norm_segment_edit(L.p, (uint32_t)(r0 + k), next, buf, n, r).differs << 32;
+                                 }
                              });
+                if constexpr (ALIGN) n_sc = (uint32_t)__popc(m.lead & 0xFFFFu);   // the code points that start in this unit
             }
             const uint32_t incl = wave_incl_scan(bytes, lane);   // (a lane has 16 segments of 65 code points at most: 32 bits hold a pass)
             uint64_t o = base + incl - bytes;
             base += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+            uint32_t e = 0, oc = 0, sc = 0;   // (ALIGN) the line's edits, output and source code points in front of this lane's unit
+            if constexpr (ALIGN) {
+                const uint32_t n_oc = (uint32_t)n_oc_ed, n_ed = (uint32_t)(n_oc_ed >> 32);
+                const uint32_t ie = wave_incl_scan(n_ed, lane), io = wave_incl_scan(n_oc, lane), is = wave_incl_scan(n_sc, lane);
+                e = ebase + ie - n_ed; oc = ocbase + io - n_oc; sc = scbase + is - n_sc;
+                ebase += (uint32_t)__builtin_amdgcn_readlane((int)ie, 63);
+                ocbase += (uint32_t)__builtin_amdgcn_readlane((int)io, 63);
+                scbase += (uint32_t)__builtin_amdgcn_readlane((int)is, 63);
+            }
             if (!mine) continue;
             // (every store is checked against the line's room: the lengths are the first launch's, and the input may have changed since)
             each_segment(m, len, r0,
                          [&](uint32_t k, uint32_t l) {
                              for (uint32_t j = 0; j < l; ++j, ++o)
                                  if (o < out_len) dst[o] = L.p[r0 + k + j];
+                             if constexpr (ALIGN) ++oc;
                          },
                          [&](uint32_t k) {
                              uint32_t n, next;
-                             if (norm_segment(a.t, a.form, L.p, (uint32_t)(r0 + k), end, buf, n, next) == NORM_OVERSIZE) return;
+                             const uint32_t r = norm_segment(a.t, a.form, L.p, (uint32_t)(r0 + k), end, buf, n, next);
+                             if (r == NORM_OVERSIZE) return;
+                             if constexpr (ALIGN) {   // (every store is checked against the line's scanned edit count, as the text's against its length)
+                                 const NormSegEdit d = norm_segment_edit(L.p, (uint32_t)(r0 + k), next, buf, n, r);
+                                 if (d.differs) {
+                                     if (e < line_edits) {   // kgpu_norm_edit as its six words (the 16-bit pairs put together in registers)
+                                         uint32_t *w = (uint32_t *)(ed + e);
+                                         w[0] = (uint32_t)o; w[1] = (uint32_t)(r0 + k); w[2] = oc; w[3] = sc + (uint32_t)__popc(m.lead & ((1u << k) - 1u));
+                                         w[4] = d.out_len | d.src_len << 16; w[5] = d.out_chars | d.src_chars << 16;
+                                     }
+                                     ++e;
+                                 }
+                                 oc += n;
+                             }
                              for (uint32_t q = 0; q < n; ++q) {
                                  const uint32_t c = buf.get(q) & 0x1FFFFFu, cl = norm_utf8_len(c);
                                  for (uint32_t j = 0; j < cl; ++j, ++o)
@@ -242,11 +310,24 @@ uint32_t normalize_blocks(uint64_t n) { return (uint32_t)(n < 8192 ? (n ? n : 1)
 int launch_normalize(const NormArgs &a, void *stream) {
     const hipStream_t st = (hipStream_t)stream;
     const uint32_t blocks = normalize_blocks(a.n);
-    if (a.n) hipLaunchKernelGGL(k_norm_len, dim3(blocks), dim3(64), 0, st, a);
+    if (a.n) hipLaunchKernelGGL(k_norm_len<false>, dim3(blocks), dim3(64), 0, st, a);
     RecordsBatch b{};
     b.n = a.n; b.sent_len = a.sent_len; b.text_offsets = a.text_offsets; b.host_ctl = a.host_ctl;
     launch_lines_scan(b, stream);
-    if (a.n) hipLaunchKernelGGL(k_norm_write, dim3(blocks), dim3(64), 0, st, a);
+    if (a.n) hipLaunchKernelGGL(k_norm_write<false>, dim3(blocks), dim3(64), 0, st, a);
+    return (int)hipGetLastError();
+}
+
+int launch_normalize_aligned(const NormAlignArgs &a, void *stream) {
+    const hipStream_t st = (hipStream_t)stream;
+    const uint32_t blocks = normalize_blocks(a.n);
+    if (a.n) hipLaunchKernelGGL(k_norm_len<true>, dim3(blocks), dim3(64), 0, st, a);
+    RecordsBatch b{}, e{};
+    b.n = a.n; b.sent_len = a.sent_len; b.text_offsets = a.text_offsets; b.host_ctl = a.host_ctl;
+    launch_lines_scan(b, stream);
+    e.n = a.n; e.sent_len = a.edit_len; e.text_offsets = a.edit_offsets; e.host_ctl = a.host_ctl + 1;   // the edits' total: the report's second word
+    launch_lines_scan(e, stream);
+    if (a.n) hipLaunchKernelGGL(k_norm_write<true>, dim3(blocks), dim3(64), 0, st, a);
     return (int)hipGetLastError();
 }
 

@@ -156,4 +156,21 @@ KGPU_NORM_HD uint32_t norm_segment(const NormTables &t, uint32_t form, const uin
     return bytes;
 }
 
+// The alignment of one walked segment (include/kanpyo_gpu.h, "source alignment"): a segment s[p .. next) that norm_segment left in buf[0 .. n) as `bytes`
+// bytes of UTF-8 gives an edit exactly when those bytes are not the source's.  Its four lengths: out_len = bytes and out_chars = n (norm_segment's), and
+// the source's, counted here (a code point is a byte that is no continuation byte: the line is UTF-8, or it has no edits).
+struct NormSegEdit { uint32_t out_len, src_len, out_chars, src_chars; bool differs; };
+template <class Buf>
+KGPU_NORM_HD NormSegEdit norm_segment_edit(const uint8_t *s, uint32_t p, uint32_t next, const Buf &buf, uint32_t n, uint32_t bytes) {
+    NormSegEdit e{bytes, next - p, n, 0, bytes != next - p};
+    for (uint32_t q = p; q < next; ++q) e.src_chars += (s[q] & 0xC0u) != 0x80u;
+    if (!e.differs)
+        for (uint32_t i = 0, q = p; i < n; ++i) {
+            const uint32_t c = buf.get(i) & 0x1FFFFFu, cl = norm_utf8_len(c);
+            for (uint32_t j = 0; j < cl; ++j, ++q)
+                if (norm_utf8_byte(c, j) != s[q]) e.differs = true;
+        }
+    return e;
+}
+
 }  // namespace kgpu

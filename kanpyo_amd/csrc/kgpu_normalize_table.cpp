@@ -5,6 +5,7 @@
 #include <cstring>
 #include <vector>
 
+#include "kgpu_align_core.h"
 #include "kgpu_internal.h"
 #include "kgpu_normalize_core.h"
 
@@ -66,16 +67,19 @@ struct HostBuf {
     void set(uint32_t i, uint32_t x) { v[i] = x; }
 };
 
-// One pass over a line: its normalised length, and with `out` the bytes.  -> the status; the length is the line's own when the status is not 0.
-uint8_t pass(const NormTables &t, uint32_t form, const uint8_t *s, uint32_t len, uint8_t *out, uint64_t &out_len) {
+// One pass over a line: its normalised length and the number of its edits ("source alignment"), and with `out` the bytes, with `edits` the records.
+// -> the status; the length is the line's own and there are no edits when the status is not 0.
+uint8_t pass(const NormTables &t, uint32_t form, const uint8_t *s, uint32_t len, uint8_t *out, uint64_t &out_len, kgpu_norm_edit *edits, uint64_t &n_edits) {
     out_len = len;
+    n_edits = 0;
     for (uint32_t p = 0; p < len;) {
         uint32_t cp;
         bool ok;
         p += norm_decode(s, p, len, cp, ok);
         if (!ok) return KGPU_SENT_INVALID_UTF8;
     }
-    uint64_t o = 0;
+    uint64_t o = 0, ne = 0;
+    uint32_t oc = 0, sc = 0;   // code points written, code points read
     HostBuf buf;
     for (uint32_t p = 0; p < len;) {
         uint32_t cp;
@@ -85,6 +89,7 @@ uint8_t pass(const NormTables &t, uint32_t form, const uint8_t *s, uint32_t len,
         if (norm_inert(w, form) && (p + l == len || norm_boundary_at(t, form, s, p + l, len))) {   // a segment of one inert code point: as it is
             if (out) std::memcpy(out + o, s + p, l);
             o += l; p += l;
+            ++oc; ++sc;
             continue;
         }
         uint32_t n, next;
@@ -95,21 +100,33 @@ uint8_t pass(const NormTables &t, uint32_t form, const uint8_t *s, uint32_t len,
                 const uint32_t c = buf.get(i) & 0x1FFFFFu, cl = norm_utf8_len(c);
                 for (uint32_t j = 0; j < cl; ++j) out[o + q++] = norm_utf8_byte(c, j);
             }
+        const NormSegEdit e = norm_segment_edit(s, p, next, buf, n, bytes);
+        if (e.differs) {
+            if (edits) edits[ne] = kgpu_norm_edit{(uint32_t)o, p, oc, sc, (uint16_t)e.out_len, (uint16_t)e.src_len, (uint16_t)e.out_chars, (uint16_t)e.src_chars};
+            ++ne;
+        }
+        oc += e.out_chars; sc += e.src_chars;
         o += bytes; p = next;
     }
     out_len = o;
+    n_edits = ne;
     return KGPU_SENT_OK;
 }
 
 }  // namespace
 
 uint8_t norm_line_host(uint32_t form, const uint8_t *s, uint32_t len, uint8_t *out, uint64_t capacity, uint64_t &out_len) {
+    uint64_t n_edits;
+    return norm_line_host_aligned(form, s, len, out, capacity, out_len, nullptr, ~0ull, n_edits);
+}
+uint8_t norm_line_host_aligned(uint32_t form, const uint8_t *s, uint32_t len, uint8_t *out, uint64_t capacity, uint64_t &out_len, kgpu_norm_edit *edits,
+                               uint64_t edit_capacity, uint64_t &n_edits) {
     const NormTables t = norm_host_tables();
-    const uint8_t st = pass(t, form, s, len, nullptr, out_len);
-    if (out_len > capacity) return st;
+    const uint8_t st = pass(t, form, s, len, nullptr, out_len, nullptr, n_edits);
+    if (out_len > capacity || n_edits > edit_capacity) return st;
     if (st != KGPU_SENT_OK) { if (len) std::memcpy(out, s, len); return st; }
-    uint64_t again;
-    (void)pass(t, form, s, len, out, again);
+    uint64_t again, edits_again;
+    (void)pass(t, form, s, len, out, again, edits, edits_again);
     return st;
 }
 
@@ -133,4 +150,32 @@ extern "C" int kgpu_normalize_host(int form, const uint8_t *in, uint64_t len, ui
         return KGPU_ERR_CAPACITY;
     }
     return KGPU_OK;
+}
+
+extern "C" int kgpu_normalize_host_aligned(int form, const uint8_t *in, uint64_t len, uint8_t *out, uint64_t capacity, uint64_t *n_bytes, uint8_t *status,
+                                           kgpu_norm_edit *edits, uint64_t edit_capacity, uint64_t *n_edits) {
+    if ((form != KGPU_NORMALIZE_NFC && form != KGPU_NORMALIZE_NFKC) || (len && !in) || (capacity && !out) || !n_bytes || (edit_capacity && !edits) || !n_edits) {
+        kgpu::set_error("kgpu_normalize_host_aligned: null argument or unknown form");
+        return KGPU_ERR_INVALID_ARG;
+    }
+    *n_bytes = 0; *n_edits = 0;
+    if (len >= (1ull << 32)) { kgpu::set_error("kgpu_normalize_host_aligned: a string of 4 GiB or more"); return KGPU_ERR_INVALID_ARG; }
+    uint64_t need = 0, need_edits = 0;
+    const uint8_t st = kgpu::norm_line_host_aligned((uint32_t)form, in, (uint32_t)len, out, capacity, need, edits, edit_capacity, need_edits);
+    *n_bytes = need; *n_edits = need_edits;
+    if (status) *status = st;
+    if (need > capacity || need_edits > edit_capacity) {
+        kgpu::set_error("kgpu_normalize_host_aligned: buffers too small: need %llu bytes (capacity %llu) and %llu edits (capacity %llu)", (unsigned long long)need,
+                        (unsigned long long)capacity, (unsigned long long)need_edits, (unsigned long long)edit_capacity);
+        return KGPU_ERR_CAPACITY;
+    }
+    return KGPU_OK;
+}
+
+extern "C" void kgpu_source_spans_host(const kgpu_token *tokens, const uint64_t *tok_offsets, uint64_t n, const kgpu_norm_edit *edits,
+                                       const uint64_t *edit_offsets, kgpu_span *spans) {
+    for (uint64_t s = 0; s < n; ++s) {
+        const uint64_t e0 = edit_offsets[s], e1 = edit_offsets[s + 1];
+        for (uint64_t k = tok_offsets[s]; k < tok_offsets[s + 1]; ++k) spans[k - tok_offsets[0]] = kgpu::align_span(tokens[k], edits + e0, e1 > e0 ? e1 - e0 : 0);
+    }
 }

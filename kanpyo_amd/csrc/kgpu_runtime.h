@@ -64,6 +64,10 @@ struct HostReport {
     hipEvent_t ev = nullptr;
     bool pending = false;
     uint64_t cap = 0;
+    // an aligned normalise (kgpu_normalize_host.cpp) publishes two SIZES: word [1] is its edit count, compared with cap1 as word [0] is with cap, and kept
+    // in word1 for kgpu_ctx_sync_normalize_aligned; arm() makes the report an ordinary one again
+    bool two_sizes = false;
+    uint64_t cap1 = 0, word1 = 0;
     int arm();                                   // before the launch: a previous use waited out (its words are about to be reset), block and event there, words zero
     unsigned long long *dev() const { return (unsigned long long *)ctl.d; }   // what the launch is given
     int record(hipStream_t stream, uint64_t cap);   // behind the launch
@@ -216,6 +220,8 @@ struct kgpu_ctx {
     HostReport split_report;
     // text normalisation (kgpu_normalize.hip): the host forms' normalised text on the device (their offsets and status bytes: out_off, out_status)
     DevBuf norm_text;
+    // ... and of the aligned forms and kgpu_source_spans_batch: edit records, their offsets, spans
+    DevBuf norm_edits, norm_eoff, span_out;
     // last enqueued batch (for the arena-overflow retry and for sync)
     BatchArgs last{};
     bool pending = false;
@@ -356,6 +362,9 @@ int enqueue_count(kgpu_ctx *c, kgpu_counts *k, const DeviceRecords &r, const cha
 // kgpu_normalize_host.cpp: the normalisation of a batch in device memory on c->stream behind whatever is queued there (waited for by kgpu_ctx_sync_normalize)
 int enqueue_normalize(kgpu_ctx *c, int form, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n, uint8_t *d_text, uint64_t text_capacity,
                       uint64_t *d_text_offsets, uint8_t *d_status, const char *who);
+// ... with the lines' edit records (waited for by kgpu_ctx_sync_normalize_aligned)
+int enqueue_normalize_aligned(kgpu_ctx *c, int form, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n, uint8_t *d_text, uint64_t text_capacity,
+                              uint64_t *d_text_offsets, uint8_t *d_status, kgpu_norm_edit *d_edits, uint64_t edit_capacity, uint64_t *d_edit_offsets, const char *who);
 
 int require_features(kgpu_dict *d, const char *who);   // KGPU_ERR_INVALID_ARG unless kgpu_dict_set_features has been called
 int ensure_label_pool(kgpu_dict *d);                   // kgpu_features.cpp: the graphviz label pool on the device (first call uploads it)

@@ -113,6 +113,36 @@ class DeviceContext(Handle):
             _lib.check(rc)
         return rc == _lib.KGPU_OK, int(n.value)
 
+    def normalize_aligned(self, d_utf8: int, d_offsets: int, n: int, d_text: int, text_capacity: int, d_text_offsets: int, d_status: int,
+                          d_edits: int, edit_capacity: int, d_edit_offsets: int, form="NFKC"):
+        """kgpu_normalize_device_aligned: normalize() that also leaves the lines' edit records (24-byte kgpu_norm_edit, at most one per input byte)
+        in d_edits and their uint64 offsets (n + 1) in d_edit_offsets.  sync_normalize_aligned waits for it."""
+        _lib.check(_lib.lib().kgpu_normalize_device_aligned(
+            self._h, _lib.normalize_form(form), C.c_void_p(d_utf8), C.c_void_p(d_offsets), n, C.c_void_p(d_text), text_capacity,
+            C.c_void_p(d_text_offsets), C.c_void_p(d_status), C.c_void_p(d_edits), edit_capacity, C.c_void_p(d_edit_offsets)))
+
+    def sync_normalize_aligned(self) -> tuple:
+        """Wait for the enqueued aligned normalisation -> (bytes, edits).  KgpuError with KGPU_ERR_CAPACITY: either capacity was too small
+        (nothing was written); try_sync_normalize_aligned returns the sizes instead."""
+        fits, nb, ne = self.try_sync_normalize_aligned()
+        if not fits:
+            _lib.check(_lib.KGPU_ERR_CAPACITY)
+        return nb, ne
+
+    def try_sync_normalize_aligned(self) -> tuple:
+        """-> (fits, bytes, edits): sync_normalize_aligned without the exception for a capacity that was too small."""
+        nb, ne = C.c_uint64(0), C.c_uint64(0)
+        rc = _lib.lib().kgpu_ctx_sync_normalize_aligned(self._h, C.byref(nb), C.byref(ne))
+        if rc != _lib.KGPU_ERR_CAPACITY:
+            _lib.check(rc)
+        return rc == _lib.KGPU_OK, int(nb.value), int(ne.value)
+
+    def source_spans(self, d_tokens: int, d_tok_offsets: int, n: int, d_edits: int, d_edit_offsets: int, d_spans: int, span_capacity: int):
+        """kgpu_source_spans_device: enqueue the source spans (16-byte kgpu_span, d_spans[k] for d_tokens[k]; d_spans 16-byte aligned) of records a
+        synced batch left in HBM, through the edit records an aligned normalisation left there.  sync_lines waits for it."""
+        _lib.check(_lib.lib().kgpu_source_spans_device(
+            self._h, C.c_void_p(d_tokens), C.c_void_p(d_tok_offsets), n, C.c_void_p(d_edits), C.c_void_p(d_edit_offsets), C.c_void_p(d_spans), span_capacity))
+
     def split_lines(self, d_in: int, len: int, d_out: int, d_offsets: int, offsets_capacity: int):
         """kgpu_split_lines_device: enqueue read_line + trim_end over a block in HBM -> the trimmed lines packed in d_out (len bytes suffice,
         no overlap with d_in) and their uint64 offsets in d_offsets."""

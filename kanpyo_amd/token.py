@@ -26,3 +26,17 @@ class Token:
 
     def length(self) -> int:  # src/token.rs:39-41
         return self.end - self.start
+
+
+@dataclass(frozen=True)
+class AlignedToken:
+    """A token of NORMALISED text with its place in the text the caller supplied (include/kanpyo_gpu.h, "source alignment"; not in the reference).
+    token: what tokenize_batch(normalize=...) returns; source_*: kgpu_span's position, byte_len, start and end; source_surface: the source bytes
+    the span covers ("EOS" for the dummy) -- every normalised character of a changed segment maps to the whole source segment."""
+
+    token: Token
+    source_position: int  # byte position in the source sentence
+    source_byte_len: int
+    source_start: int  # char position
+    source_end: int  # char position
+    source_surface: str

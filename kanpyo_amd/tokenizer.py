@@ -15,10 +15,10 @@ from typing import List, Sequence
 import numpy as np
 
 from . import _lib
-from ._calls import TOKEN8_DTYPE, TOKEN_DTYPE, Handle, batch_call, block_bytes, block_call, grown, pack_sentences, packed_input, pinned_empty, ptr, struct_dict  # noqa: F401
+from ._calls import EDIT_DTYPE, SPAN_DTYPE, TOKEN8_DTYPE, TOKEN_DTYPE, Handle, batch_call, block_bytes, block_call, grown, pack_sentences, packed_input, pinned_empty, ptr, struct_dict  # noqa: F401
 from ._probes import concurrent_callers, merge_bench, merge_shards  # noqa: F401  (they lived here once)
 from .dict import Dict
-from .token import Token, TokenClass
+from .token import AlignedToken, Token, TokenClass
 from .vocab import Vocab
 
 TEXT_UNITS = ("text[uint8]", "text_offsets")   # what the rendering calls name their out= arrays
@@ -49,6 +49,37 @@ def normalize_host(data, form="NFKC") -> bytes:
     got = C.c_uint64(0)
     _lib.check(_lib.lib().kgpu_normalize_host(_lib.normalize_form(form), ptr(src), src.size, out.ctypes.data, out.size, C.byref(got), None))
     return out[: got.value].tobytes()
+
+
+def normalize_host_aligned(data, form="NFKC") -> tuple:
+    """kgpu_normalize_host_aligned -> (bytes, edits[EDIT_DTYPE]): normalize_host, and one edit record per segment whose bytes changed (include/kanpyo_gpu.h,
+    "source alignment").  Needs no device."""
+    raw = data.encode("utf-8") if isinstance(data, str) else bytes(data)
+    src = np.frombuffer(raw, dtype=np.uint8)
+    out = np.empty(max(src.size * 11, 1), dtype=np.uint8)
+    edits = np.empty(max(src.size, 1), dtype=EDIT_DTYPE)   # (an edit covers a source byte at least)
+    got, ne = C.c_uint64(0), C.c_uint64(0)
+    _lib.check(_lib.lib().kgpu_normalize_host_aligned(_lib.normalize_form(form), ptr(src), src.size, out.ctypes.data, out.size, C.byref(got), None,
+                                                      edits.ctypes.data, edits.size, C.byref(ne)))
+    return out[: got.value].tobytes(), edits[: ne.value]
+
+
+def _span_inputs(tokens, tok_offsets, edits, edit_offsets):
+    tokens, edits = np.ascontiguousarray(tokens, dtype=TOKEN_DTYPE), np.ascontiguousarray(edits, dtype=EDIT_DTYPE)
+    toff, eoff = np.ascontiguousarray(tok_offsets, dtype=np.uint64), np.ascontiguousarray(edit_offsets, dtype=np.uint64)
+    if toff.size < 1 or eoff.size != toff.size:
+        raise ValueError("tok_offsets and edit_offsets need n+1 entries each")
+    if int(toff[-1]) > tokens.size or int(eoff[-1]) > edits.size:
+        raise ValueError("the offsets reach past the records")
+    return tokens, toff, edits, eoff, np.empty(max(int(toff[-1] - toff[0]), 1), dtype=SPAN_DTYPE)
+
+
+def source_spans_host(tokens, tok_offsets, edits, edit_offsets) -> np.ndarray:
+    """kgpu_source_spans_host -> spans[SPAN_DTYPE], one per record of tokens[tok_offsets[0]:tok_offsets[n]]: the records' position, byte_len, start and
+    end in the SOURCE text, through the lines' edits.  Needs no device; the definition of Tokenizer.source_spans."""
+    tokens, toff, edits, eoff, spans = _span_inputs(tokens, tok_offsets, edits, edit_offsets)
+    _lib.lib().kgpu_source_spans_host(ptr(tokens), toff.ctypes.data, toff.size - 1, ptr(edits), eoff.ctypes.data, spans.ctypes.data)
+    return spans[: int(toff[-1] - toff[0])]
 
 
 def _token_room(total: int, n: int) -> int:
@@ -108,6 +139,28 @@ class Tokenizer(Handle):
         has an oversize segment (status 4) comes back unchanged.  out=(text, text_offsets, status): caller-owned arrays to reuse."""
         return batch_call(partial(_lib.lib().kgpu_normalize_batch, self._h, _lib.normalize_form(form)), utf8, offsets, np.uint8, lambda total, n: total * 2 + 64,
                           TEXT_UNITS, out=out)
+
+    def normalize_packed_aligned(self, utf8: np.ndarray, offsets: np.ndarray, form="NFKC"):
+        """kgpu_normalize_batch_aligned -> (text, text_offsets, status, edits[EDIT_DTYPE], edit_offsets[uint64 n+1]): normalize_packed, and line i's edit
+        records edits[edit_offsets[i]:edit_offsets[i+1]] -- one per segment whose bytes changed, positions relative to the line -- which
+        source_spans maps token records back through."""
+        utf8, offsets, n, total = packed_input(utf8, offsets)
+        toff, eoff, status = np.empty(n + 1, dtype=np.uint64), np.empty(n + 1, dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint8)
+        got, ne = C.c_uint64(0), C.c_uint64(0)
+        caps = (total * 2 + 64, total // 4 + 64)
+        while caps is not None:   # (either size may be the one that did not fit: once more with both)
+            text, edits = np.empty(max(caps[0], 1), dtype=np.uint8), np.empty(max(caps[1], 1), dtype=EDIT_DTYPE)
+            rc = _lib.lib().kgpu_normalize_batch_aligned(self._h, _lib.normalize_form(form), ptr(utf8), offsets.ctypes.data, n, text.ctypes.data, caps[0], toff.ctypes.data,
+                                                         status.ctypes.data, C.byref(got), edits.ctypes.data, caps[1], eoff.ctypes.data, C.byref(ne))
+            caps = grown(rc, caps, (got.value, ne.value))
+        return text[: got.value], toff, status[:n], edits[: ne.value], eoff
+
+    def source_spans(self, tokens, tok_offsets, edits, edit_offsets) -> np.ndarray:
+        """kgpu_source_spans_batch -> spans[SPAN_DTYPE], one per record of tokens[tok_offsets[0]:tok_offsets[n]], computed on the device: what
+        source_spans_host gives."""
+        tokens, toff, edits, eoff, spans = _span_inputs(tokens, tok_offsets, edits, edit_offsets)
+        _lib.check(_lib.lib().kgpu_source_spans_batch(self._h, ptr(tokens), toff.ctypes.data, toff.size - 1, ptr(edits), eoff.ctypes.data, spans.ctypes.data))
+        return spans[: int(toff[-1] - toff[0])]
 
     def normalize_text(self, block, form="NFKC"):
         """kgpu_normalize_text: a raw block of input (bytes or uint8 array) -> (text, text_offsets, status) as
@@ -178,7 +231,7 @@ class Tokenizer(Handle):
     # ---- reference-shaped API --------------------------------------------------
     def tokenize_batch(self, sentences: Sequence[str], normalize=None) -> List[List[Token]]:
         """normalize="NFC" / "NFKC": the sentences are normalised on the device first; Token.position, start, end and surface then refer to
-        the NORMALISED sentence."""
+        the NORMALISED sentence -- tokenize_aligned / kgpu_source_spans_* map them back."""
         utf8, offs = pack_sentences(sentences)
         if normalize is not None:
             utf8, offs, _ = self.normalize_packed(utf8, offs, normalize)
@@ -194,6 +247,31 @@ class Tokenizer(Handle):
                 pos, bl = int(t["position"]), int(t["byte_len"])
                 surface = "EOS" if cls == TokenClass.Dummy else raw[pos : pos + bl].decode("utf-8")
                 row.append(Token(int(t["id"]), cls, pos, int(t["start"]), int(t["end"]), surface))
+            out.append(row)
+        return out
+
+    def tokenize_aligned(self, sentences: Sequence[str], normalize="NFKC") -> List[List[AlignedToken]]:
+        """tokenize_batch(sentences, normalize=...) with every token's place in the sentence AS IT WAS GIVEN: the sentences are normalised with their
+        edit records (normalize_packed_aligned), tokenized, and the records mapped back (source_spans) -- all three on the device.  AlignedToken.token
+        is tokenize_batch's Token (normalised coordinates and surface); source_position, source_byte_len, source_start, source_end and source_surface
+        refer to the source.  A sentence the normaliser left as it was maps to itself."""
+        utf8, offs = pack_sentences(sentences)
+        text, toff_text, _, edits, eoff = self.normalize_packed_aligned(utf8, offs, normalize)
+        tokens, toff, status = self.tokenize_packed(text, toff_text)
+        spans = self.source_spans(tokens, toff, edits, eoff)
+        out = []
+        for i in range(len(sentences)):
+            if status[i] == _lib.KGPU_SENT_INVALID_UTF8:
+                raise UnicodeDecodeError("utf-8", bytes(utf8[int(offs[i]) : int(offs[i + 1])]), 0, 1, "invalid UTF-8 sentence")
+            raw, src = text[int(toff_text[i]) : int(toff_text[i + 1])].tobytes(), utf8[int(offs[i]) : int(offs[i + 1])].tobytes()
+            row = []
+            for k in range(int(toff[i]), int(toff[i + 1])):
+                t, sp = tokens[k], spans[k]
+                cls = TokenClass(int(t["cls"]))
+                pos, bl, spos, sbl = int(t["position"]), int(t["byte_len"]), int(sp["position"]), int(sp["byte_len"])
+                dummy = cls == TokenClass.Dummy
+                token = Token(int(t["id"]), cls, pos, int(t["start"]), int(t["end"]), "EOS" if dummy else raw[pos : pos + bl].decode("utf-8"))
+                row.append(AlignedToken(token, spos, sbl, int(sp["start"]), int(sp["end"]), "EOS" if dummy else src[spos : spos + sbl].decode("utf-8")))
             out.append(row)
         return out
 
