@@ -117,4 +117,50 @@ def host_spans(tokens, tok_offsets, edits, edit_offsets) -> np.ndarray:
     return source_spans_host(tokens, tok_offsets, edits, edit_offsets)
 
 
+# ---- what the sweeps share (tests/test_gpu_normalize_sweep.py) -------------------------------------------------------------------------------------
+def expected_lines(lines, form: str, unchanged_has_none: bool = False):
+    """ref_edits over a list of lines -> (text, text_offsets, status, edits[EDIT_DTYPE], edit_offsets) as the aligned batch calls return them: status 1 is
+    the strict decoder's, status 4 the generator's, the text unicodedata's.  unchanged_has_none: a status-0 line that unicodedata leaves as it is has no
+    edits, without a walk over its segments (for batches of many thousands of lines)."""
+    outs, sts, eds = [], [], []
+    for ln in lines:
+        ln = bytes(ln)
+        if unchanged_has_none:
+            out, st = N.GEN.normalize_line(ln, form)
+            edits = ref_edits(ln, form)[2] if st == 0 and out != ln else []
+        else:
+            out, st, edits = ref_edits(ln, form)
+        outs.append(out)
+        sts.append(st)
+        eds.append(edits)
+    off, eoff = np.zeros(len(outs) + 1, dtype=np.uint64), np.zeros(len(outs) + 1, dtype=np.uint64)
+    if outs:
+        off[1:] = np.cumsum([len(o) for o in outs])
+        eoff[1:] = np.cumsum([len(e) for e in eds])
+    return np.frombuffer(b"".join(outs), dtype=np.uint8), off, np.array(sts, dtype=np.uint8), edit_array([e for es in eds for e in es]), eoff
+
+
+def edit_columns(**cols) -> np.ndarray:
+    """Edit records from one numpy column per field of EDIT_FIELDS."""
+    a = np.zeros(len(cols["out_pos"]), dtype=EDIT_DTYPE)
+    for f in EDIT_FIELDS:
+        a[f] = cols[f]
+    return a
+
+
+def differing_edit_lines(got, got_off, want, want_off) -> np.ndarray:
+    """The lines whose edit records differ between two batches of equally many lines (a line with another number of records differs)."""
+    g, w = got_off.astype(np.int64), want_off.astype(np.int64)
+    glen, wlen = np.diff(g), np.diff(w)
+    bad = glen != wlen
+    if g[-1] > len(got) or w[-1] > len(want) or (glen < 0).any():
+        return np.arange(len(wlen))
+    same = np.repeat(~bad, wlen)
+    idx = np.arange(int(w[0]), int(w[-1]))[same]
+    shift = np.repeat(g[:-1] - w[:-1], wlen)[same]
+    diff = idx[got[idx + shift] != want[idx]]
+    bad[np.searchsorted(w, diff, side="right") - 1] = True
+    return np.nonzero(bad)[0]
+
+
 __all__ = ["EDIT_DTYPE", "SPAN_DTYPE", "TOKEN_DTYPE"]

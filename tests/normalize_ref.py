@@ -1,6 +1,7 @@
 """What the normalisation tests share: the generator's own reference (tools/gen_normalize_tables.py: boundaries, segments and the rules of
 include/kanpyo_gpu.h over Python's unicodedata), the awkward pool the randomised strings are drawn from, and the library's host function."""
 import ctypes as C
+import functools
 import importlib.util
 import os
 import unicodedata
@@ -20,6 +21,7 @@ def generator():
 
 
 GEN = generator()
+GEN.boundary_before = functools.lru_cache(maxsize=1 << 16)(GEN.boundary_before)   # (a pure function of its arguments: long lines ask for the same few code points)
 
 # code points that decompose, compose, reorder or block: the fixture's cases as single code points, and their neighbours
 AWKWARD = [ord(c) for c in "aeAo ｶﾞﾊﾟｱＡ１㈱①　東がカガ"] + [
@@ -86,3 +88,70 @@ def host_lines(lines, form: str):
 def fixture_cases():
     g = load_golden("fixture_normalize.json")
     return g, [(c["name"], bytes.fromhex(c["input"]), {f: (bytes.fromhex(c[f.lower()]), c["status_" + f.lower()]) for f in FORMS}) for c in g["cases"]]
+
+
+# ---- what the sweeps share (tests/test_gpu_normalize_sweep.py) -------------------------------------------------------------------------------------
+def strict_utf8(data: bytes) -> bool:
+    """Does Python's strict decoder accept the line?"""
+    try:
+        data.decode("utf-8")
+        return True
+    except UnicodeDecodeError:
+        return False
+
+
+@functools.lru_cache(maxsize=None)
+def scalars() -> np.ndarray:
+    """All 1 112 064 scalar values, ascending."""
+    cps = np.arange(0x110000, dtype=np.uint32)
+    return cps[(cps < 0xD800) | (cps > 0xDFFF)]
+
+
+def utf8_len(cps: np.ndarray) -> np.ndarray:
+    """Bytes of each code point's encoding."""
+    return 1 + (cps >= 0x80).astype(np.int64) + (cps >= 0x800) + (cps >= 0x10000)
+
+
+def pack_strings(strs, line_bytes: np.ndarray):
+    """Lines that are Python strings, their byte lengths known -> (utf8, offsets) as pack_sentences gives them, with one encode for the batch."""
+    utf8 = np.frombuffer("".join(strs).encode("utf-8"), dtype=np.uint8)
+    offs = np.zeros(len(strs) + 1, dtype=np.uint64)
+    offs[1:] = np.cumsum(line_bytes)
+    assert int(offs[-1]) == utf8.size
+    return utf8, offs
+
+
+def normalize_strings(strs, form: str):
+    """unicodedata over every line -> (text[uint8], offsets[uint64 n + 1], bytes per line, code points per line, changed[bool]), without a bytes object per line."""
+    outs = [unicodedata.normalize(form, s) for s in strs]
+    joined = "".join(outs)
+    chars = np.fromiter(map(len, outs), dtype=np.int64, count=len(outs))
+    changed = np.fromiter((o != s for o, s in zip(outs, strs)), dtype=bool, count=len(outs))
+    per_cp = utf8_len(np.frombuffer(joined.encode("utf-32-le"), dtype="<u4"))
+    ends = np.concatenate([[0], np.cumsum(per_cp)])[np.cumsum(chars)]
+    offs = np.concatenate([[0], ends]).astype(np.uint64)
+    text = np.frombuffer(joined.encode("utf-8"), dtype=np.uint8)
+    assert int(offs[-1]) == text.size
+    return text, offs, np.diff(offs.astype(np.int64)), chars, changed
+
+
+@functools.lru_cache(maxsize=None)
+def boundary_table(form: str) -> np.ndarray:
+    """The generator's boundary_before for every scalar value, in the order of scalars()."""
+    cps = scalars()
+    return np.fromiter((GEN.boundary_before(int(c), form) for c in cps), dtype=bool, count=cps.size)
+
+
+def differing_lines(got_text, got_off, want_text, want_off) -> np.ndarray:
+    """The lines whose bytes differ between two packed batches of equally many lines (a line of another length differs)."""
+    g, w = got_off.astype(np.int64), want_off.astype(np.int64)
+    glen, wlen = np.diff(g), np.diff(w)
+    bad = glen != wlen
+    if g[-1] > got_text.size or w[-1] > want_text.size or (glen < 0).any():
+        return np.arange(len(wlen))   # (offsets that do not describe the text: nothing can be compared)
+    same = np.repeat(~bad, wlen)
+    idx = np.arange(int(w[0]), int(w[-1]))[same]
+    shift = np.repeat(g[:-1] - w[:-1], wlen)[same]
+    diff = idx[got_text[idx + shift] != want_text[idx]]
+    bad[np.searchsorted(w, diff, side="right") - 1] = True
+    return np.nonzero(bad)[0]
