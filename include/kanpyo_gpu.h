@@ -772,6 +772,40 @@ int kgpu_source_spans_device(kgpu_ctx *c, const kgpu_token *d_tokens, const uint
 int kgpu_source_spans_batch(kgpu_dict *d, const kgpu_token *tokens, const uint64_t *tok_offsets, uint64_t n, const kgpu_norm_edit *edits,
                             const uint64_t *edit_offsets, kgpu_span *spans);
 
+/* ---- ids with spans: a source span and a token index for every id (what token classification, extractive QA, highlighting and label projection
+ * need beside input_ids: `return_offsets_mapping` and `word_ids()` elsewhere; NOT an output of the reference) ----
+ * kgpu_encode_device_spans takes kgpu_encode_device's arguments, errors and protocol -- ragged or padded (rules 4 to 8 of "vocabulary ids", rules 5
+ * and 6 of "WordPiece ids"), the context's one pending render-kind slot, kgpu_ctx_sync_lines waits and reports id_offsets[n] -- and d_ids and
+ * d_id_offsets are exactly what kgpu_encode_device writes for the same input.  Element e of d_spans and of d_token_index belongs to element e of
+ * d_ids, in both layouts: ragged at id_offsets[s] + j, padded at s * width + j.  For a record t of sentence s:
+ *  1. Specials.  bos, eos (the eos in the last slot of a cut padded row included) and every pad slot get the span {0, 0, 0, 0} and the token index
+ *     -1.  They are never mapped through edits.
+ *  2. Token index.  An element that comes from record k of sentence s has the index k - tok_offsets[s]: its place among the sentence's records,
+ *     dropped tokens counted, so it indexes what kgpu_tokenize_device left.
+ *  3. Plain vocabulary.  The one id of a kept token carries the token's own position, byte_len, start and end.
+ *  4. WordPiece, surface words.  A surface word is one whose bytes are the text's (rule 2 of "vocabulary ids": for a known token the dictionary's
+ *     key; a row that falls back to the surface included).  Piece j of a split of two or more pieces covers the bytes [b_j, e_j) and the characters
+ *     [cb_j, ce_j) of the word, characters as in "WordPiece ids", rule 2; when the word is t.byte_len bytes long, its span is
+ *     {t.position + b_j, e_j - b_j, t.start + cb_j, t.start + ce_j}.  The pieces tile the word: b_0 = cb_0 = 0, b_(j+1) = e_j, cb_(j+1) = ce_j.
+ *  5. Everything else gets the token's whole span: a word that gives one id (listed whole, or unk_id by rule 4b or 4d of "WordPiece ids"), a word
+ *     that is a feature column, a surface word whose length differs from t.byte_len (a crafted record) -- every element, when several pieces come
+ *     from one such word.
+ *  6. Edits.  With d_edits and d_edit_offsets given (the edit records of kgpu_normalize_device_aligned for the same lines), every non-special span
+ *     is replaced by the span "source alignment" gives a record with its four fields (rules 8 to 10 there): three pieces that lie in one changed
+ *     segment all cover that whole source segment.  Both NULL: no mapping.  Only one of the two NULL: KGPU_ERR_INVALID_ARG.
+ *  7. Capacity.  On KGPU_ERR_CAPACITY nothing was written to any of the three arrays, and the count is exact.  In the padded form no slot at or
+ *     beyond n x width is ever touched.
+ *  8. Arbitrary records.  As in "source alignment", rule 12: a record's fields are compared and added (32-bit, wrapping), never used as addresses;
+ *     no record causes an access outside the sentence's text, its edits and the three output rows.
+ * d_spans: id_capacity entries, 16-byte aligned, required; d_token_index: id_capacity entries, 4-byte aligned, may be NULL.  KGPU_ERR_INVALID_ARG
+ * for a null or misaligned pointer, the unpaired edit pointers, and a context whose dictionary is not the handle's.  A WordPiece handle keeps, for
+ * this call, the byte and character end of every pooled piece of its rows: 8 bytes per kgpu_wordpiece_info.row_piece_ids, uploaded at creation. */
+int kgpu_encode_device_spans(kgpu_ctx *c, const kgpu_vocab *v, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n,
+                             const kgpu_token *d_tokens, const uint64_t *d_tok_offsets,
+                             const kgpu_norm_edit *d_edits, const uint64_t *d_edit_offsets, /* both NULL: no mapping */
+                             int32_t *d_ids, uint64_t id_capacity, uint64_t width, int32_t pad_id, uint64_t *d_id_offsets,
+                             kgpu_span *d_spans, int32_t *d_token_index);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,6 +40,7 @@ SYMBOLS = [
     "kgpu_normalize_unicode_version", "kgpu_normalize_host", "kgpu_normalize_batch", "kgpu_normalize_text", "kgpu_normalize_device", "kgpu_ctx_sync_normalize",
     "kgpu_normalize_host_aligned", "kgpu_normalize_batch_aligned", "kgpu_normalize_text_aligned", "kgpu_normalize_device_aligned", "kgpu_ctx_sync_normalize_aligned",
     "kgpu_source_spans_host", "kgpu_source_spans_device", "kgpu_source_spans_batch",
+    "kgpu_encode_device_spans",
 ]
 KGPU_VOCAB_ADD_BOS, KGPU_VOCAB_ADD_EOS = 1, 2
 KGPU_COUNTS_DEFAULT_SLOTS, KGPU_COUNTS_DEFAULT_KEY_BYTES = 1 << 22, 256 << 20
@@ -285,6 +286,8 @@ def lib():
         L.kgpu_source_spans_batch.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, vp]
         L.kgpu_debug_wordpiece_table.argtypes = [vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.c_uint64, C.c_uint64, C.POINTER(WordsSpec), vp, vp, C.c_uint64,
                                                  C.POINTER(VocabOpts), C.POINTER(WordpieceOpts), vp, vp, vp, vp, vp, vp, vp, C.POINTER(WordpieceInfo)]
+        L.kgpu_encode_device_spans.argtypes = [vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, C.c_int32, vp, vp, vp]
+        L.kgpu_debug_wordpiece_split_ends.argtypes = [vp, vp, C.c_uint64, C.POINTER(WordpieceOpts), C.c_int32, vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, C.POINTER(C.c_uint64)]
         L.kgpu_debug_wordpiece_split.argtypes = [vp, vp, C.c_uint64, C.POINTER(WordpieceOpts), C.c_int32, vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.POINTER(C.c_uint64)]
         L.kgpu_debug_counts_order.argtypes = [vp, vp, vp, C.c_uint64] + L.kgpu_counts_read.argtypes[1:]
         L.kgpu_debug_key_table.argtypes = [vp, C.c_size_t, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64), vp]

@@ -28,12 +28,16 @@ wakati's.  A line that is not UTF-8 ends the run with status 101, its 1-based li
 frequency table is worse than none; with --skip-invalid such lines are skipped, their numbers go to stderr and the status is 0.
 
 `python -m kanpyo_amd encode [INPUT] -c DICT --vocab FILE [--wordpiece [--prefix S] [--max-word-chars N]] [--field N | --base-form | --reading | --pronunciation] [--drop POS[,POS...] | --keep POS[,POS...]]
-[--unk WORD] [--bos WORD] [--eos WORD] [--split host|device] [--skip-invalid]`: NOT a subcommand of the reference either -- every input line becomes
+[--unk WORD] [--bos WORD] [--eos WORD] [--offsets] [--split host|device] [--skip-invalid]`: NOT a subcommand of the reference either -- every input line becomes
 one output line, the vocabulary ids of its words in decimal, separated by one space (kgpu_encode_batch / kgpu_encode_text; the decimal text is made
 on the host).  FILE has one word per line, line k (0-based) is id k: `count ... | cut -f2` makes one.  --unk (default "<unk>"), --bos and --eos name
 words that must be in the file (exit status 2 otherwise); a word outside the file gets --unk's id, --bos / --eos put theirs around every line's ids.
 The words and the filter are wakati's.  A line that is not UTF-8 is handled as `count` handles it: status 101, its line number on stderr and NOTHING
-on stdout; with --skip-invalid such a line prints its bos / eos only.
+on stdout; with --skip-invalid such a line prints its bos / eos only.  --offsets (include/kanpyo_gpu.h, "ids with spans") is an inspection tool: one
+output line PER ID, `id\tstart\tend\ttoken_index\ttext`, and `EOS` behind each input line -- start and end are character positions in the line as it was
+given (through --normalize's edit records), text is those characters, token_index the id's token among the line's records; bos and eos print
+`id\t0\t0\t-1\t`.  Ids, spans and indices are made on the device (Vocab.encode_tensor(return_spans=True)), the text is formatted on the host -- which needs
+the lines there: stdin's blocks are split on the host whatever --split says.
 
 `--normalize {none,nfc,nfkc}` (default none) on `tokenize`, `wakati`, `count`, `encode` and `graphviz`: the input -- INPUT, or stdin's lines with either
 --split -- is normalised on the device first (include/kanpyo_gpu.h, "text normalisation"), and what is printed are the surfaces and words of the
@@ -257,6 +261,8 @@ def count(args, stdin, stdout) -> int:
 
 
 def encode(args, stdin, stdout) -> int:
+    if args.offsets:   # (encode_tensor's tensors: torch ships its own HIP runtime, which has to be the process's one -- loaded before the library is)
+        import torch  # noqa: F401
     from .vocab import Vocab
 
     try:
@@ -282,6 +288,23 @@ def encode(args, stdin, stdout) -> int:
     v = Vocab.from_words(_words(args), listed, enc(args.unk), enc(args.bos), enc(args.eos), **wp)
     out = bytearray()   # (nothing is printed before the input is known to be valid, or --skip-invalid says not to care)
 
+    def with_offsets(utf8, offs):
+        src, so = utf8.tobytes(), offs.tolist()
+        ids, ioff, status, spans, tix = v.encode_tensor([src[so[i] : so[i + 1]] for i in range(len(so) - 1)], return_spans=True)
+        ids, sp, tix, o = ids.cpu().tolist(), spans.cpu().numpy().view(np.uint32).tolist(), tix.cpu().tolist(), ioff.cpu().tolist()
+        lines = []
+        for i in range(len(so) - 1):
+            rows = [b"%d\t%d\t%d\t%d\t" % (ids[e], sp[e][2], sp[e][3], tix[e]) + src[so[i] + sp[e][0] : so[i] + sp[e][0] + sp[e][1]] + b"\n" for e in range(o[i], o[i + 1])]
+            lines.append(b"".join(rows) + b"EOS\n")
+        return lines, status.cpu().numpy()
+
+    def listing(result):
+        out.extend(b"".join(result[0]))
+        if args.skip_invalid:
+            stdout.write(bytes(out))
+            stdout.flush()
+            out.clear()
+
     def decimal(result):
         ids, ioff, _ = result
         o, dec = ioff.tolist(), ids.tolist()
@@ -291,7 +314,13 @@ def encode(args, stdin, stdout) -> int:
             stdout.flush()
             out.clear()
 
-    if _each_checked(_results(args, stdin, v.encode_packed, v.encode_text), args.skip_invalid, decimal):
+    if args.offsets:
+        from .tokenizer import split_lines
+
+        results = _results(args, stdin, with_offsets, lambda block: with_offsets(*split_lines(block)))
+    else:
+        results = _results(args, stdin, v.encode_packed, v.encode_text)
+    if _each_checked(results, args.skip_invalid, listing if args.offsets else decimal):
         return PANIC_STATUS   # nothing has been printed
     stdout.write(bytes(out))
     stdout.flush()
@@ -427,7 +456,8 @@ def parse_args(argv=None):
                        ("--eos", dict(default=None, help="A word of the vocabulary whose id goes behind every line's ids")),
                        ("--wordpiece", dict(action="store_true", help="The vocabulary is a WordPiece list (a BERT vocab.txt): a word outside it is cut into its longest listed pieces")),
                        ("--prefix", dict(default=None, help="With --wordpiece: the continuation prefix, at most 8 bytes [default: ##]")),
-                       ("--max-word-chars", dict(type=_top, default=None, help="With --wordpiece: a longer word gets the --unk id [default: 100]"))],
+                       ("--max-word-chars", dict(type=_top, default=None, help="With --wordpiece: a longer word gets the --unk id [default: 100]")),
+                       ("--offsets", dict(action="store_true", help="One output line per id: id, start, end (characters of the line as given), token index, text; EOS behind each input line"))],
                   skip_invalid="A line that is not UTF-8 prints its bos / eos only instead of ending the run with status 101")
     args = p.parse_args(argv)
     if args.command is None:   # src/bin/kanpyo.rs:173: no subcommand == tokenize from stdin, default dictionary

@@ -12,7 +12,14 @@
 //                   consecutive dwords.  Lane 0 writes bos and eos.  Ragged: nothing at all is written when the total exceeds the capacity.
 //                   Padded: the sentence's base is s * width, the windows stop once the row is full, [min(L, width), width) is filled with pad_id
 //                   and a truncated row ends with eos_id when EOS was asked for.  All offsets are 64-bit.
-#include "kgpu_records_dev.h"
+//
+// k_encode_write is a template on SPANS.  <false> is the kernel above, statement for statement.  <true> (include/kanpyo_gpu.h, "ids with spans"; its
+// argument type derives from EncodeArgs, the length pass and the scan are the same launches) stores, wherever a lane stores an id, the element's source
+// span as ONE 16-byte store and its token index at the same slot under the same bound (kgpu_spans_dev.h): a kept token's own four fields, mapped through
+// the sentence's edits when the caller gave them; zeros and -1 for bos, eos and pad.
+#include <type_traits>
+
+#include "kgpu_spans_dev.h"
 
 namespace kgpu {
 
@@ -35,7 +42,8 @@ __global__ __launch_bounds__(256) void k_encode_len(EncodeArgs a) {
                    [&](uint64_t sum) { return sum + extra; });
 }
 
-__global__ __launch_bounds__(256) void k_encode_write(EncodeArgs a) {
+template <bool SPANS>
+__global__ __launch_bounds__(256) void k_encode_write(std::conditional_t<SPANS, EncodeSpanArgs, EncodeArgs> a) {
     const uint32_t lane = threadIdx.x & 63;
     const uint64_t *ioff = a.b.sent_len;    // the scan's offsets in device memory
     const bool padded = a.width != 0;
@@ -46,9 +54,14 @@ __global__ __launch_bounds__(256) void k_encode_write(EncodeArgs a) {
         int32_t *const row = a.ids + (padded ? s * a.width : ioff[s]);
         // the slots bos and the kept tokens may take: a truncated row keeps its last slot for eos (no two lanes ever store to one slot)
         const uint64_t lim = !padded ? L : (L > a.width ? a.width - (eos ? 1u : 0u) : L);
+        [[maybe_unused]] SpanRow sr{};   // (SPANS) the sentence's span and token-index rows, element for element beside `row`
+        if constexpr (SPANS) sr = span_row(a.o, s, padded ? s * a.width : ioff[s]);
         uint64_t at = 0;   // (wave-uniform) elements of the sequence placed so far
         if (bos) {
-            if (lane == 0 && lim > 0) row[0] = a.bos_id;
+            if (lane == 0 && lim > 0) {
+                row[0] = a.bos_id;
+                if constexpr (SPANS) span_special(sr, 0);
+            }
             at = 1;
         }
         for (uint64_t kw = k0; kw < k1 && at < lim; kw += 64) {   // (wave-uniform) padded: the windows stop once the row is full
@@ -58,17 +71,26 @@ __global__ __launch_bounds__(256) void k_encode_write(EncodeArgs a) {
             const unsigned long long keep = __ballot(wd.kept);
             if (keep == 0) continue;   // (wave-uniform)
             const uint64_t slot = at + (uint32_t)__popcll(keep & ((1ull << lane) - 1));
-            if (wd.kept && slot < lim)
+            if (wd.kept && slot < lim) {
                 row[slot] = row_determined(t, wd) ? a.row_id[feature_row(t.cls == KGPU_CLASS_KNOWN, a.b.n_morph, (uint32_t)t.id)] : vocab_lookup(a, text + wd.src, wd.len);
+                if constexpr (SPANS) span_store(sr, slot, t.position, t.byte_len, t.start, t.end, (int32_t)(kw + lane - k0));   // the record's place in its sentence
+            }
             at += (uint32_t)__popcll(keep);
         }
-        if (eos && lane == 0) row[(padded && L > a.width ? a.width : L) - 1] = a.eos_id;
+        if (eos && lane == 0) {
+            row[(padded && L > a.width ? a.width : L) - 1] = a.eos_id;
+            if constexpr (SPANS) span_special(sr, (padded && L > a.width ? a.width : L) - 1);
+        }
         if (padded)
-            for (uint64_t j = L + lane; j < a.width; j += 64) row[j] = a.pad_id;
+            for (uint64_t j = L + lane; j < a.width; j += 64) {
+                row[j] = a.pad_id;
+                if constexpr (SPANS) span_special(sr, j);
+            }
         return false;   // (the length pass has checked the records)
     });
 }
 
-int launch_encode(const EncodeArgs &a, void *stream) { return launch_render(k_encode_len, k_encode_write, a, stream); }
+int launch_encode(const EncodeArgs &a, void *stream) { return launch_render(k_encode_len, k_encode_write<false>, a, stream); }
+int launch_encode_spans(const EncodeSpanArgs &a, void *stream) { return launch_render(k_encode_len, k_encode_write<true>, a, stream); }
 
 }  // namespace kgpu

@@ -4,9 +4,9 @@
 // kgpu_vocab_create_wordpiece / kgpu_vocab_get_wordpiece_info (include/kanpyo_gpu.h, "WordPiece ids": the same handle with build_wordpiece_tables' tables,
 // kgpu_wordpiece_table.cpp; enqueue_encode sends it to kgpu_wordpiece.hip's launcher, a plain handle to kgpu_encode.hip's as before); the
 // encode's enqueue on a context (enqueue_encode: the renders' lines_report and lines_len, waited for by kgpu_ctx_sync_lines, which reports the ids),
-// kgpu_encode_device; the host calls kgpu_encode_batch and kgpu_encode_text -- the lines calls' wrappers (batch_lines, kgpu_host.cpp; text_lines,
+// kgpu_encode_device and kgpu_encode_device_spans (include/kanpyo_gpu.h, "ids with spans": the same enqueue with the write kernels' SPANS instantiation); the host calls kgpu_encode_batch and kgpu_encode_text -- the lines calls' wrappers (batch_lines, kgpu_host.cpp; text_lines,
 // kgpu_split_host.cpp) with the handle as the Renderer, the chunk's output counted in 4-byte units; and the host-only test hooks kgpu_debug_vocab_table,
-// kgpu_debug_wordpiece_table and kgpu_debug_wordpiece_split.
+// kgpu_debug_wordpiece_table, kgpu_debug_wordpiece_split and kgpu_debug_wordpiece_split_ends.
 //
 // AN ENCODE IS IDEMPOTENT, as a render is: queued behind a chunk's first pass it simply runs again when kgpu_ctx_sync had to rerun the chain
 // (LinesChunk::finish) -- unlike a count, which cannot be taken back.
@@ -40,7 +40,7 @@ bool any_known_surface_row(const std::vector<WordRow> &rows, size_t nk) {
 void free_vocab(kgpu_vocab *v) {
     (void)hipSetDevice(v->words->dict->device);
     (void)hipFree(v->d_row_id); (void)hipFree(v->d_slots); (void)hipFree(v->d_arena);
-    (void)hipFree(v->d_cont_slots); (void)hipFree(v->d_cont_arena); (void)hipFree(v->d_wp_rows); (void)hipFree(v->d_piece_ids);
+    (void)hipFree(v->d_cont_slots); (void)hipFree(v->d_cont_arena); (void)hipFree(v->d_wp_rows); (void)hipFree(v->d_piece_ids); (void)hipFree(v->d_piece_ends);
     kgpu_words *w = v->words;
     delete v;
     words_release(w);
@@ -102,7 +102,8 @@ int create_vocab(kgpu_words *w, const uint8_t *words, const uint64_t *word_offse
         v->wp.rows_whole = wt.rows_whole; v->wp.rows_split = wt.rows_split; v->wp.rows_unk = wt.rows_unk; v->wp.row_piece_ids = wt.piece_ids.size();
         v->wp.max_initial_bytes = wt.initial_max; v->wp.max_cont_bytes = wt.continuation_max();
         if (!wt.shared) ok = ok && upload(&v->d_cont_slots, ct.slots.data(), ct.slots.size() * sizeof(VocabSlot)) && upload(&v->d_cont_arena, ct.arena.data(), ct.arena.size());
-        ok = ok && upload(&v->d_wp_rows, wt.rows.data(), wt.rows.size() * sizeof(WordpieceRow)) && upload(&v->d_piece_ids, wt.piece_ids.data(), wt.piece_ids.size() * 4);
+        ok = ok && upload(&v->d_wp_rows, wt.rows.data(), wt.rows.size() * sizeof(WordpieceRow)) && upload(&v->d_piece_ids, wt.piece_ids.data(), wt.piece_ids.size() * 4) &&
+                 upload(&v->d_piece_ends, wt.piece_ends.data(), wt.piece_ends.size() * sizeof(PieceEnd));   // (8 bytes per pooled id, for the span calls)
     }
     if (!ok) {
         (void)hipGetLastError();
@@ -162,14 +163,14 @@ extern "C" int kgpu_vocab_get_info(const kgpu_vocab *v, kgpu_vocab_info *info) {
 
 // ---- the encode of a batch's records on a context --------------------------------------------------------------------------------------------
 int kgpu::enqueue_encode(kgpu_ctx *c, const kgpu_vocab *v, const DeviceRecords &r, int32_t *d_ids, uint64_t id_capacity, uint64_t width, int32_t pad_id,
-                         uint64_t *d_id_offsets, const char *who) {
+                         uint64_t *d_id_offsets, const char *who, const SpanOut *spans) {
     if (v->words->dict != c->dict) { set_error("%s: the context's dictionary is not the vocabulary handle's", who); return KGPU_ERR_INVALID_ARG; }
     if (width && (r.n > ~0ull / width || id_capacity < r.n * width)) {
         set_error("%s: id capacity %llu, the padded form needs n x width = %llu x %llu", who, (unsigned long long)id_capacity, (unsigned long long)r.n, (unsigned long long)width);
         return KGPU_ERR_INVALID_ARG;
     }
     if (v->wordpiece) {   // (the one place that tells the two kinds of handle apart: a plain handle runs exactly the kernels below)
-        WordpieceArgs a{};
+        WordpieceSpanArgs a{};   // (without spans only its WordpieceArgs part is used)
         if (int rc = records_batch(c, r, (size_t)r.n * 8 + 8, d_id_offsets, a.b)) return rc;
         a.w = word_table(v->words);
         a.rows = (const WordpieceRow *)v->d_wp_rows; a.piece_ids = (const int32_t *)v->d_piece_ids;
@@ -179,9 +180,11 @@ int kgpu::enqueue_encode(kgpu_ctx *c, const kgpu_vocab *v, const DeviceRecords &
         a.unk_id = v->unk_id; a.bos_id = v->bos_id; a.eos_id = v->eos_id; a.pad_id = pad_id;
         a.flags = v->flags;
         a.ids = d_ids; a.id_cap = id_capacity; a.width = width;
-        return records_launched(c, launch_wordpiece(a, c->stream), who, "wordpiece", width ? ~0ull : id_capacity);
+        if (!spans) return records_launched(c, launch_wordpiece(a, c->stream), who, "wordpiece", width ? ~0ull : id_capacity);
+        a.o = *spans; a.piece_ends = (const PieceEnd *)v->d_piece_ends;
+        return records_launched(c, launch_wordpiece_spans(a, c->stream), who, "wordpiece spans", width ? ~0ull : id_capacity);
     }
-    EncodeArgs a{};
+    EncodeSpanArgs a{};
     if (int rc = records_batch(c, r, (size_t)r.n * 8 + 8, d_id_offsets, a.b)) return rc;
     a.w = word_table(v->words);
     a.row_id = (const int32_t *)v->d_row_id;
@@ -190,7 +193,9 @@ int kgpu::enqueue_encode(kgpu_ctx *c, const kgpu_vocab *v, const DeviceRecords &
     a.unk_id = v->unk_id; a.bos_id = v->bos_id; a.eos_id = v->eos_id; a.pad_id = pad_id;
     a.flags = v->flags;
     a.ids = d_ids; a.id_cap = id_capacity; a.width = width;
-    return records_launched(c, launch_encode(a, c->stream), who, "encode", width ? ~0ull : id_capacity);   // (the padded form never reports KGPU_ERR_CAPACITY)
+    if (!spans) return records_launched(c, launch_encode(a, c->stream), who, "encode", width ? ~0ull : id_capacity);   // (the padded form never reports KGPU_ERR_CAPACITY)
+    a.o = *spans;
+    return records_launched(c, launch_encode_spans(a, c->stream), who, "encode spans", width ? ~0ull : id_capacity);
 }
 
 extern "C" int kgpu_encode_device(kgpu_ctx *c, const kgpu_vocab *v, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n,
@@ -205,6 +210,25 @@ extern "C" int kgpu_encode_device(kgpu_ctx *c, const kgpu_vocab *v, const uint8_
     if (v->words->dict != c->dict) { set_error("%s: the context's dictionary is not the vocabulary handle's", who); return KGPU_ERR_INVALID_ARG; }
     if (int rc = begin_records_call(c, who)) return rc;
     return enqueue_encode(c, v, DeviceRecords{d_utf8, d_offsets, n, d_tokens, d_tok_offsets, nullptr, nullptr}, d_ids, id_capacity, width, pad_id, d_id_offsets, who);
+}
+
+extern "C" int kgpu_encode_device_spans(kgpu_ctx *c, const kgpu_vocab *v, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n,
+                                        const kgpu_token *d_tokens, const uint64_t *d_tok_offsets, const kgpu_norm_edit *d_edits, const uint64_t *d_edit_offsets,
+                                        int32_t *d_ids, uint64_t id_capacity, uint64_t width, int32_t pad_id, uint64_t *d_id_offsets,
+                                        kgpu_span *d_spans, int32_t *d_token_index) {
+    const char *who = "kgpu_encode_device_spans";
+    if (!c || !v || !d_offsets || !d_tok_offsets || !d_id_offsets || !d_spans || (n && (!d_utf8 || !d_tokens)) || (id_capacity && !d_ids)) {
+        set_error("%s: null argument", who);
+        return KGPU_ERR_INVALID_ARG;
+    }
+    if ((d_edits == nullptr) != (d_edit_offsets == nullptr)) { set_error("%s: d_edits and d_edit_offsets are given together, or both NULL", who); return KGPU_ERR_INVALID_ARG; }
+    if ((uintptr_t)d_ids & 3u) { set_error("%s: d_ids is not 4-byte aligned", who); return KGPU_ERR_INVALID_ARG; }
+    if ((uintptr_t)d_spans & 15u) { set_error("%s: d_spans is not 16-byte aligned", who); return KGPU_ERR_INVALID_ARG; }
+    if ((uintptr_t)d_token_index & 3u) { set_error("%s: d_token_index is not 4-byte aligned", who); return KGPU_ERR_INVALID_ARG; }
+    if (v->words->dict != c->dict) { set_error("%s: the context's dictionary is not the vocabulary handle's", who); return KGPU_ERR_INVALID_ARG; }
+    if (int rc = begin_records_call(c, who)) return rc;
+    const SpanOut o{d_spans, d_token_index, d_edits, d_edit_offsets};
+    return enqueue_encode(c, v, DeviceRecords{d_utf8, d_offsets, n, d_tokens, d_tok_offsets, nullptr, nullptr}, d_ids, id_capacity, width, pad_id, d_id_offsets, who, &o);
 }
 
 // ---- the host calls: the lines calls' bodies with the chunks' renderer set to the encode --------------------------------------------------------
@@ -322,13 +346,10 @@ extern "C" int kgpu_debug_wordpiece_table(const uint8_t *known, size_t known_len
     return KGPU_OK;
 }
 
-// Test hook (host only, not in the header; kanpyo_amd.Vocab.split_words): wordpiece_split over packed words (word i is in[in_offsets[i] .. in_offsets[i + 1])) with
-// the tables of the list alone -> ragged ids: out_offsets has n + 1 entries, *n_ids is the exact count; KGPU_ERR_CAPACITY (nothing written to ids) when
-// ids_cap is below it.
-extern "C" int kgpu_debug_wordpiece_split(const uint8_t *words, const uint64_t *word_offsets, uint64_t n_words, const kgpu_wordpiece_opts *wp, int32_t unk_id,
-                                          const uint8_t *in, const uint64_t *in_offsets, uint64_t n, int32_t *ids, uint64_t ids_cap, uint64_t *out_offsets,
-                                          uint64_t *n_ids) {
-    const char *who = "kgpu_debug_wordpiece_split";
+// The body of the two split hooks below (ends null: the ids alone).
+namespace {
+int debug_split(const char *who, const uint8_t *words, const uint64_t *word_offsets, uint64_t n_words, const kgpu_wordpiece_opts *wp, int32_t unk_id, const uint8_t *in,
+                const uint64_t *in_offsets, uint64_t n, int32_t *ids, uint32_t *ends, uint64_t ids_cap, uint64_t *out_offsets, uint64_t *n_ids) {
     int rc;
     WpSpec ws;
     if (!n_ids || !out_offsets || (n && !in_offsets)) { set_error("%s: null argument", who); return KGPU_ERR_INVALID_ARG; }
@@ -340,14 +361,37 @@ extern "C" int kgpu_debug_wordpiece_split(const uint8_t *words, const uint64_t *
         return rc;
     }
     std::vector<int32_t> all;
+    std::vector<PieceEnd> all_ends;
     out_offsets[0] = 0;
     for (uint64_t i = 0; i < n; ++i) {
         if (in_offsets[i + 1] < in_offsets[i] || in_offsets[i + 1] - in_offsets[i] >= (1ull << 32)) { set_error("%s: bad offsets at word %llu", who, (unsigned long long)i); return KGPU_ERR_INVALID_ARG; }
-        wordpiece_split(t, in + in_offsets[i], in_offsets[i + 1] - in_offsets[i], ws.max_chars, unk_id, all);
+        wordpiece_split(t, in + in_offsets[i], in_offsets[i + 1] - in_offsets[i], ws.max_chars, unk_id, all, ends ? &all_ends : nullptr);
         out_offsets[i + 1] = all.size();
     }
     *n_ids = all.size();
     if (all.size() > ids_cap) { set_error("%s: id buffer too small: need %zu, capacity %llu", who, all.size(), (unsigned long long)ids_cap); return KGPU_ERR_CAPACITY; }
     if (!all.empty()) std::memcpy(ids, all.data(), all.size() * 4);
+    if (ends && !all_ends.empty()) std::memcpy(ends, all_ends.data(), all_ends.size() * sizeof(PieceEnd));
     return KGPU_OK;
+}
+}  // namespace
+
+// Test hook (host only, not in the header; kanpyo_amd.Vocab.split_words): wordpiece_split over packed words (word i is in[in_offsets[i] .. in_offsets[i + 1])) with
+// the tables of the list alone -> ragged ids: out_offsets has n + 1 entries, *n_ids is the exact count; KGPU_ERR_CAPACITY (nothing written to ids) when
+// ids_cap is below it.
+extern "C" int kgpu_debug_wordpiece_split(const uint8_t *words, const uint64_t *word_offsets, uint64_t n_words, const kgpu_wordpiece_opts *wp, int32_t unk_id,
+                                          const uint8_t *in, const uint64_t *in_offsets, uint64_t n, int32_t *ids, uint64_t ids_cap, uint64_t *out_offsets,
+                                          uint64_t *n_ids) {
+    return debug_split("kgpu_debug_wordpiece_split", words, word_offsets, n_words, wp, unk_id, in, in_offsets, n, ids, nullptr, ids_cap, out_offsets, n_ids);
+}
+
+// Test hook (host only, not in the header; kanpyo_amd.vocab.split_words_ends): kgpu_debug_wordpiece_split that also gives, per id, where its piece ENDS inside
+// its word -- ends: 2 x ids_cap uint32, {byte end, character end} per id, what the span calls' pool holds for a row-determined word (include/kanpyo_gpu.h,
+// "ids with spans").  The one id of a word that gives unk_id ends where the word ends.  ends is required.
+extern "C" int kgpu_debug_wordpiece_split_ends(const uint8_t *words, const uint64_t *word_offsets, uint64_t n_words, const kgpu_wordpiece_opts *wp, int32_t unk_id,
+                                               const uint8_t *in, const uint64_t *in_offsets, uint64_t n, int32_t *ids, uint32_t *ends, uint64_t ids_cap,
+                                               uint64_t *out_offsets, uint64_t *n_ids) {
+    const char *who = "kgpu_debug_wordpiece_split_ends";
+    if (!ends) { set_error("%s: null argument", who); return KGPU_ERR_INVALID_ARG; }
+    return debug_split(who, words, word_offsets, n_words, wp, unk_id, in, in_offsets, n, ids, ends, ids_cap, out_offsets, n_ids);
 }

@@ -221,6 +221,16 @@ struct EncodeArgs {
     uint64_t width;                  // 0: ragged; else the padded form's row length
 };
 int launch_encode(const EncodeArgs &a, void *stream);
+// ... with a source span and a token index per id (include/kanpyo_gpu.h, "ids with spans"): the SPANS instantiation of the write kernel.  Element e of
+// spans / token_index belongs to element e of ids, in both layouts; every store is bounded as the id's store is.
+struct SpanOut {
+    kgpu_span *spans;                // id_cap entries, 16-byte aligned
+    int32_t *token_index;            // id_cap entries, or null
+    const kgpu_norm_edit *edits;     // null: the spans stay in the coordinates of the records; else line s's edits are edits[edit_offsets[s] .. edit_offsets[s + 1])
+    const uint64_t *edit_offsets;    // n + 1
+};
+struct EncodeSpanArgs : EncodeArgs { SpanOut o; };
+int launch_encode_spans(const EncodeSpanArgs &a, void *stream);
 // kgpu_vocab_table.cpp (HIP-free, compiles alone): a vocabulary handle's two tables from the word table's rows, the dictionary's id -> key table and the list.
 struct VocabTables {
     std::vector<int32_t> row_id;
@@ -259,6 +269,11 @@ struct WordpieceArgs {
     uint64_t width;                  // 0: ragged; else the padded form's row length
 };
 int launch_wordpiece(const WordpieceArgs &a, void *stream);
+// ... with spans (SpanOut above).  piece_ends is parallel to piece_ids: the byte end and the character end of pooled piece k inside its row's word, filled for
+// the rows whose word is the surface (the dictionary's key) and zero for a feature column's, which never need them.
+struct PieceEnd { uint32_t byte_end, char_end; };
+struct WordpieceSpanArgs : WordpieceArgs { SpanOut o; const PieceEnd *piece_ends; };
+int launch_wordpiece_spans(const WordpieceSpanArgs &a, void *stream);
 // kgpu_wordpiece_table.cpp (HIP-free; compiles with kgpu_vocab_table.cpp alone): the tables of a WordPiece handle.
 constexpr uint32_t WORDPIECE_MAX_CHARS = 1024, WORDPIECE_DEFAULT_CHARS = 100, WORDPIECE_MAX_PREFIX = 8;
 struct WordpieceTables {
@@ -268,13 +283,16 @@ struct WordpieceTables {
     uint32_t initial_max = 0, cont_max = 0;   // the longest entry of each table in bytes
     std::vector<WordpieceRow> rows;
     std::vector<int32_t> piece_ids;
+    std::vector<PieceEnd> piece_ends;   // parallel to piece_ids (WordpieceSpanArgs)
     uint64_t cont_words = 0, rows_whole = 0, rows_split = 0, rows_unk = 0;
     const VocabTables &continuation() const { return shared ? initial : cont; }
     uint32_t continuation_max() const { return shared ? initial_max : cont_max; }
 };
 enum WordpieceOutcome { WP_EMPTY = 0, WP_WHOLE = 1, WP_SPLIT = 2, WP_UNK = 3 };
-// The split of include/kanpyo_gpu.h, "WordPiece ids", on the host: the pieces of the len bytes at p are APPENDED to out.
-WordpieceOutcome wordpiece_split(const WordpieceTables &t, const uint8_t *p, uint64_t len, uint32_t max_chars, int32_t unk_id, std::vector<int32_t> &out);
+// The split of include/kanpyo_gpu.h, "WordPiece ids", on the host: the pieces of the len bytes at p are APPENDED to out -- and to ends (may be null), per
+// piece, where it ends in the word in bytes and in characters; the one id of a word that gives unk_id ends where the word ends.
+WordpieceOutcome wordpiece_split(const WordpieceTables &t, const uint8_t *p, uint64_t len, uint32_t max_chars, int32_t unk_id, std::vector<int32_t> &out,
+                                 std::vector<PieceEnd> *ends = nullptr);
 int build_wordpiece_tables(const WordRow *rows, size_t n_rows, size_t n_known, const uint8_t *names, const uint8_t *key_bytes, const uint64_t *key_off,
                            const uint8_t *words, const uint64_t *word_offsets, uint64_t n_words, int32_t unk_id, const uint8_t *prefix, uint32_t prefix_len,
                            uint32_t max_chars, WordpieceTables &out, std::string &err);

@@ -139,11 +139,12 @@ __device__ __forceinline__ void write_units(uint8_t *abase, uint64_t mis, uint64
 }
 
 // A render's three launches on a stream.  -> hipGetLastError()
-template <class Args>
-int launch_render(void (*len)(Args), void (*write)(Args), const Args &a, void *stream) {
+// (A write kernel whose arguments DERIVE from the length kernel's -- the span instantiations of the ids -- gives the length kernel its base part.)
+template <class LenArgs, class Args>
+int launch_render(void (*len)(LenArgs), void (*write)(Args), const Args &a, void *stream) {
     const hipStream_t st = (hipStream_t)stream;
     const uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>((a.b.n + RENDER_WPB - 1) / RENDER_WPB, 8192));
-    hipLaunchKernelGGL(len, dim3((unsigned)blocks), dim3(64 * RENDER_WPB), 0, st, a);
+    hipLaunchKernelGGL(len, dim3((unsigned)blocks), dim3(64 * RENDER_WPB), 0, st, static_cast<const LenArgs &>(a));
     launch_lines_scan(a.b, stream);
     hipLaunchKernelGGL(write, dim3((unsigned)blocks), dim3(64 * RENDER_WPB), 0, st, a);
     return (int)hipGetLastError();

@@ -171,7 +171,7 @@ struct kgpu_vocab {
     // the 8-byte row entries and the pool behind them, uploaded once; d_row_id stays null -- the plain kernels never see such a handle
     bool wordpiece = false, cont_shared = false;
     uint32_t max_word_chars = 0, initial_max = 0, cont_max = 0;
-    void *d_cont_slots = nullptr, *d_cont_arena = nullptr, *d_wp_rows = nullptr, *d_piece_ids = nullptr;
+    void *d_cont_slots = nullptr, *d_cont_arena = nullptr, *d_wp_rows = nullptr, *d_piece_ids = nullptr, *d_piece_ends = nullptr;
     kgpu_wordpiece_info wp{};
 };
 
@@ -354,7 +354,9 @@ int build_word_table(const uint8_t *known, size_t known_len, const uint8_t *unk,
 // kgpu_words_host.cpp
 void words_release(kgpu_words *w);   // one reference less: the last one frees the tables and lets go of the dictionary
 // kgpu_encode_host.cpp: the vocabulary ids of a batch's records on c->stream (waited for by kgpu_ctx_sync_lines, which reports the ids); width 0: ragged
-int enqueue_encode(kgpu_ctx *c, const kgpu_vocab *v, const DeviceRecords &r, int32_t *d_ids, uint64_t id_capacity, uint64_t width, int32_t pad_id, uint64_t *d_id_offsets, const char *who);
+// spans (may be null): the span instantiation of the write kernel, a span and a token index beside every id (kgpu_encode_device_spans)
+int enqueue_encode(kgpu_ctx *c, const kgpu_vocab *v, const DeviceRecords &r, int32_t *d_ids, uint64_t id_capacity, uint64_t width, int32_t pad_id, uint64_t *d_id_offsets, const char *who,
+                   const SpanOut *spans = nullptr);
 void dict_key_table(kgpu_dict *d);   // kgpu_count_host.cpp: the dictionary's id -> key table (d->key_bytes, d->key_off), built by the first caller that needs it
 // kgpu_count_host.cpp: the count of a batch's records on c->stream behind whatever is queued there (waited for by kgpu_ctx_sync_count)
 int enqueue_count(kgpu_ctx *c, kgpu_counts *k, const DeviceRecords &r, const char *who);

@@ -90,6 +90,17 @@ class DeviceContext(Handle):
             self._h, vocab.handle, C.c_void_p(d_utf8), C.c_void_p(d_offsets), n, C.c_void_p(d_tokens), C.c_void_p(d_tok_offsets), C.c_void_p(d_ids),
             id_capacity, width, pad_id, C.c_void_p(d_id_offsets)))
 
+    def encode_spans(self, vocab, d_utf8: int, d_offsets: int, n: int, d_tokens: int, d_tok_offsets: int, d_ids: int, id_capacity: int, d_id_offsets: int,
+                     d_spans: int, d_token_index: int = 0, d_edits: int = 0, d_edit_offsets: int = 0, width: int = 0, pad_id: int = 0):
+        """kgpu_encode_device_spans: encode() that also leaves, for element e of d_ids, its source span (16-byte kgpu_span; d_spans 16-byte aligned,
+        id_capacity entries) in d_spans[e] and the index of its token among the sentence's records in d_token_index[e] (int32, id_capacity entries; 0:
+        not wanted); bos, eos and pad get zeros and -1.  d_edits / d_edit_offsets (both or neither): the edit records an aligned normalisation of the
+        same lines left in HBM -- the spans are then in SOURCE coordinates.  sync_lines waits for it and returns d_id_offsets[n]."""
+        _lib.check(_lib.lib().kgpu_encode_device_spans(
+            self._h, vocab.handle, C.c_void_p(d_utf8), C.c_void_p(d_offsets), n, C.c_void_p(d_tokens), C.c_void_p(d_tok_offsets),
+            C.c_void_p(d_edits) if d_edits else None, C.c_void_p(d_edit_offsets) if d_edit_offsets else None, C.c_void_p(d_ids), id_capacity, width, pad_id,
+            C.c_void_p(d_id_offsets), C.c_void_p(d_spans), C.c_void_p(d_token_index) if d_token_index else None))
+
     def normalize(self, d_utf8: int, d_offsets: int, n: int, d_text: int, text_capacity: int, d_text_offsets: int, d_status: int, form="NFKC"):
         """kgpu_normalize_device: enqueue NFC / NFKC of n lines in HBM -> the normalised lines packed in d_text (up to 11 times the input's bytes;
         no overlap with d_utf8), their uint64 offsets in d_text_offsets (n + 1) and a status byte per line in d_status: the buffers tokenize takes

@@ -11,6 +11,9 @@ equal input_ids with a real BERT-Japanese tokenizer (its NFKC is available -- To
 
 A Vocab made from a Words handle with normalize="NFC" / "NFKC" normalises the input of every encode call on the device first; the ids are those of
 the NORMALISED text, and a status byte is 4 where the normaliser left a line as it was.  Unlike the plain host forms, that needs the Tokenizer open.
+
+Ids with spans (include/kanpyo_gpu.h, "ids with spans"): encode_tensor(return_spans=True) and encode_spans give, beside every id, its span in the text
+the caller supplied (through the normaliser's edit records when a form is set) and the index of its token -- an offset_mapping and word_ids().
 """
 from __future__ import annotations
 
@@ -22,7 +25,7 @@ from typing import List, Sequence
 import numpy as np
 
 from . import _lib
-from ._calls import Handle, batch_call, block_call, pack_sentences, ptr, struct_dict
+from ._calls import SPAN_DTYPE, Handle, batch_call, block_call, pack_sentences, ptr, struct_dict
 from .device import DeviceContext
 
 
@@ -136,7 +139,7 @@ class Vocab(Handle):
         return [ids[o[i] : o[i + 1]] for i in range(len(o) - 1)]
 
     # ---- device memory out -----------------------------------------------------------------------------------------------------------------
-    def encode_tensor(self, sentences: Sequence, width=None, pad_id: int = 0, normalize=None):
+    def encode_tensor(self, sentences: Sequence, width=None, pad_id: int = 0, normalize=None, return_spans: bool = False):
         """The sentences (str or bytes) as torch tensors on the device, in ONE DeviceContext batch: upload, tokenize, sync, encode, sync_lines.
         No id passes through host memory.  THE WHOLE BATCH MUST FIT DEVICE MEMORY (its text, 24 bytes per token and 4 bytes per id): cut a
         corpus into batches.  The batch is tokenized on a DeviceContext of this Vocab's Tokenizer, made by the first call: unlike the host
@@ -146,7 +149,12 @@ class Vocab(Handle):
         eos_id when the vocabulary adds EOS) and filled with pad_id.
         normalize="NFC" / "NFKC" (None: the form the Vocab's Words handle was made with): the uploaded text is normalised on the device first
         (DeviceContext.normalize, sync_normalize) and the normalised buffers are what is tokenized and encoded: no text returns to the host.  The
-        status is the tokenizer's, 4 where the normaliser left a line as it was and the tokenizer said 0."""
+        status is the tokenizer's, 4 where the normaliser left a line as it was and the tokenizer said 0.
+        return_spans=True (kgpu_encode_device_spans) -> the tuple above and two more tensors, element for element beside ids: spans int32 [total, 4]
+        ([n, w, 4] padded), the columns position, byte_len, start, end of the id's piece (a whole token where the header's rule 5 says so) inside its
+        sentence -- columns 2:4 are character offsets, an offset_mapping -- and token_index int32 [total] ([n, w]), the index of the id's token among
+        the sentence's records (EOS record and dropped tokens counted).  bos, eos and pad have zeros and -1.  With a normalisation form the text is
+        normalised with its edit records (normalize_aligned) and the spans are in the coordinates of the SOURCE sentence, mapped on the device."""
         import torch
 
         if width is not None and int(width) < 1:
@@ -163,8 +171,24 @@ class Vocab(Handle):
             d_utf8 = torch.from_numpy(np.concatenate([utf8, np.zeros(16, dtype=np.uint8)])).to(dev)
             d_off = torch.from_numpy(offs.view(np.int64)).to(dev)
             form = self._normalize if normalize is None else _lib.normalize_form(normalize)
-            d_nst = None
-            if form is not None:   # the normalised lines and their offsets take the input's place; a capacity too small grows once, to the size reported
+            d_nst = d_edits = d_eoff = None
+            if form is not None and return_spans:   # ... with the lines' edit records, for the way back; either capacity too small grows once
+                d_nst = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+                d_noff = torch.empty(n + 1, dtype=torch.int64, device=dev)
+                d_eoff = torch.empty(n + 1, dtype=torch.int64, device=dev)
+                ncap, ecap = total * 2 + 64, total // 8 + 64
+                while True:
+                    d_norm = torch.zeros(ncap + 16, dtype=torch.uint8, device=dev)
+                    d_edits = torch.empty((ecap, 6), dtype=torch.int32, device=dev)
+                    torch.cuda.synchronize(dev)
+                    ctx.normalize_aligned(d_utf8.data_ptr(), d_off.data_ptr(), n, d_norm.data_ptr(), ncap, d_noff.data_ptr(), d_nst.data_ptr(), d_edits.data_ptr(), ecap,
+                                          d_eoff.data_ptr(), form)
+                    fits, total, n_edits = ctx.try_sync_normalize_aligned()
+                    if fits:
+                        break
+                    ncap, ecap = max(ncap, total), max(ecap, n_edits)
+                d_utf8, d_off = d_norm, d_noff
+            elif form is not None:   # the normalised lines and their offsets take the input's place; a capacity too small grows once, to the size reported
                 d_nst = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
                 d_noff = torch.empty(n + 1, dtype=torch.int64, device=dev)
                 ncap = total * 2 + 64
@@ -197,9 +221,17 @@ class Vocab(Handle):
             id_cap = n_tok + n * self._extra if width is None else n * int(width)   # (ragged, a plain Vocab: every record kept, and bos / eos: never too small)
             while True:   # (a WordPiece Vocab's tokens may give several ids each: once more with the count the device reports)
                 d_ids = torch.empty(max(id_cap, 1), dtype=torch.int32, device=dev) if width is None else torch.empty((n, int(width)), dtype=torch.int32, device=dev)
+                if return_spans:
+                    d_spans = torch.empty(tuple(d_ids.shape) + (4,), dtype=torch.int32, device=dev)
+                    d_tix = torch.empty_like(d_ids)
                 torch.cuda.synchronize(dev)
-                ctx.encode(self, d_utf8.data_ptr(), d_off.data_ptr(), n, d_tok.data_ptr(), d_toff.data_ptr(), d_ids.data_ptr(), id_cap, d_ioff.data_ptr(),
-                           width=0 if width is None else int(width), pad_id=int(pad_id))
+                if return_spans:
+                    ctx.encode_spans(self, d_utf8.data_ptr(), d_off.data_ptr(), n, d_tok.data_ptr(), d_toff.data_ptr(), d_ids.data_ptr(), id_cap, d_ioff.data_ptr(),
+                                     d_spans.data_ptr(), d_tix.data_ptr(), d_edits.data_ptr() if d_edits is not None else 0, d_eoff.data_ptr() if d_eoff is not None else 0,
+                                     width=0 if width is None else int(width), pad_id=int(pad_id))
+                else:
+                    ctx.encode(self, d_utf8.data_ptr(), d_off.data_ptr(), n, d_tok.data_ptr(), d_toff.data_ptr(), d_ids.data_ptr(), id_cap, d_ioff.data_ptr(),
+                               width=0 if width is None else int(width), pad_id=int(pad_id))
                 got = C.c_uint64(0)
                 rc = L.kgpu_ctx_sync_lines(ctx._h, C.byref(got))
                 if rc == _lib.KGPU_ERR_CAPACITY and width is None and int(got.value) > id_cap:
@@ -211,8 +243,18 @@ class Vocab(Handle):
             if d_nst is not None:   # (on the device: the normaliser's 4 shows where the tokenizer said 0)
                 d_st = torch.where((d_st == 0) & (d_nst == _lib.KGPU_SENT_NOT_NORMALIZED), d_nst, d_st)
         if width is None:
-            return d_ids[:count], d_ioff, d_st[:n]
-        return d_ids, torch.clamp(d_ioff[1:] - d_ioff[:-1], max=int(width)), d_st[:n]
+            out = d_ids[:count], d_ioff, d_st[:n]
+            return out + (d_spans[:count], d_tix[:count]) if return_spans else out
+        out = d_ids, torch.clamp(d_ioff[1:] - d_ioff[:-1], max=int(width)), d_st[:n]
+        return out + (d_spans, d_tix) if return_spans else out
+
+    def encode_spans(self, sentences: Sequence, normalize=None) -> List[tuple]:
+        """The host-friendly form of encode_tensor(return_spans=True): per sentence (ids int32, spans[SPAN_DTYPE], token_index int32) as numpy arrays.
+        The work is encode_tensor's, on the device; only the results are copied back."""
+        ids, off, _, spans, tix = self.encode_tensor(sentences, normalize=normalize, return_spans=True)
+        ids, tix, o = ids.cpu().numpy(), tix.cpu().numpy(), off.cpu().tolist()
+        spans = np.ascontiguousarray(spans.cpu().numpy()).view(np.uint32).reshape(-1, 4).copy().view(SPAN_DTYPE).reshape(-1)
+        return [(ids[o[i] : o[i + 1]], spans[o[i] : o[i + 1]], tix[o[i] : o[i + 1]]) for i in range(len(o) - 1)]
 
     # ---- the one-word-per-line file ----------------------------------------------------------------------------------------------------------
     def save(self, path):
@@ -256,6 +298,23 @@ class Vocab(Handle):
                 raise ValueError(f"the {what} word {b!r} is not in the vocabulary")
             ids.append(index[b])
         return cls(words_handle, words, ids[0], ids[1], ids[2], wordpiece, prefix, max_word_chars)
+
+
+def split_words_ends(vocab: Sequence, words: Sequence, unk_id: int, opts=None) -> List[tuple]:
+    """kgpu_debug_wordpiece_split_ends: split_words with, per id, where its piece ends inside its word -> per word (ids int32 [k], ends uint32 [k, 2]:
+    byte end, character end).  The one id of a word that gives unk_id ends where the word ends.  On the host, with no device and no handle."""
+    vp, voff = pack_sentences([_word_bytes(w) for w in vocab])
+    ip, ioff = pack_sentences([_word_bytes(w) for w in words])
+    vp, ip = np.ascontiguousarray(vp), np.ascontiguousarray(ip)
+    n = len(ioff) - 1
+    ooff = np.zeros(n + 1, dtype=np.uint64)
+    got = C.c_uint64(0)
+    cap = int(ioff[-1]) + 1
+    ids, ends = np.empty(cap, dtype=np.int32), np.zeros((cap, 2), dtype=np.uint32)
+    _lib.check(_lib.lib().kgpu_debug_wordpiece_split_ends(ptr(vp), voff.ctypes.data, len(voff) - 1, C.byref(opts) if opts is not None else None, int(unk_id),
+                                                          ptr(ip), ioff.ctypes.data, n, ids.ctypes.data, ends.ctypes.data, cap, ooff.ctypes.data, C.byref(got)))
+    o = ooff.tolist()
+    return [(ids[o[i] : o[i + 1]].copy(), ends[o[i] : o[i + 1]].copy()) for i in range(n)]
 
 
 def split_words(vocab: Sequence, words: Sequence, unk_id: int, opts=None) -> List[np.ndarray]:
