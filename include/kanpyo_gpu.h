@@ -145,6 +145,21 @@ typedef struct kgpu_routing {
                                  the tail of the launch chain had been left out (no recent batch needed it) and a sentence did need it */
     uint64_t combined_calls;  /* small kgpu_tokenize_batch calls that shared their launch with other threads' calls (the combiner) */
     uint64_t combined_launches; /* ... and the launches they shared                                                      */
+    uint64_t window_handed[10]; /* sentences the windowed kernel handed on to the next launch, by the limit they ran into (both of its
+                                 forms; of a batch rerun after the scratch arena grew (arena_regrows) the final run counts, and under [3] and [5]
+                                 the sentences the runs before it flagged for want of a chunk; not counted in KGPU_PROFILE_WORK runs, whose
+                                 instantiation uses the counters for its phase clocks):
+                                 [0] stays 0 (a refused launch configuration and a sentence of 2^24 bytes or more are handed on uncounted)
+                                 [1] a far (FIFO) entry that ends in the window has a node index more than 0x8000 below the window's base
+                                 [2] more than 8 prefixes at a position and more than 48 parked in the window's shared area (also a key of
+                                     256 characters or more, 255 prefixes or more at one position, 65536 records or more on one key)
+                                 [3] 262144 nodes in one sentence (or a node chunk the scratch arena could not give)
+                                 [4] more than 61440 far entries waiting in the FIFO
+                                 [5] a far chunk the scratch arena could not give
+                                 [6] far entries whose end positions decrease (a dictionary word longer than a window)
+                                 [7] two-wavefront form: a carry list beyond 384 entries (both forms: a carried node index below the next window's base)
+                                 [8] a window that does not fit the LDS (or its 16-bit node / slot indices) even four positions long
+                                 [9] unused                                                                                       */
 } kgpu_routing;
 
 /* The launch plan a context runs with (SURVEY.md 8d cfg 5: "LDS bytes / workgroup and achieved occupancy" as data). */

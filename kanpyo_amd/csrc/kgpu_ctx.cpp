@@ -61,7 +61,9 @@ extern "C" int kgpu_ctx_create(kgpu_dict *d, void *hip_stream, kgpu_ctx **out) {
     hipDeviceProp_t p;
     const int cus = hipGetDeviceProperties(&p, d->device) == hipSuccess ? p.multiProcessorCount : 256;
     c->plan = make_launch_plan(cus, Occupancy{pool_workgroups_per_cu, window_workgroups_per_cu, window_team_workgroups_per_cu});
-    c->aux_mode = test_hooks().aux_launch;
+    const TestHooks hooks = test_hooks();
+    c->aux_mode = hooks.aux_launch;
+    c->arena_initial = hooks.arena_initial ? (size_t)std::min<uint64_t>(ARENA_INITIAL, std::max<uint64_t>(1ull << 20, hooks.arena_initial)) : ARENA_INITIAL;
     *out = c;
     return KGPU_OK;
 }
@@ -242,7 +244,7 @@ static int tokenize_batch(kgpu_ctx *c, const uint8_t *d_utf8, const uint64_t *d_
     if (c->pending && (rc = kgpu_ctx_sync(c, nullptr)) != KGPU_OK && rc != KGPU_ERR_CAPACITY) return rc;
     const Batch b{n, total_bytes, c->dict->steer.est_q8.load(std::memory_order_relaxed), c->stop_after, false, false, c->rt.batches > 0};
     if ((rc = ctx_pick_stream(c, b))) return rc;
-    if ((rc = c->arena.ensure(ARENA_INITIAL)) || (rc = c->stage.ensure((size_t)token_bound(total_bytes, n) * sizeof(kgpu_token) + 64)) ||
+    if ((rc = c->arena.ensure(c->arena_initial)) || (rc = c->stage.ensure((size_t)token_bound(total_bytes, n) * sizeof(kgpu_token) + 64)) ||
         (rc = c->tok_count.ensure((size_t)(n + 1) * 4)) ||
         (rc = c->ovf.ensure((size_t)(n + 1) * 4 * 4)))
         return rc;
@@ -347,6 +349,9 @@ extern "C" int kgpu_ctx_sync(kgpu_ctx *c, uint64_t *n_tokens) {
             BatchArgs a = c->last;
             a.arena = (uint8_t *)c->arena.p; a.arena_bytes = c->arena.bytes;
             c->rt.arena_regrows++;
+            // (the windowed kernel counted the sentences it flagged for want of a chunk under whys 3 and 5: kept, the run's control block goes with the rerun;
+            // what the run handed on for other reasons is handed on again, and counted, by the run that stands)
+            if (!c->last.count_work) for (int k = 3; k <= 5; k += 2) c->rt.window_handed[k] += c->h_ctl->phase[k] + (c->tail_pass ? c->tail_saved.phase[k] : 0);
             c->tail_pass = false;  // (the whole batch runs again: nothing of an earlier pass is merged)
             // the rerun counts everything again: drop what the aborted run left in the per-wavefront slots (ctl->work went with the control block)
             if (a.stat_slots) HIPCHECK(hipMemsetAsync(a.stat_slots, 0, (size_t)STAT_SLOTS * STAT_WORDS * 8, c->stream));
@@ -382,6 +387,7 @@ extern "C" int kgpu_ctx_sync(kgpu_ctx *c, uint64_t *n_tokens) {
         }
         c->ev_used = 0;
     }
+    if (!c->last.count_work) for (int k = 0; k < 10; ++k) c->rt.window_handed[k] += c->h_ctl->phase[k];   // (Control::phase: the windowed kernel's reasons, when it holds no clocks)
     if (c->last.count_work) {  // what the general kernels counted (atomics on the control block)
         const unsigned long long *w = c->h_ctl->work;
         c->work.sentences += w[0]; c->work.B += w[1]; c->work.C += w[2]; c->work.T += w[3];

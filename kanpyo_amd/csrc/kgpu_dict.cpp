@@ -70,6 +70,9 @@ TestHooks kgpu::test_hooks() {
         // ... and the bytes of the scratch arena a chunk's kept lattices may use at first / at most (0: the whole arena / ARENA_MAX): tests of the overflow protocol
         if (const char *e = getenv("KGPU_HOST_GRAPHVIZ_ARENA_INITIAL")) cur.graphviz_arena_initial = strtoull(e, nullptr, 10);
         if (const char *e = getenv("KGPU_HOST_GRAPHVIZ_ARENA_MAX")) cur.graphviz_arena_max = strtoull(e, nullptr, 10);
+        // ... and the first size of a context's scratch arena on the tokenize path, in bytes (0: ARENA_INITIAL; clamped to [1 MiB, ARENA_INITIAL]; read when a context is
+        // created): tests of the windowed and the general kernel's overflow protocol (kgpu_ctx_sync doubles the arena and reruns the batch)
+        if (const char *e = getenv("KGPU_ARENA_INITIAL")) cur.arena_initial = strtoull(e, nullptr, 10);
         if (const char *e = getenv("KGPU_AUX_LAUNCH")) cur.aux_launch = atoi(e);   // scan + compaction behind a chain: 0 two launches, 1 one, 2 two with the single-wavefront scan (read when a context is created)
         if (const char *e = getenv("KGPU_MULTI_CHUNK_SENTS")) cur.multi_chunk_sents = strtoull(e, nullptr, 10);  // kgpu_tokenize_batch_multi: sentences per device and chunk (tests: many small super-chunks)
     }
@@ -469,6 +472,7 @@ extern "C" int kgpu_dict_get_routing(kgpu_dict *d, kgpu_routing *out, size_t out
             sum.long_launches += r.long_launches; sum.arena_regrows += r.arena_regrows; sum.first_ms += r.first_ms;
             sum.small_calls += r.small_calls; sum.small_fallbacks += r.small_fallbacks; sum.window_reruns += r.window_reruns; sum.tail_reruns += r.tail_reruns;
             sum.combined_calls += r.combined_calls; sum.combined_launches += r.combined_launches;
+            for (int k = 0; k < 10; ++k) sum.window_handed[k] += r.window_handed[k];
             if (reset) c->rt = kgpu_routing{};
         }
     }

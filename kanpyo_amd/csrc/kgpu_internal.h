@@ -83,7 +83,9 @@ struct Control {
     unsigned int pad0;
     unsigned long long n_tokens;      // dense token count (written by the scan kernel)
     unsigned long long work[7];       // kgpu_work, only when BatchArgs::count_work
-    unsigned long long phase[10];     // shader-clock cycles per phase of the LDS kernel (count_work only)
+    unsigned long long phase[10];     // count_work: shader-clock cycles per phase of the LDS kernel (the PROF instantiations of kgpu_pool.hip and kgpu_window.hip).  Otherwise: [why] counts the
+                                      // sentences the windowed kernel handed on by the limit they ran into (kgpu_routing::window_handed) -- its non-PROF instantiations are the only writers then:
+                                      // the pool kernel flushes its clocks under PROF alone (and into BatchArgs::stat_slots in a KGPU_STEP_TIMING build), kgpu_kernels.hip never writes the field
     unsigned int waves_done;          // single-launch small calls: wavefronts through with their sentence ...
     unsigned int waves_copied;        // ... and through with moving its tokens to the caller's (pinned) buffers
     unsigned int small_flag;          // the call's sequence number, stored LAST into the host copy: the host polls it

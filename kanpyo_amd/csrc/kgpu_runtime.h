@@ -200,6 +200,7 @@ struct kgpu_ctx {
     Control tail_saved{};      // ... what it had published (the length of the list the tail serves is copied back from here: lives in the context)
     uint32_t event_every = 1;  // KGPU_PROFILE_SAMPLED: HIP events on every 4th launch only
     DevBuf arena, stage, tok_count;
+    size_t arena_initial = 0;  // the arena's first size on the tokenize path: ARENA_INITIAL, or KGPU_ARENA_INITIAL as the context found it when it was created
     // host-buffer path staging
     DevBuf in_utf8, in_off, out_tok, out_off, out_status;
     PinBuf pin_in, pin_out;       // large host calls: input staging (offsets | bytes), mapped result block (records | first | token offsets | status)
@@ -302,7 +303,7 @@ struct WorkerPool {
     void task_done(std::atomic<int> &counter); // a task's last statement
 };
 WorkerPool &workers();
-struct TestHooks { bool no_small_calls = false, plain_leaves = false, byte_trie = false; uint64_t chunk_bytes = 4ull << 20, chunk_sents = 16384, depth = 12, multi_chunk_sents = 0, graphviz_chunk_sents = 0, graphviz_arena_initial = 0, graphviz_arena_max = 0; int aux_launch = -1; };
+struct TestHooks { bool no_small_calls = false, plain_leaves = false, byte_trie = false; uint64_t chunk_bytes = 4ull << 20, chunk_sents = 16384, depth = 12, multi_chunk_sents = 0, graphviz_chunk_sents = 0, graphviz_arena_initial = 0, graphviz_arena_max = 0, arena_initial = 0; int aux_launch = -1; };
 TestHooks test_hooks();  // test-only environment hooks, read once per process (or per call under KGPU_TEST_HOOKS_REREAD)
 bool env_flag_now(const char *name);
 

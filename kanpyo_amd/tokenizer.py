@@ -226,7 +226,7 @@ class Tokenizer(Handle):
         """kgpu_dict_get_routing: the routing counters of the handle's pooled contexts (small_calls, combined_calls, ...)."""
         r = _lib.Routing()
         _lib.check(_lib.lib().kgpu_dict_get_routing(self._h, C.byref(r), C.sizeof(r), 1 if reset else 0))
-        return {n: (list(getattr(r, n)) if n in ("deferred", "redone") else getattr(r, n)) for n, *_ in r._fields_}
+        return {n: (list(getattr(r, n)) if n in ("deferred", "redone", "window_handed") else getattr(r, n)) for n, *_ in r._fields_}
 
     # ---- reference-shaped API --------------------------------------------------
     def tokenize_batch(self, sentences: Sequence[str], normalize=None) -> List[List[Token]]:

@@ -38,6 +38,17 @@ static LaunchPlan plan_with(const char *pool, const char *window = nullptr, cons
 
 static Batch batch(uint64_t n, uint64_t bytes, bool share_known = true) { return Batch{n, bytes, 64 * 256, 0, false, false, share_known}; }
 
+// Every chain this file builds goes through here: a Window / WindowTeam step always has a list to hand on to (out >= 0).  The windowed kernel's other
+// way out -- no list: flag Control::window_fail, the host reruns the batch without it (kgpu_routing.window_reruns) -- is therefore never taken today.
+static int window_steps = 0;
+static Chain window_has_out(const Chain &c) {
+    for (int k = 0; k < c.n; ++k)
+        if (c.steps[k].kernel == Kernel::Window || c.steps[k].kernel == Kernel::WindowTeam) { ++window_steps; CHECK(c.steps[k].out >= 0 && c.steps[k].out < 4); }
+    return c;
+}
+static Chain built(const LaunchPlan &plan, const Batch &b, Steering &st, ContextSteering &cs) { return window_has_out(build_chain(plan, b, st, cs)); }
+static Chain tailed(const LaunchPlan &plan, const Chain &ran) { return window_has_out(tail_chain(plan, ran)); }
+
 static bool step_is(const Step &s, Kernel k, int in, int out, int grid) { return s.kernel == k && s.in == in && s.out == out && s.grid == grid; }
 
 static void test_plan() {
@@ -71,41 +82,41 @@ static void test_short_batch() {
     ContextSteering cs;
     cs.win_share_q8 = 20;
     // pool -> window, no general while tail_batches is 0 (was kgpu_ctx.cpp:149, :153, :159; kgpu_kernels.hip:595)
-    Chain c = build_chain(p, batch(4096, 4096 * 40), st, cs);
+    Chain c = built(p, batch(4096, 4096 * 40), st, cs);
     CHECK(c.n == 2 && c.event_behind_first && !c.small_scan && c.last_list() == 1);
     // pool grid: min(workgroups, ceil(n / waves)) (was kgpu_kernels.hip:563-565)
     CHECK(step_is(c.steps[0], Kernel::Pool, -1, 0, 1024) && c.steps[0].lds_bytes == 40 * 1024 && c.steps[0].waves == 4 && c.steps[0].max_pages == 32);
     // window grid: ((4096 * 20) >> 8) * 5 / 4 + 64 = 464 (was kgpu_ctx.cpp:190, kgpu_kernels.hip:540); expected (464 - 64) * 4 / 5 = 320 <= 464: no claim (was :543-544)
     CHECK(step_is(c.steps[1], Kernel::Window, 0, 1, 464) && !c.steps[1].claim && c.steps[1].lds_bytes == 10 * 1024);
-    CHECK(step_is(build_chain(p, batch(1000, 1000 * 40), st, cs).steps[0], Kernel::Pool, -1, 0, 250));
+    CHECK(step_is(built(p, batch(1000, 1000 * 40), st, cs).steps[0], Kernel::Pool, -1, 0, 250));
     // the context's first batch: the full grid (was kgpu_ctx.cpp:189)
-    c = build_chain(p, batch(4096, 4096 * 40, false), st, cs);
+    c = built(p, batch(4096, 4096 * 40, false), st, cs);
     CHECK(step_is(c.steps[1], Kernel::Window, 0, 1, 4096) && !c.steps[1].claim);
     // at least 256 (was kgpu_ctx.cpp:190)
     cs.win_share_q8 = 0;
-    CHECK(build_chain(p, batch(4096, 4096 * 40), st, cs).steps[1].grid == 256);
+    CHECK(built(p, batch(4096, 4096 * 40), st, cs).steps[1].grid == 256);
     // an estimate beyond the chip: the full grid, and the sentences are claimed one by one (was kgpu_kernels.hip:540-544)
     cs.win_share_q8 = 256;
-    c = build_chain(p, batch(65536, 65536 * 40), st, cs);
+    c = built(p, batch(65536, 65536 * 40), st, cs);
     CHECK(step_is(c.steps[1], Kernel::Window, 0, 1, 4096) && c.steps[1].claim);
     // disarmed windowed kernel: the pool alone (was kgpu_ctx.cpp:153-154)
     st.window_batches = 0;
-    c = build_chain(p, batch(4096, 4096 * 40), st, cs);
+    c = built(p, batch(4096, 4096 * 40), st, cs);
     CHECK(c.n == 1 && c.last_list() == 0);
     // armed general kernel: it closes the chain over the last list (was kgpu_ctx.cpp:159-160, kgpu_kernels.hip:547-551)
     st.window_batches = 64; st.tail_batches = 1;
-    c = build_chain(p, batch(4096, 4096 * 40), st, cs);
+    c = built(p, batch(4096, 4096 * 40), st, cs);
     CHECK(c.n == 3 && step_is(c.steps[2], Kernel::General, 1, -1, 512) && c.last_list() == -1);
     // two pools while big_pool_batches is armed (was kgpu_ctx.cpp:149, kgpu_kernels.hip:561-571)
     const LaunchPlan q = plan_with("80:8,160:4");
     st.tail_batches = 0; st.big_pool_batches = 1;
-    c = build_chain(q, batch(4096, 4096 * 40), st, cs);
+    c = built(q, batch(4096, 4096 * 40), st, cs);
     CHECK(c.n == 3 && step_is(c.steps[0], Kernel::Pool, -1, 0, 512) && step_is(c.steps[1], Kernel::Pool, 0, 1, 256) && c.steps[1].waves == 4);
     CHECK(c.steps[2].kernel == Kernel::Window && c.steps[2].in == 1 && c.steps[2].out == 2);
     st.big_pool_batches = 0;
-    CHECK(build_chain(q, batch(4096, 4096 * 40), st, cs).pools() == 1);
+    CHECK(built(q, batch(4096, 4096 * 40), st, cs).pools() == 1);
     // an empty batch has no chain (was kgpu_ctx.cpp:148)
-    CHECK(build_chain(p, batch(0, 0), st, cs).n == 0);
+    CHECK(built(p, batch(0, 0), st, cs).n == 0);
 }
 
 static void test_window_first() {
@@ -117,62 +128,62 @@ static void test_window_first() {
         // kgpu_kernels.hip:575-586)
         Steering st;
         ContextSteering cs;
-        const Chain c = build_chain(p, batch(1000, 3000000), st, cs);
+        const Chain c = built(p, batch(1000, 3000000), st, cs);
         CHECK(c.n == 2 && !c.event_behind_first && c.small_scan && c.pools() == 0);
         CHECK(step_is(c.steps[0], Kernel::WindowTeam, -1, 0, 1000) && c.steps[0].lds_bytes == 10 * 1024);
         CHECK(step_is(c.steps[1], Kernel::Window, 0, 1, 256) && !c.steps[1].claim);   // expected (256 - 64) * 4 / 5 = 153
         CHECK(cs.counted_long == 1000 && st.long_sentences_in_flight == 1000 && st.long_peak == 1000);
-        build_chain(p, batch(1000, 3000000), st, cs);   // a rerun of the same batch counts it once (was kgpu_ctx.cpp:167)
+        built(p, batch(1000, 3000000), st, cs);   // a rerun of the same batch counts it once (was kgpu_ctx.cpp:167)
         CHECK(cs.counted_long == 1000 && st.long_sentences_in_flight == 1000);
     }
     {   // other contexts' long sentences in flight: 2000 > 1536 -> the ordinary form over the identity, grid min(n, 4096) (was kgpu_kernels.hip:537)
         Steering st;
         ContextSteering cs;
         st.long_sentences_in_flight = 1000;
-        const Chain c = build_chain(p, batch(1000, 3000000), st, cs);
+        const Chain c = built(p, batch(1000, 3000000), st, cs);
         CHECK(c.n == 1 && step_is(c.steps[0], Kernel::Window, -1, 0, 1000) && !c.steps[0].claim && c.small_scan && c.last_list() == 0);
     }
     {   // the peak decays by an eighth per enqueue (was kgpu_ctx.cpp:168-170): max(1000, 4000 - 500) = 3500
         Steering st;
         ContextSteering cs;
         st.long_peak = 4000;
-        CHECK(build_chain(p, batch(1000, 3000000), st, cs).steps[0].kernel == Kernel::Window && st.long_peak == 3500);
+        CHECK(built(p, batch(1000, 3000000), st, cs).steps[0].kernel == Kernel::Window && st.long_peak == 3500);
     }
     {   // boundary: a peak of exactly 2 x 768 still takes the team form
         Steering st;
         ContextSteering cs;
         st.long_sentences_in_flight = 536;
-        CHECK(build_chain(p, batch(1000, 3000000), st, cs).steps[0].kernel == Kernel::WindowTeam);
+        CHECK(built(p, batch(1000, 3000000), st, cs).steps[0].kernel == Kernel::WindowTeam);
     }
     {   // more sentences than windowed workgroups: claimed one by one (was kgpu_kernels.hip:543-544)
         Steering st;
         ContextSteering cs;
-        const Chain c = build_chain(p, batch(5000, 6000000), st, cs);
+        const Chain c = built(p, batch(5000, 6000000), st, cs);
         CHECK(step_is(c.steps[0], Kernel::Window, -1, 0, 4096) && c.steps[0].claim);
     }
     {   // KGPU_WINDOW_TEAM=0: never, and nothing is counted (was kgpu_ctx.cpp:166)
         Steering st;
         ContextSteering cs;
-        const Chain c = build_chain(plan_with(nullptr, nullptr, "0"), batch(1000, 3000000), st, cs);
+        const Chain c = built(plan_with(nullptr, nullptr, "0"), batch(1000, 3000000), st, cs);
         CHECK(c.n == 1 && c.steps[0].kernel == Kernel::Window && cs.counted_long == 0 && st.long_sentences_in_flight == 0);
     }
     {   // KGPU_WINDOW_TEAM=2: whatever the load (was kgpu_ctx.cpp:172)
         Steering st;
         ContextSteering cs;
         st.long_sentences_in_flight = 100000;
-        CHECK(build_chain(plan_with(nullptr, nullptr, "2"), batch(1000, 3000000), st, cs).steps[0].kernel == Kernel::WindowTeam);
+        CHECK(built(plan_with(nullptr, nullptr, "2"), batch(1000, 3000000), st, cs).steps[0].kernel == Kernel::WindowTeam);
     }
     {   // armed general kernel behind a team chain: over list 1 (was kgpu_kernels.hip:596)
         Steering st;
         ContextSteering cs;
         st.tail_batches = 64;
-        const Chain c = build_chain(p, batch(1000, 3000000), st, cs);
+        const Chain c = built(p, batch(1000, 3000000), st, cs);
         CHECK(c.n == 3 && step_is(c.steps[2], Kernel::General, 1, -1, 512));
     }
     {   // no pools in the plan: every chain starts with the windowed kernel, the team rule applies (was kgpu_ctx.cpp:149, :166)
         Steering st;
         ContextSteering cs;
-        const Chain c = build_chain(plan_with("0"), batch(100, 1000), st, cs);
+        const Chain c = built(plan_with("0"), batch(100, 1000), st, cs);
         CHECK(c.n == 2 && step_is(c.steps[0], Kernel::WindowTeam, -1, 0, 100));
     }
 }
@@ -184,28 +195,28 @@ static void test_pool_shape() {
     cs.long_share = true;
     cs.win_share_q8 = 64;
     // long_share: two wavefronts on 20 KB, 56 pages up to 16 384 sentences, 64 beyond (was kgpu_ctx.cpp:181-184)
-    Chain c = build_chain(p, batch(16384, 16384 * 40), st, cs);
+    Chain c = built(p, batch(16384, 16384 * 40), st, cs);
     CHECK(step_is(c.steps[0], Kernel::Pool, -1, 0, 2048) && c.steps[0].lds_bytes == 20 * 1024 && c.steps[0].waves == 2 && c.steps[0].max_pages == 56);
     CHECK(c.small_scan);   // a windowed launch in the chain and long_share (was kgpu_ctx.cpp:199)
-    c = build_chain(p, batch(16385, 16385 * 40), st, cs);
+    c = built(p, batch(16385, 16385 * 40), st, cs);
     CHECK(c.steps[0].max_pages == 64 && c.steps[0].lds_bytes == 20 * 1024);
-    CHECK(build_chain(p, batch(1000, 1000 * 40), st, cs).steps[0].grid == 500);   // ceil(1000 / 2)
+    CHECK(built(p, batch(1000, 1000 * 40), st, cs).steps[0].grid == 500);   // ceil(1000 / 2)
     // an explicit KGPU_POOL keeps its shape (was kgpu_ctx.cpp:181)
-    c = build_chain(plan_with("40:4:32"), batch(16384, 16384 * 40), st, cs);
+    c = built(plan_with("40:4:32"), batch(16384, 16384 * 40), st, cs);
     CHECK(c.steps[0].lds_bytes == 40 * 1024 && c.steps[0].waves == 4 && c.steps[0].max_pages == 32);
     // "roomy": four reservations of ((bytes / n) * est >> 8) + 768 beyond 92 % of the pool -> three wavefronts, the same grid (was kgpu_ctx.cpp:104-105, :185)
     cs.long_share = false;
     Batch b = batch(4096, 4096 * 40);
     b.est_q8 = 55380;   // (40 * 55380 >> 8) + 768 = 9421; 400 * 9421 > 40960 * 92
-    c = build_chain(p, b, st, cs);
+    c = built(p, b, st, cs);
     CHECK(step_is(c.steps[0], Kernel::Pool, -1, 0, 1024) && c.steps[0].waves == 3 && c.steps[0].lds_bytes == 40 * 1024);
     b.n = 1000; b.bytes = 40000;
-    CHECK(build_chain(p, b, st, cs).steps[0].grid == 334);   // ceil(1000 / 3)
+    CHECK(built(p, b, st, cs).steps[0].grid == 334);   // ceil(1000 / 3)
     b = batch(4096, 4096 * 40);
     b.est_q8 = 55379;   // 9420: fits
-    CHECK(build_chain(p, b, st, cs).steps[0].waves == 4);
+    CHECK(built(p, b, st, cs).steps[0].waves == 4);
     b.est_q8 = 65536;   // only the shipped plan (was kgpu_ctx.cpp:105)
-    CHECK(build_chain(plan_with("40:4"), b, st, cs).steps[0].waves == 4);
+    CHECK(built(plan_with("40:4"), b, st, cs).steps[0].waves == 4);
 }
 
 static void test_general_closes() {
@@ -215,19 +226,19 @@ static void test_general_closes() {
     // ablation: the pool kernel and the general kernel, no windowed kernel, even for long sentences (was kgpu_ctx.cpp:99, :153, :159; kgpu_kernels.hip:573)
     Batch b = batch(1000, 3000000);
     b.stop_after = 3;
-    Chain c = build_chain(p, b, st, cs);
+    Chain c = built(p, b, st, cs);
     // (3000 bytes per sentence: four reservations do not fit, so the pool runs three wavefronts: ceil(1000 / 3) workgroups)
     CHECK(c.n == 2 && step_is(c.steps[0], Kernel::Pool, -1, 0, 334) && c.steps[0].waves == 3 && step_is(c.steps[1], Kernel::General, 0, -1, 512) && !c.small_scan);
     b = batch(1, 100);   // lattice dump
     b.dump = true;
-    c = build_chain(p, b, st, cs);
+    c = built(p, b, st, cs);
     CHECK(c.n == 2 && step_is(c.steps[0], Kernel::Pool, -1, 0, 1) && step_is(c.steps[1], Kernel::General, 0, -1, 512));
     b = batch(1000, 3000000);   // the rerun without the windowed kernel: no window-first chain either
     b.no_window = true;
-    c = build_chain(p, b, st, cs);
+    c = built(p, b, st, cs);
     CHECK(c.n == 2 && c.steps[0].kernel == Kernel::Pool && step_is(c.steps[1], Kernel::General, 0, -1, 512) && cs.counted_long == 0);
     // nothing but the general kernel: over the identity, grid min(n, 512) (was kgpu_kernels.hip:550)
-    c = build_chain(plan_with("0", "0"), batch(100, 1000), st, cs);
+    c = built(plan_with("0", "0"), batch(100, 1000), st, cs);
     CHECK(c.n == 1 && step_is(c.steps[0], Kernel::General, -1, -1, 100) && !c.event_behind_first);
 }
 
@@ -237,29 +248,29 @@ static void test_tail() {
     ContextSteering cs;
     cs.win_share_q8 = 20;
     // the windowed kernel was in the chain: the general kernel over its list (was kgpu_kernels.hip:604, :609)
-    Chain t = tail_chain(p, build_chain(p, batch(4096, 4096 * 40), st, cs));
+    Chain t = tailed(p, built(p, batch(4096, 4096 * 40), st, cs));
     CHECK(t.n == 1 && step_is(t.steps[0], Kernel::General, 1, -1, 512) && !t.small_scan && !t.event_behind_first);
     // pool alone: the windowed kernel over list 0 on the full grid without claims, the general kernel over list 1 (was kgpu_kernels.hip:604-609)
     st.window_batches = 0;
-    const Chain pool_only = build_chain(p, batch(4096, 4096 * 40), st, cs);
-    t = tail_chain(p, pool_only);
+    const Chain pool_only = built(p, batch(4096, 4096 * 40), st, cs);
+    t = tailed(p, pool_only);
     CHECK(t.n == 2 && step_is(t.steps[0], Kernel::Window, 0, 1, 4096) && !t.steps[0].claim && step_is(t.steps[1], Kernel::General, 1, -1, 512));
     // two pools alone (list 1) and with the windowed kernel (list 2)
     st.big_pool_batches = 1;
-    t = tail_chain(q, build_chain(q, batch(4096, 4096 * 40), st, cs));
+    t = tailed(q, built(q, batch(4096, 4096 * 40), st, cs));
     CHECK(t.n == 2 && step_is(t.steps[0], Kernel::Window, 1, 2, 4096) && step_is(t.steps[1], Kernel::General, 2, -1, 512));
     st.window_batches = 64;
-    t = tail_chain(q, build_chain(q, batch(4096, 4096 * 40), st, cs));
+    t = tailed(q, built(q, batch(4096, 4096 * 40), st, cs));
     CHECK(t.n == 1 && step_is(t.steps[0], Kernel::General, 2, -1, 512));
     // window-first chains: after the team form (list 1) and without it (list 0)
     Steering st2;
     ContextSteering cs2;
-    t = tail_chain(p, build_chain(p, batch(1000, 3000000), st2, cs2));
+    t = tailed(p, built(p, batch(1000, 3000000), st2, cs2));
     CHECK(t.n == 1 && step_is(t.steps[0], Kernel::General, 1, -1, 512));
-    t = tail_chain(p, build_chain(plan_with(nullptr, nullptr, "0"), batch(1000, 3000000), st2, cs2));
+    t = tailed(p, built(plan_with(nullptr, nullptr, "0"), batch(1000, 3000000), st2, cs2));
     CHECK(t.n == 1 && step_is(t.steps[0], Kernel::General, 0, -1, 512));
     // no windowed kernel in the plan: the general kernel over the pool's list
-    t = tail_chain(plan_with(nullptr, "0"), pool_only);
+    t = tailed(plan_with(nullptr, "0"), pool_only);
     CHECK(t.n == 1 && step_is(t.steps[0], Kernel::General, 0, -1, 512));
 }
 
@@ -277,11 +288,11 @@ static void test_feedback() {
     cs.win_share_q8 = 20;
     Steering st;
     st.tail_batches = 64;
-    const Chain full = build_chain(p, batch(1000, 40000), st, cs);   // pool -> window -> general
+    const Chain full = built(p, batch(1000, 40000), st, cs);   // pool -> window -> general
     st.tail_batches = 0;
-    const Chain pw = build_chain(p, batch(1000, 40000), st, cs);     // pool -> window
+    const Chain pw = built(p, batch(1000, 40000), st, cs);     // pool -> window
     st.window_batches = 0;
-    const Chain po = build_chain(p, batch(1000, 40000), st, cs);     // pool
+    const Chain po = built(p, batch(1000, 40000), st, cs);     // pool
     CHECK(full.n == 3 && pw.n == 2 && po.n == 1);
     const uint32_t late_ok = 20;   // 2 %: the estimate stays
 
@@ -300,7 +311,7 @@ static void test_feedback() {
     chain_feedback(p, full, nullptr, counts(5, 0, 0, late_ok), 1000, E, st, cs);
     CHECK(st.tail_batches == 56);
     // a tail pass that added the windowed kernel: its list arms the general kernel, the first pass's chain decides the decay (was kgpu_ctx.cpp:263, :355-358, :377-380)
-    const Chain tail = tail_chain(p, po);
+    const Chain tail = tailed(p, po);
     st.window_batches = 10; st.tail_batches = 10;
     chain_feedback(p, po, &tail, counts(3, 1, 0, late_ok), 1000, E, st, cs);
     CHECK(st.window_batches == 64 && st.tail_batches == 64);
@@ -346,9 +357,9 @@ static void test_feedback() {
     const LaunchPlan q = plan_with("80:8,160:4");
     Steering s2;
     ContextSteering c2;
-    const Chain one = build_chain(q, batch(1000, 40000), s2, c2);
+    const Chain one = built(q, batch(1000, 40000), s2, c2);
     s2.big_pool_batches = 1;
-    const Chain two = build_chain(q, batch(1000, 40000), s2, c2);
+    const Chain two = built(q, batch(1000, 40000), s2, c2);
     CHECK(one.pools() == 1 && two.pools() == 2);
     s2.big_pool_batches = 5;
     chain_feedback(q, two, nullptr, counts(0, 0, 0, late_ok), 1000, E, s2, c2);
@@ -367,29 +378,29 @@ static void test_feedback() {
     // a window-first chain: the windowed kernel's list arms the general kernel, 1 after the team form, 0 without (was kgpu_ctx.cpp:387-391)
     Steering s3;
     ContextSteering c3;
-    const Chain team = build_chain(p, batch(1000, 3000000), s3, c3);
+    const Chain team = built(p, batch(1000, 3000000), s3, c3);
     CHECK(team.steps[0].kernel == Kernel::WindowTeam);
     s3.tail_batches = 10; s3.window_batches = 10; s3.est_q8 = 7;
     chain_feedback(p, team, nullptr, counts(5, 0, 0, 900), 1000, E, s3, c3);
     CHECK(s3.tail_batches == 10 && s3.window_batches == 10 && s3.est_q8 == 7 && c3.win_share_q8 == 0);   // no pools: no window arming, no share, no estimate
     chain_feedback(p, team, nullptr, counts(0, 1), 1000, E, s3, c3);
     CHECK(s3.tail_batches == 64);
-    const Chain lone = build_chain(plan_with(nullptr, nullptr, "0"), batch(1000, 3000000), s3, c3);
+    const Chain lone = built(plan_with(nullptr, nullptr, "0"), batch(1000, 3000000), s3, c3);
     s3.tail_batches = 10;
     chain_feedback(p, lone, nullptr, counts(1), 1000, E, s3, c3);
     CHECK(s3.tail_batches == 64);
     s3.tail_batches = 64;
-    const Chain lone_general = build_chain(plan_with(nullptr, nullptr, "0"), batch(1000, 3000000), s3, c3);
+    const Chain lone_general = built(plan_with(nullptr, nullptr, "0"), batch(1000, 3000000), s3, c3);
     chain_feedback(p, lone_general, nullptr, counts(0), 1000, E, s3, c3);
     CHECK(lone_general.n == 2 && s3.tail_batches == 56);
     // ... not without pools in the plan (was kgpu_ctx.cpp:387: plan.n_pools)
     s3.tail_batches = 10;
-    chain_feedback(plan_with("0"), build_chain(plan_with("0"), batch(100, 1000), s3, c3), nullptr, counts(1, 1), 100, E, s3, c3);
+    chain_feedback(plan_with("0"), built(plan_with("0"), batch(100, 1000), s3, c3), nullptr, counts(1, 1), 100, E, s3, c3);
     CHECK(s3.tail_batches == 10);
 
     // an empty batch changes nothing
     st.window_batches = 10; st.tail_batches = 10; st.est_q8 = 7;
-    chain_feedback(p, build_chain(p, batch(0, 0), st, cs), nullptr, counts(0), 0, E, st, cs);
+    chain_feedback(p, built(p, batch(0, 0), st, cs), nullptr, counts(0), 0, E, st, cs);
     CHECK(st.window_batches == 10 && st.tail_batches == 10 && st.est_q8 == 7);
 }
 
@@ -401,6 +412,7 @@ int main() {
     test_general_closes();
     test_tail();
     test_feedback();
+    CHECK(window_steps >= 30);   // (the wrappers above saw the chains)
     if (failures) { printf("%d of %d checks failed\n", failures, checks); return 1; }
     printf("ok %d checks\n", checks);
     return 0;

@@ -27,6 +27,7 @@ int main(void) {
     F(kgpu_routing, batches); F(kgpu_routing, sentences); F(kgpu_routing, deferred); F(kgpu_routing, redone); F(kgpu_routing, long_launches);
     F(kgpu_routing, arena_regrows); F(kgpu_routing, first_ms); F(kgpu_routing, small_calls); F(kgpu_routing, small_fallbacks);
     F(kgpu_routing, window_reruns); F(kgpu_routing, tail_reruns); F(kgpu_routing, combined_calls); F(kgpu_routing, combined_launches);
+    F(kgpu_routing, window_handed);
     S(kgpu_plan_info);
     F(kgpu_plan_info, compute_units); F(kgpu_plan_info, pool_lds_bytes); F(kgpu_plan_info, pool_wavefronts); F(kgpu_plan_info, pool_workgroups_per_cu);
     F(kgpu_plan_info, pool_max_pages); F(kgpu_plan_info, long_lds_bytes); F(kgpu_plan_info, long_workgroups_per_cu); F(kgpu_plan_info, long_workgroups);

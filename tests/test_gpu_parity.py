@@ -647,8 +647,10 @@ def test_windowed_kernel_big_buckets_and_many_prefixes(libs, window_kib, monkeyp
     * a position whose bucket has more than 64 predecessors -- the end of a long same-category run: every start position of the run contributes its
       unknown words there (src/lattice.rs:66-84) -- gets no pair table; its step loads the connection costs itself (connection.rs:12-14);
     * a start position with more than eight dictionary prefixes parks the ninth and later ones in the window's shared overflow area
-      (trie/da.rs:155-182 yields them in ascending length; the node order of src/lattice.rs:105-110 must survive).
-    Pool off: every sentence goes through the windowed kernel.  Routing must show that nothing was handed on."""
+      (trie/da.rs:155-182 yields them in ascending length; the node order of src/lattice.rs:105-110 must survive) -- as long as the window's 48 places
+      there suffice: nine nested prefixes park one match per position and are held, thirty park 22 per position, and a run of them is handed on
+      (kgpu_routing.window_handed[2]; tests/test_gpu_window_limits.py has the exact boundary) -- the same records either way.
+    Pool off: every sentence goes through the windowed kernel.  Routing must show what was handed on, and why."""
     from kanpyo_amd import Dict, Tokenizer, synth
     from kanpyo_amd.device import PROFILE_OFF
 
@@ -667,24 +669,34 @@ def test_windowed_kernel_big_buckets_and_many_prefixes(libs, window_kib, monkeyp
     ctx, t, toff, utf8, offs = _device_run(tok, sents, PROFILE_OFF)
     exp = orc.tokenize_batch(utf8, offs, 8)
     assert np.array_equal(toff.astype(np.uint64), exp.offsets) and np.array_equal(t.reshape(-1), exp.tokens.view(np.int32).reshape(-1))
+    prof = ctx.profile()
     if window_kib != "9":   # (at 9 KB some windows do not fit even four positions long: those sentences may travel on -- still the same records)
-        assert ctx.profile()["deferred"][0] == 0, ctx.profile()
-    # (2) nested prefixes: "あ", "ああ", ... up to 30 characters, three records each: up to 30 prefixes per start position
-    kws = []
-    for n in range(1, 31):
-        kws += ["あ" * n] * 3
-    kws += ["い", "あい"]
-    kws = sorted(kws, key=lambda x: x.encode())
-    nr = np.random.default_rng(3)
-    morphs = np.stack([nr.integers(0, 5, len(kws)), nr.integers(0, 5, len(kws)), nr.integers(-500, 5000, len(kws))], axis=1)
-    p = fixture_dict_parts()
-    d = Dict.from_parts(kws, morphs, 5, 5, nr.integers(-900, 900, 25), p["char_class"], p["char_category"], p["invoke_list"], p["group_list"],
-                        {0: (1, 1), 1: (1, 2), 2: (2, 1)}, [[0, 0, 4000], [1, 1, 3500]])
-    tok2, orc2 = Tokenizer(d), oracle.OracleTokenizer.from_dict(d)
-    sents2 = ["あ" * n for n in (1, 8, 9, 10, 17, 33, 64, 200)] + ["あ" * 12 + "い" + "あ" * 40, "いあいあ" * 30, "あ" * 5 + "x" + "あ" * 70]
-    ctx2, t2, toff2, utf82, offs2 = _device_run(tok2, sents2, PROFILE_OFF)
-    exp2 = orc2.tokenize_batch(utf82, offs2, 2)
-    assert np.array_equal(toff2.astype(np.uint64), exp2.offsets) and np.array_equal(t2.reshape(-1), exp2.tokens.view(np.int32).reshape(-1))
+        assert prof["deferred"][0] == 0 and prof["window_handed"] == [0] * 10, prof
+    else:                   # ... and for that reason alone (a lone batch runs the team form first: what neither form holds is counted by both)
+        assert [k for k, v in enumerate(prof["window_handed"]) if v] in ([], [8]) and prof["window_handed"][8] == sum(prof["deferred"][:2]), prof
+    # (2) nested prefixes: "あ", "ああ", ... up to 9 / 30 characters, three records each: up to 9 / 30 prefixes per start position
+    for longest in (9, 30):
+        kws = []
+        for n in range(1, longest + 1):
+            kws += ["あ" * n] * 3
+        kws += ["い", "あい"]
+        kws = sorted(kws, key=lambda x: x.encode())
+        nr = np.random.default_rng(3)
+        morphs = np.stack([nr.integers(0, 5, len(kws)), nr.integers(0, 5, len(kws)), nr.integers(-500, 5000, len(kws))], axis=1)
+        p = fixture_dict_parts()
+        d = Dict.from_parts(kws, morphs, 5, 5, nr.integers(-900, 900, 25), p["char_class"], p["char_category"], p["invoke_list"], p["group_list"],
+                            {0: (1, 1), 1: (1, 2), 2: (2, 1)}, [[0, 0, 4000], [1, 1, 3500]])
+        tok2, orc2 = Tokenizer(d), oracle.OracleTokenizer.from_dict(d)
+        sents2 = ["あ" * n for n in (1, 8, 9, 10, 17, 33, 64, 200)] + ["あ" * 12 + "い" + "あ" * 40, "いあいあ" * 30, "あ" * 5 + "x" + "あ" * 70]
+        ctx2, t2, toff2, utf82, offs2 = _device_run(tok2, sents2, PROFILE_OFF)
+        exp2 = orc2.tokenize_batch(utf82, offs2, 2)
+        assert np.array_equal(toff2.astype(np.uint64), exp2.offsets) and np.array_equal(t2.reshape(-1), exp2.tokens.view(np.int32).reshape(-1))
+        prof2 = ctx2.profile()
+        if longest == 9:    # one parked match per position, at most 32 in a window: held, whatever the windows' lengths
+            assert prof2["deferred"] == [0] * 4 and prof2["window_handed"] == [0] * 10, prof2
+        else:               # "あ" * 33 and longer: 22 parked matches per position
+            assert prof2["window_handed"][2] >= 1 and prof2["deferred"][0] >= 1, prof2
+            assert [k for k, v in enumerate(prof2["window_handed"]) if v and k != 2] in ([], [8] if window_kib == "9" else []), prof2
 
 
 @pytest.mark.parametrize("pool,window_kib", [("40:4:40", "12"), ("0", "12"), ("0", "0")])
