@@ -821,6 +821,70 @@ int kgpu_encode_device_spans(kgpu_ctx *c, const kgpu_vocab *v, const uint8_t *d_
                              int32_t *d_ids, uint64_t id_capacity, uint64_t width, int32_t pad_id, uint64_t *d_id_offsets,
                              kgpu_span *d_spans, int32_t *d_token_index);
 
+/* ---- model inputs: ragged id sequences packed into padded rows [R, max_length] with token_type_ids and an attention_mask -- sentence pairs,
+ * truncation, overlapping stride windows (what a BERT-family model takes: `[CLS] a [SEP]` or `[CLS] a [SEP] b [SEP]`; the truncation and template
+ * processing of the `tokenizers` library; NOT an output of the reference) ----
+ * The pack step takes the RAGGED output of kgpu_encode_device or kgpu_encode_device_spans -- ids, their offsets, optionally their spans and token
+ * indices -- and moves it; it looks at no id.  A sample is one sequence a, or a pair a, b.  ns = 2 for a single, 3 for a pair; room = max_length - ns;
+ * La, Lb are the lengths after rule 1 (Lb = 0 for a single).  Sample i's rows are row_offsets[i] .. row_offsets[i + 1] of the outputs.
+ *  1. Trim.  trim_front and trim_back are 0 or 1 each: that many elements are dropped from the front and from the back of EVERY input sequence, so a
+ *     vocabulary that adds bos / eos itself is packed without a second handle.  A sequence shorter than its trims has length 0.
+ *  2. Layout of a row over the slices a[as .. as + al) and b[bs .. bs + bl).  Single: cls_id, the a-slice, sep_id.  Pair: cls_id, the a-slice, sep_id,
+ *     the b-slice, sep_id.  The remaining slots up to max_length hold pad_id.  token_type_ids is 1 on the b-slice and on the last sep_id of a pair, 0
+ *     elsewhere, the pad included.  attention_mask is 1 on everything before the pad, 0 on the pad.  Spans and token indices of slice elements are
+ *     copied from the input element; every special and every pad slot gets {0, 0, 0, 0} and -1, exactly as in rule 1 of "ids with spans".
+ *  3. Fits.  La + Lb <= room: one row with the whole of a and b, status KGPU_PACK_OK.
+ *  4. KGPU_PACK_LONGEST_FIRST when it does not fit: one row, status KGPU_PACK_CUT, both slices start at 0.  Single: al = room.  Pair: let s1 <= s2 be
+ *     the two lengths.  If s1 > room then s2 = s1, else s2 = max(s1, room - s1).  If s1 + s2 > room then s1 = room / 2 and s2 = s1 + room % 2.  They
+ *     go back to the sides they came from: the side that was not longer is s1; with equal lengths a is s1.  stride is ignored; KGPU_PACK_WINDOWS
+ *     together with this strategy is KGPU_ERR_INVALID_ARG.
+ *  5. KGPU_PACK_ONLY_FIRST / KGPU_PACK_ONLY_SECOND when it does not fit: a (b) is cut, the other side is FIXED and kept whole.  A single under
+ *     ONLY_FIRST behaves as a pair with an empty fixed side; a single under ONLY_SECOND is KGPU_ERR_INVALID_ARG at the call.  w = room - the fixed
+ *     side's length.  If w < 1, or KGPU_PACK_WINDOWS is set and stride >= w, the sample gets ZERO rows and status KGPU_PACK_NO_ROOM; the batch goes
+ *     on.  Otherwise the status is KGPU_PACK_CUT.  Without KGPU_PACK_WINDOWS: one row, the slice [0, w) of the cut side.  With it: window k starts at
+ *     k (w - stride) and is min(w, L - start) long, L the cut side's length; the last window is the first one that reaches L.  One row per window,
+ *     in order, and every window repeats the fixed side whole.  Consecutive windows share `stride` elements.
+ *  6. Arguments.  max_length is ns + 1 .. 65536; stride < max_length - ns; the flags and the strategy are known ones; the trims are 0 or 1;
+ *     opts.size is at least the struct's.  Anything else is KGPU_ERR_INVALID_ARG, as are a null or misaligned pointer (ids, token indices and the
+ *     three int32 outputs: 4 bytes; offsets: 8; spans: 16), spans out without spans in, and token indices out without token indices in.
+ *  7. Capacity.  The row outputs have row_capacity rows.  row_offsets (n + 1) and status (n) are always written.  When row_offsets[n] > row_capacity
+ *     NOTHING is written to any row array and the call (the sync) returns KGPU_ERR_CAPACITY with the exact row count: the protocol of "vocabulary
+ *     ids", rule 5.  No slot at or beyond row_capacity x max_length is ever touched.
+ *  8. Input offsets are taken as they are (they need not start at 0, and sample i + 1 need not begin where sample i ends).  An a or b range that runs
+ *     backwards or past n_ids_in makes the call (the sync) return KGPU_ERR_INVALID_ARG: it is checked where the row counts are made and never used
+ *     as an address; the row arrays are unspecified then.  Element values are copied, never interpreted.
+ * Both id arrays and the input spans / token indices are indexed by the same offsets: element e of spans_in / tix_in belongs to ids_a[e] (ids_b[e]),
+ * all of n_ids_in entries.  off_b may point into the array off_a points into (2 n sequences encoded as one batch: off_b = off_a + n). */
+#define KGPU_PACK_WINDOWS 1u        /* flags: rule 5's stride windows */
+#define KGPU_PACK_LONGEST_FIRST 0u  /* strategy */
+#define KGPU_PACK_ONLY_FIRST 1u
+#define KGPU_PACK_ONLY_SECOND 2u
+#define KGPU_PACK_OK 0              /* per-sample status (uint8) */
+#define KGPU_PACK_CUT 1
+#define KGPU_PACK_NO_ROOM 2
+typedef struct kgpu_pack_opts {
+    uint32_t size;        /* sizeof(kgpu_pack_opts): fields may be appended later */
+    uint32_t flags;       /* KGPU_PACK_WINDOWS */
+    uint32_t strategy;    /* KGPU_PACK_LONGEST_FIRST / ONLY_FIRST / ONLY_SECOND */
+    uint32_t max_length;
+    uint32_t stride;
+    int32_t cls_id, sep_id, pad_id;
+    uint32_t trim_front, trim_back;
+} kgpu_pack_opts;
+/* The rule on the host, in plain C++: no device, no dictionary; the definition of the device results (both run the same statements).  All arrays in
+ * host memory; ids_b / off_b NULL: singles.  spans_in, tix_in, type_ids, mask, spans, tix may each be NULL (rule 6 pairs them).  *n_rows (may be NULL):
+ * row_offsets[n], written or needed. */
+int kgpu_pack_host(const kgpu_pack_opts *o, uint64_t n, const int32_t *ids_a, const uint64_t *off_a, const int32_t *ids_b, const uint64_t *off_b,
+                   uint64_t n_ids_in, const kgpu_span *spans_in, const int32_t *tix_in, int32_t *input_ids, int32_t *type_ids, int32_t *mask,
+                   kgpu_span *spans, int32_t *tix, uint64_t row_capacity, uint64_t *row_offsets, uint8_t *status, uint64_t *n_rows);
+/* Device-resident, three launches on c's stream whatever the batch holds: the row counts (one lane per sample), their scan into d_row_offsets, the
+ * rows (one wavefront per output row).  Every d_* pointer is a device pointer on the context's device.  It takes the context's one pending
+ * render-kind slot; kgpu_ctx_sync_lines waits and reports row_offsets[n], written or needed (rules 7 and 8 give its errors). */
+int kgpu_pack_device(kgpu_ctx *c, const kgpu_pack_opts *o, uint64_t n, const int32_t *d_ids_a, const uint64_t *d_off_a, const int32_t *d_ids_b,
+                     const uint64_t *d_off_b, uint64_t n_ids_in, const kgpu_span *d_spans_in, const int32_t *d_tix_in, int32_t *d_input_ids,
+                     int32_t *d_type_ids, int32_t *d_mask, kgpu_span *d_spans, int32_t *d_tix, uint64_t row_capacity, uint64_t *d_row_offsets,
+                     uint8_t *d_status);
+
 #ifdef __cplusplus
 }
 #endif

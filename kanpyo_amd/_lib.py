@@ -41,11 +41,15 @@ SYMBOLS = [
     "kgpu_normalize_host_aligned", "kgpu_normalize_batch_aligned", "kgpu_normalize_text_aligned", "kgpu_normalize_device_aligned", "kgpu_ctx_sync_normalize_aligned",
     "kgpu_source_spans_host", "kgpu_source_spans_device", "kgpu_source_spans_batch",
     "kgpu_encode_device_spans",
+    "kgpu_pack_host", "kgpu_pack_device",
 ]
 KGPU_VOCAB_ADD_BOS, KGPU_VOCAB_ADD_EOS = 1, 2
 KGPU_COUNTS_DEFAULT_SLOTS, KGPU_COUNTS_DEFAULT_KEY_BYTES = 1 << 22, 256 << 20
 KGPU_WORDS_SURFACE = -1
 KGPU_WORDS_ALL, KGPU_WORDS_DROP, KGPU_WORDS_KEEP = 0, 1, 2
+KGPU_PACK_WINDOWS = 1
+KGPU_PACK_LONGEST_FIRST, KGPU_PACK_ONLY_FIRST, KGPU_PACK_ONLY_SECOND = 0, 1, 2
+KGPU_PACK_OK, KGPU_PACK_CUT, KGPU_PACK_NO_ROOM = 0, 1, 2
 
 
 def normalize_form(form) -> int:
@@ -171,6 +175,11 @@ class WordpieceInfo(C.Structure):  # kgpu_wordpiece_info: read with its size, fi
         "cont_words", "cont_table_slots", "cont_key_bytes", "rows_whole", "rows_split", "rows_unk", "row_piece_ids", "max_initial_bytes", "max_cont_bytes")]
 
 
+class PackOpts(C.Structure):  # kgpu_pack_opts
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("strategy", C.c_uint32), ("max_length", C.c_uint32), ("stride", C.c_uint32),
+                ("cls_id", C.c_int32), ("sep_id", C.c_int32), ("pad_id", C.c_int32), ("trim_front", C.c_uint32), ("trim_back", C.c_uint32)]
+
+
 class Work(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("sentences", "B", "C", "T", "N", "E", "K")]
 
@@ -287,6 +296,9 @@ def lib():
         L.kgpu_debug_wordpiece_table.argtypes = [vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.c_uint64, C.c_uint64, C.POINTER(WordsSpec), vp, vp, C.c_uint64,
                                                  C.POINTER(VocabOpts), C.POINTER(WordpieceOpts), vp, vp, vp, vp, vp, vp, vp, C.POINTER(WordpieceInfo)]
         L.kgpu_encode_device_spans.argtypes = [vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, vp, C.c_uint64, C.c_uint64, C.c_int32, vp, vp, vp]
+        pack = [C.POINTER(PackOpts), C.c_uint64, vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, vp, vp]
+        L.kgpu_pack_host.argtypes = pack + [C.POINTER(C.c_uint64)]
+        L.kgpu_pack_device.argtypes = [vp] + pack
         L.kgpu_debug_wordpiece_split_ends.argtypes = [vp, vp, C.c_uint64, C.POINTER(WordpieceOpts), C.c_int32, vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, C.POINTER(C.c_uint64)]
         L.kgpu_debug_wordpiece_split.argtypes = [vp, vp, C.c_uint64, C.POINTER(WordpieceOpts), C.c_int32, vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.POINTER(C.c_uint64)]
         L.kgpu_debug_counts_order.argtypes = [vp, vp, vp, C.c_uint64] + L.kgpu_counts_read.argtypes[1:]

@@ -28,7 +28,7 @@ wakati's.  A line that is not UTF-8 ends the run with status 101, its 1-based li
 frequency table is worse than none; with --skip-invalid such lines are skipped, their numbers go to stderr and the status is 0.
 
 `python -m kanpyo_amd encode [INPUT] -c DICT --vocab FILE [--wordpiece [--prefix S] [--max-word-chars N]] [--field N | --base-form | --reading | --pronunciation] [--drop POS[,POS...] | --keep POS[,POS...]]
-[--unk WORD] [--bos WORD] [--eos WORD] [--offsets] [--split host|device] [--skip-invalid]`: NOT a subcommand of the reference either -- every input line becomes
+[--unk WORD] [--bos WORD] [--eos WORD] [--offsets] [--max-length N [--stride S] [--truncation T] [--pair]] [--split host|device] [--skip-invalid]`: NOT a subcommand of the reference either -- every input line becomes
 one output line, the vocabulary ids of its words in decimal, separated by one space (kgpu_encode_batch / kgpu_encode_text; the decimal text is made
 on the host).  FILE has one word per line, line k (0-based) is id k: `count ... | cut -f2` makes one.  --unk (default "<unk>"), --bos and --eos name
 words that must be in the file (exit status 2 otherwise); a word outside the file gets --unk's id, --bos / --eos put theirs around every line's ids.
@@ -37,7 +37,11 @@ on stdout; with --skip-invalid such a line prints its bos / eos only.  --offsets
 output line PER ID, `id\tstart\tend\ttoken_index\ttext`, and `EOS` behind each input line -- start and end are character positions in the line as it was
 given (through --normalize's edit records), text is those characters, token_index the id's token among the line's records; bos and eos print
 `id\t0\t0\t-1\t`.  Ids, spans and indices are made on the device (Vocab.encode_tensor(return_spans=True)), the text is formatted on the host -- which needs
-the lines there: stdin's blocks are split on the host whatever --split says.
+the lines there: stdin's blocks are split on the host whatever --split says.  --max-length N (include/kanpyo_gpu.h, "model inputs") prints MODEL INPUT
+ROWS instead: one output line per row, `sample\tids...` up to the pad, sample the 0-based number of the input line the row belongs to -- a line that does not
+fit N ids with its specials is cut by --truncation (only_second, the default, only_first, longest_first) and, but for longest_first, cut into windows that
+share --stride ids (default 0).  With --pair an input line is `a<TAB>b` (a line without a tab has an empty b).  The rows are made on the device
+(Vocab.encode_pairs_tensor); the specials are --bos and --eos, which this form needs; stdin's blocks are split on the host.
 
 `--normalize {none,nfc,nfkc}` (default none) on `tokenize`, `wakati`, `count`, `encode` and `graphviz`: the input -- INPUT, or stdin's lines with either
 --split -- is normalised on the device first (include/kanpyo_gpu.h, "text normalisation"), and what is printed are the surfaces and words of the
@@ -261,7 +265,13 @@ def count(args, stdin, stdout) -> int:
 
 
 def encode(args, stdin, stdout) -> int:
-    if args.offsets:   # (encode_tensor's tensors: torch ships its own HIP runtime, which has to be the process's one -- loaded before the library is)
+    if args.max_length is None and (args.stride is not None or args.truncation is not None or args.pair):
+        print("kanpyo_amd: --stride, --truncation and --pair go with --max-length", file=sys.stderr)
+        return 2
+    if args.max_length is not None and (args.offsets or args.bos is None or args.eos is None):
+        print("kanpyo_amd: --max-length needs --bos and --eos (the rows' specials) and does not go with --offsets", file=sys.stderr)
+        return 2
+    if args.offsets or args.max_length is not None:   # (encode_tensor's tensors: torch ships its own HIP runtime, which has to be the process's one -- loaded before the library is)
         import torch  # noqa: F401
     from .vocab import Vocab
 
@@ -298,6 +308,22 @@ def encode(args, stdin, stdout) -> int:
             lines.append(b"".join(rows) + b"EOS\n")
         return lines, status.cpu().numpy()
 
+    line0 = [0]   # input lines in the blocks before this one: the rows' sample numbers run on
+
+    def model_rows(utf8, offs):
+        src, so = utf8.tobytes(), offs.tolist()
+        lines = [src[so[i] : so[i + 1]] for i in range(len(so) - 1)]
+        first, second = lines, None
+        if args.pair:
+            cut = [ln.partition(b"\t") for ln in lines]
+            first, second = [c[0] for c in cut], [c[2] for c in cut]
+        r = v.encode_pairs_tensor(first, second, max_length=args.max_length, stride=args.stride or 0, truncation=args.truncation or "only_second")
+        ids, mask, sample = r["input_ids"].cpu().numpy(), r["attention_mask"].cpu().numpy(), r["sample_of_row"].cpu().tolist()
+        rows = [b"%d\t" % (line0[0] + sample[k]) + " ".join(map(str, ids[k][mask[k] == 1].tolist())).encode() + b"\n" for k in range(ids.shape[0])]
+        line0[0] += len(lines)
+        st = r["sentence_status"].cpu().numpy()
+        return rows, (np.maximum(st[: len(lines)], st[len(lines):]) if args.pair else st)
+
     def listing(result):
         out.extend(b"".join(result[0]))
         if args.skip_invalid:
@@ -314,13 +340,14 @@ def encode(args, stdin, stdout) -> int:
             stdout.flush()
             out.clear()
 
-    if args.offsets:
+    if args.offsets or args.max_length is not None:
         from .tokenizer import split_lines
 
-        results = _results(args, stdin, with_offsets, lambda block: with_offsets(*split_lines(block)))
+        call = with_offsets if args.offsets else model_rows
+        results = _results(args, stdin, call, lambda block: call(*split_lines(block)))
     else:
         results = _results(args, stdin, v.encode_packed, v.encode_text)
-    if _each_checked(results, args.skip_invalid, listing if args.offsets else decimal):
+    if _each_checked(results, args.skip_invalid, listing if args.offsets or args.max_length is not None else decimal):
         return PANIC_STATUS   # nothing has been printed
     stdout.write(bytes(out))
     stdout.flush()
@@ -457,7 +484,11 @@ def parse_args(argv=None):
                        ("--wordpiece", dict(action="store_true", help="The vocabulary is a WordPiece list (a BERT vocab.txt): a word outside it is cut into its longest listed pieces")),
                        ("--prefix", dict(default=None, help="With --wordpiece: the continuation prefix, at most 8 bytes [default: ##]")),
                        ("--max-word-chars", dict(type=_top, default=None, help="With --wordpiece: a longer word gets the --unk id [default: 100]")),
-                       ("--offsets", dict(action="store_true", help="One output line per id: id, start, end (characters of the line as given), token index, text; EOS behind each input line"))],
+                       ("--offsets", dict(action="store_true", help="One output line per id: id, start, end (characters of the line as given), token index, text; EOS behind each input line")),
+                       ("--max-length", dict(type=_top, default=None, help="Print model input rows of at most N ids, specials included: one line per row, the input line's number and the ids up to the pad")),
+                       ("--stride", dict(type=_field, default=None, help="With --max-length: the ids consecutive windows of a cut line share [default: 0]")),
+                       ("--truncation", dict(choices=["only_second", "only_first", "longest_first"], default=None, help="With --max-length: which side is cut [default: only_second]")),
+                       ("--pair", dict(action="store_true", help="With --max-length: an input line is a<TAB>b, a sentence pair"))],
                   skip_invalid="A line that is not UTF-8 prints its bos / eos only instead of ending the run with status 101")
     args = p.parse_args(argv)
     if args.command is None:   # src/bin/kanpyo.rs:173: no subcommand == tokenize from stdin, default dictionary

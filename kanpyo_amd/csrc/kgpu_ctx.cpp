@@ -505,7 +505,7 @@ int HostReport::arm() {
     if (!ev) HIPCHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     unsigned long long *h = (unsigned long long *)ctl.h;
     h[0] = 0; h[1] = 0;
-    two_sizes = false; cap1 = 0; word1 = 0;
+    two_sizes = false; cap1 = 0; word1 = 0; bad_what = nullptr;
     return KGPU_OK;
 }
 int HostReport::record(hipStream_t stream, uint64_t cap_) {
@@ -593,7 +593,8 @@ extern "C" int kgpu_ctx_sync_lines(kgpu_ctx *c, uint64_t *n_bytes) {
         return KGPU_OK;
     }
     if (h[1]) {
-        set_error("kgpu_ctx_sync_lines: a token record names a class, morph id or surface outside the dictionary or its sentence");
+        if (c->lines_report.bad_what) set_error("kgpu_ctx_sync_lines: %s", c->lines_report.bad_what);
+        else set_error("kgpu_ctx_sync_lines: a token record names a class, morph id or surface outside the dictionary or its sentence");
         return KGPU_ERR_INVALID_ARG;
     }
     if (need > c->lines_report.cap) {

@@ -11,6 +11,7 @@
 
 #include "../../include/kanpyo_gpu.h"
 #include "kgpu_normalize_core.h"
+#include "kgpu_pack_core.h"
 
 namespace kgpu {
 
@@ -359,6 +360,27 @@ struct SpansArgs {
     kgpu_span *spans; uint64_t span_cap;   // no store at or behind span_cap
 };
 int launch_source_spans(const SpansArgs &a, void *stream);
+// The model inputs of a batch's ragged ids (kgpu_pack.hip; include/kanpyo_gpu.h, "model inputs"): padded rows [R, max_length] of ids, type ids, mask and,
+// when asked for, spans and token indices.  b: n, sent_len (each sample's rows, then their offsets), text_offsets (the caller's row_offsets) and host_ctl
+// ([0] the rows, [1] an input range out of bounds) alone are used.
+struct PackArgs {
+    RecordsBatch b;
+    PackRule r;                        // kgpu_pack_core.h: the options, and whether the samples are pairs
+    const int32_t *ids_a, *ids_b;     // n_ids_in entries each (ids_b: pairs only)
+    const uint64_t *off_a, *off_b;     // n + 1 each
+    uint64_t n_ids_in;
+    const kgpu_span *spans_in;         // n_ids_in entries, or null
+    const int32_t *tix_in;             // n_ids_in entries, or null
+    int32_t *input_ids, *type_ids, *mask, *tix;   // row_cap x max_length each; all but input_ids may be null
+    kgpu_span *spans;                  // row_cap x max_length, or null
+    uint64_t row_cap;                  // nothing is stored when sent_len[n] > row_cap
+    uint8_t *status;                   // n
+};
+int launch_pack(const PackArgs &a, void *stream);
+// kgpu_pack_rule.cpp (HIP-free, compiles alone): rule 6 of "model inputs" for both forms of the call -> KGPU_OK, or KGPU_ERR_INVALID_ARG with the error set
+int pack_check_args(const char *who, const kgpu_pack_opts *o, uint64_t n, const void *ids_a, const void *off_a, const void *ids_b, const void *off_b,
+                    uint64_t n_ids_in, const void *spans_in, const void *tix_in, const void *input_ids, const void *type_ids, const void *mask,
+                    const void *spans, const void *tix, uint64_t row_capacity, const void *row_offsets, const void *status);
 // kgpu_normalize_table.cpp (HIP-free, compiles alone): the tables in host memory, their sizes in bytes, and one line on the host -> its status; out_len is
 // the normalised length, and the bytes are in `out` when they fit `capacity` (the line itself where the status is not KGPU_SENT_OK)
 struct NormTableSizes { size_t stage1, stage2, dec, pool, comp_key, comp_val; };

@@ -68,6 +68,7 @@ struct HostReport {
     // in word1 for kgpu_ctx_sync_normalize_aligned; arm() makes the report an ordinary one again
     bool two_sizes = false;
     uint64_t cap1 = 0, word1 = 0;
+    const char *bad_what = nullptr;              // what a raised word [1] means when it is not a bad token record (the pack: an input range); arm() clears it
     int arm();                                   // before the launch: a previous use waited out (its words are about to be reset), block and event there, words zero
     unsigned long long *dev() const { return (unsigned long long *)ctl.d; }   // what the launch is given
     int record(hipStream_t stream, uint64_t cap);   // behind the launch

@@ -101,6 +101,26 @@ class DeviceContext(Handle):
             C.c_void_p(d_edits) if d_edits else None, C.c_void_p(d_edit_offsets) if d_edit_offsets else None, C.c_void_p(d_ids), id_capacity, width, pad_id,
             C.c_void_p(d_id_offsets), C.c_void_p(d_spans), C.c_void_p(d_token_index) if d_token_index else None))
 
+    def pack(self, opts, n: int, d_ids_a: int, d_off_a: int, n_ids_in: int, d_input_ids: int, row_capacity: int, d_row_offsets: int, d_status: int,
+             d_ids_b: int = 0, d_off_b: int = 0, d_type_ids: int = 0, d_mask: int = 0, d_spans_in: int = 0, d_tix_in: int = 0, d_spans: int = 0, d_tix: int = 0):
+        """kgpu_pack_device: enqueue the model inputs (include/kanpyo_gpu.h, "model inputs") of ragged ids an encode left in HBM -- rows [R, max_length]
+        of input_ids and, where a pointer is given, token_type_ids, attention_mask (int32), spans (16-byte kgpu_span, 16-byte aligned) and token
+        indices (int32), row_capacity rows each; d_row_offsets: n + 1 uint64, d_status: n bytes.  opts: pack.pack_opts(...).  d_ids_b / d_off_b:
+        the second sequences of pairs (0: singles; d_off_b may be d_off_a + 8 n when 2 n sequences were encoded as one batch).  d_spans_in /
+        d_tix_in: what encode_spans left beside the ids.  sync_lines (try_sync_lines) waits for it and returns the rows, written or needed."""
+        p = lambda v: C.c_void_p(v) if v else None   # noqa: E731
+        _lib.check(_lib.lib().kgpu_pack_device(
+            self._h, C.byref(opts), n, p(d_ids_a), p(d_off_a), p(d_ids_b), p(d_off_b), n_ids_in, p(d_spans_in), p(d_tix_in), p(d_input_ids), p(d_type_ids),
+            p(d_mask), p(d_spans), p(d_tix), row_capacity, p(d_row_offsets), p(d_status)))
+
+    def try_sync_lines(self) -> tuple:
+        """-> (fits, units): sync_lines without the exception for a capacity that was too small (nothing was written then)."""
+        n = C.c_uint64(0)
+        rc = _lib.lib().kgpu_ctx_sync_lines(self._h, C.byref(n))
+        if rc != _lib.KGPU_ERR_CAPACITY:
+            _lib.check(rc)
+        return rc == _lib.KGPU_OK, int(n.value)
+
     def normalize(self, d_utf8: int, d_offsets: int, n: int, d_text: int, text_capacity: int, d_text_offsets: int, d_status: int, form="NFKC"):
         """kgpu_normalize_device: enqueue NFC / NFKC of n lines in HBM -> the normalised lines packed in d_text (up to 11 times the input's bytes;
         no overlap with d_utf8), their uint64 offsets in d_text_offsets (n + 1) and a status byte per line in d_status: the buffers tokenize takes

@@ -248,6 +248,69 @@ class Vocab(Handle):
         out = d_ids, torch.clamp(d_ioff[1:] - d_ioff[:-1], max=int(width)), d_st[:n]
         return out + (d_spans, d_tix) if return_spans else out
 
+    def encode_pairs_tensor(self, first: Sequence, second: Sequence = None, max_length: int = 512, stride: int = 0, truncation="only_second", windows: bool = True,
+                            pad_id: int = 0, cls_id=None, sep_id=None, normalize=None, return_spans: bool = False) -> dict:
+        """Model inputs on the device (include/kanpyo_gpu.h, "model inputs"): ONE encode_tensor batch over first + second (ragged; with spans when asked),
+        then DeviceContext.pack over what it left in device memory -- rows `[cls] a [sep]` or `[cls] a [sep] b [sep]` of max_length slots, a sample that
+        does not fit cut by `truncation` ("only_second", "only_first": the other side is kept whole; "longest_first") and, with windows=True, cut into
+        overlapping windows that share `stride` elements, one row each.  No id passes through host memory.
+        -> dict of tensors on the device: input_ids, token_type_ids, attention_mask (int32 [R, max_length]); row_offsets (int64 [n + 1]: sample i's rows
+        are row_offsets[i] .. row_offsets[i + 1]); sample_of_row (int64 [R]: the overflow_to_sample_mapping of other libraries); status (uint8 [n]: 0
+        whole, 1 cut, 2 no room -- zero rows); sentence_status (uint8, one per sentence of first + second: encode_tensor's); and with return_spans
+        spans (int32 [R, max_length, 4]) and token_index (int32 [R, max_length]) as encode_tensor(return_spans=True) gives them, zeros and -1 on specials
+        and pad.  With a normalisation form the spans are in SOURCE coordinates: the encode maps them, the pack only copies.
+        cls_id / sep_id default to this Vocab's bos / eos ids (ValueError when it has none and none is given); a bos / eos the Vocab adds itself is trimmed
+        from every sequence before it is packed.  second=None: singles ("only_second" is then "only_first": the one sequence is what is cut).
+        windows=True with "longest_first" is not defined (the library refuses it): windows is taken as False there."""
+        import torch
+
+        from .pack import pack_opts
+
+        pair = second is not None
+        first = list(first)
+        second = list(second) if pair else []
+        if pair and len(second) != len(first):
+            raise ValueError("first and second have the same number of entries")
+        cls_id = self.bos_id if cls_id is None else cls_id
+        sep_id = self.eos_id if sep_id is None else sep_id
+        if cls_id is None or sep_id is None:
+            raise ValueError("the Vocab adds no bos / eos of its own: give cls_id and sep_id")
+        if truncation == "only_second" and not pair:
+            truncation = "only_first"
+        if truncation == "longest_first":
+            windows = False
+        opts = pack_opts(max_length, stride, truncation, windows, cls_id, sep_id, pad_id, trim_front=1 if self.bos_id is not None else 0,
+                         trim_back=1 if self.eos_id is not None else 0)
+        n = len(first)
+        enc = self.encode_tensor(first + second, normalize=normalize, return_spans=return_spans)
+        ids, ioff, sent_status = enc[0], enc[1], enc[2]
+        n_ids = int(ids.numel())
+        dev, ML = ids.device, int(max_length)
+        d_roff = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        d_st = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        cap = n + n_ids // max(1, ML - 3 - int(stride)) + 8
+        with self._ctx_lock:
+            ctx = self._ctx
+            while True:   # (a row count beyond the guess: once more with the count the device reports)
+                rows = {k: torch.empty((cap, ML), dtype=torch.int32, device=dev) for k in ("input_ids", "token_type_ids", "attention_mask")}
+                if return_spans:
+                    rows["spans"] = torch.empty((cap, ML, 4), dtype=torch.int32, device=dev)
+                    rows["token_index"] = torch.empty((cap, ML), dtype=torch.int32, device=dev)
+                torch.cuda.synchronize(dev)
+                ctx.pack(opts, n, ids.data_ptr(), ioff.data_ptr(), n_ids, rows["input_ids"].data_ptr(), cap, d_roff.data_ptr(), d_st.data_ptr(),
+                         d_ids_b=ids.data_ptr() if pair else 0, d_off_b=ioff.data_ptr() + 8 * n if pair else 0,
+                         d_type_ids=rows["token_type_ids"].data_ptr(), d_mask=rows["attention_mask"].data_ptr(),
+                         d_spans_in=enc[3].data_ptr() if return_spans else 0, d_tix_in=enc[4].data_ptr() if return_spans else 0,
+                         d_spans=rows["spans"].data_ptr() if return_spans else 0, d_tix=rows["token_index"].data_ptr() if return_spans else 0)
+                fits, R = ctx.try_sync_lines()
+                if fits:
+                    break
+                cap = R
+        out = {k: v[:R] for k, v in rows.items()}
+        out["row_offsets"], out["status"], out["sentence_status"] = d_roff, d_st[:n], sent_status
+        out["sample_of_row"] = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=dev), d_roff[1:] - d_roff[:-1], output_size=R)
+        return out
+
     def encode_spans(self, sentences: Sequence, normalize=None) -> List[tuple]:
         """The host-friendly form of encode_tensor(return_spans=True): per sentence (ids int32, spans[SPAN_DTYPE], token_index int32) as numpy arrays.
         The work is encode_tensor's, on the device; only the results are copied back."""
