@@ -73,6 +73,18 @@ def grown(rc: int, caps: tuple, reported: tuple, slack: int = 0):
     return None
 
 
+def device_call(attempt, caps: tuple, slack: int = 0, fixed: bool = False) -> tuple:
+    """One stage of a device-resident call (normalise, tokenize, encode, pack): attempt(*caps) allocates what the capacities size, synchronizes,
+    enqueues and syncs -> (rc, the sizes the sync reported, whatever it allocated).  -> (reported, allocated) of the attempt that fitted; `grown`
+    alone decides whether there is one more.  fixed: the capacities are the caller's (a padded encode) -- KGPU_ERR_CAPACITY raises at once."""
+    while True:
+        rc, reported, made = attempt(*caps)
+        more = _lib.check(rc) if fixed else grown(rc, caps, reported, slack)   # (check returns None)
+        if more is None:
+            return tuple(reported), made
+        caps = more
+
+
 def batch_call(entry, utf8, offsets, dtype, first_capacity, names, slack=0, alloc=np.empty, out=None, capacity=None):
     """One batch entry point: entry(utf8_ptr, offsets_ptr, n, units_ptr, capacity, unit_offsets_ptr, status_ptr, byref(got)) -> rc, the
     arguments in front of or between these bound by the caller.  -> (units[:got], unit_offsets[:n+1], status[:n]).

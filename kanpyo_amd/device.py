@@ -43,11 +43,22 @@ class DeviceContext(Handle):
             self._h, C.c_void_p(d_utf8), C.c_void_p(d_offsets), n, total_bytes, C.c_void_p(d_tokens8), token_capacity,
             C.c_void_p(d_first), C.c_void_p(d_tok_offsets), C.c_void_p(d_status)))
 
+    def _sync(self, entry: str, results: int = 1, raises: bool = True) -> tuple:
+        """The sync family's one body: wait through `entry` -> (fits, its `results` 64-bit results...).  KGPU_ERR_CAPACITY raises like every
+        other failure, or with raises=False gives fits False and the sizes the entry reported."""
+        out = [C.c_uint64(0) for _ in range(results)]
+        rc = getattr(_lib.lib(), entry)(self._h, *map(C.byref, out))
+        if raises or rc != _lib.KGPU_ERR_CAPACITY:
+            _lib.check(rc)
+        return (rc == _lib.KGPU_OK,) + tuple(int(v.value) for v in out)
+
     def sync(self) -> int:
         """Wait for the enqueued batch; returns its dense token count."""
-        n = C.c_uint64(0)
-        _lib.check(_lib.lib().kgpu_ctx_sync(self._h, C.byref(n)))
-        return int(n.value)
+        return self._sync("kgpu_ctx_sync")[1]
+
+    def try_sync(self) -> tuple:
+        """-> (fits, tokens): sync without the exception for a token capacity that was too small."""
+        return self._sync("kgpu_ctx_sync", raises=False)
 
     def format_lines(self, d_utf8: int, d_offsets: int, n: int, d_tokens: int, d_tok_offsets: int, d_text: int, text_capacity: int, d_text_offsets: int):
         """kgpu_format_lines_device: enqueue the `kanpyo tokenize` lines of records a synced batch left in HBM (the handle needs set_features)."""
@@ -64,9 +75,7 @@ class DeviceContext(Handle):
 
     def sync_lines(self) -> int:
         """Wait for the enqueued render (lines or words) or encode; returns its byte count, or the encode's id count."""
-        n = C.c_uint64(0)
-        _lib.check(_lib.lib().kgpu_ctx_sync_lines(self._h, C.byref(n)))
-        return int(n.value)
+        return self._sync("kgpu_ctx_sync_lines")[1]
 
     def count_words(self, counts, d_utf8: int, d_offsets: int, n: int, d_tokens: int, d_tok_offsets: int):
         """kgpu_count_words_device: enqueue the word counts of records a synced batch left in HBM into a WordCounts handle of this context's
@@ -76,9 +85,7 @@ class DeviceContext(Handle):
 
     def sync_count(self) -> int:
         """Wait for the enqueued count; returns the tokens it added.  KgpuError with KGPU_ERR_CAPACITY: some found no room (overflow_tokens)."""
-        n = C.c_uint64(0)
-        _lib.check(_lib.lib().kgpu_ctx_sync_count(self._h, C.byref(n)))
-        return int(n.value)
+        return self._sync("kgpu_ctx_sync_count")[1]
 
     def encode(self, vocab, d_utf8: int, d_offsets: int, n: int, d_tokens: int, d_tok_offsets: int, d_ids: int, id_capacity: int, d_id_offsets: int,
                width: int = 0, pad_id: int = 0):
@@ -115,11 +122,7 @@ class DeviceContext(Handle):
 
     def try_sync_lines(self) -> tuple:
         """-> (fits, units): sync_lines without the exception for a capacity that was too small (nothing was written then)."""
-        n = C.c_uint64(0)
-        rc = _lib.lib().kgpu_ctx_sync_lines(self._h, C.byref(n))
-        if rc != _lib.KGPU_ERR_CAPACITY:
-            _lib.check(rc)
-        return rc == _lib.KGPU_OK, int(n.value)
+        return self._sync("kgpu_ctx_sync_lines", raises=False)
 
     def normalize(self, d_utf8: int, d_offsets: int, n: int, d_text: int, text_capacity: int, d_text_offsets: int, d_status: int, form="NFKC"):
         """kgpu_normalize_device: enqueue NFC / NFKC of n lines in HBM -> the normalised lines packed in d_text (up to 11 times the input's bytes;
@@ -132,17 +135,11 @@ class DeviceContext(Handle):
     def sync_normalize(self) -> int:
         """Wait for the enqueued normalisation; returns its byte count.  KgpuError with KGPU_ERR_CAPACITY: text_capacity was too small (nothing
         was written); try_sync_normalize returns the size instead."""
-        n = C.c_uint64(0)
-        _lib.check(_lib.lib().kgpu_ctx_sync_normalize(self._h, C.byref(n)))
-        return int(n.value)
+        return self._sync("kgpu_ctx_sync_normalize")[1]
 
     def try_sync_normalize(self) -> tuple:
         """-> (fits, bytes): sync_normalize without the exception for a capacity that was too small."""
-        n = C.c_uint64(0)
-        rc = _lib.lib().kgpu_ctx_sync_normalize(self._h, C.byref(n))
-        if rc != _lib.KGPU_ERR_CAPACITY:
-            _lib.check(rc)
-        return rc == _lib.KGPU_OK, int(n.value)
+        return self._sync("kgpu_ctx_sync_normalize", raises=False)
 
     def normalize_aligned(self, d_utf8: int, d_offsets: int, n: int, d_text: int, text_capacity: int, d_text_offsets: int, d_status: int,
                           d_edits: int, edit_capacity: int, d_edit_offsets: int, form="NFKC"):
@@ -155,18 +152,11 @@ class DeviceContext(Handle):
     def sync_normalize_aligned(self) -> tuple:
         """Wait for the enqueued aligned normalisation -> (bytes, edits).  KgpuError with KGPU_ERR_CAPACITY: either capacity was too small
         (nothing was written); try_sync_normalize_aligned returns the sizes instead."""
-        fits, nb, ne = self.try_sync_normalize_aligned()
-        if not fits:
-            _lib.check(_lib.KGPU_ERR_CAPACITY)
-        return nb, ne
+        return self._sync("kgpu_ctx_sync_normalize_aligned", 2)[1:]
 
     def try_sync_normalize_aligned(self) -> tuple:
         """-> (fits, bytes, edits): sync_normalize_aligned without the exception for a capacity that was too small."""
-        nb, ne = C.c_uint64(0), C.c_uint64(0)
-        rc = _lib.lib().kgpu_ctx_sync_normalize_aligned(self._h, C.byref(nb), C.byref(ne))
-        if rc != _lib.KGPU_ERR_CAPACITY:
-            _lib.check(rc)
-        return rc == _lib.KGPU_OK, int(nb.value), int(ne.value)
+        return self._sync("kgpu_ctx_sync_normalize_aligned", 2, raises=False)
 
     def source_spans(self, d_tokens: int, d_tok_offsets: int, n: int, d_edits: int, d_edit_offsets: int, d_spans: int, span_capacity: int):
         """kgpu_source_spans_device: enqueue the source spans (16-byte kgpu_span, d_spans[k] for d_tokens[k]; d_spans 16-byte aligned) of records a
@@ -182,9 +172,7 @@ class DeviceContext(Handle):
 
     def sync_split(self) -> tuple:
         """Wait for the enqueued split; returns (n_lines, n_bytes): d_offsets holds n_lines + 1 entries, d_out n_bytes bytes."""
-        n, b = C.c_uint64(0), C.c_uint64(0)
-        _lib.check(_lib.lib().kgpu_ctx_sync_split(self._h, C.byref(n), C.byref(b)))
-        return int(n.value), int(b.value)
+        return self._sync("kgpu_ctx_sync_split", 2)[1:]
 
     def set_profiling(self, mode: int):
         _lib.check(_lib.lib().kgpu_ctx_set_profiling(self._h, int(mode)))

@@ -25,12 +25,28 @@ from typing import List, Sequence
 import numpy as np
 
 from . import _lib
-from ._calls import SPAN_DTYPE, Handle, batch_call, block_call, pack_sentences, ptr, struct_dict
+from ._calls import SPAN_DTYPE, Handle, batch_call, block_call, device_call, pack_sentences, ptr, struct_dict
 from .device import DeviceContext
 
 
 def _word_bytes(w) -> bytes:
     return w.encode("utf-8") if isinstance(w, str) else bytes(w)
+
+
+def _stage(dev, alloc, enqueue, wait, caps: tuple, slack: int = 0, fixed: bool = False) -> tuple:
+    """One stage of encode_tensor / encode_pairs_tensor over device_call.  An attempt: alloc(*caps) -> the buffers the capacities size, ONE
+    torch.cuda.synchronize (they are ready before the library's stream uses them), enqueue(buffers, *caps), wait() -> (fits, sizes...).
+    -> (sizes, buffers) of the attempt that fitted."""
+    import torch
+
+    def attempt(*caps):
+        made = alloc(*caps)
+        torch.cuda.synchronize(dev)
+        enqueue(made, *caps)
+        fits, *reported = wait()
+        return _lib.KGPU_OK if fits else _lib.KGPU_ERR_CAPACITY, reported, made
+
+    return device_call(attempt, caps, slack, fixed)
 
 
 def wordpiece_opts(prefix="##", max_word_chars=100) -> "_lib.WordpieceOpts":
@@ -159,6 +175,7 @@ class Vocab(Handle):
 
         if width is not None and int(width) < 1:
             raise ValueError("width is 1 or more (None: ragged)")
+        width = None if width is None else int(width)
         utf8, offs = pack_sentences(sentences)
         n, total = offs.size - 1, int(offs[-1])
         with self._ctx_lock:
@@ -168,85 +185,56 @@ class Vocab(Handle):
                 self._ctx = DeviceContext(self._tokenizer)
             ctx = self._ctx
             dev = torch.device("cuda", self._device)
+            empty = partial(torch.empty, device=dev)
             d_utf8 = torch.from_numpy(np.concatenate([utf8, np.zeros(16, dtype=np.uint8)])).to(dev)
             d_off = torch.from_numpy(offs.view(np.int64)).to(dev)
             form = self._normalize if normalize is None else _lib.normalize_form(normalize)
             d_nst = d_edits = d_eoff = None
-            if form is not None and return_spans:   # ... with the lines' edit records, for the way back; either capacity too small grows once
-                d_nst = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
-                d_noff = torch.empty(n + 1, dtype=torch.int64, device=dev)
-                d_eoff = torch.empty(n + 1, dtype=torch.int64, device=dev)
-                ncap, ecap = total * 2 + 64, total // 8 + 64
-                while True:
-                    d_norm = torch.zeros(ncap + 16, dtype=torch.uint8, device=dev)
-                    d_edits = torch.empty((ecap, 6), dtype=torch.int32, device=dev)
-                    torch.cuda.synchronize(dev)
-                    ctx.normalize_aligned(d_utf8.data_ptr(), d_off.data_ptr(), n, d_norm.data_ptr(), ncap, d_noff.data_ptr(), d_nst.data_ptr(), d_edits.data_ptr(), ecap,
-                                          d_eoff.data_ptr(), form)
-                    fits, total, n_edits = ctx.try_sync_normalize_aligned()
-                    if fits:
-                        break
-                    ncap, ecap = max(ncap, total), max(ecap, n_edits)
-                d_utf8, d_off = d_norm, d_noff
-            elif form is not None:   # the normalised lines and their offsets take the input's place; a capacity too small grows once, to the size reported
-                d_nst = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
-                d_noff = torch.empty(n + 1, dtype=torch.int64, device=dev)
-                ncap = total * 2 + 64
-                while True:
-                    d_norm = torch.zeros(ncap + 16, dtype=torch.uint8, device=dev)
-                    torch.cuda.synchronize(dev)
-                    ctx.normalize(d_utf8.data_ptr(), d_off.data_ptr(), n, d_norm.data_ptr(), ncap, d_noff.data_ptr(), d_nst.data_ptr(), form)
-                    fits, total = ctx.try_sync_normalize()
-                    if fits:
-                        break
-                    ncap = total
-                d_utf8, d_off = d_norm, d_noff
-            d_toff = torch.empty(n + 1, dtype=torch.int64, device=dev)
-            d_st = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
-            cap = total // 2 + n + 64
-            L = _lib.lib()
-            while True:   # (a token buffer too small: once more with the count the device reports, as tokenize_packed does)
-                d_tok = torch.empty((cap, 6), dtype=torch.int32, device=dev)
-                torch.cuda.synchronize(dev)
-                ctx.tokenize(d_utf8.data_ptr(), d_off.data_ptr(), n, total, d_tok.data_ptr(), cap, d_toff.data_ptr(), d_st.data_ptr())
-                got = C.c_uint64(0)
-                rc = L.kgpu_ctx_sync(ctx._h, C.byref(got))
-                if rc == _lib.KGPU_ERR_CAPACITY and int(got.value) > cap:
-                    cap = int(got.value) + 64
-                    continue
-                _lib.check(rc)
-                break
-            n_tok = int(got.value)
-            d_ioff = torch.empty(n + 1, dtype=torch.int64, device=dev)
-            id_cap = n_tok + n * self._extra if width is None else n * int(width)   # (ragged, a plain Vocab: every record kept, and bos / eos: never too small)
-            while True:   # (a WordPiece Vocab's tokens may give several ids each: once more with the count the device reports)
-                d_ids = torch.empty(max(id_cap, 1), dtype=torch.int32, device=dev) if width is None else torch.empty((n, int(width)), dtype=torch.int32, device=dev)
+            # 1. normalise: the normalised lines and their offsets take the input's place -- with the lines' edit records, a second capacity, for the spans' way back
+            if form is not None:
+                d_nst, d_noff = empty(max(n, 1), dtype=torch.uint8), empty(n + 1, dtype=torch.int64)
+                d_eoff = empty(n + 1, dtype=torch.int64) if return_spans else None
+
+                def norm_alloc(ncap, ecap=None):
+                    return torch.zeros(ncap + 16, dtype=torch.uint8, device=dev), empty((ecap, 6), dtype=torch.int32) if return_spans else None
+
+                def norm_enqueue(made, ncap, ecap=None):
+                    if return_spans:
+                        ctx.normalize_aligned(d_utf8.data_ptr(), d_off.data_ptr(), n, made[0].data_ptr(), ncap, d_noff.data_ptr(), d_nst.data_ptr(), made[1].data_ptr(), ecap,
+                                              d_eoff.data_ptr(), form)
+                    else:
+                        ctx.normalize(d_utf8.data_ptr(), d_off.data_ptr(), n, made[0].data_ptr(), ncap, d_noff.data_ptr(), d_nst.data_ptr(), form)
+
+                (total, *_), (d_utf8, d_edits) = _stage(dev, norm_alloc, norm_enqueue, ctx.try_sync_normalize_aligned if return_spans else ctx.try_sync_normalize,
+                                                                  (total * 2 + 64, total // 8 + 64) if return_spans else (total * 2 + 64,))
+                d_off = d_noff
+            # 2. tokenize (a token buffer too small: once more with the count the device reports and 64, as tokenize_packed does)
+            d_toff, d_st = empty(n + 1, dtype=torch.int64), empty(max(n, 1), dtype=torch.uint8)
+            (n_tok,), d_tok = _stage(dev, lambda cap: empty((cap, 6), dtype=torch.int32),
+                                     lambda d_tok, cap: ctx.tokenize(d_utf8.data_ptr(), d_off.data_ptr(), n, total, d_tok.data_ptr(), cap, d_toff.data_ptr(), d_st.data_ptr()),
+                                     ctx.try_sync, (total // 2 + n + 64,), slack=64)
+            # 3. encode.  Ragged, a plain Vocab: every record kept, and bos / eos: never too small; a WordPiece Vocab's tokens may give several ids each.
+            # Padded: n x width is all there is
+            d_ioff = empty(n + 1, dtype=torch.int64)
+
+            def ids_alloc(id_cap):
+                d_ids = empty(max(id_cap, 1), dtype=torch.int32) if width is None else empty((n, width), dtype=torch.int32)
+                return (d_ids, empty(tuple(d_ids.shape) + (4,), dtype=torch.int32), torch.empty_like(d_ids)) if return_spans else (d_ids,)
+
+            def ids_enqueue(made, id_cap):
+                args = (self, d_utf8.data_ptr(), d_off.data_ptr(), n, d_tok.data_ptr(), d_toff.data_ptr(), made[0].data_ptr(), id_cap, d_ioff.data_ptr())
                 if return_spans:
-                    d_spans = torch.empty(tuple(d_ids.shape) + (4,), dtype=torch.int32, device=dev)
-                    d_tix = torch.empty_like(d_ids)
-                torch.cuda.synchronize(dev)
-                if return_spans:
-                    ctx.encode_spans(self, d_utf8.data_ptr(), d_off.data_ptr(), n, d_tok.data_ptr(), d_toff.data_ptr(), d_ids.data_ptr(), id_cap, d_ioff.data_ptr(),
-                                     d_spans.data_ptr(), d_tix.data_ptr(), d_edits.data_ptr() if d_edits is not None else 0, d_eoff.data_ptr() if d_eoff is not None else 0,
-                                     width=0 if width is None else int(width), pad_id=int(pad_id))
+                    ctx.encode_spans(*args, made[1].data_ptr(), made[2].data_ptr(), d_edits.data_ptr() if d_edits is not None else 0,
+                                     d_eoff.data_ptr() if d_eoff is not None else 0, width=width or 0, pad_id=int(pad_id))
                 else:
-                    ctx.encode(self, d_utf8.data_ptr(), d_off.data_ptr(), n, d_tok.data_ptr(), d_toff.data_ptr(), d_ids.data_ptr(), id_cap, d_ioff.data_ptr(),
-                               width=0 if width is None else int(width), pad_id=int(pad_id))
-                got = C.c_uint64(0)
-                rc = L.kgpu_ctx_sync_lines(ctx._h, C.byref(got))
-                if rc == _lib.KGPU_ERR_CAPACITY and width is None and int(got.value) > id_cap:
-                    id_cap = int(got.value)
-                    continue
-                _lib.check(rc)
-                break
-            count = int(got.value)
+                    ctx.encode(*args, width=width or 0, pad_id=int(pad_id))
+
+            (count,), out = _stage(dev, ids_alloc, ids_enqueue, ctx.try_sync_lines, (n_tok + n * self._extra if width is None else n * width,), fixed=width is not None)
             if d_nst is not None:   # (on the device: the normaliser's 4 shows where the tokenizer said 0)
                 d_st = torch.where((d_st == 0) & (d_nst == _lib.KGPU_SENT_NOT_NORMALIZED), d_nst, d_st)
         if width is None:
-            out = d_ids[:count], d_ioff, d_st[:n]
-            return out + (d_spans[:count], d_tix[:count]) if return_spans else out
-        out = d_ids, torch.clamp(d_ioff[1:] - d_ioff[:-1], max=int(width)), d_st[:n]
-        return out + (d_spans, d_tix) if return_spans else out
+            return (out[0][:count], d_ioff, d_st[:n]) + tuple(t[:count] for t in out[1:])
+        return (out[0], torch.clamp(d_ioff[1:] - d_ioff[:-1], max=width), d_st[:n]) + out[1:]
 
     def encode_pairs_tensor(self, first: Sequence, second: Sequence = None, max_length: int = 512, stride: int = 0, truncation="only_second", windows: bool = True,
                             pad_id: int = 0, cls_id=None, sep_id=None, normalize=None, return_spans: bool = False) -> dict:
@@ -288,24 +276,23 @@ class Vocab(Handle):
         dev, ML = ids.device, int(max_length)
         d_roff = torch.empty(n + 1, dtype=torch.int64, device=dev)
         d_st = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
-        cap = n + n_ids // max(1, ML - 3 - int(stride)) + 8
-        with self._ctx_lock:
-            ctx = self._ctx
-            while True:   # (a row count beyond the guess: once more with the count the device reports)
-                rows = {k: torch.empty((cap, ML), dtype=torch.int32, device=dev) for k in ("input_ids", "token_type_ids", "attention_mask")}
-                if return_spans:
-                    rows["spans"] = torch.empty((cap, ML, 4), dtype=torch.int32, device=dev)
-                    rows["token_index"] = torch.empty((cap, ML), dtype=torch.int32, device=dev)
-                torch.cuda.synchronize(dev)
-                ctx.pack(opts, n, ids.data_ptr(), ioff.data_ptr(), n_ids, rows["input_ids"].data_ptr(), cap, d_roff.data_ptr(), d_st.data_ptr(),
-                         d_ids_b=ids.data_ptr() if pair else 0, d_off_b=ioff.data_ptr() + 8 * n if pair else 0,
-                         d_type_ids=rows["token_type_ids"].data_ptr(), d_mask=rows["attention_mask"].data_ptr(),
-                         d_spans_in=enc[3].data_ptr() if return_spans else 0, d_tix_in=enc[4].data_ptr() if return_spans else 0,
-                         d_spans=rows["spans"].data_ptr() if return_spans else 0, d_tix=rows["token_index"].data_ptr() if return_spans else 0)
-                fits, R = ctx.try_sync_lines()
-                if fits:
-                    break
-                cap = R
+
+        def alloc(cap):
+            rows = {k: torch.empty((cap, ML), dtype=torch.int32, device=dev) for k in ("input_ids", "token_type_ids", "attention_mask")}
+            if return_spans:
+                rows["spans"] = torch.empty((cap, ML, 4), dtype=torch.int32, device=dev)
+                rows["token_index"] = torch.empty((cap, ML), dtype=torch.int32, device=dev)
+            return rows
+
+        def enqueue(rows, cap):
+            self._ctx.pack(opts, n, ids.data_ptr(), ioff.data_ptr(), n_ids, rows["input_ids"].data_ptr(), cap, d_roff.data_ptr(), d_st.data_ptr(),
+                           d_ids_b=ids.data_ptr() if pair else 0, d_off_b=ioff.data_ptr() + 8 * n if pair else 0,
+                           d_type_ids=rows["token_type_ids"].data_ptr(), d_mask=rows["attention_mask"].data_ptr(),
+                           d_spans_in=enc[3].data_ptr() if return_spans else 0, d_tix_in=enc[4].data_ptr() if return_spans else 0,
+                           d_spans=rows["spans"].data_ptr() if return_spans else 0, d_tix=rows["token_index"].data_ptr() if return_spans else 0)
+
+        with self._ctx_lock:   # (a row count beyond the guess: once more with the count the device reports)
+            (R,), rows = _stage(dev, alloc, enqueue, self._ctx.try_sync_lines, (n + n_ids // max(1, ML - 3 - int(stride)) + 8,))
         out = {k: v[:R] for k, v in rows.items()}
         out["row_offsets"], out["status"], out["sentence_status"] = d_roff, d_st[:n], sent_status
         out["sample_of_row"] = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=dev), d_roff[1:] - d_roff[:-1], output_size=R)

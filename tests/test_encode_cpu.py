@@ -15,6 +15,7 @@ import encode_ref as E
 import words_ref as W
 from conftest import ROOT, load_golden
 from kanpyo_amd import _lib
+from record_cases import ref_spec
 from test_count_cpu import golden_records
 from test_words_cpu import fixture_tables
 
@@ -25,10 +26,6 @@ SPECS = {   # tests/test_gpu_words.py's (restated: that module is a GPU module)
     "surface": {}, "field0": {"field": 0}, "field7": {"field": 7}, "field8": {"field": 8}, "field40": {"field": 40},
     "drop": {"drop": ("助詞", "助動詞", "記号")}, "keep": {"keep": ("感動詞",)},
 }
-
-
-def ref_spec(field=None, drop=(), keep=()):
-    return W.Spec(W.SURFACE if field is None else field, W.KEEP if keep else W.DROP if drop else W.ALL, keep or drop)
 
 
 def test_reference_reproduces_the_golden_ids():

@@ -1,7 +1,6 @@
 """The word counts on the device (include/kanpyo_gpu.h, "word counts"; kgpu_count.hip): kgpu_count_batch, kgpu_count_text,
 kgpu_count_words_device, the read-out, the C consumer and `python -m kanpyo_amd count`.  Expected values always come from the oracle's tokens
 (or crafted records) through tests/count_ref.py -- never from the library.  No tolerance: every read-out is compared entry for entry, in order."""
-import ctypes as C
 import os
 import subprocess
 import sys
@@ -14,13 +13,13 @@ import pytest
 import count_ref as CR
 import lines_ref as R
 import words_ref as W
-from conftest import ROOT, fixture_dict_parts, load_golden
-from test_gpu_words import POS_DROP, SPECS, _Env, ref_spec, small_env  # noqa: F401  (small_env: the fixture)
+from conftest import ROOT, load_golden
+from record_cases import (LENGTHS, POS_DROP, SMALL_KEYS, SPECS, _Dev, _Env, _fixture_env, _write_dict_dir, crafted_want, dev_count, env, holds, mixed, ref_spec, small_ctx,  # noqa: F401
+                          small_env)   # (env, mixed, small_ctx, small_env: the fixtures)
 
 pytestmark = pytest.mark.gpu
 
 SMALL = {"table_slots": 1 << 14, "key_bytes": 1 << 20}   # most handles here: a default one holds 320 MiB of device memory
-SMALL_KEYS = ["テスト", "辞書", "形態素"]                 # the keys of small_env's (the fixture's) dictionary, by id
 
 
 def expect(env, utf8, offs, kw, keys, tokens=None, into=None, ids=None):
@@ -30,62 +29,15 @@ def expect(env, utf8, offs, kw, keys, tokens=None, into=None, ids=None):
     return CR.count(utf8, offs, t, to, env.known, env.unk, env.nk, env.nu, ref_spec(**kw), keys, own_records=tokens is None, into=into, ids=ids)
 
 
-def holds(counts, want, overflow=0):
-    """The handle's read-out is the reference's, entry for entry; its info agrees with it."""
-    got = counts.most_common()
-    ref = CR.ordered(want)
-    assert len(got) == len(ref), (len(got), len(ref))
-    assert got == ref, next((i, g, r) for i, (g, r) in enumerate(zip(got, ref)) if g != r)
-    info = counts.info()
-    assert info["tokens_counted"] == sum(want.values()) and info["overflow_tokens"] == overflow, info
-    for top in (1, 3, len(ref), len(ref) + 5):
-        assert counts.most_common(top) == ref[:top]
-    return info
-
-
-@pytest.fixture(scope="module")
-def env():
-    """The 20 000-record dictionary with its display tables, its oracle and its keys by id."""
-    from kanpyo_amd import synth
-
-    sd = synth.build_dict(20000, seed=5)
-    known, unk = synth.feature_tables(sd)
-    e = _Env(sd.dict, known, unk)
-    e.sd, e.keys = sd, synth.record_surfaces(sd)
-    return e
-
-
-@pytest.fixture(scope="module")
-def mixed(env):
-    """2000 cfg 2 sentences and 200 cfg 3 sentences, packed, with the oracle's tokens: computed once, never changed."""
-    from kanpyo_amd import synth
-    from kanpyo_amd.tokenizer import pack_sentences
-
-    utf8, offs = pack_sentences(synth.make_corpus(env.sd, 2000, 3, "cfg2") + synth.make_corpus(env.sd, 200, 4, "cfg3"))
-    exp = env.orc.tokenize_batch(utf8, offs, 8)
-    return utf8, offs, (exp.tokens, exp.offsets)
-
-
 def mixed_want(env, mixed, kw, ids=None):
     utf8, offs, tokens = mixed
     return CR.count(utf8, offs, *tokens, env.known, env.unk, env.nk, env.nu, ref_spec(**kw), env.keys, own_records=True, ids=ids)
 
 
 # ---- 1. the fixture golden -------------------------------------------------------------------------------------------------------------------
-def _fixture_env():
-    from kanpyo_amd import Dict
-    from kanpyo_amd.dictfile import MorphFeatureTable
-
-    p = fixture_dict_parts()
-    known = MorphFeatureTable.from_features([["名詞", f"k{i}", "*"] for i in range(1, len(p["morphs"]) + 1)])
-    unk = MorphFeatureTable.from_features([["未知語", f"u{i}"] for i in range(1, len(p["unk_morphs"]) + 1)])
-    return _Env(Dict.from_parts(**p), known, unk)
-
-
 def test_fixture_golden_host_form_and_c_consumer(tmp_path):
     from kanpyo_amd import _lib
     from kanpyo_amd.dictfile import DictFile
-    from test_gpu_lines import _write_dict_dir
 
     e = _fixture_env()
     cases = load_golden("fixture_counts.json")["cases"]
@@ -143,50 +95,6 @@ def test_mixed_corpus(env, mixed, name):
 
 
 # ---- 3. key shapes: crafted records through the device form ------------------------------------------------------------------------------------
-class _Dev:
-    """A crafted case in device memory, byte for byte: NO spare byte behind the text (an empty one gets a dummy allocation)."""
-
-    def __init__(self, case):
-        import torch
-
-        dev = torch.device("cuda", 0)
-        utf8, offsets, tokens, tok_offsets = case
-        self.n = len(offsets) - 1
-        self.utf8 = torch.from_numpy(np.ascontiguousarray(utf8).copy() if len(utf8) else np.zeros(1, dtype=np.uint8)).to(dev)
-        w = np.zeros((len(tokens) + 1, 6), dtype=np.int32)
-        w[: len(tokens)] = np.ascontiguousarray(tokens).view(np.int32).reshape(len(tokens), 6)
-        self.tok = torch.from_numpy(w).to(dev)
-        self.off = torch.from_numpy(np.ascontiguousarray(offsets, dtype=np.uint64).view(np.int64)).to(dev)
-        self.toff = torch.from_numpy(np.ascontiguousarray(tok_offsets, dtype=np.uint64).view(np.int64)).to(dev)
-        assert self.utf8.data_ptr() % 16 == 0
-        torch.cuda.synchronize()
-
-
-def dev_count(ctx, counts, case):
-    """kgpu_count_words_device + kgpu_ctx_sync_count -> (return code, tokens counted)."""
-    from kanpyo_amd import _lib
-
-    d = _Dev(case)
-    ctx.count_words(counts, d.utf8.data_ptr(), d.off.data_ptr(), d.n, d.tok.data_ptr(), d.toff.data_ptr())
-    got = C.c_uint64(0)
-    rc = _lib.lib().kgpu_ctx_sync_count(ctx._h, C.byref(got))
-    return rc, int(got.value)
-
-
-def crafted_want(env, case, kw, into=None):
-    return CR.count(*case, env.known, env.unk, env.nk, env.nu, ref_spec(**kw), SMALL_KEYS, into=into)
-
-
-@pytest.fixture(scope="module")
-def small_ctx(small_env):
-    from kanpyo_amd.device import DeviceContext
-
-    ctx = DeviceContext(small_env.tok)   # never tokenizes
-    yield ctx
-    ctx.close()
-
-
-LENGTHS = (0, 1, 2, 3, 4, 5, 7, 8, 9, 15, 16, 17, 31, 32, 33, 255, 256, 3072)
 U, K = R.UNKNOWN, R.KNOWN
 
 

@@ -16,12 +16,11 @@ import encode_ref as E
 import lines_ref as R
 import words_ref as W
 from conftest import ROOT, load_golden
-from test_gpu_count import LENGTHS, SMALL_KEYS, _Dev, _fixture_env
-from test_gpu_words import POS_DROP, SPECS, _Env, ref_spec, small_env  # noqa: F401  (small_env: the fixture)
+from record_cases import (LENGTHS, POS_DROP, SENTINEL, SMALL_KEYS, SPECS, _Dev, _Env, _fixture_env, _write_dict_dir, check_ragged, crafted_ids, dev_encode, env, mixed,  # noqa: F401
+                          ref_spec, same, small_ctx, small_env)   # (env, mixed, small_ctx, small_env: the fixtures)
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0x5A5A5A5A
 U, K = R.UNKNOWN, R.KNOWN
 
 
@@ -32,36 +31,6 @@ def ref_ids(env, utf8, offs, kw, keys, vocab, unk, bos=None, eos=None, tokens=No
         tokens = (exp.tokens, exp.offsets)
     words = E.sentence_words(utf8, offs, *tokens, env.known, env.unk, env.nk, env.nu, ref_spec(**kw), keys, sources)
     return E.encode_words(words, vocab, unk, bos, eos)
-
-
-def same(got, want, what=""):
-    ids, off = got[0], got[1]
-    assert ids.dtype == np.int32
-    assert np.array_equal(np.asarray(off, dtype=np.uint64), want[1]), what
-    assert np.array_equal(ids, want[0]), what
-
-
-@pytest.fixture(scope="module")
-def env():
-    """The 20 000-record dictionary with its display tables, its oracle and its keys by id."""
-    from kanpyo_amd import synth
-
-    sd = synth.build_dict(20000, seed=5)
-    known, unk = synth.feature_tables(sd)
-    e = _Env(sd.dict, known, unk)
-    e.sd, e.keys = sd, synth.record_surfaces(sd)
-    return e
-
-
-@pytest.fixture(scope="module")
-def mixed(env):
-    """2000 cfg 2 sentences and 200 cfg 3 sentences, packed, with the oracle's tokens: computed once, never changed."""
-    from kanpyo_amd import synth
-    from kanpyo_amd.tokenizer import pack_sentences
-
-    utf8, offs = pack_sentences(synth.make_corpus(env.sd, 2000, 3, "cfg2") + synth.make_corpus(env.sd, 200, 4, "cfg3"))
-    exp = env.orc.tokenize_batch(utf8, offs, 8)
-    return utf8, offs, (exp.tokens, exp.offsets)
 
 
 _TOP_HALF = {}
@@ -83,7 +52,6 @@ def top_half(env, mixed, kw):
 def test_fixture_golden_host_form_and_c_consumer(tmp_path):
     from kanpyo_amd import _lib
     from kanpyo_amd.dictfile import DictFile
-    from test_gpu_lines import _write_dict_dir
 
     e = _fixture_env()
     cases = load_golden("fixture_encode.json")["cases"]
@@ -144,48 +112,6 @@ def test_mixed_corpus(env, mixed, name):
 
 
 # ---- 3. key shapes: crafted records through the device form ------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def small_ctx(small_env):
-    from kanpyo_amd.device import DeviceContext
-
-    ctx = DeviceContext(small_env.tok)   # never tokenizes
-    yield ctx
-    ctx.close()
-
-
-def dev_encode(ctx, v, case, width=0, pad_id=0, capacity=None, room=None):
-    """kgpu_encode_device + kgpu_ctx_sync_lines on a crafted case -> (return code, ids reported, the whole destination int32, id_offsets uint64).
-    The destination starts ONE int32 behind a 16-byte boundary (d_ids is only 4-byte aligned) and is `room` entries of SENTINEL."""
-    import torch
-
-    from kanpyo_amd import _lib
-
-    d = case if isinstance(case, _Dev) else _Dev(case)
-    dev = d.utf8.device
-    room = (capacity if capacity is not None else 0) + 64 if room is None else room
-    buf = torch.full((room + 1,), SENTINEL, dtype=torch.int32, device=dev)
-    ioff = torch.full((d.n + 1,), -1, dtype=torch.int64, device=dev)
-    assert buf.data_ptr() % 16 == 0
-    torch.cuda.synchronize()
-    ctx.encode(v, d.utf8.data_ptr(), d.off.data_ptr(), d.n, d.tok.data_ptr(), d.toff.data_ptr(), buf.data_ptr() + 4, room if capacity is None else capacity,
-               ioff.data_ptr(), width=width, pad_id=pad_id)
-    got = C.c_uint64(0)
-    rc = _lib.lib().kgpu_ctx_sync_lines(ctx._h, C.byref(got))
-    return rc, int(got.value), buf.cpu().numpy()[1:], ioff.cpu().numpy().view(np.uint64)
-
-
-def crafted_ids(env, case, kw, vocab, unk, bos=None, eos=None):
-    return E.encode(*case, env.known, env.unk, env.nk, env.nu, ref_spec(**kw), SMALL_KEYS, vocab, unk, bos, eos)
-
-
-def check_ragged(ctx, v, case, want):
-    total = len(want[0])
-    rc, n, buf, ioff = dev_encode(ctx, v, case, room=total + 32)
-    assert (rc, n) == (0, total)
-    assert np.array_equal(ioff, want[1]) and np.array_equal(buf[:total], want[0])
-    assert (buf[total:] == SENTINEL).all(), "ids behind the ragged total"
-
-
 def half_listed(words):
     """Half of the distinct words listed, the other half absent -- and every absent word with a listed neighbour one byte or one length away."""
     words = sorted(set(words))

@@ -4,7 +4,6 @@ kgpu_encode_device_spans ragged and padded, with and without edit records, Vocab
 from tests/golden/fixture_encode_spans.json; the edit records of a line come from align_ref.expected_lines (unicodedata over the generator's segments)
 -- never from the library.  No tolerance: ids, all n + 1 offsets, every span field and every token index are compared exactly, and on every case the
 ids and offsets are also compared with what kgpu_encode_device writes for the same buffers.  The fixtures follow tests/test_gpu_wordpiece.py's pattern."""
-import ctypes as C
 import os
 import subprocess
 import sys
@@ -16,14 +15,12 @@ import align_ref as A
 import encode_spans_ref as S
 import lines_ref as R
 from conftest import ROOT, fixture_dict_parts, load_golden
-from test_gpu_wordpiece import SMALL_KEYS, SPECIALS, _Dev, _Env, bert_like, corpus_of, dev_encode, env, ref_spec, small_ctx, small_env  # noqa: F401  (three are fixtures)
+from record_cases import LIST, SENTINEL, SMALL_KEYS, SPECIALS, _Dev, _Env, bert_like, corpus_of, dev_encode, dev_spans, env, ref_spec, small_ctx  # noqa: F401
+from record_cases import plain_small_env as small_env  # noqa: F401  (env, small_ctx, small_env: the fixtures; this small_env has every EOS reachable)
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0x5A5A5A5A
 U, K, D = R.UNKNOWN, R.KNOWN, R.DUMMY
-# ids 0..3 are the specials; the pieces of テスト (a known key: from the row), あいうえお (unknown: from the text), 辞書 whole; 形態素 has no split
-LIST = SPECIALS + [w.encode() for w in ("テ", "##ス", "##ト", "あ", "##い", "##う", "##えお", "辞書")]
 
 
 def pack6(sent_bytes, per_sentence):
@@ -38,35 +35,6 @@ def pack6(sent_bytes, per_sentence):
 def edit_batch(per_sentence):
     """Per sentence a list of edit 8-tuples -> (edits[EDIT_DTYPE], edit_offsets)."""
     return A.edit_array([e for es in per_sentence for e in es]), np.concatenate([[0], np.cumsum([len(es) for es in per_sentence])]).astype(np.uint64)
-
-
-def dev_spans(ctx, v, case, edits=None, width=0, pad_id=0, capacity=None, room=None, index=True):
-    """kgpu_encode_device_spans + kgpu_ctx_sync_lines on a crafted case -> (return code, ids reported, ids int32 [room], id_offsets uint64, spans uint32
-    [room, 4], token_index int32 [room]).  All three destinations are `room` entries of SENTINEL; d_ids and d_token_index start ONE int32 behind a 16-byte
-    boundary (they are only 4-byte aligned).  edits: (edits[EDIT_DTYPE], edit_offsets) or None."""
-    import torch
-
-    from kanpyo_amd import _lib
-
-    d = case if isinstance(case, _Dev) else _Dev(case)
-    dev = d.utf8.device
-    room = (capacity if capacity is not None else 0) + 64 if room is None else room
-    ids = torch.full((room + 1,), SENTINEL, dtype=torch.int32, device=dev)
-    tix = torch.full((room + 1,), SENTINEL, dtype=torch.int32, device=dev)
-    spans = torch.full((room + 1, 4), SENTINEL, dtype=torch.int32, device=dev)
-    ioff = torch.full((d.n + 1,), -1, dtype=torch.int64, device=dev)
-    d_ed = d_eoff = None
-    if edits is not None:
-        raw = np.frombuffer(edits[0].tobytes() + bytes(24), dtype=np.uint8).copy()
-        d_ed = torch.from_numpy(raw).to(dev)
-        d_eoff = torch.from_numpy(np.ascontiguousarray(edits[1], dtype=np.uint64).view(np.int64)).to(dev)
-    torch.cuda.synchronize()
-    ctx.encode_spans(v, d.utf8.data_ptr(), d.off.data_ptr(), d.n, d.tok.data_ptr(), d.toff.data_ptr(), ids.data_ptr() + 4, room if capacity is None else capacity,
-                     ioff.data_ptr(), spans.data_ptr(), tix.data_ptr() + 4 if index else 0, d_ed.data_ptr() if d_ed is not None else 0,
-                     d_eoff.data_ptr() if d_eoff is not None else 0, width=width, pad_id=pad_id)
-    got = C.c_uint64(0)
-    rc = _lib.lib().kgpu_ctx_sync_lines(ctx._h, C.byref(got))
-    return rc, int(got.value), ids.cpu().numpy()[1:], ioff.cpu().numpy().view(np.uint64), spans.cpu().numpy().view(np.uint32)[:room], tix.cpu().numpy()[1:]
 
 
 def check_ragged(ctx, v, case, want, edits=None, what=""):

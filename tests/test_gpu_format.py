@@ -4,20 +4,14 @@ the protocol around the report words.  Every test builds its input in numpy, upl
 tokenized and compares d_text[:total] and all n + 1 text offsets byte for byte with tests/lines_ref.py::render (pinned on the CPU by
 tests/test_lines_ref_cpu.py).  No tolerance.  Every destination has 0xAB margins of 64 bytes or more on both sides, and the words around the
 offsets are canaries too; they and d_text[total:] must come back untouched."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import lines_ref as R
 from conftest import fixture_dict_parts
+from record_cases import FILL, _Dest, _enqueue, _Input, _sync
 
 pytestmark = pytest.mark.gpu
-
-MARGIN = 64
-FILL = 0xAB
-CANARY = 0x5A5AC3C35A5AC3C3
-OFF_PAD = 8   # canary words on either side of the text offsets
 
 
 # ---- dictionaries and contexts ----------------------------------------------------------------------------------------------------------
@@ -68,75 +62,7 @@ def synth_d():
     d.ctx.close()
 
 
-# ---- upload, render, compare ------------------------------------------------------------------------------------------------------------
-class _Input:
-    """A case in device memory.  The byte and record arrays carry a spare element: a batch of empty sentences still needs non-null pointers."""
-
-    def __init__(self, case):
-        import torch
-
-        dev = torch.device("cuda", 0)
-        utf8, offsets, tokens, tok_offsets = case
-        self.n, self.T = len(offsets) - 1, len(tokens)
-        u = np.zeros(utf8.size + 16, dtype=np.uint8)
-        u[: utf8.size] = utf8
-        w = np.zeros((self.T + 1, 6), dtype=np.int32)
-        w[: self.T] = np.ascontiguousarray(tokens).view(np.int32).reshape(self.T, 6)
-        self.utf8, self.tok = torch.from_numpy(u).to(dev), torch.from_numpy(w).to(dev)
-        self.off = torch.from_numpy(np.ascontiguousarray(offsets, dtype=np.uint64).view(np.int64)).to(dev)
-        self.toff = torch.from_numpy(np.ascontiguousarray(tok_offsets, dtype=np.uint64).view(np.int64)).to(dev)
-
-
-class _Dest:
-    """capacity bytes `mis` behind a 16-byte boundary, 0xAB all over, margins of MARGIN bytes or more; n + 1 offsets between canary words."""
-
-    def __init__(self, n, capacity, mis):
-        import torch
-
-        dev = torch.device("cuda", 0)
-        self.n, self.cap, self.lead = n, capacity, MARGIN + mis
-        self.buf = torch.full((MARGIN + 16 + capacity + MARGIN,), FILL, dtype=torch.uint8, device=dev)
-        assert self.buf.data_ptr() % 16 == 0 and 0 <= mis < 16
-        self.offs = torch.from_numpy(np.full(n + 1 + 2 * OFF_PAD, CANARY, dtype=np.uint64).view(np.int64)).to(dev)
-        self.text_ptr, self.offs_ptr = self.buf.data_ptr() + self.lead, self.offs.data_ptr() + 8 * OFF_PAD
-
-    def offsets(self):
-        o = self.offs.cpu().numpy().view(np.uint64)
-        assert (o[:OFF_PAD] == CANARY).all() and (o[OFF_PAD + self.n + 1 :] == CANARY).all(), "a store outside d_text_offsets[0 .. n]"
-        return o[OFF_PAD : OFF_PAD + self.n + 1]
-
-    def margins_intact(self):
-        return bool((self.buf[: self.lead] == FILL).all()) and bool((self.buf[self.lead + self.cap :] == FILL).all())
-
-    def holds(self, want: bytes, want_off):
-        """d_text[:total] is `want`, every other byte of the allocation is untouched, the offsets are want_off."""
-        got = self.buf.cpu().numpy()
-        exp = np.full(got.size, FILL, dtype=np.uint8)
-        exp[self.lead : self.lead + len(want)] = np.frombuffer(want, dtype=np.uint8)
-        if not np.array_equal(got, exp):
-            at = int(np.flatnonzero(got != exp)[0]) - self.lead
-            raise AssertionError(f"d_text differs first at byte {at} of {len(want)} (negative: the margin in front; beyond: behind the text): "
-                                 f"got {got[at + self.lead : at + self.lead + 24].tobytes()!r}, want {exp[at + self.lead : at + self.lead + 24].tobytes()!r}")
-        o = self.offsets()
-        assert np.array_equal(o, want_off), f"text offsets differ first at {int(np.flatnonzero(o != want_off)[0])}"
-
-
-def _enqueue(ctx, inp, dest, capacity=None, text_ptr=None):
-    import torch
-
-    torch.cuda.synchronize()   # the fills and uploads ran on torch's stream, the render runs on the context's
-    ctx.format_lines(inp.utf8.data_ptr(), inp.off.data_ptr(), inp.n, inp.tok.data_ptr(), inp.toff.data_ptr(),
-                     dest.text_ptr if text_ptr is None else text_ptr, dest.cap if capacity is None else capacity, dest.offs_ptr)
-
-
-def _sync(ctx):
-    """kgpu_ctx_sync_lines itself -> (return code, bytes reported)."""
-    from kanpyo_amd import _lib
-
-    nb = C.c_uint64(0)
-    return _lib.lib().kgpu_ctx_sync_lines(ctx._h, C.byref(nb)), int(nb.value)
-
-
+# ---- render, compare ---------------------------------------------------------------------------------------------------------------------
 def _check(d, inp, want, want_off, mis, slack=32):
     from kanpyo_amd import _lib
 

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, fixture_dict_parts, load_golden
+from record_cases import _write_dict_dir
 
 pytestmark = pytest.mark.gpu
 
@@ -300,32 +301,16 @@ def test_arena_overflow_protocol(fixture_tok, monkeypatch):
     assert _docs(tok, sents)[0] == _docs(tok, sents, 48, False)[0]
 
 
-def _write_dict_dir(d, known, unk, tmp_path):
-    from kanpyo_amd.dictfile import _unk_prefix_len
-
-    out = tmp_path / "blobs"
-    out.mkdir()
-    (out / "index.dict").write_bytes(d.index_dict)
-    (out / "connection.dict").write_bytes(d.connection_dict)
-    (out / "morph.dict").write_bytes(d.morph_dict)
-    (out / "unk.dict").write_bytes(d.unk_dict[: _unk_prefix_len(d.unk_dict)] + unk.encode())
-    np.asarray(d.char_category, dtype=np.uint8).tofile(out / "char_category.bin")
-    np.asarray(d.invoke_list, dtype=np.uint8).tofile(out / "invoke.bin")
-    np.asarray(d.group_list, dtype=np.uint8).tofile(out / "group.bin")
-    (out / "morph_feature.dict").write_bytes(known.encode())
-    (out / "unk_feature.dict").write_bytes(unk.encode())
-    return out
-
-
 def test_c_consumer_prints_the_golden_document(fixture_tok, tmp_path):
     from kanpyo_amd import _lib
+    from kanpyo_amd.dictfile import DictFile
 
     g, d, tok, known, unk = fixture_tok
     exe = str(tmp_path / "graphviz_consumer")
     libdir = os.path.dirname(_lib.LIB_PATH)
     subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"),
                     os.path.join(ROOT, "tests", "c_abi", "graphviz_consumer.c"), "-o", exe, "-L", libdir, "-lkanpyo_gpu", f"-Wl,-rpath,{libdir}"], check=True)
-    blobs = _write_dict_dir(d, known, unk, tmp_path)
+    blobs = _write_dict_dir(d, DictFile(d, known, unk), tmp_path)
     r = subprocess.run([exe, str(blobs), g["input"]], capture_output=True, timeout=300)
     assert r.returncode == 0, r.stderr.decode()
     assert r.stdout == g["dot"].encode()

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, fixture_dict_parts, load_golden
+from record_cases import _write_dict_dir
 
 pytestmark = pytest.mark.gpu
 
@@ -235,23 +236,6 @@ def test_set_features_errors(synth_full):
         t.set_features(known, unk)
     assert e.value.code == _lib.KGPU_ERR_INVALID_ARG
     assert t.tokenize_lines([""]) == b"EOS\t\n"
-
-
-def _write_dict_dir(d, df, tmp_path):
-    from kanpyo_amd.dictfile import _unk_prefix_len
-
-    out = tmp_path / "blobs"
-    out.mkdir()
-    (out / "index.dict").write_bytes(d.index_dict)
-    (out / "connection.dict").write_bytes(d.connection_dict)
-    (out / "morph.dict").write_bytes(d.morph_dict)
-    (out / "unk.dict").write_bytes(d.unk_dict[: _unk_prefix_len(d.unk_dict)] + df.unk_feature_table.encode())
-    np.asarray(d.char_category, dtype=np.uint8).tofile(out / "char_category.bin")
-    np.asarray(d.invoke_list, dtype=np.uint8).tofile(out / "invoke.bin")
-    np.asarray(d.group_list, dtype=np.uint8).tofile(out / "group.bin")
-    (out / "morph_feature.dict").write_bytes(df.morph_feature_table.encode())
-    (out / "unk_feature.dict").write_bytes(df.unk_feature_table.encode())
-    return out
 
 
 def _stdin_case(sd, orc, known, unk):

@@ -8,11 +8,8 @@ import pytest
 
 import encode_ref as E
 import lines_ref as R
-import test_gpu_format as F
 import words_ref as W
-from test_gpu_count import SMALL_KEYS, crafted_want, dev_count, holds
-from test_gpu_encode import SENTINEL, crafted_ids, dev_encode
-from test_gpu_words import ref_spec, small_env  # noqa: F401  (small_env: the fixture)
+from record_cases import SENTINEL, SMALL_KEYS, _Dest, _enqueue, _Input, _sync, crafted_ids, crafted_want, dev_count, dev_encode, holds, ref_spec, small_env  # noqa: F401  (small_env: the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -68,17 +65,17 @@ class _Run:
         self.krows, self.urows = R.rows_of(env.known, env.nk), R.rows_of(env.unk, env.nu)
 
     def lines(self, inp, cap, mis):
-        dest = F._Dest(inp.n, cap, mis)
-        F._enqueue(self.ctx, inp, dest)
-        return F._sync(self.ctx), dest
+        dest = _Dest(inp.n, cap, mis)
+        _enqueue(self.ctx, inp, dest)
+        return _sync(self.ctx), dest
 
     def words(self, inp, kw, cap, mis):
         import torch
 
-        dest = F._Dest(inp.n, cap, mis)
+        dest = _Dest(inp.n, cap, mis)
         torch.cuda.synchronize()
         self.ctx.format_words(self.env.words(**kw), inp.utf8.data_ptr(), inp.off.data_ptr(), inp.n, inp.tok.data_ptr(), inp.toff.data_ptr(), dest.text_ptr, cap, dest.offs_ptr)
-        return F._sync(self.ctx), dest
+        return _sync(self.ctx), dest
 
     def vocab_words(self, case, kw):
         env = self.env
@@ -110,7 +107,7 @@ def _words_in(text, off, sep):
 
 def test_each_consumer_matches_its_reference_and_they_agree(run, case):
     env = run.env
-    inp = F._Input(case)
+    inp = _Input(case)
     want_lines = R.render(*case, run.krows, run.urows)
     for mis in MIS:
         (rc, nb), dest = run.lines(inp, len(want_lines[0]) + 32, mis)
@@ -164,7 +161,7 @@ def test_one_bad_record_is_refused_by_all_four(run, case, what):
         R.render(*bad_case, run.krows, run.urows)
     with pytest.raises(ValueError):
         W.render(*bad_case, env.known, env.unk, env.nk, env.nu, ref_spec())
-    inp = F._Input(bad_case)
+    inp = _Input(bad_case)
     cap = len(R.render(*case, run.krows, run.urows)[0]) + 64
     (rc, _), dest = run.lines(inp, cap, 1)
     assert rc == _lib.KGPU_ERR_INVALID_ARG and dest.margins_intact(), what
@@ -180,6 +177,6 @@ def test_one_bad_record_is_refused_by_all_four(run, case, what):
     assert rc == _lib.KGPU_ERR_INVALID_ARG, what
     # the same context serves the good batch afterwards
     want = R.render(*case, run.krows, run.urows)
-    (rc, nb), dest = run.lines(F._Input(case), len(want[0]) + 32, 15)
+    (rc, nb), dest = run.lines(_Input(case), len(want[0]) + 32, 15)
     assert (rc, nb) == (0, len(want[0]))
     dest.holds(*want)

@@ -14,9 +14,8 @@ import encode_ref as E
 import lines_ref as R
 import table_keys as T
 import words_ref as W
-from test_gpu_count import SMALL_KEYS, _Dev, crafted_want, dev_count, holds  # noqa: F401
-from test_gpu_encode import SENTINEL, check_ragged, crafted_ids, dev_encode
-from test_gpu_words import _Env, ref_spec, small_env  # noqa: F401  (small_env: the fixture)
+from record_cases import (SENTINEL, _Dev, check_ragged, crafted_ids, crafted_want, dev_count, dev_encode, holds, ref_spec, small_ctx,  # noqa: F401
+                          small_env, synth_env)   # (small_ctx, small_env: the fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -25,24 +24,11 @@ UNK = -3
 
 
 @pytest.fixture(scope="module")
-def small_ctx(small_env):
-    from kanpyo_amd.device import DeviceContext
-
-    ctx = DeviceContext(small_env.tok)   # never tokenizes
-    yield ctx
-    ctx.close()
-
-
-@pytest.fixture(scope="module")
 def env():
     """The 20 000-record dictionary with its display tables, its keys by id and a context that never tokenizes."""
-    from kanpyo_amd import synth
     from kanpyo_amd.device import DeviceContext
 
-    sd = synth.build_dict(20000, seed=5)
-    known, unk = synth.feature_tables(sd)
-    e = _Env(sd.dict, known, unk)
-    e.sd, e.keys = sd, synth.record_surfaces(sd)
+    e = synth_env()
     e.ctx = DeviceContext(e.tok)
     yield e
     e.ctx.close()

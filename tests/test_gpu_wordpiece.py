@@ -15,122 +15,13 @@ import pytest
 import encode_ref as E
 import lines_ref as R
 import wordpiece_ref as WP
-import words_ref as W
-from conftest import ROOT, fixture_dict_parts, load_golden
+from conftest import ROOT, load_golden
+from record_cases import SENTINEL, SMALL_KEYS, SPECIALS, _Dev, _Env, bert_like, check_ragged, corpus_of, dev_encode, env, ref_spec, same, small_ctx  # noqa: F401
+from record_cases import plain_small_env as small_env  # noqa: F401  (env, small_ctx, small_env: the fixtures; this small_env has every EOS reachable)
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0x5A5A5A5A
 U, K = R.UNKNOWN, R.KNOWN
-SMALL_KEYS = ["テスト", "辞書", "形態素"]   # the keys of the fixture dictionary, by id
-SPECIALS = [b"[PAD]", b"[UNK]", b"[CLS]", b"[SEP]"]   # ids 0..3 of the lists made here
-
-
-def ref_spec(field=None, drop=(), keep=()):
-    return W.Spec(W.SURFACE if field is None else field, W.KEEP if keep else W.DROP if drop else W.ALL, keep or drop)
-
-
-class _Env:
-    """A dictionary with its display tables on the device, its oracle, and Words handles made on demand."""
-
-    def __init__(self, d, known, unk):
-        from kanpyo_amd import Tokenizer
-        from oracle import oracle
-
-        oracle.build()
-        self.dict, self.known, self.unk = d, known, unk
-        self.tok = Tokenizer(d)
-        self.tok.set_features(known, unk)
-        self.orc = oracle.OracleTokenizer.from_dict(d)
-        info = self.tok.info()
-        self.nk, self.nu = info["n_morphs"], info["n_unk_morphs"]
-        self._words = {}
-
-    def words(self, **kw):
-        key = repr(sorted(kw.items()))
-        if key not in self._words:
-            self._words[key] = self.tok.words(**kw)
-        return self._words[key]
-
-
-class _Dev:
-    """A crafted case in device memory, byte for byte: NO spare byte behind the text (an empty one gets a dummy allocation)."""
-
-    def __init__(self, case):
-        import torch
-
-        dev = torch.device("cuda", 0)
-        utf8, offsets, tokens, tok_offsets = case
-        self.n = len(offsets) - 1
-        self.utf8 = torch.from_numpy(np.ascontiguousarray(utf8).copy() if len(utf8) else np.zeros(1, dtype=np.uint8)).to(dev)
-        w = np.zeros((len(tokens) + 1, 6), dtype=np.int32)
-        w[: len(tokens)] = np.ascontiguousarray(tokens).view(np.int32).reshape(len(tokens), 6)
-        self.tok = torch.from_numpy(w).to(dev)
-        self.off = torch.from_numpy(np.ascontiguousarray(offsets, dtype=np.uint64).view(np.int64)).to(dev)
-        self.toff = torch.from_numpy(np.ascontiguousarray(tok_offsets, dtype=np.uint64).view(np.int64)).to(dev)
-        torch.cuda.synchronize()
-
-
-@pytest.fixture(scope="module")
-def small_env():
-    """The fixture dictionary with a known row without features, a row with a ten-character name and one with a 3400-character name."""
-    from kanpyo_amd import Dict
-    from kanpyo_amd.dictfile import MorphFeatureTable
-
-    p = fixture_dict_parts()
-    k = MorphFeatureTable([[], [1, 0, 1], [2]], ["", "名" * 10, "長" * 3400])
-    u = MorphFeatureTable([[1]] * len(p["unk_morphs"]), ["", "未知"])
-    return _Env(Dict.from_parts(**p), k, u)
-
-
-@pytest.fixture(scope="module")
-def small_ctx(small_env):
-    from kanpyo_amd.device import DeviceContext
-
-    ctx = DeviceContext(small_env.tok)   # never tokenizes
-    yield ctx
-    ctx.close()
-
-
-@pytest.fixture(scope="module")
-def env():
-    """The 20 000-record dictionary with its display tables, its oracle and its keys by id."""
-    from kanpyo_amd import synth
-
-    sd = synth.build_dict(20000, seed=5)
-    known, unk = synth.feature_tables(sd)
-    e = _Env(sd.dict, known, unk)
-    e.sd, e.keys = sd, synth.record_surfaces(sd)
-    return e
-
-
-def corpus_of(sd, keys, n_keyed, n_cfg2, n_cfg3, seed):
-    """Sentences strung together from the dictionary's keys of two characters and more (most tokens of the synthetic corpora are one character long:
-    nothing to split), then cfg 2 and cfg 3 sentences."""
-    from kanpyo_amd import synth
-
-    rng = random.Random(seed)
-    longer = [k for k in keys if len(k) >= 2]
-    return (["".join(rng.choice(longer) for _ in range(rng.randrange(1, 12))) for _ in range(n_keyed)]
-            + synth.make_corpus(sd, n_cfg2, seed, "cfg2") + synth.make_corpus(sd, n_cfg3, seed + 1, "cfg3"))
-
-
-def characters(words):
-    return sorted({w[s:e] for w in words for s, e in zip(WP.char_starts(w), WP.char_starts(w)[1:] + [len(w)])})
-
-
-def bert_like(per_sentence, top):
-    """[PAD] [UNK] [CLS] [SEP], the `top` most frequent words, then every distinct character c of the words and ##c -- except a handful left out."""
-    from collections import Counter
-
-    counts = Counter(w for s in per_sentence for w in s)
-    order = [w for w, _ in sorted(counts.items(), key=lambda kv: (-kv[1], kv[0]))]
-    chars = characters(order)
-    left_out = set(chars[3::25])
-    head = [w for w in order[:top] if w not in SPECIALS]
-    vocab = SPECIALS + head + [c for c in chars if c not in left_out and c not in set(head)] + [b"##" + c for c in chars if c not in left_out]
-    assert len(set(vocab)) == len(vocab) and left_out
-    return vocab
 
 
 @pytest.fixture(scope="module")
@@ -149,41 +40,6 @@ def ref_ids(env, utf8, offs, vocab, unk, bos=None, eos=None, tokens=None, kw=Non
         exp = env.orc.tokenize_batch(utf8, offs, 8)
         tokens = (exp.tokens, exp.offsets)
     return WP.encode(utf8, offs, *tokens, env.known, env.unk, env.nk, env.nu, ref_spec(**(kw or {})), env.keys, vocab, unk, bos, eos, stats=stats, **wp)
-
-
-def same(got, want, what=""):
-    ids, off = got[0], got[1]
-    assert ids.dtype == np.int32
-    assert np.array_equal(np.asarray(off, dtype=np.uint64), want[1]), what
-    assert np.array_equal(ids, want[0]), what
-
-
-def dev_encode(ctx, v, case, width=0, pad_id=0, capacity=None, room=None):
-    """kgpu_encode_device + kgpu_ctx_sync_lines on a crafted case -> (return code, ids reported, the whole destination int32, id_offsets uint64).
-    The destination starts ONE int32 behind a 16-byte boundary (d_ids is only 4-byte aligned) and is `room` entries of SENTINEL."""
-    import torch
-
-    from kanpyo_amd import _lib
-
-    d = case if isinstance(case, _Dev) else _Dev(case)
-    dev = d.utf8.device
-    room = (capacity if capacity is not None else 0) + 64 if room is None else room
-    buf = torch.full((room + 1,), SENTINEL, dtype=torch.int32, device=dev)
-    ioff = torch.full((d.n + 1,), -1, dtype=torch.int64, device=dev)
-    torch.cuda.synchronize()
-    ctx.encode(v, d.utf8.data_ptr(), d.off.data_ptr(), d.n, d.tok.data_ptr(), d.toff.data_ptr(), buf.data_ptr() + 4, room if capacity is None else capacity,
-               ioff.data_ptr(), width=width, pad_id=pad_id)
-    got = C.c_uint64(0)
-    rc = _lib.lib().kgpu_ctx_sync_lines(ctx._h, C.byref(got))
-    return rc, int(got.value), buf.cpu().numpy()[1:], ioff.cpu().numpy().view(np.uint64)
-
-
-def check_ragged(ctx, v, case, want):
-    total = len(want[0])
-    rc, n, buf, ioff = dev_encode(ctx, v, case, room=total + 32)
-    assert (rc, n) == (0, total)
-    assert np.array_equal(ioff, want[1]) and np.array_equal(buf[:total], want[0])
-    assert (buf[total:] == SENTINEL).all(), "ids behind the ragged total"
 
 
 def crafted_ids(env, case, vocab, unk, bos=None, eos=None, kw=None, **wp):

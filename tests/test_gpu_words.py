@@ -14,57 +14,9 @@ import pytest
 import lines_ref as R
 import words_ref as W
 from conftest import ROOT, fixture_dict_parts, load_golden
+from record_cases import FILL, POS_DROP, SPECS, _Dest, _Env, _Input, _sync, _write_dict_dir, ref_spec, small_env  # noqa: F401  (small_env: the fixture)
 
 pytestmark = pytest.mark.gpu
-
-POS_DROP = ("助詞", "助動詞", "記号")
-SPECS = {
-    "surface": {}, "field0": {"field": 0}, "field7": {"field": 7}, "field8": {"field": 8}, "field40": {"field": 40},
-    "drop": {"drop": POS_DROP}, "keep": {"keep": ("感動詞",)},
-}
-
-
-def ref_spec(field=None, drop=(), keep=(), separator=" "):
-    """Tokenizer.words' arguments as the reference's Spec."""
-    return W.Spec(W.SURFACE if field is None else field, W.KEEP if keep else W.DROP if drop else W.ALL, keep or drop, separator)
-
-
-class _Env:
-    """A dictionary with its display tables on the device, its oracle, and Words handles made on demand."""
-
-    def __init__(self, d, known, unk):
-        from kanpyo_amd import Tokenizer
-        from oracle import oracle
-
-        oracle.build()
-        self.dict, self.known, self.unk = d, known, unk
-        self.tok = Tokenizer(d)
-        self.tok.set_features(known, unk)
-        self.orc = oracle.OracleTokenizer.from_dict(d)
-        info = self.tok.info()
-        self.nk, self.nu = info["n_morphs"], info["n_unk_morphs"]
-        self._words = {}
-
-    def words(self, **kw):
-        key = repr(sorted(kw.items()))
-        if key not in self._words:
-            self._words[key] = self.tok.words(**kw)
-        return self._words[key]
-
-    def expect(self, utf8, offs, kw, counts=None, tokens=None):
-        exp = self.orc.tokenize_batch(utf8, offs, 8) if tokens is None else tokens
-        return W.render(utf8, offs, exp.tokens, exp.offsets, self.known, self.unk, self.nk, self.nu, ref_spec(**kw), counts), exp
-
-    def check(self, sents, kw, counts=None, tokens=None):
-        from kanpyo_amd.tokenizer import pack_sentences
-
-        utf8, offs = pack_sentences(sents)
-        text, toff, status = self.words(**kw).render_packed(utf8, offs)
-        (want, want_off), exp = self.expect(utf8, offs, kw, counts, tokens)
-        assert np.array_equal(toff, want_off), kw
-        assert text.tobytes() == want, kw
-        return text, toff, status, exp
-
 
 @pytest.fixture(scope="module")
 def full():
@@ -75,20 +27,6 @@ def full():
     e = _Env(sd.dict, known, unk)
     e.sd = sd
     return e
-
-
-@pytest.fixture(scope="module")
-def small_env():
-    """The small dictionary of test_gpu_lines.py::test_edge_cases: an empty row, a row with "" and a 10 200-byte name, an unreachable EOS."""
-    from kanpyo_amd import Dict
-    from kanpyo_amd.dictfile import MorphFeatureTable
-
-    p = fixture_dict_parts()
-    p["conn_data"] = [0, 100, 200, 100, -30000, 100, 200, 100, -30000]
-    p["morphs"] = [[0, 0, 1000], [1, 1, -20000], [2, 2, 1100]]
-    k = MorphFeatureTable([[], [1, 0, 1], [2]], ["", "名" * 10, "長" * 3400])
-    u = MorphFeatureTable([[1]] * len(p["unk_morphs"]), ["", "未知"])
-    return _Env(Dict.from_parts(**p), k, u)
 
 
 def _mix(sd):
@@ -291,16 +229,14 @@ class _Crafted:
 
     def run(self, case, kw, mis=0, capacity=None, want=None):
         """Render the crafted case -> (rc, bytes reported, destination).  want: (text, offsets) to hold the destination to."""
-        import test_gpu_format as F
-
-        inp = F._Input(case)
+        inp = _Input(case)
         cap = (len(want[0]) + 32) if capacity is None else capacity
-        dest = F._Dest(inp.n, cap, mis)
+        dest = _Dest(inp.n, cap, mis)
         import torch
 
         torch.cuda.synchronize()
         self.ctx.format_words(self.env.words(**kw), inp.utf8.data_ptr(), inp.off.data_ptr(), inp.n, inp.tok.data_ptr(), inp.toff.data_ptr(), dest.text_ptr, cap, dest.offs_ptr)
-        rc, nb = F._sync(self.ctx)
+        rc, nb = _sync(self.ctx)
         return rc, nb, dest
 
     def check(self, case, kw, mis_set=(0,)):
@@ -511,7 +447,6 @@ def test_output_past_4gib(crafted_small):
     column is the separator, or the newline at each sentence's last record.  Sentences 64..95 hold more than 2^32 bytes together."""
     import torch
 
-    import test_gpu_format as F
     from kanpyo_amd import _lib
 
     env = crafted_small.env
@@ -522,12 +457,12 @@ def test_output_past_4gib(crafted_small):
     total = T * Wd
     want_off = np.concatenate([[0], np.cumsum(counts * Wd)]).astype(np.uint64)
     assert total >= 2**32 + 2**28 and ((want_off[:-1] < 2**32) & (want_off[1:] > 2**32)).any() and int((counts[64:96] * Wd).sum()) > 2**32
-    inp = F._Input(case)
-    dest = F._Dest(inp.n, total + 32, 7)
+    inp = _Input(case)
+    dest = _Dest(inp.n, total + 32, 7)
     torch.cuda.synchronize()
     crafted_small.ctx.format_words(env.words(field=0, separator="|"), inp.utf8.data_ptr(), inp.off.data_ptr(), inp.n, inp.tok.data_ptr(), inp.toff.data_ptr(),
                                    dest.text_ptr, dest.cap, dest.offs_ptr)
-    assert F._sync(crafted_small.ctx) == (_lib.KGPU_OK, total)
+    assert _sync(crafted_small.ctx) == (_lib.KGPU_OK, total)
     assert np.array_equal(dest.offsets(), want_off)
     dev = dest.buf.device
     text = dest.buf[dest.lead : dest.lead + total].view(T, Wd)
@@ -538,7 +473,7 @@ def test_output_past_4gib(crafted_small):
     for r0 in range(0, T, 8192):
         ok = (text[r0 : r0 + 8192, : Wd - 1] == name).all(dim=1)
         assert bool(ok.all()), f"piece {r0 + int(torch.nonzero(~ok)[0])} does not hold the name"
-    assert dest.margins_intact() and bool((dest.buf[dest.lead + total : dest.lead + dest.cap] == F.FILL).all())
+    assert dest.margins_intact() and bool((dest.buf[dest.lead + total : dest.lead + dest.cap] == FILL).all())
     del text, dest, inp
     torch.cuda.empty_cache()
 
@@ -605,7 +540,6 @@ def test_a_handle_outlives_the_dictionary():
 def test_c_consumer_on_the_fixture_golden(tmp_path):
     from kanpyo_amd import Dict, _lib
     from kanpyo_amd.dictfile import DictFile, MorphFeatureTable
-    from test_gpu_lines import _write_dict_dir
 
     p = fixture_dict_parts()
     d = Dict.from_parts(**p)

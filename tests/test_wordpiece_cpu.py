@@ -16,6 +16,7 @@ import wordpiece_ref as WP
 import words_ref as W
 from conftest import ROOT, load_golden
 from kanpyo_amd import _lib
+from record_cases import characters, ref_spec
 
 HERE = os.path.join(ROOT, "tests", "c_abi")
 INC = os.path.join(ROOT, "include")
@@ -86,10 +87,6 @@ def synth20k():
     return sd, known, unk, len(known.morph_features), len(unk.morph_features), synth.record_surfaces(sd)
 
 
-def ref_spec(field=None, drop=(), keep=()):
-    return W.Spec(W.SURFACE if field is None else field, W.KEEP if keep else W.DROP if drop else W.ALL, keep or drop)
-
-
 def wordpiece_table(sd_dict, known, unk, nk, nu, kw, words, unk_id, prefix=b"##", max_chars=100, wp=None):
     """kgpu_debug_wordpiece_table -> (rc, {"initial": (slots, arena), "cont": (slots, arena), "rows": uint32 [n, 2], "pool": int32, "info": dict})."""
     from kanpyo_amd._calls import struct_dict
@@ -128,10 +125,6 @@ def row_pieces(t, r):
     if count == 1:
         return [int(np.int32(np.uint32(first)))]
     return t["pool"][first : first + count].tolist()
-
-
-def characters(words):
-    return sorted({w[s:e] for w in words for s, e in zip(WP.char_starts(w), WP.char_starts(w)[1:] + [len(w)])})
 
 
 @pytest.mark.parametrize("name, kw", [("surface", {}), ("field7", {"field": 7}), ("drop", {"drop": ("助詞", "助動詞", "記号")})])
