@@ -885,6 +885,63 @@ int kgpu_pack_device(kgpu_ctx *c, const kgpu_pack_opts *o, uint64_t n, const int
                      int32_t *d_type_ids, int32_t *d_mask, kgpu_span *d_spans, int32_t *d_tix, uint64_t row_capacity, uint64_t *d_row_offsets,
                      uint8_t *d_status);
 
+/* ---- text from ids: sequences of vocabulary ids back to the words they stand for, joined into one line per sequence (the way back from
+ * kgpu_encode_*: reading a model's output, showing a window, checking input_ids by eye; `tokenizers.decoders.WordPiece(prefix, cleanup=False)` stated
+ * on bytes; NOT an output of the reference) ----
+ * The list is the one a vocabulary handle was made from: word k is words[word_offsets[k] .. word_offsets[k + 1]), n_words of them, verbatim bytes; the
+ * empty word is a legal entry.  The prefix is the continuation prefix of "WordPiece ids" (prefix_len 0..8; 0 for a plain vocabulary).
+ * Input: n sequences of int32 ids, in one of two forms.  Ragged: ids and id_offsets (n + 1 entries, counted in ids), sequence s is
+ * ids[id_offsets[s] .. id_offsets[s + 1]), and width == 0.  Padded: id_offsets == NULL and width >= 1, sequence s is the whole row
+ * ids[s * width .. (s + 1) * width); padding is removed by the skip list, not by a length.  Any other combination is KGPU_ERR_INVALID_ARG, returned
+ * before anything touches a device; so are, in the forms whose offsets lie in host memory, offsets that run backwards.  (Offsets in device memory
+ * cannot be looked at by the call: a sequence whose offsets run backwards there is the empty sequence.)
+ *  1. Which elements give text.  An id in the skip list gives nothing.  An id outside [0, n_words) that is not in the skip list gives nothing and
+ *     sets the sequence's status byte to KGPU_DECODE_BAD_ID -- a unk_id the caller placed outside the list ("vocabulary ids", rule 3) included;
+ *     otherwise the status is KGPU_DECODE_OK.  What remains are the sequence's KEPT elements, numbered k = 0, 1, ...; the word of a kept element is
+ *     list entry `id`.
+ *  2. Joining.  Kept element 0 contributes its word as it is, even when it starts with the prefix.  Kept element k > 0 contributes its word without
+ *     its first prefix_len bytes when prefix_len > 0 and the word starts with the prefix -- the prefix is removed ONCE ("####y" gives "##y"; a word
+ *     equal to the prefix gives nothing) -- and otherwise the separator followed by its word.  The empty word at k > 0 contributes the separator
+ *     alone.  With prefix_len == 0 there are no continuation words: every k > 0 gets the separator.
+ *  3. Output.  Packed text with text_offsets (n + 1 entries, in bytes): line s is text[text_offsets[s] .. text_offsets[s + 1]), no terminator, as in
+ *     kgpu_normalize_*.  A sequence without a kept element is the empty line.  The bytes are whatever the list holds: UTF-8 only if the list and the
+ *     cut points are.
+ *  4. Capacity: the protocol of kgpu_tokenize_batch_lines.  text_offsets and status are always written; when text_offsets[n] > text_capacity NOTHING
+ *     is written to text and the call (the sync) returns KGPU_ERR_CAPACITY with the exact size.
+ *  5. The device result equals kgpu_decode_host's on every input: text, offsets and status, byte for byte.
+ * opts == NULL: one space, no skip list.  KGPU_ERR_INVALID_ARG for opts.size below the struct's, a set flag, sep_len above 8, n_skip above
+ * KGPU_DECODE_MAX_SKIP, prefix_len above 8, a null pointer where one is needed, and ids that are not 4-byte aligned. */
+#define KGPU_DECODE_OK 0            /* per-sequence status (uint8) */
+#define KGPU_DECODE_BAD_ID 1
+#define KGPU_DECODE_MAX_SKIP 8
+typedef struct kgpu_decode_opts {
+    uint32_t size;        /* sizeof(kgpu_decode_opts): fields may be appended later */
+    uint32_t flags;       /* 0; any set bit is KGPU_ERR_INVALID_ARG */
+    uint32_t sep_len;     /* 0..8 */
+    uint8_t sep[8];
+    uint32_t n_skip;      /* 0..KGPU_DECODE_MAX_SKIP */
+    int32_t skip_ids[KGPU_DECODE_MAX_SKIP];   /* any int32, inside the list's range or not */
+} kgpu_decode_opts;
+/* The rule on the host, in plain C++: no device, no handle; the definition of the device results (both run the same statements).  All arrays in host
+ * memory.  *n_bytes (may be NULL): text_offsets[n], written or needed. */
+int kgpu_decode_host(const uint8_t *words, const uint64_t *word_offsets, uint64_t n_words, const uint8_t *prefix, uint32_t prefix_len,
+                     const int32_t *ids, const uint64_t *id_offsets, uint64_t n, uint64_t width, const kgpu_decode_opts *opts,
+                     uint8_t *text, uint64_t text_capacity, uint64_t *text_offsets, uint8_t *status, uint64_t *n_bytes);
+/* Device-resident, three launches on c's stream whatever the batch holds: the lines' lengths and status bytes (one wavefront per sequence), their
+ * scan into d_text_offsets, the bytes.  Every d_* pointer is a device pointer on the context's device (d_id_offsets NULL: padded).  A WordPiece
+ * handle supplies its own prefix, a plain handle none.  It takes the context's one pending render-kind slot (one render, count, encode, normalise,
+ * span mapping, pack or decode may be pending per context); kgpu_ctx_sync_lines waits and reports text_offsets[n], written or needed.  A context
+ * whose dictionary is not the handle's is KGPU_ERR_INVALID_ARG.  The handle's first decode call uploads an id -> word table of 4 bytes per list
+ * entry, once; a handle that never decodes never holds it, and kgpu_vocab_get_info is what it was. */
+int kgpu_decode_device(kgpu_ctx *c, const kgpu_vocab *v, const int32_t *d_ids, const uint64_t *d_id_offsets, uint64_t n, uint64_t width,
+                       const kgpu_decode_opts *opts, uint8_t *d_text, uint64_t text_capacity, uint64_t *d_text_offsets, uint8_t *d_status);
+/* Host memory in, host memory out, computed on the device: kgpu_decode_host's arguments behind the handle.  This is the SIMPLE route, not a
+ * pipelined path: per chunk of sequences one upload, one kgpu_decode_device, one sync and one download on a context of the dictionary's pool, one
+ * chunk after the other.  A call of one chunk writes nothing on KGPU_ERR_CAPACITY; with several, the chunks in front of the one that did not fit
+ * have been delivered.  *n_bytes is exact either way. */
+int kgpu_decode_batch(kgpu_vocab *v, const int32_t *ids, const uint64_t *id_offsets, uint64_t n, uint64_t width, const kgpu_decode_opts *opts,
+                      uint8_t *text, uint64_t text_capacity, uint64_t *text_offsets, uint8_t *status, uint64_t *n_bytes);
+
 #ifdef __cplusplus
 }
 #endif

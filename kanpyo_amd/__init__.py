@@ -10,5 +10,6 @@ from .dict import Dict  # noqa: F401
 from .tokenizer import Tokenizer, TOKEN_DTYPE, normalize_host, normalize_host_aligned  # noqa: F401
 from .vocab import Vocab  # noqa: F401
 from .pack import pack_host  # noqa: F401
+from .decode import decode_host  # noqa: F401
 
-__all__ = ["AlignedToken", "Token", "TokenClass", "Dict", "Tokenizer", "TOKEN_DTYPE", "Vocab", "normalize_host", "normalize_host_aligned", "pack_host"]
+__all__ = ["AlignedToken", "Token", "TokenClass", "Dict", "Tokenizer", "TOKEN_DTYPE", "Vocab", "normalize_host", "normalize_host_aligned", "pack_host", "decode_host"]

@@ -42,6 +42,7 @@ SYMBOLS = [
     "kgpu_source_spans_host", "kgpu_source_spans_device", "kgpu_source_spans_batch",
     "kgpu_encode_device_spans",
     "kgpu_pack_host", "kgpu_pack_device",
+    "kgpu_decode_host", "kgpu_decode_device", "kgpu_decode_batch",
 ]
 KGPU_VOCAB_ADD_BOS, KGPU_VOCAB_ADD_EOS = 1, 2
 KGPU_COUNTS_DEFAULT_SLOTS, KGPU_COUNTS_DEFAULT_KEY_BYTES = 1 << 22, 256 << 20
@@ -50,6 +51,7 @@ KGPU_WORDS_ALL, KGPU_WORDS_DROP, KGPU_WORDS_KEEP = 0, 1, 2
 KGPU_PACK_WINDOWS = 1
 KGPU_PACK_LONGEST_FIRST, KGPU_PACK_ONLY_FIRST, KGPU_PACK_ONLY_SECOND = 0, 1, 2
 KGPU_PACK_OK, KGPU_PACK_CUT, KGPU_PACK_NO_ROOM = 0, 1, 2
+KGPU_DECODE_OK, KGPU_DECODE_BAD_ID, KGPU_DECODE_MAX_SKIP = 0, 1, 8
 
 
 def normalize_form(form) -> int:
@@ -180,6 +182,11 @@ class PackOpts(C.Structure):  # kgpu_pack_opts
                 ("cls_id", C.c_int32), ("sep_id", C.c_int32), ("pad_id", C.c_int32), ("trim_front", C.c_uint32), ("trim_back", C.c_uint32)]
 
 
+class DecodeOpts(C.Structure):  # kgpu_decode_opts
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("sep_len", C.c_uint32), ("sep", C.c_uint8 * 8), ("n_skip", C.c_uint32),
+                ("skip_ids", C.c_int32 * KGPU_DECODE_MAX_SKIP)]
+
+
 class Work(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("sentences", "B", "C", "T", "N", "E", "K")]
 
@@ -299,6 +306,10 @@ def lib():
         pack = [C.POINTER(PackOpts), C.c_uint64, vp, vp, vp, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, C.c_uint64, vp, vp]
         L.kgpu_pack_host.argtypes = pack + [C.POINTER(C.c_uint64)]
         L.kgpu_pack_device.argtypes = [vp] + pack
+        decode = [vp, vp, C.c_uint64, C.c_uint64, C.POINTER(DecodeOpts), vp, C.c_uint64, vp, vp]   # ids, id_offsets, n, width, opts, text, capacity, text_offsets, status
+        L.kgpu_decode_host.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32] + decode + [C.POINTER(C.c_uint64)]
+        L.kgpu_decode_device.argtypes = [vp, vp] + decode
+        L.kgpu_decode_batch.argtypes = [vp] + decode + [C.POINTER(C.c_uint64)]
         L.kgpu_debug_wordpiece_split_ends.argtypes = [vp, vp, C.c_uint64, C.POINTER(WordpieceOpts), C.c_int32, vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, C.POINTER(C.c_uint64)]
         L.kgpu_debug_wordpiece_split.argtypes = [vp, vp, C.c_uint64, C.POINTER(WordpieceOpts), C.c_int32, vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.POINTER(C.c_uint64)]
         L.kgpu_debug_counts_order.argtypes = [vp, vp, vp, C.c_uint64] + L.kgpu_counts_read.argtypes[1:]

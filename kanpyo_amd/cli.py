@@ -43,6 +43,13 @@ fit N ids with its specials is cut by --truncation (only_second, the default, on
 share --stride ids (default 0).  With --pair an input line is `a<TAB>b` (a line without a tab has an empty b).  The rows are made on the device
 (Vocab.encode_pairs_tensor); the specials are --bos and --eos, which this form needs; stdin's blocks are split on the host.
 
+`python -m kanpyo_amd decode [INPUT] -c DICT --vocab FILE [--wordpiece [--prefix S]] [--separator S] [--skip ID[,ID...]]`: NOT a subcommand of the
+reference either -- the way back from `encode` (include/kanpyo_gpu.h, "text from ids"): every input line is decimal ids separated by spaces, what
+`encode` prints, and becomes one output line, the words of its ids joined by --separator (0 to 8 bytes, default a space; '' is allowed here), on the
+device (kgpu_decode_batch).  With --wordpiece a continuation piece joins the word in front of it without its prefix.  --skip names at most 8 ids that
+give no text (a bos, an eos, a pad); an id outside FILE gives none either.  `encode ... | decode ...` on a corpus whose words are all listed prints what
+`wakati` prints.  A line that is not a list of int32s ends the run with status 101, its line number on stderr and NOTHING on stdout, as `count` does.
+
 `--normalize {none,nfc,nfkc}` (default none) on `tokenize`, `wakati`, `count`, `encode` and `graphviz`: the input -- INPUT, or stdin's lines with either
 --split -- is normalised on the device first (include/kanpyo_gpu.h, "text normalisation"), and what is printed are the surfaces and words of the
 NORMALISED text: half-width katakana, full-width letters and digits, U+3231 and the ideographic space then match the dictionary's keys.
@@ -354,6 +361,79 @@ def encode(args, stdin, stdout) -> int:
     return 0
 
 
+def parse_id_lines(data: bytes):
+    """Lines of decimal int32s separated by blanks (what `encode` prints) -> (ids int32, offsets uint64 [lines + 1]), or the 1-based number of the
+    first line that is something else.  The last line may lack its newline; an empty line is the empty sequence."""
+    rows = data.split(b"\n")
+    if rows and rows[-1] == b"":
+        rows.pop()
+    ids, offs = [], [0]
+    for k, row in enumerate(rows):
+        try:
+            vals = [int(t) for t in row.split()]
+        except ValueError:
+            return k + 1
+        if any(not -2**31 <= v < 2**31 for v in vals) or not row.isascii() or b"_" in row:
+            return k + 1
+        ids += vals
+        offs.append(len(ids))
+    return np.array(ids, dtype=np.int64).astype(np.int32), np.array(offs, dtype=np.uint64)
+
+
+def decode(args, stdin, stdout) -> int:
+    from .vocab import Vocab
+
+    try:
+        listed = Vocab.read_words(args.vocab)
+    except OSError as e:
+        print(f"kanpyo_amd: --vocab: {e}", file=sys.stderr)
+        return 2
+    if not args.wordpiece and args.prefix is not None:
+        print("kanpyo_amd: --prefix goes with --wordpiece", file=sys.stderr)
+        return 2
+    wp = {}
+    if args.wordpiece:
+        wp = dict(wordpiece=True, prefix=os.fsencode("##" if args.prefix is None else args.prefix))
+        if len(wp["prefix"]) > 8:
+            print("kanpyo_amd: --prefix has at most 8 bytes", file=sys.stderr)
+            return 2
+    # (the ids stand for themselves: no word of the list is special here, and unk_id only has to be an id)
+    v = Vocab(_open(args).words(), listed, 0, **wp)
+    sep = os.fsencode(args.separator)
+    out = bytearray()   # (nothing is printed before the input is known to be lists of ids)
+    line0 = 0
+    blocks = [os.fsencode(args.input)] if args.input is not None else _blocks(stdin, args.block_bytes)
+    for block in blocks:
+        parsed = parse_id_lines(block)
+        if isinstance(parsed, int):
+            print(f"kanpyo_amd: line {line0 + parsed}: not a list of int32 ids", file=sys.stderr)
+            return PANIC_STATUS
+        ids, offs = parsed
+        line0 += offs.size - 1
+        o = offs.tolist()
+        out += b"".join(ln + b"\n" for ln in v.decode([ids[o[i] : o[i + 1]] for i in range(len(o) - 1)], separator=sep, skip=args.skip))
+    stdout.write(bytes(out))
+    stdout.flush()
+    return 0
+
+
+def _skip_list(text: str):
+    """--skip: at most 8 int32 ids separated by commas."""
+    try:
+        ids = [int(t) for t in text.split(",") if t.strip()]
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"invalid skip list {text!r}: ids separated by commas")
+    if len(ids) > 8 or any(not -2**31 <= k < 2**31 for k in ids):
+        raise argparse.ArgumentTypeError(f"invalid skip list {text!r}: at most 8 ids, each an int32")
+    return ids
+
+
+def _decode_separator(text: str) -> str:
+    if len(text.encode("utf-8", "surrogateescape")) > 8:
+        raise argparse.ArgumentTypeError(f"invalid separator {text!r}: at most 8 bytes")
+    return text
+
+
 def _top(text: str) -> int:
     if not text.isascii() or not text.isdigit() or int(text) < 1:
         raise argparse.ArgumentTypeError(f"invalid value {text!r}: a count from 1")
@@ -490,6 +570,16 @@ def parse_args(argv=None):
                        ("--truncation", dict(choices=["only_second", "only_first", "longest_first"], default=None, help="With --max-length: which side is cut [default: only_second]")),
                        ("--pair", dict(action="store_true", help="With --max-length: an input line is a<TAB>b, a sentence pair"))],
                   skip_invalid="A line that is not UTF-8 prints its bos / eos only instead of ending the run with status 101")
+    dc = sub.add_parser("decode", help="The words of each input line's vocabulary ids, joined (not in the reference)")
+    dc.add_argument("input", nargs="?", default=None, help="Ids to decode: decimal numbers separated by spaces [default: stdin, one sequence per line]")
+    dc.add_argument("-d", "--dict", choices=["ipa"], default="ipa", help="Dictionary")
+    dc.add_argument("-c", "--custom-dict", default=None, help="Custom dictionary (.dict)")
+    dc.add_argument("--vocab", required=True, help="The vocabulary: one word per line, line k (0-based) is id k")
+    dc.add_argument("--wordpiece", action="store_true", help="The vocabulary is a WordPiece list: a continuation piece joins the word in front of it without its prefix")
+    dc.add_argument("--prefix", default=None, help="With --wordpiece: the continuation prefix, at most 8 bytes [default: ##]")
+    dc.add_argument("--separator", type=_decode_separator, default=" ", help="What stands between words, 0 to 8 bytes [default: a space]")
+    dc.add_argument("--skip", type=_skip_list, default=[], help="Ids that give no text: ID[,ID...], at most 8")
+    dc.add_argument("--block-bytes", type=int, default=BLOCK_BYTES, help=argparse.SUPPRESS)
     args = p.parse_args(argv)
     if args.command is None:   # src/bin/kanpyo.rs:173: no subcommand == tokenize from stdin, default dictionary
         args = t.parse_args([])
@@ -510,6 +600,8 @@ def main(argv=None) -> int:
             return count(args, sys.stdin.buffer, sys.stdout.buffer)
         if args.command == "encode":
             return encode(args, sys.stdin.buffer, sys.stdout.buffer)
+        if args.command == "decode":
+            return decode(args, sys.stdin.buffer, sys.stdout.buffer)
         if args.command == "normalize":
             return normalize(args, sys.stdin.buffer, sys.stdout.buffer)
         if args.command == "align":

@@ -39,7 +39,7 @@ bool any_known_surface_row(const std::vector<WordRow> &rows, size_t nk) {
 
 void free_vocab(kgpu_vocab *v) {
     (void)hipSetDevice(v->words->dict->device);
-    (void)hipFree(v->d_row_id); (void)hipFree(v->d_slots); (void)hipFree(v->d_arena);
+    (void)hipFree(v->d_row_id); (void)hipFree(v->d_slots); (void)hipFree(v->d_arena); (void)hipFree(v->d_entry);
     (void)hipFree(v->d_cont_slots); (void)hipFree(v->d_cont_arena); (void)hipFree(v->d_wp_rows); (void)hipFree(v->d_piece_ids); (void)hipFree(v->d_piece_ends);
     kgpu_words *w = v->words;
     delete v;
@@ -92,6 +92,8 @@ int create_vocab(kgpu_words *w, const uint8_t *words, const uint64_t *word_offse
     w->refs.fetch_add(1, std::memory_order_relaxed);
     v->flags = opts->flags; v->unk_id = opts->unk_id; v->bos_id = opts->bos_id; v->eos_id = opts->eos_id;
     v->n_words = n_words; v->table_slots = t.slots.size(); v->key_bytes = t.arena.size() - 16; v->rows_resolved = t.rows_resolved;
+    build_decode_entries(t, n_words, v->h_entry);   // (host memory, 4 bytes per word: kgpu_decode_device.cpp uploads it when a first decode asks for it)
+    if (spec) { std::memcpy(v->prefix, spec->prefix, 8); v->prefix_len = spec->prefix_len; }
     bool ok = upload(&v->d_slots, t.slots.data(), t.slots.size() * sizeof(VocabSlot)) && upload(&v->d_arena, t.arena.data(), t.arena.size());
     if (!spec) ok = ok && upload(&v->d_row_id, t.row_id.data(), t.row_id.size() * 4);
     else {

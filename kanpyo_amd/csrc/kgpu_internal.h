@@ -12,6 +12,7 @@
 #include "../../include/kanpyo_gpu.h"
 #include "kgpu_normalize_core.h"
 #include "kgpu_pack_core.h"
+#include "kgpu_decode_core.h"
 
 namespace kgpu {
 
@@ -390,6 +391,29 @@ uint8_t norm_line_host(uint32_t form, const uint8_t *s, uint32_t len, uint8_t *o
 // ... and its edits: n_edits is their number, and text and edits are written when BOTH fit
 uint8_t norm_line_host_aligned(uint32_t form, const uint8_t *s, uint32_t len, uint8_t *out, uint64_t capacity, uint64_t &out_len, kgpu_norm_edit *edits,
                                uint64_t edit_capacity, uint64_t &n_edits);
+
+// The text from ids (kgpu_decode.hip; include/kanpyo_gpu.h, "text from ids"): one line per sequence of ids, the words of its kept elements joined by the
+// rule of kgpu_decode_core.h.  A word is found through `entry` -- one uint32 per list entry: where its arena entry lies, in 8-byte units -- in the initial
+// table's arena ({u32 length, u32 hash, the bytes padded to 8}).  b: n, sent_len (each line's bytes, then their offsets), text_offsets and host_ctl ([0]
+// the bytes) alone are used.
+struct DecodeArgs {
+    RecordsBatch b;
+    DecodeRule r;
+    const int32_t *ids;                // 4-byte aligned
+    const uint64_t *id_offsets;        // n + 1, or null: padded rows of `width` ids
+    uint64_t width;
+    const uint32_t *entry;             // r.n_words entries
+    const uint8_t *arena;
+    uint8_t *status;                   // n
+    uint8_t *text; uint64_t text_cap;  // nothing is stored when sent_len[n] > text_cap
+};
+int launch_decode(const DecodeArgs &a, void *stream);
+// kgpu_vocab_table.cpp (HIP-free): the id -> arena entry table of a list's byte-keyed table, from its slots (tag = hash << 32 | (arena entry / 8 + 1))
+void build_decode_entries(const VocabTables &t, uint64_t n_words, std::vector<uint32_t> &entry);
+// kgpu_decode_host.cpp (HIP-free, compiles alone): the argument rules of all three forms of the call -> KGPU_OK, or KGPU_ERR_INVALID_ARG with the error set.
+// host_offsets: id_offsets lies in host memory and is looked at.
+int decode_check_args(const char *who, const void *ids, const void *id_offsets, bool host_offsets, uint64_t n, uint64_t width, const kgpu_decode_opts *o,
+                      uint32_t prefix_len, const void *text, uint64_t text_capacity, const void *text_offsets, const void *status);
 
 int pool_workgroups_per_cu(uint32_t pool_bytes, uint32_t waves);
 int window_workgroups_per_cu(uint32_t lds_bytes);

@@ -174,6 +174,13 @@ struct kgpu_vocab {
     uint32_t max_word_chars = 0, initial_max = 0, cont_max = 0;
     void *d_cont_slots = nullptr, *d_cont_arena = nullptr, *d_wp_rows = nullptr, *d_piece_ids = nullptr, *d_piece_ends = nullptr;
     kgpu_wordpiece_info wp{};
+    // the way back (kgpu_decode_device.cpp): the continuation prefix (none on a plain handle), and the id -> arena entry table -- made with the handle, on
+    // the host; the handle's first decode call uploads it (under decode_mu) and drops the host copy.  To its callers the handle stays immutable.
+    uint8_t prefix[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint32_t prefix_len = 0;
+    mutable std::mutex decode_mu;
+    mutable std::vector<uint32_t> h_entry;
+    mutable void *d_entry = nullptr;
 };
 
 struct kgpu_ctx {

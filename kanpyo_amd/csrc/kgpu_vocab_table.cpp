@@ -84,6 +84,14 @@ int fill_vocab_table(const std::vector<VocabKey> &keys, VocabTables &out, uint32
     return KGPU_OK;
 }
 
+// The way back (include/kanpyo_gpu.h, "text from ids"): every slot names its id and its arena entry, so one pass over the slots gives entry[id] = the
+// entry's offset / 8.  The list's words are distinct and all listed: every id below n_words is met exactly once.
+void build_decode_entries(const VocabTables &t, uint64_t n_words, std::vector<uint32_t> &entry) {
+    entry.assign((size_t)n_words, 0);
+    for (const VocabSlot &s : t.slots)
+        if (s.tag != 0 && s.id >= 0 && (uint64_t)s.id < n_words) entry[(size_t)s.id] = (uint32_t)(s.tag & 0xFFFFFFFFull) - 1;
+}
+
 bool vocab_row_bytes(const WordRow *rows, size_t r, size_t n_known, const uint8_t *names, const uint8_t *key_bytes, const uint64_t *key_off, const uint8_t *&p, uint64_t &len) {
     const WordRow &row = rows[r];
     if (!(row.len_flags & WORD_SURFACE)) { p = names + row.off; len = row.len_flags & WORD_LEN_MASK; return true; }

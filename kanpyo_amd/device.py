@@ -120,6 +120,16 @@ class DeviceContext(Handle):
             self._h, C.byref(opts), n, p(d_ids_a), p(d_off_a), p(d_ids_b), p(d_off_b), n_ids_in, p(d_spans_in), p(d_tix_in), p(d_input_ids), p(d_type_ids),
             p(d_mask), p(d_spans), p(d_tix), row_capacity, p(d_row_offsets), p(d_status)))
 
+    def decode(self, vocab, d_ids: int, d_id_offsets: int, n: int, d_text: int, text_capacity: int, d_text_offsets: int, d_status: int, width: int = 0, opts=None):
+        """kgpu_decode_device: enqueue the text (include/kanpyo_gpu.h, "text from ids") of n sequences of int32 ids in HBM, by a Vocab of this context's
+        tokenizer -- one line per sequence, packed in d_text, its uint64 offsets (n + 1) in d_text_offsets and a status byte per sequence in d_status.
+        d_id_offsets (n + 1 uint64) with width 0: ragged; d_id_offsets 0 with width w: n rows of w ids.  opts: decode.decode_opts(...) (None: one space,
+        no skip list).  sync_lines (try_sync_lines) waits for it and returns the bytes, written or needed."""
+        p = lambda v: C.c_void_p(v) if v else None   # noqa: E731
+        _lib.check(_lib.lib().kgpu_decode_device(
+            self._h, vocab.handle, p(d_ids), p(d_id_offsets), n, width, C.byref(opts) if opts is not None else None, p(d_text), text_capacity,
+            p(d_text_offsets), p(d_status)))
+
     def try_sync_lines(self) -> tuple:
         """-> (fits, units): sync_lines without the exception for a capacity that was too small (nothing was written then)."""
         return self._sync("kgpu_ctx_sync_lines", raises=False)

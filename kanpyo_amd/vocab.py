@@ -306,6 +306,59 @@ class Vocab(Handle):
         spans = np.ascontiguousarray(spans.cpu().numpy()).view(np.uint32).reshape(-1, 4).copy().view(SPAN_DTYPE).reshape(-1)
         return [(ids[o[i] : o[i + 1]], spans[o[i] : o[i + 1]], tix[o[i] : o[i + 1]]) for i in range(len(o) - 1)]
 
+    # ---- the way back: text from ids (include/kanpyo_gpu.h, "text from ids") ---------------------------------------------------------------------
+    def _decode_opts(self, separator, skip):
+        from .decode import decode_opts
+
+        if skip is None:   # the specials this handle puts around a sequence itself
+            skip = [k for k in (self.bos_id, self.eos_id) if k is not None]
+        return decode_opts(separator, skip)
+
+    def decode_tensor(self, ids, offsets=None, separator=" ", skip=None):
+        """Ids on the device (torch tensors, as encode_tensor leaves them) -> their text on the device, in ONE DeviceContext.decode: no id and no byte
+        passes through host memory.  Ragged: ids int32 [total] with offsets int64 [n + 1]; padded: ids int32 [n, w] with offsets None (name the pad id in
+        `skip`).  -> (text uint8 [bytes], text_offsets int64 [n + 1], status uint8 [n]): line s is text[text_offsets[s]:text_offsets[s + 1]], the words
+        of its ids joined by `separator` (0..8 bytes), a WordPiece continuation joined to the word in front of it without its prefix; status 1: an id
+        outside the list that `skip` does not name (it gives no text).  skip: at most 8 ids that give no text; None: this Vocab's bos and eos ids where
+        set.  Like encode_tensor it runs on a context of the Vocab's Tokenizer, which has to be open."""
+        import torch
+
+        if offsets is None and ids.dim() != 2:
+            raise ValueError("padded ids are [n, width]; ragged ids come with offsets")
+        if ids.dtype != torch.int32 or (offsets is not None and offsets.dtype != torch.int64):
+            raise ValueError("ids are int32, offsets int64")
+        opts = self._decode_opts(separator, skip)
+        ids = ids.contiguous()
+        offsets = offsets.contiguous() if offsets is not None else None
+        n = ids.shape[0] if offsets is None else offsets.numel() - 1
+        width = ids.shape[1] if offsets is None else 0
+        if n < 0 or (offsets is None and width < 1):
+            raise ValueError("offsets needs n + 1 entries; a padded row has an id at least")
+        with self._ctx_lock:
+            if self._ctx is None:
+                self._ctx = DeviceContext(self._open_tokenizer())
+            ctx = self._ctx
+            dev = torch.device("cuda", self._device)
+            d_toff, d_st = torch.empty(n + 1, dtype=torch.int64, device=dev), torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+            (count,), d_text = _stage(dev, lambda cap: torch.empty(max(cap, 1), dtype=torch.uint8, device=dev),
+                                      lambda d_text, cap: ctx.decode(self, ids.data_ptr(), offsets.data_ptr() if offsets is not None else 0, n, d_text.data_ptr(), cap,
+                                                                     d_toff.data_ptr(), d_st.data_ptr(), width=width, opts=opts),
+                                      ctx.try_sync_lines, (ids.numel() * 8 + 64,))
+        return d_text[:count], d_toff, d_st[:n]
+
+    def decode(self, sequences: Sequence, separator=" ", skip=None) -> List[bytes]:
+        """One line (bytes) per sequence of ids, over kgpu_decode_batch: host memory in and out, computed on the device.  separator and skip as
+        decode_tensor takes them.  Works on a Vocab that has outlived its Words and its Tokenizer, as the host forms of encode do."""
+        from .decode import host_call, lines
+
+        seqs = [np.asarray(s, dtype=np.int32).reshape(-1) for s in sequences]
+        offs = np.zeros(len(seqs) + 1, dtype=np.uint64)
+        if seqs:
+            offs[1:] = np.cumsum([s.size for s in seqs])
+        ids = np.concatenate(seqs) if seqs else np.zeros(0, dtype=np.int32)
+        text, toff, _ = host_call(partial(_lib.lib().kgpu_decode_batch, self._h), ids, offs, 0, self._decode_opts(separator, skip))
+        return lines(text, toff)
+
     # ---- the one-word-per-line file ----------------------------------------------------------------------------------------------------------
     def save(self, path):
         """One word per line, as raw bytes: line k (0-based) is id k.  ValueError: a word holds a newline."""
