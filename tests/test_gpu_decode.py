@@ -129,6 +129,35 @@ def test_a_plain_handle_has_no_continuation_words(small_ctx, small_env):
     v.close()
 
 
+def test_second_trips_of_the_grid_stride_loop(small_ctx, small_env):
+    """More sequences than launch_render's capped grid has wavefronts: every wavefront decodes a second sequence, in LDS rows its first one has used.  The
+    sequences are the WordPiece ids (by the reference) of test_gpu_wordpiece_adversarial.py's second-trip batch: 0 to 3 short records each, three long
+    ones at sequences 0, 32 768 and the last; ragged, and padded at width 65; the destination 3 bytes behind a 16-byte boundary."""
+    import encode_ref as E
+    import wordpiece_cases as WC
+    import wordpiece_ref as WP
+    from record_cases import SMALL_KEYS, ref_spec
+
+    n, vocab = WC.SECOND_TRIP_N, WC.second_trip_list()
+    assert n > WC.GRID_BLOCKS * WC.render_wpb()
+    recs = WC.second_trip_records(small_env.nk, small_env.nu)
+    ids, off = WP.encode(*recs, small_env.known, small_env.unk, small_env.nk, small_env.nu, ref_spec(), SMALL_KEYS, vocab, WC.UNK)
+    seqs = R.sequences_of(ids, off)
+    L = np.diff(off.astype(np.int64))
+    assert len(seqs) == n and all(L[s] > 128 for s in WC.LONG_AT) and int((L[WC.GRID_BLOCKS * WC.render_wpb():] > 0).sum()) > 100 and int((L == 0).sum()) > 1000
+    v = small_env.words().vocabulary(vocab, WC.UNK, wordpiece=True)
+    want, status = R.decode(vocab, seqs, PREFIX, b" ", [])
+    assert not any(status) and len(want[0]) > 200 and len(want[32768]) > 200 and len(want[n - 1]) > 200
+    assert check_rule_5(small_ctx, v, seqs, b" ", mis=3) == want
+    pad = len(vocab)
+    rows = E.padded(ids, off, 65, pad)
+    assert rows.shape == (n, 65) and int((L > 65).sum()) == 3 and int((rows[:, -1] != pad).sum()) == 3, "the three long sequences fill their rows, cut"
+    cut, status = R.decode(vocab, rows.tolist(), PREFIX, b" ", [pad])
+    assert not any(status) and cut[1:32768] == want[1:32768] and cut[0] != want[0]
+    assert check_rule_5(small_ctx, v, padded=(rows.reshape(-1), 65), skip=[pad], mis=3) == cut
+    v.close()
+
+
 # ---- 2. capacity, refusals --------------------------------------------------------------------------------------------------------------------------------
 def test_capacity_protocol(small_ctx, craft):
     seqs = [[A, CONT_B], [], [H3072, A], [-1]]

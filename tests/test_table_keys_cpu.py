@@ -103,6 +103,51 @@ def test_the_shared_sets():
         assert [E.key_hash(k) & (slots - 1) for k in covered] == list(range(listed - 1))
 
 
+def _printable(k):
+    return all(0x21 <= c <= 0x7E for c in k)
+
+
+def test_byte_range_argument():
+    """The range bounds every drawn byte, both ends reachable; without it the builders give what they gave (the shared sets above are byte for byte the same)."""
+    lo, hi = T.PRINTABLE
+    keys = T._draw(np.random.default_rng(1), 5000, 6, b"\x00\xff", T.PRINTABLE)
+    assert (keys[:, :2] == [0, 255]).all() and keys[:, 2:].min() == lo == 0x21 and keys[:, 2:].max() == hi == 0x7E
+    assert np.array_equal(T._draw(np.random.default_rng(1), 50, 6), T._draw(np.random.default_rng(1), 50, 6, byte_range=T.ANY)) and T.ANY == (1, 255)
+    for L, want in ((5, 15), (8, 11)):   # (the counts the draws give: 400 000 keys of 94^L are about 400 000^2 / 2^33 pairs)
+        pairs = T.colliding_pairs(L, want, 11 + (L == 8), byte_range=T.PRINTABLE)
+        assert len(pairs) == want and all(len(a) == len(b) == L and _is_pair(a, b) and _printable(a + b) for a, b in pairs)
+        assert len({k for p in pairs for k in p}) == 2 * want
+    pairs = T.cross_length_pairs(8, 7, 30, 13, byte_range=T.PRINTABLE)
+    assert len(pairs) == 30 and all(len(a) == 8 and len(b) == 7 and _is_pair(a, b) and _printable(a + b) for a, b in pairs)
+    keys = T.keys_with_home(16, 15, 12, 6, 5, byte_range=T.PRINTABLE)
+    assert len(set(keys)) == 12 and all(len(k) == 6 and _printable(k) and E.key_hash(k) & 15 == 15 for k in keys)
+    assert keys != T.keys_with_home(16, 15, 12, 6, 5)
+    words, absent, covered = T.chain(16, 15, 8, byte_range=T.PRINTABLE)
+    assert len(set(words + absent + covered)) == 8 + 4 + 7 and all(_printable(k) for k in words + absent + covered)
+    assert all(E.key_hash(k) & 15 == 15 for k in words + absent) and [E.key_hash(k) & 15 for k in covered] == list(range(7))
+    assert T.chain(16, 15, 8) != (words, absent, covered), "the printable chain is cached beside the 1..255 one, not in its place"
+
+
+def test_prefix_pairs():
+    for L, want in ((7, 4), (6, 2)):
+        pairs = T.prefix_pairs(L, want)
+        assert len(pairs) == want and len({k for p in pairs for k in p}) == 2 * want
+        assert all(len(a) == L + 1 and b == a[:L] and _is_pair(a, b) and _printable(a) for a, b in pairs), "b is a's first L bytes, with a's hash"
+        assert pairs == T.prefix_pairs(L, want)
+
+
+def test_the_wordpiece_pairs():
+    same, cross, nested = T.wordpiece_pairs()
+    assert len(same) >= 6 and {len(a) for a, _ in same} == {5, 8} and len(cross) >= 4 and len(nested) >= 2
+    assert all(len(a) == len(b) and _is_pair(a, b) for a, b in same), "equal hashes, distinct bytes"
+    assert all((len(a), len(b)) == (8, 7) and _is_pair(a, b) for a, b in cross + nested)
+    assert all(a[:7] != b for a, b in cross) and all(a[:7] == b for a, b in nested)
+    keys = [k for p in same + cross + nested for k in p]
+    assert len(set(keys)) == len(keys), "no key appears in two pairs"
+    assert all(_printable(k) for k in keys), "no byte outside 0x21..0x7E"
+    assert T.wordpiece_pairs() == (same, cross, nested)
+
+
 # ---- (b) the host builder ------------------------------------------------------------------------------------------------------------------------
 def _build(synth20k, words, unk_id=-7):
     sd, known, unk, nk, nu, _ = synth20k

@@ -1,8 +1,9 @@
 """The host side of the WordPiece ids (include/kanpyo_gpu.h, "WordPiece ids") without a device: tests/wordpiece_ref.py against the hand-derived
 tests/golden/fixture_wordpiece.json and, where `tokenizers` is installed, against tokenizers.models.WordPiece; the library's host split
 (kgpu_debug_wordpiece_split) and every row entry of a handle's tables (kgpu_debug_wordpiece_table) against the reference; both byte tables probed
-in Python; colliding keys and a wrapped chain in the CONTINUATION table; the table builder under AddressSanitizer + UBSan as a stand-alone
-program; the new symbols, the C layout of the new structs, the argument errors and the CLI's argument parsing."""
+in Python; colliding keys and a wrapped chain in the CONTINUATION table; the cases of tests/wordpiece_cases.py (what the device tests of
+tests/test_gpu_wordpiece_adversarial.py run) through the host split; the table builder under AddressSanitizer + UBSan as a stand-alone program;
+the new symbols, the C layout of the new structs, the argument errors and the CLI's argument parsing."""
 import ctypes as C
 import os
 import subprocess
@@ -12,6 +13,7 @@ import pytest
 
 import encode_ref as E
 import table_keys as TK
+import wordpiece_cases as WC
 import wordpiece_ref as WP
 import words_ref as W
 from conftest import ROOT, load_golden
@@ -229,6 +231,69 @@ def test_colliding_keys_and_a_wrapped_chain_in_the_continuation_table(synth20k):
     want = [WP.split_with(tabs, w, 100, 0) for w in words]
     assert any(len(w) == 2 for w in want) and [0] in want
     assert lib_split(vocab, words, 0) == want
+
+
+# ---- the cases of tests/test_gpu_wordpiece_adversarial.py through the HOST split: a disagreement shows on a machine without a GPU first -------------------------
+def host_agrees(case, words=None):
+    """kgpu_debug_wordpiece_split on the case's distinct words (or `words`) against wordpiece_ref, word for word."""
+    sp = case.split()
+    words = case.words() if words is None else words
+    tabs = case.tables()
+    want = [sp[w] if w in sp else WP.split_with(tabs, w, case.max_chars, WC.UNK) for w in words]
+    got = lib_split(case.vocab, words, WC.UNK, case.prefix, case.max_chars)
+    assert got == want, (case, next((w[:40], g[:8], x[:8]) for w, g, x in zip(words, got, want) if g != x))
+
+
+def test_host_split_on_colliding_prefixes():
+    for case, trios in WC.twin_cases():
+        WC.claim_twin(case, trios)
+        host_agrees(case)
+    case, pairs = WC.both_listed_case()
+    WC.claim_both_listed(case, pairs)
+    host_agrees(case)
+    for case, asked in WC.cross_length_cases():
+        WC.claim_cross(case, asked)
+        host_agrees(case)
+    for case, keys in WC.both_tables_cases():
+        WC.claim_both_tables(case, keys)
+        host_agrees(case)
+    one, rotated, keys = WC.chain_cases()
+    WC.claim_chain(one, rotated, keys)
+    host_agrees(one)
+    host_agrees(rotated)
+
+
+def test_host_split_at_the_tables_longest_entries():
+    for case in WC.longest_entry_cases():
+        WC.claim_longest(case)
+        host_agrees(case)
+
+
+@pytest.mark.parametrize("limit", WC.LIMITS)
+def test_host_split_at_max_word_chars(limit):
+    case, count = WC.limit_case(limit)
+    WC.claim_limit(case, count, limit)
+    host_agrees(case)
+    if limit == 1024:
+        WC.claim_full_window(WC.full_window_case())
+        host_agrees(WC.full_window_case())
+
+
+@pytest.mark.parametrize("limit", WC.RANDOM_LIMITS)
+@pytest.mark.parametrize("prefix", WC.PREFIXES, ids=["hashes", "at", "none", "eight-bytes"])
+def test_host_split_on_random_lists(prefix, limit):
+    """test_reference_against_tokenizers_wordpiece's draw, with the conditions asserted by the reference for every (prefix, limit), and the words of the
+    shifted layout: records that start inside a character, so the word begins with 10xxxxxx bytes -- "a character starts at byte 0"."""
+    case = WC.random_case(prefix, limit)
+    WC.claim_random(case)
+    assert len(prefix) in (0, 1, 2, 8)
+    host_agrees(case)
+    shifted = list(dict.fromkeys(w for s in WC.record_words(WC.records(case.sentences, shift=True)) for w in s))
+    inside = [w for w in shifted if w and w[0] & 0xC0 == 0x80]
+    assert len(inside) >= 100, "words that begin inside a character"
+    tabs = case.tables()
+    assert all(WP.split_with(tabs, w, limit, WC.UNK) == [WC.UNK] for w in inside), "by the reference: the first character is the stray bytes, which no list holds"
+    host_agrees(case, shifted)
 
 
 def test_table_builder_alone_under_asan_ubsan(tmp_path):
