@@ -13,10 +13,16 @@ a dead node (its tokens start in the middle of the sentence) -- or EOS itself is
 Plans: the shipped chain and a 160 KB pool through a device context (that the pool kernel served the batch is asserted from the routing counters, as
 in test_gpu_tile_groups.py), and kgpu_tokenize_batch with at most 128 sentences: the single-launch small call, the same kernel with one wavefront a
 workgroup."""
+import functools
+
 import numpy as np
 import pytest
 
+import pool_cases as PC
+import pool_model as M
 from conftest import fixture_dict_parts
+from pool_model import shape as _shape
+from test_gpu_tile_groups import MODEL_PLANS
 from test_gpu_tile_groups import PLANS as TILE_PLANS
 from test_gpu_tile_groups import _run
 
@@ -42,43 +48,41 @@ def libs():
     return _lib, oracle
 
 
-def _dict(k, negative=False):
-    from kanpyo_amd import Dict
-
+def _parts(k, negative=False):
     kws = ["あいう"] * 2 + ["い"] * k + ["う"] * 3
     p = fixture_dict_parts()
     if not negative:
         rng = np.random.default_rng(2000 + k)
         # few distinct costs: ties between predecessors are common (first minimum in insertion order, lattice.rs:125,136)
         morphs = np.stack([rng.integers(0, 5, len(kws)), rng.integers(0, 5, len(kws)), rng.integers(-3, 4, len(kws)) * 100], axis=1)
-        return Dict.from_parts(kws, morphs, 5, 5, rng.integers(-2, 3, 25) * 50, p["char_class"], p["char_category"], p["invoke_list"], p["group_list"],
-                               {0: (1, 1), 1: (1, 2), 2: (2, 1)}, [[0, 0, 4000], [1, 1, 3500]])
+        return dict(sorted_keywords=kws, morphs=morphs, conn_rows=5, conn_cols=5, conn_data=rng.integers(-2, 3, 25) * 50, char_class=p["char_class"],
+                    char_category=p["char_category"], invoke_list=p["invoke_list"], group_list=p["group_list"], unk_map={0: (1, 1), 1: (1, 2), 2: (2, 1)},
+                    unk_morphs=[[0, 0, 4000], [1, 1, 3500]])
     # the fixture's three words behind them (same first byte as the hiragana ones, then the kanji: the order the fixture itself has)
     three = [[0, 0, 1000], [1, 1, -20000], [2, 2, 1100]]
     morphs = [three[i % 3] for i in range(2)] + [three[(i + 1) % 3] for i in range(k)] + [[1, 1, -20000], [2, 2, -20000], [0, 0, 1000]] + three
     p["sorted_keywords"] = kws + list(p["sorted_keywords"])
     p["morphs"] = morphs
     p["conn_data"] = [0, 100, 200, 100, -30000, 100, 200, 100, -30000]
-    return Dict.from_parts(**p)
+    return p
+
+
+def _dict(k, negative=False):
+    from kanpyo_amd import Dict
+
+    return Dict.from_parts(**_parts(k, negative))
+
+
+@functools.lru_cache(maxsize=None)
+def _model(k, negative=False):
+    """the reservation model's view of this dictionary (tests/pool_model.py; tests/test_pool_model_cpu.py checks its shapes against the naive lattice)"""
+    return PC.Dictionary(_parts(k, negative))
 
 
 def _pyref(d):
     from oracle import pyref
 
     return pyref, pyref.PyDict(d.index_dict, d.connection_dict, d.morph_dict, d.unk_dict, d.char_category, d.invoke_list, d.group_list)
-
-
-def _shape(pyref, pd, s):
-    """-> (T, P) per start position 0..C, and the nodes, dp, pre of the naive lattice (its edges[q] holds what ends at q: BOS in edges[0]; EOS, which
-    starts at C, in edges[C + 1])."""
-    nodes, edges, dp, pre = pyref.lattice(pd, s)
-    C = len(s)
-    T = [0] * (C + 1)
-    for n in nodes[1:-1]:
-        T[n[3]] += 1
-    T[C] += 1   # EOS starts at C
-    P = [len(edges[q]) for q in range(C + 1)]
-    return list(zip(T, P)), nodes, dp, pre
 
 
 def _need(pyref, pd, s):
@@ -125,9 +129,12 @@ def _set_plan(monkeypatch, plan):
             monkeypatch.setenv(name, v)
 
 
-def _check(tok, orc, plan, alone, batch, inside, monkeypatch, d):
+def _check(tok, orc, plan, alone, batch, inside, monkeypatch, d, model):
     """every sentence of `alone` in a batch of its own, then `batch` in one; on the device-context plans the sentences for which `inside` holds must have
-    been served by the pool kernel, the rest run with the windowed kernel behind it and must not reach the general kernel"""
+    been served by the pool kernel, the rest run with the windowed kernel behind it and must not reach the general kernel.  The redo and hand-on counts
+    are the reservation model's (tests/pool_model.py), exactly: `tok` is a fresh handle, every batch on it steps the estimate by the restated rule of
+    chain_feedback (M.steer: a batch of one sentence without a redo takes 1/128 off), and every batch runs on a context of its own, so the shipped plan's
+    pool keeps its 40 KB shape (test_gpu_tile_groups.MODEL_PLANS)."""
     from kanpyo_amd import Tokenizer
 
     if plan == "small":
@@ -135,14 +142,23 @@ def _check(tok, orc, plan, alone, batch, inside, monkeypatch, d):
             _check_small(tok, orc, [s])
         _check_small(tok, orc, batch)
         return
+    est = M.EST_Q8_FRESH
+
+    def predicted(sentences, est_q8):
+        return M.counters([model.verdict(s, MODEL_PLANS[plan], est_q8)["verdict"] for s in sentences])
+
     for s in alone:
         prof = _run(tok, orc, [s])
-        assert sum(prof["deferred"]) == 0, (s, prof)   # the pool kernel served it
+        want = predicted([s], est)
+        assert sum(prof["deferred"]) == 0 and want[0] == 0, (s, prof)   # the pool kernel served it
+        assert prof["redone"][0] == want[1], (s, want, prof)
+        est = M.steer(est, want[1], 1)
     ins = [s for s in batch if inside(s)]
     beyond = [s for s in batch if not inside(s)]
     prof = _run(tok, orc, ins)
-    print(f"{plan}: {len(ins)} sentences meant for the pool kernel: deferred {prof['deferred']} redone {prof['redone']}; {len(beyond)} beyond")
-    assert sum(prof["deferred"]) == 0 and prof["redone"][0] <= len(ins), prof
+    want = predicted(ins, est)
+    print(f"{plan}: {len(ins)} sentences meant for the pool kernel: deferred {prof['deferred']} redone {prof['redone']} (est_q8 {est}); {len(beyond)} beyond")
+    assert sum(prof["deferred"]) == 0 and want[0] == 0 and prof["redone"][0] == want[1], (want, prof)
     if beyond:
         monkeypatch.setenv("KGPU_WINDOW", "24")
         tok2 = Tokenizer(d)
@@ -150,7 +166,8 @@ def _check(tok, orc, plan, alone, batch, inside, monkeypatch, d):
             prof = _run(tok2, orc, beyond)
         finally:
             tok2.close()
-        assert prof["deferred"][0] <= len(beyond) and sum(prof["deferred"][1:]) == 0, prof
+        want = predicted(beyond, M.EST_Q8_FRESH)   # (a fresh handle)
+        assert prof["deferred"][0] == want[0] <= len(beyond) and sum(prof["deferred"][1:]) == 0 and prof["redone"][0] == want[1], (want, prof)
 
 
 @pytest.mark.parametrize("plan", PLAN_NAMES)
@@ -175,7 +192,7 @@ def test_dead_positions(libs, k, plan, monkeypatch):
     _set_plan(monkeypatch, plan)
     tok, orc = Tokenizer(d), oracle.OracleTokenizer.from_dict(d)
     try:
-        _check(tok, orc, plan, BASES, _sentences(np.random.default_rng(k)), inside, monkeypatch, d)
+        _check(tok, orc, plan, BASES, _sentences(np.random.default_rng(k)), inside, monkeypatch, d, _model(k))
     finally:
         tok.close()
 
@@ -203,7 +220,7 @@ def test_dead_positions_negative_costs(libs, k, plan, monkeypatch):
     batch = [batch[i] for i in rng.permutation(len(batch))]
     inside = (lambda s: len(s) <= SHIPPED_CHARS) if plan == "shipped" else (lambda s: True)
     try:
-        _check(tok, orc, plan, BASES + DEAD_ENDS + BEHIND_TE, batch, inside, monkeypatch, d)
+        _check(tok, orc, plan, BASES + DEAD_ENDS + BEHIND_TE, batch, inside, monkeypatch, d, _model(k, True))
     finally:
         tok.close()
 

@@ -10,11 +10,17 @@ behind it): what is gathered ahead for the next group must not read a node the s
 Which kernel served a batch is asserted from the routing counters (DeviceContext.profile: `deferred`), not assumed: on the pool plans only sentences
 whose LDS need is safely below the plan's routing limit are in the asserted batch (the estimate below, with a fifth of margin, against
 max pages x page bytes of the plan); the longer ones run in a batch of their own with the windowed kernel behind the pools: those that cannot fit
-the pool must have left it, and none may reach the general kernel.  test_pool_addresses_above_64k pins the upper half-word range of the address pack:
+the pool must have left it, and none may reach the general kernel.  How many of a batch the pool kernel redoes and how many it hands on is asserted as
+the exact number tests/pool_model.py predicts (a fresh handle and one batch; tests/test_gpu_pool_limits.py aims at the limits themselves).
+test_pool_addresses_above_64k pins the upper half-word range of the address pack:
 one sentence whose node array alone is longer than 64 KB, served by a 160 KB pool."""
+import functools
+
 import numpy as np
 import pytest
 
+import pool_cases as PC
+import pool_model as M
 from conftest import fixture_dict_parts
 
 pytestmark = pytest.mark.gpu
@@ -30,6 +36,11 @@ PLANS = {
     "window": ({"KGPU_POOL": "0", "KGPU_WINDOW": "24", "KGPU_WINDOW_TEAM": "0"}, None),
     "window_team": ({"KGPU_POOL": "0", "KGPU_WINDOW": "24", "KGPU_WINDOW_TEAM": "2"}, None),
 }
+# the pool plans as tests/pool_model.py takes them: (pool bytes, wavefronts, max pages).  "shipped" leaves KGPU_POOL unset, so the chain may pick the
+# pool's shape per batch (kgpu_chain.cpp: build_chain) -- three wavefronts instead of four share the same pages of 624 bytes, and the 20 KB shape
+# needs a context that has seen a batch with an eighth of its sentences routed: every batch here runs on a context of its own (_run), so the
+# model's 40:4:32 is what decides.
+MODEL_PLANS = {"shipped": M.PLAN_SHIPPED, "pool80x8": (80 * 1024, 8, 20), "pool160x4": M.PLAN_160}
 
 
 @pytest.fixture(scope="module")
@@ -43,16 +54,33 @@ def libs():
     return _lib, oracle
 
 
-def _dict(k):
-    from kanpyo_amd import Dict
-
+def _parts(k):
     kws = ["あ"] * k + ["い"]
     rng = np.random.default_rng(1000 + k)
     # few distinct costs: ties between predecessors in different chunks of a target group are common (first minimum in insertion order, lattice.rs:125,136)
     morphs = np.stack([rng.integers(0, 5, len(kws)), rng.integers(0, 5, len(kws)), rng.integers(-3, 4, len(kws)) * 100], axis=1)
     p = fixture_dict_parts()
-    return Dict.from_parts(kws, morphs, 5, 5, rng.integers(-2, 3, 25) * 50, p["char_class"], p["char_category"], p["invoke_list"], p["group_list"],
-                           {0: (1, 1), 1: (1, 2), 2: (2, 1)}, [[0, 0, 4000], [1, 1, 3500]])
+    return dict(sorted_keywords=kws, morphs=morphs, conn_rows=5, conn_cols=5, conn_data=rng.integers(-2, 3, 25) * 50, char_class=p["char_class"],
+                char_category=p["char_category"], invoke_list=p["invoke_list"], group_list=p["group_list"], unk_map={0: (1, 1), 1: (1, 2), 2: (2, 1)},
+                unk_morphs=[[0, 0, 4000], [1, 1, 3500]])
+
+
+def _dict(k):
+    from kanpyo_amd import Dict
+
+    return Dict.from_parts(**_parts(k))
+
+
+@functools.lru_cache(maxsize=None)
+def _model(k):
+    """the reservation model's view of this dictionary (tests/pool_model.py over the lattice's shape; tests/test_pool_model_cpu.py checks that shape
+    against the naive lattice)"""
+    return PC.Dictionary(_parts(k))
+
+
+def _predicted(k, plan, sentences):
+    """-> (deferred[0], redone[0]) of one batch of these sentences on a fresh handle, by the model"""
+    return M.counters([_model(k).verdict(s, MODEL_PLANS[plan])["verdict"] for s in sentences])
 
 
 def _lds_need(k, chars):
@@ -136,7 +164,9 @@ def test_tile_groups(libs, k, plan, monkeypatch):
             prof = _run(tok, orc, inside)
             print(f"k={k} {plan}: {len(inside)} sentences meant for the pool kernel: deferred {prof['deferred']} redone {prof['redone']}; {len(beyond)} beyond")
             assert prof["deferred"][0] == 0, prof   # the pool kernel served every one of them: none left it for the windowed kernel
-            assert sum(prof["deferred"]) == 0 and prof["redone"][0] <= len(inside), prof   # ... and each was redone (reservation too small) at most once
+            # ... and redid (reservation too small) exactly those the model says: a fresh handle and one batch
+            assert _predicted(k, plan, inside)[0] == 0
+            assert sum(prof["deferred"]) == 0 and prof["redone"][0] == _predicted(k, plan, inside)[1], (prof, _predicted(k, plan, inside))
             if beyond:
                 # The longer ones: the pool kernel first, the windowed kernel (24 KB, as in the window plans: it holds four positions of 66 records)
                 # behind it.  Asserted: a sentence whose nodes, bucket entries and tiles ALONE exceed the pool's routing limit left the pool kernel,
@@ -149,9 +179,10 @@ def test_tile_groups(libs, k, plan, monkeypatch):
                     tok2.close()
                 must = sum(1 for s in beyond if _lds_floor(k, s) > limit)
                 print(f"k={k} {plan}: beyond the limit: deferred {prof['deferred']} redone {prof['redone']}; {must} of {len(beyond)} cannot fit the pool")
-                assert must <= prof["deferred"][0] <= len(beyond), (must, prof)
+                want = _predicted(k, plan, beyond)   # (tok2 is a fresh handle as well)
+                assert must <= want[0] <= len(beyond) and prof["deferred"][0] == want[0], (must, want, prof)
                 assert prof["deferred"][1] == 0 and prof["deferred"][2] == 0 and prof["deferred"][3] == 0, prof
-                assert prof["redone"][0] <= len(beyond), prof
+                assert prof["redone"][0] == want[1], (want, prof)
     finally:
         tok.close()
 
