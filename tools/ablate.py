@@ -2,9 +2,10 @@
 """Cumulative phase cost of the LDS kernel by early-stop ablation (kgpu_ctx_set_ablation),
 measured with HIP events at real occupancy.  Each value = kernel time when every
 sentence stops after phase k (1 load, 2 decode, 3 walk, 4 scan, 5 emit, 6 gather,
-7 sweep, 0 everything).  usage: python tools/ablate.py [cfg2] [n]"""
+7 sweep, 0 everything).  usage: python tools/ablate.py [cfg2] [n]
+Each value comes from a child (`ablate.py child <kind> <n>`, ABLATE_STOP in its environment: a plain program, which tools/pmc_phases.sh also
+runs under the profiler); this parent starts them through tools/measure.py's step() and stops at the first that fails or prints no RESULT."""
 import os
-import subprocess
 import sys
 
 if len(sys.argv) > 1 and sys.argv[1] == "child":
@@ -40,15 +41,20 @@ if len(sys.argv) > 1 and sys.argv[1] == "child":
     print("RESULT", p["tokenize_ms"] / p["launches"] * 1e3)
     sys.exit(0)
 
+import measure  # noqa: E402  (the parent: every child is a step of tools/measure.py, and the first that fails ends the run)
+
+if "--help" in sys.argv or "-h" in sys.argv:
+    print(__doc__)
+    sys.exit(0)
 kind = sys.argv[1] if len(sys.argv) > 1 else "cfg2"
 n = sys.argv[2] if len(sys.argv) > 2 else "4096"
 names = {1: "load", 2: "decode", 3: "walk", 4: "scan", 5: "emit", 6: "gather", 7: "sweep", 0: "all (+backtrace/tokens)"}
 prev = 0.0
 for k in (1, 2, 3, 4, 5, 6, 7, 0):
-    env = dict(os.environ, ABLATE_STOP=str(k))
-    r = subprocess.run([sys.executable, __file__, "child", kind, n], env=env, capture_output=True, text=True, timeout=300)
-    us = [float(l.split()[1]) for l in r.stdout.splitlines() if l.startswith("RESULT")]
-    if not us:
-        print("stop", k, "failed", r.stderr[-300:]); continue
+    rc, stdout, err = measure.step(["env", f"ABLATE_STOP={k}", sys.executable, os.path.abspath(__file__), "child", kind, n], 300)
+    us = [float(l.split()[1]) for l in stdout.splitlines() if l.startswith("RESULT")]
+    if rc != 0 or not us:   # nothing more is started on the device
+        print("stop", k, "failed with status", rc, err[-300:])
+        sys.exit(1)
     print(f"stop after {names[k]:26s} kernel {us[0]:8.1f} us   (+{us[0] - prev:7.1f} us)")
     prev = us[0]

@@ -2,78 +2,47 @@
 """What the word counts cost (kgpu_count.hip, kgpu_count_host.cpp), beside the wakati render on the same records and the wakati text call on the
 same block: the synthetic 392k dictionary with synth.feature_tables, cfg 2.
 
-    python tools/count_timing.py [--out profiles/experiments/count_words.txt]
+    python tools/count_timing.py [--out profiles/experiments/count_words.txt] [--only kernel|host]
 
-Every leg is a child process under its own `timeout`; a leg that ends with anything but 0 ends the run with its stderr: nothing more is started on
-the device.
-  kernel  rocprofv3 --kernel-trace over a child that tokenizes ONE 4096-sentence cfg 2 batch and the 4096-sentence hot-key batch (one dictionary word
+Legs, run by tools/measure.py (each a process of its own under a time limit; trouble in one ends the run):
+  kernel  measure.trace() per dispatch over a child that tokenizes ONE 4096-sentence cfg 2 batch and the 4096-sentence hot-key batch (one dictionary word
           repeated 32 times per sentence: tests/test_gpu_count.py::test_hot_key) on a context, leaves the records in HBM and then runs, REPS times each
           and in this order: the count for the surface and for the reading (field 7) on the cfg 2 records, the surface count on the hot-key records,
           and the two wakati renders (surface, field 7) on the cfg 2 records.  Kernel times are the trace's, per dispatch, medians over the
           repetitions behind the first two; the very first count of a handle (every unknown surface is new: probe, arena, claim) is quoted apart.
           The hot-key count is held against tokens / 88 per microsecond, what one global atomic per token on one address would cost at least.
-  host    kgpu_count_text against kgpu_tokenize_text_words on one block of 64 MiB or more (the 100k-sentence cfg 2 corpus, repeated), five windows each,
-          alternated in one process: medians and the spread of each."""
-import argparse
-import csv
-import glob
-import os
-import subprocess
-import sys
-import tempfile
+  host    kgpu_count_text against kgpu_tokenize_text_words on one block of 64 MiB or more (the 100k-sentence cfg 2 corpus, repeated) through
+          measure.alternated(): medians and the spread of each."""
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-os.environ.setdefault("KANPYO_SYNTH_CACHE", "/tmp/kanpyo_synth")
+import numpy as np
 
-import numpy as np  # noqa: E402
+import measure
 
 BATCH, REPS, SKIP = 4096, 22, 2
 ATOMICS_PER_US = 88   # one address, chip-wide (kgpu_device.h above WorkIO)
 
 
-def setup():
-    import torch  # noqa: F401  (one HIP runtime: torch's, loaded first)
-
-    from kanpyo_amd import Tokenizer, synth
-
-    sd = synth.build_dict()
-    known, unk = synth.feature_tables(sd)
-    tok = Tokenizer(sd.dict)
-    tok.set_features(known, unk)
-    return tok, sd, synth
-
-
-def leg_kernel_child():
+def kernel_child():
     import torch
 
+    from kanpyo_amd import synth
     from kanpyo_amd.device import DeviceContext
-    from kanpyo_amd.tokenizer import pack_sentences
 
-    tok, sd, synth = setup()
+    sd, tok, _, _ = measure.synthetic_tokenizer()
     dev = torch.device("cuda", 0)
     ctx = DeviceContext(tok)
     hot = synth.record_surfaces(sd)[196000]
-
-    def resident(sents):
-        u, o = pack_sentences(sents)
-        n, cap = len(o) - 1, int(o[-1]) + len(o)
-        t = (torch.from_numpy(u.copy()).to(dev), torch.from_numpy(o.astype(np.int64)).to(dev), torch.empty((cap, 6), dtype=torch.int32, device=dev),
-             torch.empty(n + 1, dtype=torch.int64, device=dev), torch.empty(n, dtype=torch.uint8, device=dev))
-        ctx.tokenize(t[0].data_ptr(), t[1].data_ptr(), n, int(o[-1]), t[2].data_ptr(), cap, t[3].data_ptr(), t[4].data_ptr())
-        return t, n, ctx.sync(), int(o[-1])
-
-    cfg2, n2, tok2, bytes2 = resident(synth.make_corpus(sd, BATCH, 1, "cfg2"))
-    hotb, nh, tokh, bytesh = resident([hot * 32] * BATCH)
+    cfg2 = measure.Resident(ctx, synth.make_corpus(sd, BATCH, 1, "cfg2"))
+    hotb = measure.Resident(ctx, [hot * 32] * BATCH)
     w_s, w_r = tok.words(), tok.words(field=7)
     text = torch.empty(8 << 20, dtype=torch.uint8, device=dev)
     text_off = torch.empty(BATCH + 1, dtype=torch.int64, device=dev)
     counted = {}
-    for name, w, (t, n) in (("count surface cfg2", w_s, (cfg2, n2)), ("count reading cfg2", w_r, (cfg2, n2)), ("count surface hot", w_s, (hotb, nh))):
+    for name, w, b in (("count surface cfg2", w_s, cfg2), ("count reading cfg2", w_r, cfg2), ("count surface hot", w_s, hotb)):
         k = w.counter()
         for _ in range(REPS):
-            ctx.count_words(k, t[0].data_ptr(), t[1].data_ptr(), n, t[2].data_ptr(), t[3].data_ptr())
+            ctx.count_words(k, *b.args())
             counted[name] = ctx.sync_count()
         info = k.info()
         print(f"INFO {name}: {counted[name]} tokens counted per launch, {info['table_slots_used']} slots and {info['key_bytes_used']} key bytes used, "
@@ -81,32 +50,18 @@ def leg_kernel_child():
         k.close()
     for w in (w_s, w_r):
         for _ in range(REPS):
-            ctx.format_words(w, cfg2[0].data_ptr(), cfg2[1].data_ptr(), n2, cfg2[2].data_ptr(), cfg2[3].data_ptr(), text.data_ptr(), text.numel(), text_off.data_ptr())
+            ctx.format_words(w, *cfg2.args(), text.data_ptr(), text.numel(), text_off.data_ptr())
             ctx.sync_lines()
-    print(f"SIZES {tok2} {bytes2} {tokh} {bytesh}", flush=True)
+    print(f"SIZES {cfg2.count} {cfg2.total} {hotb.count} {hotb.total}", flush=True)
     ctx.close()
 
 
 def leg_kernel(say):
-    with tempfile.TemporaryDirectory(dir="/tmp") as tmp:
-        cmd = ["timeout", "-k", "10", "420", "rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", tmp, "--",
-               sys.executable, os.path.abspath(__file__), "--leg", "kernel-child"]
-        r = subprocess.run(cmd, capture_output=True, text=True, cwd=tmp)
-        if r.returncode != 0:
-            raise RuntimeError(f"rocprofv3 run failed ({r.returncode}): {r.stderr[-2000:]}")
-        for ln in r.stdout.splitlines():
-            if ln.startswith("INFO "):
-                say("  " + ln[5:])
-        tok2, bytes2, tokh, bytesh = (int(x) for x in [ln for ln in r.stdout.splitlines() if ln.startswith("SIZES ")][-1].split()[1:])
-        rows = []
-        for path in glob.glob(os.path.join(tmp, "**", "*kernel_trace.csv"), recursive=True):
-            with open(path) as f:
-                for row in csv.DictReader(f):
-                    rows.append((int(row["Start_Timestamp"]), row["Kernel_Name"].split("(")[0].split("::")[-1], int(row["End_Timestamp"]) - int(row["Start_Timestamp"])))
-    rows.sort()
-    per = {}
-    for _, name, ns in rows:
-        per.setdefault(name, []).append(ns)
+    stdout, per = measure.trace(__file__, ["--leg", "kernel-child"], 420, stats=False)
+    for ln in stdout.splitlines():
+        if ln.startswith("INFO "):
+            say("  " + ln[5:])
+    tok2, bytes2, tokh, bytesh = (int(x) for x in [ln for ln in stdout.splitlines() if ln.startswith("SIZES ")][-1].split()[1:])
 
     def phases(name, k):   # the dispatches of a kernel, in time order, cut into k phases of REPS
         d = per.get(name, [])
@@ -114,7 +69,7 @@ def leg_kernel(say):
             raise RuntimeError(f"{name}: {len(d)} dispatches in the trace, expected {k * REPS}; kernels seen: {sorted(per)}")
         return [d[i * REPS : (i + 1) * REPS] for i in range(k)]
 
-    med = lambda v: float(np.median(v[SKIP:])) / 1e3   # noqa: E731
+    med = lambda v: measure.summary(v[SKIP:])[0] / 1e3   # noqa: E731
     cw, cp = phases("k_count_words", 3), phases("k_count_publish", 3)
     wl, ww, sc = phases("k_words_len", 2), phases("k_words_write", 2), phases("k_lines_scan", 2)
     say(f"  the cfg 2 batch: {BATCH} sentences, {bytes2} bytes, {tok2} records; the hot-key batch: {BATCH} sentences, {bytesh} bytes, {tokh} records")
@@ -136,7 +91,9 @@ def leg_kernel(say):
 
 
 def leg_host(say):
-    tok, sd, synth = setup()
+    from kanpyo_amd import synth
+
+    sd, tok, _, _ = measure.synthetic_tokenizer()
     sents = synth.make_corpus(sd, 100_000, 1, "cfg2")
     one = "".join(s + "\n" for s in sents).encode()
     block = np.frombuffer(one * (-(-(64 << 20) // len(one))), dtype=np.uint8)
@@ -147,14 +104,8 @@ def leg_host(say):
     count = lambda: k.add_text(block)       # noqa: E731
     text, _, _ = wakati()
     count()
-    ts = {"wakati": [], "count": []}
-    for _ in range(5):   # alternated in one process
-        for name, f in (("wakati", wakati), ("count", count)):
-            t0 = time.perf_counter()
-            f()
-            ts[name].append(time.perf_counter() - t0)
-    med = {n: float(np.median(v)) for n, v in ts.items()}
-    spread = {n: (max(v) - min(v)) / med[n] for n, v in ts.items()}
+    ts = measure.alternated({"wakati": wakati, "count": count})
+    med, spread = ({n: measure.summary(v)[i] for n, v in ts.items()} for i in (0, 1))
     info = k.info()
     say(f"host block in, {block.size} bytes = {block.size / (1 << 20):.1f} MiB, {lines} lines; five windows each, alternated (the Python wrappers' own buffers included):")
     say(f"  kgpu_tokenize_text_words : {lines / med['wakati'] / 1e6:6.2f} M sentences/s, {med['wakati'] * 1e3:7.1f} ms median, spread {spread['wakati'] * 100:.0f} % of it "
@@ -172,42 +123,13 @@ def leg_host(say):
 LEGS = {"kernel": (leg_kernel, 480), "host": (leg_host, 420)}
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--leg", default=None, help=argparse.SUPPRESS)
-    ap.add_argument("--only", default=None, choices=list(LEGS))
-    args = ap.parse_args()
-    if args.leg == "kernel-child":
-        leg_kernel_child()
-        return
-    if args.leg:
-        ok = LEGS[args.leg][0](lambda s: print(s, flush=True))
-        sys.exit(0 if ok else 3)
-    from kanpyo_amd import _lib
-
-    lines = [f"# tools/count_timing.py: cfg 2, batches of {BATCH}, synthetic 392k dictionary + synth.feature_tables, no filter; medians of {REPS - SKIP} repetitions; "
-             f"library {_lib.kernel_source_hash()}"]
-    print(lines[0], flush=True)
-    ok = True
-    for name, (_, limit) in LEGS.items():
-        if args.only and name != args.only:
-            continue
-        lines.append(f"[{name}]")
-        r = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--leg", name], capture_output=True, text=True, cwd=ROOT)
-        print(r.stdout, end="", flush=True)
-        lines += r.stdout.splitlines()
-        if r.returncode not in (0, 3):   # an exception, a fault, an abort or a time limit: nothing more runs on the device
-            lines.append(f"leg {name} ended with status {r.returncode}; its stderr ends: {r.stderr[-3000:]}")
-            print(lines[-1], flush=True)
-            ok = False
-            break
-        ok = ok and r.returncode == 0
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
-    sys.exit(0 if ok else 1)
+def header():
+    return (f"# tools/count_timing.py: cfg 2, batches of {BATCH}, synthetic 392k dictionary + synth.feature_tables, no filter; medians of {REPS - SKIP} repetitions; "
+            f"library {measure.library_hash()}")
 
 
 if __name__ == "__main__":
-    main()
+    ap = measure.parser(__doc__)
+    ap.add_argument("--only", default=None, choices=list(LEGS))
+    args = ap.parse_args()
+    measure.main(__file__, args, LEGS, header, {"kernel-child": kernel_child}, skip=[n for n in LEGS if args.only and n != args.only], headings=True)

@@ -2,103 +2,108 @@
 """The `kanpyo tokenize` output's rates (kgpu_format.hip and the lines entry points) on cfg 2: 100k sentences, batches of 4096, 8 contexts,
 the synthetic 392k dictionary with synth.feature_tables.
 
-    python tools/lines_rate.py [--out profiles/experiments/lines_rate.txt]
+    python tools/lines_rate.py [--out profiles/experiments/lines_rate.txt] [--no-trace] [--host-only]
 
-Legs: device-resident records alone vs records + render (alternated in one process); the render kernels under rocprofv3 --kernel-trace
---stats (a child process running the device leg alone) with bytes per token and bytes/s; kgpu_tokenize_batch_lines end to end (host
-memory in, text out); the CLI on a file of the same sentences; dictfile.format_tokens on 2000 sentences for scale.
+Legs, run by tools/measure.py (each a process of its own under a time limit; trouble in one ends the run):
+  device   device-resident records alone against records + render through measure.pipeline_rates() (measure.pipelined() with the render as the consumer).
+  trace    measure.trace() over `--device-only` (the pipeline once per arm): the render kernels, bytes per token and bytes/s.
+  host     kgpu_tokenize_batch_lines end to end, host memory in, text out (--host-only: this leg alone, for an A/B of builds through KGPU_LIB).
+  cli      the CLI on a file of the same sentences against the bytes the CPU oracle and the feature tables give; dictfile.format_tokens on 2000
+           sentences for scale.
 
-    python tools/lines_rate.py --split [--out profiles/experiments/split_device.txt]
+    python tools/lines_rate.py --split [--out profiles/experiments/split_device.txt] [--no-trace]
 
-The input side instead (kgpu_split.hip): the device split alone on a 64 MiB and a 4 MiB block resident in HBM (HIP events around enqueue -> sync,
-and the k_split_* kernels under rocprofv3 in child processes) against the host kgpu_split_lines on the same blocks, alternated; then
-kgpu_tokenize_text_lines against split_lines + tokenize_lines_packed and the CLI's --split device against --split host on the 100k-sentence file."""
-import argparse
-import csv
-import glob
+The input side instead (kgpu_split.hip).  Legs: per block (64 MiB and 4 MiB resident in HBM) the device split alone, HIP events around enqueue -> sync,
+against the host kgpu_split_lines on the same block, alternated, then the k_split_* kernels through measure.trace(); kgpu_tokenize_text_lines against
+split_lines + tokenize_lines_packed; the CLI's --split device against --split host on the 100k-sentence file."""
 import os
-import subprocess
 import sys
 import tempfile
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-os.environ.setdefault("KANPYO_SYNTH_CACHE", "/tmp/kanpyo_synth")
+import numpy as np
 
-import numpy as np  # noqa: E402
+import measure
 
 N, BATCH, Q = 100_000, 4096, 8
 HBM_TBS, PCIE_GBS = 6.3, 63.0
+COPY_TBS = 6.29   # MI355X device-to-device copy rate
+ARGS = None       # the command line's
 
 
 def setup():
-    import torch  # noqa: F401  (one HIP runtime: torch's, loaded first)
-
-    from kanpyo_amd import Tokenizer, synth
+    from kanpyo_amd import synth
     from kanpyo_amd.tokenizer import pack_sentences
 
-    sd = synth.build_dict()
-    known, unk = synth.feature_tables(sd)
-    tok = Tokenizer(sd.dict)
-    tok.set_features(known, unk)
+    sd, tok, known, unk = measure.synthetic_tokenizer()
     sents = synth.make_corpus(sd, N, 1, "cfg2")
     return sd, tok, known, unk, sents, pack_sentences
 
 
-def device_leg(tok, sents, pack_sentences, reps=3):
-    import torch
+def header(sents_bytes):
+    return f"# tools/lines_rate.py: cfg 2, {N} sentences ({sents_bytes / N:.0f} bytes each), batches of {BATCH}, {Q} contexts; synthetic 392k dictionary + synth.feature_tables"
 
-    from kanpyo_amd.device import DeviceContext
 
-    dev = torch.device("cuda", 0)
-    batches = []
-    for lo in range(0, len(sents), BATCH):
-        u, o = pack_sentences(sents[lo : lo + BATCH])
-        n, cap = len(o) - 1, int(o[-1]) + len(o)
-        batches.append((torch.from_numpy(u.copy()).to(dev), torch.from_numpy(o.astype(np.int64)).to(dev), n, int(o[-1]), cap))
-    ctxs = [DeviceContext(tok) for _ in range(Q)]
-    bufs = []
-    for _ in range(Q):
-        cap = max(b[4] for b in batches)
-        bufs.append((torch.empty((cap, 6), dtype=torch.int32, device=dev), torch.empty(BATCH + 1, dtype=torch.int64, device=dev),
-                     torch.empty(BATCH, dtype=torch.uint8, device=dev), torch.empty(32 << 20, dtype=torch.uint8, device=dev),
-                     torch.empty(BATCH + 1, dtype=torch.int64, device=dev)))
-    stats = {"tokens": 0, "text": 0}
-    LAG = Q - 2   # batch j is synced (and its render enqueued) when batch j + LAG is submitted: LAG + 1 chains in flight, the renders of the other contexts behind them
+def device_runs(tok, sents, reps):
+    """-> {"records": [sentences/s], "render": [...]}, {arm: (tokens, bytes of text) of its last run}."""
+    render = lambda c, args, out, out_off: c.format_lines(*args, out.data_ptr(), out.numel(), out_off.data_ptr())   # noqa: E731
+    return measure.pipeline_rates(tok, sents, BATCH, Q, {"records": None, "render": render}, reps)
 
-    def run(render):
-        """Both legs run this same loop; only the render differs.  A render needs its own context's batch synced (kgpu_format_lines_device), not the others'."""
-        nb = len(batches)
-        t0 = time.perf_counter()
-        for i in range(nb + LAG):
-            if i < nb:
-                k = i % Q
-                c, (dt, dto, dst, dtext, dtexto) = ctxs[k], bufs[k]
-                stats["text"] += c.sync_lines()   # batch i - Q's render (a no-op in the records leg)
-                du, do, n, total, cap = batches[i]
-                c.tokenize(du.data_ptr(), do.data_ptr(), n, total, dt.data_ptr(), cap, dto.data_ptr(), dst.data_ptr())
-            j = i - LAG
-            if j >= 0:
-                k = j % Q
-                c, (dt, dto, dst, dtext, dtexto) = ctxs[k], bufs[k]
-                stats["tokens"] += c.sync()
-                if render:
-                    du, do, n, total, cap = batches[j]
-                    c.format_lines(du.data_ptr(), do.data_ptr(), n, dt.data_ptr(), dto.data_ptr(), dtext.data_ptr(), dtext.numel(), dtexto.data_ptr())
-        for c in ctxs:
-            stats["text"] += c.sync_lines()
-        return len(sents) / (time.perf_counter() - t0)
 
-    run(False), run(True)
-    out = {"records": [], "render": []}
-    for _ in range(reps):
-        out["records"].append(run(False))
-        stats["tokens"] = stats["text"] = 0
-        out["render"].append(run(True))   # (the counts kept are the last render run's)
-    for c in ctxs:
-        c.close()
-    return out, stats
+def device_only():
+    """The program of the trace leg."""
+    sd, tok, known, unk, sents, pack_sentences = setup()
+    _, counts = device_runs(tok, sents, reps=1)
+    print(f"COUNTS {counts['render'][0]} {counts['render'][1]} {int(pack_sentences(sents)[1][-1])}", flush=True)
+
+
+def leg_device(say):
+    sd, tok, known, unk, sents, pack_sentences = setup()
+    say(header(int(pack_sentences(sents)[1][-1])))
+    dev, counts = device_runs(tok, sents, reps=3)
+    rec, ren = measure.summary(dev["records"])[0], measure.summary(dev["render"])[0]
+    tokens, text = counts["render"]
+    say(f"device-resident, records alone:    {rec / 1e6:.1f} M sentences/s  (runs: {', '.join(f'{x / 1e6:.1f}' for x in dev['records'])})")
+    say(f"device-resident, records + render: {ren / 1e6:.1f} M sentences/s  (runs: {', '.join(f'{x / 1e6:.1f}' for x in dev['render'])}) = {ren / rec:.2f} x records alone (target >= 0.85)")
+    say(f"  {tokens} tokens, {text} bytes of text: {tokens / N:.1f} tokens and {text / N:.0f} bytes per sentence, {text / tokens:.1f} bytes per token")
+    return True
+
+
+def leg_trace(say):
+    stdout, ks = measure.trace(__file__, ["--device-only"], 400)
+    tokens, text, in_bytes = (int(x) for x in [ln for ln in stdout.splitlines() if ln.startswith("COUNTS ")][-1].split()[1:])
+    names = [k for k in ks if k.startswith("k_lines_")]
+    total_ns = sum(ks[k][1] for k in names)
+    for k in sorted(names):
+        c, ns = ks[k]
+        say(f"  {k:<28} {c} calls, {ns / 1e3 / c:8.1f} us per call, {ns / 1e6:8.2f} ms in all")
+    feat = text - tokens * 2 - in_bytes - 3 * N   # text = surfaces (input bytes + "EOS") + tab + newline + features
+    moved = tokens * 24 * 2 + in_bytes + feat + text + N * 32
+    say(f"  render kernels: {total_ns / 1e6:.2f} ms for {N} sentences; bytes moved (records read twice, surfaces, features, text written, offsets) "
+        f"{moved / 1e6:.0f} MB = {moved / tokens:.0f} B/token -> {moved / total_ns:.0f} GB/s, {moved / total_ns / (HBM_TBS * 1e3) * 100:.1f} % of {HBM_TBS} TB/s")
+    other = sum(ns for k, (c, ns) in ks.items() if k not in names)
+    calls = ks[names[0]][0] if names else 1
+    say(f"  (the same trace: tokenize chain + scan/compaction {other / 1e6:.2f} ms over twice as many batches: "
+        f"{other / 2e3 / calls:.1f} us of kernel time per 4096-sentence batch, render {total_ns / 1e3 / calls:.1f} us: "
+        f"records + render can reach at most {other / 2 / (other / 2 + total_ns):.2f} x records alone where kernel time is the bound)")
+    return True
+
+
+def leg_host(say):
+    """kgpu_tokenize_batch_lines end to end: host memory in, text out (caller-owned arrays, reused)."""
+    sd, tok, known, unk, sents, pack_sentences = setup()
+    utf8, offs = pack_sentences(sents)
+    if ARGS.host_only:
+        say(header(int(offs[-1])))
+    first, _, _ = tok.tokenize_lines_packed(utf8, offs)
+    out = (np.empty(first.size, dtype=np.uint8), np.empty(N + 1, dtype=np.uint64), np.empty(N, dtype=np.uint8))
+    tok.tokenize_lines_packed(utf8, offs, out=out)
+    ts = measure.alternated({"lines": lambda: tok.tokenize_lines_packed(utf8, offs, out=out)})["lines"]
+    dt, size = measure.summary(ts)[0], first.size
+    say(f"kgpu_tokenize_batch_lines, host in / text out: {N / dt / 1e6:.2f} M sentences/s, {size / dt / 1e9:.1f} GB/s of text "
+        f"({size / dt / 1e9 / PCIE_GBS * 100:.0f} % of PCIe Gen5 x16's {PCIE_GBS:.0f} GB/s; target 20 GB/s); median of {len(ts)}: "
+        + ", ".join(f"{size / x / 1e9:.1f}" for x in ts) + " GB/s")
+    return True
 
 
 WHITE_SPACE = "\t\n\x0b\x0c\r \x85\xa0\u1680" + "".join(map(chr, range(0x2000, 0x200B))) + "\u2028\u2029\u202f\u205f\u3000"
@@ -127,40 +132,43 @@ def expected_stdout(sd, known, unk, lines) -> bytes:
     return b"".join(out)
 
 
-def trace_leg(tmp):
-    """rocprofv3 --kernel-trace --stats of a child running the device leg alone -> {kernel: (calls, total ns)}."""
-    env = dict(os.environ)
-    cmd = ["timeout", "-k", "10", "400", "rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "--",
-           sys.executable, os.path.abspath(__file__), "--device-only"]
-    r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=tmp)
-    if r.returncode != 0:
-        raise RuntimeError(f"rocprofv3 run failed ({r.returncode}): {r.stderr[-2000:]}")
-    path = glob.glob(os.path.join(tmp, "**", "*kernel_stats.csv"), recursive=True)[0]
-    out = {}
-    with open(path) as f:
-        for row in csv.DictReader(f):
-            out[row["Name"]] = (int(row["Calls"]), float(row["TotalDurationNs"]))
-    return out
-
-
-def host_leg(tok, utf8, offs, say):
-    """kgpu_tokenize_batch_lines end to end: host memory in, text out (caller-owned arrays, reused)."""
-    first, _, _ = tok.tokenize_lines_packed(utf8, offs)
-    out = (np.empty(first.size, dtype=np.uint8), np.empty(N + 1, dtype=np.uint64), np.empty(N, dtype=np.uint8))
-    tok.tokenize_lines_packed(utf8, offs, out=out)
-    ts = []
-    for _ in range(5):
+def cli(dpath, ipath, *more):
+    """One run of the CLI on the file, a step of its own (it takes a few seconds: a minute is its limit) -> seconds, stdout.  Any status but 0
+    ends the leg, and with it the run."""
+    with open(ipath, "rb") as fi:
         t0 = time.perf_counter()
-        t, _, _ = tok.tokenize_lines_packed(utf8, offs, out=out)
-        ts.append(time.perf_counter() - t0)
-    dt = float(np.median(ts))
-    say(f"kgpu_tokenize_batch_lines, host in / text out: {N / dt / 1e6:.2f} M sentences/s, {t.size / dt / 1e9:.1f} GB/s of text "
-        f"({t.size / dt / 1e9 / PCIE_GBS * 100:.0f} % of PCIe Gen5 x16's {PCIE_GBS:.0f} GB/s; target 20 GB/s); median of {len(ts)}: "
-        + ", ".join(f"{t.size / x / 1e9:.1f}" for x in ts) + " GB/s")
+        rc, stdout, err = measure.step([sys.executable, "-m", "kanpyo_amd", "tokenize", "-c", dpath, *more], 60, stdin=fi, text=False)
+        dt = time.perf_counter() - t0
+    if rc != 0:
+        raise RuntimeError(f"CLI {' '.join(more)} exited {rc}: {err.decode(errors='replace')}")
+    return dt, stdout
 
 
-COPY_TBS = 6.29   # MI355X device-to-device copy rate
+def leg_cli(say):
+    from kanpyo_amd.dictfile import DictFile, format_tokens, save_dict
 
+    sd, tok, known, unk, sents, pack_sentences = setup()
+    df = DictFile(sd.dict, known, unk)
+    with tempfile.TemporaryDirectory(dir="/tmp") as tmp:   # the CLI on a file of the same sentences
+        dpath, ipath = os.path.join(tmp, "t.dict"), os.path.join(tmp, "in.txt")
+        save_dict(df, dpath)
+        with open(ipath, "wb") as f:
+            f.write("\n".join(s.replace("\n", " ") for s in sents).encode() + b"\n")
+        dt, stdout = cli(dpath, ipath)
+    want = expected_stdout(sd, known, unk, [s.replace("\n", " ") for s in sents])
+    say(f"python -m kanpyo_amd tokenize < {N} lines: {dt:.2f} s wall (process start, dictionary load and upload included), "
+        f"{len(stdout) / 1e6:.0f} MB of stdout, exit 0; byte-identical to the expected bytes (oracle tokens + "
+        f"MorphFeatureTable.features, lines trimmed as trim_end does): {stdout == want}")
+    toks = tok.tokenize_batch(sents[:2000])   # format_tokens, for scale
+    t0 = time.perf_counter()
+    for row in toks:
+        format_tokens(row, df)
+    dt = time.perf_counter() - t0
+    say(f"dictfile.format_tokens (Python loop over Token objects), 2000 sentences: {2000 / dt / 1e3:.1f} k sentences/s")
+    return True
+
+
+# ---- --split
 
 def split_blocks(sd):
     """The 64 MiB block of tests/test_gpu_split.py (cfg 2 sentences joined with "\n", "\r\n" and U+3000 "\n") and its first 4 MiB cut behind a newline."""
@@ -207,7 +215,7 @@ class DeviceSplit:
 
 
 def host_split_timed(block, reps):
-    """-> seconds per kgpu_split_lines call (the C function alone, buffers allocated and touched beforehand)."""
+    """-> seconds per kgpu_split_lines call (the C function alone, buffers allocated and touched beforehand), lines, bytes kept."""
     import ctypes as C
 
     from kanpyo_amd import _lib
@@ -223,84 +231,77 @@ def host_split_timed(block, reps):
 
 
 def split_child(path, reps):
-    """The child of the rocprofv3 run: `reps` device splits of the block in the file, on a small dictionary (the split needs none of it)."""
-    import torch  # noqa: F401
-
-    from kanpyo_amd import Tokenizer, synth
-
-    ds = DeviceSplit(Tokenizer(synth.build_dict(20000, seed=11).dict), np.load(path))
+    """The program of the split's trace legs: `reps` device splits of the block in the file, on a small dictionary (the split needs none of it)."""
+    ds = DeviceSplit(measure.synthetic_tokenizer(20000, seed=11)[1], np.load(path))
     for _ in range(reps):
         ds.once()
 
 
-def split_trace(tmp, path, reps):
-    cmd = ["timeout", "-k", "10", "300", "rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "--",
-           sys.executable, os.path.abspath(__file__), "--split-child", path, "--reps", str(reps)]
-    r = subprocess.run(cmd, capture_output=True, text=True, cwd=tmp)
-    if r.returncode != 0:
-        raise RuntimeError(f"rocprofv3 run failed ({r.returncode}): {r.stderr[-2000:]}")
-    out = {}
-    with open(glob.glob(os.path.join(tmp, "**", "*kernel_stats.csv"), recursive=True)[0]) as f:
-        for row in csv.DictReader(f):
-            if "k_split_" in row["Name"]:
-                out[row["Name"].split("(")[0].split("::")[-1]] = (int(row["Calls"]), float(row["TotalDurationNs"]))
-    return out
-
-
 def spread(xs, scale=1.0, unit="s"):
-    return f"median {np.median(xs) * scale:.3f} {unit} (runs: {', '.join(f'{x * scale:.3f}' for x in xs)})"
+    return f"median {measure.summary(xs)[0] * scale:.3f} {unit} (runs: {', '.join(f'{x * scale:.3f}' for x in xs)})"
 
 
-def split_main(args, say):
-    sd, tok, known, unk, sents, pack_sentences = setup()
-    from kanpyo_amd import _lib
+def leg_split(say, name):
+    sd, tok, _, _ = measure.synthetic_tokenizer()
+    block = split_blocks(sd)[name]
+    ds = DeviceSplit(tok, block)
+    n_lines, n_bytes = ds.once()
+    h_dt, h_lines, h_bytes = host_split_timed(block, 1)   # warm-up pass of both, and the same counts
+    assert (n_lines, n_bytes) == (h_lines, h_bytes), ((n_lines, n_bytes), (h_lines, h_bytes))
+    reps_d = max(3, int(0.25 / max(ds.timed(3), 1e-6)))
+    reps_h = max(1, int(0.25 / h_dt))
+    dev_t, host_t = [], []
+    for _ in range(5):   # alternated in one process
+        dev_t.append(ds.timed(reps_d))
+        host_t.append(host_split_timed(block, reps_h)[0])
+    d, h = min(dev_t), min(host_t)
+    say(f"{name} block: {block.size} bytes, {n_lines} lines, {n_bytes} bytes kept")
+    say(f"  device, input resident, HIP events around enqueue -> sync, {reps_d} per window: best of 5 {d * 1e6:.1f} us = {block.size / d / 1e9:.1f} GB/s of input"
+        f"  (windows: {', '.join(f'{x * 1e6:.1f}' for x in dev_t)} us)")
+    say(f"  host kgpu_split_lines, {reps_h} per window: best of 5 {h * 1e3:.2f} ms = {block.size / h / 1e9:.2f} GB/s of input"
+        f"  (windows: {', '.join(f'{x * 1e3:.2f}' for x in host_t)} ms)")
+    ratio, ok = h / d, True
+    line = f"  device / host: {ratio:.1f} x"
+    if name == "64 MiB":
+        ok = ratio >= 10
+        line += f"  (acceptance: >= 10 x on this block: {'met' if ok else 'NOT MET'})"
+    say(line)
+    ds.ctx.close()
+    return ok
+
+
+def leg_split_trace(say, name):
+    from kanpyo_amd import synth
+
+    block = split_blocks(synth.build_dict())[name]
+    _, n_lines, n_bytes = host_split_timed(block, 1)   # (the host function's counts are the device's: the leg before this one has checked it)
+    moved = 2 * block.size + n_bytes + (n_lines + 1) * 8
+    reps = 20 if name == "64 MiB" else 200
+    with tempfile.TemporaryDirectory(dir="/tmp") as tmp:
+        path = os.path.join(tmp, "block.npy")
+        np.save(path, block)
+        _, ks = measure.trace(__file__, ["--split-child", path, "--reps", str(reps)], 300)
+    ks = {k: v for k, v in ks.items() if k.startswith("k_split_")}
+    total = sum(ns for _, ns in ks.values())
+    for k in sorted(ks):
+        c, ns = ks[k]
+        say(f"  {k:<16} {c} calls, {ns / 1e3 / c:8.1f} us per call")
+    per = total / reps
+    say(f"  kernels (rocprofv3 --kernel-trace --stats, a run of its own): {per / 1e3:.1f} us per split; bytes moved (input read by two passes, kept bytes and offsets "
+        f"written) {moved / 1e6:.1f} MB -> {moved / per:.0f} GB/s = {moved / per / (COPY_TBS * 1e3) * 100:.1f} % of the {COPY_TBS} TB/s copy rate")
+    return True
+
+
+def file_of(sents):
+    return "\n".join(s.replace("\n", " ") for s in sents).encode() + b"\n"
+
+
+def leg_split_end_to_end(say):
+    """On the 100k-sentence file of the CLI leg."""
     from kanpyo_amd.tokenizer import split_lines
 
-    say(f"# tools/lines_rate.py --split: read_line + trim_end on the device (kgpu_split.hip) against the host kgpu_split_lines; library {_lib.kernel_source_hash()}")
-    ok = True
-    blocks = split_blocks(sd)
-    for name, block in blocks.items():
-        ds = DeviceSplit(tok, block)
-        n_lines, n_bytes = ds.once()
-        h_dt, h_lines, h_bytes = host_split_timed(block, 1)   # warm-up pass of both, and the same counts
-        assert (n_lines, n_bytes) == (h_lines, h_bytes), ((n_lines, n_bytes), (h_lines, h_bytes))
-        reps_d = max(3, int(0.25 / max(ds.timed(3), 1e-6)))
-        reps_h = max(1, int(0.25 / h_dt))
-        dev_t, host_t = [], []
-        for _ in range(5):   # alternated in one process
-            dev_t.append(ds.timed(reps_d))
-            host_t.append(host_split_timed(block, reps_h)[0])
-        d, h = min(dev_t), min(host_t)
-        moved = 2 * block.size + n_bytes + (n_lines + 1) * 8
-        say(f"{name} block: {block.size} bytes, {n_lines} lines, {n_bytes} bytes kept")
-        say(f"  device, input resident, HIP events around enqueue -> sync, {reps_d} per window: best of 5 {d * 1e6:.1f} us = {block.size / d / 1e9:.1f} GB/s of input"
-            f"  (windows: {', '.join(f'{x * 1e6:.1f}' for x in dev_t)} us)")
-        say(f"  host kgpu_split_lines, {reps_h} per window: best of 5 {h * 1e3:.2f} ms = {block.size / h / 1e9:.2f} GB/s of input"
-            f"  (windows: {', '.join(f'{x * 1e3:.2f}' for x in host_t)} ms)")
-        ratio = h / d
-        line = f"  device / host: {ratio:.1f} x"
-        if name == "64 MiB":
-            ok = ratio >= 10
-            line += f"  (acceptance: >= 10 x on this block: {'met' if ok else 'NOT MET'})"
-        say(line)
-        if not args.no_trace:
-            reps = 20 if name == "64 MiB" else 200
-            with tempfile.TemporaryDirectory(dir="/tmp") as tmp:
-                path = os.path.join(tmp, "block.npy")
-                np.save(path, block)
-                ks = split_trace(tmp, path, reps)
-            total = sum(ns for _, ns in ks.values())
-            for k in sorted(ks):
-                c, ns = ks[k]
-                say(f"  {k:<16} {c} calls, {ns / 1e3 / c:8.1f} us per call")
-            per = total / reps
-            say(f"  kernels (rocprofv3 --kernel-trace --stats, a run of its own): {per / 1e3:.1f} us per split; bytes moved (input read by two passes, kept bytes and offsets "
-                f"written) {moved / 1e6:.1f} MB -> {moved / per:.0f} GB/s = {moved / per / (COPY_TBS * 1e3) * 100:.1f} % of the {COPY_TBS} TB/s copy rate")
-        ds.ctx.close()
-
-    # end to end on the 100k-sentence file of the CLI leg
-    data = "\n".join(s.replace("\n", " ") for s in sents).encode() + b"\n"
-    block = np.frombuffer(data, dtype=np.uint8)
+    sd, tok, known, unk, sents, pack_sentences = setup()
+    block = np.frombuffer(file_of(sents), dtype=np.uint8)
     want = tok.tokenize_lines_packed(*split_lines(block))
     got = tok.tokenize_text_lines(block)
     same = all(np.array_equal(a, b) for a, b in zip(got, want))
@@ -315,125 +316,64 @@ def split_main(args, say):
         tok.tokenize_lines_packed(u, o)
         t_old.append(time.perf_counter() - t0)
         t_split.append(t1 - t0)
+    m_new, m_old, m_split = (measure.summary(x)[0] for x in (t_new, t_old, t_split))
     say(f"end to end, {N} cfg 2 lines ({block.size / 1e6:.1f} MB in, {want[0].size / 1e6:.0f} MB of text out), outputs identical: {same}")
     say(f"  tokenize_text_lines (device split):                   {spread(t_new, 1e3, 'ms')}")
     say(f"  split_lines + tokenize_lines_packed (host split):     {spread(t_old, 1e3, 'ms')}")
-    say(f"    of which split_lines (the wrapper's count pass + kgpu_split_lines): {spread(t_split, 1e3, 'ms')} = {np.median(t_split) / np.median(t_old) * 100:.0f} % of that path's wall time")
-    say(f"  -> {'the device split' if np.median(t_new) < np.median(t_old) else 'the host split + chunk pipeline'} is faster, {max(np.median(t_new), np.median(t_old)) / min(np.median(t_new), np.median(t_old)):.2f} x")
+    say(f"    of which split_lines (the wrapper's count pass + kgpu_split_lines): {spread(t_split, 1e3, 'ms')} = {m_split / m_old * 100:.0f} % of that path's wall time")
+    say(f"  -> {'the device split' if m_new < m_old else 'the host split + chunk pipeline'} is faster, {max(m_new, m_old) / min(m_new, m_old):.2f} x")
+    return same
+
+
+def leg_split_cli(say):
+    from kanpyo_amd import synth
     from kanpyo_amd.dictfile import DictFile, save_dict
 
+    sd = synth.build_dict()   # (no device in this leg's own process: the CLI runs are its steps)
+    known, unk = synth.feature_tables(sd)
     with tempfile.TemporaryDirectory(dir="/tmp") as tmp:
         dpath, ipath = os.path.join(tmp, "t.dict"), os.path.join(tmp, "in.txt")
         save_dict(DictFile(sd.dict, known, unk), dpath)
         with open(ipath, "wb") as f:
-            f.write(data)
+            f.write(file_of(synth.make_corpus(sd, N, 1, "cfg2")))
         wall, outs = {"host": [], "device": []}, {}
         for _ in range(3):
             for mode in ("host", "device"):
-                with open(ipath, "rb") as fi:
-                    t0 = time.perf_counter()
-                    r = subprocess.run(["timeout", "-k", "10", "300", sys.executable, "-m", "kanpyo_amd", "tokenize", "-c", dpath, "--split", mode], stdin=fi,
-                                       stdout=subprocess.PIPE, cwd=ROOT)
-                    wall[mode].append(time.perf_counter() - t0)
-                if r.returncode != 0:
-                    raise RuntimeError(f"CLI --split {mode} exited {r.returncode}")
-                outs[mode] = r.stdout
-        say(f"python -m kanpyo_amd tokenize < {N} lines (process start, dictionary load and upload included), stdout identical: {outs['host'] == outs['device']}")
-        say(f"  --split host:   {spread(wall['host'])}")
-        say(f"  --split device: {spread(wall['device'])}")
-        say(f"  -> {'--split device' if np.median(wall['device']) < np.median(wall['host']) else '--split host'} is faster, by {abs(np.median(wall['device']) - np.median(wall['host'])):.3f} s")
-    return ok and same
+                dt, outs[mode] = cli(dpath, ipath, "--split", mode)
+                wall[mode].append(dt)
+    m = {k: measure.summary(v)[0] for k, v in wall.items()}
+    say(f"python -m kanpyo_amd tokenize < {N} lines (process start, dictionary load and upload included), stdout identical: {outs['host'] == outs['device']}")
+    say(f"  --split host:   {spread(wall['host'])}")
+    say(f"  --split device: {spread(wall['device'])}")
+    say(f"  -> {'--split device' if m['device'] < m['host'] else '--split host'} is faster, by {abs(m['device'] - m['host']):.3f} s")
+    return True
+
+
+LEGS = {"device": (leg_device, 400), "trace": (leg_trace, 500), "host": (leg_host, 400), "cli": (leg_cli, 500)}
+SPLIT_LEGS = {"64 MiB": (lambda say: leg_split(say, "64 MiB"), 400), "64 MiB trace": (lambda say: leg_split_trace(say, "64 MiB"), 400),
+              "4 MiB": (lambda say: leg_split(say, "4 MiB"), 400), "4 MiB trace": (lambda say: leg_split_trace(say, "4 MiB"), 400),
+              "end to end": (leg_split_end_to_end, 400), "cli": (leg_split_cli, 500)}   # (six CLI steps of 60 s at the most)
 
 
 def main():
-    ap = argparse.ArgumentParser()
+    global ARGS
+    ap = measure.parser(__doc__, no_trace=True)
     ap.add_argument("--split", action="store_true", help="the input side: the device split against the host splitter")
-    ap.add_argument("--split-child", default=None, help=argparse.SUPPRESS)
-    ap.add_argument("--reps", type=int, default=1, help=argparse.SUPPRESS)
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--device-only", action="store_true")
-    ap.add_argument("--no-trace", action="store_true")
+    ap.add_argument("--split-child", default=None, help=measure.argparse.SUPPRESS)
+    ap.add_argument("--reps", type=int, default=1, help=measure.argparse.SUPPRESS)
+    ap.add_argument("--device-only", action="store_true", help="the pipeline of the device leg once per arm, nothing printed but its counts: the trace leg's program")
     ap.add_argument("--host-only", action="store_true", help="the kgpu_tokenize_batch_lines leg alone (A/B of builds through KGPU_LIB)")
-    args = ap.parse_args()
+    ARGS = args = ap.parse_args()
     if args.split_child:
         split_child(args.split_child, args.reps)
-        return
-    if args.split:
-        lines = []
-        ok = split_main(args, lambda s: (print(s, flush=True), lines.append(s)))
-        if args.out:
-            with open(args.out, "w") as f:
-                f.write("\n".join(lines) + "\n")
-        sys.exit(0 if ok else 1)
-    sd, tok, known, unk, sents, pack_sentences = setup()
-    if args.device_only:
-        device_leg(tok, sents, pack_sentences, reps=1)
-        return
-    lines = []
-    say = lambda s: (print(s, flush=True), lines.append(s))  # noqa: E731
-    utf8, offs = pack_sentences(sents)
-    say(f"# tools/lines_rate.py: cfg 2, {N} sentences ({int(offs[-1]) / N:.0f} bytes each), batches of {BATCH}, {Q} contexts; synthetic 392k dictionary + synth.feature_tables")
-
-    if args.host_only:
-        host_leg(tok, utf8, offs, say)
-        return
-    dev, st = device_leg(tok, sents, pack_sentences)
-    rec, ren = np.median(dev["records"]), np.median(dev["render"])
-    tokens, text = st["tokens"], st["text"]
-    say(f"device-resident, records alone:    {rec / 1e6:.1f} M sentences/s  (runs: {', '.join(f'{x / 1e6:.1f}' for x in dev['records'])})")
-    say(f"device-resident, records + render: {ren / 1e6:.1f} M sentences/s  (runs: {', '.join(f'{x / 1e6:.1f}' for x in dev['render'])}) = {ren / rec:.2f} x records alone (target >= 0.85)")
-    say(f"  {tokens} tokens, {text} bytes of text: {tokens / N:.1f} tokens and {text / N:.0f} bytes per sentence, {text / tokens:.1f} bytes per token")
-
-    if not args.no_trace:
-        with tempfile.TemporaryDirectory(dir="/tmp") as tmp:
-            ks = trace_leg(tmp)
-        names = [k for k in ks if "k_lines_" in k]
-        total_ns = sum(ks[k][1] for k in names)
-        for k in sorted(names):
-            c, ns = ks[k]
-            say(f"  {k.split('(')[0]:<28} {c} calls, {ns / 1e3 / c:8.1f} us per call, {ns / 1e6:8.2f} ms in all")
-        feat = text - tokens * 2 - int(offs[-1]) - 3 * N   # text = surfaces (input bytes + "EOS") + tab + newline + features
-        moved = tokens * 24 * 2 + int(offs[-1]) + feat + text + N * 32
-        say(f"  render kernels: {total_ns / 1e6:.2f} ms for {N} sentences; bytes moved (records read twice, surfaces, features, text written, offsets) "
-            f"{moved / 1e6:.0f} MB = {moved / tokens:.0f} B/token -> {moved / total_ns:.0f} GB/s, {moved / total_ns / (HBM_TBS * 1e3) * 100:.1f} % of {HBM_TBS} TB/s")
-        other = sum(ns for k, (c, ns) in ks.items() if k not in names)
-        calls = ks[names[0]][0] if names else 1
-        say(f"  (the same trace: tokenize chain + scan/compaction {other / 1e6:.2f} ms over twice as many batches: "
-            f"{other / 2e3 / calls:.1f} us of kernel time per 4096-sentence batch, render {total_ns / 1e3 / calls:.1f} us: "
-            f"records + render can reach at most {other / 2 / (other / 2 + total_ns):.2f} x records alone where kernel time is the bound)")
-
-    host_leg(tok, utf8, offs, say)
-
-    # the CLI on a file of the same sentences
-    from kanpyo_amd.dictfile import DictFile, save_dict
-
-    with tempfile.TemporaryDirectory(dir="/tmp") as tmp:
-        dpath, ipath = os.path.join(tmp, "t.dict"), os.path.join(tmp, "in.txt")
-        save_dict(DictFile(sd.dict, known, unk), dpath)
-        with open(ipath, "wb") as f:
-            f.write("\n".join(s.replace("\n", " ") for s in sents).encode() + b"\n")
-        with open(ipath, "rb") as fi:
-            t0 = time.perf_counter()
-            r = subprocess.run([sys.executable, "-m", "kanpyo_amd", "tokenize", "-c", dpath], stdin=fi, stdout=subprocess.PIPE, cwd=ROOT, timeout=600)
-            dt = time.perf_counter() - t0
-        want = expected_stdout(sd, known, unk, [s.replace("\n", " ") for s in sents])
-        say(f"python -m kanpyo_amd tokenize < {N} lines: {dt:.2f} s wall (process start, dictionary load and upload included), "
-            f"{len(r.stdout) / 1e6:.0f} MB of stdout, exit {r.returncode}; byte-identical to the expected bytes (oracle tokens + "
-            f"MorphFeatureTable.features, lines trimmed as trim_end does): {r.stdout == want}")
-
-    # format_tokens, for scale
-    from kanpyo_amd.dictfile import format_tokens
-
-    df = DictFile(sd.dict, known, unk)
-    toks = tok.tokenize_batch(sents[:2000])
-    t0 = time.perf_counter()
-    for row in toks:
-        format_tokens(row, df)
-    dt = time.perf_counter() - t0
-    say(f"dictfile.format_tokens (Python loop over Token objects), 2000 sentences: {2000 / dt / 1e3:.1f} k sentences/s")
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    elif args.device_only:
+        device_only()
+    elif args.split:
+        measure.main(__file__, args, SPLIT_LEGS, lambda: f"# tools/lines_rate.py --split: read_line + trim_end on the device (kgpu_split.hip) against the host kgpu_split_lines; library {measure.library_hash()}",
+                     skip=[n for n in SPLIT_LEGS if args.no_trace and n.endswith("trace")], leg_args=["--split"])
+    else:   # (no header of the parent's: the first leg says it, with the size of the corpus it has built)
+        skip = [n for n in LEGS if n != "host"] if args.host_only else ["trace"] if args.no_trace else []
+        measure.main(__file__, args, LEGS, None, skip=skip, leg_args=["--host-only"] if args.host_only else [])
 
 
 if __name__ == "__main__":
