@@ -139,6 +139,35 @@ __device__ __forceinline__ uint32_t backtrace_path(uint32_t a_y, uint32_t a_path
     return min(k, C + 1);
 }
 
+// The decode phase's view of the staged text: byte k and the three behind it in ONE register -- the two aligned dwords around k and a byte-align (the
+// text starts on an 8-byte boundary of LDS and is staged with four bytes of 0x80 behind its end, so the window of any k <= B is staged bytes; the
+// second dword of the last ones may reach into the per-position arrays behind the text -- inside the reservation, and shifted out).
+__device__ __forceinline__ uint32_t text_window(const uint8_t *text, uint32_t k) {
+    const uint32_t *p = (const uint32_t *)(text + (k & ~3u));
+    return __builtin_amdgcn_alignbyte(p[1], p[0], k & 3u);
+}
+// utf8_decode_lead (kgpu_device.h) over such a window, without its loop: win = the lead byte at k (not 10xxxxxx) and the three bytes behind it.  The same
+// sequence length, cp and bad for every input -- a continuation byte is looked at exactly when that loop looks at it (j < l, l after the k + l > B test).
+__device__ __forceinline__ uint32_t utf8_decode_window(uint32_t win, uint32_t k, uint32_t B, uint32_t &cp, uint32_t &bad) {
+    // (selects and bit arithmetic throughout -- `|` and `&` on the tests, not `||` and `&&`: written with ifs this compiles to a tree of exec masks)
+    const uint32_t b = win & 0xFFu;
+    const uint32_t is1 = b < 0x80u, is2 = b - 0xC2u <= 0xDFu - 0xC2u, is3 = (b & 0xF0u) == 0xE0u, is4 = b - 0xF0u <= 4u;
+    const uint32_t l0 = is2 ? 2u : is3 ? 3u : is4 ? 4u : 1u;
+    const uint32_t c0 = b & (is1 ? 0x7Fu : is2 ? 0x1Fu : is3 ? 0x0Fu : is4 ? 0x07u : 0u);
+    const uint32_t cut = k + l0 > B;                        // the sequence runs past the end
+    const uint32_t l = cut ? 1u : l0;
+    const uint32_t c1 = (c0 << 6) | ((win >> 8) & 0x3Fu), c2 = (c1 << 6) | ((win >> 16) & 0x3Fu), c3 = (c2 << 6) | ((win >> 24) & 0x3Fu);
+    cp = l == 1u ? c0 : l == 2u ? c1 : l == 3u ? c2 : c3;
+    const uint32_t notcont = ((win >> 8) & 0xC0C0C0u) ^ 0x808080u;   // byte j - 1 of it: non-zero when window byte j is not 10xxxxxx
+    const uint32_t looked = (1u << (8u * (l - 1u))) - 1u;            // ... and the bytes j < l
+    bad |= (is1 | is2 | is3 | is4) ^ 1u;
+    bad |= cut;
+    bad |= (notcont & looked) != 0u;
+    bad |= (l == 3u) & ((cp < 0x800u) | (cp - 0xD800u <= 0x7FFu));
+    bad |= (l == 4u) & (cp - 0x10000u > 0xFFFFFu);
+    return l;
+}
+
 }  // namespace
 
 // PROF: device-side work counters + per-phase shader clocks (KGPU_PROFILE_WORK).  A separate
@@ -275,6 +304,13 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(KGPU_POOL_
         KGPU_TM(const uint64_t tm_p1 = __builtin_amdgcn_s_memtime(); tmPool += tm_p1 - tm_p0;)
         if (pg == NONE) { defer_s(s); continue; }
         for (uint32_t attempt = 0;; ++attempt) {  // at most one redo, with the exact size
+        // (B and C pass through an empty asm at the top of every attempt: left visible, everything an attempt derives from them -- the carve's offsets, loop
+        // bounds, a dozen wave-uniform tests kept as 64-bit lane masks -- is hoisted in front of this loop, held across the whole sentence and, with
+        // 102 SGPRs, spilled to VGPR lanes here and read back where it is used; opaque, a test is a scalar compare in front of its branch)
+        uint32_t B_at = B, C_at = C;
+        asm volatile("" : "+s"(B_at), "+s"(C_at));
+        {
+        const uint32_t B = B_at, C = C_at;
         uint8_t *smem = pool + POOL_HDR + pg * page;
         const uint32_t lds_bytes = npg * page;
 
@@ -323,13 +359,16 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(KGPU_POOL_
         uint32_t cb = 0, bad = 0, lensum = 0;
         for (uint32_t k0 = 0; k0 < B; k0 += 64) {
             const uint32_t k = k0 + lane;
-            const uint32_t b = k < B ? text[k] : 0x80u;
-            const bool start = k < B && (b & 0xC0) != 0x80;
+            // (lanes past the end look at the padding behind it: 0x80, no start -- no exec mask around the reads, and every lane decodes: what is
+            // not a start is decoded for nothing and dropped, which is cheaper than the masks of a divergent loop over the continuation bytes)
+            const uint32_t win = text_window(text, min(k, B));
+            const bool start = (win & 0xC0u) != 0x80u;
             const uint64_t m = __ballot(start);
             const uint32_t ci = cb + __popcll(m & ((1ull << lane) - 1));
+            uint32_t cp, bd = 0;
+            const uint32_t l = utf8_decode_window(win, k, B, cp, bd);
             if (start) {
-                uint32_t cp;
-                const uint32_t l = utf8_decode_lead(b, k, B, [&](uint32_t kk) -> uint32_t { return text[kk]; }, cp, bad);
+                bad |= bd;
                 lensum += l;
                 cbyte[ci] = (uint16_t)k;
                 cp16[ci] = (uint16_t)(cp < 0xFFFFu ? cp : 0xFFFFu);
@@ -459,9 +498,10 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(KGPU_POOL_
             const uint32_t x = ABSENT_TILES ? (v ? tile_groups(v) * max(1u, tile_groups(w)) : 0u) : tile_count(v, w);  // tiles of position i
             const uint32_t vs = wave_incl_scan(v, lane), ws = wave_incl_scan(w, lane), xs = wave_incl_scan(x, lane);
             if (i < C + 2) { nb[i] = ncarry + vs - v; boff[i] = bcarry + ws - w; ebase[i] = tcarry + xs - x; }
-            ncarry += __shfl(vs, 63, 64);
-            bcarry += __shfl(ws, 63, 64);
-            tcarry += __shfl(xs, 63, 64);
+            // (lane 63's totals by v_readlane, into SGPRs: the carries are wave-uniform -- a __shfl is a trip through the LDS crossbar each)
+            ncarry += (uint32_t)__builtin_amdgcn_readlane((int)vs, 63);
+            bcarry += (uint32_t)__builtin_amdgcn_readlane((int)ws, 63);
+            tcarry += (uint32_t)__builtin_amdgcn_readlane((int)xs, 63);
             if constexpr (PROF) Esum += (uint64_t)v * w;  // relaxations at i (lattice.rs:122-125): the work counter E
         }
         // scalarise: the carve and the fit test below must be wave-uniform branches
@@ -588,19 +628,28 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(KGPU_POOL_
         // 3c, lane = start position: its tiles (the descriptors of kgpu_device.h: tile_desc0); (a, b) = (target group, predecessor chunk), b fastest: tile_groups(P)
         // chunks for each of the tile_groups(T) groups -- tile_count(T, P) descriptors from ebase[q] on, as the scan counted them.  A dead position (P = 0)
         // writes none (3b has written its nodes' result); a sentence may have no tile at all (one character nothing starts at: EOS alone, dead).
+        // ONE loop over the lane's descriptors, (ta, b) stepped along: it runs until the busiest position of the round is through, and a lane that is through
+        // repeats its last store -- the same word to the same address -- so there is no exec mask inside it (the rule stage B lives by); positions
+        // without a tile are masked once, around the loop.
         for (uint32_t q0 = 0; q0 <= C; q0 += 64) {
-            const uint32_t q = q0 + lane;
-            if (q <= C) {
-                const uint32_t t0 = nb[q], Tr = nb[q + 1] - t0, p0r = boff[q], Pr = boff[q + 1] - p0r;
-                const uint32_t p0 = ABSENT_TILES && !Pr ? Nb + 1 : p0r, P = ABSENT_TILES && !Pr ? 1u : Pr;
-                const uint32_t T = P ? Tr : 0u;   // a dead position: no group, so a group has at least one chunk
-                uint32_t k = ebase[q];
-                const uint32_t kb = tile_groups(P);
-                for (uint32_t ta = 0; ta < T; ta += 8)
-                    for (uint32_t b = 0;;) {
-                        tiles[k++] = make_uint2(tile_desc0(a_node + 8 * (t0 + ta), min(8u, T - ta), min(8u, P - 8 * b), b == 0, b == kb - 1), a_bk + 8 * (p0 + 8 * b));
-                        if (++b >= kb) break;
-                    }
+            const uint32_t q = q0 + lane, qc = min(q, C);   // (lanes past C read position C's entries and write nothing)
+            const uint32_t t0 = nb[qc], Tr = nb[qc + 1] - t0, p0r = boff[qc], Pr = boff[qc + 1] - p0r;
+            const uint32_t p0 = ABSENT_TILES && !Pr ? Nb + 1 : p0r, P = ABSENT_TILES && !Pr ? 1u : Pr;
+            const uint32_t T = P ? Tr : 0u;   // a dead position: no group, so a group has at least one chunk
+            const uint32_t kb = tile_groups(P);
+            const uint32_t n = q <= C ? tile_groups(T) * kb : 0u;
+            if (n) {
+                uint32_t k = ebase[qc], ta = 0, b = 0;
+                const uint32_t kend = k + n;
+                bool more;
+                do {
+                    tiles[k] = make_uint2(tile_desc0(a_node + 8 * (t0 + ta), min(8u, T - ta), min(8u, P - 8 * b), b == 0, b == kb - 1), a_bk + 8 * (p0 + 8 * b));
+                    more = k + 1 < kend;
+                    const bool wrap = b + 1 == kb;   // the group's last chunk: on to the next group
+                    ta += (more & wrap) ? 8u : 0u;
+                    b = more ? (wrap ? 0u : b + 1) : b;
+                    k += more ? 1u : 0u;
+                } while (__ballot(more) != 0);
             }
         }
         const uint32_t null0 = (a_node + 8 * N) | TILE_FIRST;   // what the last group gathers for the tiles it does not have: a target group that is never reduced (M[BOS's right][0]: always in the matrix)
@@ -636,13 +685,21 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(KGPU_POOL_
             // (any power of two >= the highest one in C may start the search -- a probe past the end is clamped onto nb[C + 1] -- so up to 255 characters it is eight
             // steps with nothing between them; beyond, the loop)
             const uint32_t hb = 1u << (31 - __clz((int)max(C, 1u)));
-            auto start_of = [&](uint32_t t) {
+            auto start_loop = [&](uint32_t t) {
                 uint32_t lo = 0;
-                if (C < 256) {
+                for (uint32_t st = hb; st; st >>= 1) { const uint32_t m = min(lo + st, C + 1); if (nb[m] <= t) lo = m; }
+                return lo;
+            };
+            auto start_of = [&](uint32_t t) {
+                if (C >= 256) return start_loop(t);
+                uint32_t lo = 0;
+                // (below 64 characters the steps of 128 and 64 find nothing -- both probes are clamped onto nb[C + 1] = N > t: a wave-uniform skip)
+                if (C >= 64) {
 #pragma unroll
-                    for (uint32_t st = 128; st; st >>= 1) { const uint32_t m = min(lo + st, C + 1); if (nb[m] <= t) lo = m; }
-                } else
-                    for (uint32_t st = hb; st; st >>= 1) { const uint32_t m = min(lo + st, C + 1); if (nb[m] <= t) lo = m; }
+                    for (uint32_t st = 128; st >= 64; st >>= 1) { const uint32_t m = min(lo + st, C + 1); if (nb[m] <= t) lo = m; }
+                }
+#pragma unroll
+                for (uint32_t st = 32; st; st >>= 1) { const uint32_t m = min(lo + st, C + 1); if (nb[m] <= t) lo = m; }
                 return lo;
             };
             for (uint32_t k0 = 0; k0 < K; k0 += 64) {
@@ -650,7 +707,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(KGPU_POOL_
                 const uint32_t t = path[K - 1 - min(k, K - 1)];
                 const uint32_t st = start_of(t);
                 uint32_t en = (uint32_t)__builtin_amdgcn_update_dpp((int)st, (int)st, 0x130 /* wave_shl:1: lane l reads lane l + 1 */, 0xF, 0xF, false);
-                if (lane == 63 && k + 1 < K) en = start_of(path[K - 2 - k]);   // (more than 64 tokens: the successor belongs to the next round)
+                if (lane == 63 && k + 1 < K) en = start_loop(path[K - 2 - k]);   // (more than 64 tokens: the successor belongs to the next round; rare: the loop)
                 if (k < K) {
                     const int32_t sid = nSid[t];
                     kgpu_token tk;
@@ -679,6 +736,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(KGPU_POOL_
             accP[6] += tick[6] - tick[5] - cyc_gather; accP[7] += t7 - tick[6]; accP[8] += 1;
         }
         break;
+        }
         }  // attempt
         if (pg != NONE) pool_free(bm, pg, 0, npg, lane);
     }
