@@ -33,6 +33,7 @@
 #include <type_traits>
 
 #include "kgpu_device.h"
+#include "kgpu_backtrace_core.h"
 
 namespace kgpu {
 
@@ -100,43 +101,45 @@ __device__ __forceinline__ uint32_t pool_wait_alloc(uint64_t *bm, uint32_t k, ui
 }
 
 
-// The backtrace (lattice.rs:144-153), one lane: node `last` (EOS), then best predecessors (the low half of node[].y; a_y = LDS address of node[0].y) until a
-// node has none -- BOS, or a node nothing reached; the indices go to the half-words at a_path, last first.  -> their count.  The walk costs the whole
-// wavefront a slot of four cycles per instruction for one lane's work, K times a sentence, and the compiler's version of this loop is seventeen instructions a
-// step (exec-mask bookkeeping for the divergent exit, the loaded half-word zero-extended again, values moved between registers): spelled out it is the
-// address (one shift-add), the read, the test, the exit branch, the path's store -- two steps a round so that nothing moves, then the cursor, the count and
-// the bound (node indices fall strictly along a path, so it ends within C + 1 steps; the walk is bounded all the same -- a round may run one step over: the
-// two bytes behind path[] are the dead category array's -- and the count clamped).
-__device__ __forceinline__ uint32_t backtrace_path(uint32_t a_y, uint32_t a_path, uint32_t last, uint32_t C) {
-    uint32_t pos = last, pa = a_path, ad, pr, k;
+// The backtrace (lattice.rs:144-153) over QUADS (kgpu_backtrace_core.h): once the sweep is through, a node's 8 bytes hold its four nearest ancestors -- y = p1 |
+// p2 << 16, x = p3 | p4 << 16, NONE16 where a chain has ended -- written by the two doubling passes in front of this (phase 5).  One lane walks from node `last`
+// (EOS): a round reads the node's two words (two reads issued together, one round trip: inline assembly cannot name the halves of a 64-bit operand), writes
+// pos, p1, p2, p3 to the path as two words and goes on from p4 while that is a node -- a quarter of the dependent round trips (address, read, wait, compare,
+// branch on vcc) of a walk over single predecessors, which is what a step costs: the other 63 lanes wait.  Spelled out as before (the compiler's loop over
+// single steps was seventeen instructions a step); fourteen instructions a round.  -> K, by the header's rule from the entries in front of the last round and
+// that round's words: the entries that count are the nodes with a predecessor of their own (BOS is not written as far as K goes), min(., C + 1).
+//   a_node: LDS address of node[0]; a_path: of path[0], a multiple of 4 (the carve: align_up(B + 4, 4) + 20 (C + 2) behind a 16-byte aligned base).
+//   Bounded: a round starts while k <= C (node indices fall strictly along a path, so it never gets there); on that exit the last quad was whole and the
+//   count taken back so that the rule adds it once.
+//   A round writes four half-words whatever the chain's length: up to bt_path_overrun_bytes(C) <= 4 bytes behind path[C + 1] -- the first bytes of ccat[], at
+//   least align_up(C + 2, 4) >= 4 bytes for every C (C = 0 included), inside the reservation (need1 counts them) and dead since emit 3a.
+__device__ __forceinline__ uint32_t backtrace_quads(uint32_t a_node, uint32_t a_path, uint32_t last, uint32_t C) {
+    uint32_t pos = last, pa = a_path, ad, x, y, w0, w1, k;
     asm volatile(
         "s_mov_b32 %[k], 0\n"
         "Lbt_loop%=:\n\t"
-        "v_lshl_add_u32 %[ad], %[pos], 3, %[ay]\n\t"
-        "ds_read_u16 %[pr], %[ad]\n\t"
+        "v_lshl_add_u32 %[ad], %[pos], 3, %[an]\n\t"
+        "ds_read_b32 %[y], %[ad] offset:4\n\t"
+        "ds_read_b32 %[x], %[ad]\n\t"
         "s_waitcnt lgkmcnt(0)\n\t"
-        "v_cmp_eq_u32_e32 vcc, 0xffff, %[pr]\n\t"
-        "s_cbranch_vccnz Lbt_done%=\n\t"
-        "ds_write_b16 %[pa], %[pos]\n\t"
-        "v_lshl_add_u32 %[ad], %[pr], 3, %[ay]\n\t"
-        "ds_read_u16 %[pos], %[ad]\n\t"
-        "s_waitcnt lgkmcnt(0)\n\t"
+        "v_lshl_or_b32 %[w0], %[y], 16, %[pos]\n\t"      // bt_quad_word0
+        "v_alignbit_b32 %[w1], %[x], %[y], 16\n\t"       // bt_quad_word1
+        "v_lshrrev_b32_e32 %[pos], 16, %[x]\n\t"         // bt_quad_next
+        "ds_write2_b32 %[pa], %[w0], %[w1] offset1:1\n\t"
         "v_cmp_eq_u32_e32 vcc, 0xffff, %[pos]\n\t"
-        "s_cbranch_vccnz Lbt_odd%=\n\t"
-        "ds_write_b16 %[pa], %[pr] offset:2\n\t"
-        "v_add_u32_e32 %[pa], 4, %[pa]\n\t"
-        "s_add_u32 %[k], %[k], 2\n\t"
+        "s_cbranch_vccnz Lbt_done%=\n\t"
+        "v_add_u32_e32 %[pa], 8, %[pa]\n\t"
+        "s_add_u32 %[k], %[k], 4\n\t"
         "s_cmp_le_u32 %[k], %[c]\n\t"
         "s_cbranch_scc1 Lbt_loop%=\n\t"
-        "s_branch Lbt_done%=\n"
-        "Lbt_odd%=:\n\t"
-        "s_add_u32 %[k], %[k], 1\n"
+        "s_sub_u32 %[k], %[k], 4\n"
         "Lbt_done%=:\n\t"
         "s_waitcnt lgkmcnt(0)"
-        : [k] "=&s"(k), [pos] "+v"(pos), [pa] "+v"(pa), [ad] "=&v"(ad), [pr] "=&v"(pr)
-        : [ay] "s"(a_y), [c] "s"(C)
+        : [k] "=&s"(k), [pos] "+v"(pos), [pa] "+v"(pa), [ad] "=&v"(ad), [x] "=&v"(x), [y] "=&v"(y), [w0] "=&v"(w0), [w1] "=&v"(w1)
+        : [an] "s"(a_node), [c] "s"(C)
         : "vcc", "scc", "memory");
-    return min(k, C + 1);
+    static_assert(BT_NONE == NONE16 && BT_QUAD == 4, "the assembly above");
+    return bt_path_count(k, x, y, C);
 }
 
 // The decode phase's view of the staged text: byte k and the three behind it in ONE register -- the two aligned dwords around k and a byte-align (the
@@ -512,7 +515,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(KGPU_POOL_
         // lie over it: a sentence's peak is max(3a's, the sweep's), not their sum.  A node's start position is not kept: the tokens look it up in nb[].
         off = align_up(off, 8);
         uint2 *node = (uint2 *)(smem + off);        off += 8 * (N + 1);  // {word cost (i16) | bucket slot of the node << 16, byte offset of the node's matrix row (left * rows * 2)}; [N]: the padding tiles' target
-                                                                    // the sweep stores the best predecessor into the low half of .y once the node's costs are gathered
+                                                                    // the sweep stores the best predecessor into the low half of .y once the node's costs are gathered; phase 5 overlays the rest of the node
         int32_t *nSid = (int32_t *)(smem + off);    off += 4 * N;   // +id known, -id unknown, 0 dummy
         off = align_up(off, 8);
         const uint32_t off_emit_end = off;                          // everything above is written by emit 3a
@@ -616,7 +619,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(KGPU_POOL_
             // (measurement build) what a position without predecessors relaxes from: a total no real one reaches (real <= INF + 32767) that cannot overflow
             // when a connection cost and a word cost are added, and stays >= INF when they are negative
             if (ABSENT_TILES) bk[Nb + 1] = make_uint2(0x7FFEFFFFu, 0u);
-            node[N] = make_uint2(0u, 0u);              // what a padding tile gathers for: row 0 of the matrix, never swept, so never overwritten
+            node[N] = make_uint2(0u, 0u);              // what a padding tile gathers for: row 0 of the matrix, never swept, so never overwritten while stage B runs (phase 5 makes it the backtrace's "none" entry)
         }
         wave_sync();
         {   // the match buffer is dead now: give back the pages beyond the tile list
@@ -671,8 +674,41 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(KGPU_POOL_
         KGPU_STOP(7)
         KGPU_ARGS();
         // ---- phase 5: backtrace (lattice.rs:144-153) + Node -> Token (tokenizer.rs:22-43)
+        // The doubling passes, lane = node (kgpu_backtrace_core.h).  node[t] is dead behind stage B but for the low half of y, the best predecessor p1: x (word
+        // cost | bucket slot) and the upper half of y (matrix row offset) were the sweep's, and the tokens below read nSid, nb, cbyte and path only -- so the
+        // node's three further ancestors go there, without a byte of LDS of their own.  Four nodes per lane and trip as in emit 3b: a trip's reads are issued
+        // together, no exec mask around anything -- a lane past node N - 1 works on node N - 1 again and stores the same word to the same address.  A hop from
+        // NONE16 reads node[N] (bt_hop: one v_min), never index 0xFFFF: the padding tiles' target, which stage B is through with, is made all NONE16 here (every
+        // lane the same store), so dead nodes and unreachable ones come out as four NONE16 without a select.
+        {
+            const uint32_t a_last = a_node + 8u * (N - 1u);
+            uint32_t a_mine = a_node + 8u * lane;   // node[t0 + lane]
+            const auto addr_of = [&](uint32_t t) { return a_node + 8u * t; };
+            lds_st<uint64_t>(a_node + 8u * N, ~0ull);
+            for (uint32_t t0 = 0; t0 < N; t0 += 256, a_mine += 2048u) {   // level 1: p2 = p1 of p1, into the upper half of y
+                uint32_t ad[4], p1[4], p2[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) { ad[k] = min(a_mine + 512u * k, a_last); p1[k] = lds_ld<uint16_t>(ad[k] + 4u); }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) p2[k] = lds_ld<uint16_t>(addr_of(bt_hop(p1[k], N)) + 4u);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) lds_st<uint16_t>(ad[k] + 6u, (uint16_t)p2[k]);
+            }
+            wave_sync();
+            a_mine = a_node + 8u * lane;
+            for (uint32_t t0 = 0; t0 < N; t0 += 256, a_mine += 2048u) {   // level 2: p3 | p4 << 16 = the y word of p2, into x
+                uint32_t ad[4], yy[4], xx[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) { ad[k] = min(a_mine + 512u * k, a_last); yy[k] = lds_ld<uint32_t>(ad[k] + 4u); }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) xx[k] = lds_ld<uint32_t>(addr_of(bt_hop(bt_p2(yy[k]), N)) + 4u);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) lds_st<uint32_t>(ad[k], xx[k]);
+            }
+            wave_sync();
+        }
         uint32_t K = 0;
-        if (lane == 0) K = backtrace_path(a_node + 4, lds0 + (uint32_t)((uint8_t *)path - pool), N - 1, C);
+        if (lane == 0) K = backtrace_quads(a_node, lds0 + (uint32_t)((uint8_t *)path - pool), N - 1, C);
         K = bcast32(K);
         // staging slot of the sentence: K <= C + 1 <= B + 1 tokens always fit at b0 + s
         // (no cursor atomics: a single hot word serialises ~90 sentences/us chip-wide)
