@@ -3,7 +3,7 @@
 render() restates print_tokens (reference src/bin/kanpyo.rs:174-197) on bytes: per record the surface -- the record's byte_len bytes at
 `position` of its sentence, the literal EOS for the dummy class -- then '\\t', the joined features of row id - 1 (nothing for the dummy class
 and for id 0), then '\\n'.  It works on Python bytes and numpy only and imports nothing from the library's parser, pool or kernels;
-tests/test_lines_ref_cpu.py pins it against the per-token loop of tests/test_gpu_lines.py and the hand-derived fixture lines, so the expected
+tests/test_lines_ref_cpu.py pins it against the per-token loop of tests/test_gpu_lines.py (expected_lines, below) and the hand-derived fixture lines, so the expected
 values of tests/test_gpu_format.py are themselves checked wherever the CPU suite runs."""
 import numpy as np
 
@@ -12,6 +12,28 @@ TOKEN_DTYPE = np.dtype([("id", "<i4"), ("cls", "<u4"), ("position", "<u4"), ("st
 DUMMY, KNOWN, UNKNOWN = 0, 1, 2
 
 KINDS = ("known", "known_edge", "unk", "unk_edge", "known0", "dummy", "dummy_id", "empty0", "emptyB", "overlap", "backwards")
+
+
+def expected_lines(utf8, offs, tokens, tok_offsets, known, unk):
+    """(text bytes, text offsets[n + 1]) the reference prints for these records: print_tokens (kanpyo.rs:174-197) restated."""
+    cache = ({}, {})
+    out, toff, size = [], [0], 0
+    for i in range(len(offs) - 1):
+        raw = utf8[int(offs[i]) : int(offs[i + 1])].tobytes()
+        for t in tokens[int(tok_offsets[i]) : int(tok_offsets[i + 1])]:
+            cls, tid, pos, bl = int(t["cls"]), int(t["id"]), int(t["position"]), int(t["byte_len"])
+            surf = b"EOS" if cls == 0 else raw[pos : pos + bl]
+            feats = b""
+            if cls != 0 and tid != 0:
+                c = cache[cls - 1]
+                if tid not in c:
+                    c[tid] = ",".join((known if cls == 1 else unk).features(tid)).encode()
+                feats = c[tid]
+            line = surf + b"\t" + feats + b"\n"
+            out.append(line)
+            size += len(line)
+        toff.append(size)
+    return b"".join(out), np.array(toff, dtype=np.uint64)
 
 
 def rows_of(table, n):

@@ -4,14 +4,14 @@ asks the device for the same counters).  A case is a dictionary (Dict.from_parts
 verdict is, on which side of which boundary it lies and by how many bytes is said HERE, from tests/pool_model.py over the lattice's shape, before a
 GPU is touched -- a change to a dictionary builder or to the kernel's arithmetic then cannot turn a case into a no-op.
 
-The lattice's shape comes from the key list (test_gpu_window_limits.Shape: prefixes and unknown words per position, src/lattice.rs:42-99); the CPU
+The lattice's shape comes from the key list (window_cases.Shape: prefixes and unknown words per position, src/lattice.rs:42-99); the CPU
 test checks it against oracle/pyref.py's naive lattice for every sentence used.  Nothing here needs a device or the library."""
 import functools
 
 import numpy as np
 
 import pool_model as M
-from test_gpu_window_limits import Shape, make_parts
+from window_cases import Shape, make_parts
 
 SHORT = ["テスト", "", "漢字かな", "xyz テスト", "いうえお", "辞書x形態素"]   # ordinary company: a few characters each, HELD on every plan (asserted)
 

@@ -10,6 +10,7 @@ import pytest
 
 import count_ref as CR
 import encode_ref as E
+import encode_spans_ref as S
 import wordpiece_ref as WP
 import words_ref as W
 from conftest import fixture_dict_parts
@@ -374,3 +375,36 @@ def check_ragged(ctx, v, case, want):
     assert (rc, n) == (0, total)
     assert np.array_equal(ioff, want[1]) and np.array_equal(buf[:total], want[0])
     assert (buf[total:] == SENTINEL).all(), "ids behind the ragged total"
+
+
+def check_spans_ragged(ctx, v, case, want, edits=None, what=""):
+    """The ragged kgpu_encode_spans_device call against (ids, offsets, spans, index), nothing behind the total, and the same ids and offsets as
+    kgpu_encode_device."""
+    d = case if isinstance(case, _Dev) else _Dev(case)
+    total = len(want[0])
+    rc, n, ids, ioff, spans, tix = dev_spans(ctx, v, d, edits, room=total + 32)
+    assert (rc, n) == (0, total), (what, rc, n, total)
+    assert np.array_equal(ioff, want[1]) and np.array_equal(ids[:total], want[0]), (what, ioff.tolist()[:64], ids[:total].tolist()[:64], want[0].tolist()[:64])
+    assert np.array_equal(spans[:total], want[2]), (what, spans[:total].tolist(), want[2].tolist())
+    assert np.array_equal(tix[:total], want[3]), (what, tix[:total].tolist()[:64], want[3].tolist()[:64])
+    assert (ids[total:] == SENTINEL).all() and (spans[total:] == SENTINEL).all() and (tix[total:] == SENTINEL).all(), f"{what}: something behind the ragged total"
+    rc, n, plain, poff = dev_encode(ctx, v, d, room=total + 32)
+    assert (rc, n) == (0, total) and plain.tobytes() == ids.tobytes() and poff.tobytes() == ioff.tobytes(), f"{what}: kgpu_encode_device gives other ids for the same buffers ({rc}, {n} of {total})"
+
+
+def check_spans_padded(ctx, v, case, want, width, eos, edits=None, pad_id=-9):
+    """The same for the padded form: n rows of `width`, encode_spans_ref.padded's.  -> its (ids, spans, index)"""
+    d = case if isinstance(case, _Dev) else _Dev(case)
+    n = d.n
+    pi, ps, px = S.padded(*want, width, pad_id, eos)
+    rc, got, ids, ioff, spans, tix = dev_spans(ctx, v, d, edits, width=width, pad_id=pad_id, capacity=n * width, room=n * width + 48)
+    assert (rc, got) == (0, len(want[0])), (width, rc, got, len(want[0]))
+    assert np.array_equal(ioff, want[1]), f"width {width}: id_offsets of the padded form are not the ragged run's: {ioff.tolist()[:64]} {want[1].tolist()[:64]}"
+    for name, have, ref in (("ids", ids[: n * width].reshape(n, width), pi), ("spans", spans[: n * width].reshape(n, width, 4), ps), ("token index", tix[: n * width].reshape(n, width), px)):
+        if not np.array_equal(have, ref):
+            row = int(np.argwhere(have != ref)[0][0])
+            raise AssertionError(f"width {width}: {name} differ, first in row {row}: device {have[row].tolist()} reference {ref[row].tolist()}")
+    assert (ids[n * width:] == SENTINEL).all() and (spans[n * width:] == SENTINEL).all() and (tix[n * width:] == SENTINEL).all(), f"width {width}: something behind n x width"
+    rc, got, plain, poff = dev_encode(ctx, v, d, width=width, pad_id=pad_id, capacity=n * width, room=n * width + 48)
+    assert rc == 0 and plain.tobytes() == ids.tobytes() and poff.tobytes() == ioff.tobytes(), f"width {width}: kgpu_encode_device gives other ids for the same buffers (rc {rc})"
+    return pi, ps, px

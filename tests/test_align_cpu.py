@@ -14,12 +14,12 @@ import align_ref as A
 import normalize_ref as N
 from conftest import ROOT, load_golden
 from kanpyo_amd import _lib
-from test_gpu_normalize import CLEAN, DIRTY
-from test_normalize_cpu import SAME_UNICODE, StubLib, _view
+from normalize_cases import CLEAN, DIRTY, StubLib, same_unicode, view
 
 HERE = os.path.join(ROOT, "tests", "c_abi")
 INC = os.path.join(ROOT, "include")
 CSRC = os.path.join(ROOT, "kanpyo_amd", "csrc")
+SAME_UNICODE = same_unicode()
 NEW = ("kgpu_normalize_host_aligned", "kgpu_normalize_batch_aligned", "kgpu_normalize_text_aligned", "kgpu_normalize_device_aligned", "kgpu_ctx_sync_normalize_aligned",
        "kgpu_source_spans_host", "kgpu_source_spans_device", "kgpu_source_spans_batch")
 SEEDS = (11, 20260102, 777)
@@ -255,13 +255,13 @@ class AlignStub(StubLib):
         self.log[-1] = ("normalize_batch_aligned", form)
         ne._obj.value = 0
         if rc == 0:
-            _view(eoff, np.uint64, n + 1)[:] = 0
+            view(eoff, np.uint64, n + 1)[:] = 0
         return rc
 
     def kgpu_source_spans_batch(self, h, tokens, toff, n, edits, eoff, spans):
         self.log.append("source_spans_batch")
-        t = _view(toff, np.uint64, n + 1)
-        _view(spans, np.uint8, int(t[n] - t[0]) * 16)[:] = 0
+        t = view(toff, np.uint64, n + 1)
+        view(spans, np.uint8, int(t[n] - t[0]) * 16)[:] = 0
         return 0
 
 

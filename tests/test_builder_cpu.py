@@ -7,37 +7,11 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
+from dict_cases import CHAR_DEF, LEX_A, LEX_B, UNK_DEF
+from dict_cases import mecab_matrix as _matrix
 from kanpyo_amd import builder
 from kanpyo_amd.dictfile import format_tokens, load_dict, save_dict
 from kanpyo_amd.token import Token, TokenClass
-
-CHAR_DEF = """# test char.def in MeCab format
-DEFAULT         0 1 0  # mandatory
-SPACE           0 1 0
-KANJI           0 0 2
-HIRAGANA        0 1 2
-KATAKANA        1 1 2
-NUMERIC         1 1 0
-
-0x0020 SPACE
-0x0030..0x0039 NUMERIC
-0x3041..0x309F  HIRAGANA
-0x30A1..0x30FF  KATAKANA
-0x4E00..0x9FA5  KANJI
-0x4E00 NUMERIC KANJI  # first category wins (char_def.rs:65-71)
-"""
-UNK_DEF = "DEFAULT,5,5,4769,記号,一般,*,*,*,*,*\nKATAKANA,1,1,3000,名詞,一般,*,*,*,*,*\nKATAKANA,1,1,2500,名詞,固有,*,*,*,*,*\nHIRAGANA,2,2,9000,助詞,*,*,*,*,*,*\nKANJI,1,1,8000,名詞,一般,*,*,*,*,*\nNUMERIC,3,3,1000,名詞,数,*,*,*,*,*\nSPACE,4,4,100,記号,空白,*,*,*,*,*\n"
-LEX_A = "東京,1,1,3000,名詞,固有名詞,地域,一般,*,*,東京,トウキョウ,トーキョー\n東京都,1,1,3500,名詞,固有名詞,地域,一般,*,*,東京都,トウキョウト,トーキョート\nに,2,2,500,助詞,格助詞,一般,*,*,*,に,ニ,ニ\n"
-LEX_B = "住む,6,6,4000,動詞,自立,*,*,五段・マ行,基本形,住む,スム,スム\nに,2,2,700,助詞,副助詞,*,*,*,*,に,ニ,ニ\n都,1,1,6000,名詞,接尾,地域,*,*,*,都,ト,ト\n\"a,b\",1,1,100,名詞,一般,*,*,*,*,\"a,b\",*,*\n"
-
-
-def _matrix(n=7):
-    lines = [f"{n} {n}"]
-    for r in range(n):
-        for c in range(n):
-            lines.append(f"{r} {c} {(r * 31 + c * 17) % 200 - 100}")
-    return "\n".join(lines) + "\n"
-
 
 def test_matrix_def_known_answer():
     g = load_golden("matrix_kat.json")["matrix_def"]

@@ -12,29 +12,13 @@ import pytest
 import count_ref as CR
 import words_ref as W
 from conftest import ROOT, fixture_dict_parts, load_golden
+from golden_cases import TOKEN_DTYPE, fixture_tables, golden_records
 from kanpyo_amd import _lib
-from test_words_cpu import TOKEN_DTYPE, fixture_tables
 
 HERE = os.path.join(ROOT, "tests", "c_abi")
 INC = os.path.join(ROOT, "include")
 NEW = ("kgpu_counts_create", "kgpu_counts_destroy", "kgpu_counts_reset", "kgpu_counts_get_info", "kgpu_count_batch", "kgpu_count_text",
        "kgpu_count_words_device", "kgpu_ctx_sync_count", "kgpu_counts_read")
-
-
-def golden_records(sentences):
-    """The hand-derived tokens of tests/golden/fixture_tokens.json for these sentences, packed -> (utf8 bytes, offsets, tokens, tok_offsets)."""
-    tokens_of = {c["input"]: c["tokens"] for c in load_golden("fixture_tokens.json")["cases"]}
-    raw, offs, recs, toff = b"", [0], [], [0]
-    for s in sentences:
-        raw += s.encode()
-        offs.append(len(raw))
-        for tid, cls, pos, start, end, surface in tokens_of[s]:
-            recs.append((tid, cls, pos, start, end, 0 if cls == 0 else len(surface.encode())))
-        toff.append(len(recs))
-    tokens = np.zeros(len(recs), dtype=TOKEN_DTYPE)
-    for i, r in enumerate(recs):
-        tokens[i] = r
-    return raw, np.array(offs, dtype=np.uint64), tokens, np.array(toff, dtype=np.uint64)
 
 
 def test_reference_reproduces_the_golden_counts():

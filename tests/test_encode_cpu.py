@@ -14,10 +14,9 @@ import count_ref as CR
 import encode_ref as E
 import words_ref as W
 from conftest import ROOT, load_golden
+from golden_cases import fixture_tables, golden_records, synth20k, vocab_table  # noqa: F401  (synth20k: the fixture)
 from kanpyo_amd import _lib
 from record_cases import ref_spec
-from test_count_cpu import golden_records
-from test_words_cpu import fixture_tables
 
 HERE = os.path.join(ROOT, "tests", "c_abi")
 INC = os.path.join(ROOT, "include")
@@ -44,15 +43,6 @@ def test_reference_reproduces_the_golden_ids():
         E.encode_words([[b"a"]], ["a", "b", "a"], 0)
     assert E.padded(np.array([5, 6, 7, 8, 9], dtype=np.int32), [0, 3, 3, 5], 2, -1, eos_id=4).tolist() == [[5, 4], [-1, -1], [8, 9]]
     assert E.padded(np.array([5, 6, 7], dtype=np.int32), [0, 3], 2, -1).tolist() == [[5, 6]]
-
-
-@pytest.fixture(scope="module")
-def synth20k():
-    from kanpyo_amd import synth
-
-    sd = synth.build_dict(20000, seed=5)
-    known, unk = synth.feature_tables(sd)
-    return sd, known, unk, len(known.morph_features), len(unk.morph_features), synth.record_surfaces(sd)
 
 
 def test_encode_and_count_agree_on_identity(synth20k):
@@ -82,32 +72,6 @@ def test_encode_and_count_agree_on_identity(synth20k):
 
 
 # ---- the handle's tables -----------------------------------------------------------------------------------------------------------------------
-def vocab_table(sd_dict, known, unk, nk, nu, kw, words, unk_id, flags=0, bos=0, eos=0):
-    """kgpu_debug_vocab_table -> (rc, row_id int32[nk + nu], slots uint64[n, 2], arena bytes, rows_resolved)."""
-    from kanpyo_amd.tokenizer import pack_sentences, words_spec
-
-    L = _lib.lib()
-    spec, keep = words_spec(**kw)
-    kb = np.frombuffer(known.encode(), dtype=np.uint8)
-    ub = np.frombuffer(unk.encode(), dtype=np.uint8)
-    ib = np.frombuffer(sd_dict.index_dict, dtype=np.uint8)
-    packed, woff = pack_sentences(words)
-    packed = np.ascontiguousarray(packed)
-    opts = _lib.VocabOpts(C.sizeof(_lib.VocabOpts), flags, unk_id, bos, eos)
-    row_id = np.full(nk + nu, 0x5A5A5A5A, dtype=np.int32)
-    ns, al, rr = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-    args = (kb.ctypes.data, kb.size, ub.ctypes.data, ub.size, ib.ctypes.data, ib.size, nk, nu, C.byref(spec), packed.ctypes.data if packed.size else None,
-            woff.ctypes.data, len(words), C.byref(opts), row_id.ctypes.data)
-    rc = L.kgpu_debug_vocab_table(*args, None, 0, C.byref(ns), None, 0, C.byref(al), C.byref(rr))
-    if rc != _lib.KGPU_ERR_CAPACITY:
-        return rc, row_id, None, None, int(rr.value)
-    slots = np.zeros((int(ns.value), 2), dtype=np.uint64)
-    arena = np.zeros(max(int(al.value), 1), dtype=np.uint8)
-    rc = L.kgpu_debug_vocab_table(*args, slots.ctypes.data, len(slots), C.byref(ns), arena.ctypes.data, int(al.value), C.byref(al), C.byref(rr))
-    del keep
-    return rc, row_id, slots, arena.tobytes()[: int(al.value)], int(rr.value)
-
-
 @pytest.mark.parametrize("name", list(SPECS))
 def test_vocab_table_on_the_synthetic_dictionary(synth20k, name):
     sd, known, unk, nk, nu, keys = synth20k

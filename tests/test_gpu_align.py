@@ -15,31 +15,11 @@ import pytest
 
 import align_ref as A
 import normalize_ref as N
-from conftest import ROOT, fixture_dict_parts, load_golden
+from conftest import ROOT, load_golden
 from kanpyo_amd import _lib
-from test_gpu_normalize import DAKUTEN, KA, SENTENCES, Env, mixed_lines
+from normalize_cases import DAKUTEN, KA, SENTENCES, env, mixed_lines  # noqa: F401  (env: the fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def env():
-    """The dictionary of tests/test_gpu_normalize.py: the reference's test dictionary with what half-width and full-width text normalises to."""
-    from kanpyo_amd import Dict, Tokenizer
-    from kanpyo_amd.dictfile import MorphFeatureTable
-
-    p = fixture_dict_parts()
-    keys = sorted(["テスト", "辞書", "形態素", "ハンカク", "ABC", "(株)", "ガ", "東京", "123"], key=lambda s: s.encode())
-    p["sorted_keywords"] = keys
-    p["morphs"] = [[i % 3, i % 3, 1000 + 10 * i] for i in range(len(keys))]
-    e = Env()
-    e.dict = Dict.from_parts(**p)
-    e.known = MorphFeatureTable.from_features([["名詞"]] * len(keys))
-    e.unk = MorphFeatureTable.from_features([["未知"]] * len(p["unk_morphs"]))
-    e.tok = Tokenizer(e.dict)
-    e.tok.set_features(e.known, e.unk)
-    e.keys = keys
-    return e
 
 
 def check_batch(tok, lines, form):

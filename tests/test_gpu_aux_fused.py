@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import fixture_dict_parts
+from kernel_run import libs  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -40,13 +41,10 @@ def _batch(n, shift=0):
 
 
 @pytest.fixture(scope="module")
-def env():
-    from kanpyo_amd import Dict, Tokenizer, _lib
+def env(libs):
+    from kanpyo_amd import Dict, Tokenizer
 
-    assert _lib.lib().kgpu_device_count() > 0, "no HIP device: the gpu tests need an MI355X"
-    from oracle import oracle
-
-    oracle.build()
+    _, oracle = libs
     d = Dict.from_parts(**fixture_dict_parts())
     tok, orc = Tokenizer(d), oracle.OracleTokenizer.from_dict(d)
     yield tok, orc, {}

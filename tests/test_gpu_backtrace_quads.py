@@ -20,25 +20,12 @@ import pytest
 
 import pool_cases as PC
 import pool_model as M
-from test_gpu_dead_positions import BASES, BEHIND_TE, DEAD_ENDS
-from test_gpu_dead_positions import _parts as dead_parts
-from test_gpu_pool_limits import COUNTERS, _set_env, run_case
-from test_gpu_tile_groups import _run
+from kernel_cases import BASES, BEHIND_TE, DEAD_ENDS, dead_parts
+from kernel_run import COUNTERS, host_batch, libs, run_case, run_fresh, set_env  # noqa: F401  (libs: the fixture)
 
 pytestmark = pytest.mark.gpu
 
 ENV_160 = {"KGPU_WINDOW_FIRST": "0"}   # (as pool_cases.cases_g: the batch's average length must not send it to the windowed kernel first)
-
-
-@pytest.fixture(scope="module")
-def libs():
-    from kanpyo_amd import _lib
-
-    assert _lib.lib().kgpu_device_count() > 0, "no HIP device: the gpu tests need an MI355X"
-    from oracle import oracle
-
-    oracle.build()
-    return _lib, oracle
 
 
 class Group:
@@ -161,21 +148,17 @@ def test_quads_small_call(libs, name, monkeypatch):
     """kgpu_tokenize_batch with at most 128 sentences: one launch, one wavefront a workgroup with a slice of its own -- every special sentence alone, then all
     among short ones; nothing falls back to the general path (every one of them fits the slice of 65 024 bytes)"""
     from kanpyo_amd import Tokenizer
-    from kanpyo_amd.tokenizer import pack_sentences
 
     g = GROUPS[name]()
-    _set_env(monkeypatch, {})
+    set_env(monkeypatch, {})
     d, orc = _orc(libs, g)
     assert all(g.d.verdict(s, M.PLAN_SMALL)["verdict"] == M.HELD for s in g.specials)
     tok = Tokenizer(d)
     try:
         batches = [[s] for s in g.specials] + [PC.among(g.specials)]
         for part in batches:
-            utf8, offs = pack_sentences(part)
-            assert len(part) <= 128 and int(offs[-1]) < 16 * 1024
-            got_t, got_off, status = tok.tokenize_packed(utf8, offs)
-            exp = orc.tokenize_batch(utf8, offs, 2)
-            assert not status.any() and np.array_equal(got_off, exp.offsets) and np.array_equal(got_t, exp.tokens), (g.name, [len(s) for s in part])
+            assert len(part) <= 128 and sum(len(s.encode()) for s in part) < 16 * 1024
+            host_batch(tok, orc, part, what=f"{g.name} {[len(s) for s in part]}")
         r = tok.routing()
         print(f"{g.name}: small_calls {r['small_calls']} small_fallbacks {r['small_fallbacks']}")
         assert r["small_calls"] == len(batches) and r["small_fallbacks"] == 0, r
@@ -186,34 +169,18 @@ def test_quads_small_call(libs, name, monkeypatch):
 @pytest.mark.parametrize("name", list(GROUPS))
 def test_quads_profile_work(libs, name, monkeypatch):
     """the kernel's profiling instantiation: the same tokens, and its work counters -- K among them -- are the oracle's"""
-    import torch
-
     from kanpyo_amd import Tokenizer
-    from kanpyo_amd.device import PROFILE_WORK, DeviceContext
+    from kanpyo_amd.device import PROFILE_WORK
     from kanpyo_amd.tokenizer import pack_sentences
 
     g = GROUPS[name]()
-    _set_env(monkeypatch, dict({"KGPU_POOL": M.POOL_ENV[g.plan]}, **g.env))
+    set_env(monkeypatch, dict({"KGPU_POOL": M.POOL_ENV[g.plan]}, **g.env))
     d, orc = _orc(libs, g)
     sentences = PC.among(g.specials)
-    utf8, offs = pack_sentences(sentences)
-    dev = torch.device("cuda", 0)
-    d_utf8, d_off = torch.from_numpy(utf8.copy()).to(dev), torch.from_numpy(offs.astype(np.int64)).to(dev)
-    n, cap = len(sentences), int(offs[-1]) + len(sentences)
-    d_tok = torch.empty((cap, 6), dtype=torch.int32, device=dev)
-    d_toff, d_st = torch.empty(n + 1, dtype=torch.int64, device=dev), torch.empty(n, dtype=torch.uint8, device=dev)
+    exp = orc.tokenize_batch(*pack_sentences(sentences), 2)
     tok = Tokenizer(d)
     try:
-        ctx = DeviceContext(tok)
-        ctx.set_profiling(PROFILE_WORK)
-        ctx.tokenize(d_utf8.data_ptr(), d_off.data_ptr(), n, int(offs[-1]), d_tok.data_ptr(), cap, d_toff.data_ptr(), d_st.data_ptr())
-        nt = ctx.sync()
-        exp = orc.tokenize_batch(utf8, offs, 2)
-        assert not d_st.cpu().numpy().any()
-        assert np.array_equal(d_toff.cpu().numpy().astype(np.uint64), exp.offsets)
-        assert np.array_equal(d_tok[:nt].cpu().numpy().reshape(-1), exp.tokens.view(np.int32).reshape(-1))
-        work, prof = ctx.work(), ctx.profile()
-        ctx.close()
+        prof, work = run_fresh(tok, orc, sentences, PROFILE_WORK, exp=exp, also=("work",))
         assert work == exp.counters, (work, exp.counters)
         want = PC.Batch(g.d, g.plan, sentences).expect()
         assert {k: prof[k] for k in COUNTERS} == want, (prof, want)

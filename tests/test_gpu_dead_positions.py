@@ -13,70 +13,25 @@ a dead node (its tokens start in the middle of the sentence) -- or EOS itself is
 Plans: the shipped chain and a 160 KB pool through a device context (that the pool kernel served the batch is asserted from the routing counters, as
 in test_gpu_tile_groups.py), and kgpu_tokenize_batch with at most 128 sentences: the single-launch small call, the same kernel with one wavefront a
 workgroup."""
-import functools
-
 import numpy as np
 import pytest
 
-import pool_cases as PC
 import pool_model as M
-from conftest import fixture_dict_parts
+from kernel_cases import BASES, BEHIND_TE, DEAD_ENDS, MODEL_PLANS, PLANS, dead_model, dead_need, dead_parts, dead_sentences
+from kernel_run import host_batch, libs, run_fresh, set_env  # noqa: F401  (libs: the fixture)
 from pool_model import shape as _shape
-from test_gpu_tile_groups import MODEL_PLANS
-from test_gpu_tile_groups import PLANS as TILE_PLANS
-from test_gpu_tile_groups import _run
 
 pytestmark = pytest.mark.gpu
 
 KS = [1, 7, 8, 9, 16, 17]
-BASES = ["あいう", "あいうあいう", "いあいう", "あいういう"]
-ORDINARY = ["", "あ", "い", "う", "いう", "うい", "ういあ", "いいい", "あいあ", "ううう", "あい", "いあ"]
-DEAD_ENDS = ["テ", "テあ", "テ辞書", "テ辞書形態素", "テスト辞書", "ト辞書あ", "辞書テ", "形態素テ形態素", "テテ辞書辞書"]   # test_unreachable_eos_and_dead_ends
-BEHIND_TE = ["テいう", "テあいう", "テいうあいう", "テあいういう", "いうテいう", "テう", "テい"]
 PLAN_NAMES = ["shipped", "pool160x4", "small"]
-SHIPPED_CHARS = 36   # what the shipped plan's pool kernel is asserted to serve itself (see _need)
-
-
-@pytest.fixture(scope="module")
-def libs():
-    from kanpyo_amd import _lib
-
-    assert _lib.lib().kgpu_device_count() > 0, "no HIP device: the gpu tests need an MI355X"
-    from oracle import oracle
-
-    oracle.build()
-    return _lib, oracle
-
-
-def _parts(k, negative=False):
-    kws = ["あいう"] * 2 + ["い"] * k + ["う"] * 3
-    p = fixture_dict_parts()
-    if not negative:
-        rng = np.random.default_rng(2000 + k)
-        # few distinct costs: ties between predecessors are common (first minimum in insertion order, lattice.rs:125,136)
-        morphs = np.stack([rng.integers(0, 5, len(kws)), rng.integers(0, 5, len(kws)), rng.integers(-3, 4, len(kws)) * 100], axis=1)
-        return dict(sorted_keywords=kws, morphs=morphs, conn_rows=5, conn_cols=5, conn_data=rng.integers(-2, 3, 25) * 50, char_class=p["char_class"],
-                    char_category=p["char_category"], invoke_list=p["invoke_list"], group_list=p["group_list"], unk_map={0: (1, 1), 1: (1, 2), 2: (2, 1)},
-                    unk_morphs=[[0, 0, 4000], [1, 1, 3500]])
-    # the fixture's three words behind them (same first byte as the hiragana ones, then the kanji: the order the fixture itself has)
-    three = [[0, 0, 1000], [1, 1, -20000], [2, 2, 1100]]
-    morphs = [three[i % 3] for i in range(2)] + [three[(i + 1) % 3] for i in range(k)] + [[1, 1, -20000], [2, 2, -20000], [0, 0, 1000]] + three
-    p["sorted_keywords"] = kws + list(p["sorted_keywords"])
-    p["morphs"] = morphs
-    p["conn_data"] = [0, 100, 200, 100, -30000, 100, 200, 100, -30000]
-    return p
+SHIPPED_CHARS = 36   # what the shipped plan's pool kernel is asserted to serve itself (see kernel_cases.dead_need)
 
 
 def _dict(k, negative=False):
     from kanpyo_amd import Dict
 
-    return Dict.from_parts(**_parts(k, negative))
-
-
-@functools.lru_cache(maxsize=None)
-def _model(k, negative=False):
-    """the reservation model's view of this dictionary (tests/pool_model.py; tests/test_pool_model_cpu.py checks its shapes against the naive lattice)"""
-    return PC.Dictionary(_parts(k, negative))
+    return Dict.from_parts(**dead_parts(k, negative))
 
 
 def _pyref(d):
@@ -85,48 +40,16 @@ def _pyref(d):
     return pyref, pyref.PyDict(d.index_dict, d.connection_dict, d.morph_dict, d.unk_dict, d.char_category, d.invoke_list, d.group_list)
 
 
-def _need(pyref, pd, s):
-    """Upper estimate of the pool kernel's LDS bytes for s, from the naive lattice: text, the per-character arrays, 12 bytes a node, 8 a bucket entry,
-    8 a tile of a live position -- or, while the nodes are emitted, the match buffer (32 bytes a character) in the place of buckets and tiles."""
-    tp, nodes, _, _ = _shape(pyref, pd, s)
-    C, N = len(s), len(nodes)
-    tiles = sum(((t + 7) // 8) * ((p + 7) // 8) for t, p in tp)
-    return 3 * C + 4 + 26 * (C + 2) + 12 * (N + 1) + max(8 * (N + 1) + 8 * tiles, 32 * C + 32) + 64
-
-
-def _sentences(rng):
-    """about 200: the four shapes 1 to 12 times repeated, mixed with ordinary ones"""
-    out = [b * r for b in BASES for r in range(1, 13)]
-    out += [b * r + o for b in BASES for r in (1, 2, 5) for o in ("い", "う", "あ")]
-    while len(out) < 200:
-        out.append("".join(rng.choice(ORDINARY + BASES, size=int(rng.integers(1, 5)))))
-    return [out[i] for i in rng.permutation(len(out))]
-
-
 def _check_small(tok, orc, sentences):
     """kgpu_tokenize_batch in calls of at most 100 sentences and well below 16 KB: the single-launch small call"""
-    from kanpyo_amd.tokenizer import pack_sentences
-
     for i0 in range(0, len(sentences), 100):
         part = sentences[i0:i0 + 100]
-        utf8, offs = pack_sentences(part)
-        assert len(part) <= 128 and int(offs[-1]) < 16 * 1024
-        got_t, got_off, status = tok.tokenize_packed(utf8, offs)
-        exp = orc.tokenize_batch(utf8, offs, 2)
-        assert not status.any()
-        assert np.array_equal(got_off, exp.offsets), "per-sentence token counts differ"
-        if not np.array_equal(got_t, exp.tokens):
-            bad = int(np.nonzero(got_t != exp.tokens)[0][0])
-            s = int(np.searchsorted(exp.offsets, bad, side="right") - 1)
-            raise AssertionError(f"token {bad} (sentence {s}: {part[s]!r}) differs: gpu {got_t[bad]} oracle {exp.tokens[bad]}")
+        assert len(part) <= 128 and sum(len(s.encode()) for s in part) < 16 * 1024
+        host_batch(tok, orc, part)
 
 
 def _set_plan(monkeypatch, plan):
-    for name in ("KGPU_POOL", "KGPU_WINDOW", "KGPU_WINDOW_TEAM", "KGPU_WINDOW_FIRST"):
-        monkeypatch.delenv(name, raising=False)
-    if plan in TILE_PLANS:
-        for name, v in TILE_PLANS[plan][0].items():
-            monkeypatch.setenv(name, v)
+    set_env(monkeypatch, PLANS[plan][0] if plan in PLANS else {})
 
 
 def _check(tok, orc, plan, alone, batch, inside, monkeypatch, d, model):
@@ -134,7 +57,7 @@ def _check(tok, orc, plan, alone, batch, inside, monkeypatch, d, model):
     been served by the pool kernel, the rest run with the windowed kernel behind it and must not reach the general kernel.  The redo and hand-on counts
     are the reservation model's (tests/pool_model.py), exactly: `tok` is a fresh handle, every batch on it steps the estimate by the restated rule of
     chain_feedback (M.steer: a batch of one sentence without a redo takes 1/128 off), and every batch runs on a context of its own, so the shipped plan's
-    pool keeps its 40 KB shape (test_gpu_tile_groups.MODEL_PLANS)."""
+    pool keeps its 40 KB shape (kernel_cases.MODEL_PLANS)."""
     from kanpyo_amd import Tokenizer
 
     if plan == "small":
@@ -148,14 +71,14 @@ def _check(tok, orc, plan, alone, batch, inside, monkeypatch, d, model):
         return M.counters([model.verdict(s, MODEL_PLANS[plan], est_q8)["verdict"] for s in sentences])
 
     for s in alone:
-        prof = _run(tok, orc, [s])
+        prof = run_fresh(tok, orc, [s])
         want = predicted([s], est)
         assert sum(prof["deferred"]) == 0 and want[0] == 0, (s, prof)   # the pool kernel served it
         assert prof["redone"][0] == want[1], (s, want, prof)
         est = M.steer(est, want[1], 1)
     ins = [s for s in batch if inside(s)]
     beyond = [s for s in batch if not inside(s)]
-    prof = _run(tok, orc, ins)
+    prof = run_fresh(tok, orc, ins)
     want = predicted(ins, est)
     print(f"{plan}: {len(ins)} sentences meant for the pool kernel: deferred {prof['deferred']} redone {prof['redone']} (est_q8 {est}); {len(beyond)} beyond")
     assert sum(prof["deferred"]) == 0 and want[0] == 0 and prof["redone"][0] == want[1], (want, prof)
@@ -163,7 +86,7 @@ def _check(tok, orc, plan, alone, batch, inside, monkeypatch, d, model):
         monkeypatch.setenv("KGPU_WINDOW", "24")
         tok2 = Tokenizer(d)
         try:
-            prof = _run(tok2, orc, beyond)
+            prof = run_fresh(tok2, orc, beyond)
         finally:
             tok2.close()
         want = predicted(beyond, M.EST_Q8_FRESH)   # (a fresh handle)
@@ -186,13 +109,13 @@ def test_dead_positions(libs, k, plan, monkeypatch):
         assert all(dp[i] == 1 << 30 and pre[i] is None for i in dead)
     assert _shape(pyref, pd, "あいういう")[0][3] == (k + 1, 5)   # ... and a live position with the same targets beside it
     limit = 32 * 624 if plan == "shipped" else 64 * 2544
-    assert all(_need(pyref, pd, b * (SHIPPED_CHARS // len(b))) * 6 <= 32 * 624 * 5 for b in BASES)
-    assert all(_need(pyref, pd, b * 12 + "あ") * 6 <= 64 * 2544 * 5 for b in BASES)
+    assert all(dead_need(pyref, pd, b * (SHIPPED_CHARS // len(b))) * 6 <= 32 * 624 * 5 for b in BASES)
+    assert all(dead_need(pyref, pd, b * 12 + "あ") * 6 <= 64 * 2544 * 5 for b in BASES)
     inside = (lambda s: len(s) <= SHIPPED_CHARS) if limit == 32 * 624 else (lambda s: True)
     _set_plan(monkeypatch, plan)
     tok, orc = Tokenizer(d), oracle.OracleTokenizer.from_dict(d)
     try:
-        _check(tok, orc, plan, BASES, _sentences(np.random.default_rng(k)), inside, monkeypatch, d, _model(k))
+        _check(tok, orc, plan, BASES, dead_sentences(np.random.default_rng(k)), inside, monkeypatch, d, dead_model(k))
     finally:
         tok.close()
 
@@ -216,11 +139,11 @@ def test_dead_positions_negative_costs(libs, k, plan, monkeypatch):
     _set_plan(monkeypatch, plan)
     tok, orc = Tokenizer(d), oracle.OracleTokenizer.from_dict(d)
     rng = np.random.default_rng(100 + k)
-    batch = _sentences(rng) + DEAD_ENDS + BEHIND_TE + [a + b for a in BEHIND_TE for b in DEAD_ENDS[:4]]
+    batch = dead_sentences(rng) + DEAD_ENDS + BEHIND_TE + [a + b for a in BEHIND_TE for b in DEAD_ENDS[:4]]
     batch = [batch[i] for i in rng.permutation(len(batch))]
     inside = (lambda s: len(s) <= SHIPPED_CHARS) if plan == "shipped" else (lambda s: True)
     try:
-        _check(tok, orc, plan, BASES + DEAD_ENDS + BEHIND_TE, batch, inside, monkeypatch, d, _model(k, True))
+        _check(tok, orc, plan, BASES + DEAD_ENDS + BEHIND_TE, batch, inside, monkeypatch, d, dead_model(k, True))
     finally:
         tok.close()
 
@@ -239,7 +162,7 @@ def test_many_dead_positions_long_sentence(libs, k, plan, monkeypatch):
         d = _dict(k, negative)
         tok, orc = Tokenizer(d), oracle.OracleTokenizer.from_dict(d)
         try:
-            prof = _run(tok, orc, ["あいう" * 40, "あいう", ("テ" if negative else "") + "あいういう" * 24, "いあいう" * 3, ""])
+            prof = run_fresh(tok, orc, ["あいう" * 40, "あいう", ("テ" if negative else "") + "あいういう" * 24, "いあいう" * 3, ""])
             print(f"k={k} {plan} negative={negative}: deferred {prof['deferred']} redone {prof['redone']} long_launches {prof['long_launches']}")
         finally:
             tok.close()

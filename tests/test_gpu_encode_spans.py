@@ -16,6 +16,8 @@ import encode_spans_ref as S
 import lines_ref as R
 from conftest import ROOT, fixture_dict_parts, load_golden
 from record_cases import LIST, SENTINEL, SMALL_KEYS, SPECIALS, _Dev, _Env, bert_like, corpus_of, dev_encode, dev_spans, env, ref_spec, small_ctx  # noqa: F401
+from record_cases import check_spans_padded as check_padded
+from record_cases import check_spans_ragged as check_ragged
 from record_cases import plain_small_env as small_env  # noqa: F401  (env, small_ctx, small_env: the fixtures; this small_env has every EOS reachable)
 
 pytestmark = pytest.mark.gpu
@@ -35,36 +37,6 @@ def pack6(sent_bytes, per_sentence):
 def edit_batch(per_sentence):
     """Per sentence a list of edit 8-tuples -> (edits[EDIT_DTYPE], edit_offsets)."""
     return A.edit_array([e for es in per_sentence for e in es]), np.concatenate([[0], np.cumsum([len(es) for es in per_sentence])]).astype(np.uint64)
-
-
-def check_ragged(ctx, v, case, want, edits=None, what=""):
-    """The ragged call against (ids, offsets, spans, index), nothing behind the total, and the same ids and offsets as kgpu_encode_device."""
-    d = case if isinstance(case, _Dev) else _Dev(case)
-    total = len(want[0])
-    rc, n, ids, ioff, spans, tix = dev_spans(ctx, v, d, edits, room=total + 32)
-    assert (rc, n) == (0, total), what
-    assert np.array_equal(ioff, want[1]) and np.array_equal(ids[:total], want[0]), what
-    assert np.array_equal(spans[:total], want[2]), (what, spans[:total].tolist(), want[2].tolist())
-    assert np.array_equal(tix[:total], want[3]), what
-    assert (ids[total:] == SENTINEL).all() and (spans[total:] == SENTINEL).all() and (tix[total:] == SENTINEL).all(), "something behind the ragged total"
-    rc, n, plain, poff = dev_encode(ctx, v, d, room=total + 32)
-    assert (rc, n) == (0, total) and plain.tobytes() == ids.tobytes() and poff.tobytes() == ioff.tobytes(), "kgpu_encode_device gives other ids for the same buffers"
-
-
-def check_padded(ctx, v, case, want, width, eos, edits=None, pad_id=-9):
-    d = case if isinstance(case, _Dev) else _Dev(case)
-    n = d.n
-    pi, ps, px = S.padded(*want, width, pad_id, eos)
-    rc, got, ids, ioff, spans, tix = dev_spans(ctx, v, d, edits, width=width, pad_id=pad_id, capacity=n * width, room=n * width + 48)
-    assert (rc, got) == (0, len(want[0])), width
-    assert np.array_equal(ioff, want[1]), "id_offsets of the padded form are the ragged run's"
-    assert np.array_equal(ids[: n * width].reshape(n, width), pi), width
-    assert np.array_equal(spans[: n * width].reshape(n, width, 4), ps), width
-    assert np.array_equal(tix[: n * width].reshape(n, width), px), width
-    assert (ids[n * width:] == SENTINEL).all() and (spans[n * width:] == SENTINEL).all() and (tix[n * width:] == SENTINEL).all(), "something behind n x width"
-    rc, got, plain, poff = dev_encode(ctx, v, d, width=width, pad_id=pad_id, capacity=n * width, room=n * width + 48)
-    assert rc == 0 and plain.tobytes() == ids.tobytes() and poff.tobytes() == ioff.tobytes()
-    return pi, ps, px
 
 
 def crafted(env, case, vocab, unk, bos=None, eos=None, kw=None, wordpiece=True, edits=None, stats=None, **wp):

@@ -5,8 +5,9 @@ more than eight prefixes at one position (src/lattice.rs:24-38) -- under every l
 pool kernel off (long-sentence / HBM-scratch kernels only).  Integer work: exact equality."""
 import random
 
-import numpy as np
 import pytest
+
+from kernel_run import host_batch, libs  # noqa: F401  (libs: the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -14,29 +15,8 @@ POOLS = ["0", "8:2:64", "16:4:32", "40:4:32", "40:4:40", "40:4:48", "40:8:20", "
 WINDOWS = ["0", "8", "10", "12", "16", "32"]  # KiB of LDS of the windowed kernel behind the pools ("0": off, the general kernel takes its place)
 
 
-@pytest.fixture(scope="module")
-def libs():
-    from kanpyo_amd import _lib
-
-    assert _lib.lib().kgpu_device_count() > 0, "no HIP device: the gpu tests need an MI355X"
-    from oracle import oracle
-
-    oracle.build()
-    return _lib, oracle
-
-
 def _same(tok, orc, sentences, what):
-    from kanpyo_amd.tokenizer import pack_sentences
-
-    utf8, offs = pack_sentences(sentences)
-    exp = orc.tokenize_batch(utf8, offs, 16)
-    got_t, got_off, status = tok.tokenize_packed(utf8, offs)
-    assert not status.any(), what
-    assert np.array_equal(got_off, exp.offsets), f"{what}: per-sentence token counts differ"
-    if not np.array_equal(got_t, exp.tokens):
-        bad = int(np.nonzero(got_t != exp.tokens)[0][0])
-        s = int(np.searchsorted(exp.offsets, bad, side="right") - 1)
-        raise AssertionError(f"{what}: token {bad} (sentence {s}: {sentences[s]!r}) gpu {got_t[bad]} oracle {exp.tokens[bad]}")
+    host_batch(tok, orc, sentences, 16, what)
     return len(sentences)
 
 

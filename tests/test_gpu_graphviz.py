@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, fixture_dict_parts, load_golden
+from dict_cases import lattice_from_pyref, transposed_parts
 from record_cases import _write_dict_dir
 
 pytestmark = pytest.mark.gpu
@@ -40,7 +41,6 @@ def _docs(tok, sents, dpi=48, full_state=False):
 
 def _want_pyref(pd, known, unk, text, dpi, full_state):
     from kanpyo_amd.lattice import graphviz
-    from test_lattice_cpu import lattice_from_pyref
 
     conn = lambda r, l: pd.conn[pd.row * l + r]  # noqa: E731  ConnectionTable::get (connection.rs:12-14)
     return graphviz(lattice_from_pyref(pd, text), conn, known.features, unk.features, dpi, full_state).encode()
@@ -143,7 +143,6 @@ def test_unranked_and_non_square_dictionaries(monkeypatch):
     the i16 extremes among them.  Every edge label is ConnectionTable::get over the dictionary's own ids."""
     from kanpyo_amd import Dict, Tokenizer, synth
     from kanpyo_amd.dictfile import MorphFeatureTable
-    from test_matrix_cpu import transposed_parts
 
     cases = [(Dict.from_parts(**transposed_parts()), True)]
     for shape, cost in (("nonsquare", "plain"), ("flat", "extreme"), ("huge", "plain"), ("corner", "ties")):

@@ -11,31 +11,10 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, fixture_dict_parts, load_golden
+from lines_ref import expected_lines
 from record_cases import _write_dict_dir
 
 pytestmark = pytest.mark.gpu
-
-
-def expected_lines(utf8, offs, tokens, tok_offsets, known, unk):
-    """(text bytes, text offsets[n + 1]) the reference prints for these records: print_tokens (kanpyo.rs:174-197) restated."""
-    cache = ({}, {})
-    out, toff, size = [], [0], 0
-    for i in range(len(offs) - 1):
-        raw = utf8[int(offs[i]) : int(offs[i + 1])].tobytes()
-        for t in tokens[int(tok_offsets[i]) : int(tok_offsets[i + 1])]:
-            cls, tid, pos, bl = int(t["cls"]), int(t["id"]), int(t["position"]), int(t["byte_len"])
-            surf = b"EOS" if cls == 0 else raw[pos : pos + bl]
-            feats = b""
-            if cls != 0 and tid != 0:
-                c = cache[cls - 1]
-                if tid not in c:
-                    c[tid] = ",".join((known if cls == 1 else unk).features(tid)).encode()
-                feats = c[tid]
-            line = surf + b"\t" + feats + b"\n"
-            out.append(line)
-            size += len(line)
-        toff.append(size)
-    return b"".join(out), np.array(toff, dtype=np.uint64)
 
 
 @pytest.fixture(scope="module")

@@ -11,8 +11,9 @@ import numpy as np
 import pytest
 
 from conftest import fixture_dict_parts
-from test_gpu_fuzz import _same
-from test_matrix_cpu import saturation_parts, transposed_parts
+from dict_cases import lattice_from_pyref, saturation_parts, transposed_parts
+from kernel_cases import CHAIN_KNOBS
+from kernel_run import STATUS_MARKER, assert_records, device_batch, host_batch, libs, set_env  # noqa: F401  (libs: the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -23,27 +24,17 @@ PATHS = [
     ("general", {"KGPU_POOL": "0", "KGPU_WINDOW": "0"}),
     ("team", {"KGPU_WINDOW_TEAM": "2", "KGPU_WINDOW_FIRST": "0"}),
 ]
-KNOBS = ("KGPU_POOL", "KGPU_WINDOW", "KGPU_WINDOW_TEAM", "KGPU_WINDOW_FIRST", "KGPU_NO_SMALL_CALLS")
+KNOBS = CHAIN_KNOBS + ("KGPU_NO_SMALL_CALLS",)
 
 
-@pytest.fixture(scope="module")
-def libs():
-    from kanpyo_amd import _lib
-
-    assert _lib.lib().kgpu_device_count() > 0, "no HIP device: the gpu tests need an MI355X"
-    from oracle import oracle
-
-    oracle.build()
-    return _lib, oracle
+def _same(tok, orc, sentences, what):
+    host_batch(tok, orc, sentences, 16, what)
 
 
 def _tok(d, env, monkeypatch):
     from kanpyo_amd import Tokenizer
 
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
+    set_env(monkeypatch, env, KNOBS)
     return Tokenizer(d)
 
 
@@ -66,27 +57,22 @@ def _compact_vs_full(tok, orc, sents):
     from kanpyo_amd.tokenizer import pack_sentences
 
     utf8, offs = pack_sentences(sents)
+    exp = orc.tokenize_batch(utf8, offs, 16)
     dev = torch.device("cuda", 0)
     n, cap = len(sents), int(offs[-1]) + len(sents)
     d_utf8 = torch.from_numpy(utf8.copy()).to(dev) if utf8.size else torch.zeros(1, dtype=torch.uint8, device=dev)
     d_off = torch.from_numpy(offs.astype(np.int64)).to(dev)
-    d_t8, d_t24 = torch.empty((cap, 2), dtype=torch.int32, device=dev), torch.empty((cap, 6), dtype=torch.int32, device=dev)
-    d_first = torch.empty((n, 2), dtype=torch.int32, device=dev)
-    d_toff, d_toff24 = torch.empty(n + 1, dtype=torch.int64, device=dev), torch.empty(n + 1, dtype=torch.int64, device=dev)
-    d_st, d_st24 = torch.empty(n, dtype=torch.uint8, device=dev), torch.empty(n, dtype=torch.uint8, device=dev)
+    d_t8, d_first = torch.empty((cap, 2), dtype=torch.int32, device=dev), torch.empty((n, 2), dtype=torch.int32, device=dev)
+    d_toff, d_st = torch.empty(n + 1, dtype=torch.int64, device=dev), torch.full((n,), STATUS_MARKER, dtype=torch.uint8, device=dev)
     ctx = DeviceContext(tok)
     ctx.tokenize_compact(d_utf8.data_ptr(), d_off.data_ptr(), n, int(offs[-1]), d_t8.data_ptr(), cap, d_first.data_ptr(), d_toff.data_ptr(), d_st.data_ptr())
     nt = ctx.sync()
-    ctx.tokenize(d_utf8.data_ptr(), d_off.data_ptr(), n, int(offs[-1]), d_t24.data_ptr(), cap, d_toff24.data_ptr(), d_st24.data_ptr())
-    nt24 = ctx.sync()
+    nt24, _ = device_batch(ctx, orc, sents, exp, what="24-byte records")
     ctx.close()
-    exp = orc.tokenize_batch(utf8, offs, 16)
     toff = d_toff.cpu().numpy().astype(np.uint64)
-    assert nt == nt24 == len(exp.tokens) and np.array_equal(toff, exp.offsets) and np.array_equal(d_toff24.cpu().numpy().astype(np.uint64), toff)
-    assert not d_st.cpu().numpy().any() and not d_st24.cpu().numpy().any()
-    t24 = d_t24[:nt24].cpu().numpy().reshape(-1)
-    assert np.array_equal(t24, exp.tokens.view(np.int32).reshape(-1))
-    assert np.array_equal(expand_tokens(d_t8[:nt].cpu().numpy(), toff, d_first.cpu().numpy()), exp.tokens)
+    assert nt == nt24 == len(exp.tokens), (nt, nt24, len(exp.tokens))
+    assert np.array_equal(toff, exp.offsets), "8-byte records: per-sentence token counts differ"
+    assert_records(d_st.cpu().numpy(), toff, expand_tokens(d_t8[:nt].cpu().numpy(), toff, d_first.cpu().numpy()), exp, sents, "8-byte records")
 
 
 def _every_path(d, sents, what, monkeypatch, oracle):
@@ -208,7 +194,6 @@ def test_lattice_dump_ranked_and_unranked(libs, monkeypatch):
     from kanpyo_amd import Dict, Tokenizer, synth
     from kanpyo_amd.lattice import dump_lattice, graphviz
     from oracle import pyref
-    from test_lattice_cpu import lattice_from_pyref
 
     cases = [(Dict.from_parts(**transposed_parts()), True)]
     for shape in ("nonsquare", "flat", "huge"):

@@ -15,55 +15,11 @@ import numpy as np
 import pytest
 
 import normalize_ref as N
-from conftest import ROOT, fixture_dict_parts
+from conftest import ROOT
 from kanpyo_amd import _lib
+from normalize_cases import DAKUTEN, KA, SENTENCES, env, mixed_lines  # noqa: F401  (env: the fixture)
 
 pytestmark = pytest.mark.gpu
-
-KA, DAKUTEN = "ｶ", "ﾞ"
-DIRTY = ["ﾊﾝｶｸｶﾀｶﾅ", "ＡＢＣ１２３", "㈱①", "ｶﾞｷﾞｸﾞ", "　", "e\u0301", "\u1100\u1161\u11a8", "\ufdfa", "a\u0323\u0301", "\u2126\u212b", "\ufa10", "ﾊﾟ"]
-CLEAN = ["東京", "すもも", "abc", " ", "テスト", "。", "辞書", "xyz 123", "形態素"]
-
-
-class Env:
-    pass
-
-
-@pytest.fixture(scope="module")
-def env():
-    """The reference's test dictionary with a few more keys -- among them what half-width and full-width text normalises to -- and display tables."""
-    from kanpyo_amd import Dict, Tokenizer
-    from kanpyo_amd.dictfile import MorphFeatureTable
-
-    p = fixture_dict_parts()
-    keys = sorted(["テスト", "辞書", "形態素", "ハンカク", "ABC", "(株)", "ガ", "東京", "123"], key=lambda s: s.encode())
-    p["sorted_keywords"] = keys
-    p["morphs"] = [[i % 3, i % 3, 1000 + 10 * i] for i in range(len(keys))]
-    e = Env()
-    e.dict = Dict.from_parts(**p)
-    e.known = MorphFeatureTable.from_features([["名詞"]] * len(keys))
-    e.unk = MorphFeatureTable.from_features([["未知"]] * len(p["unk_morphs"]))
-    e.tok = Tokenizer(e.dict)
-    e.tok.set_features(e.known, e.unk)
-    e.keys = keys
-    return e
-
-
-def mixed_lines(n, seed, max_bytes=200):
-    """n lines of clean and dirty pieces, 0 .. max_bytes bytes each (every fourth one clean, some empty)."""
-    rng = np.random.default_rng(seed)
-    lines = []
-    for i in range(n):
-        want = int(rng.integers(0, max_bytes + 1))
-        pool = CLEAN if i % 4 == 0 else CLEAN + DIRTY
-        s = b""
-        while True:
-            piece = pool[int(rng.integers(0, len(pool)))].encode()
-            if len(s) + len(piece) > want:
-                break
-            s += piece
-        lines.append(s)
-    return lines
 
 
 def check_batch(tok, lines, form):
@@ -189,7 +145,6 @@ def test_capacity(env):
 
 
 # ---- 6. the device-resident chain --------------------------------------------------------------------------------------------------------------------------------
-SENTENCES = ["ﾊﾝｶｸＡＢＣ㈱", "テスト辞書", "", "形態素ｶﾞ東京１２３", "あいうえお", "ﾃｽﾄ辞書ｶﾞ", "ＡＢＣ" * 30, "漢字ﾊﾝｶｸ", "a" + "\u0301" * 65, "東京"] * 7
 
 
 def test_device_chain_and_encode_tensor(env):

@@ -12,7 +12,7 @@ import pytest
 
 import pack_ref as P
 from conftest import ROOT
-from test_pack_cpu import ragged, sweep_calls
+from pack_cases import ragged, sweep_calls
 
 pytestmark = pytest.mark.gpu
 

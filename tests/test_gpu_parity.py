@@ -5,19 +5,10 @@ import numpy as np
 import pytest
 
 from conftest import fixture_dict_parts, load_golden
+from dict_cases import CHAR_DEF, LEX_A, LEX_B, UNK_DEF, lattice_from_pyref, mecab_matrix
+from kernel_run import device_batch, host_batch, libs, run_fresh  # noqa: F401  (libs: the fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def libs():
-    from kanpyo_amd import _lib
-
-    assert _lib.lib().kgpu_device_count() > 0, "no HIP device: the gpu tests need an MI355X"
-    from oracle import oracle
-
-    oracle.build()
-    return _lib, oracle
 
 
 @pytest.fixture(scope="module")
@@ -41,18 +32,7 @@ def full(libs):
 
 
 def assert_same(tok, orc, sentences, nthreads=8):
-    from kanpyo_amd.tokenizer import pack_sentences
-
-    utf8, offs = pack_sentences(sentences)
-    got_t, got_off, status = tok.tokenize_packed(utf8, offs)
-    exp = orc.tokenize_batch(utf8, offs, nthreads)
-    assert np.array_equal(status, np.zeros(len(sentences), dtype=np.uint8))
-    assert np.array_equal(got_off, exp.offsets), "per-sentence token counts differ"
-    if not np.array_equal(got_t, exp.tokens):
-        bad = np.nonzero(got_t != exp.tokens)[0][0]
-        s = int(np.searchsorted(exp.offsets, bad, side="right") - 1)
-        raise AssertionError(f"token {bad} (sentence {s}: {sentences[s]!r}) differs: gpu {got_t[bad]} oracle {exp.tokens[bad]}")
-    return exp
+    return host_batch(tok, orc, sentences, nthreads)
 
 
 def test_fixture_vectors(libs):
@@ -315,41 +295,17 @@ def test_full_size_dense_dictionary(libs):
     tok.close()
 
 
-def _device_run(tok, sentences, mode):
-    """Drive the device-resident C ABI (kgpu_ctx_*) with torch-owned HBM buffers."""
-    import torch
-
-    from kanpyo_amd.device import DeviceContext
-    from kanpyo_amd.tokenizer import pack_sentences
-
-    utf8, offs = pack_sentences(sentences)
-    dev = torch.device("cuda", 0)
-    d_utf8 = torch.from_numpy(utf8.copy()).to(dev) if utf8.size else torch.zeros(1, dtype=torch.uint8, device=dev)
-    d_off = torch.from_numpy(offs.astype(np.int64)).to(dev)
-    n, cap = len(sentences), int(offs[-1]) + len(sentences)
-    d_tok = torch.empty((cap, 6), dtype=torch.int32, device=dev)
-    d_toff = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    d_st = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
-    ctx = DeviceContext(tok)
-    ctx.set_profiling(mode)
-    ctx.tokenize(d_utf8.data_ptr(), d_off.data_ptr(), n, int(offs[-1]), d_tok.data_ptr(), cap, d_toff.data_ptr(), d_st.data_ptr())
-    nt = ctx.sync()
-    return ctx, d_tok[:nt].cpu().numpy(), d_toff.cpu().numpy(), utf8, offs
-
-
 def test_device_api_and_work_counters(full):
     """The device-side work counters (B, C, T, N, E, K) equal the oracle's."""
     from kanpyo_amd import synth
     from kanpyo_amd.device import PROFILE_EVENTS, PROFILE_WORK
+    from kanpyo_amd.tokenizer import pack_sentences
 
     sd, tok, orc = full
     sents = synth.make_corpus(sd, 4096, 1, "cfg2") + synth.make_corpus(sd, 200, 2, "cfg3") + synth.make_corpus(sd, 3, 5, "cfg5")
-    ctx, t, toff, utf8, offs = _device_run(tok, sents, PROFILE_WORK | PROFILE_EVENTS)
-    exp = orc.tokenize_batch(utf8, offs, 8)
-    assert np.array_equal(toff.astype(np.uint64), exp.offsets)
-    assert np.array_equal(t.reshape(-1), exp.tokens.view(np.int32).reshape(-1))
-    assert ctx.work() == exp.counters
-    p = ctx.profile()
+    exp = orc.tokenize_batch(*pack_sentences(sents), 8)
+    p, work = run_fresh(tok, orc, sents, PROFILE_WORK | PROFILE_EVENTS, exp=exp, also=("work",))
+    assert work == exp.counters, (work, exp.counters)
     assert p["launches"] == 1 and p["tokenize_ms"] > 0  # (a batch that finds the chain's tail left out gets the tail alone afterwards: the chain is timed once)
 
 
@@ -377,13 +333,11 @@ def test_every_launch_chain_is_bit_exact(libs, pool, window_kib, monkeypatch):
 def test_built_and_reloaded_dictionary(libs, tmp_path):
     """8(f): a dictionary built from MeCab-format sources, saved as a Kanpyo .dict, reloaded and
     uploaded tokenises bit-exactly like the oracle over the same blobs."""
-    from test_builder_cpu import CHAR_DEF, LEX_A, LEX_B, UNK_DEF, _matrix
-
     from kanpyo_amd import Tokenizer, builder
     from kanpyo_amd.dictfile import format_tokens, load_dict, save_dict
 
     _, oracle = libs
-    df = builder.build(builder.parse_csv(LEX_A) + builder.parse_csv(LEX_B), _matrix(), CHAR_DEF, builder.parse_unk_def(UNK_DEF))
+    df = builder.build(builder.parse_csv(LEX_A) + builder.parse_csv(LEX_B), mecab_matrix(), CHAR_DEF, builder.parse_unk_def(UNK_DEF))
     p = tmp_path / "mini.dict"
     save_dict(df, str(p))
     back = load_dict(str(p))
@@ -475,7 +429,6 @@ def test_lattice_dump_and_graphviz(libs, full):
     from kanpyo_amd import Dict, Tokenizer, synth
     from kanpyo_amd.lattice import dump_lattice, graphviz
     from oracle import pyref
-    from test_lattice_cpu import lattice_from_pyref
 
     g = load_golden("fixture_graphviz.json")
     d = Dict.from_parts(**fixture_dict_parts())
@@ -652,7 +605,6 @@ def test_windowed_kernel_big_buckets_and_many_prefixes(libs, window_kib, monkeyp
       (kgpu_routing.window_handed[2]; tests/test_gpu_window_limits.py has the exact boundary) -- the same records either way.
     Pool off: every sentence goes through the windowed kernel.  Routing must show what was handed on, and why."""
     from kanpyo_amd import Dict, Tokenizer, synth
-    from kanpyo_amd.device import PROFILE_OFF
 
     _, oracle = libs
     monkeypatch.setenv("KGPU_POOL", "0")
@@ -666,10 +618,7 @@ def test_windowed_kernel_big_buckets_and_many_prefixes(libs, window_kib, monkeyp
     for k in range(300):
         run = "".join(map(chr, rng.integers(0x30A1, 0x30F7, size=int(rng.integers(20, 200))))) if k % 3 else "".join(map(chr, rng.integers(0x30, 0x3A, size=int(rng.integers(20, 200)))))
         sents.append(words[k][: int(rng.integers(0, 30))] + run + words[k + 1][: int(rng.integers(1, 30))] + (run[:40] if k % 5 == 0 else ""))
-    ctx, t, toff, utf8, offs = _device_run(tok, sents, PROFILE_OFF)
-    exp = orc.tokenize_batch(utf8, offs, 8)
-    assert np.array_equal(toff.astype(np.uint64), exp.offsets) and np.array_equal(t.reshape(-1), exp.tokens.view(np.int32).reshape(-1))
-    prof = ctx.profile()
+    prof = run_fresh(tok, orc, sents, nthreads=8)
     if window_kib != "9":   # (at 9 KB some windows do not fit even four positions long: those sentences may travel on -- still the same records)
         assert prof["deferred"][0] == 0 and prof["window_handed"] == [0] * 10, prof
     else:                   # ... and for that reason alone (a lone batch runs the team form first: what neither form holds is counted by both)
@@ -688,10 +637,7 @@ def test_windowed_kernel_big_buckets_and_many_prefixes(libs, window_kib, monkeyp
                             {0: (1, 1), 1: (1, 2), 2: (2, 1)}, [[0, 0, 4000], [1, 1, 3500]])
         tok2, orc2 = Tokenizer(d), oracle.OracleTokenizer.from_dict(d)
         sents2 = ["あ" * n for n in (1, 8, 9, 10, 17, 33, 64, 200)] + ["あ" * 12 + "い" + "あ" * 40, "いあいあ" * 30, "あ" * 5 + "x" + "あ" * 70]
-        ctx2, t2, toff2, utf82, offs2 = _device_run(tok2, sents2, PROFILE_OFF)
-        exp2 = orc2.tokenize_batch(utf82, offs2, 2)
-        assert np.array_equal(toff2.astype(np.uint64), exp2.offsets) and np.array_equal(t2.reshape(-1), exp2.tokens.view(np.int32).reshape(-1))
-        prof2 = ctx2.profile()
+        prof2 = run_fresh(tok2, orc2, sents2)
         if longest == 9:    # one parked match per position, at most 32 in a window: held, whatever the windows' lengths
             assert prof2["deferred"] == [0] * 4 and prof2["window_handed"] == [0] * 10, prof2
         else:               # "あ" * 33 and longer: 22 parked matches per position
@@ -747,25 +693,23 @@ def test_chain_tail_is_left_out_and_comes_back(libs):
     a batch that does need the tail is found by the last work list's count and run again with it (kgpu_routing.tail_reruns) -- same records
     (src/tokenizer.rs:16: calls are independent, a rerun is invisible)."""
     from kanpyo_amd import Tokenizer, synth
-    from kanpyo_amd.device import PROFILE_OFF
+    from kanpyo_amd.tokenizer import pack_sentences
 
     _, oracle = libs
     sd = synth.build_dict(20000, seed=5)
     tok, orc = Tokenizer(sd.dict), oracle.OracleTokenizer.from_dict(sd.dict)
     short = [s[:30] for s in synth.make_corpus(sd, 600, 9, "cfg2")]
+    exp = orc.tokenize_batch(*pack_sentences(short), 8)
     reruns = 0
     for k in range(14):  # the dictionary's contexts start with the tail armed; eight clean batches disarm it
-        ctx, t, toff, utf8, offs = _device_run(tok, short, PROFILE_OFF)
-        reruns += ctx.profile()["tail_reruns"]
+        reruns += run_fresh(tok, orc, short, exp=exp)["tail_reruns"]
     assert reruns == 0
     mixed = short[:100] + ["ア" * 900, "漢字かな" * 150] + synth.make_corpus(sd, 5, 10, "cfg3") + short[100:200]
-    ctx, t, toff, utf8, offs = _device_run(tok, mixed, PROFILE_OFF)
-    exp = orc.tokenize_batch(utf8, offs, 8)
-    assert np.array_equal(toff.astype(np.uint64), exp.offsets)
-    assert np.array_equal(t.reshape(-1), exp.tokens.view(np.int32).reshape(-1))
-    assert ctx.profile()["tail_reruns"] == 1
-    ctx, t, toff, utf8, offs = _device_run(tok, mixed, PROFILE_OFF)  # armed again: no rerun
-    assert np.array_equal(t.reshape(-1), exp.tokens.view(np.int32).reshape(-1)) and ctx.profile()["tail_reruns"] == 0
+    exp = orc.tokenize_batch(*pack_sentences(mixed), 8)
+    first = run_fresh(tok, orc, mixed, exp=exp)
+    assert first["tail_reruns"] == 1, first
+    again = run_fresh(tok, orc, mixed, exp=exp)  # armed again: no rerun
+    assert again["tail_reruns"] == 0, again
 
 
 def test_long_batches_start_with_the_windowed_kernel(libs, monkeypatch):
@@ -774,7 +718,6 @@ def test_long_batches_start_with_the_windowed_kernel(libs, monkeypatch):
     same as through the pool-first chain and the oracle's (src/tokenizer.rs:16: a call's result does not depend on how it was scheduled).  Alternating
     long and short batches on ONE context switches its stream back and forth; the host-buffer entry point takes the same decision per chunk."""
     from kanpyo_amd import Tokenizer, synth
-    from kanpyo_amd.device import PROFILE_OFF
     from kanpyo_amd.tokenizer import pack_sentences
 
     _, oracle = libs
@@ -785,28 +728,15 @@ def test_long_batches_start_with_the_windowed_kernel(libs, monkeypatch):
     utf8, offs = pack_sentences(docs)
     assert int(offs[-1]) >= 1024 * len(docs)
     exp = orc.tokenize_batch(utf8, offs, 8)
-    ctx, t, toff, _, _ = _device_run(tok, docs, PROFILE_OFF)
-    plan, prof = ctx.plan(), ctx.profile()
+    prof, plan = run_fresh(tok, orc, docs, exp=exp, also=("plan",))
     assert plan["window_first_bytes"] == 1024
-    assert np.array_equal(toff.astype(np.uint64), exp.offsets) and np.array_equal(t.reshape(-1), exp.tokens.view(np.int32).reshape(-1))
     assert prof["long_launches"] == 1 and prof["deferred"][0] == 0 and prof["redone"][0] == 0   # list 0 is the windowed kernel's own output: nothing left, nothing routed
     # the same context, alternating: short batch (pool first, shared stream), long, short
-    import torch
-
     from kanpyo_amd.device import DeviceContext
 
-    dev = torch.device("cuda", 0)
     c = DeviceContext(tok)
     for sents in (short, docs, short, docs):
-        u, o = pack_sentences(sents)
-        e = orc.tokenize_batch(u, o, 8)
-        n, cap = len(sents), int(o[-1]) + len(sents)
-        bufs = (torch.from_numpy(u.copy()).to(dev), torch.from_numpy(o.astype(np.int64)).to(dev), torch.empty((cap, 6), dtype=torch.int32, device=dev),
-                torch.empty(n + 1, dtype=torch.int64, device=dev), torch.empty(n, dtype=torch.uint8, device=dev))
-        c.tokenize(bufs[0].data_ptr(), bufs[1].data_ptr(), n, int(o[-1]), bufs[2].data_ptr(), cap, bufs[3].data_ptr(), bufs[4].data_ptr())
-        nt = c.sync()
-        assert np.array_equal(bufs[3].cpu().numpy().astype(np.uint64), e.offsets)
-        assert np.array_equal(bufs[2][:nt].cpu().numpy().reshape(-1), e.tokens.view(np.int32).reshape(-1))
+        device_batch(c, orc, sents, nthreads=8)
     # the host-buffer entry point (chunks of its pipeline take the decision one by one)
     assert_same(tok, orc, docs * 3 + short + docs)
     # with the rule switched off the pool kernel routes as before, and with the two-wavefronts-per-sentence form forced on (or off) for the window-first

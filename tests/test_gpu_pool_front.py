@@ -1,7 +1,7 @@
 """The pool kernel's front end after its diet (kanpyo_amd/csrc/kgpu_pool.hip: the window decode of phase 0b, the attempt loop that no longer sees B and
 C as invariants, the one-loop tile-list builder 3c, the token search that skips its two widest steps below 64 characters), at the sizes where that
-code takes another path.  Every batch is the oracle's bit for bit (test_gpu_tile_groups._run) and `deferred`, `redone`, `window_handed`, `tail_reruns`
-(with `window_reruns` and `arena_regrows`) EQUAL what tests/pool_model.py predicts from the lattice's shape (test_gpu_pool_limits.run_case): nothing a
+code takes another path.  Every batch is the oracle's bit for bit (kernel_run.device_batch) and `deferred`, `redone`, `window_handed`, `tail_reruns`
+(with `window_reruns` and `arena_regrows`) EQUAL what tests/pool_model.py predicts from the lattice's shape (kernel_run.run_case): nothing a
 sentence decides may have changed.
 
 round edges   C = 1, 2, 61, 62, 63, 64, 65, 126, 127 characters, once of one byte and once of three: the lane = position loops (decode, walk, scan, emit,
@@ -23,25 +23,13 @@ import pytest
 
 import pool_cases as PC
 import pool_model as M
-from test_gpu_pool_limits import COUNTERS, _set_env, run_case
-from test_gpu_tile_groups import _run
-from test_gpu_window_limits import make_parts
+from kernel_run import COUNTERS, libs, run_case, run_fresh, set_env  # noqa: F401  (libs: the fixture)
+from window_cases import make_parts
 
 pytestmark = pytest.mark.gpu
 
 ROUND_EDGES = [1, 2, 61, 62, 63, 64, 65, 126, 127]
 ENV_160 = {"KGPU_WINDOW_FIRST": "0"}   # (a batch's average length must not send it to the windowed kernel first)
-
-
-@pytest.fixture(scope="module")
-def libs():
-    from kanpyo_amd import _lib
-
-    assert _lib.lib().kgpu_device_count() > 0, "no HIP device: the gpu tests need an MI355X"
-    from oracle import oracle
-
-    oracle.build()
-    return _lib, oracle
 
 
 @functools.lru_cache(maxsize=None)
@@ -164,7 +152,7 @@ def test_tile_list_of_1_2_4_6(libs, monkeypatch):
     sents = [s, s * 2, "あ" + s, s + "あ", "あああ", "いあ" * 4, s[::-1]]
     run_case(PC.Case("tile list", d, plan, [PC.Batch(d, plan, PC.among(sents, k=1), "among short ones"), PC.Batch(d, plan, [s], "alone")]), libs[1], monkeypatch)
     # the device's own lattice of s has the shape the model counted: nodes per start position, entries per bucket
-    _set_env(monkeypatch, {})
+    set_env(monkeypatch, {})
     tok = Tokenizer(Dict.from_parts(**d.parts))
     try:
         lat = dump_lattice(tok, s)
@@ -211,14 +199,14 @@ def test_tickets_from_a_work_list(libs, monkeypatch):
     v0 = [d.verdict(s, M.PLAN_SHIPPED, est1)["verdict"] for s in second]
     assert M.counters(v0) == (3, 0)
     assert all(d.verdict(s, M.PLAN_160, est1)["verdict"] == M.HELD for s in long3)   # ... and the 160 KB pool holds the three without a redo
-    _set_env(monkeypatch, {"KGPU_POOL": "40:4:32,160:4"})
+    set_env(monkeypatch, {"KGPU_POOL": "40:4:32,160:4"})
     dd = Dict.from_parts(**d.parts)
     orc = libs[1].OracleTokenizer.from_dict(dd)
     tok = Tokenizer(dd)
     try:
-        p1 = _run(tok, orc, first)
+        p1 = run_fresh(tok, orc, first)
         assert p1["deferred"][0] == 3 and p1["redone"] == [0, 0, 0, 0], p1   # (one pool in this chain: the windowed kernel served the three)
-        p2 = _run(tok, orc, second)
+        p2 = run_fresh(tok, orc, second)
         got = {k: p2[k] for k in COUNTERS}
         print(f"work list: first {p1['deferred']} second {got}")
         assert got == {"deferred": [3, 0, 0, 0], "redone": [0, 0, 0, 0], "window_handed": [0] * 10, "tail_reruns": 0, "window_reruns": 0, "arena_regrows": 0}, got

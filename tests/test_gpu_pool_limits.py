@@ -7,7 +7,7 @@ function of that sentence alone; tests/pool_model.py restates that arithmetic li
 it -- a HELD sentence just inside each limit, a REDONE or handed one just outside -- and tests/test_pool_model_cpu.py asserts every such claim without
 a device.  Here every batch runs on a FRESH Tokenizer (Steering::est_q8 is the initial 64 x 256) with KGPU_POOL set explicitly ("40:4:32": the shipped
 shape without the per-batch choices of the shipped plan; "160:4" with KGPU_WINDOW_FIRST=0); records, offsets and status are the oracle's bit for bit
-(test_gpu_tile_groups._run) and deferred, redone, window_handed, tail_reruns, window_reruns and arena_regrows EQUAL the model's prediction:
+(kernel_run.device_batch) and deferred, redone, window_handed, tail_reruns, window_reruns and arena_regrows EQUAL the model's prediction:
 
 a  routed before the walk at the exact page (n = 100 / 101 x "あ", 32 / 33 pages);
 b  the redo from both sides of a page -- need_full binding, need_emit binding, and a one-load sentence whose redo stages the text the long way --
@@ -22,53 +22,12 @@ i  the estimate learns: the mixed batch three times on ONE handle, the redo coun
 
 Left out on purpose: `N > 0xFFFF || Nb + 1 > SLOT_MAX` cannot be reached (neither fits a pool of 160 KB); the pool_wait_alloc time-out is not to be
 provoked; the one-load byte lengths and alignments are test_byte_length_and_alignment_boundaries', the WIDE layout is test_plain_leaves_layout's."""
-import numpy as np
 import pytest
 
 import pool_cases as PC
-import pool_model as M
-from test_gpu_tile_groups import _run
+from kernel_run import COUNTERS, host_batch, libs, run_case, run_fresh, set_env  # noqa: F401  (libs: the fixture)
 
 pytestmark = pytest.mark.gpu
-
-COUNTERS = ("deferred", "redone", "window_handed", "tail_reruns", "window_reruns", "arena_regrows")
-ENV_NAMES = ("KGPU_POOL", "KGPU_WINDOW", "KGPU_WINDOW_TEAM", "KGPU_WINDOW_FIRST")
-
-
-@pytest.fixture(scope="module")
-def libs():
-    from kanpyo_amd import _lib
-
-    assert _lib.lib().kgpu_device_count() > 0, "no HIP device: the gpu tests need an MI355X"
-    from oracle import oracle
-
-    oracle.build()
-    return _lib, oracle
-
-
-def _set_env(monkeypatch, env):
-    for name in ENV_NAMES:
-        monkeypatch.delenv(name, raising=False)
-    for name, v in env.items():
-        monkeypatch.setenv(name, v)
-
-
-def run_case(case, oracle, monkeypatch):
-    """every batch of the case on a fresh handle: the oracle's records, the model's counters"""
-    from kanpyo_amd import Dict, Tokenizer
-
-    _set_env(monkeypatch, case.env)
-    d = Dict.from_parts(**case.parts)
-    orc = oracle.OracleTokenizer.from_dict(d)
-    for b in case.batches:
-        tok = Tokenizer(d)
-        try:
-            prof = _run(tok, orc, b.sentences)
-        finally:
-            tok.close()
-        got, want = {k: prof[k] for k in COUNTERS}, b.expect()
-        print(f"{case.name} [{b.note}] {len(b.sentences)} sentences: {got}")
-        assert got == want, (case.name, b.note, got, want)
 
 
 def test_a_routed_before_the_walk(libs, monkeypatch):
@@ -110,22 +69,18 @@ def test_h_the_small_calls_slice(libs, monkeypatch):
     """kgpu_tokenize_batch with one sentence: served in the one launch while its exact need fits the slice, redone on the general path (small_fallbacks)
     when it does not -- the oracle's records either way."""
     from kanpyo_amd import Dict, Tokenizer
-    from kanpyo_amd.tokenizer import pack_sentences
 
-    _set_env(monkeypatch, {})
+    set_env(monkeypatch, {})
     h = PC.case_h()
     d = Dict.from_parts(**h["d"].parts)
     orc = libs[1].OracleTokenizer.from_dict(d)
     for key, fallbacks in (("held", 0), ("handed", 1)):
         tok = Tokenizer(d)
         try:
-            utf8, offs = pack_sentences(PC.SHORT[:2] + [h[key]] + PC.SHORT[2:])
-            got_t, got_off, status = tok.tokenize_packed(utf8, offs)
+            host_batch(tok, orc, PC.SHORT[:2] + [h[key]] + PC.SHORT[2:], what=key)
             r = tok.routing()
         finally:
             tok.close()
-        exp = orc.tokenize_batch(utf8, offs, 2)
-        assert not status.any() and np.array_equal(got_off, exp.offsets) and np.array_equal(got_t, exp.tokens), key
         print(f"small call, {key} ({len(h[key])} characters): small_calls {r['small_calls']} small_fallbacks {r['small_fallbacks']} deferred {r['deferred']} redone {r['redone']}")
         assert r["small_calls"] == 1 and r["small_fallbacks"] == fallbacks, (key, r)
         if not fallbacks:   # the one launch served it: nothing left the pool kernel, no reservation to prove too small
@@ -141,13 +96,13 @@ def test_i_the_estimate_learns(libs, monkeypatch):
     from kanpyo_amd import Dict, Tokenizer
 
     case = PC.case_b_mixed()
-    _set_env(monkeypatch, case.env)
+    set_env(monkeypatch, case.env)
     d = Dict.from_parts(**case.parts)
     orc = libs[1].OracleTokenizer.from_dict(d)
     tok = Tokenizer(d)
     try:
         for est, b in PC.learning_runs():
-            prof = _run(tok, orc, b.sentences)
+            prof = run_fresh(tok, orc, b.sentences)
             got, want = {k: prof[k] for k in COUNTERS}, b.expect()
             print(f"est_q8 {est}: {got}")
             assert got == want, (est, got, want)

@@ -10,9 +10,12 @@ created without a stream runs each batch on the least-loaded shared stream.  Whi
 Every batch is compared bit-exactly with the oracle.  Batches of 64 short sentences over a small synthetic dictionary."""
 import ctypes as C
 import threading
+import types
 
 import numpy as np
 import pytest
+
+from kernel_run import assert_records, libs  # noqa: F401  (libs: the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -20,13 +23,11 @@ N = 64
 
 
 @pytest.fixture(scope="module")
-def env():
-    from kanpyo_amd import Tokenizer, _lib, synth
+def env(libs):
+    from kanpyo_amd import Tokenizer, synth
     from kanpyo_amd.tokenizer import pack_sentences
-    from oracle import oracle
 
-    assert _lib.lib().kgpu_device_count() > 0, "no HIP device: the gpu tests need an MI355X"
-    oracle.build()
+    _, oracle = libs
     sd = synth.build_dict(5000, seed=11)
     tok, orc = Tokenizer(sd.dict), oracle.OracleTokenizer.from_dict(sd.dict)
     sents = synth.make_corpus(sd, N * 5, 23, "cfg2")
@@ -80,15 +81,11 @@ class _Slot:
         self.busy = True
 
     def collect(self, batch, what):
-        from kanpyo_amd.tokenizer import TOKEN_DTYPE
-
         _, _, etok, eoff = batch
         nt = self.ctx.sync()
         self.busy = False
         assert nt == len(etok), (what, nt, len(etok))
-        assert not self.d_st.cpu().numpy().any(), what
-        assert np.array_equal(self.d_toff.cpu().numpy().astype(np.uint64), eoff), f"{what}: token offsets differ"
-        assert np.array_equal(self.d_rec[:nt].cpu().numpy().view(TOKEN_DTYPE).reshape(-1), etok), f"{what}: records differ"
+        assert_records(self.d_st.cpu().numpy(), self.d_toff.cpu().numpy(), self.d_rec[:nt].cpu().numpy(), types.SimpleNamespace(tokens=etok, offsets=eoff), None, what)
         self.d_rec.zero_()   # the next batch on this slot has to write them again (waited for here: the contexts' streams do not wait for torch's)
         self.d_toff.zero_()
         self.torch.cuda.synchronize(self.d_rec.device)

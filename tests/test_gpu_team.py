@@ -4,32 +4,15 @@ its team form whatever the load.  What the form hands on (a carry list beyond it
 positions independently and relaxes them in order (src/lattice.rs:101-114, 116-142): which wavefront ran which window cannot show in the records."""
 import random
 
-import numpy as np
 import pytest
+
+from kernel_run import host_batch, libs  # noqa: F401  (libs: the fixture)
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def libs():
-    from kanpyo_amd import _lib
-
-    assert _lib.lib().kgpu_device_count() > 0, "no HIP device: the gpu tests need an MI355X"
-    from oracle import oracle
-
-    oracle.build()
-    return _lib, oracle
-
-
 def _same(tok, orc, sentences, what):
-    from kanpyo_amd.tokenizer import pack_sentences
-
-    utf8, offs = pack_sentences(sentences)
-    exp = orc.tokenize_batch(utf8, offs, 16)
-    got_t, got_off, status = tok.tokenize_packed(utf8, offs)
-    assert not status.any(), what
-    assert np.array_equal(got_off, exp.offsets), f"{what}: per-sentence token counts differ"
-    assert np.array_equal(got_t, exp.tokens), f"{what}: records differ"
+    host_batch(tok, orc, sentences, 16, what)
 
 
 @pytest.mark.parametrize("window_kib", ["10", "9", "16"])

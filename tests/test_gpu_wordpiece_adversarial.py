@@ -17,7 +17,8 @@ import encode_ref as E
 import encode_spans_ref as S
 import wordpiece_cases as WC
 from record_cases import SENTINEL, SMALL_KEYS, _Dev, dev_encode, ref_spec, small_ctx, small_env  # noqa: F401  (small_ctx, small_env: the fixtures)
-from test_gpu_encode_spans import check_padded, check_ragged
+from record_cases import check_spans_padded as check_padded
+from record_cases import check_spans_ragged as check_ragged
 
 pytestmark = pytest.mark.gpu
 

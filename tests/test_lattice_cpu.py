@@ -4,21 +4,10 @@ the lattice here comes from the naive Python restatement -- the device dump is c
 import numpy as np
 
 from conftest import fixture_dict_parts, load_golden
+from dict_cases import lattice_from_pyref
 from kanpyo_amd.dict import Dict
-from kanpyo_amd.lattice import Lattice, Node, graphviz
-from kanpyo_amd.token import TokenClass
+from kanpyo_amd.lattice import graphviz
 from oracle import pyref
-
-
-def lattice_from_pyref(pd, text):
-    """oracle/pyref.lattice -> kanpyo_amd.lattice.Lattice (shared with tests/test_gpu_parity.py)."""
-    raw = text.encode("utf-8")
-    nodes, edges, dp, pre = pyref.lattice(pd, text)
-    out = []
-    for i, (cls, nid, bpos, cpos, morph, bl, cl) in enumerate(nodes):
-        out.append(Node(nid, TokenClass(cls), bpos, cpos, cpos + cl, morph[0], morph[1], morph[2], raw[bpos : bpos + bl].decode("utf-8"),
-                        0 if dp[i] is None else dp[i], pre[i]))
-    return Lattice(out, [list(e) for e in edges])
 
 
 def _fixture():

@@ -1,5 +1,5 @@
 """tests/lines_ref.py -- the reference renderer the GPU tests of kgpu_format.hip compare with -- pinned on the CPU: against the per-token
-loop of tests/test_gpu_lines.py (expected_lines, which stays as it is), against the hand-derived lines of tests/golden/fixture_tokens.json,
+loop tests/test_gpu_lines.py compares with (lines_ref.expected_lines, which stays as it is), against the hand-derived lines of tests/golden/fixture_tokens.json,
 and on every generator tests/test_gpu_format.py uses (each kind of crafted record, the window regimes, the 70 001-sentence shape and the
 4 GiB shape scaled down to a few MiB)."""
 import numpy as np
@@ -7,7 +7,7 @@ import pytest
 
 import lines_ref as R
 from conftest import load_golden
-from test_gpu_lines import expected_lines
+from lines_ref import expected_lines
 
 
 def _small_tables():

@@ -3,40 +3,14 @@
 (connection.rs:12-14); the Viterbi total is (dp + cost + matrix).min(INF) with a strict '<' against INF, and the
 backtrace stops at the first node without a predecessor (lattice.rs:116-150).  The same dictionaries run on the GPU in
 tests/test_gpu_matrix.py.  CPU only."""
-import numpy as np
 import pytest
 
-from conftest import fixture_dict_parts
+from dict_cases import saturation_parts, transposed_parts
 from kanpyo_amd.dict import Dict
 from oracle import oracle, pyref
 
 INF = 1 << 30
 A, I = "あ", "い"
-
-
-def saturation_parts():
-    """The fixture with no unknown hiragana nodes, a 2x3 matrix and two words at the i16 extremes:
-    あ = (left 1, right 1, 32767), い = (left 2, right 1, -32768).  get(r, l) = data[2 l + r]:
-    BOS -> あ data[2] = 0; あ -> あ data[3] = 32767; あ / い -> い data[5] = -32768; あ / い -> EOS data[1] = 0."""
-    p = fixture_dict_parts()
-    p["invoke_list"] = np.array([0, 1, 0], dtype=np.uint8)
-    p["group_list"] = np.array([0, 1, 0], dtype=np.uint8)
-    p["sorted_keywords"] = [A, I]
-    p["morphs"] = [[1, 1, 32767], [2, 1, -32768]]
-    p["conn_rows"], p["conn_cols"], p["conn_data"] = 2, 3, [0, 0, 0, 32767, 0, -32768]
-    return p
-
-
-def transposed_parts():
-    """A 3x2 matrix (rows > cols) where the layout decides the token: あ has two records, (1, 0) = id 1 and (1, 2) = id 2,
-    い = (1, 0) = id 3.  get(r, l) = data[3 l + r]: id 1 -> い reads data[3] = 0, id 2 -> い reads data[5] = -100, so id 2
-    wins.  Indexed by cols instead (data[2 l + r]) the two read data[2] = -500 and data[4] = 0 and id 1 would win."""
-    p = fixture_dict_parts()
-    p["invoke_list"] = np.array([0, 1, 0], dtype=np.uint8)
-    p["sorted_keywords"] = [A, A, I]
-    p["morphs"] = [[1, 0, 0], [1, 2, 0], [1, 0, 0]]
-    p["conn_rows"], p["conn_cols"], p["conn_data"] = 3, 2, [0, 0, -500, 0, 0, -100]
-    return p
 
 
 def saturation_expected(n, m):

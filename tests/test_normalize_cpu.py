@@ -4,7 +4,6 @@ composition pairs and on seeded random strings; the committed tables against a f
 AddressSanitizer + UBSan; the new symbols, the header, the argument errors, the CLI's options, and the binding's normalize= keyword over a stub
 library (normalize=None reaches no normalise entry point)."""
 import ctypes as C
-import functools
 import gc
 import os
 import subprocess
@@ -16,13 +15,13 @@ import pytest
 import normalize_ref as N
 from conftest import ROOT
 from kanpyo_amd import _lib
+from normalize_cases import StubLib, same_unicode
 
 HERE = os.path.join(ROOT, "tests", "c_abi")
 INC = os.path.join(ROOT, "include")
 CSRC = os.path.join(ROOT, "kanpyo_amd", "csrc")
 NEW = ("kgpu_normalize_unicode_version", "kgpu_normalize_host", "kgpu_normalize_batch", "kgpu_normalize_text", "kgpu_normalize_device", "kgpu_ctx_sync_normalize")
-SAME_UNICODE = pytest.mark.skipif(not N.versions_agree(), reason=f"Python's unicodedata is {unicodedata.unidata_version}, the committed tables are "
-                                  f"{_lib.lib().kgpu_normalize_unicode_version().decode()}")
+SAME_UNICODE = same_unicode()
 
 
 # ---- the fixture ----------------------------------------------------------------------------------------------------------------------------
@@ -259,98 +258,6 @@ def test_help_lists_normalize(command, capsys):
 
 
 # ---- the binding over a stub library ------------------------------------------------------------------------------------------------------------------
-def _view(addr, dtype, count):
-    dt = np.dtype(dtype)
-    return np.frombuffer((C.c_uint8 * max(count * dt.itemsize, 1)).from_address(addr), dtype=dt)[:count]
-
-
-class StubLib:
-    """Stands where _lib.lib() stands: logs the entry points reached.  A normalise entry upper-cases ASCII, leaves the offsets and marks line 1 with status 4; every other
-    batch / block entry writes one unit per line and status 0."""
-
-    def __init__(self):
-        self.log, self.seen = [], []
-        self._next = 0x1000
-        for kind in ("dict", "words", "counts", "vocab"):
-            setattr(self, f"kgpu_{kind}_create", functools.partial(self._create, kind))
-            setattr(self, f"kgpu_{kind}_destroy", lambda h: None)
-
-    def kgpu_last_error(self):
-        return b"stub"
-
-    def _create(self, kind, *args):
-        self._next += 0x10
-        args[-1]._obj.value = self._next
-        return 0
-
-    def kgpu_dict_get_info(self, h, ref):
-        ref._obj.device = 0
-        return 0
-
-    def kgpu_normalize_batch(self, h, form, u, o, n, text, cap, toff, st, got):
-        self.log.append(("normalize_batch", form))
-        off = _view(o, np.uint64, n + 1)
-        total = int(off[n] - off[0])
-        got._obj.value = total
-        if total > cap:
-            return _lib.KGPU_ERR_CAPACITY
-        _view(text, np.uint8, total)[:] = np.frombuffer(_view(u, np.uint8, int(off[n]))[int(off[0]):].tobytes().upper(), dtype=np.uint8)
-        _view(toff, np.uint64, n + 1)[:] = off - off[0]
-        _view(st, np.uint8, n)[:] = [4 if i == 1 else 0 for i in range(n)]
-        return 0
-
-    def kgpu_normalize_text(self, h, form, src, length, text, cap, toff, ocap, st, n_ref, got):
-        self.log.append(("normalize_text", form))
-        lines = _view(src, np.uint8, length).tobytes().upper().split(b"\n")[:-1]
-        n_ref._obj.value, got._obj.value = len(lines), sum(map(len, lines))
-        if got._obj.value > cap or len(lines) + 1 > ocap:
-            return _lib.KGPU_ERR_CAPACITY
-        _view(text, np.uint8, got._obj.value)[:] = np.frombuffer(b"".join(lines), dtype=np.uint8)
-        _view(toff, np.uint64, len(lines) + 1)[:] = np.cumsum([0] + [len(x) for x in lines])
-        _view(st, np.uint8, len(lines))[:] = [4 if i == 1 else 0 for i in range(len(lines))]
-        return 0
-
-    def _batch(self, name, itemsize, h, u, o, n, units, cap, uoff, st, got):
-        off = _view(o, np.uint64, n + 1)
-        self.log.append(name)
-        self.seen.append(_view(u, np.uint8, int(off[n])).tobytes() if n and int(off[n]) else b"")
-        got._obj.value = n
-        if n > cap:
-            return _lib.KGPU_ERR_CAPACITY
-        _view(units, np.uint8, n * itemsize)[:] = 0
-        _view(uoff, np.uint64, n + 1)[:] = np.arange(n + 1)
-        _view(st, np.uint8, n)[:] = [1 if i == 2 else 0 for i in range(n)]
-        return 0
-
-    def _block(self, name, itemsize, h, src, length, units, cap, uoff, ocap, st, n_ref, got):
-        self.log.append(name)
-        n = _view(src, np.uint8, length).tobytes().count(b"\n")
-        n_ref._obj.value, got._obj.value = n, n
-        if n > cap or n + 1 > ocap:
-            return _lib.KGPU_ERR_CAPACITY
-        _view(uoff, np.uint64, n + 1)[:] = np.arange(n + 1)
-        _view(st, np.uint8, n)[:] = 0
-        return 0
-
-    def kgpu_count_batch(self, h, u, o, n, st):
-        self.log.append("count_batch")
-        off = _view(o, np.uint64, n + 1)
-        self.seen.append(_view(u, np.uint8, int(off[n])).tobytes())
-        _view(st, np.uint8, n)[:] = 0
-        return 0
-
-    def kgpu_count_text(self, h, src, length, st, cap, n_ref):
-        self.log.append("count_text")
-        n_ref._obj.value = _view(src, np.uint8, length).tobytes().count(b"\n")
-        return 0
-
-
-for _name, _size in (("tokenize_batch", 24), ("tokenize_batch_lines", 1), ("tokenize_batch_words", 1), ("encode_batch", 4)):
-    setattr(StubLib, "kgpu_" + _name, functools.partialmethod(StubLib._batch, _name, _size))
-for _name, _size in (("tokenize_text_lines", 1), ("tokenize_text_words", 1), ("encode_text", 4)):
-    setattr(StubLib, "kgpu_" + _name, functools.partialmethod(StubLib._block, _name, _size))
-
-
 @pytest.fixture
 def stub(fixture_dict, monkeypatch):
     from kanpyo_amd import Tokenizer

@@ -4,6 +4,7 @@ of which boundary it lies and by how many bytes -- by the model and the naive la
 case from passing for the wrong reason: a sentence that stopped being REDONE, or is REDONE for another need than the case names, fails here first."""
 import pytest
 
+import kernel_cases as KC
 import pool_cases as PC
 import pool_model as M
 
@@ -19,7 +20,7 @@ def _pyref(parts):
 # ------------------------------------------------------------------------------------------------------------------------------------------ the model
 def test_page_sizes_and_limits():
     assert [M.page_bytes(p) for p in (M.PLAN_SHIPPED, M.PLAN_160, M.PLAN_SMALL)] == [624, 2544, 1016]
-    assert M.page_bytes((80 * 1024, 8, 20)) == 1264 and M.page_bytes((20 * 1024, 2, 56)) == 304   # (test_gpu_tile_groups.PLANS; the shipped chain's other shape)
+    assert M.page_bytes((80 * 1024, 8, 20)) == 1264 and M.page_bytes((20 * 1024, 2, 56)) == 304   # (kernel_cases.PLANS; the shipped chain's other shape)
     assert 32 * 624 == 19968 and 64 * 1016 == 65024 and 64 * 2544 == 162816
     # one wavefront: pages of 8 bytes' granularity, not 16 (1016 = 127 x 8 is no multiple of 16)
     assert M.page_bytes((64 * 1024, 4, 64)) == 1008
@@ -202,31 +203,28 @@ def test_case_h_the_small_call():
     assert h["d"].verdict(h["handed"], M.PLAN_SHIPPED)["verdict"] == M.ROUTED_BEFORE_WALK
 
 
-# --------------------------------------------------------------------------------- the two older modules whose counters are the model's (test_gpu_tile_groups, test_gpu_dead_positions)
+# --------------------------------------------------------------------------------- the two older modules whose counters are the model's (tests/kernel_cases.py)
 def test_tile_groups_batches_by_the_model():
     """what test_gpu_tile_groups.py asks of the device, by the model alone: none of the sentences meant for the pool kernel is routed, and of the longer
     ones at least those whose nodes, bucket entries and tiles alone exceed the limit are; the shapes are the naive lattice's."""
-    import test_gpu_tile_groups as TG
-
-    plain = ["あ" * n for n in reversed(TG.NS)]
-    mixed = ["あ" * 3 + "い" + "あ" * 2, "い" + "あ" * 4, "あい" * 3, "いい", "あ" * 5 + "い", "い", "あ" * 7 + "いい" + "あ"]
+    plain, mixed = KC.tile_sentences()
     redone = 0
-    for k in TG.KS:
+    for k in KC.TILE_KS:
         if k in (1, 8, 9, 33, 66):
-            pyref, pd = _pyref(TG._parts(k))
+            pyref, pd = _pyref(KC.tile_parts(k))
             for s in plain[:2] + mixed:
-                assert TG._model(k).look(s)[2] == M.shape(pyref, pd, s)[0], (k, s)
-        for plan, mp in TG.MODEL_PLANS.items():
-            assert M.page_bytes(mp) * mp[2] == TG.PLANS[plan][1]
-            limit = TG.PLANS[plan][1]
-            inside = [s for s in plain + mixed if TG._lds_need(k, len(s)) * 6 <= limit * 5]
+                assert KC.tile_model(k).look(s)[2] == M.shape(pyref, pd, s)[0], (k, s)
+        for plan, mp in KC.MODEL_PLANS.items():
+            assert M.page_bytes(mp) * mp[2] == KC.PLANS[plan][1]
+            limit = KC.PLANS[plan][1]
+            inside = [s for s in plain + mixed if KC.tile_lds_need(k, len(s)) * 6 <= limit * 5]
             beyond = [s for s in plain + mixed if s not in inside]
-            want = TG._predicted(k, plan, inside)
+            want = KC.tile_predicted(k, plan, inside)
             assert want[0] == 0, (k, plan, want)
             redone += want[1]
             if beyond:
-                must = sum(1 for s in beyond if TG._lds_floor(k, s) > limit)
-                assert must <= TG._predicted(k, plan, beyond)[0] <= len(beyond), (k, plan)
+                must = sum(1 for s in beyond if KC.tile_lds_floor(k, s) > limit)
+                assert must <= KC.tile_predicted(k, plan, beyond)[0] <= len(beyond), (k, plan)
     assert redone > 0   # the equality is about something: some of these batches do redo sentences
 
 
@@ -234,10 +232,8 @@ def test_dead_positions_batches_by_the_model():
     """test_gpu_dead_positions.py's dictionaries: the model's shapes are the naive lattice's (dead positions, unreachable nodes and all)"""
     import numpy as np
 
-    import test_gpu_dead_positions as DP
-
     for k, negative in ((1, False), (9, False), (17, True), (8, True)):
-        pyref, pd = _pyref(DP._parts(k, negative))
-        sents = DP.BASES + DP._sentences(np.random.default_rng(k))[:40] + (DP.DEAD_ENDS + DP.BEHIND_TE if negative else [])
+        pyref, pd = _pyref(KC.dead_parts(k, negative))
+        sents = KC.BASES + KC.dead_sentences(np.random.default_rng(k))[:40] + (KC.DEAD_ENDS + KC.BEHIND_TE if negative else [])
         for s in sents:
-            assert DP._model(k, negative).look(s)[2] == M.shape(pyref, pd, s)[0], (k, negative, s)
+            assert KC.dead_model(k, negative).look(s)[2] == M.shape(pyref, pd, s)[0], (k, negative, s)

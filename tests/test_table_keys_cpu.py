@@ -8,7 +8,7 @@ import pytest
 import encode_ref as E
 import table_keys as T
 from kanpyo_amd import _lib
-from test_encode_cpu import synth20k, vocab_table  # noqa: F401  (synth20k: the fixture)
+from golden_cases import synth20k, vocab_table  # noqa: F401  (synth20k: the fixture)
 
 
 # ---- (a) the builders ----------------------------------------------------------------------------------------------------------------------------

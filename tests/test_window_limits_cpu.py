@@ -1,7 +1,7 @@
-"""The cases of tests/test_gpu_window_limits.py without a device: every scenario's sentences are on the intended side of their limit by the oracle's node
+"""The cases of tests/test_gpu_window_limits.py (tests/window_cases.py) without a device: every scenario's sentences are on the intended side of their limit by the oracle's node
 counts and the key lists alone (the scenarios_* functions assert that while they build the cases), the arena batches have the lengths the test
 counts on, and every limit from 1 to 8 has a held and a handed sentence."""
-import test_gpu_window_limits as L
+import window_cases as L
 
 
 def test_every_case_is_on_its_side_of_its_limit():

@@ -9,24 +9,14 @@ import numpy as np
 import pytest
 
 import words_ref as W
-from conftest import ROOT, fixture_dict_parts, load_golden
+from conftest import ROOT, load_golden
+from golden_cases import TOKEN_DTYPE, fixture_tables
 from kanpyo_amd import _lib
 from kanpyo_amd.dictfile import MorphFeatureTable
 
 HERE = os.path.join(ROOT, "tests", "c_abi")
 INC = os.path.join(ROOT, "include")
 SURFACE_BIT, DROPPED_BIT = 1 << 30, 1 << 31
-
-TOKEN_DTYPE = np.dtype([("id", "<i4"), ("cls", "<u4"), ("position", "<u4"), ("start", "<u4"), ("end", "<u4"), ("byte_len", "<u4")])
-
-
-def fixture_tables():
-    """The display rows of tests/test_gpu_lines.py::test_fixture_dictionary_hand_derived."""
-    p = fixture_dict_parts()
-    known = MorphFeatureTable.from_features([["名詞", f"k{i}", "*"] for i in range(1, len(p["morphs"]) + 1)])
-    unk = MorphFeatureTable.from_features([["未知語", f"u{i}"] for i in range(1, len(p["unk_morphs"]) + 1)])
-    return p, known, unk
-
 
 def golden_spec(c):
     return W.Spec(c["field"], c["filter"], c["names"], c["separator"])
