@@ -942,6 +942,52 @@ int kgpu_decode_device(kgpu_ctx *c, const kgpu_vocab *v, const int32_t *d_ids, c
 int kgpu_decode_batch(kgpu_vocab *v, const int32_t *ids, const uint64_t *id_offsets, uint64_t n, uint64_t width, const kgpu_decode_opts *opts,
                       uint8_t *text, uint64_t text_capacity, uint64_t *text_offsets, uint8_t *status, uint64_t *n_bytes);
 
+/* ---- N-best paths: the k lowest-cost tokenizations of each sentence (NOT an output of the reference: what `mecab -N k` prints) ----
+ * Take the lattice of Lattice::build (src/lattice.rs:29-114): nodes in insertion order, BOS = 0, EOS last; the predecessors of a node t are the nodes
+ * ending at t.char_pos (EOS has char_pos = C, the sentence's characters).  Take n_best = k with 1 <= k <= KGPU_NBEST_MAX.
+ *  The list per node.  Every node t gets a ranked list L(t) of at most k entries (cost, pred, pred_rank).
+ *    L(BOS) = [(0, none, none)].
+ *    For every other t the candidates are (L(j)[r].cost + t.cost + M[j.right_id][t.left_id], j, r) for every predecessor j and every rank r that L(j)
+ *    has; the arithmetic is int32.  A candidate whose cost is >= 1 << 30 is dropped: the reference's clamp and its strict '<' do the same
+ *    (src/lattice.rs:117,135-136).  L(t) holds the k smallest candidates under the lexicographic order of the triple (cost, j, r), sorted.
+ *  The result is L(EOS), best first.  Path number r is read back through (pred, pred_rank) down to BOS; BOS is dropped and EOS is kept, as tokenize does,
+ *  and each node on the path becomes the same 24-byte kgpu_token that tokenize emits for it.  The definition works on real BOS -> EOS paths only: a
+ *  node that nothing reachable ends at has an empty list.
+ * What follows from the rule:
+ *  1. Paths compare by cost, then backwards from the end: the order on paths is cost first, then (backwards from EOS) the lower predecessor node
+ *     index, then recursively the order of the two prefixes.  A brute-force enumeration of all paths sorted with that recursive comparator gives
+ *     exactly the first k (tests/nbest_ref.py does that).
+ *  2. Path 0 is tokenize's path: it holds exactly the records of kgpu_tokenize_batch whenever EOS is truly reachable -- the lowest-index tie-break of
+ *     the strict '<' is the (cost, j) order, and an unreachable predecessor's 1 << 30 candidate can never tie with or beat a real one.
+ *  3. Unreachable EOS gives 0 paths: where the reference returns [] or a chain whose head is an unreachable node (src/lattice.rs:144-153) there is no
+ *     real path; the sentence gets 0 paths and status KGPU_SENT_OK.
+ *  4. Fewer than k paths is not an error: a sentence with fewer than k paths gives them all.  "" gives one path, [EOS], with cost M[0][0].
+ *  5. Invalid UTF-8: the sentence gets KGPU_SENT_INVALID_UTF8 and 0 paths.
+ *  6. Too large: a lattice, with its lists (8 k N bytes for N nodes), that does not fit the largest scratch arena gets KGPU_SENT_NO_SCRATCH and 0 paths,
+ *     as in kgpu_graphviz_batch; the same holds for a lattice of 2^26 nodes or more.
+ * Output: sentence i's paths are path_offsets[i] .. path_offsets[i + 1] (n + 1 entries); path p has cost costs[p] and the records
+ * tokens[tok_offsets[p] .. tok_offsets[p + 1]) (tok_offsets: one entry more than there are paths). */
+#define KGPU_NBEST_MAX 64
+/* The rule on the host, in plain C++ over one lattice as kgpu_lattice_dump returns it (the dictionary's own context ids): no device, no handle; the
+ * definition of the device result, byte for byte.  conn: the connection matrix, element (right_id, left_id) at left_id * conn_rows + right_id
+ * (connection.rs:12-14).  tok_offsets has path_capacity + 1 entries.  KGPU_ERR_CAPACITY: nothing is written but *n_paths and *n_tokens, the exact sizes
+ * needed.  KGPU_ERR_INVALID_ARG: n_best 0 or above KGPU_NBEST_MAX, a null pointer where one is needed, fewer than two nodes or 2^26 of them or more,
+ * and a lattice whose edges or node fields contradict each other -- an edge node out of range or not in front of the node it leads to, a node that
+ * starts behind the last position, end_char < char_pos, a context id outside the matrix. */
+int kgpu_nbest_host(const kgpu_lattice *lattice, const int16_t *conn, uint64_t conn_rows, uint64_t conn_cols, uint32_t n_best,
+                    kgpu_token *tokens, uint64_t token_capacity, uint64_t *tok_offsets, int32_t *costs, uint64_t path_capacity,
+                    uint64_t *n_paths, uint64_t *n_tokens);
+/* n sentences in host memory, on the device: the general kernel leaves every lattice of a chunk (at most 256 KiB and 1024 sentences) in the scratch
+ * arena, one workgroup per sentence builds the lists (a wavefront per target node), and three small launches count, scan and write the paths -- the protocol of
+ * kgpu_graphviz_batch, chunk after chunk on one pooled context: a tool beside the throughput path, not a part of it.  Needs no feature tables.
+ * path_offsets: n + 1 entries; tok_offsets: path_capacity + 1; n * n_best paths always suffice.  status may be NULL; n_paths and n_tokens are
+ * required.  KGPU_ERR_CAPACITY: *n_paths and *n_tokens are the exact sizes needed (either may be the one that did not fit; a call whose input is one
+ * chunk has written nothing but the status bytes then). */
+int kgpu_tokenize_batch_nbest(kgpu_dict *d, const uint8_t *utf8, const uint64_t *offsets, uint64_t n, uint32_t n_best,
+                              kgpu_token *tokens, uint64_t token_capacity,
+                              uint64_t *path_offsets /* n + 1 */, uint64_t *tok_offsets, int32_t *costs, uint64_t path_capacity,
+                              uint8_t *status /* may be NULL */, uint64_t *n_paths, uint64_t *n_tokens);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,11 +5,12 @@ Host-side mirror of the reference's public API for that one path
 (include/kanpyo_gpu.h).  The HIP extension is mandatory: there is no CPU
 fallback, importing the tokenizer without the built library raises.
 """
-from .token import AlignedToken, Token, TokenClass  # noqa: F401
+from .token import AlignedToken, NBestPath, Token, TokenClass  # noqa: F401
 from .dict import Dict  # noqa: F401
 from .tokenizer import Tokenizer, TOKEN_DTYPE, normalize_host, normalize_host_aligned  # noqa: F401
 from .vocab import Vocab  # noqa: F401
 from .pack import pack_host  # noqa: F401
 from .decode import decode_host  # noqa: F401
+from .nbest import nbest_host  # noqa: F401
 
-__all__ = ["AlignedToken", "Token", "TokenClass", "Dict", "Tokenizer", "TOKEN_DTYPE", "Vocab", "normalize_host", "normalize_host_aligned", "pack_host", "decode_host"]
+__all__ = ["AlignedToken", "Token", "TokenClass", "Dict", "Tokenizer", "TOKEN_DTYPE", "Vocab", "normalize_host", "normalize_host_aligned", "pack_host", "decode_host", "NBestPath", "nbest_host"]

@@ -43,6 +43,7 @@ SYMBOLS = [
     "kgpu_encode_device_spans",
     "kgpu_pack_host", "kgpu_pack_device",
     "kgpu_decode_host", "kgpu_decode_device", "kgpu_decode_batch",
+    "kgpu_nbest_host", "kgpu_tokenize_batch_nbest",
 ]
 KGPU_VOCAB_ADD_BOS, KGPU_VOCAB_ADD_EOS = 1, 2
 KGPU_COUNTS_DEFAULT_SLOTS, KGPU_COUNTS_DEFAULT_KEY_BYTES = 1 << 22, 256 << 20
@@ -52,6 +53,7 @@ KGPU_PACK_WINDOWS = 1
 KGPU_PACK_LONGEST_FIRST, KGPU_PACK_ONLY_FIRST, KGPU_PACK_ONLY_SECOND = 0, 1, 2
 KGPU_PACK_OK, KGPU_PACK_CUT, KGPU_PACK_NO_ROOM = 0, 1, 2
 KGPU_DECODE_OK, KGPU_DECODE_BAD_ID, KGPU_DECODE_MAX_SKIP = 0, 1, 8
+KGPU_NBEST_MAX = 64
 
 
 def normalize_form(form) -> int:
@@ -310,6 +312,9 @@ def lib():
         L.kgpu_decode_host.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint32] + decode + [C.POINTER(C.c_uint64)]
         L.kgpu_decode_device.argtypes = [vp, vp] + decode
         L.kgpu_decode_batch.argtypes = [vp] + decode + [C.POINTER(C.c_uint64)]
+        nbest_out = [vp, C.c_uint64, vp, vp, C.c_uint64]   # tokens, token_capacity, tok_offsets, costs, path_capacity
+        L.kgpu_nbest_host.argtypes = [C.POINTER(LatticeOut), vp, C.c_uint64, C.c_uint64, C.c_uint32] + nbest_out + [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.kgpu_tokenize_batch_nbest.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, vp, vp, vp, C.c_uint64, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.kgpu_debug_wordpiece_split_ends.argtypes = [vp, vp, C.c_uint64, C.POINTER(WordpieceOpts), C.c_int32, vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, C.POINTER(C.c_uint64)]
         L.kgpu_debug_wordpiece_split.argtypes = [vp, vp, C.c_uint64, C.POINTER(WordpieceOpts), C.c_int32, vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.POINTER(C.c_uint64)]
         L.kgpu_debug_counts_order.argtypes = [vp, vp, vp, C.c_uint64] + L.kgpu_counts_read.argtypes[1:]

@@ -6,6 +6,10 @@ read_line + trim_end do) -- here in blocks of whole lines, each tokenized and re
 call and written out as soon as it is done.  `--split device` hands each block to kgpu_tokenize_text_lines as it was read: the split and the
 trim run on the device too (`--split host`, the default, splits with kgpu_split_lines on the host).  A line that is not UTF-8 ends the
 run as the reference's `expect` panic does: the lines before it are printed, exit status 101.  No subcommand means `tokenize` from stdin.
+`--nbest K` (1..64; NOT an option of the reference: what `mecab -N K` prints) prints for every input line its K lowest-cost paths, best first (fewer where
+the lattice has fewer, none where EOS is unreachable): each path is the lines of its tokens, ending with its EOS line, exactly as `tokenize` prints
+one.  The paths are found on the device (kgpu_tokenize_batch_nbest); their lines are rendered on the host from the records -- which needs the lines
+there: `--split device` with it is an argument error.
 
 `python -m kanpyo_amd graphviz [INPUT] [-c DICT] [-f/--full-state] [--dpi N]`: the reference's `kanpyo graphviz` (src/bin/kanpyo.rs:31-48,
 127-148 over src/graphviz.rs:30-163): the lattice of ONE sentence as a DOT document, built and rendered on the device in one
@@ -126,6 +130,7 @@ def _open(args):
     df = dictfile.load_dict(args.custom_dict or default_dict_path())
     tok = Tokenizer(df.dict)
     tok.set_features(df.morph_feature_table, df.unk_feature_table)
+    tok.dictfile = df   # (what renders records on the host reads the display tables here)
     return tok
 
 
@@ -188,10 +193,32 @@ def _form(args):
     return None if form == "none" else form.upper()
 
 
+def _nbest_lines(tok, n_best: int, form, utf8, offs):
+    """tokenize_lines_packed's result with every line's n_best paths in place of its one: the paths from the device, their lines made here."""
+    from .nbest import path_lines
+    from .tokenizer import merge_status
+
+    nstatus = None
+    if form:
+        utf8, offs, nstatus = tok.normalize_packed(utf8, offs, form)
+    tokens, poff, toff, _, status = tok.tokenize_nbest_packed(utf8, offs, n_best)
+    if nstatus is not None:
+        merge_status(status, nstatus)
+    raw, o, po, to = utf8.tobytes(), offs.tolist(), poff.tolist(), toff.tolist()
+    known, unk = tok.dictfile.morph_feature_table, tok.dictfile.unk_feature_table
+    out = [b"".join(path_lines(raw[o[i] : o[i + 1]], tokens[to[p] : to[p + 1]], known, unk) for p in range(po[i], po[i + 1])) for i in range(len(o) - 1)]
+    loff = np.zeros(len(out) + 1, dtype=np.uint64)
+    if out:
+        loff[1:] = np.cumsum([len(x) for x in out])
+    return np.frombuffer(b"".join(out), dtype=np.uint8), loff, status
+
+
 def tokenize(args, stdin, stdout) -> int:
     tok = _open(args)
     packed, text = tok.tokenize_lines_packed, tok.tokenize_text_lines
-    if _form(args):
+    if getattr(args, "nbest", None) is not None:
+        packed, text = partial(_nbest_lines, tok, args.nbest, _form(args)), None   # (parse_args refuses --split device)
+    elif _form(args):
         packed, text = partial(packed, normalize=_form(args)), partial(text, normalize=_form(args))
     return _print_lines(_results(args, stdin, packed, text), stdout,
                         "thread 'main' panicked: failed to read from stdin: stream did not contain valid UTF-8")
@@ -434,6 +461,12 @@ def _decode_separator(text: str) -> str:
     return text
 
 
+def _nbest(text: str) -> int:
+    if not text.isascii() or not text.isdigit() or not 1 <= int(text) <= 64:
+        raise argparse.ArgumentTypeError(f"invalid value {text!r}: a number of paths from 1 to 64")
+    return int(text)
+
+
 def _top(text: str) -> int:
     if not text.isascii() or not text.isdigit() or int(text) < 1:
         raise argparse.ArgumentTypeError(f"invalid value {text!r}: a count from 1")
@@ -539,7 +572,8 @@ def parse_args(argv=None):
     """The reference's command line (src/bin/kanpyo.rs:14-49).  -> the namespace; .command is "tokenize" or "graphviz" -- or "wakati", "count", "encode", "normalize" or "align", which are this package's own."""
     p = argparse.ArgumentParser(prog="kanpyo_amd", description="Japanese Morphological Analyzer (kanpyo) on AMD Instinct GPUs")
     sub = p.add_subparsers(dest="command")
-    t = _text_command(sub, "tokenize", "Tokenize input text")
+    t = _text_command(sub, "tokenize", "Tokenize input text",
+                      own=[("--nbest", dict(type=_nbest, default=None, metavar="K", help="Print each line's K lowest-cost paths, best first (1..64; not in the reference: mecab -N K)"))])
     g = sub.add_parser("graphviz", help="Output lattice in Graphviz format")
     g.add_argument("input", nargs="?", default=None, help="Input text to analyze [default: one line of stdin]")
     g.add_argument("-d", "--dict", choices=["ipa"], default="ipa", help="Dictionary")
@@ -581,6 +615,8 @@ def parse_args(argv=None):
     dc.add_argument("--skip", type=_skip_list, default=[], help="Ids that give no text: ID[,ID...], at most 8")
     dc.add_argument("--block-bytes", type=int, default=BLOCK_BYTES, help=argparse.SUPPRESS)
     args = p.parse_args(argv)
+    if args.command == "tokenize" and args.nbest is not None and args.split == "device":
+        t.error("--nbest renders its lines on the host: it does not go with --split device")
     if args.command is None:   # src/bin/kanpyo.rs:173: no subcommand == tokenize from stdin, default dictionary
         args = t.parse_args([])
         args.command = "tokenize"

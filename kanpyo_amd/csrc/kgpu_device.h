@@ -65,6 +65,39 @@ __device__ __forceinline__ uint32_t ld_l2(const uint32_t *p) {  // bypass the CU
 }
 __device__ __forceinline__ uint64_t round_up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
 
+// Exclusive scan of arr[0 .. n) in place by the whole workgroup of TPB threads; arr[n] = the total, which every thread gets (the scans of kgpu_graphviz.hip
+// and kgpu_nbest.hip: one workgroup over a chunk's per-sentence sizes).
+template <uint32_t TPB>
+__device__ uint64_t wg_excl_scan64(uint64_t *arr, uint64_t n) {
+    __shared__ uint64_t part[TPB];
+    __shared__ uint64_t carry_s;
+    const uint32_t tid = threadIdx.x;
+    __syncthreads();
+    if (tid == 0) carry_s = 0;
+    __syncthreads();
+    for (uint64_t base = 0; base < n; base += TPB) {
+        const uint64_t i = base + tid;
+        const uint64_t v = i < n ? arr[i] : 0;
+        part[tid] = v;
+        __syncthreads();
+        for (uint32_t d = 1; d < TPB; d <<= 1) {
+            const uint64_t add = tid >= d ? part[tid - d] : 0;
+            __syncthreads();
+            part[tid] += add;
+            __syncthreads();
+        }
+        const uint64_t carry = carry_s;
+        if (i < n) arr[i] = carry + part[tid] - v;
+        __syncthreads();
+        if (tid == TPB - 1) carry_s = carry + part[tid];
+        __syncthreads();
+    }
+    const uint64_t total = carry_s;
+    if (tid == 0) arr[n] = total;
+    __syncthreads();
+    return total;
+}
+
 struct Slab {
     uint8_t *ptr;
     uint64_t size;

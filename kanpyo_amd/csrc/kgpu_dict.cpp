@@ -70,6 +70,10 @@ TestHooks kgpu::test_hooks() {
         // ... and the bytes of the scratch arena a chunk's kept lattices may use at first / at most (0: the whole arena / ARENA_MAX): tests of the overflow protocol
         if (const char *e = getenv("KGPU_HOST_GRAPHVIZ_ARENA_INITIAL")) cur.graphviz_arena_initial = strtoull(e, nullptr, 10);
         if (const char *e = getenv("KGPU_HOST_GRAPHVIZ_ARENA_MAX")) cur.graphviz_arena_max = strtoull(e, nullptr, 10);
+        // ... the same three for kgpu_tokenize_batch_nbest, whose chunks keep their lattices and the lists behind them
+        if (const char *e = getenv("KGPU_HOST_NBEST_CHUNK_SENTS")) cur.nbest_chunk_sents = strtoull(e, nullptr, 10);
+        if (const char *e = getenv("KGPU_HOST_NBEST_ARENA_INITIAL")) cur.nbest_arena_initial = strtoull(e, nullptr, 10);
+        if (const char *e = getenv("KGPU_HOST_NBEST_ARENA_MAX")) cur.nbest_arena_max = strtoull(e, nullptr, 10);
         // ... and the first size of a context's scratch arena on the tokenize path, in bytes (0: ARENA_INITIAL; clamped to [1 MiB, ARENA_INITIAL]; read when a context is
         // created): tests of the windowed and the general kernel's overflow protocol (kgpu_ctx_sync doubles the arena and reruns the batch)
         if (const char *e = getenv("KGPU_ARENA_INITIAL")) cur.arena_initial = strtoull(e, nullptr, 10);

@@ -86,37 +86,6 @@ __device__ void wg_sort64(uint64_t *arr, uint32_t n) {
     }
 }
 
-// Exclusive scan of arr[0 .. n) in place by the whole workgroup; arr[n] = the total, which every thread gets.
-__device__ uint64_t wg_excl_scan64(uint64_t *arr, uint64_t n) {
-    __shared__ uint64_t part[TPB];
-    __shared__ uint64_t carry_s;
-    const uint32_t tid = threadIdx.x;
-    __syncthreads();
-    if (tid == 0) carry_s = 0;
-    __syncthreads();
-    for (uint64_t base = 0; base < n; base += TPB) {
-        const uint64_t i = base + tid;
-        const uint64_t v = i < n ? arr[i] : 0;
-        part[tid] = v;
-        __syncthreads();
-        for (uint32_t d = 1; d < TPB; d <<= 1) {
-            const uint64_t add = tid >= d ? part[tid - d] : 0;
-            __syncthreads();
-            part[tid] += add;
-            __syncthreads();
-        }
-        const uint64_t carry = carry_s;
-        if (i < n) arr[i] = carry + part[tid] - v;
-        __syncthreads();
-        if (tid == TPB - 1) carry_s = carry + part[tid];
-        __syncthreads();
-    }
-    const uint64_t total = carry_s;
-    if (tid == 0) arr[n] = total;
-    __syncthreads();
-    return total;
-}
-
 // ---- the text, written once: a sink either counts or stores
 struct Count {
     uint64_t n = 0;
@@ -283,14 +252,14 @@ __global__ __launch_bounds__(TPB) void k_gv_len(GraphvizArgs a) {
         if (!l.valid) { if (tid == 0) a.sent_len[s] = 0; continue; }
         for (uint32_t r = tid; r < l.V; r += TPB) { Count c; put_node(c, a, l, r); l.noff[r] = c.n; }
         for (uint32_t k = tid; k < l.N; k += TPB) { Count c; put_edges(c, a, l, k); l.eoff[k] = c.n; }
-        const uint64_t nodes = wg_excl_scan64(l.noff, l.V), edges = wg_excl_scan64(l.eoff, l.N);
+        const uint64_t nodes = wg_excl_scan64<TPB>(l.noff, l.V), edges = wg_excl_scan64<TPB>(l.eoff, l.N);
         if (tid == 0) { Count h; put_header(h, a.dpi); a.sent_len[s] = h.n + nodes + edges + 2; }
     }
 }
 
 // (the pattern of k_lines_scan, kgpu_format.hip)
 __global__ __launch_bounds__(TPB) void k_gv_scan(GraphvizArgs a) {
-    wg_excl_scan64(a.sent_len, a.n);
+    wg_excl_scan64<TPB>(a.sent_len, a.n);
 }
 
 __global__ __launch_bounds__(TPB) void k_gv_write(GraphvizArgs a) {

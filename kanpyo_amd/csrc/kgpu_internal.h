@@ -318,6 +318,23 @@ struct GraphvizArgs {
 };
 int launch_graphviz_measure(const GraphvizArgs &a, void *stream);   // prepare, lengths, scan: sent_len is final behind it
 int launch_graphviz_write(const GraphvizArgs &a, void *stream);
+// The N-best paths of a batch's kept lattices (kgpu_nbest.hip; include/kanpyo_gpu.h, "N-best paths").
+struct NbestArgs {
+    uint64_t n;                    // the sentences of the launch that kept the lattices
+    uint32_t k;                   // n_best, 1 .. KGPU_NBEST_MAX
+    Control *ctl;                  // the launch's control block: the forward kernel takes its list slabs behind the lattices' (arena_cursor, arena_overflow)
+    uint8_t *arena; uint64_t arena_bytes;   // as BatchArgs::arena / arena_bytes of that launch
+    unsigned long long *desc;      // BatchArgs::lat_desc; the forward kernel stores the arena offset of a sentence's lists -- u64[N][k] -- in word 7, and
+                                   // clears word 5 (valid) where they did not fit
+    const int16_t *conn; uint32_t conn_rows;   // DictView::conn: the ids in the slabs index it as they are
+    uint8_t *status;               // BatchArgs::status: KGPU_SENT_NO_SCRATCH where the lists did not fit
+    uint64_t *path_len;            // device scratch, n * k + 1: the records of path (s, r) at [s * k + r] (0: no such path), then (the scan, in place) their offsets; [n * k] = the total
+    uint64_t *path_offsets;        // n + 1: each sentence's paths, then (the scan, in place) their offsets; [n] = the total
+    kgpu_token *tokens; uint64_t token_cap;      // the write pass: nothing is stored when path_len[n * k] > token_cap or path_offsets[n] > path_cap
+    uint64_t *tok_offsets; int32_t *costs; uint64_t path_cap;   // tok_offsets: path_cap + 1
+};
+int launch_nbest_measure(const NbestArgs &a, void *stream);   // forward, count, scan: path_len and path_offsets are final behind it
+int launch_nbest_write(const NbestArgs &a, void *stream);
 // read_line + trim_end over a block in HBM (kgpu_split.hip; reference src/bin/kanpyo.rs:114-122).
 struct SplitTile { uint32_t x, y, z, w; };   // one tile's aggregate, then its carry (kgpu_split.hip says which word is what)
 struct SplitArgs {

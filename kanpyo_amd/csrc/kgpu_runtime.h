@@ -221,7 +221,8 @@ struct kgpu_ctx {
     DevBuf lines_len;
     HostReport lines_report;
     PinBuf lines_text, lines_off, lines_status;
-    // the DOT documents of a chunk (kgpu_graphviz_host.cpp): the lattice descriptors, the documents' lengths / offsets, the chunk's text
+    // the DOT documents of a chunk (kgpu_graphviz_host.cpp): the lattice descriptors, the documents' lengths / offsets, the chunk's text -- and, the other call
+    // that keeps lattices, the N-best paths of a chunk (kgpu_nbest_batch.cpp): the descriptors, the scans' arrays, the output block
     DevBuf gv_desc, gv_len, gv_text;
     // read_line + trim_end on the device (kgpu_split.hip): the tile aggregates, what the carry kernel publishes ([0] lines, [1] packed bytes), and
     // for kgpu_tokenize_text_lines the device copy of the raw block, its packed lines and their offsets
@@ -311,7 +312,7 @@ struct WorkerPool {
     void task_done(std::atomic<int> &counter); // a task's last statement
 };
 WorkerPool &workers();
-struct TestHooks { bool no_small_calls = false, plain_leaves = false, byte_trie = false; uint64_t chunk_bytes = 4ull << 20, chunk_sents = 16384, depth = 12, multi_chunk_sents = 0, graphviz_chunk_sents = 0, graphviz_arena_initial = 0, graphviz_arena_max = 0, arena_initial = 0; int aux_launch = -1; };
+struct TestHooks { bool no_small_calls = false, plain_leaves = false, byte_trie = false; uint64_t chunk_bytes = 4ull << 20, chunk_sents = 16384, depth = 12, multi_chunk_sents = 0, graphviz_chunk_sents = 0, graphviz_arena_initial = 0, graphviz_arena_max = 0, nbest_chunk_sents = 0, nbest_arena_initial = 0, nbest_arena_max = 0, arena_initial = 0; int aux_launch = -1; };
 TestHooks test_hooks();  // test-only environment hooks, read once per process (or per call under KGPU_TEST_HOOKS_REREAD)
 bool env_flag_now(const char *name);
 

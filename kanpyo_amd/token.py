@@ -40,3 +40,12 @@ class AlignedToken:
     source_start: int  # char position
     source_end: int  # char position
     source_surface: str
+
+
+@dataclass(frozen=True)
+class NBestPath:
+    """One of a sentence's N-best paths (include/kanpyo_gpu.h, "N-best paths"; not in the reference): its total cost and its tokens, the Token
+    objects tokenize_batch gives -- EOS last."""
+
+    cost: int
+    tokens: tuple

@@ -18,7 +18,7 @@ from . import _lib
 from ._calls import EDIT_DTYPE, SPAN_DTYPE, TOKEN8_DTYPE, TOKEN_DTYPE, Handle, batch_call, block_bytes, block_call, grown, pack_sentences, packed_input, pinned_empty, ptr, struct_dict  # noqa: F401
 from ._probes import concurrent_callers, merge_bench, merge_shards  # noqa: F401  (they lived here once)
 from .dict import Dict
-from .token import AlignedToken, Token, TokenClass
+from .token import AlignedToken, NBestPath, Token, TokenClass
 from .vocab import Vocab
 
 TEXT_UNITS = ("text[uint8]", "text_offsets")   # what the rendering calls name their out= arrays
@@ -221,6 +221,49 @@ class Tokenizer(Handle):
         text, toff, _ = self.graphviz_packed(utf8, offs, dpi, full_state)
         raw = text.tobytes()
         return [raw[int(toff[i]) : int(toff[i + 1])].decode("utf-8") for i in range(len(toff) - 1)]
+
+    # ---- N-best paths (include/kanpyo_gpu.h, "N-best paths"; not an output of the reference: `mecab -N k`) ------
+    def tokenize_nbest_packed(self, utf8: np.ndarray, offsets: np.ndarray, n_best: int, token_capacity: int | None = None, path_capacity: int | None = None):
+        """kgpu_tokenize_batch_nbest -> (tokens[TOKEN_DTYPE], path_offsets[uint64 n+1], tok_offsets[uint64 P+1], costs[int32 P], status[uint8 n]):
+        sentence i's paths are path_offsets[i]:path_offsets[i+1], best first; path p costs costs[p] and holds tokens[tok_offsets[p]:tok_offsets[p+1]].
+        The capacities, when given, are never grown: KGPU_ERR_CAPACITY surfaces as KgpuError."""
+        utf8, offsets, n, total = packed_input(utf8, offsets)
+        k = int(n_best)
+        fixed = token_capacity is not None or path_capacity is not None
+        caps = (_token_room(total, n) * min(max(k, 1), 4) if token_capacity is None else int(token_capacity), n * max(k, 0) if path_capacity is None else int(path_capacity))
+        poff, status = np.zeros(n + 1, dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint8)
+        P, T = C.c_uint64(0), C.c_uint64(0)
+        while caps is not None:
+            tokens, toff, costs = np.empty(max(caps[0], 1), dtype=TOKEN_DTYPE), np.zeros(caps[1] + 1, dtype=np.uint64), np.empty(max(caps[1], 1), dtype=np.int32)
+            status[:] = 0
+            rc = _lib.lib().kgpu_tokenize_batch_nbest(self._h, ptr(utf8), offsets.ctypes.data, n, k, tokens.ctypes.data, caps[0], poff.ctypes.data, toff.ctypes.data,
+                                                      costs.ctypes.data, caps[1], status.ctypes.data, C.byref(P), C.byref(T))
+            caps = _lib.check(rc) if fixed else grown(rc, caps, (T.value, P.value))
+        return tokens[: T.value], poff, toff[: P.value + 1], costs[: P.value], status[:n]
+
+    def tokenize_nbest(self, sentences: Sequence[str], n_best: int, normalize=None) -> List[List[NBestPath]]:
+        """Per sentence its n_best lowest-cost paths, best first (fewer where the lattice has fewer; none where EOS is unreachable): NBestPath.cost and
+        NBestPath.tokens, the Token objects tokenize_batch gives.  Path 0 holds tokenize_batch's tokens.  normalize="NFC" / "NFKC": the sentences are
+        normalised on the device first and every position refers to the NORMALISED sentence, as in tokenize_batch."""
+        utf8, offs = pack_sentences(sentences)
+        if normalize is not None:
+            utf8, offs, _ = self.normalize_packed(utf8, offs, normalize)
+        tokens, poff, toff, costs, status = self.tokenize_nbest_packed(utf8, offs, n_best)
+        out = []
+        for i in range(len(sentences)):
+            if status[i] == _lib.KGPU_SENT_INVALID_UTF8:
+                raise UnicodeDecodeError("utf-8", bytes(utf8[int(offs[i]) : int(offs[i + 1])]), 0, 1, "invalid UTF-8 sentence")
+            raw = utf8[int(offs[i]) : int(offs[i + 1])].tobytes()
+            paths = []
+            for p in range(int(poff[i]), int(poff[i + 1])):
+                row = []
+                for t in tokens[int(toff[p]) : int(toff[p + 1])]:
+                    cls = TokenClass(int(t["cls"]))
+                    pos, bl = int(t["position"]), int(t["byte_len"])
+                    row.append(Token(int(t["id"]), cls, pos, int(t["start"]), int(t["end"]), "EOS" if cls == TokenClass.Dummy else raw[pos : pos + bl].decode("utf-8")))
+                paths.append(NBestPath(int(costs[p]), tuple(row)))
+            out.append(paths)
+        return out
 
     def routing(self, reset: bool = False) -> dict:
         """kgpu_dict_get_routing: the routing counters of the handle's pooled contexts (small_calls, combined_calls, ...)."""
