@@ -988,6 +988,76 @@ int kgpu_tokenize_batch_nbest(kgpu_dict *d, const uint8_t *utf8, const uint64_t 
                               uint64_t *path_offsets /* n + 1 */, uint64_t *tok_offsets, int32_t *costs, uint64_t path_capacity,
                               uint8_t *status /* may be NULL */, uint64_t *n_paths, uint64_t *n_tokens);
 
+/* ---- lattice probabilities: the lattice read as a distribution over tokenizations, P(path) proportional to exp(-theta cost(path)) -- token marginals
+ * (what `mecab -m` / `mecab -a` give) and sampled paths (`mecab -l --theta`); NOT an output of the reference ----
+ * Take the lattice of "N-best paths": nodes numbered by start position, BOS = 0, EOS last; the predecessors of t are the nodes ending at t.char_pos, the
+ * successors of j the nodes starting at j.end_char.  Take theta, a double with 0 < theta <= KGPU_THETA_MAX = 2^64 -- the cap keeps every weight and log-sum finite: theta times a path's cost stays far below
+ * the largest double, so no infinity and no NaN arises, on which a maximum would depend on its order -- (KGPU_THETA_DEFAULT = 0.75 / 800: MeCab's default theta over IPADIC's
+ * cost factor).  The rule is INDEPENDENT OF ORDER by construction -- a maximum and an unsigned integer sum are -- and uses no library exp / log, so that
+ * the device result is the host rule byte for byte although a bucket's slots are filled in no fixed order.
+ *  Edge weight.  w(j, t) = -theta * (double)(M[j.right_id][t.left_id] + t.cost): the integer sum is exact, then one multiplication.
+ *  Forward.  alpha[BOS] = 0.  For every other t, in node order: a_j = alpha[j] + w(j, t) over the predecessors j with finite alpha[j]; m = max a_j;
+ *    S = sum_j fix(kexp(a_j - m)), an unsigned 64-bit integer sum; alpha[t] = m + klog(S * 2^-40).  fix(x) is x * 2^40 rounded to the nearest integer
+ *    (ties to even); kexp(0) is exactly 1, so S >= 2^40.  A node with no finite predecessor has alpha = -inf.
+ *  Backward.  beta[EOS] = 0.  For every other j, by descending end position, over the successors t with finite beta[t]: the same recursion with
+ *    b_t = beta[t] + w(j, t).
+ *  Results.  log_z = alpha[EOS].  A node's marginal is kexp(min(0, (alpha[t] + beta[t]) - log_z)).  best_logprob = -theta * (double)dp(EOS) - log_z, dp(EOS)
+ *    tokenize's cost.  An unreachable EOS gives log_z = best_logprob = -inf, no records and status KGPU_SENT_OK, as N-best gives no paths; so does (with its
+ *    own status) a sentence that is not UTF-8 or does not fit.
+ *  kexp, klog (kanpyo_amd/csrc/kgpu_prob_core.h, compiled for host and device).  IEEE-754 double + - x, fma only where the source spells one
+ *    (#pragma clang fp contract(off): the device would fuse a * b + c, the host would not), comparisons and integer operations; no libm function, no
+ *    division.  kexp(x) for x <= 0: exactly 0 below -32, absolute error <= 2^-46.  klog(x) for positive normal x: error <= 2^-46 * max(1, |log x|).
+ *    u64 -> double is (double)hi * 2^32 + (double)lo, one rounding.
+ *  Limits.  N < 2^24 nodes, so S cannot overflow; a larger lattice, or one whose slabs (16 N + N bytes for the marginals, 8 N + 4 (C + 2) n_samples for the
+ *    samples) do not fit the largest scratch arena, gets KGPU_SENT_NO_SCRATCH.  NO 2^30 clamp applies to the sums: every real BOS -> EOS path counts,
+ *    which differs from N-best's cut-off only at cost extremes (a path whose prefix reaches 2^30 is no N-best path; here it has its weight).
+ *  Marginals out.  KGPU_MARGINAL_BEST: the nodes tokenize's backtrace visits (the chain over the best predecessors from EOS) -- tokenize's own records, path
+ *    0 of N-best wherever that equals them -- each with its marginal, EOS last with 1.  (The chain is the 2^30-clamped Viterbi state's, the sums have no clamp: at cost extremes EOS may
+ *    have a finite alpha and no best predecessor.  The sentence then has NO KGPU_MARGINAL_BEST records, on_best is 0 everywhere, and best_logprob is
+ *    -theta * 2^30 - log_z, dp(EOS) being the clamp; log_z and KGPU_MARGINAL_ALL are what they always are.)  KGPU_MARGINAL_ALL: every node but BOS with finite alpha and beta
+ *    and marginal >= min_prob (0 <= min_prob <= 1), in node order, on_best[r] = 1 where the node is one of KGPU_MARGINAL_BEST's.  Sentence i's records are
+ *    tok_offsets[i] .. tok_offsets[i + 1]; probs and on_best are parallel to tokens.
+ *  Sampling.  Sample i of sentence s -- s the sentence's index IN THE CALL -- walks back from EOS: at node t it takes the predecessor j (finite alpha)
+ *    that maximises (alpha[j] + w(j, t)) + G, the lower j at a tie, G = -klog(-klog(u)), u = (2 h + 1) * 2^-53 with h the top 52 bits of a hash of
+ *    (seed, s, i, t, j): splitmix64's output function applied per word, hash = mix(mix(mix(mix(mix(seed) ^ s) ^ i) ^ t) ^ j).  u is exactly a double strictly
+ *    inside (0, 1).  This is the Gumbel-max trick: no normalising sum, no order among the candidates.  A sampled path's cost is the int32 sum of its edge
+ *    costs, accumulated in int64 and saturated.  The output has N-best's format; a sentence with a reachable EOS gives exactly n_samples paths (the same
+ *    path may come more than once), 1 <= n_samples <= KGPU_SAMPLES_MAX. */
+#define KGPU_MARGINAL_BEST 0u
+#define KGPU_MARGINAL_ALL 1u
+#define KGPU_SAMPLES_MAX 256
+#define KGPU_THETA_DEFAULT (0.75 / 800.0)
+#define KGPU_THETA_MAX 18446744073709551616.0 /* 2^64 */
+/* The rule on the host, in plain C++ over one lattice as kgpu_lattice_dump returns it (the dictionary's own context ids; conn as for kgpu_nbest_host): no
+ * device, no handle; the definition of the device results, byte for byte.  KGPU_ERR_CAPACITY: nothing is written but the sizes (and log_z, best_logprob).
+ * KGPU_ERR_INVALID_ARG: a theta that is not above 0 and at most KGPU_THETA_MAX (a NaN included), an unknown select, min_prob outside [0, 1], n_samples 0 or above KGPU_SAMPLES_MAX, a null
+ * pointer where one is needed, fewer than two nodes or 2^24 of them or more, and a lattice whose edges or node fields contradict each other (as
+ * kgpu_nbest_host; also nodes that are not numbered by start position, a node without characters between BOS and EOS, a best predecessor that is not in
+ * front of its node).  tok_offsets of the samples has path_capacity + 1 entries. */
+int kgpu_marginals_host(const kgpu_lattice *lattice, const int16_t *conn, uint64_t conn_rows, uint64_t conn_cols, double theta, uint32_t select,
+                        double min_prob, kgpu_token *tokens, uint64_t token_capacity, double *probs, uint8_t *on_best, double *log_z,
+                        double *best_logprob, uint64_t *n_tokens);
+int kgpu_samples_host(const kgpu_lattice *lattice, const int16_t *conn, uint64_t conn_rows, uint64_t conn_cols, double theta, uint32_t n_samples,
+                      uint64_t seed, uint64_t sentence_index, kgpu_token *tokens, uint64_t token_capacity, uint64_t *tok_offsets, int32_t *costs,
+                      uint64_t path_capacity, uint64_t *n_paths, uint64_t *n_tokens);
+/* (tests) kexp / klog over n doubles on the host; the library's test-only export kgpu_debug_prob_device runs the same two functions on a device */
+void kgpu_prob_exp_host(const double *x, uint64_t n, double *out);
+void kgpu_prob_log_host(const double *x, uint64_t n, double *out);
+/* n sentences in host memory, on the device, by kgpu_tokenize_batch_nbest's protocol (chunks of at most 256 KiB and 1024 sentences on one pooled context,
+ * the general kernel leaving every lattice in the scratch arena): a forward kernel (one workgroup per sentence, a wavefront per target node), then the
+ * backward kernel and count / scan / write (marginals), or one wavefront per (sentence, sample) and scan / write (samples).  Tools beside the throughput
+ * path.  Need no feature tables.  tok_offsets of the marginals, log_z and best_logprob: n + 1, n and n entries; the samples' arrays as N-best's, n * n_samples
+ * paths always suffice.  status may be NULL.  KGPU_ERR_CAPACITY: the sizes reported are exact; a call whose input is one chunk has written nothing but
+ * the per-sentence arrays then. */
+int kgpu_tokenize_batch_marginals(kgpu_dict *d, const uint8_t *utf8, const uint64_t *offsets, uint64_t n, double theta, uint32_t select, double min_prob,
+                                  kgpu_token *tokens, uint64_t token_capacity, double *probs, uint8_t *on_best,
+                                  uint64_t *tok_offsets /* n + 1 */, double *log_z /* n */, double *best_logprob /* n */,
+                                  uint8_t *status /* may be NULL */, uint64_t *n_tokens);
+int kgpu_tokenize_batch_samples(kgpu_dict *d, const uint8_t *utf8, const uint64_t *offsets, uint64_t n, double theta, uint32_t n_samples, uint64_t seed,
+                                kgpu_token *tokens, uint64_t token_capacity,
+                                uint64_t *path_offsets /* n + 1 */, uint64_t *tok_offsets, int32_t *costs, uint64_t path_capacity,
+                                uint8_t *status /* may be NULL */, uint64_t *n_paths, uint64_t *n_tokens);
+
 #ifdef __cplusplus
 }
 #endif

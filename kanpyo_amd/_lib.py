@@ -44,6 +44,7 @@ SYMBOLS = [
     "kgpu_pack_host", "kgpu_pack_device",
     "kgpu_decode_host", "kgpu_decode_device", "kgpu_decode_batch",
     "kgpu_nbest_host", "kgpu_tokenize_batch_nbest",
+    "kgpu_marginals_host", "kgpu_samples_host", "kgpu_prob_exp_host", "kgpu_prob_log_host", "kgpu_tokenize_batch_marginals", "kgpu_tokenize_batch_samples",
 ]
 KGPU_VOCAB_ADD_BOS, KGPU_VOCAB_ADD_EOS = 1, 2
 KGPU_COUNTS_DEFAULT_SLOTS, KGPU_COUNTS_DEFAULT_KEY_BYTES = 1 << 22, 256 << 20
@@ -54,6 +55,8 @@ KGPU_PACK_LONGEST_FIRST, KGPU_PACK_ONLY_FIRST, KGPU_PACK_ONLY_SECOND = 0, 1, 2
 KGPU_PACK_OK, KGPU_PACK_CUT, KGPU_PACK_NO_ROOM = 0, 1, 2
 KGPU_DECODE_OK, KGPU_DECODE_BAD_ID, KGPU_DECODE_MAX_SKIP = 0, 1, 8
 KGPU_NBEST_MAX = 64
+KGPU_MARGINAL_BEST, KGPU_MARGINAL_ALL, KGPU_SAMPLES_MAX, KGPU_THETA_DEFAULT = 0, 1, 256, 0.75 / 800.0
+KGPU_THETA_MAX = 2.0**64
 
 
 def normalize_form(form) -> int:
@@ -315,6 +318,14 @@ def lib():
         nbest_out = [vp, C.c_uint64, vp, vp, C.c_uint64]   # tokens, token_capacity, tok_offsets, costs, path_capacity
         L.kgpu_nbest_host.argtypes = [C.POINTER(LatticeOut), vp, C.c_uint64, C.c_uint64, C.c_uint32] + nbest_out + [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.kgpu_tokenize_batch_nbest.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, vp, vp, vp, C.c_uint64, vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        u64p, lat_in = C.POINTER(C.c_uint64), [C.POINTER(LatticeOut), vp, C.c_uint64, C.c_uint64, C.c_double]   # lattice, conn, rows, cols, theta
+        L.kgpu_marginals_host.argtypes = lat_in + [C.c_uint32, C.c_double, vp, C.c_uint64, vp, vp, C.POINTER(C.c_double), C.POINTER(C.c_double), u64p]
+        L.kgpu_samples_host.argtypes = lat_in + [C.c_uint32, C.c_uint64, C.c_uint64] + nbest_out + [u64p, u64p]
+        L.kgpu_prob_exp_host.argtypes = L.kgpu_prob_log_host.argtypes = [vp, C.c_uint64, vp]
+        L.kgpu_prob_exp_host.restype = L.kgpu_prob_log_host.restype = None
+        L.kgpu_debug_prob_device.argtypes = [C.c_int, C.c_uint32, vp, C.c_uint64, vp]
+        L.kgpu_tokenize_batch_marginals.argtypes = [vp, vp, vp, C.c_uint64, C.c_double, C.c_uint32, C.c_double, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, u64p]
+        L.kgpu_tokenize_batch_samples.argtypes = [vp, vp, vp, C.c_uint64, C.c_double, C.c_uint32, C.c_uint64, vp, C.c_uint64, vp, vp, vp, C.c_uint64, vp, u64p, u64p]
         L.kgpu_debug_wordpiece_split_ends.argtypes = [vp, vp, C.c_uint64, C.POINTER(WordpieceOpts), C.c_int32, vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, C.POINTER(C.c_uint64)]
         L.kgpu_debug_wordpiece_split.argtypes = [vp, vp, C.c_uint64, C.POINTER(WordpieceOpts), C.c_int32, vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.POINTER(C.c_uint64)]
         L.kgpu_debug_counts_order.argtypes = [vp, vp, vp, C.c_uint64] + L.kgpu_counts_read.argtypes[1:]

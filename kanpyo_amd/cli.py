@@ -10,6 +10,11 @@ run as the reference's `expect` panic does: the lines before it are printed, exi
 the lattice has fewer, none where EOS is unreachable): each path is the lines of its tokens, ending with its EOS line, exactly as `tokenize` prints
 one.  The paths are found on the device (kgpu_tokenize_batch_nbest); their lines are rendered on the host from the records -- which needs the lines
 there: `--split device` with it is an argument error.
+`--marginal [--all-morphs] [--min-prob P] [--theta T]` and `--sample N [--seed S] [--theta T]` (NOT options of the reference either: `mecab -m` / `-a`
+and `mecab -l --theta`) read the lattice as a distribution, P(path) proportional to exp(-T cost): --marginal prints `tokenize`'s lines with `\t%.6f`,
+the token's marginal probability, appended (--all-morphs: a line for every node whose marginal is at least P); --sample N prints N tokenizations drawn
+from the lattice, one after the other as --nbest prints its paths.  Computed on the device (kgpu_tokenize_batch_marginals / _samples), rendered on the
+host: not with `--split device`, not with --nbest.
 
 `python -m kanpyo_amd graphviz [INPUT] [-c DICT] [-f/--full-state] [--dpi N]`: the reference's `kanpyo graphviz` (src/bin/kanpyo.rs:31-48,
 127-148 over src/graphviz.rs:30-163): the lattice of ONE sentence as a DOT document, built and rendered on the device in one
@@ -213,11 +218,41 @@ def _nbest_lines(tok, n_best: int, form, utf8, offs):
     return np.frombuffer(b"".join(out), dtype=np.uint8), loff, status
 
 
+def _prob_lines(tok, args, form, utf8, offs):
+    """tokenize_lines_packed's result for --marginal (every line of `tokenize` -- or of every node, --all-morphs -- with its marginal appended) and for
+    --sample N (every line's N sampled paths one after the other): the numbers and paths from the device, their lines made here."""
+    from .nbest import path_lines
+    from .prob import marginal_lines
+    from .tokenizer import merge_status
+
+    nstatus = None
+    if form:
+        utf8, offs, nstatus = tok.normalize_packed(utf8, offs, form)
+    raw, o = utf8.tobytes(), offs.tolist()
+    known, unk = tok.dictfile.morph_feature_table, tok.dictfile.unk_feature_table
+    if args.marginal:
+        tokens, probs, _, toff, _, _, status = tok.tokenize_marginals_packed(utf8, offs, args.theta, args.all_morphs, args.min_prob)
+        to = toff.tolist()
+        out = [marginal_lines(raw[o[i] : o[i + 1]], tokens[to[i] : to[i + 1]], probs[to[i] : to[i + 1]], known, unk) for i in range(len(o) - 1)]
+    else:
+        tokens, poff, toff, _, status = tok.tokenize_samples_packed(utf8, offs, args.sample, args.seed, args.theta)
+        po, to = poff.tolist(), toff.tolist()
+        out = [b"".join(path_lines(raw[o[i] : o[i + 1]], tokens[to[p] : to[p + 1]], known, unk) for p in range(po[i], po[i + 1])) for i in range(len(o) - 1)]
+    if nstatus is not None:
+        merge_status(status, nstatus)
+    loff = np.zeros(len(out) + 1, dtype=np.uint64)
+    if out:
+        loff[1:] = np.cumsum([len(x) for x in out])
+    return np.frombuffer(b"".join(out), dtype=np.uint8), loff, status
+
+
 def tokenize(args, stdin, stdout) -> int:
     tok = _open(args)
     packed, text = tok.tokenize_lines_packed, tok.tokenize_text_lines
     if getattr(args, "nbest", None) is not None:
         packed, text = partial(_nbest_lines, tok, args.nbest, _form(args)), None   # (parse_args refuses --split device)
+    elif getattr(args, "marginal", False) or getattr(args, "sample", None) is not None:
+        packed, text = partial(_prob_lines, tok, args, _form(args)), None          # (likewise)
     elif _form(args):
         packed, text = partial(packed, normalize=_form(args)), partial(text, normalize=_form(args))
     return _print_lines(_results(args, stdin, packed, text), stdout,
@@ -467,6 +502,38 @@ def _nbest(text: str) -> int:
     return int(text)
 
 
+def _sample(text: str) -> int:
+    if not text.isascii() or not text.isdigit() or not 1 <= int(text) <= 256:
+        raise argparse.ArgumentTypeError(f"invalid value {text!r}: a number of samples from 1 to 256")
+    return int(text)
+
+
+def _seed(text: str) -> int:
+    if not text.isascii() or not text.isdigit() or int(text) >= 1 << 64:
+        raise argparse.ArgumentTypeError(f"invalid value {text!r}: an unsigned integer below 2^64")
+    return int(text)
+
+
+def _theta(text: str) -> float:
+    try:
+        v = float(text)
+    except ValueError:
+        v = 0.0
+    if not 0.0 < v <= 2.0**64:   # KGPU_THETA_MAX
+        raise argparse.ArgumentTypeError(f"invalid value {text!r}: a number above 0 and at most 2^64")
+    return v
+
+
+def _min_prob(text: str) -> float:
+    try:
+        v = float(text)
+    except ValueError:
+        v = -1.0
+    if not 0.0 <= v <= 1.0:
+        raise argparse.ArgumentTypeError(f"invalid value {text!r}: a probability from 0 to 1")
+    return v
+
+
 def _top(text: str) -> int:
     if not text.isascii() or not text.isdigit() or int(text) < 1:
         raise argparse.ArgumentTypeError(f"invalid value {text!r}: a count from 1")
@@ -568,12 +635,27 @@ def _text_command(sub, name: str, help: str, verb: str = None, first=(), own=(),
     return p
 
 
+def _prob_defaults(args):
+    """The documented defaults of --min-prob, --seed and --theta (None on the command line: not given, which parse_args tells apart)."""
+    from ._lib import KGPU_THETA_DEFAULT
+
+    args.min_prob = 0.0 if args.min_prob is None else args.min_prob
+    args.seed = 0 if args.seed is None else args.seed
+    args.theta = KGPU_THETA_DEFAULT if args.theta is None else args.theta
+
+
 def parse_args(argv=None):
     """The reference's command line (src/bin/kanpyo.rs:14-49).  -> the namespace; .command is "tokenize" or "graphviz" -- or "wakati", "count", "encode", "normalize" or "align", which are this package's own."""
     p = argparse.ArgumentParser(prog="kanpyo_amd", description="Japanese Morphological Analyzer (kanpyo) on AMD Instinct GPUs")
     sub = p.add_subparsers(dest="command")
     t = _text_command(sub, "tokenize", "Tokenize input text",
-                      own=[("--nbest", dict(type=_nbest, default=None, metavar="K", help="Print each line's K lowest-cost paths, best first (1..64; not in the reference: mecab -N K)"))])
+                      own=[("--nbest", dict(type=_nbest, default=None, metavar="K", help="Print each line's K lowest-cost paths, best first (1..64; not in the reference: mecab -N K)")),
+                           ("--marginal", dict(action="store_true", help="Append each token's marginal probability to its line (not in the reference: mecab -m)")),
+                           ("--all-morphs", dict(action="store_true", help="With --marginal: a line for every node of the lattice, not only the best path's (mecab -a)")),
+                           ("--min-prob", dict(type=_min_prob, default=None, metavar="P", help="With --marginal --all-morphs: only the nodes whose marginal is at least P [default: 0]")),
+                           ("--sample", dict(type=_sample, default=None, metavar="N", help="Print N tokenizations of each line drawn from the lattice (1..256; not in the reference: mecab -l)")),
+                           ("--seed", dict(type=_seed, default=None, metavar="S", help="With --sample: the seed of the draws [default: 0]")),
+                           ("--theta", dict(type=_theta, default=None, metavar="T", help="With --marginal / --sample: P(path) is proportional to exp(-T cost) [default: 0.75 / 800]"))])
     g = sub.add_parser("graphviz", help="Output lattice in Graphviz format")
     g.add_argument("input", nargs="?", default=None, help="Input text to analyze [default: one line of stdin]")
     g.add_argument("-d", "--dict", choices=["ipa"], default="ipa", help="Dictionary")
@@ -617,9 +699,25 @@ def parse_args(argv=None):
     args = p.parse_args(argv)
     if args.command == "tokenize" and args.nbest is not None and args.split == "device":
         t.error("--nbest renders its lines on the host: it does not go with --split device")
+    if args.command == "tokenize":
+        prob = args.marginal or args.sample is not None
+        if args.marginal and args.sample is not None:
+            t.error("--marginal and --sample are two outputs: one of them")
+        if prob and args.nbest is not None:
+            t.error("--marginal / --sample do not go with --nbest")
+        if prob and args.split == "device":
+            t.error("--marginal / --sample render their lines on the host: they do not go with --split device")
+        if (args.all_morphs or args.min_prob is not None) and not args.marginal:
+            t.error("--all-morphs / --min-prob go with --marginal")
+        if args.seed is not None and args.sample is None:
+            t.error("--seed goes with --sample")
+        if args.theta is not None and not prob:
+            t.error("--theta goes with --marginal or --sample")
+        _prob_defaults(args)
     if args.command is None:   # src/bin/kanpyo.rs:173: no subcommand == tokenize from stdin, default dictionary
         args = t.parse_args([])
         args.command = "tokenize"
+        _prob_defaults(args)
     return args
 
 

@@ -335,6 +335,36 @@ struct NbestArgs {
 };
 int launch_nbest_measure(const NbestArgs &a, void *stream);   // forward, count, scan: path_len and path_offsets are final behind it
 int launch_nbest_write(const NbestArgs &a, void *stream);
+// The lattice probabilities of a batch's kept lattices (kgpu_prob.hip; include/kanpyo_gpu.h, "lattice probabilities"): token marginals, or sampled paths.
+struct ProbArgs {
+    uint64_t n;                    // the sentences of the launch that kept the lattices
+    uint64_t sent_base;            // the call's index of the launch's first sentence: a sample's hash takes the sentence's index IN THE CALL
+    double theta, min_prob;
+    uint32_t select;               // KGPU_MARGINAL_BEST / KGPU_MARGINAL_ALL
+    uint32_t n_samples;            // 0: marginals; else 1 .. KGPU_SAMPLES_MAX
+    uint64_t seed;
+    Control *ctl;                  // the launch's control block: the forward kernel takes its slabs behind the lattices' (arena_cursor, arena_overflow)
+    uint8_t *arena; uint64_t arena_bytes;   // as BatchArgs::arena / arena_bytes of that launch
+    unsigned long long *desc;      // BatchArgs::lat_desc; the forward kernel stores the arena offset of a sentence's slab in word 7 and clears word 5 (valid) where
+                                   // it did not fit.  The slab: alpha f64[N], then beta f64[N] | best-path bytes u8[N] (marginals) or the sampled nodes u32[n_samples][C + 2]
+    const int16_t *conn; uint32_t conn_rows;   // DictView::conn: the ids in the slabs index it as they are
+    uint8_t *status;               // BatchArgs::status: KGPU_SENT_NO_SCRATCH where the slab did not fit
+    // marginals
+    uint64_t *sent_len;            // device scratch, n + 1: each sentence's records, then (the scan, in place) their offsets = the call's tok_offsets; [n] = the total
+    double *log_z, *best_logprob;  // n each
+    kgpu_token *tokens; uint64_t token_cap;   // the write passes: nothing is stored when the total exceeds token_cap (samples: or the paths path_cap)
+    double *probs; uint8_t *on_best;
+    // samples
+    uint64_t *path_len;            // device scratch, n * n_samples + 1: the records of sample (s, r), then (the scan, in place) their offsets
+    uint64_t *path_offsets;        // n + 1: each sentence's paths (n_samples or 0), then their offsets
+    int32_t *path_cost;            // device scratch, n * n_samples
+    uint64_t *tok_offsets; int32_t *costs; uint64_t path_cap;   // tok_offsets: path_cap + 1
+};
+int launch_prob_marginals_measure(const ProbArgs &a, void *stream);   // forward, backward, count, scan: sent_len, log_z and best_logprob are final behind it
+int launch_prob_marginals_write(const ProbArgs &a, void *stream);
+int launch_prob_samples_measure(const ProbArgs &a, void *stream);     // forward, sample, scan: path_len and path_offsets are final behind it
+int launch_prob_samples_write(const ProbArgs &a, void *stream);
+int launch_prob_eval(const double *d_x, uint64_t n, double *d_out, uint32_t which, void *stream);   // (tests) kexp / klog over an array
 // read_line + trim_end over a block in HBM (kgpu_split.hip; reference src/bin/kanpyo.rs:114-122).
 struct SplitTile { uint32_t x, y, z, w; };   // one tile's aggregate, then its carry (kgpu_split.hip says which word is what)
 struct SplitArgs {

@@ -82,6 +82,13 @@ def source_spans_host(tokens, tok_offsets, edits, edit_offsets) -> np.ndarray:
     return spans[: int(toff[-1] - toff[0])]
 
 
+def _token_of(raw: bytes, t) -> Token:
+    """One 24-byte record of the sentence `raw` as a Token."""
+    cls = TokenClass(int(t["cls"]))
+    pos, bl = int(t["position"]), int(t["byte_len"])
+    return Token(int(t["id"]), cls, pos, int(t["start"]), int(t["end"]), "EOS" if cls == TokenClass.Dummy else raw[pos : pos + bl].decode("utf-8"))
+
+
 def _token_room(total: int, n: int) -> int:
     """The token records a first call allocates for n sentences of `total` bytes."""
     return total // 2 + n + 64
@@ -263,6 +270,77 @@ class Tokenizer(Handle):
                     row.append(Token(int(t["id"]), cls, pos, int(t["start"]), int(t["end"]), "EOS" if cls == TokenClass.Dummy else raw[pos : pos + bl].decode("utf-8")))
                 paths.append(NBestPath(int(costs[p]), tuple(row)))
             out.append(paths)
+        return out
+
+    # ---- lattice probabilities (include/kanpyo_gpu.h, "lattice probabilities"; not an output of the reference: `mecab -m`, `mecab -l --theta`) ------
+    def tokenize_marginals_packed(self, utf8: np.ndarray, offsets: np.ndarray, theta: float = _lib.KGPU_THETA_DEFAULT, all_nodes: bool = False, min_prob: float = 0.0,
+                                  token_capacity: int | None = None):
+        """kgpu_tokenize_batch_marginals -> (tokens[TOKEN_DTYPE], probs[float64 T], on_best[uint8 T], tok_offsets[uint64 n+1], log_z[float64 n],
+        best_logprob[float64 n], status[uint8 n]): sentence i's records are tokens[tok_offsets[i]:tok_offsets[i+1]] -- tokenize's own, each with its
+        marginal, or with all_nodes every node whose marginal is at least min_prob, in node order, on_best telling tokenize's.  A given capacity is never
+        grown: KGPU_ERR_CAPACITY surfaces as KgpuError."""
+        utf8, offsets, n, total = packed_input(utf8, offsets)
+        sel = _lib.KGPU_MARGINAL_ALL if all_nodes else _lib.KGPU_MARGINAL_BEST
+        caps = (_token_room(total, n) * (8 if all_nodes else 1) if token_capacity is None else int(token_capacity),)
+        toff, status = np.zeros(n + 1, dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint8)
+        log_z, best_lp = np.zeros(max(n, 1), dtype=np.float64), np.zeros(max(n, 1), dtype=np.float64)
+        T = C.c_uint64(0)
+        while caps is not None:
+            tokens, probs, on_best = np.empty(max(caps[0], 1), dtype=TOKEN_DTYPE), np.empty(max(caps[0], 1), dtype=np.float64), np.empty(max(caps[0], 1), dtype=np.uint8)
+            status[:] = 0
+            rc = _lib.lib().kgpu_tokenize_batch_marginals(self._h, ptr(utf8), offsets.ctypes.data, n, float(theta), sel, float(min_prob), tokens.ctypes.data, caps[0],
+                                                          probs.ctypes.data, on_best.ctypes.data, toff.ctypes.data, log_z.ctypes.data, best_lp.ctypes.data,
+                                                          status.ctypes.data, C.byref(T))
+            caps = _lib.check(rc) if token_capacity is not None else grown(rc, caps, (T.value,))
+        return tokens[: T.value], probs[: T.value], on_best[: T.value], toff, log_z[:n], best_lp[:n], status[:n]
+
+    def tokenize_marginals(self, sentences: Sequence[str], theta: float = _lib.KGPU_THETA_DEFAULT, all_nodes: bool = False, min_prob: float = 0.0, normalize=None) -> list:
+        """Per sentence a list of (Token, marginal probability, on tokenize's path) -- tokenize_batch's tokens, or with all_nodes every node whose
+        marginal is at least min_prob, in node order.  P(path) is proportional to exp(-theta cost).  normalize: as in tokenize_nbest."""
+        utf8, offs = pack_sentences(sentences)
+        if normalize is not None:
+            utf8, offs, _ = self.normalize_packed(utf8, offs, normalize)
+        tokens, probs, on_best, toff, _, _, status = self.tokenize_marginals_packed(utf8, offs, theta, all_nodes, min_prob)
+        out = []
+        for i in range(len(sentences)):
+            if status[i] == _lib.KGPU_SENT_INVALID_UTF8:
+                raise UnicodeDecodeError("utf-8", bytes(utf8[int(offs[i]) : int(offs[i + 1])]), 0, 1, "invalid UTF-8 sentence")
+            raw = utf8[int(offs[i]) : int(offs[i + 1])].tobytes()
+            out.append([(_token_of(raw, tokens[r]), float(probs[r]), bool(on_best[r])) for r in range(int(toff[i]), int(toff[i + 1]))])
+        return out
+
+    def tokenize_samples_packed(self, utf8: np.ndarray, offsets: np.ndarray, n_samples: int, seed: int = 0, theta: float = _lib.KGPU_THETA_DEFAULT,
+                                token_capacity: int | None = None, path_capacity: int | None = None):
+        """kgpu_tokenize_batch_samples -> N-best's arrays (tokens, path_offsets[n+1], tok_offsets[P+1], costs[P], status[n]): per sentence n_samples
+        paths drawn with P(path) proportional to exp(-theta cost) (none where EOS is unreachable); the same (seed, sentence index in the call) draws the
+        same paths.  The capacities, when given, are never grown."""
+        utf8, offsets, n, total = packed_input(utf8, offsets)
+        k = int(n_samples)
+        fixed = token_capacity is not None or path_capacity is not None
+        caps = (_token_room(total, n) * min(max(k, 1), 4) if token_capacity is None else int(token_capacity), n * max(k, 0) if path_capacity is None else int(path_capacity))
+        poff, status = np.zeros(n + 1, dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint8)
+        P, T = C.c_uint64(0), C.c_uint64(0)
+        while caps is not None:
+            tokens, toff, costs = np.empty(max(caps[0], 1), dtype=TOKEN_DTYPE), np.zeros(caps[1] + 1, dtype=np.uint64), np.empty(max(caps[1], 1), dtype=np.int32)
+            status[:] = 0
+            rc = _lib.lib().kgpu_tokenize_batch_samples(self._h, ptr(utf8), offsets.ctypes.data, n, float(theta), k, int(seed) & (2**64 - 1), tokens.ctypes.data, caps[0],
+                                                        poff.ctypes.data, toff.ctypes.data, costs.ctypes.data, caps[1], status.ctypes.data, C.byref(P), C.byref(T))
+            caps = _lib.check(rc) if fixed else grown(rc, caps, (T.value, P.value))
+        return tokens[: T.value], poff, toff[: P.value + 1], costs[: P.value], status[:n]
+
+    def tokenize_samples(self, sentences: Sequence[str], n_samples: int, seed: int = 0, theta: float = _lib.KGPU_THETA_DEFAULT, normalize=None) -> List[List[NBestPath]]:
+        """Per sentence n_samples sampled tokenizations (NBestPath.cost, NBestPath.tokens; none where EOS is unreachable): segmentations for
+        subword-regularisation-style augmentation -- another seed, other paths.  normalize: as in tokenize_nbest."""
+        utf8, offs = pack_sentences(sentences)
+        if normalize is not None:
+            utf8, offs, _ = self.normalize_packed(utf8, offs, normalize)
+        tokens, poff, toff, costs, status = self.tokenize_samples_packed(utf8, offs, n_samples, seed, theta)
+        out = []
+        for i in range(len(sentences)):
+            if status[i] == _lib.KGPU_SENT_INVALID_UTF8:
+                raise UnicodeDecodeError("utf-8", bytes(utf8[int(offs[i]) : int(offs[i + 1])]), 0, 1, "invalid UTF-8 sentence")
+            raw = utf8[int(offs[i]) : int(offs[i + 1])].tobytes()
+            out.append([NBestPath(int(costs[p]), tuple(_token_of(raw, t) for t in tokens[int(toff[p]) : int(toff[p + 1])])) for p in range(int(poff[i]), int(poff[i + 1]))])
         return out
 
     def routing(self, reset: bool = False) -> dict:
