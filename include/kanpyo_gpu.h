@@ -1058,6 +1058,53 @@ int kgpu_tokenize_batch_samples(kgpu_dict *d, const uint8_t *utf8, const uint64_
                                 uint64_t *path_offsets /* n + 1 */, uint64_t *tok_offsets, int32_t *costs, uint64_t path_capacity,
                                 uint8_t *status /* may be NULL */, uint64_t *n_paths, uint64_t *n_tokens);
 
+/* ---- search mode: one-best with a length penalty on long words, so that a compound gives way to its parts where the dictionary has them (what
+ * Kuromoji, Kagome, Lindera and Sudachi offer for search indexing); extended mode also cuts unknown words into characters.  NOT an output of the
+ * reference (its README lists "Support search mode" as open) ----
+ * Take the lattice of "N-best paths": nodes in insertion order, BOS = 0, EOS last; the predecessors of t are the nodes ending at t.char_pos.
+ *  Options.  kgpu_mode_opts: mode is KGPU_MODE_NORMAL, _SEARCH or _EXTENDED; kanji_length, kanji_penalty, other_length, other_penalty default to 2,
+ *    3000, 7, 1700 (KGPU_MODE_OPTS_DEFAULT: the constants of Kuromoji and Kagome).  A non-zero reserved word or a mode above 2 is KGPU_ERR_INVALID_ARG.
+ *    KGPU_MODE_NORMAL ignores the four numbers: every penalty is 0.
+ *  Kanji.  A code point is kanji iff it is U+3005, U+3007, or in U+3400..4DBF, U+4E00..9FFF, U+F900..FAFF or U+20000..3FFFF.  This list IS the rule;
+ *    it is not claimed to equal Unicode's Han script property.
+ *  Penalty of a node t.  BOS and EOS: 0.  Known and Unknown nodes alike, with L = t.end_char - t.char_pos: if L > kanji_length and all L characters
+ *    are kanji, (L - kanji_length) * kanji_penalty; otherwise, if L > other_length, (L - other_length) * other_penalty; otherwise 0.  The product is
+ *    formed in 64 bits and capped at 1 << 29, so that a candidate dp[j] + cost + penalty + M cannot wrap an int32.
+ *  Forward.  The reference's forward as written (src/lattice.rs:116-142) with t.cost + penalty(t) where it has t.cost: dp[t] starts at 1 << 30; a BOS
+ *    predecessor counts 0; tot = min(dp[j] + t.cost + penalty(t) + M[j.right_id][t.left_id], 1 << 30) in int32; a candidate is accepted iff it is
+ *    strictly less, so among equals the lowest predecessor index wins.  Stated without an order: dp[t], pre[t] are the minimum of the key (tot, j)
+ *    over the candidates with tot < 1 << 30 (a bucket's slots are filled in no fixed order on the device).  The reference's quirk is KEPT: an unreachable
+ *    predecessor's 1 << 30 plus a negative cost is below 1 << 30 and is accepted.  With all penalties 0 the result is tokenize's on every sentence.
+ *  Backtrace.  The reference's (src/lattice.rs:144-153): from EOS along pre while there is one; the chain's head is dropped, EOS is kept.  No records
+ *    where EOS has no predecessor.
+ *  Records.  The 24-byte kgpu_token tokenize emits for each node.  In KGPU_MODE_EXTENDED a record of class Unknown with more than one character is
+ *    replaced by one record per character c, ascending: the same id and class, start = c, end = c + 1, position and byte_len that character's.
+ *    costs[i] = dp[EOS] under the penalised costs, 1 << 30 where nothing was accepted (or the sentence has status 1 or 2).
+ *  Statuses.  As in the N-best call: invalid UTF-8 gives KGPU_SENT_INVALID_UTF8 and no records; a lattice that, with its slab of 8 N + 4 (C + 1)
+ *    bytes, does not fit the largest scratch arena gives KGPU_SENT_NO_SCRATCH and no records. */
+#define KGPU_MODE_NORMAL 0u
+#define KGPU_MODE_SEARCH 1u
+#define KGPU_MODE_EXTENDED 2u
+typedef struct kgpu_mode_opts {
+    uint32_t mode;
+    uint32_t kanji_length, kanji_penalty, other_length, other_penalty;
+    uint32_t reserved[3]; /* 0 */
+} kgpu_mode_opts;
+#define KGPU_MODE_OPTS_DEFAULT(m) {(m), 2u, 3000u, 7u, 1700u, {0u, 0u, 0u}}
+/* The rule on the host, in plain C++ over one lattice as kgpu_lattice_dump returns it and the sentence's bytes: no device, no handle; the definition of
+ * the device result, byte for byte.  conn as for kgpu_nbest_host.  KGPU_ERR_CAPACITY: nothing is written but *n_tokens, the exact count.
+ * KGPU_ERR_INVALID_ARG: invalid options, a null pointer where one is needed, text that is not UTF-8, and a lattice that contradicts itself or the text
+ * (kgpu_nbest_host's checks; also a node whose byte_pos + byte_len lies beyond len, or whose end_char lies beyond the text's characters). */
+int kgpu_mode_host(const kgpu_lattice *lattice, const uint8_t *utf8, uint64_t len, const int16_t *conn, uint64_t conn_rows, uint64_t conn_cols,
+                   const kgpu_mode_opts *opts, kgpu_token *tokens, uint64_t token_capacity, uint64_t *n_tokens, int32_t *cost);
+/* n sentences in host memory, on the device, by kgpu_tokenize_batch_nbest's protocol (chunks of at most 256 KiB and 1024 sentences on one pooled context,
+ * the general kernel leaving every lattice in the scratch arena): a forward kernel (one workgroup per sentence, a wavefront per target node), then count /
+ * scan / write.  A tool beside the throughput path.  Needs no feature tables.  tok_offsets: n + 1 entries; costs (n) and status may be NULL.
+ * KGPU_ERR_CAPACITY: *n_tokens is exact; a call whose input is one chunk has written nothing but the per-sentence arrays then. */
+int kgpu_tokenize_batch_mode(kgpu_dict *d, const uint8_t *utf8, const uint64_t *offsets, uint64_t n, const kgpu_mode_opts *opts,
+                             kgpu_token *tokens, uint64_t token_capacity, uint64_t *tok_offsets /* n + 1 */, int32_t *costs /* n, may be NULL */,
+                             uint8_t *status /* may be NULL */, uint64_t *n_tokens);
+
 #ifdef __cplusplus
 }
 #endif

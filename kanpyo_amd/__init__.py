@@ -13,5 +13,6 @@ from .pack import pack_host  # noqa: F401
 from .decode import decode_host  # noqa: F401
 from .nbest import nbest_host  # noqa: F401
 from .prob import marginals_host, samples_host  # noqa: F401
+from .mode import mode_host  # noqa: F401
 
-__all__ = ["AlignedToken", "Token", "TokenClass", "Dict", "Tokenizer", "TOKEN_DTYPE", "Vocab", "normalize_host", "normalize_host_aligned", "pack_host", "decode_host", "NBestPath", "nbest_host", "marginals_host", "samples_host"]
+__all__ = ["AlignedToken", "Token", "TokenClass", "Dict", "Tokenizer", "TOKEN_DTYPE", "Vocab", "normalize_host", "normalize_host_aligned", "pack_host", "decode_host", "NBestPath", "nbest_host", "marginals_host", "samples_host", "mode_host"]

@@ -45,6 +45,7 @@ SYMBOLS = [
     "kgpu_decode_host", "kgpu_decode_device", "kgpu_decode_batch",
     "kgpu_nbest_host", "kgpu_tokenize_batch_nbest",
     "kgpu_marginals_host", "kgpu_samples_host", "kgpu_prob_exp_host", "kgpu_prob_log_host", "kgpu_tokenize_batch_marginals", "kgpu_tokenize_batch_samples",
+    "kgpu_mode_host", "kgpu_tokenize_batch_mode",
 ]
 KGPU_VOCAB_ADD_BOS, KGPU_VOCAB_ADD_EOS = 1, 2
 KGPU_COUNTS_DEFAULT_SLOTS, KGPU_COUNTS_DEFAULT_KEY_BYTES = 1 << 22, 256 << 20
@@ -57,6 +58,7 @@ KGPU_DECODE_OK, KGPU_DECODE_BAD_ID, KGPU_DECODE_MAX_SKIP = 0, 1, 8
 KGPU_NBEST_MAX = 64
 KGPU_MARGINAL_BEST, KGPU_MARGINAL_ALL, KGPU_SAMPLES_MAX, KGPU_THETA_DEFAULT = 0, 1, 256, 0.75 / 800.0
 KGPU_THETA_MAX = 2.0**64
+KGPU_MODE_NORMAL, KGPU_MODE_SEARCH, KGPU_MODE_EXTENDED = 0, 1, 2
 
 
 def normalize_form(form) -> int:
@@ -190,6 +192,11 @@ class PackOpts(C.Structure):  # kgpu_pack_opts
 class DecodeOpts(C.Structure):  # kgpu_decode_opts
     _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("sep_len", C.c_uint32), ("sep", C.c_uint8 * 8), ("n_skip", C.c_uint32),
                 ("skip_ids", C.c_int32 * KGPU_DECODE_MAX_SKIP)]
+
+
+class ModeOpts(C.Structure):  # kgpu_mode_opts
+    _fields_ = [("mode", C.c_uint32), ("kanji_length", C.c_uint32), ("kanji_penalty", C.c_uint32), ("other_length", C.c_uint32),
+                ("other_penalty", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
 class Work(C.Structure):
@@ -326,6 +333,8 @@ def lib():
         L.kgpu_debug_prob_device.argtypes = [C.c_int, C.c_uint32, vp, C.c_uint64, vp]
         L.kgpu_tokenize_batch_marginals.argtypes = [vp, vp, vp, C.c_uint64, C.c_double, C.c_uint32, C.c_double, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, u64p]
         L.kgpu_tokenize_batch_samples.argtypes = [vp, vp, vp, C.c_uint64, C.c_double, C.c_uint32, C.c_uint64, vp, C.c_uint64, vp, vp, vp, C.c_uint64, vp, u64p, u64p]
+        L.kgpu_mode_host.argtypes = [C.POINTER(LatticeOut), vp, C.c_uint64, vp, C.c_uint64, C.c_uint64, C.POINTER(ModeOpts), vp, C.c_uint64, u64p, C.POINTER(C.c_int32)]
+        L.kgpu_tokenize_batch_mode.argtypes = [vp, vp, vp, C.c_uint64, C.POINTER(ModeOpts), vp, C.c_uint64, vp, vp, vp, u64p]
         L.kgpu_debug_wordpiece_split_ends.argtypes = [vp, vp, C.c_uint64, C.POINTER(WordpieceOpts), C.c_int32, vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, C.POINTER(C.c_uint64)]
         L.kgpu_debug_wordpiece_split.argtypes = [vp, vp, C.c_uint64, C.POINTER(WordpieceOpts), C.c_int32, vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.POINTER(C.c_uint64)]
         L.kgpu_debug_counts_order.argtypes = [vp, vp, vp, C.c_uint64] + L.kgpu_counts_read.argtypes[1:]

@@ -15,6 +15,10 @@ and `mecab -l --theta`) read the lattice as a distribution, P(path) proportional
 the token's marginal probability, appended (--all-morphs: a line for every node whose marginal is at least P); --sample N prints N tokenizations drawn
 from the lattice, one after the other as --nbest prints its paths.  Computed on the device (kgpu_tokenize_batch_marginals / _samples), rendered on the
 host: not with `--split device`, not with --nbest.
+`--mode {normal,search,extended} [--mode-penalties KL,KP,OL,OP]` (NOT an option of the reference: what Kuromoji and Kagome offer for search indexing)
+prints every line's best path under a length penalty on long words, so that a compound gives way to the parts the dictionary has; extended also cuts
+unknown words into characters; normal prints what `tokenize` prints.  Decoded on the device (kgpu_tokenize_batch_mode), rendered on the host: not with
+`--split device`, --nbest, --marginal or --sample.
 
 `python -m kanpyo_amd graphviz [INPUT] [-c DICT] [-f/--full-state] [--dpi N]`: the reference's `kanpyo graphviz` (src/bin/kanpyo.rs:31-48,
 127-148 over src/graphviz.rs:30-163): the lattice of ONE sentence as a DOT document, built and rendered on the device in one
@@ -246,10 +250,32 @@ def _prob_lines(tok, args, form, utf8, offs):
     return np.frombuffer(b"".join(out), dtype=np.uint8), loff, status
 
 
+def _mode_lines(tok, mode: str, penalties, form, utf8, offs):
+    """tokenize_lines_packed's result with every line's path under a mode's penalised costs: the records from the device, their lines made here."""
+    from .nbest import path_lines
+    from .tokenizer import merge_status
+
+    nstatus = None
+    if form:
+        utf8, offs, nstatus = tok.normalize_packed(utf8, offs, form)
+    tokens, toff, _, status = tok.tokenize_mode_packed(utf8, offs, mode, penalties)
+    if nstatus is not None:
+        merge_status(status, nstatus)
+    raw, o, to = utf8.tobytes(), offs.tolist(), toff.tolist()
+    known, unk = tok.dictfile.morph_feature_table, tok.dictfile.unk_feature_table
+    out = [path_lines(raw[o[i] : o[i + 1]], tokens[to[i] : to[i + 1]], known, unk) for i in range(len(o) - 1)]
+    loff = np.zeros(len(out) + 1, dtype=np.uint64)
+    if out:
+        loff[1:] = np.cumsum([len(x) for x in out])
+    return np.frombuffer(b"".join(out), dtype=np.uint8), loff, status
+
+
 def tokenize(args, stdin, stdout) -> int:
     tok = _open(args)
     packed, text = tok.tokenize_lines_packed, tok.tokenize_text_lines
-    if getattr(args, "nbest", None) is not None:
+    if getattr(args, "mode", None) is not None:
+        packed, text = partial(_mode_lines, tok, args.mode, args.mode_penalties, _form(args)), None   # (parse_args refuses --split device)
+    elif getattr(args, "nbest", None) is not None:
         packed, text = partial(_nbest_lines, tok, args.nbest, _form(args)), None   # (parse_args refuses --split device)
     elif getattr(args, "marginal", False) or getattr(args, "sample", None) is not None:
         packed, text = partial(_prob_lines, tok, args, _form(args)), None          # (likewise)
@@ -502,6 +528,14 @@ def _nbest(text: str) -> int:
     return int(text)
 
 
+def _mode_penalties(text: str):
+    """--mode-penalties KL,KP,OL,OP: four unsigned 32-bit numbers."""
+    parts = text.split(",")
+    if len(parts) != 4 or not all(v.isascii() and v.isdigit() and int(v) < 1 << 32 for v in parts):
+        raise argparse.ArgumentTypeError(f"invalid value {text!r}: KL,KP,OL,OP -- kanji length, kanji penalty, other length, other penalty, each below 2^32")
+    return tuple(int(v) for v in parts)
+
+
 def _sample(text: str) -> int:
     if not text.isascii() or not text.isdigit() or not 1 <= int(text) <= 256:
         raise argparse.ArgumentTypeError(f"invalid value {text!r}: a number of samples from 1 to 256")
@@ -655,7 +689,9 @@ def parse_args(argv=None):
                            ("--min-prob", dict(type=_min_prob, default=None, metavar="P", help="With --marginal --all-morphs: only the nodes whose marginal is at least P [default: 0]")),
                            ("--sample", dict(type=_sample, default=None, metavar="N", help="Print N tokenizations of each line drawn from the lattice (1..256; not in the reference: mecab -l)")),
                            ("--seed", dict(type=_seed, default=None, metavar="S", help="With --sample: the seed of the draws [default: 0]")),
-                           ("--theta", dict(type=_theta, default=None, metavar="T", help="With --marginal / --sample: P(path) is proportional to exp(-T cost) [default: 0.75 / 800]"))])
+                           ("--theta", dict(type=_theta, default=None, metavar="T", help="With --marginal / --sample: P(path) is proportional to exp(-T cost) [default: 0.75 / 800]")),
+                           ("--mode", dict(choices=["normal", "search", "extended"], default=None, help="search: a length penalty on long words splits compounds into the parts the dictionary has; extended: unknown words are also cut into characters; normal: what tokenize prints (not in the reference)")),
+                           ("--mode-penalties", dict(type=_mode_penalties, default=None, metavar="KL,KP,OL,OP", help="With --mode: kanji length, kanji penalty, other length, other penalty [default: 2,3000,7,1700]"))])
     g = sub.add_parser("graphviz", help="Output lattice in Graphviz format")
     g.add_argument("input", nargs="?", default=None, help="Input text to analyze [default: one line of stdin]")
     g.add_argument("-d", "--dict", choices=["ipa"], default="ipa", help="Dictionary")
@@ -713,6 +749,12 @@ def parse_args(argv=None):
             t.error("--seed goes with --sample")
         if args.theta is not None and not prob:
             t.error("--theta goes with --marginal or --sample")
+        if args.mode is not None and (prob or args.nbest is not None):
+            t.error("--mode does not go with --nbest, --marginal or --sample")
+        if args.mode is not None and args.split == "device":
+            t.error("--mode renders its lines on the host: it does not go with --split device")
+        if args.mode_penalties is not None and args.mode is None:
+            t.error("--mode-penalties goes with --mode")
         _prob_defaults(args)
     if args.command is None:   # src/bin/kanpyo.rs:173: no subcommand == tokenize from stdin, default dictionary
         args = t.parse_args([])

@@ -78,6 +78,10 @@ TestHooks kgpu::test_hooks() {
         if (const char *e = getenv("KGPU_HOST_PROB_CHUNK_SENTS")) cur.prob_chunk_sents = strtoull(e, nullptr, 10);
         if (const char *e = getenv("KGPU_HOST_PROB_ARENA_INITIAL")) cur.prob_arena_initial = strtoull(e, nullptr, 10);
         if (const char *e = getenv("KGPU_HOST_PROB_ARENA_MAX")) cur.prob_arena_max = strtoull(e, nullptr, 10);
+        // ... and for kgpu_tokenize_batch_mode, whose chunks keep their lattices and the kanji counts and dp/pre slabs behind them
+        if (const char *e = getenv("KGPU_HOST_MODE_CHUNK_SENTS")) cur.mode_chunk_sents = strtoull(e, nullptr, 10);
+        if (const char *e = getenv("KGPU_HOST_MODE_ARENA_INITIAL")) cur.mode_arena_initial = strtoull(e, nullptr, 10);
+        if (const char *e = getenv("KGPU_HOST_MODE_ARENA_MAX")) cur.mode_arena_max = strtoull(e, nullptr, 10);
         // ... and the first size of a context's scratch arena on the tokenize path, in bytes (0: ARENA_INITIAL; clamped to [1 MiB, ARENA_INITIAL]; read when a context is
         // created): tests of the windowed and the general kernel's overflow protocol (kgpu_ctx_sync doubles the arena and reruns the batch)
         if (const char *e = getenv("KGPU_ARENA_INITIAL")) cur.arena_initial = strtoull(e, nullptr, 10);

@@ -364,6 +364,23 @@ int launch_prob_marginals_measure(const ProbArgs &a, void *stream);   // forward
 int launch_prob_marginals_write(const ProbArgs &a, void *stream);
 int launch_prob_samples_measure(const ProbArgs &a, void *stream);     // forward, sample, scan: path_len and path_offsets are final behind it
 int launch_prob_samples_write(const ProbArgs &a, void *stream);
+// The search / extended mode decode of a batch's kept lattices (kgpu_mode.hip; include/kanpyo_gpu.h, "search mode").
+struct ModeArgs {
+    uint64_t n;                    // the sentences of the launch that kept the lattices
+    kgpu_mode_opts opts;           // checked by the caller (mode_opts_valid)
+    Control *ctl;                  // the launch's control block: the forward kernel takes its slabs behind the lattices' (arena_cursor, arena_overflow)
+    uint8_t *arena; uint64_t arena_bytes;   // as BatchArgs::arena / arena_bytes of that launch
+    const uint8_t *utf8; const uint64_t *offsets;   // BatchArgs::utf8 / offsets of that launch: the characters the penalties look at
+    unsigned long long *desc;      // BatchArgs::lat_desc; the forward kernel stores the arena offset of a sentence's slab in word 7 and clears word 5 (valid) where
+                                   // it did not fit.  The slab: state u64[N] (dp << 32 | pre), then the kanji counts u32[C + 1]
+    const int16_t *conn; uint32_t conn_rows;   // DictView::conn: the ids in the slabs index it as they are
+    uint8_t *status;               // BatchArgs::status: KGPU_SENT_NO_SCRATCH where the slab did not fit
+    uint64_t *sent_len;            // device scratch, n + 1: each sentence's records, then (the scan, in place) their offsets = the call's tok_offsets; [n] = the total
+    int32_t *costs;                // n: dp of EOS under the penalised costs (1 << 30 where nothing was accepted or the sentence has no lattice)
+    kgpu_token *tokens; uint64_t token_cap;   // the write pass: nothing is stored when sent_len[n] > token_cap
+};
+int launch_mode_measure(const ModeArgs &a, void *stream);   // forward, count, scan: sent_len and costs are final behind it
+int launch_mode_write(const ModeArgs &a, void *stream);
 int launch_prob_eval(const double *d_x, uint64_t n, double *d_out, uint32_t which, void *stream);   // (tests) kexp / klog over an array
 // read_line + trim_end over a block in HBM (kgpu_split.hip; reference src/bin/kanpyo.rs:114-122).
 struct SplitTile { uint32_t x, y, z, w; };   // one tile's aggregate, then its carry (kgpu_split.hip says which word is what)

@@ -312,7 +312,7 @@ struct WorkerPool {
     void task_done(std::atomic<int> &counter); // a task's last statement
 };
 WorkerPool &workers();
-struct TestHooks { bool no_small_calls = false, plain_leaves = false, byte_trie = false; uint64_t chunk_bytes = 4ull << 20, chunk_sents = 16384, depth = 12, multi_chunk_sents = 0, graphviz_chunk_sents = 0, graphviz_arena_initial = 0, graphviz_arena_max = 0, nbest_chunk_sents = 0, nbest_arena_initial = 0, nbest_arena_max = 0, prob_chunk_sents = 0, prob_arena_initial = 0, prob_arena_max = 0, arena_initial = 0; int aux_launch = -1; };
+struct TestHooks { bool no_small_calls = false, plain_leaves = false, byte_trie = false; uint64_t chunk_bytes = 4ull << 20, chunk_sents = 16384, depth = 12, multi_chunk_sents = 0, graphviz_chunk_sents = 0, graphviz_arena_initial = 0, graphviz_arena_max = 0, nbest_chunk_sents = 0, nbest_arena_initial = 0, nbest_arena_max = 0, prob_chunk_sents = 0, prob_arena_initial = 0, prob_arena_max = 0, mode_chunk_sents = 0, mode_arena_initial = 0, mode_arena_max = 0, arena_initial = 0; int aux_launch = -1; };
 TestHooks test_hooks();  // test-only environment hooks, read once per process (or per call under KGPU_TEST_HOOKS_REREAD)
 bool env_flag_now(const char *name);
 

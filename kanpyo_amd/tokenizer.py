@@ -272,6 +272,42 @@ class Tokenizer(Handle):
             out.append(paths)
         return out
 
+    # ---- search and extended modes (include/kanpyo_gpu.h, "search mode"; not an output of the reference: what Kuromoji and Kagome offer for indexing) ------
+    def tokenize_mode_packed(self, utf8: np.ndarray, offsets: np.ndarray, mode="search", penalties=None, token_capacity: int | None = None):
+        """kgpu_tokenize_batch_mode -> (tokens[TOKEN_DTYPE], tok_offsets[uint64 n+1], costs[int32 n], status[uint8 n]): sentence i's records are
+        tokens[tok_offsets[i]:tok_offsets[i+1]], the best path under the mode's penalised costs (mode.mode_opts says what mode and penalties may be);
+        costs[i] is dp of EOS, 1 << 30 where nothing was accepted.  A given capacity is never grown: KGPU_ERR_CAPACITY surfaces as KgpuError."""
+        from .mode import mode_opts
+
+        utf8, offsets, n, total = packed_input(utf8, offsets)
+        opts = mode if isinstance(mode, _lib.ModeOpts) else mode_opts(mode, penalties)
+        caps = (_token_room(total, n) if token_capacity is None else int(token_capacity),)
+        toff, costs, status = np.zeros(n + 1, dtype=np.uint64), np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.uint8)
+        T = C.c_uint64(0)
+        while caps is not None:
+            tokens = np.empty(max(caps[0], 1), dtype=TOKEN_DTYPE)
+            status[:] = 0
+            rc = _lib.lib().kgpu_tokenize_batch_mode(self._h, ptr(utf8), offsets.ctypes.data, n, C.byref(opts), tokens.ctypes.data, caps[0], toff.ctypes.data,
+                                                     costs.ctypes.data, status.ctypes.data, C.byref(T))
+            caps = _lib.check(rc) if token_capacity is not None else grown(rc, caps, (T.value,))
+        return tokens[: T.value], toff, costs[:n], status[:n]
+
+    def tokenize_mode(self, sentences: Sequence[str], mode="search", penalties=None, normalize=None) -> List[List[Token]]:
+        """Per sentence the Token objects of its best path under the mode's penalised costs, as tokenize_batch gives them: mode="normal" gives
+        tokenize_batch's, "search" splits long words where the dictionary has their parts, "extended" also cuts unknown words into characters.
+        penalties: (kanji_length, kanji_penalty, other_length, other_penalty), default (2, 3000, 7, 1700).  normalize: as in tokenize_nbest."""
+        utf8, offs = pack_sentences(sentences)
+        if normalize is not None:
+            utf8, offs, _ = self.normalize_packed(utf8, offs, normalize)
+        tokens, toff, _, status = self.tokenize_mode_packed(utf8, offs, mode, penalties)
+        out = []
+        for i in range(len(sentences)):
+            if status[i] == _lib.KGPU_SENT_INVALID_UTF8:
+                raise UnicodeDecodeError("utf-8", bytes(utf8[int(offs[i]) : int(offs[i + 1])]), 0, 1, "invalid UTF-8 sentence")
+            raw = utf8[int(offs[i]) : int(offs[i + 1])].tobytes()
+            out.append([_token_of(raw, tokens[r]) for r in range(int(toff[i]), int(toff[i + 1]))])
+        return out
+
     # ---- lattice probabilities (include/kanpyo_gpu.h, "lattice probabilities"; not an output of the reference: `mecab -m`, `mecab -l --theta`) ------
     def tokenize_marginals_packed(self, utf8: np.ndarray, offsets: np.ndarray, theta: float = _lib.KGPU_THETA_DEFAULT, all_nodes: bool = False, min_prob: float = 0.0,
                                   token_capacity: int | None = None):
