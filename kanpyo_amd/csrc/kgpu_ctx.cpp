@@ -85,7 +85,7 @@ extern "C" void kgpu_ctx_destroy(kgpu_ctx *c) {
     c->lines_report.release(); c->split_report.release();
     c->lines_len.release(); c->lines_text.release(); c->lines_off.release(); c->lines_status.release();
     c->split_agg.release(); c->split_raw.release(); c->split_text.release(); c->split_off.release();
-    c->gv_desc.release(); c->gv_len.release(); c->gv_text.release(); c->norm_text.release();
+    c->lat_desc.release(); c->lat_words.release(); c->lat_out.release(); c->norm_text.release();
     c->norm_edits.release(); c->norm_eoff.release(); c->span_out.release();
     if (c->switch_ev) (void)hipEventDestroy(c->switch_ev);
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
@@ -668,11 +668,11 @@ extern "C" int kgpu_lattice_dump(kgpu_dict *d, const uint8_t *utf8, uint64_t len
         if (want > ARENA_MAX) { set_error("scratch arena exceeded %zu bytes", ARENA_MAX); return KGPU_ERR_INTERNAL; }
         if ((rc = c->arena.ensure(want))) return rc;
     }
-    if (!hc.dump[5]) { set_error("kgpu_lattice_dump: the sentence is not valid UTF-8"); return KGPU_ERR_INVALID_ARG; }
-    const uint64_t B = hc.dump[2], C = hc.dump[3], N = hc.dump[4], na = B + 4;
+    if (!hc.dump[LAT_VALID]) { set_error("kgpu_lattice_dump: the sentence is not valid UTF-8"); return KGPU_ERR_INVALID_ARG; }
+    const uint64_t B = hc.dump[LAT_B], C = hc.dump[LAT_C], N = hc.dump[LAT_N], na = B + 4;
     std::vector<uint32_t> cbyte(C + 1), boff(C + 2), pre(N);
     std::vector<uint32_t> nodeA(4 * N), bucket(4 * N), nodeB(2 * N);
-    const uint8_t *sa = (const uint8_t *)c->arena.p + hc.dump[0], *sn = (const uint8_t *)c->arena.p + hc.dump[1];
+    const uint8_t *sa = (const uint8_t *)c->arena.p + hc.dump[LAT_SLAB_A], *sn = (const uint8_t *)c->arena.p + hc.dump[LAT_SLAB_N];
     // slab layouts: k_tokenize_general (kgpu_kernels.hip): cbyte | uspan | nb | boff | ... (u32[na] each); nodeA | bucket | nodeB | pre
     if ((e = hipMemcpy(cbyte.data(), sa, (C + 1) * 4, hipMemcpyDeviceToHost)) != hipSuccess ||
         (e = hipMemcpy(boff.data(), sa + 3 * na * 4, (C + 2) * 4, hipMemcpyDeviceToHost)) != hipSuccess ||
@@ -697,7 +697,7 @@ extern "C" int kgpu_lattice_dump(kgpu_dict *d, const uint8_t *utf8, uint64_t len
         nd.cls = sid > 0 ? KGPU_CLASS_KNOWN : sid < 0 ? KGPU_CLASS_UNKNOWN : KGPU_CLASS_DUMMY;
         nd.char_pos = st; nd.end_char = en; nd.byte_pos = cbyte[st]; nd.byte_len = cbyte[en] - cbyte[st];
         if (sid != 0) { nd.left_id = orig(d->left_of_rank, A[0] & 0xFFFFu); nd.right_id = orig(d->right_of_rank, A[0] >> 16); nd.cost = (int16_t)(int32_t)A[1]; }
-        nd.dp = A[2] == 0xFFFFFFFFu ? (int32_t)hc.dump[6] : (int32_t)bucket[4 * A[2]];
+        nd.dp = A[2] == 0xFFFFFFFFu ? (int32_t)hc.dump[LAT_EOS_DP] : (int32_t)bucket[4 * A[2]];
         nd.pre = pre[t] == 0xFFFFFFFFu ? -1 : (int32_t)pre[t];
     }
     // edges[e] = nodes ending at e, ascending node index (the kernel fills a bucket in arrival order)

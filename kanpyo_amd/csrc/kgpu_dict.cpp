@@ -11,6 +11,7 @@
 #include <cstring>
 #include <dirent.h>
 #include <mutex>
+#include <string>
 #include <unistd.h>
 #include <vector>
 
@@ -66,23 +67,15 @@ TestHooks kgpu::test_hooks() {
         if (const char *e = getenv("KGPU_HOST_DEPTH")) cur.depth = strtoull(e, nullptr, 10);
         if (const char *e = getenv("KGPU_HOST_CHUNK_BYTES")) cur.chunk_bytes = strtoull(e, nullptr, 10);
         if (const char *e = getenv("KGPU_HOST_CHUNK_SENTS")) cur.chunk_sents = strtoull(e, nullptr, 10);
-        if (const char *e = getenv("KGPU_HOST_GRAPHVIZ_CHUNK_SENTS")) cur.graphviz_chunk_sents = strtoull(e, nullptr, 10);  // kgpu_graphviz_batch: sentences per chunk (0: the default)
-        // ... and the bytes of the scratch arena a chunk's kept lattices may use at first / at most (0: the whole arena / ARENA_MAX): tests of the overflow protocol
-        if (const char *e = getenv("KGPU_HOST_GRAPHVIZ_ARENA_INITIAL")) cur.graphviz_arena_initial = strtoull(e, nullptr, 10);
-        if (const char *e = getenv("KGPU_HOST_GRAPHVIZ_ARENA_MAX")) cur.graphviz_arena_max = strtoull(e, nullptr, 10);
-        // ... the same three for kgpu_tokenize_batch_nbest, whose chunks keep their lattices and the lists behind them
-        if (const char *e = getenv("KGPU_HOST_NBEST_CHUNK_SENTS")) cur.nbest_chunk_sents = strtoull(e, nullptr, 10);
-        if (const char *e = getenv("KGPU_HOST_NBEST_ARENA_INITIAL")) cur.nbest_arena_initial = strtoull(e, nullptr, 10);
-        if (const char *e = getenv("KGPU_HOST_NBEST_ARENA_MAX")) cur.nbest_arena_max = strtoull(e, nullptr, 10);
-        // ... and for kgpu_tokenize_batch_marginals / _samples, whose chunks keep their lattices and the probability slabs behind them
-        if (const char *e = getenv("KGPU_HOST_PROB_CHUNK_SENTS")) cur.prob_chunk_sents = strtoull(e, nullptr, 10);
-        if (const char *e = getenv("KGPU_HOST_PROB_ARENA_INITIAL")) cur.prob_arena_initial = strtoull(e, nullptr, 10);
-        if (const char *e = getenv("KGPU_HOST_PROB_ARENA_MAX")) cur.prob_arena_max = strtoull(e, nullptr, 10);
-        // ... and for kgpu_tokenize_batch_mode, whose chunks keep their lattices and the kanji counts and dp/pre slabs behind them
-        if (const char *e = getenv("KGPU_HOST_MODE_CHUNK_SENTS")) cur.mode_chunk_sents = strtoull(e, nullptr, 10);
-        if (const char *e = getenv("KGPU_HOST_MODE_ARENA_INITIAL")) cur.mode_arena_initial = strtoull(e, nullptr, 10);
-        if (const char *e = getenv("KGPU_HOST_MODE_ARENA_MAX")) cur.mode_arena_max = strtoull(e, nullptr, 10);
-        // ... and the first size of a context's scratch arena on the tokenize path, in bytes (0: ARENA_INITIAL; clamped to [1 MiB, ARENA_INITIAL]; read when a context is
+        // ... and the three hooks of each kept-lattice family (kgpu_runtime.h: LatticeHooks)
+        static const char *const LATTICE_HOOK_NAMES[LATTICE_HOOKS] = {"GRAPHVIZ", "NBEST", "PROB", "MODE"};
+        for (uint32_t h = 0; h < LATTICE_HOOKS; ++h) {
+            uint64_t *const field[3] = {&cur.lattice[h].chunk_sents, &cur.lattice[h].arena_initial, &cur.lattice[h].arena_max};
+            static const char *const FIELD_NAMES[3] = {"CHUNK_SENTS", "ARENA_INITIAL", "ARENA_MAX"};
+            for (int f = 0; f < 3; ++f)
+                if (const char *e = getenv((std::string("KGPU_HOST_") + LATTICE_HOOK_NAMES[h] + "_" + FIELD_NAMES[f]).c_str())) *field[f] = strtoull(e, nullptr, 10);
+        }
+        // ... the first size of a context's scratch arena on the tokenize path, in bytes (0: ARENA_INITIAL; clamped to [1 MiB, ARENA_INITIAL]; read when a context is
         // created): tests of the windowed and the general kernel's overflow protocol (kgpu_ctx_sync doubles the arena and reruns the batch)
         if (const char *e = getenv("KGPU_ARENA_INITIAL")) cur.arena_initial = strtoull(e, nullptr, 10);
         if (const char *e = getenv("KGPU_AUX_LAUNCH")) cur.aux_launch = atoi(e);   // scan + compaction behind a chain: 0 two launches, 1 one, 2 two with the single-wavefront scan (read when a context is created)

@@ -1,6 +1,6 @@
 // kanpyo_amd/csrc/kgpu_graphviz.hip -- the `kanpyo graphviz` output of a batch on the device (reference src/graphviz.rs:30-163 behind
-// src/bin/kanpyo.rs:127-148): one DOT document per sentence, byte for byte what Graphviz::graphviz(dpi, full_state) prints, over the
-// lattices the general kernel left in the arena (BatchArgs::keep_lattice).  kanpyo_amd/lattice.py::graphviz states every case in Python.
+// src/bin/kanpyo.rs:127-148): one DOT document per sentence, byte for byte what Graphviz::graphviz(dpi, full_state) prints, over kept lattices
+// ("The kept-lattice protocol"; kgpu_lattice_dev.h is the view of one).  kanpyo_amd/lattice.py::graphviz states every case in Python.
 //
 // Four launches on the context's stream, one workgroup per sentence at a time:
 //   k_gv_prepare  bests (the backtrace over `pre`, graphviz.rs:31-35), the nodes sorted by (end position, index) -- Lattice.edges as one array.  The
@@ -16,7 +16,7 @@
 
 #include <algorithm>
 
-#include "kgpu_device.h"
+#include "kgpu_lattice_dev.h"
 
 namespace kgpu {
 
@@ -27,36 +27,27 @@ namespace {
 constexpr uint32_t TPB = 256;
 constexpr uint32_t F_BEST = 1u, F_VISIBLE = 2u;
 
-// One sentence's kept lattice and the passes' scratch (kgpu_internal.h: lat_scratch_off).
-struct Lat {
-    bool valid;
-    uint32_t B, C, N, V;
+// A sentence's kept lattice with what lies at LAT_OWN -- its visible nodes, V -- its text, and the passes' arrays in the scratch behind slab N
+// (kgpu_internal.h: lat_scratch_bytes) and in slab A's backtrace array.
+struct GvLat : KeptLat {
+    uint32_t V;
     const uint8_t *text;
-    const uint32_t *cbyte, *boff;
-    uint32_t *reach;                 // slab A's backtrace array, dead behind the tokenize kernel: u32 per position
-    const uint4 *nodeA; const uint2 *nodeB; const uint32_t *pre;
+    uint32_t *reach;                 // KeptLat::path: u32 per position
     uint64_t *sorted, *key, *noff, *eoff;
     uint32_t *vis, *order, *flags;
 };
-__device__ __forceinline__ Lat lat_of(const GraphvizArgs &a, uint64_t s) {
-    Lat l{};
-    const unsigned long long *ds = a.desc + LAT_DESC_WORDS * s;
-    l.valid = ds[5] != 0;
+__device__ __forceinline__ GvLat gv_lat(const GraphvizArgs &a, uint64_t s) {
+    GvLat l{kept_lat(a.arena, a.desc, s), 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     if (!l.valid) return l;
-    l.B = (uint32_t)ds[2]; l.C = (uint32_t)ds[3]; l.N = (uint32_t)ds[4]; l.V = (uint32_t)ds[7];
+    l.V = (uint32_t)l.own;
     l.text = a.utf8 + a.offsets[s];
-    uint32_t *sa = (uint32_t *)(a.arena + ds[0]);
-    const uint64_t na = (uint64_t)l.B + 4;
-    l.cbyte = sa + SLAB_A_CBYTE * na; l.boff = sa + SLAB_A_BOFF * na; l.reach = sa + SLAB_A_PATH * na;
-    uint8_t *sn = a.arena + ds[1];
+    l.reach = l.path;
     const uint64_t N = l.N;
-    l.nodeA = (const uint4 *)sn; l.nodeB = (const uint2 *)(sn + N * 32); l.pre = (const uint32_t *)(sn + N * 40);
-    uint8_t *sc = sn + lat_scratch_off(N);
-    l.sorted = (uint64_t *)sc; l.key = l.sorted + (N + 1); l.noff = l.key + (N + 1); l.eoff = l.noff + (N + 1);
+    l.sorted = (uint64_t *)l.scratch; l.key = l.sorted + (N + 1); l.noff = l.key + (N + 1); l.eoff = l.noff + (N + 1);
     l.vis = (uint32_t *)(l.eoff + (N + 1)); l.order = l.vis + N; l.flags = l.order + N;
     return l;
 }
-__device__ __forceinline__ int32_t node_sid(const Lat &l, uint32_t t) { return (int32_t)l.nodeA[t].w; }   // > 0 known, < 0 unknown, 0 BOS / EOS
+__device__ __forceinline__ int32_t node_sid(const GvLat &l, uint32_t t) { return (int32_t)l.nodeA[t].w; }   // > 0 known, < 0 unknown, 0 BOS / EOS
 
 // Ascending sort of arr[0 .. n) by the whole workgroup: the bitonic network whose comparators all put the smaller element at the lower index (a merge
 // starts with the mirrored step), so elements past n are +infinity that never move: a comparator that reaches past n is skipped.
@@ -123,7 +114,7 @@ __device__ void put_header(S &o, uint64_t dpi) {   // graphviz.rs:36-40
 
 // The line of visible node `vid` (graphviz.rs:55-119).
 template <class S>
-__device__ void put_node(S &o, const GraphvizArgs &a, const Lat &l, uint32_t vid) {
+__device__ void put_node(S &o, const GraphvizArgs &a, const GvLat &l, uint32_t vid) {
     const uint32_t t = l.order[vid];
     const int32_t sid = node_sid(l, t);
     put_u64(o, vid);
@@ -151,7 +142,7 @@ __device__ void put_node(S &o, const GraphvizArgs &a, const Lat &l, uint32_t vid
 
 // The edge lines into the k-th node by (end position, index) (graphviz.rs:120-161): from every visible node of edges[its start], ascending.
 template <class S>
-__device__ void put_edges(S &o, const GraphvizArgs &a, const Lat &l, uint32_t k) {
+__device__ void put_edges(S &o, const GraphvizArgs &a, const GvLat &l, uint32_t k) {
     if (l.C == 0) return;   // "": BOS and EOS compare equal, the id map holds one of them and from_id == id skips the pair (graphviz.rs:120-124,138-140)
     const uint32_t t = (uint32_t)l.sorted[k];
     const uint32_t nid = l.vis[t];
@@ -179,7 +170,7 @@ __global__ __launch_bounds__(TPB) void k_gv_prepare(GraphvizArgs a) {
     __shared__ uint32_t nvis_s;
     const uint32_t tid = threadIdx.x;
     for (uint64_t s = blockIdx.x; s < a.n; s += gridDim.x) {
-        const Lat l = lat_of(a, s);
+        const GvLat l = gv_lat(a, s);
         if (!l.valid) continue;   // (workgroup-uniform)
         const uint32_t N = l.N, C = l.C;
         __syncthreads();
@@ -240,7 +231,7 @@ __global__ __launch_bounds__(TPB) void k_gv_prepare(GraphvizArgs a) {
                 l.vis[t] = lo; l.order[lo] = t;
             }
         }
-        if (tid == 0) a.desc[LAT_DESC_WORDS * s + 7] = V;
+        if (tid == 0) a.desc[LAT_DESC_WORDS * s + LAT_OWN] = V;
         __syncthreads();
     }
 }
@@ -248,7 +239,7 @@ __global__ __launch_bounds__(TPB) void k_gv_prepare(GraphvizArgs a) {
 __global__ __launch_bounds__(TPB) void k_gv_len(GraphvizArgs a) {
     const uint32_t tid = threadIdx.x;
     for (uint64_t s = blockIdx.x; s < a.n; s += gridDim.x) {
-        const Lat l = lat_of(a, s);
+        const GvLat l = gv_lat(a, s);
         if (!l.valid) { if (tid == 0) a.sent_len[s] = 0; continue; }
         for (uint32_t r = tid; r < l.V; r += TPB) { Count c; put_node(c, a, l, r); l.noff[r] = c.n; }
         for (uint32_t k = tid; k < l.N; k += TPB) { Count c; put_edges(c, a, l, k); l.eoff[k] = c.n; }
@@ -266,7 +257,7 @@ __global__ __launch_bounds__(TPB) void k_gv_write(GraphvizArgs a) {
     if (a.sent_len[a.n] > a.text_cap) return;   // the host reports KGPU_ERR_CAPACITY with the size needed
     const uint32_t tid = threadIdx.x;
     for (uint64_t s = blockIdx.x; s < a.n; s += gridDim.x) {
-        const Lat l = lat_of(a, s);
+        const GvLat l = gv_lat(a, s);
         if (!l.valid) continue;
         uint8_t *doc = a.text + a.sent_len[s];
         Count h; put_header(h, a.dpi);

@@ -96,7 +96,7 @@ struct Control {
     unsigned int small_abort;         // ... a wavefront gave up waiting at the rendezvous: the host redoes the call on the general path
     unsigned int win_ticket;          // the windowed kernel's ordinary form: next entry of its work list (its workgroups claim sentences one by one)
     unsigned int pad3;
-    unsigned long long dump[8];       // kgpu_lattice_dump: arena offsets of the sentence's two slabs, B, C, N, 1 = valid, dp of EOS
+    unsigned long long dump[8];       // kgpu_lattice_dump: the sentence's lattice descriptor (the LAT_* words below)
 };
 
 struct BatchArgs {
@@ -125,12 +125,18 @@ struct BatchArgs {
     uint8_t *status8;                // optional (host path): the compaction kernel mirrors status[] there (mapped host memory)
     uint64_t *toff8;                 // optional (host path): ... and tok_offsets[] (n + 1), so that it reads its offsets from HBM, not back over PCIe
     // general kernel, whole batches (kgpu_graphviz_batch): every sentence's lattice stays in the arena behind the launch -- a fresh slab pair per sentence,
-    // slab N followed by the render passes' per-node scratch (lat_scratch_*) -- and sentence s's descriptor goes to lat_desc[LAT_DESC_WORDS * s ..]:
-    // arena offsets of slab A and slab N, B, C, N, 1 = valid, dp of EOS, (the render's) visible nodes.  The table is zeroed by the host.  0 everywhere else.
+    // slab N followed by the render passes' per-node scratch (lat_scratch_*) -- and sentence s's descriptor goes to lat_desc[LAT_DESC_WORDS * s ..]
+    // (the LAT_* words below).  The table is zeroed by the host.  0 everywhere else.
     uint32_t keep_lattice;
     unsigned long long *lat_desc;
 };                                   // (added to by its owner, summed on the host: hot atomics on a few words would distort the run)
-constexpr uint32_t LAT_DESC_WORDS = 8;
+// The words of a kept lattice's descriptor, and of Control::dump (kgpu_lattice_dump's single sentence): k_tokenize_general writes words 0 .. 6.  LAT_OWN is the
+// consumer's own word (kgpu_lattice_dev.h): the visible nodes for graphviz; the arena offset of the slab the forward kernel took for N-best, the
+// probabilities and the modes.
+enum : uint32_t { LAT_SLAB_A = 0, LAT_SLAB_N = 1,   // arena offsets of the sentence's two slabs
+                  LAT_B = 2, LAT_C = 3, LAT_N = 4,  // its bytes, characters and nodes
+                  LAT_VALID = 5,                    // 1: the lattice is there (0: invalid UTF-8 or no scratch -- the status says which; a consumer whose own slab did not fit clears it)
+                  LAT_EOS_DP = 6, LAT_OWN = 7, LAT_DESC_WORDS = 8 };
 // The slabs of k_tokenize_general (kgpu_kernels.hip), as kgpu_lattice_dump and the graphviz passes read them.  Slab A: u32[B + 4] arrays, in this order
 // (the kernel has more behind them); slab N: nodeA uint4[N] | bucket uint4[N] | nodeB uint2[N] | pre u32[N].
 enum : uint32_t { SLAB_A_CBYTE = 0, SLAB_A_USPAN = 1, SLAB_A_NB = 2, SLAB_A_BOFF = 3, SLAB_A_BFILL = 4, SLAB_A_PATH = 5 };
@@ -306,7 +312,7 @@ struct GraphvizArgs {
     const uint64_t *offsets;       // n + 1
     uint64_t n;
     uint8_t *arena;                // the arena the descriptors' offsets are relative to
-    unsigned long long *desc;      // BatchArgs::lat_desc; the prepare pass stores a sentence's visible node count in word 7
+    unsigned long long *desc;      // BatchArgs::lat_desc; the prepare pass stores a sentence's visible node count in LAT_OWN
     const int16_t *conn; uint32_t conn_rows;   // DictView::conn: the ids in the slabs index it as they are
     const uint8_t *label;          // the label pool (kgpu_features.cpp): row r is label[label_off[r] .. label_off[r + 1]), rows as LinesArgs::feat (feature_row)
     const uint32_t *label_off;
@@ -324,8 +330,8 @@ struct NbestArgs {
     uint32_t k;                   // n_best, 1 .. KGPU_NBEST_MAX
     Control *ctl;                  // the launch's control block: the forward kernel takes its list slabs behind the lattices' (arena_cursor, arena_overflow)
     uint8_t *arena; uint64_t arena_bytes;   // as BatchArgs::arena / arena_bytes of that launch
-    unsigned long long *desc;      // BatchArgs::lat_desc; the forward kernel stores the arena offset of a sentence's lists -- u64[N][k] -- in word 7, and
-                                   // clears word 5 (valid) where they did not fit
+    unsigned long long *desc;      // BatchArgs::lat_desc; the forward kernel stores the arena offset of a sentence's lists -- u64[N][k] -- in LAT_OWN, and
+                                   // clears LAT_VALID where they did not fit
     const int16_t *conn; uint32_t conn_rows;   // DictView::conn: the ids in the slabs index it as they are
     uint8_t *status;               // BatchArgs::status: KGPU_SENT_NO_SCRATCH where the lists did not fit
     uint64_t *path_len;            // device scratch, n * k + 1: the records of path (s, r) at [s * k + r] (0: no such path), then (the scan, in place) their offsets; [n * k] = the total
@@ -345,7 +351,7 @@ struct ProbArgs {
     uint64_t seed;
     Control *ctl;                  // the launch's control block: the forward kernel takes its slabs behind the lattices' (arena_cursor, arena_overflow)
     uint8_t *arena; uint64_t arena_bytes;   // as BatchArgs::arena / arena_bytes of that launch
-    unsigned long long *desc;      // BatchArgs::lat_desc; the forward kernel stores the arena offset of a sentence's slab in word 7 and clears word 5 (valid) where
+    unsigned long long *desc;      // BatchArgs::lat_desc; the forward kernel stores the arena offset of a sentence's slab in LAT_OWN and clears LAT_VALID where
                                    // it did not fit.  The slab: alpha f64[N], then beta f64[N] | best-path bytes u8[N] (marginals) or the sampled nodes u32[n_samples][C + 2]
     const int16_t *conn; uint32_t conn_rows;   // DictView::conn: the ids in the slabs index it as they are
     uint8_t *status;               // BatchArgs::status: KGPU_SENT_NO_SCRATCH where the slab did not fit
@@ -371,7 +377,7 @@ struct ModeArgs {
     Control *ctl;                  // the launch's control block: the forward kernel takes its slabs behind the lattices' (arena_cursor, arena_overflow)
     uint8_t *arena; uint64_t arena_bytes;   // as BatchArgs::arena / arena_bytes of that launch
     const uint8_t *utf8; const uint64_t *offsets;   // BatchArgs::utf8 / offsets of that launch: the characters the penalties look at
-    unsigned long long *desc;      // BatchArgs::lat_desc; the forward kernel stores the arena offset of a sentence's slab in word 7 and clears word 5 (valid) where
+    unsigned long long *desc;      // BatchArgs::lat_desc; the forward kernel stores the arena offset of a sentence's slab in LAT_OWN and clears LAT_VALID where
                                    // it did not fit.  The slab: state u64[N] (dp << 32 | pre), then the kanji counts u32[C + 1]
     const int16_t *conn; uint32_t conn_rows;   // DictView::conn: the ids in the slabs index it as they are
     uint8_t *status;               // BatchArgs::status: KGPU_SENT_NO_SCRATCH where the slab did not fit

@@ -58,7 +58,7 @@ __global__ __launch_bounds__(64) void k_tokenize_general(DictView d, BatchArgs a
         // ---- slab A: per-char arrays (C <= B) --------------------------------
         const uint64_t na = (uint64_t)B + 4;
         // (keep_lattice: the sentence's own slabs, left behind for the graphviz passes; the descriptor table is zero where a sentence leaves early)
-        unsigned long long *const eos_dp = a.keep_lattice ? a.lat_desc + LAT_DESC_WORDS * s + 6 : a.dump_lattice ? &a.ctl->dump[6] : nullptr;
+        unsigned long long *const eos_dp = a.keep_lattice ? a.lat_desc + LAT_DESC_WORDS * s + LAT_EOS_DP : a.dump_lattice ? &a.ctl->dump[LAT_EOS_DP] : nullptr;
         if (!(a.keep_lattice ? slab_fresh(sa, na * (28 + 5 * GMAXM) + 64, a, lane) : slab_ensure(sa, na * (28 + 5 * GMAXM) + 64, a, lane))) {
             if (lane == 0) { a.status[s] = KGPU_SENT_NO_SCRATCH; a.tok_count[s] = 0; }
             continue;
@@ -349,13 +349,13 @@ __global__ __launch_bounds__(64) void k_tokenize_general(DictView d, BatchArgs a
         }
         if (lane == 0) { a.status[s] = KGPU_SENT_OK; a.tok_count[s] = K; }
         if (a.dump_lattice && lane == 0) {  // kgpu_lattice_dump: the host reads the lattice straight out of the two slabs
-            a.ctl->dump[0] = (unsigned long long)(sa.ptr - a.arena); a.ctl->dump[1] = (unsigned long long)(sn.ptr - a.arena);
-            a.ctl->dump[2] = B; a.ctl->dump[3] = C; a.ctl->dump[4] = N; a.ctl->dump[5] = 1;
+            a.ctl->dump[LAT_SLAB_A] = (unsigned long long)(sa.ptr - a.arena); a.ctl->dump[LAT_SLAB_N] = (unsigned long long)(sn.ptr - a.arena);
+            a.ctl->dump[LAT_B] = B; a.ctl->dump[LAT_C] = C; a.ctl->dump[LAT_N] = N; a.ctl->dump[LAT_VALID] = 1;
         }
         if (a.keep_lattice && lane == 0) {
             unsigned long long *ds = a.lat_desc + LAT_DESC_WORDS * s;
-            ds[0] = (unsigned long long)(sa.ptr - a.arena); ds[1] = (unsigned long long)(sn.ptr - a.arena);
-            ds[2] = B; ds[3] = C; ds[4] = N; ds[5] = 1;
+            ds[LAT_SLAB_A] = (unsigned long long)(sa.ptr - a.arena); ds[LAT_SLAB_N] = (unsigned long long)(sn.ptr - a.arena);
+            ds[LAT_B] = B; ds[LAT_C] = C; ds[LAT_N] = N; ds[LAT_VALID] = 1;
         }
         if (a.count_work) {
             wT = wave_sum(wT);

@@ -1,6 +1,6 @@
 // kanpyo_amd/csrc/kgpu_mode.hip -- the search / extended mode decode of a batch on the device (include/kanpyo_gpu.h, "search mode"; not an output of the
-// reference), over the lattices the general kernel left in the arena (BatchArgs::keep_lattice).  kgpu_mode_host.cpp states the rule on the host; both run
-// the statements of kgpu_mode_core.h.
+// reference), over kept lattices ("The kept-lattice protocol"; kgpu_lattice_dev.h is the view of one).  kgpu_mode_host.cpp states the rule on the
+// host; both run the statements of kgpu_mode_core.h.
 //
 // Four launches on the context's stream:
 //   k_mode_forward  the hot path, one workgroup of FWD_WAVES wavefronts per sentence.  First the workgroup decodes the sentence's characters once (slab A's
@@ -13,8 +13,7 @@
 //                   TARGET; the lanes run over the bucket slots of the target's predecessors, 64 per round, each loading its predecessor's dp and ITS
 //                   connection cost straight from the matrix (the layout and the read pattern of k_nbest_forward); one wave_min_u64 of the keys (tot, j)
 //                   where that kernel sorts.  A key holds the predecessor's node index, so the result does not depend on the order a bucket's slots were
-//                   filled in.  The state (dp << 32 | pre) is u64[N], in ONE slab with the counts, which the kernel takes itself (slab_fresh: the arena
-//                   cursor carries on behind the lattice launch).
+//                   filled in.  The state (dp << 32 | pre) is u64[N], in ONE slab with the counts, which the kernel takes itself (lat_take_slab).
 //   k_mode_count    per sentence the chain's records (extended mode: an Unknown node counts its characters) and dp of EOS
 //   k_mode_scan     one workgroup: the counts scanned in place; [n] = the batch's records
 //   k_mode_write    the records, one wavefront per sentence: nothing when the total exceeds the capacity.  The chain is met from its end; the characters
@@ -23,7 +22,7 @@
 
 #include <algorithm>
 
-#include "kgpu_device.h"
+#include "kgpu_lattice_dev.h"
 #include "kgpu_mode_core.h"
 
 namespace kgpu {
@@ -35,31 +34,18 @@ namespace {
 constexpr uint32_t TPB = 256;
 constexpr uint32_t FWD_WAVES = 4;   // wavefronts of a forward workgroup: one sentence's targets of one start position are dealt among them
 
-// One sentence's kept lattice (kgpu_internal.h: the slabs of k_tokenize_general) as the passes behind the forward kernel read it, and its state.
-struct Lat {
-    bool valid;
-    uint32_t N;
-    const uint32_t *cbyte;
-    const uint4 *nodeA; const uint2 *nodeB;
-    const uint64_t *state;
-};
-__device__ __forceinline__ Lat lat_of(const ModeArgs &a, uint64_t s) {
-    Lat l{};
-    const unsigned long long *ds = a.desc + LAT_DESC_WORDS * s;
-    l.valid = ds[5] != 0;
-    if (!l.valid) return l;
-    l.N = (uint32_t)ds[4];
-    l.cbyte = (const uint32_t *)(a.arena + ds[0]) + SLAB_A_CBYTE * (ds[2] + 4);
-    const uint8_t *sn = a.arena + ds[1];
-    l.nodeA = (const uint4 *)sn; l.nodeB = (const uint2 *)(sn + (uint64_t)l.N * 32);
-    l.state = (const uint64_t *)(a.arena + ds[7]);
+// A sentence's kept lattice with what lies at LAT_OWN: state u64[N] (dp << 32 | pre), then the kanji counts u32[C + 1] (the passes behind the forward
+// kernel read the state alone).
+struct ModeLat : KeptLat { const uint64_t *state; };
+__device__ __forceinline__ ModeLat mode_lat(const ModeArgs &a, uint64_t s) {
+    ModeLat l{kept_lat(a.arena, a.desc, s), nullptr};
+    if (l.valid) l.state = (const uint64_t *)(a.arena + l.own);
     return l;
 }
-__device__ __forceinline__ uint32_t class_of(int32_t sid) { return sid > 0 ? KGPU_CLASS_KNOWN : sid < 0 ? KGPU_CLASS_UNKNOWN : KGPU_CLASS_DUMMY; }
 
 // The chain from EOS along pre: visit(node) for every node on it but its head, EOS first -> the nodes visited.  Bounded by N: a chain's nodes descend.
 template <class F>
-__device__ __forceinline__ uint32_t walk_chain(const Lat &l, F &&visit) {
+__device__ __forceinline__ uint32_t walk_chain(const ModeLat &l, F &&visit) {
     uint32_t node = l.N - 1, len = 0;
     for (uint32_t pre; (pre = mode_state_pre(l.state[node])) != MODE_NO_PRE && pre < node && len < l.N; node = pre, ++len) visit(node);
     return len;
@@ -68,40 +54,25 @@ __device__ __forceinline__ uint32_t walk_chain(const Lat &l, F &&visit) {
 }  // namespace
 
 __global__ __launch_bounds__(64 * FWD_WAVES) void k_mode_forward(ModeArgs a) {
-    __shared__ unsigned long long slab_off;   // the arena offset of the sentence's slab (~0: it did not fit), from wavefront 0 to the others
+    __shared__ unsigned long long slab_off;   // lat_take_slab's word
     __shared__ uint32_t wave_kanji[FWD_WAVES];
     const uint32_t lane = threadIdx.x & 63u, wave = bcast32(threadIdx.x >> 6);
     const kgpu_mode_opts opts = a.opts;
     const bool counted = opts.mode != KGPU_MODE_NORMAL;   // (NORMAL: every penalty is 0 and nothing reads the counts)
-    BatchArgs arena{};   // (what slab_fresh reads)
-    arena.ctl = a.ctl; arena.arena = a.arena; arena.arena_bytes = a.arena_bytes;
-    // (every branch around a barrier below is workgroup-uniform: it tests the sentence's descriptor, which only this workgroup writes, slab_off or the options)
+    const BatchArgs arena = lat_arena_args(a.ctl, a.arena, a.arena_bytes);
+    // (every branch around a barrier below is workgroup-uniform: it tests what lat_take_slab gave, or the options)
     for (uint64_t s = blockIdx.x; s < a.n; s += gridDim.x) {
-        unsigned long long *ds = a.desc + LAT_DESC_WORDS * s;
-        if (bcast32((uint32_t)ds[5]) == 0) continue;   // invalid UTF-8, or the lattice itself did not fit: the status says which
-        const uint64_t N = bcast64(ds[4]);
-        const uint32_t C = bcast32((uint32_t)ds[3]);
-        if (wave == 0) {
-            Slab sl{nullptr, 0};
-            const bool ok = N < MODE_MAX_NODES && slab_fresh(sl, 8ull * N + 4ull * ((uint64_t)C + 1), arena, lane);
-            if (lane == 0) slab_off = ok ? (unsigned long long)(sl.ptr - a.arena) : ~0ull;
-        }
-        __syncthreads();
-        const uint64_t off = bcast64(slab_off);
-        __syncthreads();   // (read by all before the next sentence's is stored)
-        if (off == ~0ull) {
-            if (threadIdx.x == 0) { a.status[s] = KGPU_SENT_NO_SCRATCH; ds[5] = 0; }
-            continue;
-        }
-        if (threadIdx.x == 0) ds[7] = off;
+        const KeptLat l = kept_lat<true>(a.arena, a.desc, s);
+        if (!l.valid) continue;   // invalid UTF-8, or the lattice itself did not fit: the status says which
+        const uint64_t N = l.N;
+        const uint32_t C = l.C;
+        const uint64_t off = lat_take_slab(a.desc + LAT_DESC_WORDS * s, 8ull * N + 4ull * ((uint64_t)C + 1), N, MODE_MAX_NODES, &slab_off, arena, a.status + s);
+        if (off == LAT_NO_SLAB) continue;
         uint64_t *state = (uint64_t *)(a.arena + off);
         uint32_t *kanji = (uint32_t *)(state + N);   // [p]: the kanji among the characters in front of position p
-        const uint32_t *sa = (const uint32_t *)(a.arena + ds[0]);
-        const uint64_t na = bcast64(ds[2]) + 4;
-        const uint32_t *cbyte = sa + SLAB_A_CBYTE * na, *nb = sa + SLAB_A_NB * na, *boff = sa + SLAB_A_BOFF * na;
-        const uint8_t *sn = a.arena + ds[1];
-        const uint4 *nodeA = (const uint4 *)sn, *bucket = (const uint4 *)(sn + N * 16);
-        const uint2 *nodeB = (const uint2 *)(sn + N * 32);
+        const uint32_t *cbyte = l.cbyte, *nb = l.nb, *boff = l.boff;
+        const uint4 *nodeA = l.nodeA, *bucket = l.bucket;
+        const uint2 *nodeB = l.nodeB;
         if (counted) {
             const uint8_t *text = a.utf8 + bcast64(a.offsets[s]);
             uint32_t carry = 0;
@@ -149,7 +120,7 @@ __global__ __launch_bounds__(64 * FWD_WAVES) void k_mode_forward(ModeArgs a) {
 
 __global__ __launch_bounds__(TPB) void k_mode_count(ModeArgs a) {
     for (uint64_t s = (uint64_t)blockIdx.x * TPB + threadIdx.x; s < a.n; s += (uint64_t)gridDim.x * TPB) {
-        const Lat l = lat_of(a, s);
+        const ModeLat l = mode_lat(a, s);
         uint64_t records = 0;
         if (l.valid) walk_chain(l, [&](uint32_t t) { const uint2 se = l.nodeB[t]; records += mode_record_count(a.opts.mode, class_of((int32_t)l.nodeA[t].w), se.x, se.y); });
         a.sent_len[s] = records;
@@ -164,7 +135,7 @@ __global__ __launch_bounds__(TPB) void k_mode_write(ModeArgs a) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t waves = (uint64_t)gridDim.x * (TPB / 64);
     for (uint64_t s = (uint64_t)blockIdx.x * (TPB / 64) + (threadIdx.x >> 6); s < a.n; s += waves) {
-        const Lat l = lat_of(a, s);
+        const ModeLat l = mode_lat(a, s);
         if (!l.valid) continue;
         uint64_t at = a.sent_len[s + 1];   // the chain is met from its end; every lane walks it, the stores are dealt among the lanes
         const uint64_t lo = a.sent_len[s];
@@ -175,8 +146,7 @@ __global__ __launch_bounds__(TPB) void k_mode_write(ModeArgs a) {
             if (at - lo < cnt) { at = lo; return; }   // (cannot be: k_mode_count walked the same chain)
             at -= cnt;
             if (cnt == 1) {
-                const uint32_t bs = l.cbyte[se.x];
-                if (lane == 0) a.tokens[at] = nbest_record(cls, sid < 0 ? -sid : sid, bs, se.x, se.y, l.cbyte[se.y] - bs);
+                if (lane == 0) a.tokens[at] = lat_record(l, t);
                 return;
             }
             for (uint32_t c = se.x + lane; c < se.y; c += 64) a.tokens[at + (c - se.x)] = mode_char_record(-sid, c, l.cbyte[c], l.cbyte[c + 1]);

@@ -1,6 +1,6 @@
 // kanpyo_amd/csrc/kgpu_nbest.hip -- the N-best paths of a batch on the device (include/kanpyo_gpu.h, "N-best paths"; not an output of the reference:
-// what `mecab -N k` prints), over the lattices the general kernel left in the arena (BatchArgs::keep_lattice).  kgpu_nbest_host.cpp states the rule on the
-// host; both run the statements of kgpu_nbest_core.h.
+// what `mecab -N k` prints), over kept lattices ("The kept-lattice protocol"; kgpu_lattice_dev.h is the view of one).  kgpu_nbest_host.cpp states
+// the rule on the host; both run the statements of kgpu_nbest_core.h.
 //
 // Four launches on the context's stream:
 //   k_nbest_forward  the hot path, one workgroup of FWD_WAVES wavefronts per sentence: every node's ranked list of k entries, position after position (nodes
@@ -11,7 +11,7 @@
 //                    in registers as 64-bit keys -- a bitonic network over the lanes, no LDS -- and merged with the running sorted top 64 of the rounds
 //                    before: the elementwise minimum of A[i] and B[63 - i], then the six merge steps.  Lanes 0 .. k - 1 store the list.  A key holds the
 //                    predecessor's node index and rank, so the result does not depend on the order a bucket's slots were filled in.
-//                    The lists are u64[N][k] in a slab the kernel takes itself (slab_fresh: the arena cursor carries on behind the lattice launch).
+//                    The lists are u64[N][k] in a slab the kernel takes itself (lat_take_slab).
 //   k_nbest_count    per (sentence, rank) the chain's length, per sentence its paths
 //   k_nbest_scan     one workgroup: both arrays scanned in place; [n k] = the batch's records, [n] = its paths
 //   k_nbest_write    the offsets, the costs and the records: nothing when the totals exceed the capacities
@@ -19,8 +19,7 @@
 
 #include <algorithm>
 
-#include "kgpu_device.h"
-#include "kgpu_nbest_core.h"
+#include "kgpu_lattice_dev.h"
 
 namespace kgpu {
 
@@ -31,24 +30,11 @@ namespace {
 constexpr uint32_t TPB = 256;
 constexpr uint32_t FWD_WAVES = 4;   // wavefronts of a forward workgroup: one sentence's targets of one start position are dealt among them
 
-// One sentence's kept lattice (kgpu_internal.h: the slabs of k_tokenize_general) as the passes behind the forward kernel read it, and its lists.
-struct Lat {
-    bool valid;
-    uint32_t N;
-    const uint32_t *cbyte;
-    const uint4 *nodeA; const uint2 *nodeB;
-    uint64_t *lists;
-};
-__device__ __forceinline__ Lat lat_of(const NbestArgs &a, uint64_t s) {
-    Lat l{};
-    const unsigned long long *ds = a.desc + LAT_DESC_WORDS * s;
-    l.valid = ds[5] != 0;
-    if (!l.valid) return l;
-    l.N = (uint32_t)ds[4];
-    l.cbyte = (const uint32_t *)(a.arena + ds[0]) + SLAB_A_CBYTE * (ds[2] + 4);
-    const uint8_t *sn = a.arena + ds[1];
-    l.nodeA = (const uint4 *)sn; l.nodeB = (const uint2 *)(sn + (uint64_t)l.N * 32);
-    l.lists = (uint64_t *)(a.arena + ds[7]);
+// A sentence's kept lattice with what lies at LAT_OWN: its lists, u64[N][k] (the passes behind the forward kernel).
+struct ListLat : KeptLat { uint64_t *lists; };
+__device__ __forceinline__ ListLat list_lat(const NbestArgs &a, uint64_t s) {
+    ListLat l{kept_lat(a.arena, a.desc, s), nullptr};
+    if (l.valid) l.lists = (uint64_t *)(a.arena + l.own);
     return l;
 }
 
@@ -86,7 +72,7 @@ __device__ __forceinline__ uint64_t wave_merge64(uint64_t a, uint64_t b, uint32_
 
 // The chain of path (node, rank) down to BOS: visit(node) for every node on it, EOS first -> the nodes visited.  Bounded by N: a chain's nodes descend.
 template <class F>
-__device__ __forceinline__ uint32_t walk_chain(const Lat &l, uint32_t k, uint32_t rank, F &&visit) {
+__device__ __forceinline__ uint32_t walk_chain(const ListLat &l, uint32_t k, uint32_t rank, F &&visit) {
     uint32_t node = l.N - 1, len = 0;
     while (node != 0 && len < l.N) {
         visit(node);
@@ -100,35 +86,18 @@ __device__ __forceinline__ uint32_t walk_chain(const Lat &l, uint32_t k, uint32_
 }  // namespace
 
 __global__ __launch_bounds__(64 * FWD_WAVES) void k_nbest_forward(NbestArgs a) {
-    __shared__ unsigned long long lists_off;   // the arena offset of the sentence's lists (~0: they did not fit), from wavefront 0 to the others
+    __shared__ unsigned long long lists_off;   // lat_take_slab's word
     const uint32_t lane = threadIdx.x & 63u, wave = bcast32(threadIdx.x >> 6), k = a.k;
-    BatchArgs arena{};   // (what slab_fresh reads)
-    arena.ctl = a.ctl; arena.arena = a.arena; arena.arena_bytes = a.arena_bytes;
-    // (every branch around a barrier below is workgroup-uniform: it tests the sentence's descriptor, which only this workgroup writes, or lists_off)
+    const BatchArgs arena = lat_arena_args(a.ctl, a.arena, a.arena_bytes);
     for (uint64_t s = blockIdx.x; s < a.n; s += gridDim.x) {
-        unsigned long long *ds = a.desc + LAT_DESC_WORDS * s;
-        if (bcast32((uint32_t)ds[5]) == 0) continue;   // invalid UTF-8, or the lattice itself did not fit: the status says which
-        const uint64_t N = bcast64(ds[4]);
-        if (wave == 0) {
-            Slab sl{nullptr, 0};
-            const bool ok = N < NBEST_MAX_NODES && slab_fresh(sl, 8ull * k * N, arena, lane);
-            if (lane == 0) lists_off = ok ? (unsigned long long)(sl.ptr - a.arena) : ~0ull;
-        }
-        __syncthreads();
-        const uint64_t off = bcast64(lists_off);
-        __syncthreads();   // (read by all before the next sentence's is stored)
-        if (off == ~0ull) {
-            if (threadIdx.x == 0) { a.status[s] = KGPU_SENT_NO_SCRATCH; ds[5] = 0; }
-            continue;
-        }
-        if (threadIdx.x == 0) ds[7] = off;
+        const KeptLat l = kept_lat<true>(a.arena, a.desc, s);
+        if (!l.valid) continue;   // invalid UTF-8, or the lattice itself did not fit: the status says which
+        const uint64_t off = lat_take_slab(a.desc + LAT_DESC_WORDS * s, 8ull * k * l.N, l.N, NBEST_MAX_NODES, &lists_off, arena, a.status + s);
+        if (off == LAT_NO_SLAB) continue;
         uint64_t *lists = (uint64_t *)(a.arena + off);
-        const uint32_t *sa = (const uint32_t *)(a.arena + ds[0]);
-        const uint64_t na = bcast64(ds[2]) + 4;
-        const uint32_t *nb = sa + SLAB_A_NB * na, *boff = sa + SLAB_A_BOFF * na;
-        const uint8_t *sn = a.arena + ds[1];
-        const uint4 *nodeA = (const uint4 *)sn, *bucket = (const uint4 *)(sn + N * 16);
-        const uint32_t C = bcast32((uint32_t)ds[3]);
+        const uint32_t *nb = l.nb, *boff = l.boff;
+        const uint4 *nodeA = l.nodeA, *bucket = l.bucket;
+        const uint32_t C = l.C;
         if (threadIdx.x < k) lists[threadIdx.x] = threadIdx.x == 0 ? nbest_bos_key() : NBEST_NONE;   // L(BOS)
         __syncthreads();
         for (uint32_t q = 0; q <= C; ++q) {   // the nodes that start at q: independent of each other, their predecessors' lists are final -- dealt among the wavefronts
@@ -161,7 +130,7 @@ __global__ __launch_bounds__(TPB) void k_nbest_count(NbestArgs a) {
     for (uint64_t i = (uint64_t)blockIdx.x * TPB + threadIdx.x; i < items; i += (uint64_t)gridDim.x * TPB) {
         const uint64_t s = i / a.k;
         const uint32_t r = (uint32_t)(i - s * a.k);
-        const Lat l = lat_of(a, s);
+        const ListLat l = list_lat(a, s);
         const uint64_t *eos = l.valid ? l.lists + (uint64_t)(l.N - 1) * a.k : nullptr;
         a.path_len[i] = l.valid && eos[r] != NBEST_NONE ? walk_chain(l, a.k, r, [](uint32_t) {}) : 0;
         if (r == 0) {
@@ -185,17 +154,12 @@ __global__ __launch_bounds__(TPB) void k_nbest_write(NbestArgs a) {
         const uint64_t s = i / a.k;
         const uint32_t r = (uint32_t)(i - s * a.k);
         if (r >= a.path_offsets[s + 1] - a.path_offsets[s]) continue;
-        const Lat l = lat_of(a, s);
+        const ListLat l = list_lat(a, s);
         const uint64_t p = a.path_offsets[s] + r;
         a.tok_offsets[p] = a.path_len[i];
         a.costs[p] = nbest_key_cost(l.lists[(uint64_t)(l.N - 1) * a.k + r]);
         kgpu_token *at = a.tokens + a.path_len[i + 1];   // the chain is met from its end
-        walk_chain(l, a.k, r, [&](uint32_t t) {
-            const int32_t sid = (int32_t)l.nodeA[t].w;
-            const uint2 se = l.nodeB[t];
-            const uint32_t bs = l.cbyte[se.x];
-            *--at = nbest_record(sid > 0 ? KGPU_CLASS_KNOWN : sid < 0 ? KGPU_CLASS_UNKNOWN : KGPU_CLASS_DUMMY, sid < 0 ? -sid : sid, bs, se.x, se.y, l.cbyte[se.y] - bs);
-        });
+        walk_chain(l, a.k, r, [&](uint32_t t) { *--at = lat_record(l, t); });
     }
 }
 

@@ -1,122 +1,75 @@
 // kanpyo_amd/csrc/kgpu_nbest_batch.cpp -- kgpu_tokenize_batch_nbest: the N-best paths (include/kanpyo_gpu.h, "N-best paths") of n sentences in host memory.
 //
-// The protocol of kgpu_graphviz_host.cpp, followed here in a file of its own (that file stays as it is): the call's chunks (cut by input bytes and
-// sentences, so that the lattices and lists a chunk keeps in the arena stay bounded; run one after the other on ONE pooled context: not a throughput
-// path), a chunk's launches -- the general kernel with BatchArgs::keep_lattice over the whole chunk, then the four launches of kgpu_nbest.hip, one host
-// wait between the scan and the write -- the arena_overflow protocol of the kept lattices and their lists, and the delivery into the caller's buffers.
-#include <algorithm>
-#include <cstring>
-#include <vector>
-
-#include "kgpu_runtime.h"
+// A kept-lattice call (kgpu_lattice_call.h has the protocol; DESIGN.md, "The kept-lattice protocol"): this file has the call's own part -- the launches of
+// kgpu_nbest.hip over a chunk's lattices, the lists they keep behind them, and where the paths go.
+#include "kgpu_lattice_call.h"
 
 namespace {
 
-constexpr uint64_t CHUNK_BYTES = 256u << 10, CHUNK_SENTS = 1024;   // a chunk's input: its lattices take a few hundred bytes per input byte, its lists 8 k bytes per node
-
-struct Call {
-    kgpu_dict *d; kgpu_ctx *c;
-    const uint8_t *utf8; const uint64_t *offsets;
+struct NbestOps : LatticeOps {
+    const char *who = "kgpu_tokenize_batch_nbest";
+    static constexpr LatticeHook hook = HOOK_NBEST;
+    static constexpr const char *measure_what = "list launch";
     uint32_t k;
     kgpu_token *tokens; uint64_t token_capacity;
     uint64_t *path_offsets, *tok_offsets; int32_t *costs; uint64_t path_capacity;
-    uint8_t *status;
-    uint64_t paths_done = 0, tokens_done = 0;
-    bool overflow = false;
-    std::vector<uint64_t> rel, poff, toff;
-    std::vector<uint8_t> st;
-};
-
-int hip_fail(Call &k, hipError_t e, const char *what) {
-    set_error("kgpu_tokenize_batch_nbest: %s: %s", what, hipGetErrorString(e));
-    k.c->ctl_dirty = true;
-    return KGPU_ERR_HIP;
-}
-
-// Sentences [lo, lo + m) of the call: lattices, lists, paths, delivery behind what has been delivered.
-int run_chunk(Call &k, uint64_t lo, uint64_t m) {
-    kgpu_ctx *c = k.c;
-    kgpu_dict *d = k.d;
-    const uint64_t *off = k.offsets + lo;
-    const uint64_t base = off[0], total = off[m] - base, items = m * k.k;
-    int rc;
-    // (the context's graphviz buffers serve: the descriptors, the scans' arrays -- path_len [items + 1] | path_offsets [m + 1] -- and the output block)
-    if ((rc = c->arena.ensure(ARENA_INITIAL)) || (rc = c->stage.ensure((size_t)token_bound(total, m) * sizeof(kgpu_token) + 64)) ||
-        (rc = c->tok_count.ensure((size_t)m * 4 + 8)) || (rc = c->in_utf8.ensure((size_t)total + 16)) || (rc = c->in_off.ensure((size_t)(m + 1) * 8)) ||
-        (rc = c->out_status.ensure((size_t)m + 16)) || (rc = c->gv_desc.ensure((size_t)m * LAT_DESC_WORDS * 8 + 8)) || (rc = c->gv_len.ensure((size_t)(items + m + 2) * 8)))
-        return rc;
-    k.rel.resize((size_t)m + 1);
-    for (uint64_t i = 0; i <= m; ++i) k.rel[(size_t)i] = off[i] - base;
-    hipError_t e;
-    // (every copy and launch goes on c->stream and is waited for below: no batch is begun -- as kgpu_lattice_dump)
-    if (total && (e = hipMemcpyAsync(c->in_utf8.p, k.utf8 + base, (size_t)total, hipMemcpyHostToDevice, c->stream)) != hipSuccess) return hip_fail(k, e, "H2D");
-    if ((e = hipMemcpyAsync(c->in_off.p, k.rel.data(), (size_t)(m + 1) * 8, hipMemcpyHostToDevice, c->stream)) != hipSuccess) return hip_fail(k, e, "H2D");
+    uint64_t *n_paths, *n_tokens;
     NbestArgs g{};
-    uint64_t sizes[2] = {0, 0};   // the chunk's records, its paths
-    const TestHooks hooks = test_hooks();
-    const size_t arena_max = hooks.nbest_arena_max ? (size_t)hooks.nbest_arena_max : ARENA_MAX;
-    size_t limit = (size_t)hooks.nbest_arena_initial;   // what of the arena the kept lattices and the lists may use (0: all of it)
-    for (;;) {
-        BatchArgs a{};
-        a.utf8 = (const uint8_t *)c->in_utf8.p; a.offsets = (const uint64_t *)c->in_off.p; a.n = m; a.ctl = c->d_ctl;
-        a.arena = (uint8_t *)c->arena.p; a.arena_bytes = limit ? std::min(limit, c->arena.bytes) : c->arena.bytes;
-        a.stage = (kgpu_token *)c->stage.p; a.tok_count = (uint32_t *)c->tok_count.p; a.status = (uint8_t *)c->out_status.p;
-        a.keep_lattice = 1; a.lat_desc = (unsigned long long *)c->gv_desc.p;
+    std::vector<uint64_t> poff, toff;
+
+    void begin() { path_offsets[0] = 0; tok_offsets[0] = 0; }
+    // the scans' arrays: path_len [m k + 1] | path_offsets [m + 1]
+    size_t chunk_words(uint64_t m) const { return (size_t)(m * k + m + 2); }
+    void fill(const LatticeChunk &f) {
         g = NbestArgs{};
-        g.n = m; g.k = k.k; g.ctl = a.ctl; g.arena = a.arena; g.arena_bytes = a.arena_bytes; g.desc = a.lat_desc;
-        g.conn = d->view.conn; g.conn_rows = d->view.conn_rows; g.status = a.status;
-        g.path_len = (uint64_t *)c->gv_len.p; g.path_offsets = g.path_len + items + 1;
-        c->ctl_dirty = true;   // no scan kernel behind this launch: the next batch zeroes the block itself
-        Control hc{};
-        if ((e = hipMemsetAsync(c->d_ctl, 0, sizeof(Control), c->stream)) != hipSuccess ||
-            (e = hipMemsetAsync(c->gv_desc.p, 0, (size_t)m * LAT_DESC_WORDS * 8 + 8, c->stream)) != hipSuccess) return hip_fail(k, e, "memset");
-        if ((e = (hipError_t)launch_general_keep(d->view, a, c->stream)) != hipSuccess) return hip_fail(k, e, "lattice launch");
-        if ((e = (hipError_t)launch_nbest_measure(g, c->stream)) != hipSuccess) return hip_fail(k, e, "list launch");
-        if ((e = hipMemcpyAsync(&hc, c->d_ctl, sizeof(Control), hipMemcpyDeviceToHost, c->stream)) != hipSuccess ||
-            (e = hipMemcpyAsync(&sizes[0], g.path_len + items, 8, hipMemcpyDeviceToHost, c->stream)) != hipSuccess ||
-            (e = hipMemcpyAsync(&sizes[1], g.path_offsets + m, 8, hipMemcpyDeviceToHost, c->stream)) != hipSuccess) return hip_fail(k, e, "D2H");
-        if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return hip_fail(k, e, "sync");
-        if (!hc.arena_overflow) break;
-        // the kept lattices and their lists did not fit (the arena_overflow protocol): a bigger arena and the chunk once more; at the largest arena the chunk in
-        // halves, and a sentence that alone does not fit keeps KGPU_SENT_NO_SCRATCH and has no paths
-        const size_t want = (limit ? std::min(limit, c->arena.bytes) : c->arena.bytes) * 2;
-        if (want <= arena_max) { if ((rc = c->arena.ensure(want))) return rc; if (limit) limit = want; c->rt.arena_regrows++; continue; }
-        if (m > 1) { if ((rc = run_chunk(k, lo, m / 2))) return rc; return run_chunk(k, lo + m / 2, m - m / 2); }
-        break;
+        g.n = f.m; g.k = k; g.ctl = f.ctl; g.arena = f.arena; g.arena_bytes = f.arena_bytes; g.desc = f.desc;
+        g.conn = f.conn; g.conn_rows = f.conn_rows; g.status = f.status;
+        g.path_len = f.words; g.path_offsets = g.path_len + f.m * k + 1;
     }
-    const uint64_t T = sizes[0], P = sizes[1];
-    if (k.tokens_done + T > k.token_capacity || k.paths_done + P > k.path_capacity) k.overflow = true;
-    if (!k.overflow) {
-        // the output block: records [T] | tok_offsets [P + 1] | costs [P]
-        const size_t o_toff = (size_t)T * sizeof(kgpu_token), o_cost = o_toff + (size_t)(P + 1) * 8;
-        if ((rc = c->gv_text.ensure(o_cost + (size_t)P * 4 + 16))) return rc;
-        uint8_t *blk = (uint8_t *)c->gv_text.p;
-        g.tokens = (kgpu_token *)blk; g.token_cap = T; g.tok_offsets = (uint64_t *)(blk + o_toff); g.costs = (int32_t *)(blk + o_cost); g.path_cap = P;
-        if ((e = (hipError_t)launch_nbest_write(g, c->stream)) != hipSuccess) return hip_fail(k, e, "write launch");
-        k.poff.resize((size_t)m + 1); k.toff.resize((size_t)P + 1);
-        if (T && (e = hipMemcpyAsync(k.tokens + k.tokens_done, g.tokens, (size_t)T * sizeof(kgpu_token), hipMemcpyDeviceToHost, c->stream)) != hipSuccess) return hip_fail(k, e, "D2H records");
-        if (P && (e = hipMemcpyAsync(k.costs + k.paths_done, g.costs, (size_t)P * 4, hipMemcpyDeviceToHost, c->stream)) != hipSuccess) return hip_fail(k, e, "D2H costs");
-        if ((e = hipMemcpyAsync(k.toff.data(), g.tok_offsets, (size_t)(P + 1) * 8, hipMemcpyDeviceToHost, c->stream)) != hipSuccess ||
-            (e = hipMemcpyAsync(k.poff.data(), g.path_offsets, (size_t)(m + 1) * 8, hipMemcpyDeviceToHost, c->stream)) != hipSuccess) return hip_fail(k, e, "D2H offsets");
+    int measure(hipStream_t st) { return launch_nbest_measure(g, st); }
+    void totals(const uint64_t *t[2]) const { t[0] = g.path_len + g.n * k; t[1] = g.path_offsets + g.n; }   // the chunk's records, its paths
+    bool fits(const uint64_t done[2], const uint64_t sz[2]) const { return done[0] + sz[0] <= token_capacity && done[1] + sz[1] <= path_capacity; }
+    // the output block: records [T] | tok_offsets [P + 1] | costs [P]
+    size_t out_bytes(const uint64_t sz[2]) const { return (size_t)sz[0] * sizeof(kgpu_token) + (size_t)(sz[1] + 1) * 8 + (size_t)sz[1] * 4; }
+    void place(uint8_t *blk, const uint64_t sz[2]) {
+        const size_t o_toff = (size_t)sz[0] * sizeof(kgpu_token), o_cost = o_toff + (size_t)(sz[1] + 1) * 8;
+        g.tokens = (kgpu_token *)blk; g.token_cap = sz[0]; g.tok_offsets = (uint64_t *)(blk + o_toff); g.costs = (int32_t *)(blk + o_cost); g.path_cap = sz[1];
     }
-    k.st.resize((size_t)m + 1);
-    if (k.status && m && (e = hipMemcpyAsync(k.st.data(), c->out_status.p, (size_t)m, hipMemcpyDeviceToHost, c->stream)) != hipSuccess) return hip_fail(k, e, "D2H status");
-    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return hip_fail(k, e, "sync");
-    if (!k.overflow) {
-        for (uint64_t i = 0; i <= m; ++i) k.path_offsets[lo + i] = k.paths_done + k.poff[(size_t)i];
-        for (uint64_t p = 0; p <= P; ++p) k.tok_offsets[k.paths_done + p] = k.tokens_done + k.toff[(size_t)p];
+    int write(hipStream_t st) { return launch_nbest_write(g, st); }
+    // Everything, the offsets included, is delivered only while nothing has overflowed: tok_offsets has path_capacity + 1 entries, so the offsets of paths
+    // that did not fit have nowhere to go.
+    hipError_t deliver(const LatticeChunk &f, const uint64_t done[2], const uint64_t sz[2], bool fits, const char *&what) {
+        if (!fits) return hipSuccess;
+        const uint64_t T = sz[0], P = sz[1];
+        hipError_t e;
+        poff.resize((size_t)f.m + 1); toff.resize((size_t)P + 1);
+        what = "D2H records";
+        if ((e = d2h(tokens + done[0], g.tokens, (size_t)T * sizeof(kgpu_token), f.stream)) != hipSuccess) return e;
+        what = "D2H costs";
+        if ((e = d2h(costs + done[1], g.costs, (size_t)P * 4, f.stream)) != hipSuccess) return e;
+        what = "D2H offsets";
+        if ((e = d2h(toff.data(), g.tok_offsets, (size_t)(P + 1) * 8, f.stream)) != hipSuccess) return e;
+        return d2h(poff.data(), g.path_offsets, (size_t)(f.m + 1) * 8, f.stream);
     }
-    if (k.status && m) std::memcpy(k.status + lo, k.st.data(), (size_t)m);
-    k.tokens_done += T; k.paths_done += P;
-    return KGPU_OK;
-}
+    void fix_up(const LatticeChunk &f, const uint64_t done[2], const uint64_t sz[2], bool fits) {
+        if (!fits) return;
+        for (uint64_t i = 0; i <= f.m; ++i) path_offsets[f.lo + i] = done[1] + poff[(size_t)i];
+        for (uint64_t p = 0; p <= sz[1]; ++p) tok_offsets[done[1] + p] = done[0] + toff[(size_t)p];
+    }
+    void report(const uint64_t done[2]) { *n_paths = done[1]; *n_tokens = done[0]; }
+    void too_small(const uint64_t done[2]) {
+        set_error("buffers too small: need %llu paths (capacity %llu) and %llu tokens (capacity %llu)", (unsigned long long)done[1], (unsigned long long)path_capacity,
+                  (unsigned long long)done[0], (unsigned long long)token_capacity);
+    }
+};
 
 }  // namespace
 
 extern "C" int kgpu_tokenize_batch_nbest(kgpu_dict *d, const uint8_t *utf8, const uint64_t *offsets, uint64_t n, uint32_t n_best,
                                          kgpu_token *tokens, uint64_t token_capacity, uint64_t *path_offsets, uint64_t *tok_offsets, int32_t *costs,
                                          uint64_t path_capacity, uint8_t *status, uint64_t *n_paths, uint64_t *n_tokens) {
-    const char *who = "kgpu_tokenize_batch_nbest";
+    NbestOps ops;
+    const char *who = ops.who;
     if (n_paths) *n_paths = 0;
     if (n_tokens) *n_tokens = 0;
     if (!d || !offsets || !path_offsets || !tok_offsets || !n_paths || !n_tokens || (token_capacity && !tokens) || (path_capacity && !costs)) {
@@ -124,31 +77,7 @@ extern "C" int kgpu_tokenize_batch_nbest(kgpu_dict *d, const uint8_t *utf8, cons
         return KGPU_ERR_INVALID_ARG;
     }
     if (n_best < 1 || n_best > KGPU_NBEST_MAX) { set_error("%s: n_best %u is outside 1 .. %d", who, n_best, KGPU_NBEST_MAX); return KGPU_ERR_INVALID_ARG; }
-    int rc;
-    if ((rc = check_host_batch(who, offsets, n, utf8))) return rc;
-    for (uint64_t i = 0; i < n; ++i)
-        if (offsets[i + 1] - offsets[i] >= (1ull << 31)) { set_error("%s: sentence %llu too long", who, (unsigned long long)i); return KGPU_ERR_INVALID_ARG; }
-    HIPCHECK(hipSetDevice(d->device));
-    PooledCtx lease(d);
-    if (lease.rc) return lease.rc;
-    kgpu_ctx *c = lease.c;
-    Call k{d, c, utf8, offsets, n_best, tokens, token_capacity, path_offsets, tok_offsets, costs, path_capacity, status};
-    if (c->pending && (rc = kgpu_ctx_sync(c, nullptr)) != KGPU_OK && rc != KGPU_ERR_CAPACITY) return rc;
-    rc = KGPU_OK;
-    path_offsets[0] = 0;
-    tok_offsets[0] = 0;
-    const uint64_t hook = test_hooks().nbest_chunk_sents, max_sents = hook ? hook : CHUNK_SENTS;
-    for (uint64_t done = 0; !rc && done < n;) {
-        uint64_t m = 0;
-        while (done + m < n && m < max_sents && (m == 0 || offsets[done + m + 1] - offsets[done] <= CHUNK_BYTES)) ++m;
-        rc = run_chunk(k, done, m);
-        done += m;
-    }
-    *n_paths = k.paths_done; *n_tokens = k.tokens_done;
-    if (!rc && k.overflow) {
-        set_error("buffers too small: need %llu paths (capacity %llu) and %llu tokens (capacity %llu)", (unsigned long long)k.paths_done, (unsigned long long)path_capacity,
-                  (unsigned long long)k.tokens_done, (unsigned long long)token_capacity);
-        return KGPU_ERR_CAPACITY;
-    }
-    return rc;
+    ops.k = n_best; ops.tokens = tokens; ops.token_capacity = token_capacity; ops.path_offsets = path_offsets; ops.tok_offsets = tok_offsets; ops.costs = costs;
+    ops.path_capacity = path_capacity; ops.n_paths = n_paths; ops.n_tokens = n_tokens;
+    return lattice_call(ops, d, utf8, offsets, n, status);
 }

@@ -1,5 +1,5 @@
 // kanpyo_amd/csrc/kgpu_prob.hip -- the lattice probabilities of a batch on the device (include/kanpyo_gpu.h, "lattice probabilities"; not an output of the
-// reference: what `mecab -m` and `mecab -l --theta` give), over the lattices the general kernel left in the arena (BatchArgs::keep_lattice).
+// reference: what `mecab -m` and `mecab -l --theta` give), over kept lattices ("The kept-lattice protocol"; kgpu_lattice_dev.h is the view of one).
 // kgpu_prob_host.cpp states the rule on the host; both run the statements of kgpu_prob_core.h, whose sums are integer sums and whose maxima are
 // maxima: nothing below depends on the order a bucket's slots were filled in, or on which lane met which term.
 //
@@ -8,7 +8,7 @@
 //                    dealt among the wavefronts, ONE WAVEFRONT PER TARGET, lanes over the predecessors of the position's bucket, 64 per round.  A lane loads its
 //                    bucket entry, alpha[j] and its connection cost from the target's matrix column; a wave maximum of doubles, fix(kexp(a - m)), a wave sum of
 //                    u64 -- cross-lane operations, no LDS.  A target of at most 64 predecessors keeps a_j in its register between the two passes.
-//                    alpha is f64[N] at the head of a slab the kernel takes itself (slab_fresh: the arena cursor carries on behind the lattice launch); the
+//                    alpha is f64[N] at the head of a slab the kernel takes itself (lat_take_slab); the
 //                    slab also holds what the later launches of the call need: beta f64[N] and the best-path bytes u8[N] (marginals), or the sampled nodes
 //                    u32[n_samples][C + 2] (samples).
 //   k_prob_backward  the mirror: positions descending, one wavefront per node OF THE BUCKET of q, lanes over the nodes that start at q.  A lane's matrix
@@ -20,7 +20,7 @@
 
 #include <algorithm>
 
-#include "kgpu_device.h"
+#include "kgpu_lattice_dev.h"
 #include "kgpu_prob_core.h"
 
 namespace kgpu {
@@ -37,32 +37,15 @@ __host__ __device__ inline uint64_t prob_slab_bytes(uint64_t N, uint64_t C, uint
     return n_samples ? 8 * N + 4 * (C + 2) * n_samples : 16 * N + ((N + 7) & ~7ull);
 }
 
-// One sentence's kept lattice (kgpu_internal.h: the slabs of k_tokenize_general) and its probability slab, as the passes behind the forward kernel read them.
-struct Lat {
-    bool valid;
-    uint32_t N, C;
-    const uint32_t *cbyte, *nb, *boff, *pre;
-    const uint4 *nodeA, *bucket; const uint2 *nodeB;
-    double *alpha, *beta; uint8_t *best; uint32_t *picks;
-    int32_t eos_dp;
-};
-__device__ __forceinline__ Lat lat_of(const ProbArgs &a, uint64_t s) {
-    Lat l{};
-    const unsigned long long *ds = a.desc + LAT_DESC_WORDS * s;
-    l.valid = ds[5] != 0;
+// A sentence's kept lattice with what lies at LAT_OWN: the probability slab (prob_slab_bytes), as the passes behind the forward kernel read it.
+struct ProbLat : KeptLat { double *alpha, *beta; uint8_t *best; uint32_t *picks; };
+__device__ __forceinline__ ProbLat prob_lat(const ProbArgs &a, uint64_t s) {
+    ProbLat l{kept_lat(a.arena, a.desc, s), nullptr, nullptr, nullptr, nullptr};
     if (!l.valid) return l;
-    l.N = (uint32_t)ds[4]; l.C = (uint32_t)ds[3];
-    const uint32_t *sa = (const uint32_t *)(a.arena + ds[0]);
-    const uint64_t na = ds[2] + 4;
-    l.cbyte = sa + SLAB_A_CBYTE * na; l.nb = sa + SLAB_A_NB * na; l.boff = sa + SLAB_A_BOFF * na;
-    const uint8_t *sn = a.arena + ds[1];
-    l.nodeA = (const uint4 *)sn; l.bucket = (const uint4 *)(sn + (uint64_t)l.N * 16); l.nodeB = (const uint2 *)(sn + (uint64_t)l.N * 32);
-    l.pre = (const uint32_t *)(sn + (uint64_t)l.N * 40);
-    uint8_t *sp = a.arena + ds[7];
+    uint8_t *sp = a.arena + l.own;
     l.alpha = (double *)sp;
     l.beta = (double *)(sp + 8ull * l.N); l.best = sp + 16ull * l.N;   // (marginals)
     l.picks = (uint32_t *)(sp + 8ull * l.N);                           // (samples)
-    l.eos_dp = (int32_t)(uint32_t)ds[6];
     return l;
 }
 
@@ -105,7 +88,7 @@ __device__ __forceinline__ double wave_logsum(uint32_t cnt, uint32_t lane, F &&t
     return prob_logsum(m, wave_sum64(S));
 }
 
-__device__ __forceinline__ bool listed(const ProbArgs &a, const Lat &l, uint32_t t, double log_z, double &p) {
+__device__ __forceinline__ bool listed(const ProbArgs &a, const ProbLat &l, uint32_t t, double log_z, double &p) {
     const double al = l.alpha[t], be = l.beta[t];
     p = prob_marginal(al, be, log_z);
     if (a.select == KGPU_MARGINAL_BEST) return l.best[t] != 0;
@@ -115,36 +98,19 @@ __device__ __forceinline__ bool listed(const ProbArgs &a, const Lat &l, uint32_t
 }  // namespace
 
 __global__ __launch_bounds__(64 * FWD_WAVES) void k_prob_forward(ProbArgs a) {
-    __shared__ unsigned long long slab_off;   // the arena offset of the sentence's slab (~0: it did not fit), from wavefront 0 to the others
+    __shared__ unsigned long long slab_off;   // lat_take_slab's word
     const uint32_t lane = threadIdx.x & 63u, wave = bcast32(threadIdx.x >> 6);
     const double theta = a.theta;
-    BatchArgs arena{};   // (what slab_fresh reads)
-    arena.ctl = a.ctl; arena.arena = a.arena; arena.arena_bytes = a.arena_bytes;
-    // (every branch around a barrier below is workgroup-uniform: it tests the sentence's descriptor, which only this workgroup writes, or slab_off)
+    const BatchArgs arena = lat_arena_args(a.ctl, a.arena, a.arena_bytes);
     for (uint64_t s = blockIdx.x; s < a.n; s += gridDim.x) {
-        unsigned long long *ds = a.desc + LAT_DESC_WORDS * s;
-        if (bcast32((uint32_t)ds[5]) == 0) continue;   // invalid UTF-8, or the lattice itself did not fit: the status says which
-        const uint64_t N = bcast64(ds[4]);
-        const uint32_t C = bcast32((uint32_t)ds[3]);
-        if (wave == 0) {
-            Slab sl{nullptr, 0};
-            const bool ok = N < PROB_MAX_NODES && slab_fresh(sl, prob_slab_bytes(N, C, a.n_samples), arena, lane);
-            if (lane == 0) slab_off = ok ? (unsigned long long)(sl.ptr - a.arena) : ~0ull;
-        }
-        __syncthreads();
-        const uint64_t off = bcast64(slab_off);
-        __syncthreads();   // (read by all before the next sentence's is stored)
-        if (off == ~0ull) {
-            if (threadIdx.x == 0) { a.status[s] = KGPU_SENT_NO_SCRATCH; ds[5] = 0; }
-            continue;
-        }
-        if (threadIdx.x == 0) ds[7] = off;
+        const KeptLat l = kept_lat<true>(a.arena, a.desc, s);
+        if (!l.valid) continue;   // invalid UTF-8, or the lattice itself did not fit: the status says which
+        const uint32_t C = l.C;
+        const uint64_t off = lat_take_slab(a.desc + LAT_DESC_WORDS * s, prob_slab_bytes(l.N, C, a.n_samples), l.N, PROB_MAX_NODES, &slab_off, arena, a.status + s);
+        if (off == LAT_NO_SLAB) continue;
         double *alpha = (double *)(a.arena + off);
-        const uint32_t *sa = (const uint32_t *)(a.arena + ds[0]);
-        const uint64_t na = bcast64(ds[2]) + 4;
-        const uint32_t *nb = sa + SLAB_A_NB * na, *boff = sa + SLAB_A_BOFF * na;
-        const uint8_t *sn = a.arena + ds[1];
-        const uint4 *nodeA = (const uint4 *)sn, *bucket = (const uint4 *)(sn + N * 16);
+        const uint32_t *nb = l.nb, *boff = l.boff;
+        const uint4 *nodeA = l.nodeA, *bucket = l.bucket;
         if (threadIdx.x == 0) alpha[0] = 0.0;   // BOS
         __syncthreads();
         for (uint32_t q = 0; q <= C; ++q) {   // the nodes that start at q: independent of each other, their predecessors' alpha is final
@@ -168,7 +134,7 @@ __global__ __launch_bounds__(64 * FWD_WAVES) void k_prob_backward(ProbArgs a) {
     const uint32_t lane = threadIdx.x & 63u, wave = bcast32(threadIdx.x >> 6);
     const double theta = a.theta;
     for (uint64_t s = blockIdx.x; s < a.n; s += gridDim.x) {
-        const Lat l = lat_of(a, s);
+        const ProbLat l = prob_lat(a, s);
         if (!bcast32(l.valid)) continue;
         const uint32_t N = bcast32(l.N), C = bcast32(l.C);
         for (uint32_t t = threadIdx.x; t < N; t += 64 * FWD_WAVES) { l.beta[t] = t == N - 1 ? 0.0 : prob_neg_inf(); l.best[t] = 0; }
@@ -199,7 +165,7 @@ __global__ __launch_bounds__(TPB) void k_prob_count(ProbArgs a) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t waves = (uint64_t)gridDim.x * (TPB / 64);
     for (uint64_t s = (uint64_t)blockIdx.x * (TPB / 64) + (threadIdx.x >> 6); s < a.n; s += waves) {
-        const Lat l = lat_of(a, s);
+        const ProbLat l = prob_lat(a, s);
         const double log_z = l.valid ? l.alpha[l.N - 1] : prob_neg_inf();
         const bool reach = prob_finite(log_z);
         uint64_t cnt = 0;
@@ -222,7 +188,7 @@ __global__ __launch_bounds__(TPB) void k_prob_write(ProbArgs a) {
     const uint64_t waves = (uint64_t)gridDim.x * (TPB / 64);
     for (uint64_t s = (uint64_t)blockIdx.x * (TPB / 64) + (threadIdx.x >> 6); s < a.n; s += waves) {
         if (a.sent_len[s + 1] == a.sent_len[s]) continue;
-        const Lat l = lat_of(a, s);
+        const ProbLat l = prob_lat(a, s);
         const double log_z = l.alpha[l.N - 1];
         uint64_t at = a.sent_len[s];
         for (uint32_t t0 = 1; t0 < l.N; t0 += 64) {   // in node order: a round's records behind those of the rounds before, a lane's behind the lower lanes'
@@ -232,10 +198,7 @@ __global__ __launch_bounds__(TPB) void k_prob_write(ProbArgs a) {
             const uint64_t mask = __ballot(keep);
             if (keep) {
                 const uint64_t o = at + __popcll(mask & ((1ull << lane) - 1ull));
-                const int32_t sid = (int32_t)l.nodeA[t].w;
-                const uint2 se = l.nodeB[t];
-                const uint32_t bs = l.cbyte[se.x];
-                a.tokens[o] = nbest_record(sid > 0 ? KGPU_CLASS_KNOWN : sid < 0 ? KGPU_CLASS_UNKNOWN : KGPU_CLASS_DUMMY, sid < 0 ? -sid : sid, bs, se.x, se.y, l.cbyte[se.y] - bs);
+                a.tokens[o] = lat_record(l, t);
                 a.probs[o] = p;
                 a.on_best[o] = l.best[t];
             }
@@ -252,7 +215,7 @@ __global__ __launch_bounds__(TPB) void k_prob_sample(ProbArgs a) {
     for (uint64_t i = (uint64_t)blockIdx.x * (TPB / 64) + (threadIdx.x >> 6); i < items; i += waves) {
         const uint64_t s = i / ns;
         const uint32_t r = (uint32_t)(i - s * ns);
-        const Lat l = lat_of(a, s);
+        const ProbLat l = prob_lat(a, s);
         const bool reach = bcast32(l.valid && prob_finite(l.alpha[l.N - 1]));
         if (r == 0 && lane == 0) a.path_offsets[s] = reach ? ns : 0;
         if (!reach) { if (lane == 0) { a.path_len[i] = 0; a.path_cost[i] = 0; } continue; }
@@ -309,16 +272,12 @@ __global__ __launch_bounds__(TPB) void k_prob_write_paths(ProbArgs a) {
         const uint64_t s = i / ns;
         const uint32_t r = (uint32_t)(i - s * ns);
         if (r >= a.path_offsets[s + 1] - a.path_offsets[s]) continue;
-        const Lat l = lat_of(a, s);
+        const ProbLat l = prob_lat(a, s);
         const uint64_t p = a.path_offsets[s] + r, at = a.path_len[i], len = a.path_len[i + 1] - at;
         if (lane == 0) { a.tok_offsets[p] = at; a.costs[p] = a.path_cost[i]; }
         const uint32_t *picks = l.picks + (uint64_t)r * (l.C + 2);
         for (uint64_t k = lane; k < len; k += 64) {   // the walk met the path from its end
-            const uint32_t t = picks[len - 1 - k];
-            const int32_t sid = (int32_t)l.nodeA[t].w;
-            const uint2 se = l.nodeB[t];
-            const uint32_t bs = l.cbyte[se.x];
-            a.tokens[at + k] = nbest_record(sid > 0 ? KGPU_CLASS_KNOWN : sid < 0 ? KGPU_CLASS_UNKNOWN : KGPU_CLASS_DUMMY, sid < 0 ? -sid : sid, bs, se.x, se.y, l.cbyte[se.y] - bs);
+            a.tokens[at + k] = lat_record(l, picks[len - 1 - k]);
         }
     }
 }

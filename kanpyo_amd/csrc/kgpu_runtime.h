@@ -1,6 +1,6 @@
 // kanpyo_amd/csrc/kgpu_runtime.h -- the host runtime's own types and the functions its files share: kgpu_dict.cpp (dictionary),
 // kgpu_ctx.cpp (contexts, launch chain, the shared head and tail of the four record consumers' enqueues), kgpu_host.cpp (large host calls: the chunk frame of the lines, words, encode and count calls), kgpu_small.cpp (small calls), kgpu_multi.cpp (the
-// multi-device entry points), kgpu_split_host.cpp (lines of a raw block), kgpu_graphviz_host.cpp (DOT documents of a batch), kgpu_words_host.cpp (wakati), kgpu_count_host.cpp (word counts), kgpu_encode_host.cpp (vocabulary ids), kgpu_normalize_host.cpp (text normalisation).  Not part of the public ABI.
+// multi-device entry points), kgpu_split_host.cpp (lines of a raw block), kgpu_lattice_call.h (the frame of the kept-lattice calls: DOT documents, N-best, probabilities, modes), kgpu_words_host.cpp (wakati), kgpu_count_host.cpp (word counts), kgpu_encode_host.cpp (vocabulary ids), kgpu_normalize_host.cpp (text normalisation).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "kgpu_chain.h"
+#include "kgpu_chunk_policy.h"
 
 #define HIPCHECK(expr)                                                                  \
     do {                                                                                \
@@ -221,9 +222,9 @@ struct kgpu_ctx {
     DevBuf lines_len;
     HostReport lines_report;
     PinBuf lines_text, lines_off, lines_status;
-    // the DOT documents of a chunk (kgpu_graphviz_host.cpp): the lattice descriptors, the documents' lengths / offsets, the chunk's text -- and, the other call
-    // that keeps lattices, the N-best paths of a chunk (kgpu_nbest_batch.cpp): the descriptors, the scans' arrays, the output block
-    DevBuf gv_desc, gv_len, gv_text;
+    // a chunk of a kept-lattice call (kgpu_lattice_call.h; graphviz, N-best, marginals / samples, mode): the lattice descriptors (LAT_DESC_WORDS per sentence),
+    // the 8-byte words of the call's per-chunk arrays (what its scans run over: LatticeOps::chunk_words), and the block its write launch fills
+    DevBuf lat_desc, lat_words, lat_out;
     // read_line + trim_end on the device (kgpu_split.hip): the tile aggregates, what the carry kernel publishes ([0] lines, [1] packed bytes), and
     // for kgpu_tokenize_text_lines the device copy of the raw block, its packed lines and their offsets
     DevBuf split_agg, split_raw, split_text, split_off;
@@ -312,7 +313,12 @@ struct WorkerPool {
     void task_done(std::atomic<int> &counter); // a task's last statement
 };
 WorkerPool &workers();
-struct TestHooks { bool no_small_calls = false, plain_leaves = false, byte_trie = false; uint64_t chunk_bytes = 4ull << 20, chunk_sents = 16384, depth = 12, multi_chunk_sents = 0, graphviz_chunk_sents = 0, graphviz_arena_initial = 0, graphviz_arena_max = 0, nbest_chunk_sents = 0, nbest_arena_initial = 0, nbest_arena_max = 0, prob_chunk_sents = 0, prob_arena_initial = 0, prob_arena_max = 0, mode_chunk_sents = 0, mode_arena_initial = 0, mode_arena_max = 0, arena_initial = 0; int aux_launch = -1; };
+// The hooks of the kept-lattice calls (kgpu_lattice_call.h), one slot per family: KGPU_HOST_<NAME>_CHUNK_SENTS, sentences per chunk (0: the default), and
+// KGPU_HOST_<NAME>_ARENA_INITIAL / _ARENA_MAX, the bytes of the scratch arena a chunk's kept lattices may use at first / at most (0: the whole arena /
+// ARENA_MAX): tests of the overflow protocol.  LATTICE_HOOK_NAMES (kgpu_dict.cpp) holds the <NAME>s in this order.
+enum LatticeHook : uint32_t { HOOK_GRAPHVIZ, HOOK_NBEST, HOOK_PROB, HOOK_MODE, LATTICE_HOOKS };
+struct LatticeHooks { uint64_t chunk_sents = 0, arena_initial = 0, arena_max = 0; };
+struct TestHooks { bool no_small_calls = false, plain_leaves = false, byte_trie = false; uint64_t chunk_bytes = 4ull << 20, chunk_sents = 16384, depth = 12, multi_chunk_sents = 0, arena_initial = 0; int aux_launch = -1; LatticeHooks lattice[LATTICE_HOOKS]; };
 TestHooks test_hooks();  // test-only environment hooks, read once per process (or per call under KGPU_TEST_HOOKS_REREAD)
 bool env_flag_now(const char *name);
 
@@ -508,8 +514,7 @@ int run_pipeline(kgpu_dict *d, const uint64_t *offsets, uint64_t n, int depth, i
         }
         Job &j = jobs[(head + inflight) % depth];
         if (!j.c && (rc = pool_get(d, &j.c))) break;
-        uint64_t m = 0;
-        while (done + m < n && m < lim.sents && (m == 0 || offsets[done + m + 1] - offsets[done] <= lim.bytes)) ++m;
+        const uint64_t m = cut_chunk(offsets, done, n, lim.sents, lim.bytes);
         j.lo = done; j.m = m;
         if ((rc = submit(j))) {   // (a batch may be queued without what follows it: the context goes back to the pool idle)
             if (j.c->pending) (void)kgpu_ctx_sync(j.c, nullptr);

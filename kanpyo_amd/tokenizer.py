@@ -89,6 +89,21 @@ def _token_of(raw: bytes, t) -> Token:
     return Token(int(t["id"]), cls, pos, int(t["start"]), int(t["end"]), "EOS" if cls == TokenClass.Dummy else raw[pos : pos + bl].decode("utf-8"))
 
 
+def _sentences(utf8, offs, status, n: int):
+    """(i, raw) for each of a packed batch's n sentences, raw being its bytes; UnicodeDecodeError at the first one the device found not to be UTF-8."""
+    for i in range(n):
+        raw = bytes(utf8[int(offs[i]) : int(offs[i + 1])])
+        if status[i] == _lib.KGPU_SENT_INVALID_UTF8:
+            raise UnicodeDecodeError("utf-8", raw, 0, 1, "invalid UTF-8 sentence")
+        yield i, raw
+
+
+def _paths_of(utf8, offs, n: int, tokens, poff, toff, costs, status) -> list:
+    """Per sentence its NBestPath objects, from the arrays of a paths call (Tokenizer._paths_call)."""
+    return [[NBestPath(int(costs[p]), tuple(_token_of(raw, t) for t in tokens[int(toff[p]) : int(toff[p + 1])])) for p in range(int(poff[i]), int(poff[i + 1]))]
+            for i, raw in _sentences(utf8, offs, status, n)]
+
+
 def _token_room(total: int, n: int) -> int:
     """The token records a first call allocates for n sentences of `total` bytes."""
     return total // 2 + n + 64
@@ -234,8 +249,13 @@ class Tokenizer(Handle):
         """kgpu_tokenize_batch_nbest -> (tokens[TOKEN_DTYPE], path_offsets[uint64 n+1], tok_offsets[uint64 P+1], costs[int32 P], status[uint8 n]):
         sentence i's paths are path_offsets[i]:path_offsets[i+1], best first; path p costs costs[p] and holds tokens[tok_offsets[p]:tok_offsets[p+1]].
         The capacities, when given, are never grown: KGPU_ERR_CAPACITY surfaces as KgpuError."""
+        return self._paths_call(_lib.lib().kgpu_tokenize_batch_nbest, lambda k: (k,), utf8, offsets, n_best, token_capacity, path_capacity)
+
+    def _paths_call(self, fn, lead, utf8, offsets, k, token_capacity, path_capacity):
+        """A call that gives up to k paths per sentence in N-best's arrays: fn(handle, utf8, offsets, n, *lead(k), tokens, token_capacity, path_offsets,
+        tok_offsets, costs, path_capacity, status, &n_paths, &n_tokens), grown and called again on KGPU_ERR_CAPACITY unless a capacity was given."""
         utf8, offsets, n, total = packed_input(utf8, offsets)
-        k = int(n_best)
+        k = int(k)
         fixed = token_capacity is not None or path_capacity is not None
         caps = (_token_room(total, n) * min(max(k, 1), 4) if token_capacity is None else int(token_capacity), n * max(k, 0) if path_capacity is None else int(path_capacity))
         poff, status = np.zeros(n + 1, dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint8)
@@ -243,8 +263,8 @@ class Tokenizer(Handle):
         while caps is not None:
             tokens, toff, costs = np.empty(max(caps[0], 1), dtype=TOKEN_DTYPE), np.zeros(caps[1] + 1, dtype=np.uint64), np.empty(max(caps[1], 1), dtype=np.int32)
             status[:] = 0
-            rc = _lib.lib().kgpu_tokenize_batch_nbest(self._h, ptr(utf8), offsets.ctypes.data, n, k, tokens.ctypes.data, caps[0], poff.ctypes.data, toff.ctypes.data,
-                                                      costs.ctypes.data, caps[1], status.ctypes.data, C.byref(P), C.byref(T))
+            rc = fn(self._h, ptr(utf8), offsets.ctypes.data, n, *lead(k), tokens.ctypes.data, caps[0], poff.ctypes.data, toff.ctypes.data, costs.ctypes.data, caps[1],
+                    status.ctypes.data, C.byref(P), C.byref(T))
             caps = _lib.check(rc) if fixed else grown(rc, caps, (T.value, P.value))
         return tokens[: T.value], poff, toff[: P.value + 1], costs[: P.value], status[:n]
 
@@ -255,22 +275,7 @@ class Tokenizer(Handle):
         utf8, offs = pack_sentences(sentences)
         if normalize is not None:
             utf8, offs, _ = self.normalize_packed(utf8, offs, normalize)
-        tokens, poff, toff, costs, status = self.tokenize_nbest_packed(utf8, offs, n_best)
-        out = []
-        for i in range(len(sentences)):
-            if status[i] == _lib.KGPU_SENT_INVALID_UTF8:
-                raise UnicodeDecodeError("utf-8", bytes(utf8[int(offs[i]) : int(offs[i + 1])]), 0, 1, "invalid UTF-8 sentence")
-            raw = utf8[int(offs[i]) : int(offs[i + 1])].tobytes()
-            paths = []
-            for p in range(int(poff[i]), int(poff[i + 1])):
-                row = []
-                for t in tokens[int(toff[p]) : int(toff[p + 1])]:
-                    cls = TokenClass(int(t["cls"]))
-                    pos, bl = int(t["position"]), int(t["byte_len"])
-                    row.append(Token(int(t["id"]), cls, pos, int(t["start"]), int(t["end"]), "EOS" if cls == TokenClass.Dummy else raw[pos : pos + bl].decode("utf-8")))
-                paths.append(NBestPath(int(costs[p]), tuple(row)))
-            out.append(paths)
-        return out
+        return _paths_of(utf8, offs, len(sentences), *self.tokenize_nbest_packed(utf8, offs, n_best))
 
     # ---- search and extended modes (include/kanpyo_gpu.h, "search mode"; not an output of the reference: what Kuromoji and Kagome offer for indexing) ------
     def tokenize_mode_packed(self, utf8: np.ndarray, offsets: np.ndarray, mode="search", penalties=None, token_capacity: int | None = None):
@@ -300,13 +305,7 @@ class Tokenizer(Handle):
         if normalize is not None:
             utf8, offs, _ = self.normalize_packed(utf8, offs, normalize)
         tokens, toff, _, status = self.tokenize_mode_packed(utf8, offs, mode, penalties)
-        out = []
-        for i in range(len(sentences)):
-            if status[i] == _lib.KGPU_SENT_INVALID_UTF8:
-                raise UnicodeDecodeError("utf-8", bytes(utf8[int(offs[i]) : int(offs[i + 1])]), 0, 1, "invalid UTF-8 sentence")
-            raw = utf8[int(offs[i]) : int(offs[i + 1])].tobytes()
-            out.append([_token_of(raw, tokens[r]) for r in range(int(toff[i]), int(toff[i + 1]))])
-        return out
+        return [[_token_of(raw, t) for t in tokens[int(toff[i]) : int(toff[i + 1])]] for i, raw in _sentences(utf8, offs, status, len(sentences))]
 
     # ---- lattice probabilities (include/kanpyo_gpu.h, "lattice probabilities"; not an output of the reference: `mecab -m`, `mecab -l --theta`) ------
     def tokenize_marginals_packed(self, utf8: np.ndarray, offsets: np.ndarray, theta: float = _lib.KGPU_THETA_DEFAULT, all_nodes: bool = False, min_prob: float = 0.0,
@@ -337,32 +336,15 @@ class Tokenizer(Handle):
         if normalize is not None:
             utf8, offs, _ = self.normalize_packed(utf8, offs, normalize)
         tokens, probs, on_best, toff, _, _, status = self.tokenize_marginals_packed(utf8, offs, theta, all_nodes, min_prob)
-        out = []
-        for i in range(len(sentences)):
-            if status[i] == _lib.KGPU_SENT_INVALID_UTF8:
-                raise UnicodeDecodeError("utf-8", bytes(utf8[int(offs[i]) : int(offs[i + 1])]), 0, 1, "invalid UTF-8 sentence")
-            raw = utf8[int(offs[i]) : int(offs[i + 1])].tobytes()
-            out.append([(_token_of(raw, tokens[r]), float(probs[r]), bool(on_best[r])) for r in range(int(toff[i]), int(toff[i + 1]))])
-        return out
+        return [[(_token_of(raw, tokens[r]), float(probs[r]), bool(on_best[r])) for r in range(int(toff[i]), int(toff[i + 1]))]
+                for i, raw in _sentences(utf8, offs, status, len(sentences))]
 
     def tokenize_samples_packed(self, utf8: np.ndarray, offsets: np.ndarray, n_samples: int, seed: int = 0, theta: float = _lib.KGPU_THETA_DEFAULT,
                                 token_capacity: int | None = None, path_capacity: int | None = None):
         """kgpu_tokenize_batch_samples -> N-best's arrays (tokens, path_offsets[n+1], tok_offsets[P+1], costs[P], status[n]): per sentence n_samples
         paths drawn with P(path) proportional to exp(-theta cost) (none where EOS is unreachable); the same (seed, sentence index in the call) draws the
         same paths.  The capacities, when given, are never grown."""
-        utf8, offsets, n, total = packed_input(utf8, offsets)
-        k = int(n_samples)
-        fixed = token_capacity is not None or path_capacity is not None
-        caps = (_token_room(total, n) * min(max(k, 1), 4) if token_capacity is None else int(token_capacity), n * max(k, 0) if path_capacity is None else int(path_capacity))
-        poff, status = np.zeros(n + 1, dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint8)
-        P, T = C.c_uint64(0), C.c_uint64(0)
-        while caps is not None:
-            tokens, toff, costs = np.empty(max(caps[0], 1), dtype=TOKEN_DTYPE), np.zeros(caps[1] + 1, dtype=np.uint64), np.empty(max(caps[1], 1), dtype=np.int32)
-            status[:] = 0
-            rc = _lib.lib().kgpu_tokenize_batch_samples(self._h, ptr(utf8), offsets.ctypes.data, n, float(theta), k, int(seed) & (2**64 - 1), tokens.ctypes.data, caps[0],
-                                                        poff.ctypes.data, toff.ctypes.data, costs.ctypes.data, caps[1], status.ctypes.data, C.byref(P), C.byref(T))
-            caps = _lib.check(rc) if fixed else grown(rc, caps, (T.value, P.value))
-        return tokens[: T.value], poff, toff[: P.value + 1], costs[: P.value], status[:n]
+        return self._paths_call(_lib.lib().kgpu_tokenize_batch_samples, lambda k: (float(theta), k, int(seed) & (2**64 - 1)), utf8, offsets, n_samples, token_capacity, path_capacity)
 
     def tokenize_samples(self, sentences: Sequence[str], n_samples: int, seed: int = 0, theta: float = _lib.KGPU_THETA_DEFAULT, normalize=None) -> List[List[NBestPath]]:
         """Per sentence n_samples sampled tokenizations (NBestPath.cost, NBestPath.tokens; none where EOS is unreachable): segmentations for
@@ -370,14 +352,7 @@ class Tokenizer(Handle):
         utf8, offs = pack_sentences(sentences)
         if normalize is not None:
             utf8, offs, _ = self.normalize_packed(utf8, offs, normalize)
-        tokens, poff, toff, costs, status = self.tokenize_samples_packed(utf8, offs, n_samples, seed, theta)
-        out = []
-        for i in range(len(sentences)):
-            if status[i] == _lib.KGPU_SENT_INVALID_UTF8:
-                raise UnicodeDecodeError("utf-8", bytes(utf8[int(offs[i]) : int(offs[i + 1])]), 0, 1, "invalid UTF-8 sentence")
-            raw = utf8[int(offs[i]) : int(offs[i + 1])].tobytes()
-            out.append([NBestPath(int(costs[p]), tuple(_token_of(raw, t) for t in tokens[int(toff[p]) : int(toff[p + 1])])) for p in range(int(poff[i]), int(poff[i + 1]))])
-        return out
+        return _paths_of(utf8, offs, len(sentences), *self.tokenize_samples_packed(utf8, offs, n_samples, seed, theta))
 
     def routing(self, reset: bool = False) -> dict:
         """kgpu_dict_get_routing: the routing counters of the handle's pooled contexts (small_calls, combined_calls, ...)."""
@@ -393,19 +368,7 @@ class Tokenizer(Handle):
         if normalize is not None:
             utf8, offs, _ = self.normalize_packed(utf8, offs, normalize)
         tokens, toff, status = self.tokenize_packed(utf8, offs)
-        out = []
-        for i, s in enumerate(sentences):
-            if status[i] == _lib.KGPU_SENT_INVALID_UTF8:
-                raise UnicodeDecodeError("utf-8", bytes(utf8[int(offs[i]) : int(offs[i + 1])]), 0, 1, "invalid UTF-8 sentence")
-            raw = utf8[int(offs[i]) : int(offs[i + 1])].tobytes()
-            row = []
-            for t in tokens[int(toff[i]) : int(toff[i + 1])]:
-                cls = TokenClass(int(t["cls"]))
-                pos, bl = int(t["position"]), int(t["byte_len"])
-                surface = "EOS" if cls == TokenClass.Dummy else raw[pos : pos + bl].decode("utf-8")
-                row.append(Token(int(t["id"]), cls, pos, int(t["start"]), int(t["end"]), surface))
-            out.append(row)
-        return out
+        return [[_token_of(raw, t) for t in tokens[int(toff[i]) : int(toff[i + 1])]] for i, raw in _sentences(utf8, offs, status, len(sentences))]
 
     def tokenize_aligned(self, sentences: Sequence[str], normalize="NFKC") -> List[List[AlignedToken]]:
         """tokenize_batch(sentences, normalize=...) with every token's place in the sentence AS IT WAS GIVEN: the sentences are normalised with their

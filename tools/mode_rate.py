@@ -32,7 +32,7 @@ def setup():
 
 
 def chunks_of(offs) -> int:
-    """The chunks the call cuts this input into: at most 256 KiB and 1024 sentences each (kgpu_mode_batch.cpp, as kgpu_nbest_batch.cpp)."""
+    """The chunks the call cuts this input into: at most 256 KiB and 1024 sentences each (kgpu_lattice_call.h over cut_chunk)."""
     o, n, done, chunks = offs.tolist(), len(offs) - 1, 0, 0
     while done < n:
         m = 0

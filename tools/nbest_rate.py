@@ -29,7 +29,7 @@ def setup(kind):
 
 
 def chunks_of(offs) -> int:
-    """The chunks kgpu_tokenize_batch_nbest cuts this input into: at most 256 KiB and 1024 sentences each (kgpu_nbest_batch.cpp)."""
+    """The chunks kgpu_tokenize_batch_nbest cuts this input into: at most 256 KiB and 1024 sentences each (kgpu_lattice_call.h over cut_chunk)."""
     o, n, done, chunks = offs.tolist(), len(offs) - 1, 0, 0
     while done < n:
         m = 0

@@ -35,7 +35,7 @@ def setup(kind):
 
 
 def chunks_of(offs) -> int:
-    """The chunks the calls cut this input into: at most 256 KiB and 1024 sentences each (kgpu_prob_batch.cpp)."""
+    """The chunks the calls cut this input into: at most 256 KiB and 1024 sentences each (kgpu_lattice_call.h over cut_chunk)."""
     o, n, done, chunks = offs.tolist(), len(offs) - 1, 0, 0
     while done < n:
         m = 0
