@@ -1105,6 +1105,59 @@ int kgpu_tokenize_batch_mode(kgpu_dict *d, const uint8_t *utf8, const uint64_t *
                              kgpu_token *tokens, uint64_t token_capacity, uint64_t *tok_offsets /* n + 1 */, int32_t *costs /* n, may be NULL */,
                              uint8_t *status /* may be NULL */, uint64_t *n_tokens);
 
+/* ---- sentences: lines cut into sentences on the device (NOT an output of the reference: a MeCab-style tokenizer is fed sentences, and every Japanese
+ * corpus pipeline cuts its paragraphs at the full stop first, keeping quoted speech together) ----
+ * The input is n lines as every packed call takes them; the rule is stated on bytes and applies to each line by itself.
+ *  1. Classes.  A class is found by the occurrence of a code point's complete UTF-8 encoding inside the line, as kgpu_split_lines finds White_Space,
+ *     on invalid text too; occurrences cannot overlap (a lead byte is never a continuation byte).
+ *     TERMINATOR: U+3002, U+FF61, U+FF01, U+FF1F, '!' and '?' ('.' and U+FF0E are none: decimals, URLs, abbreviations) -- or the up to 16 scalar values
+ *     of the options, each >= U+0021, no surrogate, no White_Space and no bracket (else KGPU_ERR_INVALID_ARG).
+ *     OPENER: U+300C U+300E U+FF08 '(' U+FF3B '[' U+FF5B '{' U+3008 U+300A U+3010 U+3014 U+FF62.
+ *     CLOSER: U+300D U+300F U+FF09 ')' U+FF3D ']' U+FF5D '}' U+3009 U+300B U+3011 U+3015 U+FF63.  Bracket kinds are not told apart.
+ *     SPACE: the 25 White_Space code points of kgpu_split_lines.
+ *  2. Enclosing depth.  Brackets are matched within the line as a stack would; a closer with nothing open matches nothing, and neither does an opener
+ *     that never closes in its line.  eff(j) is the number of matched pairs (o, c) with o <= j < c.  Equally, with r(j) = openers minus closers over
+ *     0..j, P(j) = min(0, min r(0..j)) and S(j) = min r(j..end): eff(j) = r(j) - max(P(j), S(j)).
+ *  3. Boundary.  One lies behind character i iff c_i is a terminator, c_(i+1) is none (or the line ends there: a run stays whole) and eff(i) = 0.
+ *  4. Sentences.  A line's first sentence starts at byte 0.  Behind a boundary the next one starts at the first character that is not SPACE; if only
+ *     SPACE follows up to the line's end there is no further sentence and those bytes stay in the last one.  Nothing else is trimmed: a line's bytes
+ *     are its sentences plus the SPACE dropped between two of them, every line gives one sentence at least (the empty line an empty one), and a line
+ *     without a boundary comes back as it was.
+ *  5. Output.  The sentences packed back to back in line order (the input's byte count always suffices), out_offsets[S + 1], and one kgpu_sentence
+ *     each: its line, where it starts in the line, and the bytes in front of it there that are not 10xxxxxx.  byte_start and char_start added to a
+ *     token's position fields place the token in its line.
+ *  6. Options.  NULL: the defaults.  n_terminators == 0: the default set.  KGPU_SENTENCES_NO_BRACKETS: eff is 0 everywhere.  Other flag bits and the
+ *     reserved words must be 0.
+ *  7. Capacity.  KGPU_ERR_CAPACITY when S exceeds sent_capacity: the exact S is reported and nothing was written (out_offsets holds
+ *     sent_capacity + 1 entries).  The calls take less than 4 GiB of text.
+ *  8. The device result equals kgpu_split_sentences_host byte for byte, for any bytes: both decide by kgpu_sentence_core.h.
+ * Not claimed: closers directly behind a terminator run joining the sentence, a length cap, abbreviations, symmetric quotes, told-apart bracket kinds. */
+#define KGPU_SENTENCES_NO_BRACKETS 1u
+typedef struct kgpu_sentence {
+    uint64_t line;       /* the index of the sentence's line */
+    uint32_t byte_start; /* where it starts in that line */
+    uint32_t char_start; /* ... and the characters in front of it there */
+} kgpu_sentence;
+typedef struct kgpu_sentence_opts {
+    uint32_t flags;
+    uint32_t n_terminators; /* 0: the default set */
+    uint32_t terminators[16];
+    uint32_t reserved[2]; /* 0 */
+} kgpu_sentence_opts;
+/* Host, no device needed.  out (offsets[n] - offsets[0] bytes suffice) and sents may be NULL where nothing can be written to them. */
+int kgpu_split_sentences_host(const uint8_t *utf8, const uint64_t *offsets, uint64_t n, const kgpu_sentence_opts *opts, uint8_t *out,
+                              uint64_t *out_offsets, kgpu_sentence *sents, uint64_t sent_capacity, uint64_t *n_sentences);
+/* Host memory in and out, split on the device in chunks on a pooled context. */
+int kgpu_split_sentences_batch(kgpu_dict *d, const uint8_t *utf8, const uint64_t *offsets, uint64_t n, const kgpu_sentence_opts *opts, uint8_t *out,
+                               uint64_t *out_offsets, kgpu_sentence *sents, uint64_t sent_capacity, uint64_t *n_sentences);
+/* Device-resident, enqueued on c's stream: five launches whatever the batch holds (work is dealt by bytes, not by lines).  total_bytes is
+ * offsets[n] - offsets[0], as kgpu_tokenize_device takes it; d_out (total_bytes) must not overlap the text; d_sents is 16-byte aligned.
+ * kgpu_ctx_sync_sentences waits and reports the sentences and their bytes: KGPU_ERR_CAPACITY (nothing written) when they exceed sent_capacity.  One
+ * render, count, encode, normalise or sentence split may be pending per context.  The buffers are what kgpu_tokenize_device takes next. */
+int kgpu_split_sentences_device(kgpu_ctx *c, const uint8_t *d_utf8, const uint64_t *d_offsets, uint64_t n, uint64_t total_bytes,
+                                const kgpu_sentence_opts *opts, uint8_t *d_out, uint64_t *d_out_offsets, kgpu_sentence *d_sents, uint64_t sent_capacity);
+int kgpu_ctx_sync_sentences(kgpu_ctx *c, uint64_t *n_sentences, uint64_t *n_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,7 +7,7 @@ fallback, importing the tokenizer without the built library raises.
 """
 from .token import AlignedToken, NBestPath, Token, TokenClass  # noqa: F401
 from .dict import Dict  # noqa: F401
-from .tokenizer import Tokenizer, TOKEN_DTYPE, normalize_host, normalize_host_aligned  # noqa: F401
+from .tokenizer import Tokenizer, TOKEN_DTYPE, normalize_host, normalize_host_aligned, split_sentences_host, SENTENCE_DTYPE  # noqa: F401
 from .vocab import Vocab  # noqa: F401
 from .pack import pack_host  # noqa: F401
 from .decode import decode_host  # noqa: F401
@@ -15,4 +15,4 @@ from .nbest import nbest_host  # noqa: F401
 from .prob import marginals_host, samples_host  # noqa: F401
 from .mode import mode_host  # noqa: F401
 
-__all__ = ["AlignedToken", "Token", "TokenClass", "Dict", "Tokenizer", "TOKEN_DTYPE", "Vocab", "normalize_host", "normalize_host_aligned", "pack_host", "decode_host", "NBestPath", "nbest_host", "marginals_host", "samples_host", "mode_host"]
+__all__ = ["AlignedToken", "Token", "TokenClass", "Dict", "Tokenizer", "TOKEN_DTYPE", "Vocab", "normalize_host", "normalize_host_aligned", "split_sentences_host", "SENTENCE_DTYPE", "pack_host", "decode_host", "NBestPath", "nbest_host", "marginals_host", "samples_host", "mode_host"]

@@ -19,6 +19,7 @@ TOKEN8_DTYPE = np.dtype([("id", "<i4"), ("packed", "<u4")])  # kgpu_token8: cls 
 EDIT_DTYPE = np.dtype([("out_pos", "<u4"), ("src_pos", "<u4"), ("out_char", "<u4"), ("src_char", "<u4"),
                        ("out_len", "<u2"), ("src_len", "<u2"), ("out_chars", "<u2"), ("src_chars", "<u2")])
 SPAN_DTYPE = np.dtype([("position", "<u4"), ("byte_len", "<u4"), ("start", "<u4"), ("end", "<u4")])
+SENTENCE_DTYPE = np.dtype([("line", "<u8"), ("byte_start", "<u4"), ("char_start", "<u4")])   # kgpu_sentence (include/kanpyo_gpu.h, "sentences")
 
 
 def pinned_empty(shape, dtype=np.uint8) -> np.ndarray:

@@ -46,6 +46,7 @@ SYMBOLS = [
     "kgpu_nbest_host", "kgpu_tokenize_batch_nbest",
     "kgpu_marginals_host", "kgpu_samples_host", "kgpu_prob_exp_host", "kgpu_prob_log_host", "kgpu_tokenize_batch_marginals", "kgpu_tokenize_batch_samples",
     "kgpu_mode_host", "kgpu_tokenize_batch_mode",
+    "kgpu_split_sentences_host", "kgpu_split_sentences_batch", "kgpu_split_sentences_device", "kgpu_ctx_sync_sentences",
 ]
 KGPU_VOCAB_ADD_BOS, KGPU_VOCAB_ADD_EOS = 1, 2
 KGPU_COUNTS_DEFAULT_SLOTS, KGPU_COUNTS_DEFAULT_KEY_BYTES = 1 << 22, 256 << 20
@@ -59,6 +60,7 @@ KGPU_NBEST_MAX = 64
 KGPU_MARGINAL_BEST, KGPU_MARGINAL_ALL, KGPU_SAMPLES_MAX, KGPU_THETA_DEFAULT = 0, 1, 256, 0.75 / 800.0
 KGPU_THETA_MAX = 2.0**64
 KGPU_MODE_NORMAL, KGPU_MODE_SEARCH, KGPU_MODE_EXTENDED = 0, 1, 2
+KGPU_SENTENCES_NO_BRACKETS, KGPU_SENTENCES_MAX_TERMINATORS = 1, 16
 
 
 def normalize_form(form) -> int:
@@ -199,6 +201,32 @@ class ModeOpts(C.Structure):  # kgpu_mode_opts
                 ("other_penalty", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
+class SentenceOpts(C.Structure):  # kgpu_sentence_opts
+    _fields_ = [("flags", C.c_uint32), ("n_terminators", C.c_uint32), ("terminators", C.c_uint32 * 16), ("reserved", C.c_uint32 * 2)]
+
+
+class Sentence(C.Structure):  # kgpu_sentence: 16 bytes, one per sentence
+    _fields_ = [("line", C.c_uint64), ("byte_start", C.c_uint32), ("char_start", C.c_uint32)]
+
+
+def sentence_opts(terminators=None, brackets=True) -> SentenceOpts:
+    """terminators: None (the default set), a str or an iterable of scalar values; brackets=False: no enclosing depth.  What does not fit the struct is a
+    ValueError; what the rule forbids (White_Space, a bracket, ...) is the library's KGPU_ERR_INVALID_ARG."""
+    cps = [] if terminators is None else [ord(c) if isinstance(c, str) else int(c) for c in terminators]
+    if terminators is not None and not cps:
+        raise ValueError("terminators: an empty set (None selects the default set)")
+    if len(cps) > KGPU_SENTENCES_MAX_TERMINATORS:
+        raise ValueError(f"terminators: {len(cps)} given, at most {KGPU_SENTENCES_MAX_TERMINATORS}")
+    o = SentenceOpts()
+    o.flags = 0 if brackets else KGPU_SENTENCES_NO_BRACKETS
+    o.n_terminators = len(cps)
+    for k, cp in enumerate(cps):
+        if not 0 <= cp <= 0xFFFFFFFF:
+            raise ValueError(f"terminators: {cp!r} is no scalar value")
+        o.terminators[k] = cp
+    return o
+
+
 class Work(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("sentences", "B", "C", "T", "N", "E", "K")]
 
@@ -335,6 +363,11 @@ def lib():
         L.kgpu_tokenize_batch_samples.argtypes = [vp, vp, vp, C.c_uint64, C.c_double, C.c_uint32, C.c_uint64, vp, C.c_uint64, vp, vp, vp, C.c_uint64, vp, u64p, u64p]
         L.kgpu_mode_host.argtypes = [C.POINTER(LatticeOut), vp, C.c_uint64, vp, C.c_uint64, C.c_uint64, C.POINTER(ModeOpts), vp, C.c_uint64, u64p, C.POINTER(C.c_int32)]
         L.kgpu_tokenize_batch_mode.argtypes = [vp, vp, vp, C.c_uint64, C.POINTER(ModeOpts), vp, C.c_uint64, vp, vp, vp, u64p]
+        sent_out = [C.POINTER(SentenceOpts), vp, vp, vp, C.c_uint64]   # opts, out, out_offsets, sents, sent_capacity
+        L.kgpu_split_sentences_host.argtypes = [vp, vp, C.c_uint64] + sent_out + [u64p]
+        L.kgpu_split_sentences_batch.argtypes = [vp, vp, vp, C.c_uint64] + sent_out + [u64p]
+        L.kgpu_split_sentences_device.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64] + sent_out
+        L.kgpu_ctx_sync_sentences.argtypes = [vp, u64p, u64p]
         L.kgpu_debug_wordpiece_split_ends.argtypes = [vp, vp, C.c_uint64, C.POINTER(WordpieceOpts), C.c_int32, vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, C.POINTER(C.c_uint64)]
         L.kgpu_debug_wordpiece_split.argtypes = [vp, vp, C.c_uint64, C.POINTER(WordpieceOpts), C.c_int32, vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.POINTER(C.c_uint64)]
         L.kgpu_debug_counts_order.argtypes = [vp, vp, vp, C.c_uint64] + L.kgpu_counts_read.argtypes[1:]

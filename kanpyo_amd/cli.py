@@ -77,6 +77,11 @@ alignment (include/kanpyo_gpu.h, "source alignment"): every line is normalised w
 to the line as it was given (kgpu_normalize_batch_aligned, kgpu_tokenize_batch, kgpu_source_spans_batch: all on the device); one output line per token,
 `source_start\tsource_end\tsource surface\tnormalised surface` (character positions), and `EOS` behind each input line.  The text is formatted on
 the host -- which needs the lines there: stdin's blocks are split on the host whatever --split says.  A line that is not UTF-8 ends the run with status 101.
+
+`--sentences [--terminators CHARS] [--no-brackets]` on `tokenize`, `wakati`, `count`, `encode` and `normalize`: every line -- a paragraph, a document --
+is cut into sentences on the device (include/kanpyo_gpu.h, "sentences": at 。｡！？!? outside matched brackets, or at CHARS) behind the normalisation
+and in front of the subcommand's packed call, so one output line, or one EOS block, is printed per SENTENCE.  It goes with --nbest, --marginal, --sample
+and --mode; not with `--split device` (the text calls split inside one C call), --offsets, --pair or --max-length, and not on `align` and `graphviz`.
 """
 from __future__ import annotations
 
@@ -154,6 +159,39 @@ def _results(args, stdin, packed_call, text_call):
     from .tokenizer import split_lines
 
     return (packed_call(*split_lines(b)) for b in _blocks(stdin, args.block_bytes))
+
+
+def _sentence_form(args):
+    """With --sentences the stage normalises, not the command: -> the form asked for (None: none), and the command's own is turned off."""
+    if not getattr(args, "sentences", False):
+        return None
+    if args.command == "normalize":
+        return args.form.upper()
+    form, args.normalize = _form(args), "none"
+    return form
+
+
+def _sentence_stage(tok, args, form, call):
+    """--sentences: call(utf8, offsets) over the lines' SENTENCES -- normalised first where --normalize (or `normalize`'s --form) asks for it, then cut on
+    the device (Tokenizer.split_sentences_packed) -- so that every result has one entry per sentence.  A sentence's status is its own, and 4 where
+    the normaliser left its line as it was.  form: _sentence_form's answer.  call=None: the sentences themselves (`normalize`)."""
+    from .tokenizer import merge_status
+
+    def packed(utf8, offs):
+        nstatus = None
+        if form:
+            utf8, offs, nstatus = tok.normalize_packed(utf8, offs, form)
+        text, soff, recs = tok.split_sentences_packed(utf8, offs, args.terminators, not args.no_brackets)
+        if nstatus is not None:
+            nstatus = nstatus[recs["line"].astype(np.int64)]
+        if call is None:
+            return text, soff, nstatus if nstatus is not None else np.zeros(len(recs), dtype=np.uint8)
+        result = call(text, soff)
+        if nstatus is not None:
+            merge_status(result[-1] if isinstance(result, tuple) else result, nstatus)
+        return result
+
+    return packed
 
 
 def _warn_unnormalized(status, line0: int) -> None:
@@ -272,6 +310,7 @@ def _mode_lines(tok, mode: str, penalties, form, utf8, offs):
 
 def tokenize(args, stdin, stdout) -> int:
     tok = _open(args)
+    sent_form = _sentence_form(args)
     packed, text = tok.tokenize_lines_packed, tok.tokenize_text_lines
     if getattr(args, "mode", None) is not None:
         packed, text = partial(_mode_lines, tok, args.mode, args.mode_penalties, _form(args)), None   # (parse_args refuses --split device)
@@ -281,6 +320,8 @@ def tokenize(args, stdin, stdout) -> int:
         packed, text = partial(_prob_lines, tok, args, _form(args)), None          # (likewise)
     elif _form(args):
         packed, text = partial(packed, normalize=_form(args)), partial(text, normalize=_form(args))
+    if args.sentences:
+        packed, text = _sentence_stage(tok, args, sent_form, packed), None   # (parse_args refuses --split device)
     return _print_lines(_results(args, stdin, packed, text), stdout,
                         "thread 'main' panicked: failed to read from stdin: stream did not contain valid UTF-8")
 
@@ -296,7 +337,10 @@ def normalize(args, stdin, stdout) -> int:
     tok = _open(args)
     form = args.form.upper()
     line0 = 0
-    for text, toff, status in _results(args, stdin, partial(tok.normalize_packed, form=form), partial(tok.normalize_text, form=form)):
+    packed, text = partial(tok.normalize_packed, form=form), partial(tok.normalize_text, form=form)
+    if args.sentences:
+        packed, text = _sentence_stage(tok, args, _sentence_form(args), None), None
+    for text, toff, status in _results(args, stdin, packed, text):
         bad = np.flatnonzero(status == 1)
         shown = int(bad[0]) if bad.size else len(status)
         _warn_unnormalized(status[:shown], line0)
@@ -342,14 +386,19 @@ def align(args, stdin, stdout) -> int:
 
 
 def wakati(args, stdin, stdout) -> int:
+    form = _sentence_form(args)
     w = _words(args, separator=os.fsencode(args.separator))
-    return _print_lines(_results(args, stdin, w.render_packed, w.render_text), stdout,
+    packed = _sentence_stage(w.tokenizer, args, form, w.render_packed) if args.sentences else w.render_packed
+    return _print_lines(_results(args, stdin, packed, w.render_text), stdout,
                         "kanpyo_amd: failed to read from stdin: stream did not contain valid UTF-8")
 
 
 def count(args, stdin, stdout) -> int:
-    counts = _words(args).counter()
-    if _each_checked(_results(args, stdin, counts.add_packed, counts.add_text), args.skip_invalid):
+    form = _sentence_form(args)
+    words = _words(args)
+    counts = words.counter()
+    packed = _sentence_stage(words.tokenizer, args, form, counts.add_packed) if args.sentences else counts.add_packed
+    if _each_checked(_results(args, stdin, packed, counts.add_text), args.skip_invalid):
         return PANIC_STATUS   # nothing has been printed
     out = bytearray()
     for word, n in counts.most_common(args.top):
@@ -390,6 +439,7 @@ def encode(args, stdin, stdout) -> int:
         if len(wp["prefix"]) > 8 or wp["max_word_chars"] > 1024:
             print("kanpyo_amd: --prefix has at most 8 bytes, --max-word-chars is at most 1024", file=sys.stderr)
             return 2
+    form = _sentence_form(args)
     v = Vocab.from_words(_words(args), listed, enc(args.unk), enc(args.bos), enc(args.eos), **wp)
     out = bytearray()   # (nothing is printed before the input is known to be valid, or --skip-invalid says not to care)
 
@@ -441,7 +491,8 @@ def encode(args, stdin, stdout) -> int:
         call = with_offsets if args.offsets else model_rows
         results = _results(args, stdin, call, lambda block: call(*split_lines(block)))
     else:
-        results = _results(args, stdin, v.encode_packed, v.encode_text)
+        packed = _sentence_stage(v._open_tokenizer(), args, form, v.encode_packed) if args.sentences else v.encode_packed
+        results = _results(args, stdin, packed, v.encode_text)
     if _each_checked(results, args.skip_invalid, listing if args.offsets or args.max_length is not None else decimal):
         return PANIC_STATUS   # nothing has been printed
     stdout.write(bytes(out))
@@ -568,6 +619,12 @@ def _min_prob(text: str) -> float:
     return v
 
 
+def _terminators(text: str) -> str:
+    if not 1 <= len(text) <= 16:
+        raise argparse.ArgumentTypeError(f"invalid value {text!r}: 1 to 16 characters")
+    return text
+
+
 def _top(text: str) -> int:
     if not text.isascii() or not text.isdigit() or int(text) < 1:
         raise argparse.ArgumentTypeError(f"invalid value {text!r}: a count from 1")
@@ -661,6 +718,11 @@ def _text_command(sub, name: str, help: str, verb: str = None, first=(), own=(),
         p.add_argument(flag, **kw)
     if name not in ("normalize", "align"):
         p.add_argument("--normalize", choices=NORMALIZE_CHOICES, default="none", help=NORMALIZE_HELP)
+    if name != "align":
+        p.add_argument("--sentences", action="store_true",
+                       help="Cut every line into sentences on the device first, behind the normalisation: at 。｡！？!? outside brackets; one output line (or EOS block) per sentence")
+        p.add_argument("--terminators", type=_terminators, default=None, metavar="CHARS", help="With --sentences: the characters a sentence ends at, at most 16 [default: 。｡！？!?]")
+        p.add_argument("--no-brackets", action="store_true", help="With --sentences: a terminator inside brackets ends a sentence too")
     p.add_argument("--split", choices=["host", "device"], default="host",
                    help="Where stdin's blocks are split into lines and trimmed [default: host]")
     if skip_invalid:
@@ -756,6 +818,13 @@ def parse_args(argv=None):
         if args.mode_penalties is not None and args.mode is None:
             t.error("--mode-penalties goes with --mode")
         _prob_defaults(args)
+    if getattr(args, "sentences", False):
+        if args.split == "device":
+            p.error("--sentences works on packed lines: it does not go with --split device (the text calls split inside one C call)")
+        if getattr(args, "offsets", False) or getattr(args, "pair", False) or getattr(args, "max_length", None) is not None:
+            p.error("--sentences does not go with --offsets, --pair or --max-length")
+    elif getattr(args, "terminators", None) is not None or getattr(args, "no_brackets", False):
+        p.error("--terminators and --no-brackets go with --sentences")
     if args.command is None:   # src/bin/kanpyo.rs:173: no subcommand == tokenize from stdin, default dictionary
         args = t.parse_args([])
         args.command = "tokenize"

@@ -13,6 +13,7 @@
 #include "kgpu_normalize_core.h"
 #include "kgpu_pack_core.h"
 #include "kgpu_decode_core.h"
+#include "kgpu_sentence_core.h"
 
 namespace kgpu {
 
@@ -399,6 +400,27 @@ struct SplitArgs {
 };
 uint32_t split_tiles(const uint8_t *d_in, uint64_t len);
 int launch_split_lines(const SplitArgs &a, void *stream);
+// Lines cut into sentences (kgpu_sentence.hip; include/kanpyo_gpu.h, "sentences").  The per-tile scratch: what the two reduce launches leave and what the
+// two carry launches make of it (kgpu_sentence.hip says which word is what); carry_b[ntiles] holds the totals.
+struct SentAggA { int32_t fb, fa, bb, ba; uint32_t fixed, pad; };
+struct SentCarryA { int32_t v_in, u_in; };
+struct SentAggB { uint64_t lines; uint32_t ns, dropped, head, tail, kinds, nc; };
+struct SentCarryB { uint64_t sent_before; uint32_t kept_before, char_in, fl, pad; };
+struct SentArgs {
+    const uint8_t *utf8; const uint64_t *offsets; uint64_t n;   // line i is utf8[offsets[i] .. offsets[i + 1])
+    uint64_t total;                    // offsets[n] - offsets[0] as the caller states it, < 2^32: no byte behind it is read
+    SentRule rule;                     // kgpu_sentence_core.h: the terminators, and whether brackets count
+    uint8_t *out;                      // the sentences packed back to back: total bytes always suffice
+    uint64_t *out_offsets; kgpu_sentence *sents; uint64_t sent_cap;   // sent_cap + 1 offsets, sent_cap records; nothing is stored when S > sent_cap
+    SentAggA *agg_a; SentCarryA *carry_a; SentAggB *agg_b; SentCarryB *carry_b; uint64_t *tile_lines; uint32_t ntiles;   // device scratch (sent_scratch_bytes)
+    unsigned long long *host_ctl;      // device pointer of pinned, mapped words: [0] sentences, [1] packed bytes
+};
+uint32_t sent_tiles(uint64_t total);
+inline size_t sent_scratch_bytes(uint32_t ntiles) { return ((size_t)ntiles + 1) * (sizeof(SentAggA) + sizeof(SentCarryA) + sizeof(SentAggB) + sizeof(SentCarryB) + 16); }
+void sent_place_scratch(SentArgs &a, void *scratch);   // a.ntiles set: the four arrays inside a block of sent_scratch_bytes (8-byte aligned)
+int launch_split_sentences(const SentArgs &a, void *stream);
+// kgpu_sentence_host.cpp (HIP-free, compiles alone): the options checked and turned into the rule -> KGPU_OK, or KGPU_ERR_INVALID_ARG with the error set
+int sent_rule_from_opts(const char *who, const kgpu_sentence_opts *opts, SentRule &rule);
 
 // Text normalisation (kgpu_normalize.hip; include/kanpyo_gpu.h, "text normalisation"): line i of the batch, NFC or NFKC, into text[text_offsets[i] ..).
 struct NormArgs {

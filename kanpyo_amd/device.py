@@ -184,6 +184,24 @@ class DeviceContext(Handle):
         """Wait for the enqueued split; returns (n_lines, n_bytes): d_offsets holds n_lines + 1 entries, d_out n_bytes bytes."""
         return self._sync("kgpu_ctx_sync_split", 2)[1:]
 
+    def split_sentences(self, d_utf8: int, d_offsets: int, n: int, total_bytes: int, d_out: int, d_out_offsets: int, d_sents: int, sent_capacity: int, opts=None):
+        """kgpu_split_sentences_device: enqueue the sentence split (include/kanpyo_gpu.h, "sentences") of n lines in HBM -> the sentences packed in
+        d_out (total_bytes suffice, no overlap with the text), their uint64 offsets in d_out_offsets (sent_capacity + 1) and a 16-byte kgpu_sentence
+        each in d_sents (16-byte aligned): the buffers tokenize takes next.  opts: _lib.sentence_opts(...) (None: the defaults).  sync_sentences
+        waits for it."""
+        _lib.check(_lib.lib().kgpu_split_sentences_device(
+            self._h, C.c_void_p(d_utf8), C.c_void_p(d_offsets), n, total_bytes, C.byref(opts) if opts is not None else None, C.c_void_p(d_out),
+            C.c_void_p(d_out_offsets), C.c_void_p(d_sents) if d_sents else None, sent_capacity))
+
+    def sync_sentences(self) -> tuple:
+        """Wait for the enqueued sentence split -> (sentences, bytes).  KgpuError with KGPU_ERR_CAPACITY: sent_capacity was too small (nothing was
+        written); try_sync_sentences returns the count instead."""
+        return self._sync("kgpu_ctx_sync_sentences", 2)[1:]
+
+    def try_sync_sentences(self) -> tuple:
+        """-> (fits, sentences, bytes): sync_sentences without the exception for a capacity that was too small."""
+        return self._sync("kgpu_ctx_sync_sentences", 2, raises=False)
+
     def set_profiling(self, mode: int):
         _lib.check(_lib.lib().kgpu_ctx_set_profiling(self._h, int(mode)))
 

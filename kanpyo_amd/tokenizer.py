@@ -15,7 +15,7 @@ from typing import List, Sequence
 import numpy as np
 
 from . import _lib
-from ._calls import EDIT_DTYPE, SPAN_DTYPE, TOKEN8_DTYPE, TOKEN_DTYPE, Handle, batch_call, block_bytes, block_call, grown, pack_sentences, packed_input, pinned_empty, ptr, struct_dict  # noqa: F401
+from ._calls import EDIT_DTYPE, SENTENCE_DTYPE, SPAN_DTYPE, TOKEN8_DTYPE, TOKEN_DTYPE, Handle, batch_call, block_bytes, block_call, grown, pack_sentences, packed_input, pinned_empty, ptr, struct_dict  # noqa: F401
 from ._probes import concurrent_callers, merge_bench, merge_shards  # noqa: F401  (they lived here once)
 from .dict import Dict
 from .token import AlignedToken, NBestPath, Token, TokenClass
@@ -62,6 +62,27 @@ def normalize_host_aligned(data, form="NFKC") -> tuple:
     _lib.check(_lib.lib().kgpu_normalize_host_aligned(_lib.normalize_form(form), ptr(src), src.size, out.ctypes.data, out.size, C.byref(got), None,
                                                       edits.ctypes.data, edits.size, C.byref(ne)))
     return out[: got.value].tobytes(), edits[: ne.value]
+
+
+def _sentence_call(entry, utf8, offsets, terminators, brackets) -> tuple:
+    """One sentence split (kgpu_split_sentences_host, or _batch with its handle bound): the first call with room for twice the lines, one more with
+    the count the library reports -> (text[uint8], offsets[uint64 S+1], records[SENTENCE_DTYPE S])."""
+    utf8, offsets, n, total = packed_input(utf8, offsets)
+    opts = _lib.sentence_opts(terminators, brackets)
+    out, got = np.empty(max(total, 1), dtype=np.uint8), C.c_uint64(0)
+    caps = (2 * n + total // 32 + 64,)
+    while caps is not None:
+        ooff, recs = np.empty(caps[0] + 1, dtype=np.uint64), np.empty(max(caps[0], 1), dtype=SENTENCE_DTYPE)
+        rc = entry(ptr(utf8), offsets.ctypes.data, n, C.byref(opts), out.ctypes.data, ooff.ctypes.data, recs.ctypes.data, caps[0], C.byref(got))
+        caps = grown(rc, caps, (got.value,))
+    S = got.value
+    return out[: int(ooff[S])], ooff[: S + 1], recs[:S]
+
+
+def split_sentences_host(utf8, offsets, terminators=None, brackets=True) -> tuple:
+    """kgpu_split_sentences_host: packed lines cut into sentences (include/kanpyo_gpu.h, "sentences") on the host, by the rule the device runs ->
+    (text[uint8], offsets[uint64 S+1], records[SENTENCE_DTYPE S]).  Needs no device; the definition of Tokenizer.split_sentences_packed."""
+    return _sentence_call(_lib.lib().kgpu_split_sentences_host, utf8, offsets, terminators, brackets)
 
 
 def _span_inputs(tokens, tok_offsets, edits, edit_offsets):
@@ -194,6 +215,23 @@ class Tokenizer(Handle):
         text, toff, _ = self.normalize_packed(*pack_sentences(sentences), form)
         raw, o = text.tobytes(), toff.tolist()
         return [raw[o[i] : o[i + 1]].decode("utf-8") if isinstance(s, str) else raw[o[i] : o[i + 1]] for i, s in enumerate(sentences)]
+
+    # ---- sentences (include/kanpyo_gpu.h, "sentences"; not an output of the reference) ------
+    def split_sentences_packed(self, utf8: np.ndarray, offsets: np.ndarray, terminators=None, brackets=True):
+        """kgpu_split_sentences_batch -> (text[uint8], offsets[uint64 S+1], records[SENTENCE_DTYPE S]): the lines cut into sentences on the device --
+        the (utf8, offsets) pair every packed call takes -- and for each sentence its line, byte_start and char_start there.  terminators: a str
+        or scalar values replacing the default set (at most 16); brackets=False: a terminator inside brackets is a boundary too."""
+        return _sentence_call(partial(_lib.lib().kgpu_split_sentences_batch, self._h), utf8, offsets, terminators, brackets)
+
+    def split_sentences(self, lines: Sequence, terminators=None, brackets=True) -> list:
+        """Per line the list of its sentences, cut on the device: str in gives str out, bytes in gives bytes out."""
+        text, off, recs = self.split_sentences_packed(*pack_sentences(lines), terminators, brackets)
+        raw, o = text.tobytes(), off.tolist()
+        out = [[] for _ in lines]
+        for k, r in enumerate(recs):
+            piece = raw[o[k] : o[k + 1]]
+            out[int(r["line"])].append(piece.decode("utf-8", "replace") if isinstance(lines[int(r["line"])], str) else piece)
+        return out
 
     def tokenize_lines_packed(self, utf8: np.ndarray, offsets: np.ndarray, out=None, normalize=None):
         """-> (text[uint8], text_offsets[uint64 n+1], status[uint8 n]): sentence i's `surface\\tfeatures\\n` lines are

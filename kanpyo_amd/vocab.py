@@ -155,7 +155,7 @@ class Vocab(Handle):
         return [ids[o[i] : o[i + 1]] for i in range(len(o) - 1)]
 
     # ---- device memory out -----------------------------------------------------------------------------------------------------------------
-    def encode_tensor(self, sentences: Sequence, width=None, pad_id: int = 0, normalize=None, return_spans: bool = False):
+    def encode_tensor(self, sentences: Sequence, width=None, pad_id: int = 0, normalize=None, return_spans: bool = False, split_sentences=False):
         """The sentences (str or bytes) as torch tensors on the device, in ONE DeviceContext batch: upload, tokenize, sync, encode, sync_lines.
         No id passes through host memory.  THE WHOLE BATCH MUST FIT DEVICE MEMORY (its text, 24 bytes per token and 4 bytes per id): cut a
         corpus into batches.  The batch is tokenized on a DeviceContext of this Vocab's Tokenizer, made by the first call: unlike the host
@@ -170,11 +170,18 @@ class Vocab(Handle):
         ([n, w, 4] padded), the columns position, byte_len, start, end of the id's piece (a whole token where the header's rule 5 says so) inside its
         sentence -- columns 2:4 are character offsets, an offset_mapping -- and token_index int32 [total] ([n, w]), the index of the id's token among
         the sentence's records (EOS record and dropped tokens counted).  bos, eos and pad have zeros and -1.  With a normalisation form the text is
-        normalised with its edit records (normalize_aligned) and the spans are in the coordinates of the SOURCE sentence, mapped on the device."""
+        normalised with its edit records (normalize_aligned) and the spans are in the coordinates of the SOURCE sentence, mapped on the device.
+        split_sentences=True (or a _lib.sentence_opts(...) value): the entries are LINES -- paragraphs, documents -- and are cut into sentences on the
+        device (DeviceContext.split_sentences; include/kanpyo_gpu.h, "sentences") behind the normalisation, which turns U+FF01 into '!' and U+FF62
+        into U+300C first; the sentences are what is tokenized and encoded, no text returns to the host.  The tuple then has one row per SENTENCE
+        and gains a last tensor, sentences int64 [S, 3]: line, byte_start, char_start of each in its (normalised) line.  Not with return_spans
+        (ValueError): spans mapped through both the edits and the sentence starts are not offered."""
         import torch
 
         if width is not None and int(width) < 1:
             raise ValueError("width is 1 or more (None: ragged)")
+        if split_sentences and return_spans:
+            raise ValueError("split_sentences with return_spans is not offered: encode the sentences (Tokenizer.split_sentences) with return_spans instead")
         width = None if width is None else int(width)
         utf8, offs = pack_sentences(sentences)
         n, total = offs.size - 1, int(offs[-1])
@@ -208,6 +215,17 @@ class Vocab(Handle):
                 (total, *_), (d_utf8, d_edits) = _stage(dev, norm_alloc, norm_enqueue, ctx.try_sync_normalize_aligned if return_spans else ctx.try_sync_normalize,
                                                                   (total * 2 + 64, total // 8 + 64) if return_spans else (total * 2 + 64,))
                 d_off = d_noff
+            # 1b. sentences: the sentences and their offsets take the lines' place; a normaliser's status goes with the line to its sentences
+            d_rec = None
+            if split_sentences:
+                sopts = split_sentences if isinstance(split_sentences, _lib.SentenceOpts) else None
+                (n_sent, total), (d_utf8, d_soff, d_rec) = _stage(
+                    dev, lambda cap: (torch.zeros(total + 16, dtype=torch.uint8, device=dev), empty(cap + 1, dtype=torch.int64), empty((max(cap, 1), 2), dtype=torch.int64)),
+                    lambda made, cap: ctx.split_sentences(d_utf8.data_ptr(), d_off.data_ptr(), n, total, made[0].data_ptr(), made[1].data_ptr(), made[2].data_ptr(), cap, sopts),
+                    ctx.try_sync_sentences, (2 * n + total // 32 + 64,))
+                d_off, d_rec, n = d_soff[: n_sent + 1], d_rec[:n_sent], n_sent
+                if d_nst is not None:
+                    d_nst = d_nst[d_rec[:, 0]] if n else d_nst[:1]
             # 2. tokenize (a token buffer too small: once more with the count the device reports and 64, as tokenize_packed does)
             d_toff, d_st = empty(n + 1, dtype=torch.int64), empty(max(n, 1), dtype=torch.uint8)
             (n_tok,), d_tok = _stage(dev, lambda cap: empty((cap, 6), dtype=torch.int32),
@@ -232,9 +250,10 @@ class Vocab(Handle):
             (count,), out = _stage(dev, ids_alloc, ids_enqueue, ctx.try_sync_lines, (n_tok + n * self._extra if width is None else n * width,), fixed=width is not None)
             if d_nst is not None:   # (on the device: the normaliser's 4 shows where the tokenizer said 0)
                 d_st = torch.where((d_st == 0) & (d_nst == _lib.KGPU_SENT_NOT_NORMALIZED), d_nst, d_st)
+        more = () if d_rec is None else (torch.stack([d_rec[:, 0], d_rec[:, 1] & 0xFFFFFFFF, (d_rec[:, 1] >> 32) & 0xFFFFFFFF], dim=1),)
         if width is None:
-            return (out[0][:count], d_ioff, d_st[:n]) + tuple(t[:count] for t in out[1:])
-        return (out[0], torch.clamp(d_ioff[1:] - d_ioff[:-1], max=width), d_st[:n]) + out[1:]
+            return (out[0][:count], d_ioff, d_st[:n]) + tuple(t[:count] for t in out[1:]) + more
+        return (out[0], torch.clamp(d_ioff[1:] - d_ioff[:-1], max=width), d_st[:n]) + out[1:] + more
 
     def encode_pairs_tensor(self, first: Sequence, second: Sequence = None, max_length: int = 512, stride: int = 0, truncation="only_second", windows: bool = True,
                             pad_id: int = 0, cls_id=None, sep_id=None, normalize=None, return_spans: bool = False) -> dict:
