@@ -1158,6 +1158,66 @@ int kgpu_split_sentences_device(kgpu_ctx *c, const uint8_t *d_utf8, const uint64
                                 const kgpu_sentence_opts *opts, uint8_t *d_out, uint64_t *d_out_offsets, kgpu_sentence *d_sents, uint64_t sent_capacity);
 int kgpu_ctx_sync_sentences(kgpu_ctx *c, uint64_t *n_sentences, uint64_t *n_bytes);
 
+/* ---- user dictionary: extra words beside the uploaded dictionary (what `mecab -u`, Kagome, Kuromoji, Lindera and Sudachi offer), matched against the
+ * text and laid beside the lattice on the device; NOT an output of the reference (its README lists "support various dictionaries" as open) ----
+ * Take the lattice of "N-best paths" / "search mode" for the sentence: N nodes in insertion order, BOS = 0, EOS = N - 1; the sentence has C characters.
+ *  Entries.  E entries, e = 0 .. E - 1, each a key (valid UTF-8, 1 to 64 characters, at most 255 bytes), left_id and right_id (the dictionary's own
+ *    context ids, inside the connection matrix) and an int16 cost.  Several entries may share a key, as MeCab CSVs do: each is its own node.  E = 0 is a
+ *    valid dictionary.
+ *  Matches.  Entry e matches at character position q (0 <= q < C) iff its key's bytes equal the text's bytes from that character's first byte on.  Every
+ *    match is a USER NODE with start q, end q + the key's characters, and the entry's ids and cost.  User nodes are numbered N, N + 1, .. by (q, e)
+ *    ascending; there are U of them.  Overlapping matches all exist.
+ *  Withdrawn unknown nodes.  The reference adds unknown nodes at q only if no known word matched there or the character's category is in invoke_list
+ *    (src/lattice.rs:54); an entry behaves as if it had been in the dictionary: an Unknown lattice node that starts at q is WITHDRAWN iff at least one
+ *    entry matches at q, no Known lattice node starts at q, and the category of the character at q has invoke = 0.  A withdrawn node is neither a target
+ *    nor a predecessor.
+ *  Forward, backtrace, options.  The rule of "search mode" over the widened node set (opts NULL: KGPU_MODE_NORMAL).  A user node is penalised by its
+ *    length and kanji count as any node is.  The predecessors of a target that starts at q are all nodes ending at q that are not withdrawn, lattice and
+ *    user alike.  dp and pre are the minimum of the key (tot, j) over the candidates with tot < 1 << 30, j the combined index: among equal totals a
+ *    lattice node wins over a user node, and a lower (q, e) over a higher.  The reference's unreachable-predecessor quirk is kept.  Nothing depends on
+ *    the order in which a bucket or a table was filled.
+ *  Records.  A lattice node gives the record tokenize emits for it.  A user node gives {id = e + 1, cls = KGPU_CLASS_USER, position, start, end,
+ *    byte_len}.  KGPU_MODE_EXTENDED cuts Unknown nodes only.  costs[i], tok_offsets and the status bytes are kgpu_tokenize_batch_mode's.  With E = 0 the
+ *    result is kgpu_tokenize_batch_mode's, byte for byte.
+ *  Statuses.  Invalid UTF-8 gives KGPU_SENT_INVALID_UTF8 and no records; a lattice that, with its slab of 8 N + 32 U + 16 C + 44 bytes, does not fit the
+ *    largest scratch arena, or with N + U >= 2^32 - 1, gives KGPU_SENT_NO_SCRATCH and no records.
+ * Not claimed: the output of `mecab -u` (which needs MeCab and IPADIC), a cost for an entry that has none, Kuromoji's "simple" format. */
+#define KGPU_CLASS_USER 3
+#define KGPU_USERDICT_MAX_KEY_CHARS 64
+#define KGPU_USERDICT_MAX_KEY_BYTES 255
+typedef struct kgpu_userdict kgpu_userdict;
+typedef struct kgpu_userdict_info {
+    uint64_t entries;      /* E */
+    uint64_t keys;         /* distinct keys */
+    uint64_t longest_key;  /* in characters (0: E = 0) */
+    uint64_t device_bytes; /* what the handle holds in device memory */
+} kgpu_userdict_info;
+/* A handle over d's connection matrix: entry e has the key keys[key_offsets[e] .. key_offsets[e + 1]) (E + 1 offsets from 0).  The ids are mapped once
+ * to the numbering the device matrix uses.  KGPU_ERR_INVALID_ARG: an empty key, one over 64 characters or 255 bytes, one that is not UTF-8, an id
+ * outside the matrix, offsets that run backwards, 2^31 entries or more.  A few kilobytes for a typical list: many handles may live over one dictionary.
+ * Immutable; it holds a reference to d as a words handle does (destroy it before the dictionary; one that outlives kgpu_dict_destroy keeps the tables
+ * alive until it goes). */
+int kgpu_userdict_create(kgpu_dict *d, const uint8_t *keys, const uint64_t *key_offsets /* E + 1 */, const uint16_t *left_id, const uint16_t *right_id,
+                         const int16_t *cost, uint64_t E, kgpu_userdict **out);
+void kgpu_userdict_destroy(kgpu_userdict *u);
+int kgpu_userdict_get_info(const kgpu_userdict *u, kgpu_userdict_info *info);
+/* The rule on the host, in plain C++ over one lattice as kgpu_lattice_dump returns it and the sentence's bytes: no device, no handle; the definition of
+ * the device result, byte for byte.  conn as for kgpu_nbest_host; invoke: one byte per character position (C of them; may be NULL when C or E is 0):
+ * non-zero where the character's category is in invoke_list.  opts NULL: KGPU_MODE_NORMAL.  KGPU_ERR_CAPACITY: nothing is written but *n_tokens, the
+ * exact count.  KGPU_ERR_INVALID_ARG: kgpu_mode_host's checks, kgpu_userdict_create's on the entries, lattice nodes that are not numbered by start
+ * position, and a lattice with fewer positions than the text's characters + 2. */
+int kgpu_userdict_host(const kgpu_lattice *lattice, const uint8_t *utf8, uint64_t len, const int16_t *conn, uint64_t conn_rows, uint64_t conn_cols,
+                       const uint8_t *invoke, const uint8_t *keys, const uint64_t *key_offsets, const uint16_t *left_id, const uint16_t *right_id,
+                       const int16_t *cost, uint64_t E, const kgpu_mode_opts *opts, kgpu_token *tokens, uint64_t token_capacity, uint64_t *n_tokens,
+                       int32_t *cost_out);
+/* n sentences in host memory, on the device, by kgpu_tokenize_batch_mode's protocol and with its error behaviour: per chunk the general kernel leaves the
+ * lattices in the scratch arena; one workgroup per sentence matches the keys (a lane per start character, a hash probe per key length that exists),
+ * lays the user nodes beside the lattice and runs the forward pass over both (a wavefront per target node); then count / scan / write.  A tool beside
+ * the throughput path.  u must have been made over d.  opts NULL: KGPU_MODE_NORMAL. */
+int kgpu_tokenize_batch_user(kgpu_dict *d, const kgpu_userdict *u, const uint8_t *utf8, const uint64_t *offsets, uint64_t n, const kgpu_mode_opts *opts,
+                             kgpu_token *tokens, uint64_t token_capacity, uint64_t *tok_offsets /* n + 1 */, int32_t *costs /* n, may be NULL */,
+                             uint8_t *status /* may be NULL */, uint64_t *n_tokens);
+
 #ifdef __cplusplus
 }
 #endif

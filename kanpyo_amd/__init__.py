@@ -14,5 +14,6 @@ from .decode import decode_host  # noqa: F401
 from .nbest import nbest_host  # noqa: F401
 from .prob import marginals_host, samples_host  # noqa: F401
 from .mode import mode_host  # noqa: F401
+from .userdict import UserDict, UserEntry, userdict_host  # noqa: F401
 
-__all__ = ["AlignedToken", "Token", "TokenClass", "Dict", "Tokenizer", "TOKEN_DTYPE", "Vocab", "normalize_host", "normalize_host_aligned", "split_sentences_host", "SENTENCE_DTYPE", "pack_host", "decode_host", "NBestPath", "nbest_host", "marginals_host", "samples_host", "mode_host"]
+__all__ = ["AlignedToken", "Token", "TokenClass", "Dict", "Tokenizer", "TOKEN_DTYPE", "Vocab", "normalize_host", "normalize_host_aligned", "split_sentences_host", "SENTENCE_DTYPE", "pack_host", "decode_host", "NBestPath", "nbest_host", "marginals_host", "samples_host", "mode_host", "UserDict", "UserEntry", "userdict_host"]

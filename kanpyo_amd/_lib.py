@@ -47,6 +47,7 @@ SYMBOLS = [
     "kgpu_marginals_host", "kgpu_samples_host", "kgpu_prob_exp_host", "kgpu_prob_log_host", "kgpu_tokenize_batch_marginals", "kgpu_tokenize_batch_samples",
     "kgpu_mode_host", "kgpu_tokenize_batch_mode",
     "kgpu_split_sentences_host", "kgpu_split_sentences_batch", "kgpu_split_sentences_device", "kgpu_ctx_sync_sentences",
+    "kgpu_userdict_create", "kgpu_userdict_destroy", "kgpu_userdict_get_info", "kgpu_userdict_host", "kgpu_tokenize_batch_user",
 ]
 KGPU_VOCAB_ADD_BOS, KGPU_VOCAB_ADD_EOS = 1, 2
 KGPU_COUNTS_DEFAULT_SLOTS, KGPU_COUNTS_DEFAULT_KEY_BYTES = 1 << 22, 256 << 20
@@ -61,6 +62,7 @@ KGPU_MARGINAL_BEST, KGPU_MARGINAL_ALL, KGPU_SAMPLES_MAX, KGPU_THETA_DEFAULT = 0,
 KGPU_THETA_MAX = 2.0**64
 KGPU_MODE_NORMAL, KGPU_MODE_SEARCH, KGPU_MODE_EXTENDED = 0, 1, 2
 KGPU_SENTENCES_NO_BRACKETS, KGPU_SENTENCES_MAX_TERMINATORS = 1, 16
+KGPU_CLASS_USER, KGPU_USERDICT_MAX_KEY_CHARS, KGPU_USERDICT_MAX_KEY_BYTES = 3, 64, 255
 
 
 def normalize_form(form) -> int:
@@ -199,6 +201,10 @@ class DecodeOpts(C.Structure):  # kgpu_decode_opts
 class ModeOpts(C.Structure):  # kgpu_mode_opts
     _fields_ = [("mode", C.c_uint32), ("kanji_length", C.c_uint32), ("kanji_penalty", C.c_uint32), ("other_length", C.c_uint32),
                 ("other_penalty", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class UserdictInfo(C.Structure):  # kgpu_userdict_info
+    _fields_ = [("entries", C.c_uint64), ("keys", C.c_uint64), ("longest_key", C.c_uint64), ("device_bytes", C.c_uint64)]
 
 
 class SentenceOpts(C.Structure):  # kgpu_sentence_opts
@@ -368,6 +374,17 @@ def lib():
         L.kgpu_split_sentences_batch.argtypes = [vp, vp, vp, C.c_uint64] + sent_out + [u64p]
         L.kgpu_split_sentences_device.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64] + sent_out
         L.kgpu_ctx_sync_sentences.argtypes = [vp, u64p, u64p]
+        entries = [vp, vp, vp, vp, vp, C.c_uint64]   # keys, key_offsets, left_id, right_id, cost, E
+        L.kgpu_userdict_create.argtypes = [vp] + entries + [C.POINTER(vp)]
+        L.kgpu_userdict_destroy.argtypes = [vp]
+        L.kgpu_userdict_destroy.restype = None
+        L.kgpu_userdict_get_info.argtypes = [vp, C.POINTER(UserdictInfo)]
+        L.kgpu_userdict_host.argtypes = [C.POINTER(LatticeOut), vp, C.c_uint64, vp, C.c_uint64, C.c_uint64, vp] + entries + [C.POINTER(ModeOpts), vp, C.c_uint64, u64p, C.POINTER(C.c_int32)]
+        L.kgpu_tokenize_batch_user.argtypes = [vp, vp, vp, vp, C.c_uint64, C.POINTER(ModeOpts), vp, C.c_uint64, vp, vp, vp, u64p]
+        L.kgpu_debug_userdict_hash.argtypes = [vp, C.c_uint32]
+        L.kgpu_debug_userdict_hash.restype = C.c_uint32
+        L.kgpu_debug_userdict_slots.argtypes = [C.c_uint64]
+        L.kgpu_debug_userdict_slots.restype = C.c_uint64
         L.kgpu_debug_wordpiece_split_ends.argtypes = [vp, vp, C.c_uint64, C.POINTER(WordpieceOpts), C.c_int32, vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, C.POINTER(C.c_uint64)]
         L.kgpu_debug_wordpiece_split.argtypes = [vp, vp, C.c_uint64, C.POINTER(WordpieceOpts), C.c_int32, vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.POINTER(C.c_uint64)]
         L.kgpu_debug_counts_order.argtypes = [vp, vp, vp, C.c_uint64] + L.kgpu_counts_read.argtypes[1:]

@@ -308,11 +308,46 @@ def _mode_lines(tok, mode: str, penalties, form, utf8, offs):
     return np.frombuffer(b"".join(out), dtype=np.uint8), loff, status
 
 
+def _user_lines(tok, userdict, mode, penalties, form, utf8, offs):
+    """_mode_lines over the lattices widened by a user dictionary's matches (kgpu_tokenize_batch_user): a user token prints as its surface, a tab and
+    the entry's features joined by commas."""
+    from .nbest import path_lines
+    from .tokenizer import merge_status
+
+    nstatus = None
+    if form:
+        utf8, offs, nstatus = tok.normalize_packed(utf8, offs, form)
+    tokens, toff, _, status = tok.tokenize_user_packed(utf8, offs, userdict, mode or "normal", penalties)
+    if nstatus is not None:
+        merge_status(status, nstatus)
+    raw, o, to = utf8.tobytes(), offs.tolist(), toff.tolist()
+    known, unk = tok.dictfile.morph_feature_table, tok.dictfile.unk_feature_table
+    lines = []
+    for i in range(len(o) - 1):
+        line, recs, first, out = raw[o[i] : o[i + 1]], tokens[to[i] : to[i + 1]], 0, []
+        for k in np.flatnonzero(recs["cls"] == 3).tolist() + [len(recs)]:   # (the runs between two user tokens are path_lines' to render)
+            out.append(path_lines(line, recs[first:k], known, unk))
+            if k < len(recs):
+                pos, bl = int(recs[k]["position"]), int(recs[k]["byte_len"])
+                out.append(line[pos : pos + bl] + b"\t" + ",".join(userdict.features(int(recs[k]["id"]))).encode("utf-8") + b"\n")
+            first = k + 1
+        lines.append(b"".join(out))
+    loff = np.zeros(len(lines) + 1, dtype=np.uint64)
+    if lines:
+        loff[1:] = np.cumsum([len(x) for x in lines])
+    return np.frombuffer(b"".join(lines), dtype=np.uint8), loff, status
+
+
 def tokenize(args, stdin, stdout) -> int:
     tok = _open(args)
     sent_form = _sentence_form(args)
     packed, text = tok.tokenize_lines_packed, tok.tokenize_text_lines
-    if getattr(args, "mode", None) is not None:
+    if getattr(args, "user_entries", None) is not None:
+        from .userdict import UserDict
+
+        userdict = UserDict(tok, args.user_entries)
+        packed, text = partial(_user_lines, tok, userdict, args.mode, args.mode_penalties, _form(args)), None   # (parse_args refuses --split device)
+    elif getattr(args, "mode", None) is not None:
         packed, text = partial(_mode_lines, tok, args.mode, args.mode_penalties, _form(args)), None   # (parse_args refuses --split device)
     elif getattr(args, "nbest", None) is not None:
         packed, text = partial(_nbest_lines, tok, args.nbest, _form(args)), None   # (parse_args refuses --split device)
@@ -753,7 +788,8 @@ def parse_args(argv=None):
                            ("--seed", dict(type=_seed, default=None, metavar="S", help="With --sample: the seed of the draws [default: 0]")),
                            ("--theta", dict(type=_theta, default=None, metavar="T", help="With --marginal / --sample: P(path) is proportional to exp(-T cost) [default: 0.75 / 800]")),
                            ("--mode", dict(choices=["normal", "search", "extended"], default=None, help="search: a length penalty on long words splits compounds into the parts the dictionary has; extended: unknown words are also cut into characters; normal: what tokenize prints (not in the reference)")),
-                           ("--mode-penalties", dict(type=_mode_penalties, default=None, metavar="KL,KP,OL,OP", help="With --mode: kanji length, kanji penalty, other length, other penalty [default: 2,3000,7,1700]"))])
+                           ("--mode-penalties", dict(type=_mode_penalties, default=None, metavar="KL,KP,OL,OP", help="With --mode: kanji length, kanji penalty, other length, other penalty [default: 2,3000,7,1700]")),
+                           ("--user-dict", dict(default=None, metavar="FILE", help="Extra words beside the dictionary's: a MeCab user CSV, surface,left_id,right_id,cost,feature,... per line; a user token prints its surface and the entry's features (not in the reference: mecab -u)"))])
     g = sub.add_parser("graphviz", help="Output lattice in Graphviz format")
     g.add_argument("input", nargs="?", default=None, help="Input text to analyze [default: one line of stdin]")
     g.add_argument("-d", "--dict", choices=["ipa"], default="ipa", help="Dictionary")
@@ -817,6 +853,21 @@ def parse_args(argv=None):
             t.error("--mode renders its lines on the host: it does not go with --split device")
         if args.mode_penalties is not None and args.mode is None:
             t.error("--mode-penalties goes with --mode")
+        args.user_entries = None
+        if args.user_dict is not None:
+            if prob or args.nbest is not None:
+                t.error("--user-dict does not go with --nbest, --marginal or --sample")
+            if args.split == "device":
+                t.error("--user-dict renders its lines on the host: it does not go with --split device")
+            from .userdict import UserDictFormatError, parse_csv
+
+            try:
+                with open(args.user_dict, encoding="utf-8", newline="") as f:
+                    args.user_entries = parse_csv(f.read(), _form(args))
+            except (OSError, UnicodeDecodeError) as e:
+                t.error(f"--user-dict {args.user_dict}: {e}")
+            except UserDictFormatError as e:
+                t.error(f"--user-dict {args.user_dict}: {e}")
         _prob_defaults(args)
     if getattr(args, "sentences", False):
         if args.split == "device":

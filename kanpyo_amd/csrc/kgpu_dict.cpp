@@ -68,7 +68,7 @@ TestHooks kgpu::test_hooks() {
         if (const char *e = getenv("KGPU_HOST_CHUNK_BYTES")) cur.chunk_bytes = strtoull(e, nullptr, 10);
         if (const char *e = getenv("KGPU_HOST_CHUNK_SENTS")) cur.chunk_sents = strtoull(e, nullptr, 10);
         // ... and the three hooks of each kept-lattice family (kgpu_runtime.h: LatticeHooks)
-        static const char *const LATTICE_HOOK_NAMES[LATTICE_HOOKS] = {"GRAPHVIZ", "NBEST", "PROB", "MODE"};
+        static const char *const LATTICE_HOOK_NAMES[LATTICE_HOOKS] = {"GRAPHVIZ", "NBEST", "PROB", "MODE", "USER"};
         for (uint32_t h = 0; h < LATTICE_HOOKS; ++h) {
             uint64_t *const field[3] = {&cur.lattice[h].chunk_sents, &cur.lattice[h].arena_initial, &cur.lattice[h].arena_max};
             static const char *const FIELD_NAMES[3] = {"CHUNK_SENTS", "ARENA_INITIAL", "ARENA_MAX"};

@@ -14,6 +14,7 @@
 #include "kgpu_pack_core.h"
 #include "kgpu_decode_core.h"
 #include "kgpu_sentence_core.h"
+#include "kgpu_user_core.h"
 
 namespace kgpu {
 
@@ -388,6 +389,27 @@ struct ModeArgs {
 };
 int launch_mode_measure(const ModeArgs &a, void *stream);   // forward, count, scan: sent_len and costs are final behind it
 int launch_mode_write(const ModeArgs &a, void *stream);
+// The user dictionary over a batch's kept lattices (kgpu_user.hip; include/kanpyo_gpu.h, "user dictionary"): ModeArgs with the table and what tells a
+// character's category.  The slab a sentence's forward workgroup takes (its arena offset in LAT_OWN): a 16-byte head {U}, the user nodes uint4[U], the
+// state u64[N + U], then u32 arrays -- kanji counts [C + 1], user nodes by start [C + 2], by end [C + 2] twice (offsets, fill cursors), the end-sorted
+// user nodes [U], their entries [U].
+struct UserArgs {
+    ModeArgs m;
+    UserTableView t;               // in device memory
+    const uint8_t *cat; uint32_t cat_len; const CatInfo *cinfo;   // DictView's
+};
+int launch_user_measure(const UserArgs &a, void *stream);   // forward (match, lay out, sweep), count, scan: sent_len and costs are final behind it
+int launch_user_write(const UserArgs &a, void *stream);
+// kgpu_user_table.cpp (HIP-free, compiles alone): a user dictionary's table in host memory.  left_rank / right_rank (null or empty: identity): the
+// numbering of the matrix the table is used with, by the dictionary's own id.
+struct UserTable {
+    std::vector<uint64_t> slots; std::vector<UserGroup> groups; std::vector<UserEntry> ents; std::vector<uint8_t> arena;
+    uint64_t len_mask = 0; uint32_t longest = 0;
+    UserTableView view() const;
+};
+int build_user_table(const char *who, const uint8_t *keys, const uint64_t *key_offsets, const uint16_t *left_id, const uint16_t *right_id, const int16_t *cost,
+                     uint64_t E, uint64_t conn_rows, uint64_t conn_cols, const std::vector<uint32_t> *left_rank, const std::vector<uint32_t> *right_rank,
+                     UserTable &out);
 int launch_prob_eval(const double *d_x, uint64_t n, double *d_out, uint32_t which, void *stream);   // (tests) kexp / klog over an array
 // read_line + trim_end over a block in HBM (kgpu_split.hip; reference src/bin/kanpyo.rs:114-122).
 struct SplitTile { uint32_t x, y, z, w; };   // one tile's aggregate, then its carry (kgpu_split.hip says which word is what)

@@ -1,6 +1,6 @@
 // kanpyo_amd/csrc/kgpu_lattice_call.h -- the one frame of the host calls that decode over kept lattices ("The kept-lattice protocol"):
 // kgpu_graphviz_batch (kgpu_graphviz_host.cpp), kgpu_tokenize_batch_nbest (kgpu_nbest_batch.cpp), kgpu_tokenize_batch_marginals / _samples
-// (kgpu_prob_batch.cpp), kgpu_tokenize_batch_mode (kgpu_mode_batch.cpp).
+// (kgpu_prob_batch.cpp), kgpu_tokenize_batch_mode (kgpu_mode_batch.cpp), kgpu_tokenize_batch_user (kgpu_user_batch.cpp).
 //
 // Owns: the call's common checks and the lease of ONE pooled context (the chunks run one after the other: not a throughput path); the chunks, cut by input
 // bytes and sentences so that what a chunk keeps in the arena stays bounded; a chunk's launches -- the general kernel with BatchArgs::keep_lattice over the

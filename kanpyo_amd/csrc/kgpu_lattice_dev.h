@@ -1,10 +1,11 @@
 // kanpyo_amd/csrc/kgpu_lattice_dev.h -- one view of a kept lattice for the kernels that decode over it (kgpu_graphviz.hip, kgpu_nbest.hip, kgpu_prob.hip,
-// kgpu_mode.hip; DESIGN.md, "The kept-lattice protocol"): the descriptor k_tokenize_general leaves per sentence under BatchArgs::keep_lattice (the LAT_*
+// kgpu_mode.hip, kgpu_user.hip; DESIGN.md, "The kept-lattice protocol"): the descriptor k_tokenize_general leaves per sentence under BatchArgs::keep_lattice (the LAT_*
 // words of kgpu_internal.h), the two slabs it points to, the slab a forward kernel takes behind them, and the record of a node.  The layout of the slabs is
 // written HERE and nowhere else.
 //
-// LAT_OWN is the consumer's own word: graphviz keeps the sentence's visible nodes there; the forward kernels of the other three keep the arena offset of
-// their slab (lists; alpha | beta | best, or alpha | picks; state | kanji counts), and each file has a small struct of its own for what lies there.
+// LAT_OWN is the consumer's own word: graphviz keeps the sentence's visible nodes there; the forward kernels of the other four keep the arena offset of
+// their slab (lists; alpha | beta | best, or alpha | picks; state | kanji counts; a head with the user nodes' number, the user nodes, state | kanji counts and the
+// user nodes by start and by end), and each file has a small struct of its own for what lies there.
 #pragma once
 #include "kgpu_device.h"
 #include "kgpu_nbest_core.h"

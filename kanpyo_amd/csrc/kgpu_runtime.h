@@ -184,6 +184,14 @@ struct kgpu_vocab {
     mutable void *d_entry = nullptr;
 };
 
+// A user dictionary (kgpu_user_batch.cpp): the table of kgpu_user_table.cpp in ONE device allocation, ids as the dictionary's device matrix numbers them.  Immutable.
+struct kgpu_userdict {
+    kgpu_dict *dict = nullptr;          // holds a reference, as a words handle does
+    void *d_block = nullptr;            // slots | groups | entries | key bytes (null: no entries)
+    UserTableView view{};               // ... as the kernels are given them
+    kgpu_userdict_info info{};
+};
+
 struct kgpu_ctx {
     kgpu_dict *dict = nullptr;
     hipStream_t stream = nullptr;       // the stream of the pending / next batch (one of the dictionary's shared streams unless the caller gave one)
@@ -222,7 +230,7 @@ struct kgpu_ctx {
     DevBuf lines_len;
     HostReport lines_report;
     PinBuf lines_text, lines_off, lines_status;
-    // a chunk of a kept-lattice call (kgpu_lattice_call.h; graphviz, N-best, marginals / samples, mode): the lattice descriptors (LAT_DESC_WORDS per sentence),
+    // a chunk of a kept-lattice call (kgpu_lattice_call.h; graphviz, N-best, marginals / samples, mode, user dictionary): the lattice descriptors (LAT_DESC_WORDS per sentence),
     // the 8-byte words of the call's per-chunk arrays (what its scans run over: LatticeOps::chunk_words), and the block its write launch fills
     DevBuf lat_desc, lat_words, lat_out;
     // read_line + trim_end on the device (kgpu_split.hip): the tile aggregates, what the carry kernel publishes ([0] lines, [1] packed bytes), and
@@ -316,7 +324,7 @@ WorkerPool &workers();
 // The hooks of the kept-lattice calls (kgpu_lattice_call.h), one slot per family: KGPU_HOST_<NAME>_CHUNK_SENTS, sentences per chunk (0: the default), and
 // KGPU_HOST_<NAME>_ARENA_INITIAL / _ARENA_MAX, the bytes of the scratch arena a chunk's kept lattices may use at first / at most (0: the whole arena /
 // ARENA_MAX): tests of the overflow protocol.  LATTICE_HOOK_NAMES (kgpu_dict.cpp) holds the <NAME>s in this order.
-enum LatticeHook : uint32_t { HOOK_GRAPHVIZ, HOOK_NBEST, HOOK_PROB, HOOK_MODE, LATTICE_HOOKS };
+enum LatticeHook : uint32_t { HOOK_GRAPHVIZ, HOOK_NBEST, HOOK_PROB, HOOK_MODE, HOOK_USER, LATTICE_HOOKS };
 struct LatticeHooks { uint64_t chunk_sents = 0, arena_initial = 0, arena_max = 0; };
 struct TestHooks { bool no_small_calls = false, plain_leaves = false, byte_trie = false; uint64_t chunk_bytes = 4ull << 20, chunk_sents = 16384, depth = 12, multi_chunk_sents = 0, arena_initial = 0; int aux_launch = -1; LatticeHooks lattice[LATTICE_HOOKS]; };
 TestHooks test_hooks();  // test-only environment hooks, read once per process (or per call under KGPU_TEST_HOOKS_REREAD)

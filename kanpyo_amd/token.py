@@ -11,6 +11,8 @@ class TokenClass(enum.IntEnum):
     Dummy = 0
     Known = 1
     Unknown = 2
+    User = 3   # a user dictionary's entry (include/kanpyo_gpu.h, "user dictionary"; not in the reference): Token.id is the entry's index + 1
+    USER = 3
 
 
 @dataclass(frozen=True)

@@ -345,6 +345,36 @@ class Tokenizer(Handle):
         tokens, toff, _, status = self.tokenize_mode_packed(utf8, offs, mode, penalties)
         return [[_token_of(raw, t) for t in tokens[int(toff[i]) : int(toff[i + 1])]] for i, raw in _sentences(utf8, offs, status, len(sentences))]
 
+    # ---- user dictionary (include/kanpyo_gpu.h, "user dictionary"; not an output of the reference: `mecab -u`, what Kuromoji and Kagome take beside the system dictionary) ------
+    def tokenize_user_packed(self, utf8: np.ndarray, offsets: np.ndarray, userdict, mode="normal", penalties=None, token_capacity: int | None = None):
+        """kgpu_tokenize_batch_user -> (tokens[TOKEN_DTYPE], tok_offsets[uint64 n+1], costs[int32 n], status[uint8 n]): tokenize_mode_packed's arrays over
+        the lattices widened by the matches of `userdict` (a userdict.UserDict made over this tokenizer).  A record of class 3 (TokenClass.User) has
+        id = the entry's index + 1.  A given capacity is never grown: KGPU_ERR_CAPACITY surfaces as KgpuError."""
+        from .mode import mode_opts
+
+        utf8, offsets, n, total = packed_input(utf8, offsets)
+        opts = mode if isinstance(mode, _lib.ModeOpts) else mode_opts(mode, penalties)
+        caps = (_token_room(total, n) if token_capacity is None else int(token_capacity),)
+        toff, costs, status = np.zeros(n + 1, dtype=np.uint64), np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.uint8)
+        T = C.c_uint64(0)
+        while caps is not None:
+            tokens = np.empty(max(caps[0], 1), dtype=TOKEN_DTYPE)
+            status[:] = 0
+            rc = _lib.lib().kgpu_tokenize_batch_user(self._h, userdict.handle, ptr(utf8), offsets.ctypes.data, n, C.byref(opts), tokens.ctypes.data, caps[0],
+                                                     toff.ctypes.data, costs.ctypes.data, status.ctypes.data, C.byref(T))
+            caps = _lib.check(rc) if token_capacity is not None else grown(rc, caps, (T.value,))
+        return tokens[: T.value], toff, costs[:n], status[:n]
+
+    def tokenize_user(self, sentences: Sequence[str], userdict, mode="normal", penalties=None, normalize=None) -> List[List[Token]]:
+        """Per sentence the Token objects of its best path over the dictionary's words and the user dictionary's, under the mode's penalised costs.  A
+        token of class TokenClass.User is an entry of `userdict`: userdict.features(token.id) are its features.  normalize: as in tokenize_nbest (make the
+        user dictionary with the same form: UserDict.from_csv(..., normalize=...))."""
+        utf8, offs = pack_sentences(sentences)
+        if normalize is not None:
+            utf8, offs, _ = self.normalize_packed(utf8, offs, normalize)
+        tokens, toff, _, status = self.tokenize_user_packed(utf8, offs, userdict, mode, penalties)
+        return [[_token_of(raw, t) for t in tokens[int(toff[i]) : int(toff[i + 1])]] for i, raw in _sentences(utf8, offs, status, len(sentences))]
+
     # ---- lattice probabilities (include/kanpyo_gpu.h, "lattice probabilities"; not an output of the reference: `mecab -m`, `mecab -l --theta`) ------
     def tokenize_marginals_packed(self, utf8: np.ndarray, offsets: np.ndarray, theta: float = _lib.KGPU_THETA_DEFAULT, all_nodes: bool = False, min_prob: float = 0.0,
                                   token_capacity: int | None = None):
