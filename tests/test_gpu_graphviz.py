@@ -1,7 +1,7 @@
 """`kanpyo graphviz` on the device (src/bin/kanpyo.rs:127-148 over src/graphviz.rs:30-163): kgpu_graphviz_batch, Tokenizer.graphviz*, the C
 consumer and `python -m kanpyo_amd graphviz`.  Every comparison is bytes against bytes.  The expected documents come from the Python
 statement of the renderer (kanpyo_amd/lattice.py::graphviz) -- over the naive restatement's lattice (oracle/pyref.py) on the fixture and the
-hand dictionaries, over kgpu_lattice_dump's (itself checked against pyref in tests/test_gpu_parity.py and test_gpu_matrix.py) on the
+hand dictionaries, over kgpu_lattice_dump's (itself checked against pyref in tests/test_gpu_parity.py and test_gpu_matrix.py, and swept against it in tests/test_gpu_lattice_sweep.py) on the
 synthetic dictionary -- with the feature names taken from MorphFeatureTable.features in Python and the connection costs from the
 dictionary's own blob: never from the library's label pool, its ranked matrix or its kernels."""
 import ctypes as C

@@ -1,6 +1,8 @@
 """Search and extended modes on the device (include/kanpyo_gpu.h, "search mode"): kgpu_tokenize_batch_mode, Tokenizer.tokenize_mode* and
 `python -m kanpyo_amd tokenize --mode`.  The device must equal kgpu_mode_host applied to kgpu_lattice_dump of the same sentence, byte for byte:
-records, tok_offsets, costs and status.  The host function itself is pinned to a plain restatement and to brute force in tests/test_mode_cpu.py."""
+records, tok_offsets, costs and status.  The host function itself is pinned to a plain restatement and to brute force in tests/test_mode_cpu.py; the dump is
+compared with the naive restatement's lattice node for node, and this call with the host rule over the restatement's lattices, in
+tests/test_gpu_lattice_sweep.py."""
 import ctypes as C
 import os
 import random

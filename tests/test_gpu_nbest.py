@@ -1,6 +1,8 @@
 """N-best paths on the device (include/kanpyo_gpu.h, "N-best paths"): kgpu_tokenize_batch_nbest, Tokenizer.tokenize_nbest* and
 `python -m kanpyo_amd tokenize --nbest`.  The device must equal kgpu_nbest_host applied to kgpu_lattice_dump of the same sentence, byte for byte:
-path_offsets, tok_offsets, costs, records and status.  The host function itself is pinned to a brute-force enumeration in tests/test_nbest_cpu.py."""
+path_offsets, tok_offsets, costs, records and status.  The host function itself is pinned to a brute-force enumeration in tests/test_nbest_cpu.py;
+the dump is compared with the naive restatement's lattice node for node, and this call with the host rule over the restatement's lattices, in
+tests/test_gpu_lattice_sweep.py."""
 import ctypes as C
 import os
 import random

@@ -1,7 +1,8 @@
 """Lattice probabilities on the device (include/kanpyo_gpu.h, "lattice probabilities"): kgpu_tokenize_batch_marginals, kgpu_tokenize_batch_samples,
 Tokenizer.tokenize_marginals* / tokenize_samples* and `python -m kanpyo_amd tokenize --marginal / --sample`.  The device must equal kgpu_marginals_host
 and kgpu_samples_host applied to kgpu_lattice_dump of the same sentence, byte for byte: records, probs, on_best, offsets, log_z, best_logprob, costs and
-status.  The host functions themselves are pinned to a brute-force enumeration in tests/test_prob_cpu.py.  test_the_two_functions_alone comes first:
+status.  The host functions themselves are pinned to a brute-force enumeration in tests/test_prob_cpu.py; the dump is compared with the naive restatement's
+lattice node for node, and these calls with the host rules over the restatement's lattices, in tests/test_gpu_lattice_sweep.py.  test_the_two_functions_alone comes first:
 everything else rests on the device rounding kexp and klog as the host does."""
 import ctypes as C
 import os

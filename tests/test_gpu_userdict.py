@@ -1,7 +1,9 @@
 """The user dictionary on the device (include/kanpyo_gpu.h, "user dictionary"): kgpu_userdict_create, kgpu_tokenize_batch_user,
 Tokenizer.tokenize_user* and `python -m kanpyo_amd tokenize --user-dict`.  The device must equal kgpu_userdict_host applied to kgpu_lattice_dump of the
 same sentence, byte for byte: records, tok_offsets, costs and status.  The host function itself is pinned to a plain restatement, to brute force and
-to a dictionary that holds the entries among its own words in tests/test_userdict_cpu.py."""
+to a dictionary that holds the entries among its own words in tests/test_userdict_cpu.py; the dump is compared with the naive restatement's lattice node
+for node, and this call with the host rule over the restatement's lattices (the withdrawal decisions where the invoke flag decides among them), in
+tests/test_gpu_lattice_sweep.py."""
 import ctypes as C
 import os
 import random
